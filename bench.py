@@ -26,6 +26,12 @@ Rank 0 prints ONE JSON line.  Extra objects:
   fp8_large     (N = 1, default workload) BASELINE.json configs[4] on one GPU: EcgVit-large / 501 tokens with fp8 Linear operands, and the
                 same step with bf16 operands back to back on the same device (value, ms_per_step, fp8_over_bf16, roofline vs 5 PFLOP/s).
   cpu_baseline  the CPU oracle's train step (torch eager f32, all host cores) on a bounded sample of the same workload.
+  dumped_outputs  (--dump-outputs DIR) the directory and the shape of every array written there.
+
+--dump-outputs DIR: after the timed steps of the headline run, rank 0 writes what its LAST timed step returned to the caller, float32,
+one DIR/<name>.npy each (at most 64 MB in all): loss, logits (pred for --objective masked), grad_norm (the pre-clip global norm) and params
+(the updated state_dict, concatenated in sorted key order, as a fixed seeded sample).  Weights, inputs and dropout seeds come from fixed
+seeds, so the same arguments give the same inputs on every run and two builds can be compared array for array.
 """
 import argparse
 import glob
@@ -181,6 +187,32 @@ def pmc_traffic(kernel_key, args):
     return None, stale or f'none: no counter profile of workload {key} under profiles/'
 
 
+DUMP_MAX_ELEMS = 4 << 20          # --dump-outputs: per array, 16 MB of float32; larger arrays are sampled down to this many elements
+DUMP_MAX_BYTES = 64 << 20         # --dump-outputs: all arrays together
+DUMP_SAMPLE_SEED = 77
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write each of `arrays` ({name: tensor}) as `<out_dir>/<name>.npy` in float32.  An array of more than DUMP_MAX_ELEMS
+    elements is replaced by a fixed sample of its flattened elements: the sorted distinct indices of DUMP_MAX_ELEMS draws of
+    numpy.random.default_rng(DUMP_SAMPLE_SEED), the same on every run.  Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    written, total = {}, 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.unique(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f'--dump-outputs: {total} bytes written by {name}.npy, more than {DUMP_MAX_BYTES}')
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def cpu_model_name():
     try:
         with open('/proc/cpuinfo') as f:
@@ -291,7 +323,14 @@ def parse_args(argv=None):
     ap.add_argument('--hip-lib', default=None, help='measurement only: load another build of the same C-ABI (A/B candidate, tools build)')
     ap.add_argument('--mask-on-device', action='store_true', help='measurement only (A/B): hand the masked step device-resident indices (validated with three blocking reads per step)')
     ap.add_argument('--bf16-aux', action='store_true', help='measurement only (A/B): the saved FFN tensor as bf16 (round 4) instead of e4m3 bytes')
-    return ap.parse_args(argv)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step of the headline run returned (rank 0) as DIR/<name>.npy, float32: '
+                         'loss, logits (supervised) or pred (masked), grad_norm (pre-clip), params (the updated state_dict, concatenated in key order; '
+                         f'arrays above {DUMP_MAX_ELEMS} elements as a fixed seeded sample)')
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def free_port():
@@ -393,8 +432,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed_run(objective, steps, warmup, conf=conf, batch=batch, dtype=dtype, fp8=fp8, saved_e4m3=None):
-        """W untimed + K timed steps of one objective; returns (seconds (max over ranks), final loss, probe result, ms per step of every rank)"""
+    def timed_run(objective, steps, warmup, conf=conf, batch=batch, dtype=dtype, fp8=fp8, saved_e4m3=None, dump=None):
+        """W untimed + K timed steps of one objective; returns (seconds (max over ranks), final loss, probe result, ms per step of every rank,
+        what `dump_outputs` wrote when `dump` names a directory -- rank 0 writes, after the timed region)"""
         torch.manual_seed(77)  # identical initial weights on every rank (HipTrainStep broadcasts rank 0's anyway)
         if args.bf16_aux:
             saved_e4m3 = False
@@ -424,7 +464,7 @@ def main():
         for i in range(steps):
             if probe:
                 probe.enabled = rank == 0 and i % 4 == 0   # HIP events around the dominant kernel's launches on every 4th timed step
-            loss, _ = run_step(x, y)                      # (192 event records per probed step cost ~0.7 % when taken on every step)
+            loss, step_out = run_step(x, y)               # (192 event records per probed step cost ~0.7 % when taken on every step)
         sync()
         dt = time.perf_counter() - t0
         if probe:
@@ -440,7 +480,14 @@ def main():
             dt = max(rank_dt)          # MAX over ranks
         final_loss = float(loss)
         step.finish()
-        return dt, final_loss, (probe.result() if probe else None), [1e3 * d / steps for d in rank_dt]
+        dumped = None
+        if dump and rank == 0:
+            params = model.state_dict()
+            dumped = dump_outputs(dump, {
+                'loss': loss, ('pred' if objective == 'masked' else 'logits'): step_out,
+                'grad_norm': torch.tensor([step.grad_norm()], dtype=torch.float32),
+                'params': torch.cat([params[k].reshape(-1).float() for k in sorted(params)])})
+        return dt, final_loss, (probe.result() if probe else None), [1e3 * d / steps for d in rank_dt], dumped
 
     def roofline_of(r, objective, **over):
         if not r:
@@ -457,12 +504,12 @@ def main():
             'alg_flops_per_launch': r['flops_per_launch'], 'alg_bytes_per_launch': r['alg_bytes_per_launch'], 'bytes_model': BYTES_MODEL,
         }
 
-    dt, final_loss, pres, rank_ms = timed_run(args.objective, args.steps, args.warmup)   # the headline run: its own per-rank times
+    dt, final_loss, pres, rank_ms, dumped = timed_run(args.objective, args.steps, args.warmup, dump=args.dump_outputs)   # the headline run: its own per-rank times
     masked_line = None
     if args.objective == 'supervised' and world == 1 and args.config == 'base' and not args.no_masked:
         # the build's own masked pre-train objective (absent from the reference: SURVEY 0), driver-timed next to the headline step
         msteps = min(args.steps, 20)
-        mdt, mloss, mres, _ = timed_run('masked', msteps, min(args.warmup, 3))
+        mdt, mloss, mres, _, _ = timed_run('masked', msteps, min(args.warmup, 3))
         n_patch = conf.max_signal_length // conf.patch_size
         masked_line = {
             'workload': f'EcgVit-{args.config} masked-patch pre-train step (SimMIM-style: 50 % of the {n_patch} patches replaced by a mask token, no CLS, '
@@ -477,7 +524,7 @@ def main():
     if args.objective == 'supervised' and world == 1 and args.config == 'base' and args.dtype == 'bf16' and not args.no_bf16_saved and not args.bf16_aux:
         # the headline step keeps ONE backward-only tensor per layer (gelu'(pre) x dropout multiplier, [tokens, 3072]) as e4m3 bytes; this is the same
         # step with that tensor in bf16 -- every stored tensor then has the metric's dtype -- timed by the same caller, same steps
-        bdt, bloss, _, _ = timed_run('supervised', args.steps, args.warmup, saved_e4m3=False)
+        bdt, bloss, _, _, _ = timed_run('supervised', args.steps, args.warmup, saved_e4m3=False)
         bf16_saved_line = {
             'workload': 'the headline step with saved_ffn_e4m3=False: the FFN backward tensor gelu\'(pre) x dropout multiplier stored as bf16 (2 bytes) instead of e4m3 (1 byte)',
             'value': batch * args.steps / bdt, 'unit': 'records/s', 'steps': args.steps, 'ms_per_step': 1e3 * bdt / args.steps, 'final_loss': bloss,
@@ -490,7 +537,7 @@ def main():
         # BASELINE.json configs[1]: EcgVit-small, 250 patches (251 tokens), 256 records, driver-timed next to the headline step
         sconf, sbatch = make_config(E, 'small', args.patch, args.length, args.dropout)
         ssteps = min(args.steps, 20)
-        sdt, sloss, sres, _ = timed_run('supervised', ssteps, min(args.warmup, 5), conf=sconf, batch=sbatch, dtype=torch.bfloat16, fp8=False)
+        sdt, sloss, sres, _, _ = timed_run('supervised', ssteps, min(args.warmup, 5), conf=sconf, batch=sbatch, dtype=torch.bfloat16, fp8=False)
         sflops = E.workload.train_flops_per_record(sconf)
         sv = sbatch * ssteps / sdt
         small_line = {
@@ -512,7 +559,7 @@ def main():
         for tag, f8 in (('bf16', False), ('fp8', True)):
             gc.collect()
             torch.cuda.empty_cache()
-            ldt, lloss, lres, _ = timed_run('supervised', lsteps, lwarm, conf=lconf, batch=lbatch, dtype=torch.bfloat16, fp8=f8)
+            ldt, lloss, lres, _, _ = timed_run('supervised', lsteps, lwarm, conf=lconf, batch=lbatch, dtype=torch.bfloat16, fp8=f8)
             res[tag] = (ldt, lloss, lres)
         gc.collect()
         torch.cuda.empty_cache()
@@ -577,6 +624,8 @@ def main():
             out['small'] = small_line
         if fp8_line:
             out['fp8_large'] = fp8_line
+        if dumped:
+            out['dumped_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
         if not args.no_cpu_baseline and world == 1:
             out['cpu_baseline'] = cpu_baseline(conf, masked=args.objective == 'masked')
         print(json.dumps(out), flush=True)

@@ -1,7 +1,9 @@
 """CPU, world_size 2 / 4 / 8, gloo: the N > 1 path's logic -- contiguous equal shards, one SUM all-reduce over the flat gradient
 buffer, 1/world folded into the update, clip on the REDUCED gradient -- reproduces the single-process full-batch step.
 The per-rank compute here is the CPU oracle (the HIP kernels need a GPU); what is under test is ecg_..._amd.ddp + the
-flat layout, which are device-agnostic and are exactly what HipTrainStep calls on the GPU."""
+flat layout, which are device-agnostic and are exactly what HipTrainStep calls on the GPU.
+The world-2/4/8 test takes each shard's oracle backward in the test process and hands it to its rank: torch's autograd engine
+initialises every device runtime on its first backward, so eight ranks each running one would each open the GPU of a GPU machine."""
 import os
 import socket
 
@@ -22,6 +24,34 @@ def _free_port():
     return p
 
 
+CFG = dict(max_signal_length=400, patch_size=20, hidden_size=32, num_hidden_layers=2, num_attention_heads=2, intermediate_size=64)
+
+
+def _global_batch(world):
+    return 8 if world <= 4 else 16                      # global batch: 4 / 2 / 2 records per rank
+
+
+def _shard_backward(world, out_dir):
+    """each rank's forward + backward on ITS shard of the global batch, from rank 0's initial weights (seed 1234: what the broadcast hands
+    every rank), taken here in the test process -> <out_dir>/shard<rank>.pt (loss, flat gradient)"""
+    import ecg_representation_learning_amd as E
+    from ecg_representation_learning_amd.engine import ParamLayout
+    from oracle import vit_oracle as O
+    G = _global_batch(world)
+    x, y = O.synthetic_batch(G, length=400, seed=77)    # the GLOBAL batch
+    for rank in range(world):
+        torch.manual_seed(1234)
+        model = O.OracleEcgVit(config=Cfg(**CFG)).train()
+        layout = ParamLayout([(n, tuple(p.shape)) for n, p in model.named_parameters()])
+        lo, hi = E.ddp.shard_range(G, rank, world)
+        out = model(sample_values=x[lo:hi], labels=y[lo:hi])
+        out.loss.backward()
+        gflat = torch.zeros(layout.total)
+        for n, p in model.named_parameters():
+            layout.view(gflat, n).copy_(p.grad)
+        torch.save(dict(loss=out.loss.detach(), g=gflat, lo=lo, hi=hi), os.path.join(out_dir, f'shard{rank}.pt'))
+
+
 def _worker(rank, world, port, out_dir):
     import sys
     sys.path.insert(0, ROOT)
@@ -31,23 +61,18 @@ def _worker(rank, world, port, out_dir):
     from ecg_representation_learning_amd.engine import ParamLayout
     from oracle import vit_oracle as O
     torch.set_num_threads(2 if world <= 2 else 1)
-    cfg = Cfg(max_signal_length=400, patch_size=20, hidden_size=32, num_hidden_layers=2, num_attention_heads=2, intermediate_size=64)
     torch.manual_seed(1234 + rank)                      # deliberately different init per rank ...
-    model = O.OracleEcgVit(config=cfg).train()
+    model = O.OracleEcgVit(config=Cfg(**CFG)).train()
     layout = ParamLayout([(n, tuple(p.shape)) for n, p in model.named_parameters()])
     pflat = torch.zeros(layout.total)
     for n, p in model.named_parameters():
         layout.view(pflat, n).copy_(p.data)
         p.data = layout.view(pflat, n)
     E.ddp.broadcast_flat_(pflat, src=0)                 # ... made identical by one broadcast of the flat buffer
-    G = 8 if world <= 4 else 16                        # global batch: 4 / 2 / 2 records per rank
-    x, y = O.synthetic_batch(G, length=400, seed=77)    # the GLOBAL batch, identical on every rank
-    lo, hi = E.ddp.shard_range(G, rank, world)
-    out = model(sample_values=x[lo:hi], labels=y[lo:hi])
-    out.loss.backward()
-    gflat = torch.zeros(layout.total)
-    for n, p in model.named_parameters():
-        layout.view(gflat, n).copy_(p.grad)
+    shard = torch.load(os.path.join(out_dir, f'shard{rank}.pt'))   # this rank's shard backward, on rank 0's weights (_shard_backward)
+    assert (shard['lo'], shard['hi']) == E.ddp.shard_range(_global_batch(world), rank, world)
+    out_loss, gflat = shard['loss'], shard['g']
+    cfg = Cfg(**CFG)
     # the train step's exchange object: per-layer buckets launched in backward order (overlap), f32 and bf16 on the wire
     local = gflat.clone()
     xout = {}
@@ -65,9 +90,9 @@ def _worker(rank, world, port, out_dir):
     gflat /= w
     norm = gflat.norm()
     coef = torch.clamp(1.0 / (norm + 1e-6), max=1.0)
-    torch.save(dict(g=gflat * coef, norm=norm, loss=out.loss.detach(), p=pflat.clone(), seed=E.ddp.rank_seed(77, rank), xchg=xout, gavg=gflat.clone()),
+    torch.save(dict(g=gflat * coef, norm=norm, loss=out_loss, p=pflat.clone(), seed=E.ddp.rank_seed(77, rank), xchg=xout, gavg=gflat.clone()),
                os.path.join(out_dir, f'rank{rank}.pt'))
-    dist.barrier()
+    dist.all_reduce(torch.zeros(1))                     # every rank done before teardown (dist.barrier() would probe for, and open, a GPU)
     dist.destroy_process_group()
 
 
@@ -80,21 +105,25 @@ BF16_WIRE_REL = {2: 8e-3, 4: 1.0e-2, 8: 1.4e-2}
 
 @pytest.mark.parametrize('world', [2, 4, 8])
 def test_gradient_allreduce_equals_full_batch(tmp_path, world):
+    _shard_backward(world, str(tmp_path))
     port = _free_port()
     mp.spawn(_worker, args=(world, port, str(tmp_path)), nprocs=world, join=True)
     rs = [torch.load(os.path.join(tmp_path, f'rank{r}.pt')) for r in range(world)]
     r0, r1 = rs[0], rs[1]
-    G = 8 if world <= 4 else 16
+    G = _global_batch(world)
     for r in rs[1:]:
         assert torch.equal(r0['p'], r['p'])                       # broadcast made the replicas identical
         assert torch.equal(r0['g'], r['g'])                       # every rank holds the same reduced, clipped gradient
     assert [r['seed'] for r in rs] == [77 + i for i in range(world)]
     from ecg_representation_learning_amd.engine import ParamLayout
     from oracle import vit_oracle as O
-    cfg = Cfg(max_signal_length=400, patch_size=20, hidden_size=32, num_hidden_layers=2, num_attention_heads=2, intermediate_size=64)
     torch.manual_seed(1234)
-    model = O.OracleEcgVit(config=cfg).train()
+    model = O.OracleEcgVit(config=Cfg(**CFG)).train()
     layout = ParamLayout([(n, tuple(p.shape)) for n, p in model.named_parameters()])
+    p0 = torch.zeros(layout.total)
+    for n, p in model.named_parameters():
+        layout.view(p0, n).copy_(p.data)
+    assert torch.equal(r0['p'], p0)                               # ... to rank 0's weights: those the shard gradients were taken on
     # GradExchange: the f32 forms equal the plain all-reduce bit for bit; bf16 on the wire stays within bf16 rounding of it
     # (world 2: a + b has one order; beyond that a ring's sum order depends on how the buffer is cut into buckets -> f32 rounding)
     for tag in ('f32_overlap', 'f32_single'):
