@@ -329,6 +329,9 @@ template <typename TO> __device__ __forceinline__ float epilogue_value(float acc
     return v;
 }
 
+// mask row pitch of the launch in flight (ecgvit_gemm_rowpitch): output row m draws the dropout bits of row m * pitch, so a product over a
+// compact subset of rows (one per record) applies exactly the mask a full launch applies to those rows.  1 everywhere else
+inline thread_local int g_mask_row_pitch = 1;
 static inline EpiParams make_epi(const ecgvit_gemm_desc *d) {
     EpiParams e;
     e.flags = d->epilogue;
@@ -343,7 +346,7 @@ static inline EpiParams make_epi(const ecgvit_gemm_desc *d) {
     const bool q8 = d->out_dtype == ECGVIT_BF16;
     e.drop_thresh = q8 ? dropout_threshold8(d->dropout_p) : dropout_threshold(d->dropout_p);
     e.inv_keep = d->dropout_p > 0.f ? (q8 ? dropout_inv_keep8(d->dropout_p) : 1.0f / (1.0f - d->dropout_p)) : 1.0f;
-    e.N = d->N;
+    e.N = d->N * g_mask_row_pitch;   // m * (N * pitch) + n == (m * pitch) * N + n
     return e;
 }
 

@@ -432,6 +432,14 @@ static int gemm_dispatch(const ecgvit_gemm_desc *d, void *stream, int *route) {
 
 extern "C" int ecgvit_gemm(const ecgvit_gemm_desc *d, void *stream) { return gemm_dispatch(d, stream, nullptr); }
 
+extern "C" int ecgvit_gemm_rowpitch(const ecgvit_gemm_desc *d, int mask_row_pitch, void *stream) {
+    if (!d || mask_row_pitch < 1 || (int64_t)d->N * mask_row_pitch >= (1ll << 31)) return ECGVIT_EINVAL;
+    g_mask_row_pitch = mask_row_pitch;
+    const int rc = gemm_dispatch(d, stream, nullptr);
+    g_mask_row_pitch = 1;
+    return rc;
+}
+
 extern "C" int ecgvit_gemm_kernel(const ecgvit_gemm_desc *d) {
     int route = ECGVIT_KERNEL_NONE;
     return gemm_dispatch(d, nullptr, &route) == ECGVIT_OK ? route : ECGVIT_KERNEL_NONE;

@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T *__restrict_
                                                             const float *__restrict__ gamma, const float *__restrict__ mean,
                                                             const float *__restrict__ rstd, const T *__restrict__ dres,
                                                             T *__restrict__ dx, float *__restrict__ partial, int64_t rows, int d,
-                                                            T *__restrict__ dxm, uint64_t seed, uint32_t thresh, float inv_keep) {
+                                                            T *__restrict__ dxm, uint64_t seed, uint32_t thresh, float inv_keep, uint32_t mrp) {
     constexpr int VN = Vec16<T>::N;
     constexpr int NP = EXTRA ? 3 : 2;
     extern __shared__ __attribute__((aligned(16))) float red[];  // [4][NP][d]
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T *__restrict_
                     if (thresh) {
                         Vec16<T> om;
                         float mk[VN];
-                        dropout_maskN<VN, sizeof(T) == 2>(seed, (uint32_t)r * (uint32_t)d + (uint32_t)c, thresh, inv_keep, mk);
+                        dropout_maskN<VN, sizeof(T) == 2>(seed, (uint32_t)r * mrp * (uint32_t)d + (uint32_t)c, thresh, inv_keep, mk);
 #pragma unroll
                         for (int k = 0; k < VN; ++k) om.set(k, o.get(k) * mk[k]);
                         st16(dxm + r * d + c, om);
@@ -421,7 +421,7 @@ __global__ __launch_bounds__(256, E <= 12 ? 4 : 2) void layernorm_bwd_fit_kernel
                                                                 bf16_t *__restrict__ dx, float *__restrict__ partial, int64_t rows,
                                                                 bf16_t *__restrict__ dxm, uint64_t seed, uint32_t thresh, float inv_keep,
                                                                 uint8_t *__restrict__ g8 = nullptr, const float *__restrict__ q8_scale = nullptr,
-                                                                float *__restrict__ q8_amax = nullptr) {
+                                                                float *__restrict__ q8_amax = nullptr, uint32_t mrp = 1) {
     using L = LaneRow<E>;
     [[maybe_unused]] float q8_inv = 0.f, qmax = 0.f;
     if constexpr (Q8) { const float sc = *q8_scale; q8_inv = sc > 0.f ? 1.0f / sc : 0.f; }
@@ -463,16 +463,17 @@ __global__ __launch_bounds__(256, E <= 12 ? 4 : 2) void layernorm_bwd_fit_kernel
         L::store(dx + ro, lane, o);
         if (EXTRA) {
             if (thresh) {
+                const uint32_t mo = ro * mrp;   // mask counter of row r * mrp (ecgvit_layernorm_bwd_fused_rowpitch)
 #pragma unroll
                 for (int i = 0; i < L::N16; ++i) {
                     float mk[8];
-                    dropout_maskN<8, true>(seed, ro + (uint32_t)((i * 64 + lane) * 8), thresh, inv_keep, mk);
+                    dropout_maskN<8, true>(seed, mo + (uint32_t)((i * 64 + lane) * 8), thresh, inv_keep, mk);
 #pragma unroll
                     for (int k = 0; k < 8; ++k) o[8 * i + k] = (float)(bf16_t)(o[8 * i + k] * mk[k]);
                 }
                 if constexpr (L::N8 == 1) {
                     float mk[4];
-                    dropout_maskN<4, true>(seed, ro + (uint32_t)(512 * L::N16 + 4 * lane), thresh, inv_keep, mk);
+                    dropout_maskN<4, true>(seed, mo + (uint32_t)(512 * L::N16 + 4 * lane), thresh, inv_keep, mk);
 #pragma unroll
                     for (int k = 0; k < 4; ++k) o[8 * L::N16 + k] = (float)(bf16_t)(o[8 * L::N16 + k] * mk[k]);
                 }
@@ -624,13 +625,15 @@ __global__ __launch_bounds__(256) void softmax_bwd_rows_kernel(const float *__re
 
 template <typename T>
 __global__ __launch_bounds__(256) void dropout_apply_kernel(const T *__restrict__ in, T *__restrict__ out, int64_t count,
-                                                            uint64_t seed, uint32_t thresh, float inv_keep) {
+                                                            uint64_t seed, uint32_t thresh, float inv_keep, uint32_t cols, uint32_t mrp) {
     constexpr int VN = Vec16<T>::N;
     const int64_t nv = count / VN;
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < nv; i += (int64_t)gridDim.x * 256) {
         Vec16<T> v = ld16(in + i * VN);
         float mk[VN];
-        dropout_maskN<VN, sizeof(T) == 2>(seed, (uint32_t)i * (uint32_t)VN, thresh, inv_keep, mk);
+        uint32_t idx = (uint32_t)i * (uint32_t)VN;
+        if (mrp != 1) idx += idx / cols * (mrp - 1) * cols;   // compact row r draws the mask of row r * mrp (cols % VN == 0)
+        dropout_maskN<VN, sizeof(T) == 2>(seed, idx, thresh, inv_keep, mk);
 #pragma unroll
         for (int k = 0; k < VN; ++k) v.set(k, v.get(k) * mk[k]);
         st16(out + i * VN, v);
@@ -748,7 +751,9 @@ int64_t ecgvit_layernorm_bwd_workspace(int64_t rows, int d) { return (int64_t)ln
 static int ln_bwd_launch(const void *dy, const void *x, const float *gamma, const float *mean, const float *rstd, const void *dres,
                          void *dx, float *dgamma, float *dbeta, void *partial, int64_t rows, int d, int dtype, void *stream,
                          bool extra, void *dxm, float *dcolsum, float dropout_p, uint64_t seed,
-                         void *g8 = nullptr, const float *q8_scale = nullptr, float *q8_amax = nullptr) {
+                         void *g8 = nullptr, const float *q8_scale = nullptr, float *q8_amax = nullptr, int mask_row_pitch = 1) {
+    if (mask_row_pitch < 1 || (mask_row_pitch > 1 && (g8 || rows * mask_row_pitch * d >= (1ll << 32)))) return ECGVIT_EINVAL;
+    const uint32_t mrp = (uint32_t)mask_row_pitch;
     if (g8 && (!extra || !q8_scale || !q8_amax || dtype != ECGVIT_BF16 || !ln_fit(d) || (int64_t)rows * d >= (1ll << 31))) return ECGVIT_EINVAL;
     if (rows <= 0 || d <= 0 || d % 8 != 0 || d > 2048 || !partial) return ECGVIT_EINVAL;
     if (extra && (!dcolsum || (dropout_p > 0.f && !dxm && !g8) || ((int64_t)rows * d) % 2)) return ECGVIT_EINVAL;
@@ -764,7 +769,7 @@ static int ln_bwd_launch(const void *dy, const void *x, const float *gamma, cons
 #define LN_FIT(EE)                                                                                                                \
     case EE:                                                                                                                      \
         if (g8) hipLaunchKernelGGL((layernorm_bwd_fit_kernel<EE, true, true>), dim3(grid), dim3(256), ldsf, as_stream(stream), (const bf16_t *)dy, (const bf16_t *)x, gamma, mean, rstd, (const bf16_t *)dres, (bf16_t *)dx, (float *)partial, rows, (bf16_t *)dxm, seed, th, ik, (uint8_t *)g8, q8_scale, q8_amax); \
-        else if (extra) hipLaunchKernelGGL((layernorm_bwd_fit_kernel<EE, true>), dim3(grid), dim3(256), ldsf, as_stream(stream), (const bf16_t *)dy, (const bf16_t *)x, gamma, mean, rstd, (const bf16_t *)dres, (bf16_t *)dx, (float *)partial, rows, (bf16_t *)dxm, seed, th, ik); \
+        else if (extra) hipLaunchKernelGGL((layernorm_bwd_fit_kernel<EE, true>), dim3(grid), dim3(256), ldsf, as_stream(stream), (const bf16_t *)dy, (const bf16_t *)x, gamma, mean, rstd, (const bf16_t *)dres, (bf16_t *)dx, (float *)partial, rows, (bf16_t *)dxm, seed, th, ik, nullptr, nullptr, nullptr, mrp); \
         else hipLaunchKernelGGL((layernorm_bwd_fit_kernel<EE, false>), dim3(grid), dim3(256), ldsf, as_stream(stream), (const bf16_t *)dy, (const bf16_t *)x, gamma, mean, rstd, (const bf16_t *)dres, (bf16_t *)dx, (float *)partial, rows, (bf16_t *)nullptr, seed, 0u, 1.f); \
         break;
         switch (d / 64) { LN_FIT(4) LN_FIT(8) LN_FIT(12) LN_FIT(16) LN_FIT(24) LN_FIT(32) default: return ECGVIT_EINVAL; }
@@ -777,8 +782,8 @@ static int ln_bwd_launch(const void *dy, const void *x, const float *gamma, cons
     const int nv = (d + (dtype == ECGVIT_F32 ? 256 : 512) - 1) / (dtype == ECGVIT_F32 ? 256 : 512);
 #define LN_BWD(T, MV)                                                                                                             \
     do {                                                                                                                          \
-        if (extra) hipLaunchKernelGGL((layernorm_bwd_kernel<T, MV, true>), dim3(grid), dim3(256), lds, as_stream(stream), (const T *)dy, (const T *)x, gamma, mean, rstd, (const T *)dres, (T *)dx, (float *)partial, rows, d, (T *)dxm, seed, th, ik); \
-        else hipLaunchKernelGGL((layernorm_bwd_kernel<T, MV, false>), dim3(grid), dim3(256), lds, as_stream(stream), (const T *)dy, (const T *)x, gamma, mean, rstd, (const T *)dres, (T *)dx, (float *)partial, rows, d, (T *)nullptr, seed, 0u, 1.f); \
+        if (extra) hipLaunchKernelGGL((layernorm_bwd_kernel<T, MV, true>), dim3(grid), dim3(256), lds, as_stream(stream), (const T *)dy, (const T *)x, gamma, mean, rstd, (const T *)dres, (T *)dx, (float *)partial, rows, d, (T *)dxm, seed, th, ik, mrp); \
+        else hipLaunchKernelGGL((layernorm_bwd_kernel<T, MV, false>), dim3(grid), dim3(256), lds, as_stream(stream), (const T *)dy, (const T *)x, gamma, mean, rstd, (const T *)dres, (T *)dx, (float *)partial, rows, d, (T *)nullptr, seed, 0u, 1.f, 1u); \
     } while (0)
     if (dtype == ECGVIT_F32) { if (nv <= 1) LN_BWD(float, 1); else if (nv <= 2) LN_BWD(float, 2); else if (nv <= 4) LN_BWD(float, 4); else LN_BWD(float, 8); }
     else { if (nv <= 1) LN_BWD(bf16_t, 1); else if (nv <= 2) LN_BWD(bf16_t, 2); else LN_BWD(bf16_t, 4); }
@@ -798,6 +803,13 @@ int ecgvit_layernorm_bwd_fused(const void *dy, const void *x, const float *gamma
                                void *dx, float *dgamma, float *dbeta, void *partial, int64_t rows, int d, void *dxm, float *dcolsum,
                                float dropout_p, uint64_t seed, int dtype, void *stream) {
     return ln_bwd_launch(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, partial, rows, d, dtype, stream, true, dxm, dcolsum, dropout_p, seed);
+}
+
+int ecgvit_layernorm_bwd_fused_rowpitch(const void *dy, const void *x, const float *gamma, const float *mean, const float *rstd, const void *dres,
+                                        void *dx, float *dgamma, float *dbeta, void *partial, int64_t rows, int d, void *dxm, float *dcolsum,
+                                        float dropout_p, uint64_t seed, int mask_row_pitch, int dtype, void *stream) {
+    return ln_bwd_launch(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, partial, rows, d, dtype, stream, true, dxm, dcolsum, dropout_p, seed,
+                         nullptr, nullptr, nullptr, mask_row_pitch);
 }
 
 int ecgvit_layernorm_bwd_fused_q8(const void *dy, const void *x, const float *gamma, const float *mean, const float *rstd, const void *dres,
@@ -829,19 +841,31 @@ int ecgvit_colsum(const void *in, int64_t ld, float *out, void *partial, int64_t
     return ECGVIT_OK;
 }
 
-int ecgvit_dropout_apply(const void *in, void *out, int64_t count, float dropout_p, uint64_t seed, int dtype, void *stream) {
-    if (count <= 0 || count % 8 != 0) return ECGVIT_EINVAL;
+static int dropout_apply_launch(const void *in, void *out, int64_t count, float dropout_p, uint64_t seed, int dtype, void *stream, int64_t cols,
+                                int64_t mrp) {
+    if (count <= 0 || count % 8 != 0 || cols < 8 || cols % 8 != 0 || count % cols != 0 || mrp < 1 || (mrp > 1 && count * mrp >= (1ll << 32)))
+        return ECGVIT_EINVAL;
     uint32_t th;
     float ik;
     if (!dropout_site_params(dropout_p, dtype == ECGVIT_BF16, th, ik)) return ECGVIT_EINVAL;   // (bf16: p applied as round(256 p) / 256; below 1/512: rejected)
     const int grid = (int)std::min<int64_t>((count / 4 + 255) / 256, 4096);
     if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(dropout_apply_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), (const float *)in, (float *)out, count, seed, th, ik);
+        hipLaunchKernelGGL(dropout_apply_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), (const float *)in, (float *)out, count, seed, th, ik, (uint32_t)cols, (uint32_t)mrp);
     else if (dtype == ECGVIT_BF16)
-        hipLaunchKernelGGL(dropout_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), (const bf16_t *)in, (bf16_t *)out, count, seed, th, ik);
+        hipLaunchKernelGGL(dropout_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), (const bf16_t *)in, (bf16_t *)out, count, seed, th, ik, (uint32_t)cols, (uint32_t)mrp);
     else return ECGVIT_EINVAL;
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
+}
+
+int ecgvit_dropout_apply(const void *in, void *out, int64_t count, float dropout_p, uint64_t seed, int dtype, void *stream) {
+    return dropout_apply_launch(in, out, count, dropout_p, seed, dtype, stream, 8, 1);
+}
+
+int ecgvit_dropout_apply_rows(const void *in, void *out, int64_t rows, int cols, int mask_row_pitch, float dropout_p, uint64_t seed, int dtype,
+                              void *stream) {
+    if (rows <= 0) return ECGVIT_EINVAL;
+    return dropout_apply_launch(in, out, rows * cols, dropout_p, seed, dtype, stream, cols, mask_row_pitch);
 }
 
 int ecgvit_softmax_rows(float *S, int64_t rows, int N, int64_t ld, void *stream) {

@@ -405,6 +405,11 @@ class VitEngine:
                   dtok=((Mp, d), T), dxm=((M, d), T))
         if T == torch.float32:
             sp.update(pd=((B * h * N * N,), T), dp=((B * h * N * N,), T))
+        if T == torch.bfloat16 and not masked:
+            # the pruned last block (forward(..., cls_only_last=True)): its activations and gradients past K / V, one row per record
+            sp.update({f'cls_{k}': ((B, d), T) for k in ('attn', 'x1', 'xn2', 'x2', 'dx', 'dy', 'dxn', 'dx1', 'dxm', 'dattn', 'dq')})
+            sp.update(cls_hpre=((B, f), T), cls_hact=((B, f), T), cls_dh=((B, f), T), cls_lse=((B * h,), f32), cls_mean2=((B,), f32),
+                      cls_rstd2=((B,), f32))
         l = lib()
         ws = max(l.ecgvit_layernorm_bwd_workspace(M, d), l.ecgvit_colsum_workspace(M, max(f, 3 * d)), 8 * ((M + 255) // 256) * f, 4096)
         if T == torch.bfloat16:
@@ -495,8 +500,9 @@ class VitEngine:
         self._gemm(GEMM_NT, a['patches'], W[pre + 'to_patch_embedding.1.weight'], a['tok'], B * self.n, self.d, self.CP, self.CP,
                  self.CP, self.d, epilogue=EPI_BIAS, bias=self.P32[pre + 'to_patch_embedding.1.bias'])
 
-    def _trunk_fwd(self, B, ph, seed):
-        """L x { x = Attn(LN(x)) + x ; x = FF(LN(x)) + x } on act['x0'] ([B*T, d]); returns the output slab"""
+    def _trunk_fwd(self, B, ph, seed, cls_only_last=False):
+        """L x { x = Attn(LN(x)) + x ; x = FF(LN(x)) + x } on act['x0'] ([B*T, d]); returns the output slab (cls_only_last: the last
+        block's CLS rows only, compact [B, d] -- see `_cls_block_fwd`)"""
         a, W, T = self.act, self.W, hip.code(self.dtype)
         l, st = lib(), stream()
         d, f, h, dh, N = self.d, self.f, self.h, self.dh, self.T
@@ -506,6 +512,8 @@ class VitEngine:
         for i, L in enumerate(a['layers']):
             lp = f'{pre}transformer.layers.{i}.'
             s0 = seed + 100 * (i + 1)
+            if cls_only_last and i == self.Ly - 1:
+                return self._cls_block_fwd(L, X, B, ph, s0, lp)
             # a6/a7: PreNorm(Attention)
             f8 = self.fp8 and M >= 2048
             q1 = self._ln_fwd(X, self.P32[lp + '0.norm.weight'], self.P32[lp + '0.norm.bias'], L['xn1'], L['mean1'], L['rstd1'], M, q8_site=8 * i,
@@ -542,21 +550,52 @@ class VitEngine:
             X = L['x2']
         return X
 
-    def forward(self, x, labels=None, weight=None, training=True, seed=0, want_mean=True):
-        """x: (B, C, L) f32 contiguous device tensor. Returns (logits (B,K) f32, loss_elem (B,K) f32 | None, loss_mean (1,) | None)."""
+    def _cls_block_fwd(self, L, X, B, ph, s0, lp):
+        """the last block when only its CLS rows are consumed (the classifier reads x[:, 0]): LayerNorm 1 and the K / V columns of to_qkv
+        over every row (the CLS query attends to all keys), everything after them over one row per record.  The compact launches draw the
+        dropout bits of the rows they stand for (mask row pitch T), so the result is the full block's row 0.  Returns x2 of the CLS rows [B, d]"""
+        a, W, P = self.act, self.W, self.P32
+        l, st = lib(), stream()
+        d, f, h, dh, N = self.d, self.f, self.h, self.dh, self.T
+        M, T = B * N, hip.code(self.dtype)
+        self._ln_fwd(X, P[lp + '0.norm.weight'], P[lp + '0.norm.bias'], L['xn1'], L['mean1'], L['rstd1'], M)
+        wqkv = W[lp + '0.fn.to_qkv.weight']   # [3d, d]: rows [q | k | v]
+        self._gemm(GEMM_NT, L['xn1'], wqkv, L['qkv'], M, 2 * d, d, d, d, 3 * d, b_off=d * d, c_off=d)   # K, V of every row
+        self._gemm(GEMM_NT, L['xn1'], wqkv, L['qkv'], B, d, d, N * d, d, N * 3 * d)                       # Q of the CLS rows, in place
+        check(l.ecgvit_attention_cls_fwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_lse']), B, N, h, dh, self.scale, ph, s0 + 1, T, st),
+              'attention_cls_fwd')
+        drop = EPI_DROPOUT if ph > 0 else 0
+        self._gemm(GEMM_NT, a['cls_attn'], W[lp + '0.fn.to_out.0.weight'], a['cls_x1'], B, d, d, d, d, d, epilogue=EPI_BIAS | EPI_RESIDUAL | drop,
+                   bias=P[lp + '0.fn.to_out.0.bias'], residual=X, ldr=N * d, dropout_p=ph, seed=s0 + 2, mask_row_pitch=N)
+        self._ln_fwd(a['cls_x1'], P[lp + '1.norm.weight'], P[lp + '1.norm.bias'], a['cls_xn2'], a['cls_mean2'], a['cls_rstd2'], B)
+        self._gemm(GEMM_NT, a['cls_xn2'], W[lp + '1.fn.net.0.weight'], a['cls_hact'], B, f, d, d, d, f,
+                   epilogue=EPI_BIAS | EPI_GELU | EPI_GELU_GRAD_AUX | drop, bias=P[lp + '1.fn.net.0.bias'], aux=a['cls_hpre'], ldaux=f,
+                   dropout_p=ph, seed=s0 + 3, mask_row_pitch=N)
+        self._gemm(GEMM_NT, a['cls_hact'], W[lp + '1.fn.net.3.weight'], a['cls_x2'], B, d, f, f, f, d, epilogue=EPI_BIAS | EPI_RESIDUAL | drop,
+                   bias=P[lp + '1.fn.net.3.bias'], residual=a['cls_x1'], ldr=d, dropout_p=ph, seed=s0 + 4, mask_row_pitch=N)
+        return a['cls_x2']
+
+    def forward(self, x, labels=None, weight=None, training=True, seed=0, want_mean=True, cls_only_last=False):
+        """x: (B, C, L) f32 contiguous device tensor. Returns (logits (B,K) f32, loss_elem (B,K) f32 | None, loss_mean (1,) | None).
+        cls_only_last: compute the last block for the CLS rows only (past its K / V), the rows the classifier reads -- same loss, logits and
+        gradients, 1/12 of the base trunk less work.  bf16 engine without fp8_linear; the last block's other rows are then not computed
+        (attention_probs of that layer is unavailable until the next full forward)."""
         B = x.shape[0]
         assert x.shape[1] == self.C and x.dtype == torch.float32 and x.is_contiguous()
         if self.input_transform is None:
             assert x.shape[2] == self.L
         else:
             assert self.input_transform.padded_length(x.shape[2]) == self.L, 'config.max_signal_length must be the padded length'
+        cls_only_last = bool(cls_only_last)
+        if cls_only_last and (self.dtype != torch.bfloat16 or self.fp8):
+            raise ValueError('cls_only_last needs the bf16 engine without fp8_linear')
         self._alloc(B)
         a, T = self.act, hip.code(self.dtype)
         l, st = lib(), stream()
         d, N, n = self.d, self.N, self.n
         ph = self.p_hidden if training else 0.0
         pe = self.p_emb if training else 0.0
-        self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, labels=labels, weight=weight, masked=False, training=training)
+        self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, labels=labels, weight=weight, masked=False, training=training, cls_only_last=cls_only_last)
         if self.fp8:
             # EVERY forward, eval included, starts from the scales of the pass before it (delayed scaling with a history of one pass): an
             # inference-only model otherwise keeps its first batch's scales forever and clamps larger activations silently.  No backward can be
@@ -568,10 +607,10 @@ class VitEngine:
         # a5: cat CLS, += pos_embedding[:, :n+1], emb dropout
         check(l.ecgvit_embed_finish(ptr(a['tok']), ptr(self.P32[pre + 'cls_token']), ptr(self.P32[pre + 'pos_embedding']),
                                     ptr(a['x0']), B, n, d, pe, seed + 1, T, st), 'embed_finish')
-        X = self._trunk_fwd(B, ph, seed)
+        X = self._trunk_fwd(B, ph, seed, cls_only_last)
         self.saved['xL'] = X
-        # a10: x[:, 0] -> LayerNorm -> Linear(d, K)
-        check(l.ecgvit_head_fwd(ptr(X), N, ptr(self.P32[pre + 'mlp_head.0.weight']), ptr(self.P32[pre + 'mlp_head.0.bias']),
+        # a10: x[:, 0] -> LayerNorm -> Linear(d, K)   (cls_only_last: X holds the CLS rows only)
+        check(l.ecgvit_head_fwd(ptr(X), 1 if cls_only_last else N, ptr(self.P32[pre + 'mlp_head.0.weight']), ptr(self.P32[pre + 'mlp_head.0.bias']),
                                 ptr(self.P32[pre + 'mlp_head.1.weight']), ptr(self.P32[pre + 'mlp_head.1.bias']),
                                 ptr(a['logits']), ptr(a['xhat']), ptr(a['hrstd']), B, d, self.K, LN_EPS, T, st), 'head_fwd')
         if labels is None:
@@ -710,14 +749,15 @@ class VitEngine:
             dlog = glogits
         else:
             raise ValueError('backward needs an upstream gradient')
-        dX = a['dxa']
+        cls = sv.get('cls_only_last', False)
+        dX = a['cls_dx'] if cls else a['dxa']   # (cls_only_last: the gradient of the CLS rows only, compact)
         check(l.ecgvit_head_bwd(ptr(dlog), ptr(a['xhat']), ptr(a['hrstd']), ptr(self.P32[pre + 'mlp_head.0.weight']),
                                 ptr(self.P32[pre + 'mlp_head.0.bias']), ptr(self.P32[pre + 'mlp_head.1.weight']),
                                 ptr(G[pre + 'mlp_head.1.weight']), ptr(G[pre + 'mlp_head.1.bias']),
-                                ptr(G[pre + 'mlp_head.0.weight']), ptr(G[pre + 'mlp_head.0.bias']), ptr(dX), N, B, d, self.K,
+                                ptr(G[pre + 'mlp_head.0.weight']), ptr(G[pre + 'mlp_head.0.bias']), ptr(dX), 1 if cls else N, B, d, self.K,
                                 T, st), 'head_bwd')
         self._ready('head')
-        dX = self._trunk_bwd(dX, a['dxb'])
+        dX = self._trunk_bwd(dX, a['dxb'], cls_only_last=cls)
         for k in G:
             if k.startswith('pretrain.'):
                 G[k].zero_()   # the masked-objective head takes no part in the supervised step
@@ -733,8 +773,9 @@ class VitEngine:
         if self.on_grads_ready is not None:
             self.on_grads_ready(tag)
 
-    def _trunk_bwd(self, dX, other):
-        """backward of _trunk_fwd: consumes dX = d(loss)/d(x_L) ([B*T, d]), fills every layer's parameter gradients, returns d(x_0)"""
+    def _trunk_bwd(self, dX, other, cls_only_last=False):
+        """backward of _trunk_fwd: consumes dX = d(loss)/d(x_L) ([B*T, d]; cls_only_last: [B, d], the CLS rows), fills every layer's
+        parameter gradients, returns d(x_0)"""
         a, W, T = self.act, self.W, hip.code(self.dtype)
         l, st = lib(), stream()
         sv = self.saved
@@ -748,7 +789,12 @@ class VitEngine:
         have = False
         dY = dX
         pq4 = pq6 = False   # fp8_linear: the LayerNorm backward before a site already wrote its e5m2 operand copy
-        for i in reversed(range(self.Ly)):
+        top = self.Ly
+        if cls_only_last:
+            top -= 1
+            dX, other = self._cls_block_bwd(dX, a['dxa'], other, B, ph, seed)
+            have, dY = True, (a['dxm'] if ph > 0 else dX)
+        for i in reversed(range(top)):
             L = a['layers'][i]
             lp = f'{pre}transformer.layers.{i}.'
             s0 = seed + 100 * (i + 1)
@@ -815,6 +861,70 @@ class VitEngine:
             self._ready(f'layer{i}')
         return dX
 
+    def _cls_block_bwd(self, dXc, dres, out, B, ph, seed):
+        """backward of `_cls_block_fwd`: dXc = d(loss)/d(x2) of the CLS rows [B, d].  The FFN, the out-projection and LayerNorm 2 run over B
+        rows; the CLS attention backward writes dK / dV of every row and the compact dQ; the K / V products over every row, the Q products
+        over the CLS rows.  LayerNorm 1's backward runs over every row as in `_trunk_bwd`, its residual gradient d(x1) being non-zero on
+        the CLS rows only (scattered into the zeroed `dres`).  Fills the layer's gradients and releases its bucket; returns (d(x_in) = out,
+        the free full slab = dres)"""
+        a, W, P, G = self.act, self.W, self.P32, self.G32
+        l, st = lib(), stream()
+        d, f, h, dh, N = self.d, self.f, self.h, self.dh, self.T
+        M, T, ws = B * N, hip.code(self.dtype), a['ws']
+        i = self.Ly - 1
+        L = a['layers'][i]
+        lp = f'vit.transformer.layers.{i}.'
+        s0 = seed + 100 * (i + 1)
+        Xin = a['x0'] if i == 0 else a['layers'][i - 1]['x2']
+        # ---- FeedForward: x2 = drop(hact W2^T + b2) + x1, the CLS rows
+        dY = dXc
+        if ph > 0:
+            check(l.ecgvit_dropout_apply_rows(ptr(dXc), ptr(a['cls_dy']), B, d, N, ph, s0 + 4, T, st), 'dropout_apply_rows')
+            dY = a['cls_dy']
+        self._colsum(dY, d, G[lp + '1.fn.net.3.bias'], B, d)
+        self._gemm(GEMM_TN, dY, a['cls_hact'], G[lp + '1.fn.net.3.weight'], d, f, B, d, f, f, workspace=ws)
+        self._gemm(GEMM_NN, dY, W[lp + '1.fn.net.3.weight'], a['cls_dh'], B, f, d, d, f, f, epilogue=EPI_MUL_AUX | EPI_COLSUM, aux=a['cls_hpre'],
+                   ldaux=f, workspace=ws, colsum_out=G[lp + '1.fn.net.0.bias'])
+        self._gemm(GEMM_TN, a['cls_dh'], a['cls_xn2'], G[lp + '1.fn.net.0.weight'], f, d, B, f, d, d, workspace=ws)
+        self._gemm(GEMM_NN, a['cls_dh'], W[lp + '1.fn.net.0.weight'], a['cls_dxn'], B, d, f, f, d, d)
+        check(l.ecgvit_layernorm_bwd_fused_rowpitch(ptr(a['cls_dxn']), ptr(a['cls_x1']), ptr(P[lp + '1.norm.weight']), ptr(a['cls_mean2']),
+                                                    ptr(a['cls_rstd2']), ptr(dXc), ptr(a['cls_dx1']), ptr(G[lp + '1.norm.weight']),
+                                                    ptr(G[lp + '1.norm.bias']), ptr(ws), B, d, ptr(a['cls_dxm']), ptr(G[lp + '0.fn.to_out.0.bias']),
+                                                    ph, s0 + 2, N, T, st), 'layernorm_bwd_fused_rowpitch')
+        # ---- Attention: x1 = drop(attn Wo^T + bo) + x, the CLS rows
+        dY = a['cls_dxm'] if ph > 0 else a['cls_dx1']
+        self._gemm(GEMM_TN, dY, a['cls_attn'], G[lp + '0.fn.to_out.0.weight'], d, d, B, d, d, d, workspace=ws)
+        self._gemm(GEMM_NN, dY, W[lp + '0.fn.to_out.0.weight'], a['cls_dattn'], B, d, d, d, d, d)
+        check(l.ecgvit_attention_cls_bwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_dattn']), ptr(a['cls_lse']), ptr(a['dqkv']), ptr(a['cls_dq']),
+                                         B, N, h, dh, self.scale, ph, s0 + 1, T, st), 'attention_cls_bwd')
+        # to_qkv: dW[K|V] = dKV^T . xn1 over every row, dW[Q] = dQ^T . xn1 over the CLS rows; d(xn1) = dKV . W[K|V] (+ dQ . W[Q] on the CLS rows)
+        name = lp + '0.fn.to_qkv.weight'
+        self._gemm(GEMM_TN, a['dqkv'], L['xn1'], G[name], 2 * d, d, M, 3 * d, d, d, workspace=ws, a_off=d, c_off=d * d)
+        self._gemm(GEMM_TN, a['cls_dq'], L['xn1'], G[name], d, d, B, d, N * d, d, workspace=ws)
+        wt = self.WT.get(name)
+        if wt is not None and M >= 2048:
+            self._gemm(GEMM_NT, a['dqkv'], wt, a['dxn'], M, d, 2 * d, 3 * d, 3 * d, d, a_off=d, b_off=d)
+        else:
+            self._gemm(GEMM_NN, a['dqkv'], W[name], a['dxn'], M, d, 2 * d, 3 * d, d, d, a_off=d, b_off=d * d)
+        self._gemm(GEMM_NN, a['cls_dq'], W[name], a['dxn'], B, d, d, d, d, N * d, epilogue=hip.EPI_ACCUM)
+        dres.zero_()
+        check(l.ecgvit_scatter_rows(ptr(a['cls_dx1']), ptr(self._cls_rows(B)), ptr(dres), B, N, 1, d, d, d, T, st), 'scatter_rows')
+        if i > 0:
+            lq = f'vit.transformer.layers.{i - 1}.'
+            self._ln_bwd_fused(a['dxn'], Xin, P[lp + '0.norm.weight'], L['mean1'], L['rstd1'], dres, out, G[lp + '0.norm.weight'],
+                               G[lp + '0.norm.bias'], M, a['dxm'], G[lq + '1.fn.net.3.bias'], ph, seed + 100 * i + 4)
+        else:
+            self._ln_bwd(a['dxn'], Xin, P[lp + '0.norm.weight'], L['mean1'], L['rstd1'], dres, out, G[lp + '0.norm.weight'], G[lp + '0.norm.bias'], M)
+        self._ready(f'layer{i}')
+        return out, dres
+
+    def _cls_rows(self, B):
+        """int32 [B, 1] zeros: row 0 of every record (ecgvit_scatter_rows index)"""
+        t = getattr(self, '_cls_idx', None)
+        if t is None or t.numel() < B or t.device != self.device:
+            t = self._cls_idx = torch.zeros(max(B, 1), dtype=torch.int32, device=self.device)
+        return t[:B]
+
     def _attn_bwd_f32(self, L, B, ph, seed):
         d, h, dh, N = self.d, self.h, self.dh, self.T
         a = self.act
@@ -841,6 +951,8 @@ class VitEngine:
         """Post-softmax attention of `layer` for the last forward, (B, h, N, N) f32 -- what vit_pytorch's Recorder hooks
         (reference ecg_vit.py:176-194). The f32 path keeps them; the fused bf16 path rebuilds them from its saved qkv + log-sum-exp."""
         B, L = self.saved['B'], self.act['layers'][layer]
+        if self.saved.get('cls_only_last') and layer % self.Ly == self.Ly - 1:
+            raise RuntimeError('the last forward ran with cls_only_last: its last block computed the CLS query only')
         if self.dtype == torch.float32:
             return L['probs'].view(B, self.h, self.T, self.T)
         out = torch.empty(B, self.h, self.T, self.T, dtype=torch.float32, device=L['qkv'].device)

@@ -50,6 +50,7 @@ SIGNATURES = {
     'ecgvit_version': (c_char_p, []),
     'ecgvit_abi_version': (c_int, []),
     'ecgvit_gemm': (c_int, [POINTER(GemmDesc), _P]),
+    'ecgvit_gemm_rowpitch': (c_int, [POINTER(GemmDesc), _I, _P]),
     'ecgvit_gemm_workspace': (c_int64, [POINTER(GemmDesc)]),
     'ecgvit_gemm_kernel': (c_int, [POINTER(GemmDesc)]),
     'ecgvit_fp8_amax': (c_int, [_P, _P, _I, _L, _P, _P]),
@@ -64,14 +65,18 @@ SIGNATURES = {
     'ecgvit_layernorm_bwd_workspace': (c_int64, [_L, _I]),
     'ecgvit_layernorm_bwd': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P]),
     'ecgvit_layernorm_bwd_fused': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _F, _U, _I, _P]),
+    'ecgvit_layernorm_bwd_fused_rowpitch': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _F, _U, _I, _I, _P]),
     'ecgvit_layernorm_bwd_fused_q8': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _F, _U, _P, _P, _P, _P]),
     'ecgvit_dropout_apply': (c_int, [_P, _P, _L, _F, _U, _I, _P]),
+    'ecgvit_dropout_apply_rows': (c_int, [_P, _P, _L, _I, _I, _F, _U, _I, _P]),
     'ecgvit_colsum_workspace': (c_int64, [_L, _I]),
     'ecgvit_colsum': (c_int, [_P, _L, _P, _P, _L, _I, _I, _P]),
     'ecgvit_attention_fwd': (c_int, [_P, _P, _P, _I, _I, _I, _I, _F, _F, _U, _I, _P]),
     'ecgvit_attention_fwd_q8': (c_int, [_P, _P, _P, _I, _I, _I, _I, _F, _F, _U, _P, _P, _P, _P]),
     'ecgvit_attention_bwd': (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _U, _I, _P]),
     'ecgvit_attention_bwd_q8': (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _U, _P, _P, _P, _P]),
+    'ecgvit_attention_cls_fwd': (c_int, [_P, _P, _P, _I, _I, _I, _I, _F, _F, _U, _I, _P]),
+    'ecgvit_attention_cls_bwd': (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _U, _I, _P]),
     'ecgvit_attention_probs': (c_int, [_P, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
     'ecgvit_softmax_rows': (c_int, [_P, _L, _I, _L, _P]),
     'ecgvit_softmax_bwd_rows': (c_int, [_P, _P, _L, _I, _L, _F, _P]),
@@ -184,14 +189,19 @@ def gemm_desc(layout, A, B, C, M, N, K, lda, ldb, ldc, *, epilogue=0, bias=None,
     return d
 
 
-def gemm(layout, A, B, C, M, N, K, lda, ldb, ldc, **kw):
-    """C = epilogue(alpha * op(A) . op(B)); keyword arguments as `gemm_desc`."""
+def gemm(layout, A, B, C, M, N, K, lda, ldb, ldc, mask_row_pitch=1, **kw):
+    """C = epilogue(alpha * op(A) . op(B)); keyword arguments as `gemm_desc`.  mask_row_pitch > 1: output row m draws the dropout bits
+    of row m * mask_row_pitch (ecgvit_gemm_rowpitch: a product over one row per record)."""
     d = gemm_desc(layout, A, B, C, M, N, K, lda, ldb, ldc, **kw)
-    check(lib().ecgvit_gemm(byref(d), stream()), 'ecgvit_gemm')
+    if mask_row_pitch != 1:
+        check(lib().ecgvit_gemm_rowpitch(byref(d), mask_row_pitch, stream()), 'ecgvit_gemm_rowpitch')
+    else:
+        check(lib().ecgvit_gemm(byref(d), stream()), 'ecgvit_gemm')
 
 
-def gemm_kernel(layout, A, B, C, M, N, K, lda, ldb, ldc, **kw):
-    """KERNEL_* id of the kernel family `gemm()` would launch for these arguments (the library's own dispatch, nothing launched)"""
+def gemm_kernel(layout, A, B, C, M, N, K, lda, ldb, ldc, mask_row_pitch=1, **kw):
+    """KERNEL_* id of the kernel family `gemm()` would launch for these arguments (the library's own dispatch, nothing launched; the mask row
+    pitch takes no part in it)"""
     d = gemm_desc(layout, A, B, C, M, N, K, lda, ldb, ldc, **kw)
     return lib().ecgvit_gemm_kernel(byref(d))
 

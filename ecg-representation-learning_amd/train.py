@@ -242,7 +242,10 @@ class HipTrainStep:
         w = None
         if model.loss_weight:
             w = torch.tensor(model.loss_weight, device=y.device, dtype=torch.float32)[y.long()].contiguous()
-        logits, _, loss_mean = eng.forward(x, y, w, training=True, seed=seed, want_mean=True)
+        # the classifier reads the CLS rows only: the last block skips the other rows past its K / V (bf16 engine; the fp8 step keeps the
+        # full block -- its 512-row products would fall below the 8-bit kernels' gates and change the delayed-scaling sites)
+        cls_only = eng.dtype == torch.bfloat16 and not eng.fp8
+        logits, _, loss_mean = eng.forward(x, y, w, training=True, seed=seed, want_mean=True, cls_only_last=cls_only)
         model._fwd_id += 1
         B, K = x.shape[0], eng.K
         tpw = self._arm_overlap(model)

@@ -117,6 +117,10 @@ typedef struct ecgvit_gemm_desc {
 } ecgvit_gemm_desc;
 
 int ecgvit_gemm(const ecgvit_gemm_desc *d, void *stream);
+/* Same product; every dropout epilogue draws the bits of output row m * mask_row_pitch (element index (m * mask_row_pitch) * N + n): a product
+ * over one row per record (addressed compactly or through lda / ldc) applies exactly the mask the full launch applies to those rows.
+ * mask_row_pitch >= 1; 1 == ecgvit_gemm. */
+int ecgvit_gemm_rowpitch(const ecgvit_gemm_desc *d, int mask_row_pitch, void *stream);
 /* which kernel family ecgvit_gemm would launch for this descriptor (nothing is launched, pointers are not dereferenced but must be
  * the real ones: alignment decides eligibility).  Lets a profiler attribute a call to a kernel symbol without restating the dispatch. */
 #define ECGVIT_KERNEL_NONE 0        /* the call would return ECGVIT_EINVAL                                   */
@@ -187,6 +191,11 @@ int ecgvit_layernorm_bwd_fused(const void *dy, const void *x, const float *gamma
                                const void *dres, void *dx, float *dgamma, float *dbeta, void *partial, int64_t rows, int d,
                                void *dxm, float *dcolsum, float dropout_p, uint64_t seed, int dtype, void *stream);
 
+/* Same, with the dropout bits of row r * mask_row_pitch for row r (a compact launch over one row per record; 1 == ecgvit_layernorm_bwd_fused) */
+int ecgvit_layernorm_bwd_fused_rowpitch(const void *dy, const void *x, const float *gamma, const float *mean, const float *rstd,
+                                        const void *dres, void *dx, float *dgamma, float *dbeta, void *partial, int64_t rows, int d,
+                                        void *dxm, float *dcolsum, float dropout_p, uint64_t seed, int mask_row_pitch, int dtype, void *stream);
+
 /* fp8 operand path: the same fused backward (bf16, d in 64 * {4, 8, 12, 16, 24, 32}) that also writes g8 = saturate(v / *q8_scale) in e5m2 for
  * v = the gradient the next stage consumes (dxm when dropout_p > 0, else dx; as stored) and accumulates *q8_amax = max(*q8_amax, max |v|):
  * the 8-bit A operand of that stage's input-gradient product, without a quantise pass over the gradient.
@@ -199,6 +208,9 @@ int ecgvit_layernorm_bwd_fused_q8(const void *dy, const void *x, const float *ga
 /* out[i] = in[i] * keep(seed, i) / (1-p): re-applies an epilogue dropout mask (element index = m*N+n, contiguous [M,N])
  * to the incoming gradient of a `dropout(acc + bias) + residual` site.  in == out allowed. */
 int ecgvit_dropout_apply(const void *in, void *out, int64_t count, float dropout_p, uint64_t seed, int dtype, void *stream);
+/* the same over a contiguous [rows, cols] slab whose row r takes the mask of row r * mask_row_pitch of a [*, cols] tensor (cols % 8 == 0) */
+int ecgvit_dropout_apply_rows(const void *in, void *out, int64_t rows, int cols, int mask_row_pitch, float dropout_p, uint64_t seed, int dtype,
+                              void *stream);
 
 /* out[n] = sum_m in[m,n]  (bias gradients).  `partial`: ecgvit_colsum_workspace(M,N) bytes. */
 int64_t ecgvit_colsum_workspace(int64_t M, int N);
@@ -228,6 +240,16 @@ int ecgvit_attention_bwd(const void *qkv, const void *out, const void *dout, con
 int ecgvit_attention_bwd_q8(const void *qkv, const void *out, const void *dout, const float *lse, void *dqkv,
                             int B, int N, int h, int dh, float scale, float dropout_p, uint64_t seed, void *dqkv8,
                             const float *q8_scale, float *q8_amax, void *stream);
+/* CLS-row attention (the pruned last block of the supervised step: the classifier reads row 0 of each record only).  Query row 0 of every
+ * (record, head) against all N keys of `qkv` (layout as above): out_cls [B, h*dh] compact = row 0 of ecgvit_attention_fwd's out,
+ * lse_cls [B, h] = its log-sum-exp, the same attention-dropout bits (bf16, dh == 64, N <= 512). */
+int ecgvit_attention_cls_fwd(const void *qkv, void *out_cls, float *lse_cls, int B, int N, int h, int dh, float scale, float dropout_p,
+                             uint64_t seed, int dtype, void *stream);
+/* its backward for an upstream gradient dout_cls [B, h*dh] on row 0 only: writes the K and V columns of dqkv for EVERY row (what
+ * ecgvit_attention_bwd writes there for a dout that is zero outside row 0) and dq_cls [B, h*dh] = the Q gradient of row 0; the Q columns of
+ * dqkv are not touched. */
+int ecgvit_attention_cls_bwd(const void *qkv, const void *out_cls, const void *dout_cls, const float *lse_cls, void *dqkv, void *dq_cls,
+                             int B, int N, int h, int dh, float scale, float dropout_p, uint64_t seed, int dtype, void *stream);
 /* export of the fused path's post-softmax probabilities (next row f3; what vit_pytorch's Recorder hooks, reference ecg_vit.py:176-180):
  * probs[B,h,N,N] f32 = exp(scale * q k^T - lse), from the qkv / lse a fused forward left behind. bf16 path only (the f32 path
  * materialises the scores anyway); visualisation-time, not tuned. B*h <= 65535. */
