@@ -29,22 +29,12 @@ namespace {
 // SPLIT (records of more than 256 tokens, e.g. patch 10 -> 501): one workgroup per (record, head, 256-query half); the keys pass through
 // the SAME 64 KiB of images in 256-key windows (the online softmax carries m, l and O across them), so two workgroups still share a CU --
 // with all 501 keys resident (128 KiB) a CU held one workgroup, two waves per SIMD, and this VALU-bound kernel ran at 2/3 of its rate.
-#ifdef ECGVIT_TOOLS
-__device__ unsigned long long *g_attn_stamps = nullptr;   // diagnostics (ecgvit_debug_attn_stamps, tools build): per-block cycle stamps, else null
-#endif
-// `make tools TOOLS_EXTRA=-DECGVIT_ATTN_ABL=n` (tools/attn_ablate.sh): timing diagnostics with WRONG results -- one phase of the persistent backward removed
-// per build (1: dQ product, 2: dV / dK products, 3: the vector arithmetic, 4: S / dP products, 5: dS -> LDS, 6: the slab / K stream, 7: the dQ stores), and of the
-// forward (8: the softmax / dropout arithmetic, 9: the Q.K^T products, 10: the P.V products, 11: the K / V image loads, 12: the output stores)
-#if defined(ECGVIT_TOOLS) && defined(ECGVIT_ATTN_ABL)
-#define ATTN_ABL(n) (((ECGVIT_ATTN_ABL) >> (n)) & 1)   // a bit mask: bit n removes phase n
-#else
-#define ATTN_ABL(n) false
-#endif
 // ---- the vector phase of one 32-key x 32-query score tile, shared by both forward kernels (so that they agree bit for bit): lazy running maximum,
-// p = exp2(s c - m c) and the row sum two elements per instruction (v_pk_fma_f32 / v_pk_add_f32: the same IEEE operations per element; the sum runs
-// as two interleaved partial sums), packed to bf16, dropout applied to the PACKED pairs -- per key quad (one hash word, 8 bits per key) the keep bits
-// in three bit-parallel instructions (the >= / < 128 threshold forms are ONE three-input bit operation on a uniform mask), per pair one byte permute,
-// one packed arithmetic shift, one AND.  ~9 vector instructions per score element instead of ~11 (round 6).
+// p = exp2(s c - m c) and the row sum (scalar fma / exp / add), dropout as four selects per hash word (one hash word per key quad, 8 bits per key),
+// packed to bf16.  Measured against two packed forms at 256 x 16 x 501 (streamed kernel) / 512 x 12 x 251 (one-item kernel) on one device
+// (profiles/r06_attn_fwd_stream.txt): this form 476.7 / 198.3 us; dropout on the packed pairs (keep bits in three bit-parallel instructions, permute +
+// packed shift + AND per pair) 485.6 / 201.3; that plus v_pk_fma_f32 / v_pk_add_f32 for the exponent argument and the row sum 498.8 / 200.5 -- fewer
+// instructions, slower: packed f32 forms issue at half rate beside the MFMAs (profiles/r04_valu_rate.txt) and the select form overlaps better.
 template <bool DROP>
 __device__ __forceinline__ void attn_fwd_tile_vec(f32x16 &sc, float &m, float &l, f32x16 (&o)[2], float c, uint32_t hb, uint32_t c4, uint32_t thi_mask,
                                                   u32x4 (&pk)[2]) {
@@ -66,21 +56,6 @@ __device__ __forceinline__ void attn_fwd_tile_vec(f32x16 &sc, float &m, float &l
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
     }
-#ifndef ATTN_VEC_FORM
-#define ATTN_VEC_FORM 0   // 0 ships.  Measured at 256 x 16 x 501 (streamed kernel) / 512 x 12 x 251 (one-item kernel) against round 5 on one device (profiles/r06_attn_fwd_stream.txt): form 0 (scalar fma / exp / add, dropout as four selects per hash word) 476.7 / 198.3 us; 1 (dropout on the packed pairs: keep bits in three bit-parallel instructions, permute + packed shift + AND per pair) 485.6 / 201.3; 2 (1 + v_pk_fma_f32 / v_pk_add_f32 for the exponent argument and the row sum) 498.8 / 200.5 -- fewer instructions, slower: packed f32 forms issue at half rate beside the MFMAs (profiles/r04_valu_rate.txt) and the select form overlaps better
-#endif
-#if ATTN_VEC_FORM >= 2
-    const f32x2 c2 = {c, c}, nmc = {-m * c, -m * c};
-    f32x2 ls2 = {0.f, 0.f};
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-        const f32x2 a = __builtin_elementwise_fma(f32x2{sc[r], sc[r + 1]}, c2, nmc);   // argument <= 8
-        const f32x2 p = {__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])};
-        sc[r] = p[0]; sc[r + 1] = p[1];
-        ls2 += p;
-    }
-    l += ls2[0] + ls2[1];                           // per-half partial sums; halves are combined after the loop
-#else
     const float mc = m * c;
     float ls = 0.f;
 #pragma unroll
@@ -90,8 +65,6 @@ __device__ __forceinline__ void attn_fwd_tile_vec(f32x16 &sc, float &m, float &l
         ls += p;
     }
     l += ls;
-#endif
-#if ATTN_VEC_FORM == 0
     if constexpr (DROP) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -102,24 +75,6 @@ __device__ __forceinline__ void attn_fwd_tile_vec(f32x16 &sc, float &m, float &l
     }
 #pragma unroll
     for (int ss = 0; ss < 2; ++ss) pk[ss] = __builtin_bit_cast(u32x4, pack8(sc, ss));
-#else
-#pragma unroll
-    for (int ss = 0; ss < 2; ++ss) pk[ss] = __builtin_bit_cast(u32x4, pack8(sc, ss));
-    if constexpr (DROP) {  // dropout on the probabilities (the normaliser keeps the un-dropped sum: softmax -> Dropout); the 1/(1-p) rescale is folded
-        // into the final normalisation.  My 16 keys are 4 quads: kt*32 + 8g + 4*lh + {0..3}; dword j of pk[ss] = keys (2 (j & 1), + 1) of quad 2 ss + (j >> 1)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const uint32_t hh = pair_finish(hb + (uint32_t)(2 * g) * ECGVIT_WEYL);
-            const uint32_t x1 = (hh & 0x7F7F7F7Fu) + c4;
-            const uint32_t x = (x1 & hh & thi_mask) | ((x1 | hh) & ~thi_mask);      // bit 7 of byte k: keep(key k) -- quad_keepbits for either threshold range
-#pragma unroll
-            for (int pp = 0; pp < 2; ++pp) {
-                const uint32_t wv = __builtin_amdgcn_perm(x, x, pp ? 0x030C020Cu : 0x010C000Cu);
-                pk[g >> 1][2 * (g & 1) + pp] &= __builtin_bit_cast(uint32_t, __builtin_bit_cast(s16x2_t, wv) >> (s16x2_t){15, 15});
-            }
-        }
-    }
-#endif
 }
 
 template <bool DROP, bool Q8 = false, bool SPLIT = false>
@@ -140,28 +95,18 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_bf16_kernel(const bf16_t *__r
     const int64_t d3 = 3 * (int64_t)d;
     const bf16_t *base = qkv + (int64_t)b * N * d3 + hd * 64;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // One workgroup per work item, two per CU.  Round 5 measured where such a workgroup's 16.7 us go (tools/attn_fwd_timeline.py: 4.5 us waiting for its
+    // One workgroup per work item, two per CU.  Round 5 measured where such a workgroup's 16.7 us go (per-workgroup clock stamps: 4.5 us waiting for its
     // images, 7.0 in products and softmax, 0.8 storing, 4.3 of empty slot until the next one runs) and built both persistent forms: 2 x CUs workgroups
     // walking the items behind one barrier each (241 against 203 us at 512 x 12 x 251: the two workgroups of a CU fall into step, load together, compute
     // together) and ONE 16-wave workgroup per CU whose two 8-wave groups alternate by construction, one computing while the other loads (218 against 194:
     // two waves per SIMD cannot hide the LDS / MFMA / exp latencies that four do).  The dispatcher's refill keeps the phases mixed: kept.
     // profiles/r05_attn_ablation.txt
-#ifdef ECGVIT_TOOLS
-    // tools/attn_fwd_timeline.py: per workgroup {start, images landed, last product done, stores issued} on the 100-MHz clock, and the hardware id
-    unsigned long long *fst = (g_attn_stamps && threadIdx.x == 0) ? g_attn_stamps + (int64_t)blockIdx.x * 8 : nullptr;
-    if (fst) { fst[0] = __builtin_amdgcn_s_memrealtime(); fst[4] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)); }
-#else
-    unsigned long long *const fst = nullptr;
-#endif
     if constexpr (!SPLIT) {
         // K and V images by LDS-DMA: all 64 one-KiB pieces of the item in flight at once, no VGPR round trip and no ds_write pass
-        if constexpr (!ATTN_ABL(11)) {
         dma_image<8>(Kimg, base + d, d3, N, NK, wave, lane);
         dma_image<8>(Vimg, base + 2 * d, d3, N, NK, wave, lane);
-        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (fst) fst[1] = __builtin_amdgcn_s_memrealtime();
     }
 
     const int lr = lane & 31, lh = lane >> 5;
@@ -201,7 +146,6 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_bf16_kernel(const bf16_t *__r
             f32x16 s;
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[r] = 0.f;
-            if constexpr (ATTN_ABL(9)) { asm volatile("" : "+v"(s)); } else
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks)
                 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag_c(Kimg + ktl * 4096, ro.ks[ks]), qf[ks], s, 0, 0, 0);
@@ -213,24 +157,16 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_bf16_kernel(const bf16_t *__r
                 }
             }
             u32x4 pk[2];
-            if constexpr (!ATTN_ABL(8)) {
-                attn_fwd_tile_vec<DROP>(s, m, l, o, c, (rowquad + (uint32_t)(kt * 8 + lh)) * ECGVIT_WEYL + smix, quad_c4(thresh), thresh >= 128u ? ~0u : 0u, pk);
-            } else {
-#pragma unroll
-                for (int ss = 0; ss < 2; ++ss) pk[ss] = __builtin_bit_cast(u32x4, pack8(s, ss));
-            }
+            attn_fwd_tile_vec<DROP>(s, m, l, o, c, (rowquad + (uint32_t)(kt * 8 + lh)) * ECGVIT_WEYL + smix, quad_c4(thresh), thresh >= 128u ? ~0u : 0u, pk);
 #pragma unroll
             for (int ss = 0; ss < 2; ++ss) {
                 const bf16x8 pf = __builtin_bit_cast(bf16x8, pk[ss]);
 #pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    if constexpr (ATTN_ABL(10)) { asm volatile("" : "+v"(o[dt]) : "v"(pf)); continue; }
+                for (int dt = 0; dt < 2; ++dt)
                     o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag_c(Vimg + ktl * 4096 + ss * 2048, to.lo[dt], to.hi[dt]), pf, o[dt], 0, 0, 0);
-                }
             }
         }
         l += __shfl_xor(l, 32, 64);
-        if (fst) fst[2] = __builtin_amdgcn_s_memrealtime();
         [[maybe_unused]] float qmax = 0.f;
         // output: lane (lr, lh) holds columns dt*32 + 8*g4 + 4*lh + {0..3} of query row lr -- 8-B runs interleaved with its partner lane's (lr, lh^1).
         // One v_permlane32_swap per dword hands each lane of the pair BOTH halves of two g4 groups: 16-B stores of contiguous bytes (4 per wave and
@@ -278,7 +214,7 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_bf16_kernel(const bf16_t *__r
                         const auto sw = __builtin_amdgcn_permlane32_swap(D[0][k], D[1][k], false, false);
                         st[k] = sw[0]; st[2 + k] = sw[1];
                     }
-                    if (q < N && !(ATTN_ABL(12) && st[0] != 0x12345u)) *reinterpret_cast<u32x4 *>(orow + dt * 32 + 16 * lh + 8 * j) = st;
+                    if (q < N) *reinterpret_cast<u32x4 *>(orow + dt * 32 + 16 * lh + 8 * j) = st;
                     if constexpr (Q8) {
                         const auto sw = __builtin_amdgcn_permlane32_swap(W8[0], W8[1], false, false);
                         w8[2 * j] = sw[0]; w8[2 * j + 1] = sw[1];
@@ -290,7 +226,6 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_bf16_kernel(const bf16_t *__r
             }
             if (q < N && lh == 0) lse[(int64_t)bh * N + q] = m * scale + logf(l);
         }
-        if (fst) fst[3] = __builtin_amdgcn_s_memrealtime();
         if constexpr (Q8) {
             wave_amax_publish(q8_amax, qmax, amax_seen);
         }
@@ -530,7 +465,7 @@ template <int NKT, bool DROP>
 __global__ __launch_bounds__(NKT * 64) void attn_bwd_bf16_kernel(const bf16_t *__restrict__ qkv, const bf16_t *__restrict__ out,
                                                                  const bf16_t *__restrict__ dout, const float *__restrict__ lse,
                                                                  bf16_t *__restrict__ dqkv, int N, int h, float scale,
-                                                                 uint64_t seed, uint32_t thresh, float inv_keep, int ablate) {
+                                                                 uint64_t seed, uint32_t thresh, float inv_keep) {
     constexpr int NK = NKT * 32, NT = NKT * 64;
     constexpr int IMG = NK * 128, DSB = NK * 64;
     __shared__ __attribute__((aligned(16))) char smem[3 * IMG + 2 * DSB + 2 * NK * 4];
@@ -611,7 +546,7 @@ __global__ __launch_bounds__(NKT * 64) void attn_bwd_bf16_kernel(const bf16_t *_
 #pragma unroll
     for (int dhc = 0; dhc < 4; ++dhc) dq_b[dhc] = img_off(dq_key, (dhc * 16 + (dq_i & 3) * 4) * 2);
 
-    for (int qb = (ablate & 4) ? nqb : 0; qb < nqb; ++qb) {
+    for (int qb = 0; qb < nqb; ++qb) {
         const char *Qrow = Qimg + qb * 4096, *dOrow = dOimg + qb * 4096;
         // dropout: the forward kernel's function -- quad = (bh*N + q) * ceil(N/4) + key/4, byte = key & 3.  The 4 keys of a quad sit on 4
         // adjacent lanes: lane j of the quad hashes query j of each group of four and the others take it by a quad_perm broadcast
@@ -655,7 +590,6 @@ __global__ __launch_bounds__(NKT * 64) void attn_bwd_bf16_kernel(const bf16_t *_
                 dp[r] = p * (g - d4[k]) * scale;  // dS, in place
             }
         }
-        if (!(ablate & 2))
 #pragma unroll
         for (int ss = 0; ss < 2; ++ss) {
             const bf16x8 pf = pack8(s, ss), dsf = pack8(dp, ss);
@@ -682,7 +616,7 @@ __global__ __launch_bounds__(NKT * 64) void attn_bwd_bf16_kernel(const bf16_t *_
         // dQ[32 x 64] = dS[32 x NK] . K[NK x 64] as 8 tiles of 16x16 (qt = tile&1, dhc = tile>>1).  The contraction index of
         // the 16x16x32 MFMA is permuted (k = 8g + j  <->  key = 32*st + 4g + (j&3) + 16*(j>>2)) so that each half-wave's
         // transposed read covers 8 CONSECUTIVE key rows of the dS and K images -- conflict-free on both.
-        for (int tile = (ablate & 1) ? 8 : wave; tile < 8; tile += NKT) {
+        for (int tile = wave; tile < 8; tile += NKT) {
             const int qt = tile & 1, dhc = tile >> 1;
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             const int g = lane >> 4, i = lane & 15;
@@ -746,11 +680,10 @@ __global__ __launch_bounds__(NKT * 64) void attn_bwd_bf16_kernel(const bf16_t *_
 
 // Records longer than 256 tokens (N <= 512, e.g. patch 10 -> 501) run as TWO launches, one per half of the keys: `k0` is the first key
 // of this launch's 256-key window, queries always run over all of N; the second launch adds its dQ to the first one's (ACCUM).
-// PRIO: static wave priority for the whole kernel (no per-phase flips): 0 none, 1 waves 4-7 raised, 2 waves 0-3 raised
 // Q8 (fp8_linear; bit 0: dK / dV, bit 1: dQ): additionally dqkv8 = saturate(dqkv as stored / *q8_scale) in e5m2 (same [B*N, 3*h*dh] layout, one
 // byte per element) -- the A operand of the QKV projection's two backward products, written here instead of by a quantise pass over
 // dqkv -- and *q8_amax = max(*q8_amax, max |dqkv|).  With two key windows the first launch emits its dK / dV only (dQ is final in the second).
-template <bool DROP, bool ACCUM, bool STAGGER = true, int PRIO = 1, int Q8 = 0>
+template <bool DROP, bool ACCUM, bool STAGGER = true, int Q8 = 0>
 __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__restrict__ qkv, const bf16_t *__restrict__ out,
                                                             const bf16_t *__restrict__ dout, const float *__restrict__ lse,
                                                             bf16_t *__restrict__ dqkv, int N, int h, float scale, uint64_t seed,
@@ -880,23 +813,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
 
     // the second-dispatched half of the workgroup loses VALU arbitration to the older half in every block (priority, then age): one
     // static priority raise for it, no per-phase flips (guide: two waves per SIMD, item 4)
-    if (PRIO == 1 && late) __builtin_amdgcn_s_setprio(1);
-    if (PRIO == 2 && !late) __builtin_amdgcn_s_setprio(1);
-#ifdef ECGVIT_TOOLS
-    unsigned long long *stamps = g_attn_stamps ? g_attn_stamps + (int64_t)blockIdx.x * 128 : nullptr;
-#else
-    unsigned long long *const stamps = nullptr;   // (every stamp below folds away)
-#endif
-#if defined(ECGVIT_TOOLS) && defined(ECGVIT_ATTN_PHASE_STAMPS)
-    // `make tools TOOLS_EXTRA=-DECGVIT_ATTN_PHASE_STAMPS` only (tools/attn_phase_stamps.py): per-PHASE stamps of the second item, one record per wave
-    // group (lane 0 of waves 0 and 4), behind the 768 block records of the buffer: [768 + block][group][query block][phase 0..7 = start, issue, A, V,
-    // B+W, C, wait, barrier].  Not in the default tools build: the per-lane stamp conditions cost the staggered schedule 13 % (570 against 500 us)
-    unsigned long long *pstamps = (g_attn_stamps && (lane == 0) && (wave == 0 || wave == 4)) ? g_attn_stamps + (768 + (int64_t)blockIdx.x) * 128 + (wave >> 2) * 64 : nullptr;
-#define PH_STAMP(QB, IDX) do { if (pstamps && item_no == 1 && (QB) < 8) pstamps[(QB) * 8 + (IDX)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define PH_STAMP(QB, IDX) do { } while (0)
-#endif
-    int item_no = 0;
+    if (late) __builtin_amdgcn_s_setprio(1);
     int slot = 0, par = 0, jj = 0;   // ring slot of the current slab, K / LSE buffer of the current item, running slab counter (delta / dS parity)
     for (;;) {
         const int next_it = it + (int)gridDim.x;
@@ -910,7 +827,6 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
 #pragma unroll
             for (int r = 0; r < 16; ++r) { dKt[dt][r] = 0.f; dVt[dt][r] = 0.f; }
 
-        if (stamps && threadIdx.x == 0 && item_no < 4) stamps[item_no * 32] = __builtin_amdgcn_s_memtime();
         // ---- one query block = phases  issue | A: S, dP (8 MFMA) | V: softmax / dropout / dS arithmetic (VALU) | B: dV, dK (8 MFMA) |
         // W: dS -> LDS | wait + barrier | C: dQ tile (8 small MFMA) + store.  Block j lives in ring slot (slot0 + j) & 3 and uses
         // delta / dS buffer (jj0 + j) & 1.
@@ -941,10 +857,8 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
                 dma_k(nxt, Kimg0 + (par ^ 1) * IMG);
                 lse_n = load_lse(nxt);
             }
-            if constexpr (!ATTN_ABL(6)) {
             if (qb + 3 < nqb) dma_slab(cur, qb + 3, (sl + 3) & 3);
             else if (has_next) dma_slab(nxt, qb + 3 - nqb, (sl + 3) & 3);
-            }
             // delta of the NEXT slab (visible since the previous barrier), published by this iteration's barrier
             slab_delta((sl + 1) & 3, (jj0 + qb + 1) & 1);
         };
@@ -952,7 +866,6 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
             const char *Qrow = slab0 + ((slot0 + qb) & 3) * SLAB, *dOrow = Qrow + 4096;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-            if constexpr (ATTN_ABL(4)) { asm volatile("" : "+v"(s), "+v"(dp)); return; }
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {   // K fragments of this wave's 32 keys come from the image every time (4 reads): 16 VGPRs less
                 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(row_frag_c(Qrow, ro.ks[ks]), row_frag_c(Kimg + wave * 4096, ro.ks[ks]), s, 0, 0, 0);
@@ -966,11 +879,6 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
         // dS' = P_dropped dP - p' delta' with delta' = delta (1 - p_drop); the factor `scale` is applied to the dQ tile and the dK flush instead
         // of every element (exact for the power-of-two dh^-1/2).
         auto ph_V = [&](int qb) __attribute__((always_inline)) {
-            if constexpr (ATTN_ABL(3)) {
-#pragma unroll
-                for (int m = 0; m < 8; ++m) { Pk[m] = cvt_pk_bf16(s[2 * m], s[2 * m + 1]); Dk[m] = cvt_pk_bf16(dp[2 * m], dp[2 * m + 1]); }
-                return;
-            }
             const float *delta_c = delta_s + ((jj0 + qb) & 1) * 32;
             const uint32_t qpitch = (uint32_t)((N + 3) >> 2);
             const uint32_t hstep = qpitch * ECGVIT_WEYL;
@@ -1010,7 +918,6 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
             for (int m = 0; m < 8; ++m) { Pk[m] = cvt_pk_bf16(s[2 * m], s[2 * m + 1]); Dk[m] = cvt_pk_bf16(dp[2 * m], dp[2 * m + 1]); }
         };
         auto ph_B = [&](int qb) __attribute__((always_inline)) {
-            if constexpr (ATTN_ABL(2)) { asm volatile("" : "+v"(dVt[0]), "+v"(dKt[0]) : "v"(Pk[0]), "v"(Dk[0])); return; }
             const char *Qrow = slab0 + ((slot0 + qb) & 3) * SLAB, *dOrow = Qrow + 4096;
             uint32_t qa[4], da[4];
 #pragma unroll
@@ -1048,7 +955,6 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
 #undef TRM
         };
         auto ph_W = [&](int qb) __attribute__((always_inline)) {
-            if constexpr (ATTN_ABL(5)) return;
             char *dsb = dSimg + ((jj0 + qb) & 1) * DSB;
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
@@ -1063,7 +969,6 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
         // block 1 (4 + 1), one dQ store (the previous block's) -- or, on an item's first query block, the 8 dK / dV stores + last dQ store.
         auto ph_waitbar = [&](int qb) __attribute__((always_inline)) {
             __builtin_amdgcn_sched_barrier(0);
-            if (stamps && threadIdx.x == 0 && item_no < 4 && qb < 8) stamps[item_no * 32 + 1 + qb] = __builtin_amdgcn_s_memtime();
             // allowed in flight (youngest first), with SQ = stores of a dQ tile and SF = dK / dV stores of an item's flush:
             //   leading:  this block's 2 slab pieces [+ K / LSE prefetch 5 at qb == 1] + the previous dQ tile's SQ stores [qb == 0: + SF + SQ of the previous item]
             //   trailing: 1 slab piece [+ 5] + SQ [qb == 0: + SF + SQ]
@@ -1088,9 +993,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
                 else ATTN_WAIT(2);
             }
 #undef ATTN_WAIT
-            if (stamps && threadIdx.x == 0 && item_no < 4 && qb < 8) stamps[item_no * 32 + 9 + qb] = __builtin_amdgcn_s_memtime();
             __builtin_amdgcn_s_barrier();
-            if (stamps && threadIdx.x == 0 && item_no < 4 && qb < 8) stamps[item_no * 32 + 17 + qb] = __builtin_amdgcn_s_memtime();
             __builtin_amdgcn_sched_barrier(0);
             // the next item's V fragments start travelling behind the item's last barrier
             if (has_next && qb == nqb - 1) load_v(nxt, vfn);
@@ -1117,7 +1020,6 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(join_halves(T[6], T[7]), join_halves(T[4], T[5]), acc, 0, 0, 0);   \
             __builtin_amdgcn_sched_barrier(0);
             bf16x4 tA[8], tB[8];
-            if constexpr (!ATTN_ABL(1)) {
             DQR(0, tA)
             DQR(1, tB)
             DQM(tA, 8)
@@ -1126,7 +1028,6 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
             DQR(3, tB)
             DQM(tA, 8)
             DQM(tB, 0)
-            }
 #undef DQR
 #undef DQM
             const int q = qb * 32 + qt * 16 + dq_i;
@@ -1141,7 +1042,6 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = (bf16_t)(acc[r] * scale + (float)o[r]);
             }
-            if constexpr (!ATTN_ABL(7))
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), rdq, (q * d3 + dhc * 16 + 4 * dq_g) * 2, 0, 0);   // rows >= N: dropped
             if constexpr ((Q8 & 2) != 0) {
                 float f[4];
@@ -1166,19 +1066,12 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
         // for bit: every block's arithmetic is the same instruction sequence, only its placement relative to the barriers moves.
         if (!STAGGER || !late) {
             for (int qb = 0; qb < nqb; ++qb) {
-                PH_STAMP(qb, 0);
                 ph_issue(qb);
-                PH_STAMP(qb, 1);
                 ph_A(qb);
-                PH_STAMP(qb, 2);
                 ph_V(qb);
-                PH_STAMP(qb, 3);
                 ph_B(qb);
                 ph_W(qb);   // (W ahead of B, the trailing group's order, was measured here too: 504.4 against 503.1 us)
-                PH_STAMP(qb, 4);
-                PH_STAMP(qb, 5);
                 ph_waitbar(qb);
-                PH_STAMP(qb, 7);
                 ph_C(qb);
             }
         } else {
@@ -1191,20 +1084,13 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
             ph_A(1);
             ph_waitbar(0);
             for (int qb = 1; qb < nqb - 1; ++qb) {
-                PH_STAMP(qb, 0);
                 ph_issue(qb);
-                PH_STAMP(qb, 1);
                 ph_V(qb);
-                PH_STAMP(qb, 3);
                 ph_W(qb);
                 ph_B(qb);
-                PH_STAMP(qb, 4);
                 ph_C(qb - 1, true);
-                PH_STAMP(qb, 5);
                 ph_A(qb + 1);
-                PH_STAMP(qb, 2);
                 ph_waitbar(qb);
-                PH_STAMP(qb, 7);
             }
             ph_issue(nqb - 1);
             ph_V(nqb - 1);
@@ -1214,10 +1100,8 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
             ph_waitbar(nqb - 1);
             ph_C(nqb - 1);
         }
-#undef PH_STAMP
         slot = (slot0 + nqb) & 3;
         jj = jj0 + nqb;
-        if (stamps && threadIdx.x == 0 && item_no < 4) stamps[item_no * 32 + 25] = __builtin_amdgcn_s_memtime();
         // ---- item done: dK^T / dV^T (dh on rows, key on the lane) -> this wave's 32 [key][dh] rows in a private 4-KiB patch -> 128-B rows
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                 // every wave is done reading both dS buffers
@@ -1263,8 +1147,6 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
                 }
             }
         }
-        if (stamps && threadIdx.x == 0 && item_no < 4) stamps[item_no * 32 + 26] = __builtin_amdgcn_s_memtime();
-        ++item_no;
         if (!has_next) break;
         // ---- switch to the next item: its K image and LSE row were fetched during query block 1, its V fragments during the drain
 #pragma unroll
@@ -1479,19 +1361,11 @@ __global__ __launch_bounds__(CLS_THREADS) void attn_cls_bwd_kernel(const bf16_t 
 }  // namespace
 
 #ifdef ECGVIT_TOOLS
-static int g_tools_attn_variant = -1;
-extern "C" int ecgvit_tools_attn_variant(int v) { g_tools_attn_variant = v; return ECGVIT_OK; }
 static int g_tools_attn_fwd_variant = -1;   // -1: the product's dispatch; 0: always the one-item forward; 1: always the streamed forward
 extern "C" int ecgvit_tools_attn_fwd_variant(int v) { g_tools_attn_fwd_variant = v; return ECGVIT_OK; }
 #endif
 
 extern "C" {
-
-#ifdef ECGVIT_TOOLS   // declared in tools/ecgvit_hip_tools.h, exported by build/libecgvit_hip_tools.so only
-int ecgvit_debug_attn_stamps(void *buf) {   // diagnostics: 768 workgroups x 128 uint64 cycle stamps written by the eight-wave persistent backward; NULL = off
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_attn_stamps), &buf, sizeof(buf)) == hipSuccess ? ECGVIT_OK : ECGVIT_ELAUNCH;
-}
-#endif
 
 int ecgvit_attention_probs(const void *qkv, const float *lse, float *probs, int B, int N, int h, int dh, float scale, int dtype, void *stream) {
     if (dtype != ECGVIT_BF16 || dh % 8 || B <= 0 || N <= 0 || h <= 0 || (int64_t)B * h > 65535) return ECGVIT_EINVAL;
@@ -1530,9 +1404,6 @@ static int attention_fwd_launch(const void *qkv, void *out, float *lse, int B, i
 #ifdef ECGVIT_TOOLS
         if (g_tools_attn_fwd_variant == 0) stream_form = false;
         if (g_tools_attn_fwd_variant >= 1) stream_form = (int64_t)N * 3 * h * 64 * 2 < (1ll << 31);
-#endif
-#ifdef ECGVIT_AB_NO_STREAM
-        stream_form = false;   // (A/B builds only)
 #endif
         if (stream_form) {
             static bool sattr = false;
@@ -1610,7 +1481,7 @@ static int attention_bwd_oneitem(const void *qkv, const void *out, const void *d
     const uint32_t th = dropout_threshold8(dropout_p);
     const float ik = dropout_inv_keep8(dropout_p);
     dim3 grid((unsigned)(B * h));
-#define BWD(NKT, DR) hipLaunchKernelGGL((attn_bwd_bf16_kernel<NKT, DR>), grid, dim3(NKT * 64), 0, as_stream(stream), (const bf16_t *)qkv, (const bf16_t *)out, (const bf16_t *)dout, lse, (bf16_t *)dqkv, N, h, scale, seed, th, ik, 0)
+#define BWD(NKT, DR) hipLaunchKernelGGL((attn_bwd_bf16_kernel<NKT, DR>), grid, dim3(NKT * 64), 0, as_stream(stream), (const bf16_t *)qkv, (const bf16_t *)out, (const bf16_t *)dout, lse, (bf16_t *)dqkv, N, h, scale, seed, th, ik)
     if (N <= 128) { if (th) BWD(4, true); else BWD(4, false); }
     else { if (th) BWD(8, true); else BWD(8, false); }
 #undef BWD
@@ -1635,33 +1506,13 @@ static int attention_bwd_launch(const void *qkv, const void *out, const void *do
     // GPU with a collective's kernels is not left with late workgroups a full static share behind (one per CU measured the same alone)
     const dim3 pg((unsigned)(nitems < 768 ? nitems : 768));
 #define PERS_ARGS(K0) pg, dim3(512), 0, as_stream(stream), (const bf16_t *)qkv, (const bf16_t *)out, (const bf16_t *)dout, lse, (bf16_t *)dqkv, N, h, scale, seed, th, ik, nitems, K0
-#ifndef ATTN_BWD_STAGGER
-#define ATTN_BWD_STAGGER true
-#endif
-#ifndef ATTN_BWD_PRIO
-#define ATTN_BWD_PRIO 1
-#endif
-#define PERS(DR, AC, K0) hipLaunchKernelGGL((attn_bwd_pers_kernel<DR, AC, ATTN_BWD_STAGGER, ATTN_BWD_PRIO>), PERS_ARGS(K0))
+#define PERS(DR, AC, K0) hipLaunchKernelGGL((attn_bwd_pers_kernel<DR, AC>), PERS_ARGS(K0))
 // (the emitting variants run the staggered schedule as well since round 4's vector diet -- 239-255 VGPRs, no spills -- except the second key
 // window under dropout with all three conversions, which would spill 4 registers: scratch traffic would join the counted vmcnt waits, so that
 // one keeps the lockstep schedule; round 6 took ten loop-invariant registers out of the kernel -- the K-image offsets recomputed per item, the dQ offset
 // tables replaced by the wave's one offset -- and it still spilled those four (the peak is inside the block's vector phase, not in what lives across it),
 // while the other instantiations got 1.6-2 % SLOWER with the different allocation: taken out again)
-#define PERS8(DR, AC, K0, Q) hipLaunchKernelGGL((attn_bwd_pers_kernel<DR, AC, ATTN_BWD_STAGGER && !(DR && AC && Q == 3), ATTN_BWD_PRIO, Q>), PERS_ARGS(K0), (uint8_t *)dqkv8, q8_scale, q8_amax)
-#ifdef ECGVIT_TOOLS
-    if (g_tools_attn_variant >= 0 && th && N <= 256 && !dqkv8) {   // tools build: A/B of the stagger / priority variants (tools/attn_variants.py)
-        switch (g_tools_attn_variant) {
-            case 0: hipLaunchKernelGGL((attn_bwd_pers_kernel<true, false, false, 1>), PERS_ARGS(0)); break;   // lockstep
-            case 1: hipLaunchKernelGGL((attn_bwd_pers_kernel<true, false, false, 0>), PERS_ARGS(0)); break;
-            case 2: hipLaunchKernelGGL((attn_bwd_pers_kernel<true, false, true, 1>), PERS_ARGS(0)); break;    // what ships
-            case 3: hipLaunchKernelGGL((attn_bwd_pers_kernel<true, false, true, 0>), PERS_ARGS(0)); break;
-            case 4: hipLaunchKernelGGL((attn_bwd_pers_kernel<true, false, true, 2>), PERS_ARGS(0)); break;
-            default: hipLaunchKernelGGL((attn_bwd_pers_kernel<true, false, false, 2>), PERS_ARGS(0)); break;
-        }
-        ECGVIT_CHECK_LAUNCH();
-        return ECGVIT_OK;
-    }
-#endif
+#define PERS8(DR, AC, K0, Q) hipLaunchKernelGGL((attn_bwd_pers_kernel<DR, AC, !(DR && AC && Q == 3), Q>), PERS_ARGS(K0), (uint8_t *)dqkv8, q8_scale, q8_amax)
     if (dqkv8) {
         // one window: dK / dV / dQ all final in this launch; two windows: the first emits its dK / dV, the second its dK / dV and the final dQ
         if (N <= 256) { if (th) PERS8(true, false, 0, 3); else PERS8(false, false, 0, 3); }

@@ -1,5 +1,5 @@
-// Shared device helpers of the fused attention kernels (attention.hip: forward, one-item backward; attention_bwd4.hip: the four-wave
-// persistent backward): the swizzled [row][64 x bf16] LDS image, its row / transposed fragment reads, the dS^T image slot swizzle.
+// Shared device helpers of the fused attention kernels (attention.hip: the forward kernels, the one-item and the persistent backward):
+// the swizzled [row][64 x bf16] LDS image, its row / transposed fragment reads, the dS^T image slot swizzle.
 //
 // LDS image for every [row][64 x bf16] tile (128-B rows):  16-B chunk index ^= bitrev3((row>>1)&7)
 //   -> ds_read_b128 row reads (MFMA K-contiguous operand) hit 16 distinct slots per 16-lane group, and

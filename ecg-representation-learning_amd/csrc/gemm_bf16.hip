@@ -305,8 +305,8 @@ bool ecgvit_gemm_wgrad_applicable(const ecgvit_gemm_desc *d);
 int64_t ecgvit_gemm_wgrad_workspace(const ecgvit_gemm_desc *d);
 int ecgvit_gemm_wgrad_launch(const ecgvit_gemm_desc *d, hipStream_t s);
 bool ecgvit_gemm_nt_applicable(const ecgvit_gemm_desc *d);
-int ecgvit_gemm_nt_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g, int diag);
-int ecgvit_gemm_nt4w_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g, int diag);   // gemm_nt.hip: the four-wave body
+int ecgvit_gemm_nt_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g);
+int ecgvit_gemm_nt4w_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g, bool nt_stores);   // gemm_nt.hip: the four-wave body
 
 extern "C" int64_t ecgvit_gemm_workspace(const ecgvit_gemm_desc *d) {
     if ((d->dtype == ECGVIT_FP8_E4M3 || d->dtype == ECGVIT_BF8_E5M2) && d->layout == ECGVIT_GEMM_TN) return ecgvit_gemm_wgrad_workspace(d);
@@ -336,7 +336,7 @@ int ecgvit_gemm_bf16_launch(const ecgvit_gemm_desc *d, hipStream_t s, int *route
     if (d->layout != ECGVIT_GEMM_NT && d->layout != ECGVIT_GEMM_NN && d->layout != ECGVIT_GEMM_TN) return ECGVIT_EINVAL;
     if (ecgvit_gemm_nt_applicable(d)) {
         if (route) { *route = ECGVIT_KERNEL_GEMM_NT; return ECGVIT_OK; }
-        return ecgvit_gemm_nt_launch(d, s, 0, 0);
+        return ecgvit_gemm_nt_launch(d, s, 0);
     }
     if (ecgvit_gemm_wgrad_applicable(d)) {
         if (route) { *route = ECGVIT_KERNEL_GEMM_WGRAD; return ECGVIT_OK; }
@@ -398,7 +398,7 @@ static int gemm_dispatch(const ecgvit_gemm_desc *d, void *stream, int *route) {
         if (d->dtype == ECGVIT_BF16 && ecgvit_gemm_nt_applicable(d)) return ecgvit_gemm_bf16_launch(d, as_stream(stream), route);   // fused column sums
         if ((d->dtype == ECGVIT_FP8_E4M3 || d->dtype == ECGVIT_BF8_E5M2) && ecgvit_gemm_nt_applicable(d)) {
             if (route) { *route = ECGVIT_KERNEL_GEMM_NT; return ECGVIT_OK; }
-            return ecgvit_gemm_nt_launch(d, as_stream(stream), 0, 0);
+            return ecgvit_gemm_nt_launch(d, as_stream(stream), 0);
         }
         // generic path: plain GEMM, then the stand-alone column-sum kernel over the stored output
         if (d->workspace_bytes < ecgvit_colsum_workspace(d->M, d->N)) return ECGVIT_EINVAL;
@@ -425,7 +425,7 @@ static int gemm_dispatch(const ecgvit_gemm_desc *d, void *stream, int *route) {
         if ((d->epilogue & ECGVIT_EPI_RESIDUAL) && (!d->residual || d->ldr % 8 || reinterpret_cast<uintptr_t>(d->residual) % 16)) return ECGVIT_EINVAL;
         if (d->ldc % 8 != 0 || !ecgvit_gemm_nt_applicable(d)) return ECGVIT_EINVAL;
         if (route) { *route = ECGVIT_KERNEL_GEMM_NT; return ECGVIT_OK; }
-        return ecgvit_gemm_nt_launch(d, as_stream(stream), 0, 0);
+        return ecgvit_gemm_nt_launch(d, as_stream(stream), 0);
     }
     return ECGVIT_EINVAL;
 }
@@ -446,12 +446,12 @@ extern "C" int ecgvit_gemm_kernel(const ecgvit_gemm_desc *d) {
 }
 
 #ifdef ECGVIT_TOOLS
-// tools build only (libecgvit_hip_tools.so): one A . B^T call on gemm_nt_kernel with column groups of raster_g n-tiles (0 = the
-// built-in order) and diag bits (1 = stamped instantiation, 2 = its output stores dropped): tools/gemm_ab.py, tools/nt_stamps.py
-extern "C" int ecgvit_tools_gemm(const ecgvit_gemm_desc *d, void *stream, int kernel, int raster_g, int diag) {
+// tools build only (libecgvit_hip_tools.so): one A . B^T call with column groups of raster_g n-tiles (0 = the built-in order) on
+// gemm_nt_kernel's dispatch (kernel 2) or on the four-wave body with default-policy stores (kernel 3): tools/gemm_ab.py
+extern "C" int ecgvit_tools_gemm(const ecgvit_gemm_desc *d, void *stream, int kernel, int raster_g) {
     if (!d) return ECGVIT_EINVAL;
-    if (kernel == 2) return ecgvit_gemm_nt_applicable(d) ? ecgvit_gemm_nt_launch(d, as_stream(stream), raster_g, diag) : ECGVIT_EINVAL;
-    if (kernel == 3) return ecgvit_gemm_nt_applicable(d) ? ecgvit_gemm_nt4w_launch(d, as_stream(stream), raster_g, diag) : ECGVIT_EINVAL;
+    if (kernel == 2) return ecgvit_gemm_nt_applicable(d) ? ecgvit_gemm_nt_launch(d, as_stream(stream), raster_g) : ECGVIT_EINVAL;
+    if (kernel == 3) return ecgvit_gemm_nt_applicable(d) ? ecgvit_gemm_nt4w_launch(d, as_stream(stream), raster_g, false) : ECGVIT_EINVAL;
     return ecgvit_gemm(d, stream);
 }
 #endif

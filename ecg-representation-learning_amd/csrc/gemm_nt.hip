@@ -24,7 +24,6 @@
 //     combination runs the same kernel with run-time flags.
 #include "common.h"
 #include "nt_tiles.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -42,14 +41,6 @@ using nt_tiles::xcd_remap;
 using nt_tiles::decode_tile;
 
 #define NT_HAS(f) (((FL >= 0) ? FL : e.flags) & (f))
-// PRICING EXPERIMENT (round 6, tools build only; a template flag, never a descriptor flag): LayerNorm folded into its consumer product --
-// LN(x) . W^T = rstd[m] (x . (gamma o W)^T)[m, n] - (rstd mu)[m] ((gamma o W) . 1)[n] + (W . beta)[n], i.e. per output element two FMAs on a row pair
-// (a[m], b[m]) and a column vector g[n] (the second column vector rides on the bias).  tools/gemm_ab.py --rowaffine times the QKV forward and the FFN-up
-// forward with it against what ships; nothing in the product instantiates it.  profiles/r06_ln_fold_pricing.txt
-#define ECGVIT_EPI_ROWAFFINE_X 4096
-#ifdef ECGVIT_TOOLS
-__device__ const float *g_ra_a = nullptr, *g_ra_b = nullptr, *g_ra_g = nullptr;   // row vectors [M], column vector [N] (ecgvit_tools_rowaffine)
-#endif
 
 // two f32 -> one dword of two bf16 (RNE, NaN-safe); written out because hipcc otherwise pairs the converts of an 8-element
 // run across odd register boundaries (5 converts + 4 v_perm/v_alignbit per 16-B store instead of 4 converts)
@@ -134,7 +125,7 @@ __device__ __forceinline__ void nt_epi8(float (&v)[8], const float *bias8, uint3
             for (int k = 0; k < 8; ++k) v[k] *= e.alpha;
         }
     }
-    if (NT_HAS(ECGVIT_EPI_BIAS) && !(kLightBody && (FL & ECGVIT_EPI_ROWAFFINE_X))) {   // (the light row-affine pricing body has folded the bias into its second FMA)
+    if (NT_HAS(ECGVIT_EPI_BIAS)) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] += bias8[k];
     }
@@ -305,18 +296,6 @@ __device__ __forceinline__ void nt_epilogue(f32x4 (&acc)[8][4], const ecgvit_gem
 #pragma unroll
         for (int k = 0; k < 16; ++k) bias[k] = 0.f;
     }
-    constexpr bool kRA = FL >= 0 && (FL & ECGVIT_EPI_ROWAFFINE_X) != 0;
-    [[maybe_unused]] float rag[16];
-    [[maybe_unused]] const float *ra_a = nullptr, *ra_b = nullptr;
-#ifdef ECGVIT_TOOLS
-    if constexpr (kRA) {
-        ra_a = g_ra_a; ra_b = g_ra_b;
-        const f32x4 g0 = *reinterpret_cast<const f32x4 *>(g_ra_g + nl0), g1 = *reinterpret_cast<const f32x4 *>(g_ra_g + nl0 + 4);
-        const f32x4 g2 = *reinterpret_cast<const f32x4 *>(g_ra_g + nl1), g3 = *reinterpret_cast<const f32x4 *>(g_ra_g + nl1 + 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { rag[k] = g0[k]; rag[4 + k] = g1[k]; rag[8 + k] = g2[k]; rag[12 + k] = g3[k]; }
-    }
-#endif
     float cs[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) cs[k] = 0.f;
@@ -369,11 +348,6 @@ __device__ __forceinline__ void nt_epilogue(f32x4 (&acc)[8][4], const ecgvit_gem
         // light bodies: every row load of the tile is issued up front (the 64 fragment registers are free now), then the 8 row steps
         // run fully unrolled on the accumulators in place; stores are fire-and-forget
         u32x4 R[8][2], X[8][2];
-        [[maybe_unused]] float RA[8], RB[8];
-        if constexpr (kRA) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { const int mc = min((int)mrow + 16 * i, M - 1); RA[i] = ra_a[mc]; RB[i] = ra_b[mc]; }
-        }
 #pragma unroll
         for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -389,10 +363,6 @@ __device__ __forceinline__ void nt_epilogue(f32x4 (&acc)[8][4], const ecgvit_gem
             float v0[8], v1[8];
 #pragma unroll
             for (int r = 0; r < 4; ++r) { v0[r] = acc[i][0][r]; v0[4 + r] = acc[i][1][r]; v1[r] = acc[i][2][r]; v1[4 + r] = acc[i][3][r]; }
-            if constexpr (kRA) {   // two FMAs per element: v rstd[m] + ((rstd mu)[m] g[n] + c[n]) (c = the bias vector)
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { v0[k] = fmaf(v0[k], RA[i], fmaf(RB[i], rag[k], bias[k])); v1[k] = fmaf(v1[k], RA[i], fmaf(RB[i], rag[8 + k], bias[8 + k])); }
-            }
             const uint32_t m = mrow + 16 * i, mm = mrowm + 16 * i;
             const bool mok = (int)m < M, mokm = (int)mm < M;
             nt_epi8<TO, FL, CAUX>(v0, bias, m, nb, mok && nok0, mm, nbm, mokm && nokm0, bf, e, to_acc(R[i][0], want_res), to_acc_aux(X[i][0], want_aux), cs, qmax);
@@ -403,8 +373,6 @@ __device__ __forceinline__ void nt_epilogue(f32x4 (&acc)[8][4], const ecgvit_gem
         // heavy bodies must exist ONCE in the instruction stream (I-cache): rolled loop, only the accumulator pick is a switch;
         // row loads one step ahead
         u32x4 nr0 = ld_res(0, 0), nr1 = ld_res(0, 1), na0 = ld_aux(0, 0), na1 = ld_aux(0, 1);
-        [[maybe_unused]] float nra = 0.f, nrb = 0.f;
-        if constexpr (kRA) { const int mc = min((int)mrow, M - 1); nra = ra_a[mc]; nrb = ra_b[mc]; }
         // hipcc's wait-count model does not see LDS-DMA: behind the pieces it would wait `vmcnt(0)` for the bias (all of it is needed by
         // the first row), i.e. for the pieces too.  Consume the bias here, while only the epilogue's own loads are in flight
         if (NT_HAS(ECGVIT_EPI_BIAS)) {
@@ -416,9 +384,7 @@ __device__ __forceinline__ void nt_epilogue(f32x4 (&acc)[8][4], const ecgvit_gem
 #pragma unroll 1
         for (int i = 0; i < 8; ++i) {
             const u32x4 r0 = nr0, r1 = nr1, a0 = na0, a1 = na1;
-            [[maybe_unused]] const float cra = nra, crb = nrb;
             if (i < 7) { nr0 = ld_res(i + 1, 0); nr1 = ld_res(i + 1, 1); na0 = ld_aux(i + 1, 0); na1 = ld_aux(i + 1, 1); }
-            if constexpr (kRA) { if (i < 7) { const int mc = min((int)mrow + 16 * (i + 1), M - 1); nra = ra_a[mc]; nrb = ra_b[mc]; } }
             float v0[8], v1[8];
 #define NT_PICK(I)                                                                                       \
     case I:                                                                                              \
@@ -428,10 +394,6 @@ __device__ __forceinline__ void nt_epilogue(f32x4 (&acc)[8][4], const ecgvit_gem
         break;
             switch (i) { NT_PICK(0) NT_PICK(1) NT_PICK(2) NT_PICK(3) NT_PICK(4) NT_PICK(5) NT_PICK(6) default: NT_PICK(7) }
 #undef NT_PICK
-            if constexpr (kRA) {   // (the bias add stays where it is in the heavy body: here fma + multiply = the same two instructions per element)
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { v0[k] = fmaf(v0[k], cra, crb * rag[k]); v1[k] = fmaf(v1[k], cra, crb * rag[8 + k]); }
-            }
             const uint32_t m = mrow + 16 * i, mm = mrowm + 16 * i;
             const bool mok = (int)m < M, mokm = (int)mm < M;
             nt_epi8<TO, FL, CAUX>(v0, bias, m, nb, mok && nok0, mm, nbm, mokm && nokm0, bf, e, to_acc(r0, want_res), to_acc_aux(a0, want_aux), cs, qmax);
@@ -464,18 +426,8 @@ __device__ __forceinline__ void nt_epilogue(f32x4 (&acc)[8][4], const ecgvit_gem
     }
 }
 
-#ifdef ECGVIT_TOOLS
-// diagnostics (tools build only): per block {s_memtime, s_memrealtime} at start and end, cycles summed over main loops and epilogues
-__device__ unsigned long long g_nt_stamps[256 * 8];
-// XCD rendezvous experiment (ablate bit 16): one arrival counter per XCD (own cache line), zeroed by the launcher
-__device__ unsigned int g_nt_rdv[8 * 32];
-#define NT_STAMP_T() (STAMP ? __builtin_amdgcn_s_memtime() : 0ull)
-#else
-#define NT_STAMP_T() 0ull
-#endif
-
-template <typename TO, int FL, bool STAMP = false, int OPS = 0, int CAUX = 0>
-__global__ __launch_bounds__(512, 2) void gemm_nt_kernel(ecgvit_gemm_desc d, EpiParams e, int tiles_m, int tiles_n, int ngroup, int nitems, int ablate) {
+template <typename TO, int FL, int OPS = 0, int CAUX = 0>
+__global__ __launch_bounds__(512, 2) void gemm_nt_kernel(ecgvit_gemm_desc d, EpiParams e, int tiles_m, int tiles_n, int ngroup, int nitems) {
     __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
     const int M = d.M, N = d.N;
     const int lane = threadIdx.x & 63;
@@ -499,7 +451,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(ecgvit_gemm_desc d, Epi
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(d.B), 0, (uint32_t)((int64_t)N * ldb2), 0x00020000);
     NtBufs bf;
     bf.ldc2 = (int)d.ldc * (int)sizeof(TO); bf.ldr2 = (int)e.ldr * 2; bf.ldx2 = (int)e.ldaux * ((FL >= 0 && (FL & ECGVIT_EPI_AUX8)) ? 1 : 2);   // (AUX8: the saved tensor is bytes)
-    bf.c = __builtin_amdgcn_make_buffer_rsrc(d.C, 0, ((STAMP && (ablate & 1)) || !d.C) ? 0u : (uint32_t)((int64_t)M * bf.ldc2), 0x00020000);   // ablate 1 (diagnostics): stores dropped
+    bf.c = __builtin_amdgcn_make_buffer_rsrc(d.C, 0, !d.C ? 0u : (uint32_t)((int64_t)M * bf.ldc2), 0x00020000);
     bf.res = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(e.residual), 0, e.residual ? (uint32_t)((int64_t)M * bf.ldr2) : 0u, 0x00020000);
     bf.aux = __builtin_amdgcn_make_buffer_rsrc(e.aux, 0, e.aux ? (uint32_t)((int64_t)M * bf.ldx2) : 0u, 0x00020000);
     bf.ldq = (int)d.ldq8;
@@ -522,7 +474,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(ecgvit_gemm_desc d, Epi
 
 #define R_DMA_A(h, ring, soff)                                                                                                   \
     do {                                                                                                                         \
-        if (STAMP && (ablate & 2) && dma_off) break;                                                                             \
         char *dst_ = smem + (3 * (h) + (ring)) * HALF_BYTES + wave * 2048;                                                       \
         const int so_ = (soff) + (h) * 128 * lda2;                                                                               \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lptr_t)dst_, 16, voA0, so_, 0, 0);                                        \
@@ -530,7 +481,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(ecgvit_gemm_desc d, Epi
     } while (0)
 #define R_DMA_B(h, ring, soff)                                                                                                   \
     do {                                                                                                                         \
-        if (STAMP && (ablate & 2) && dma_off) break;                                                                             \
         char *dst_ = smem + (6 + 2 * (h) + (ring)) * HALF_BYTES + wave * 2048;                                                   \
         const int so_ = (soff) + (h) * 128 * ldb2;                                                                               \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lptr_t)dst_, 16, voB0, so_, 0, 0);                                        \
@@ -594,7 +544,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(ecgvit_gemm_desc d, Epi
         }                                      \
     } while (0)
 
-    [[maybe_unused]] bool dma_off = false;   // diagnostics (stamped builds): ablate 2 = no DMA pieces after the prologue, 4 = no counted waits
     int cm0, cn0, nm0, nn0;
     decode_tile(it, ntile, tiles_m, tiles_n, ngroup, cm0, cn0);
     nm0 = cm0; nn0 = cn0;
@@ -604,7 +553,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(ecgvit_gemm_desc d, Epi
     bool a_ok = true, b_ok = true;
 #define R_ADV_A()                                                                                         \
     do {                                                                                                  \
-        if (STAMP && (ablate & 8) && dma_off) break;                                                      \
         if (++a_kt == nk) {                                                                               \
             a_kt = 0;                                                                                     \
             a_it += (int)gridDim.x;                                                                       \
@@ -614,7 +562,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(ecgvit_gemm_desc d, Epi
     } while (0)
 #define R_ADV_B()                                          \
     do {                                                   \
-        if (STAMP && (ablate & 8) && dma_off) break;       \
         if (++b_kt == nk) {                                \
             b_kt = 0;                                      \
             b_it += (int)gridDim.x;                        \
@@ -636,7 +583,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(ecgvit_gemm_desc d, Epi
     }
     __builtin_amdgcn_s_barrier();
 
-    dma_off = true;
     int ga = 0, gb = 0;   // ring slots of the K-tile being multiplied
     bool pre = false;     // the coming K-tile's DMA pieces were issued ahead of the previous tile's epilogue
     // VMEM instructions the epilogue leaves in flight at least: its output stores (masked lanes still issue)
@@ -647,32 +593,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(ecgvit_gemm_desc d, Epi
     // per column half, or 32 for its first four row steps) spills in its main loop AND in its epilogue: not built in
     constexpr bool kAuxPre = OPS == 0 && sizeof(TO) == 2 && FL >= 0 && (FL & ECGVIT_EPI_MUL_AUX) && (FL & ECGVIT_EPI_AUX8) && !(FL & (ECGVIT_EPI_GELU | ECGVIT_EPI_GELU_BWD));
     constexpr int NAUXPRE = kAuxPre ? 16 : 0;
-    [[maybe_unused]] unsigned long long st_t0 = 0, st_r0 = 0, st_main = 0, st_epi = 0, st_ntile = 0;
-#ifdef ECGVIT_TOOLS
-    if constexpr (STAMP) { st_t0 = __builtin_amdgcn_s_memtime(); st_r0 = __builtin_amdgcn_s_memrealtime(); }
-#endif
-    [[maybe_unused]] unsigned int rdv_cum = 0;
-    [[maybe_unused]] int rdv_round = 0;
     for (;;) {
-#ifdef ECGVIT_TOOLS
-        if constexpr (STAMP) {
-            if (ablate & 16) {
-                // experiment: the workgroups of an XCD (blockIdx & 7) start every tile round together -- their K-tiles then
-                // march through the shared activation / weight panels in step, and a panel slice fetched by one is an L2 hit for the others
-                const int x = blockIdx.x & 7, left = nitems - rdv_round * (int)gridDim.x;   // items of this round: blocks b < left take one
-                const int nb = left >= (int)gridDim.x ? (int)gridDim.x / 8 : (left > x ? (left - x + 7) / 8 : 0);
-                rdv_cum += (unsigned int)nb;
-                if (threadIdx.x == 0) {
-                    atomicAdd(&g_nt_rdv[x * 32], 1u);
-                    int spins = 0;
-                    while (__hip_atomic_load(&g_nt_rdv[x * 32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < rdv_cum && ++spins < 20000) __builtin_amdgcn_s_sleep(1);
-                }
-                ++rdv_round;
-                __builtin_amdgcn_s_barrier();
-            }
-        }
-#endif
-        [[maybe_unused]] const unsigned long long st_a = NT_STAMP_T();
         f32x4 acc[8][4];
 #pragma unroll
         for (int i = 0; i < 8; ++i)
@@ -704,8 +625,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(ecgvit_gemm_desc d, Epi
             // 1-4 of the next K-tile, the trailing group in quadrant 4 of this one and 1-3 of the next.
 #define R_BAR()                                                                  \
     do {                                                                         \
-        if (STAMP && (ablate & 6)) { }                                           \
-        else if (a_iss) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");         \
+        if (a_iss) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");              \
         else if (pre_k) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 + NST + NAUXPRE) : "memory"); \
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                    \
         __builtin_amdgcn_sched_barrier(0);                                       \
@@ -788,24 +708,13 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(ecgvit_gemm_desc d, Epi
                 pre = true;
             }
         };
-        [[maybe_unused]] const unsigned long long st_b = NT_STAMP_T();
         if constexpr (kAuxPre) nt_epilogue<TO, FL, CAUX>(acc, d, e, bf, cm0, cn0, wave, lane, issue_next, auxpre);
         else nt_epilogue<TO, FL, CAUX>(acc, d, e, bf, cm0, cn0, wave, lane, issue_next);
-        if constexpr (STAMP) { st_main += st_b - st_a; st_epi += NT_STAMP_T() - st_b; ++st_ntile; }
         if (!has_next) break;
         it = next_it;
         if (a_it == it) { cm0 = nm0; cn0 = nn0; }                     // the producer cursor already decoded this item
         else decode_tile(it, ntile, tiles_m, tiles_n, ngroup, cm0, cn0);
     }
-#ifdef ECGVIT_TOOLS
-    if constexpr (STAMP) {
-        if (threadIdx.x == 0) {
-            unsigned long long *o = g_nt_stamps + blockIdx.x * 8;
-            o[0] = st_t0; o[1] = st_r0; o[2] = __builtin_amdgcn_s_memtime(); o[3] = __builtin_amdgcn_s_memrealtime();
-            o[4] = st_main; o[5] = st_epi; o[6] = st_ntile; o[7] = (unsigned long long)nk;
-        }
-    }
-#endif
 #undef R_DMA_A
 #undef R_DMA_B
 #undef R_PHASE_SYNC_A
@@ -834,8 +743,8 @@ __device__ __forceinline__ void q4_static_for(F &&f) { q4_static_for_impl(std::m
 // front-loaded one per four MFMAs: 0-3 % slower.)
 __device__ constexpr int q4_read_at(int x) { return (x & 3) == 1 ? x >> 2 : -1; }
 __device__ constexpr int q4_dma_at(int x) { return (x & 7) == 3 ? x >> 3 : -1; }
-template <typename TO, int FL, int CAUX = 0, bool STAMP = false>
-__global__ __launch_bounds__(256, 1) void gemm_nt_kernel_4w(ecgvit_gemm_desc d, EpiParams e, int tiles_m, int tiles_n, int ngroup, int nitems, int ablate) {
+template <typename TO, int FL, int CAUX = 0>
+__global__ __launch_bounds__(256, 1) void gemm_nt_kernel_4w(ecgvit_gemm_desc d, EpiParams e, int tiles_m, int tiles_n, int ngroup, int nitems) {
     __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
     e.alpha = 1.f;   // (the launcher takes alpha == 1 only: the epilogue's scaling branch folds away)
     const int M = d.M, N = d.N;
@@ -851,7 +760,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_kernel_4w(ecgvit_gemm_desc d, 
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(d.B), 0, (uint32_t)((int64_t)N * ldb2), 0x00020000);
     NtBufs bf;
     bf.ldc2 = (int)d.ldc * (int)sizeof(TO); bf.ldr2 = (int)e.ldr * 2; bf.ldx2 = (int)e.ldaux * 2;
-    bf.c = __builtin_amdgcn_make_buffer_rsrc(d.C, 0, (STAMP && (ablate & 1)) ? 0u : (uint32_t)((int64_t)M * bf.ldc2), 0x00020000);   // ablate 1: stores dropped
+    bf.c = __builtin_amdgcn_make_buffer_rsrc(d.C, 0, (uint32_t)((int64_t)M * bf.ldc2), 0x00020000);
     bf.res = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(e.residual), 0, e.residual ? (uint32_t)((int64_t)M * bf.ldr2) : 0u, 0x00020000);
     bf.aux = __builtin_amdgcn_make_buffer_rsrc(e.aux, 0, e.aux ? (uint32_t)((int64_t)M * bf.ldx2) : 0u, 0x00020000);
     bf.ldq = 0; bf.q8 = bf.aux; bf.q8_bf8 = false; bf.q8_inv = 0.f;
@@ -964,12 +873,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_kernel_4w(ecgvit_gemm_desc d, 
     constexpr int NST = 2 * (sizeof(TO) == 2 ? 16 : 32) + ((FL & ECGVIT_EPI_RESIDUAL) ? 16 : 0) + ((FL & ECGVIT_EPI_MUL_AUX) ? 16 : 0);
     static_assert(FL >= 0 && !(FL & (ECGVIT_EPI_GELU | ECGVIT_EPI_GELU_BWD | ECGVIT_EPI_ACCUM | ECGVIT_EPI_QUANT_OUT)) && 8 + NST <= 63, "light bodies only");
     constexpr bool kRoll = (FL & ECGVIT_EPI_MUL_AUX) != 0;
-    [[maybe_unused]] unsigned long long st_t0 = 0, st_r0 = 0, st_main = 0, st_epi = 0, st_ntile = 0;
-#ifdef ECGVIT_TOOLS
-    if constexpr (STAMP) { st_t0 = __builtin_amdgcn_s_memtime(); st_r0 = __builtin_amdgcn_s_memrealtime(); }
-#endif
     for (;;) {
-        [[maybe_unused]] const unsigned long long st_a = NT_STAMP_T();
         f32x4 acc[2][8][4];
 #pragma unroll
         for (int g = 0; g < 2; ++g)
@@ -1020,17 +924,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_kernel_4w(ecgvit_gemm_desc d, 
             Q_DMA_A(0, gaf, a_base + a_kt * (BK * 2)); Q_DMA_A(1, gaf, a_base + a_kt * (BK * 2)); Q_ADV_A();
         };
         auto none = [&]() __attribute__((always_inline)) {};
-        [[maybe_unused]] const unsigned long long st_b = NT_STAMP_T();
-        if (STAMP && (ablate & 2)) {   // ablate 2: no epilogue at all (the accumulators are consumed by one dummy store)
-            float sum = 0.f;
-#pragma unroll
-            for (int g = 0; g < 2; ++g)
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) sum += acc[g][i][j][0];
-            if (sum == 12345.678f) reinterpret_cast<float *>(d.C)[lane] = sum;
-        } else {
         // (the epilogue's lane-derived offsets from a fresh lane id, per tile: hoisted out of the tile loop they are
         // spilled, and the reload's `s_waitcnt vmcnt(0)` would wait for the pieces just issued)
         int eln;
@@ -1038,8 +931,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_kernel_4w(ecgvit_gemm_desc d, 
         bf.t_out = ((eln >> 2) + 16 * (eln & 3)) << 2;
         nt_epilogue<TO, FL, CAUX, kRoll>(acc[0], d, e, bf, cm0, cn0, 4 * wm + 2 * wn, eln, issue_next);
         nt_epilogue<TO, FL, CAUX, kRoll>(acc[1], d, e, bf, cm0, cn0, 4 * wm + 2 * wn + 1, eln, none);
-        }
-        if constexpr (STAMP) { st_main += st_b - st_a; st_epi += NT_STAMP_T() - st_b; ++st_ntile; }
         if (!has_next) break;
         it = next_it;
         decode_tile(it, ntile, tiles_m, tiles_n, ngroup, cm0, cn0);
@@ -1049,15 +940,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_kernel_4w(ecgvit_gemm_desc d, 
     // nothing of this wave's may still be on its way into LDS when the workgroup's allocation is released (the cursors keep issuing
     // pieces past the end of the share)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef ECGVIT_TOOLS
-    if constexpr (STAMP) {
-        if (threadIdx.x == 0) {
-            unsigned long long *o = g_nt_stamps + blockIdx.x * 8;
-            o[0] = st_t0; o[1] = st_r0; o[2] = __builtin_amdgcn_s_memtime(); o[3] = __builtin_amdgcn_s_memrealtime();
-            o[4] = st_main; o[5] = st_epi; o[6] = st_ntile; o[7] = (unsigned long long)nk;
-        }
-    }
-#endif
 #undef Q_DMA_A
 #undef Q_DMA_B
 #undef Q_ADV_A
@@ -1114,20 +996,12 @@ bool ecgvit_gemm_nt_applicable(const ecgvit_gemm_desc *d) {
 
 void ecgvit_colsum_reduce_launch(const float *partial, int nparts, int N, float *out, hipStream_t s);   // gemm_wgrad.hip
 
-int ecgvit_gemm_nt4w_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g, int diag);
+int ecgvit_gemm_nt4w_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g, bool nt_stores);
 // argument validation is done by the caller (ecgvit_gemm_bf16_launch); raster_g <= 0 selects the built-in choice
-int ecgvit_gemm_nt_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g, int diag) {
-#ifdef ECGVIT_TOOLS
-    {   // tools build only: whole-step A/B of the diag bits (bench.py under ECGVIT_HIP_LIB=libecgvit_hip_tools.so)
-        static const int env_diag = [] { const char *e = getenv("ECGVIT_NT_DIAG"); return e ? atoi(e) : 0; }();
-        static const int env_g = [] { const char *e = getenv("ECGVIT_NT_G"); return e ? atoi(e) : 0; }();
-        diag |= env_diag;
-        if (raster_g == 0) raster_g = env_g;
-    }
-#endif
+int ecgvit_gemm_nt_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g) {
     const int tiles_m = (d->M + BM - 1) / BM, tiles_n = (d->N + BN - 1) / BN, ntile = tiles_m * tiles_n;
     // Built-in tile walk: column groups of 6 n-tiles (m-major inside a group).  Measured inside the train step against the plain
-    // n-fastest order (tools/pmc_step_raster.sh, tools/ab_bench.sh ECGVIT_NT_G): the same step time (+-0.02 %) with 13 % fewer bytes
+    // n-fastest order (profiles/r02_raster_step.txt): the same step time (+-0.02 %) with 13 % fewer bytes
     // fetched from beyond L2 per launch (1.08 -> 0.94 GB); groups of 3 fetch 0.97 GB at -0.1 %, groups of 4 cost 0.6 % of the step.
     // Up to 8 n-tiles (N <= 2048: the FFN-wide products of EcgVit-small) stay ONE group -- a 6 + 2 split costs that step 0.9 % (round 4).
     const int G = raster_g > 0 ? std::min(raster_g, tiles_n) : nt_default_group(tiles_n);
@@ -1139,50 +1013,14 @@ int ecgvit_gemm_nt_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g
     constexpr int F_LIN = ECGVIT_EPI_BIAS | ECGVIT_EPI_RESIDUAL;
     constexpr int F_UP = ECGVIT_EPI_BIAS | ECGVIT_EPI_GELU | ECGVIT_EPI_GELU_GRAD_AUX;
     constexpr int F_DH = ECGVIT_EPI_MUL_AUX | ECGVIT_EPI_COLSUM;
-#define NT_LAUNCH(TO, FL) hipLaunchKernelGGL((gemm_nt_kernel<TO, FL>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile, 0)
-#ifdef ECGVIT_TOOLS
-    if ((diag & 1) && d->out_dtype == ECGVIT_BF16) {   // stamped diagnostic instantiations; diag & 2: output stores dropped
-        const int ab = (diag >> 1) & 31;   // ablate bits: 1 stores dropped, 2 no DMA after the prologue, 4 no counted waits, 8 operand cursors frozen, 16 XCD rendezvous per tile round
-        if (ab & 16) {
-            void *p = nullptr;
-            if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_nt_rdv)) != hipSuccess || hipMemsetAsync(p, 0, sizeof(unsigned int) * 8 * 32, s) != hipSuccess) return ECGVIT_ELAUNCH;
-        }
-        if (fl == 0) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, 0, true>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile, ab);
-        else if (fl == (F_UP | ECGVIT_EPI_DROPOUT)) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, F_UP | ECGVIT_EPI_DROPOUT, true>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile, ab);
-        else if (fl == F_DH) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, F_DH, true>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile, ab);
-        else return ECGVIT_EINVAL;
-        ECGVIT_CHECK_LAUNCH();
-        return ECGVIT_OK;
-    }
-#endif
-#define NT_LAUNCH8(FL, OPS) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, FL, false, OPS>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile, 0)
-#ifdef ECGVIT_TOOLS
-    if ((diag & 1024) && d->dtype == ECGVIT_BF16 && d->out_dtype == ECGVIT_BF16) {   // LayerNorm-fold pricing (ECGVIT_EPI_ROWAFFINE_X): QKV forward / FFN-up forward bodies
-        constexpr int RA = ECGVIT_EPI_ROWAFFINE_X;
-        if (fl == ECGVIT_EPI_BIAS) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, ECGVIT_EPI_BIAS | RA, false, 0, 2>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile, 0);
-        else if (fl == (F_UP | ECGVIT_EPI_DROPOUT | ECGVIT_EPI_AUX8)) NT_LAUNCH(bf16_t, F_UP | ECGVIT_EPI_DROPOUT | ECGVIT_EPI_AUX8 | RA);
-        else return ECGVIT_EINVAL;
-        ECGVIT_CHECK_LAUNCH();
-        return ECGVIT_OK;
-    }
-    if ((diag & 64) && fl == 0 && d->dtype == ECGVIT_FP8_E4M3) { NT_LAUNCH8(0, 1); ECGVIT_CHECK_LAUNCH(); return ECGVIT_OK; }   // plain fp8 MFMA (A/B)
-#endif
+#define NT_LAUNCH(TO, FL) hipLaunchKernelGGL((gemm_nt_kernel<TO, FL>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile)
+#define NT_LAUNCH8(FL, OPS) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, FL, OPS>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile)
     // plain 8-bit products whose bf16 output does not fit the 256-MB Infinity Cache (EcgVit-large: the QKV forward's 788 MB) store it non-temporally, as
     // the bf16 QKV forward does since round 3: written through L2 the output evicts the operand panels the tile's neighbours are about to re-read
-    // (tools/fp8_nt_ab.py at 256 x 501 token rows, default -> non-temporal: QKV forward K = 1024, 752 MB: 403.8 -> 350.5 us; the 250-MB outputs: K = 1024
+    // (profiles/r06_fp8_nt_stores.txt at 256 x 501 token rows, default -> non-temporal: QKV forward K = 1024, 752 MB: 403.8 -> 350.5 us; the 250-MB outputs: K = 1024
     // 145.5 -> 133.8, K = 3072 323.0 -> 338.1, K = 4096 411.8 -> 422.9: a long main loop re-reads its panels from L2 often enough to want the cache's help)
-    [[maybe_unused]] bool nt8 = (int64_t)d->M * d->N * 2 > (320ll << 20) || ((int64_t)d->M * d->N * 2 > (240ll << 20) && d->K <= 1024);
-#ifdef ECGVIT_TOOLS
-    if (diag & 256) nt8 = false;   // A/B: bit 256 = default-policy stores, 512 = non-temporal stores, whatever the size
-    if (diag & 512) nt8 = true;
-#endif
-#ifdef ECGVIT_AB_NO_NT8
-    nt8 = false;   // (A/B builds only: tools/ab_bench.sh --hip-lib)
-#endif
-#ifdef ECGVIT_AB_NT8_BIG_ONLY
-    nt8 = (int64_t)d->M * d->N * 2 > (320ll << 20);
-#endif
-#define NT_LAUNCH8_NT(OPS) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, 0, false, OPS, 2>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile, 0)
+    const bool nt8 = (int64_t)d->M * d->N * 2 > (320ll << 20) || ((int64_t)d->M * d->N * 2 > (240ll << 20) && d->K <= 1024);
+#define NT_LAUNCH8_NT(OPS) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, 0, OPS, 2>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile)
     if (d->dtype == ECGVIT_FP8_E4M3) {          // forward products: e4m3 activations x e4m3 weights
         switch (fl) {
             case 0: if (nt8) NT_LAUNCH8_NT(3); else NT_LAUNCH8(0, 3); break;
@@ -1222,32 +1060,16 @@ int ecgvit_gemm_nt_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g
             // evict the operand panels the tile's neighbours are about to re-read (main loop 3,020 -> 2,620 cycles per K-tile, launch
             // -6...-10 %); smaller outputs (197 MB) are absorbed by the cache and nt costs them 2-3 % (profiles/r03_gemm_4w.txt)
             const bool big_out = (int64_t)d->M * d->N * 2 > (256ll << 20);
-#ifdef ECGVIT_TOOLS
-            // A/B: ECGVIT_NT_NO4W (whole step) or diag bits 128 / 256 / 512 (one launch): 1 = eight-wave body everywhere, 2 = no nt stores, 4 = nt stores everywhere
-            static const int env_no4w = [] { const char *e_ = getenv("ECGVIT_NT_NO4W"); return e_ ? atoi(e_) : 0; }();
-            const int no4w = env_no4w | ((diag >> 7) & 7);
-            const bool use4w = !(no4w & 1), use_nt = (big_out && !(no4w & 2)) || (no4w & 4);
-#else
-            const bool use4w = true, use_nt = big_out;
-#endif
-            if (use4w && d->K >= 1536 && e.alpha == 1.f && !d->scale_a && !d->scale_b) return ecgvit_gemm_nt4w_launch(d, s, raster_g, use_nt ? 2 : 0);
-            if (use_nt) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, 0, false, 0, 2>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile, 0);
+            if (d->K >= 1536 && e.alpha == 1.f && !d->scale_a && !d->scale_b) return ecgvit_gemm_nt4w_launch(d, s, raster_g, big_out);
+            if (big_out) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, 0, 0, 2>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile);
             else NT_LAUNCH(bf16_t, 0);
             ECGVIT_CHECK_LAUNCH();
             return ECGVIT_OK;
         }
         // the two residual launches (bias + residual [+ dropout]: attn-out and FFN-down forward) with K >= 768: the four-wave body as well --
         // its shorter main loop outweighs the one-wave epilogue (launch -2 % at K = 768, -3 % at K = 3072; step +0.2...0.3 %)
-        {
-#ifdef ECGVIT_TOOLS
-            static const int env_no4w = [] { const char *e_ = getenv("ECGVIT_NT_NO4W"); return e_ ? atoi(e_) : 0; }();
-            const bool use4w = !((env_no4w | (diag >> 7)) & 1);
-#else
-            const bool use4w = true;
-#endif
-            if (use4w && (fl & ~ECGVIT_EPI_DROPOUT) == F_LIN && d->K >= 768 && e.alpha == 1.f && !d->scale_a && !d->scale_b)
-                return ecgvit_gemm_nt4w_launch(d, s, raster_g, 0);
-        }
+        if ((fl & ~ECGVIT_EPI_DROPOUT) == F_LIN && d->K >= 768 && e.alpha == 1.f && !d->scale_a && !d->scale_b)
+            return ecgvit_gemm_nt4w_launch(d, s, raster_g, false);
         switch (fl) {
             case ECGVIT_EPI_BIAS: NT_LAUNCH(bf16_t, ECGVIT_EPI_BIAS); break;   // the masked objective's pixel head
             case F_LIN: NT_LAUNCH(bf16_t, F_LIN); break;
@@ -1275,9 +1097,9 @@ int ecgvit_gemm_nt_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g
     return ECGVIT_OK;
 }
 
-// the four-wave body (bf16 products, plain or bias + residual [+ dropout], alpha 1; persistent grid or dispatcher-balanced chunks); diag: 2 = non-temporal output stores (plain); tools build: 1 = stamped
-// instantiation with ablate bits (diag >> 2: 1 stores dropped, 2 no epilogue)
-int ecgvit_gemm_nt4w_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g, int diag) {
+// the four-wave body (bf16 products, plain or bias + residual [+ dropout], alpha 1; persistent grid or dispatcher-balanced chunks); nt_stores: non-temporal
+// output stores (plain products only)
+int ecgvit_gemm_nt4w_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g, bool nt_stores) {
     const EpiParams e = make_epi(d);
     constexpr int F_LIN = ECGVIT_EPI_BIAS | ECGVIT_EPI_RESIDUAL;
     const int fl = d->epilogue;
@@ -1289,20 +1111,12 @@ int ecgvit_gemm_nt4w_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster
     const int G = raster_g > 0 ? std::min(raster_g, tiles_n) : nt_default_group(tiles_n);
     const int tpw = d->tiles_per_workgroup;   // > 0: dispatcher-balanced chunks of ~tpw tiles, as in ecgvit_gemm_nt_launch
     const dim3 grid((unsigned)(tpw > 0 ? std::max(std::min(ntile, 256), (ntile + tpw - 1) / tpw) : std::min(ntile, 256))), block(256);
-#define NT4W_GO(FL, CAUX, ST, AB) hipLaunchKernelGGL((gemm_nt_kernel_4w<bf16_t, FL, CAUX, ST>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile, AB)
-#ifdef ECGVIT_TOOLS
-    if ((diag & 1) && fl == 0) {
-        if (diag & 2) NT4W_GO(0, 2, true, (diag >> 2) & 3);
-        else NT4W_GO(0, 0, true, (diag >> 2) & 3);
-        ECGVIT_CHECK_LAUNCH();
-        return ECGVIT_OK;
-    }
-#endif
-    if (fl == F_LIN) NT4W_GO(F_LIN, 0, false, 0);
-    else if (fl == (F_LIN | ECGVIT_EPI_DROPOUT)) NT4W_GO(F_LIN | ECGVIT_EPI_DROPOUT, 0, false, 0);
-    else if (fl == F_DH) NT4W_GO(F_DH, 0, false, 0);
-    else if (diag & 2) NT4W_GO(0, 2, false, 0);
-    else NT4W_GO(0, 0, false, 0);
+#define NT4W_GO(FL, CAUX) hipLaunchKernelGGL((gemm_nt_kernel_4w<bf16_t, FL, CAUX>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile)
+    if (fl == F_LIN) NT4W_GO(F_LIN, 0);
+    else if (fl == (F_LIN | ECGVIT_EPI_DROPOUT)) NT4W_GO(F_LIN | ECGVIT_EPI_DROPOUT, 0);
+    else if (fl == F_DH) NT4W_GO(F_DH, 0);
+    else if (nt_stores) NT4W_GO(0, 2);
+    else NT4W_GO(0, 0);
 #undef NT4W_GO
     ECGVIT_CHECK_LAUNCH();
     if (fl & ECGVIT_EPI_COLSUM) {
@@ -1312,26 +1126,3 @@ int ecgvit_gemm_nt4w_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster
     return ECGVIT_OK;
 }
 
-#ifdef ECGVIT_TOOLS
-extern "C" int ecgvit_tools_rowaffine(const float *row_a, const float *row_b, const float *col_g) {   // operands of the LayerNorm-fold pricing bodies
-    return (hipMemcpyToSymbol(HIP_SYMBOL(g_ra_a), &row_a, sizeof(row_a)) == hipSuccess && hipMemcpyToSymbol(HIP_SYMBOL(g_ra_b), &row_b, sizeof(row_b)) == hipSuccess &&
-            hipMemcpyToSymbol(HIP_SYMBOL(g_ra_g), &col_g, sizeof(col_g)) == hipSuccess) ? ECGVIT_OK : ECGVIT_ELAUNCH;
-}
-// stand-in for a collective's kernel: n workgroups that each hold a whole CU (all of its LDS) for `cycles` shader cycles
-__global__ __launch_bounds__(64) void tools_occupy_kernel(unsigned long long cycles, unsigned int *done) {
-    __shared__ char hold[LDS_BYTES];
-    hold[threadIdx.x] = 1;
-    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-    while (__builtin_amdgcn_s_memtime() - t0 < cycles) __builtin_amdgcn_s_sleep(32);
-    if (threadIdx.x == 0 && hold[0]) atomicAdd(done, 1u);
-}
-extern "C" int ecgvit_tools_occupy(int n_cus, unsigned long long cycles, unsigned int *done, void *stream) {
-    hipLaunchKernelGGL(tools_occupy_kernel, dim3(n_cus), dim3(64), 0, as_stream(stream), cycles, done);
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
-}
-
-extern "C" int ecgvit_tools_nt_stamps(unsigned long long *h_out) {   // host buffer of 256*8 words
-    return hipMemcpyFromSymbol(h_out, HIP_SYMBOL(g_nt_stamps), sizeof(unsigned long long) * 256 * 8) == hipSuccess ? ECGVIT_OK : ECGVIT_ELAUNCH;
-}
-#endif

@@ -1,12 +1,11 @@
 // Weight-gradient products dW = dY^T . X for the Linear layers (C = A^T . B, both operands k-major: A[K, M], B[K, N] row-major with
-// K = token rows): 256 x 256 x 64 block tile, 8 waves (2 x 4, wave tile 128 x 64), v_mfma_f32_32x32x16_bf16, split-K over the token
+// K = token rows): 256 x 256 x 64 block tile, 4 waves (2 x 2, wave tile 128 x 128), v_mfma_f32_32x32x16_bf16, split-K over the token
 // rows with f32 slabs + a deterministic reduce.
 //
-// gemm_wgrad_kernel: one (K-slice, tile) item per block; operands stream HBM -> LDS by LDS-DMA (`buffer_load ... lds`, no VGPR
+// gemm_wgrad_kernel_4w: one (K-slice, tile) item per block; operands stream HBM -> LDS by LDS-DMA (`buffer_load ... lds`, no VGPR
 // staging): A tiles ([64 k][256 m], 32 KiB) two K-tiles ahead in a 3-slot ring, B tiles one ahead in 2 slots (5 x 32 KiB = all of
-// LDS); a K-tile = four 16-deep phases (12 transposed `ds_read_b64_tr_b16` fragment reads + 2 DMA pieces | 8 MFMAs), ONE counted
-// vmcnt(4) per K-tile, waves 4-7 one barrier behind waves 0-3 (ping-pong per SIMD).  K-slices are pinned to XCDs (slice counts that
-// are multiples of 8) or laid out XCD-contiguously, so a slice's operand rows live in one L2.
+// LDS); ONE counted vmcnt and ONE workgroup barrier per K-tile.  K-slices are pinned to XCDs (slice counts that are multiples of 8) or
+// laid out XCD-contiguously, so a slice's operand rows live in one L2.
 // LDS image of a k-major operand: [64 k][256 mn] (512-B rows), 16-B chunk ^= (k&3)<<2 (applied to the per-lane SOURCE address: the
 // DMA destination is wave-uniform base + lane*16) -- the 4 k-rows of one transposed half-wave read land on the 4 distinct 64-B
 // quarters of the bank row.  Rows beyond a slice's end fall outside the buffer descriptor and read as zero.
@@ -14,7 +13,6 @@
 // Also here: the column-sum reducer shared with gemm_nt.hip's EPI_COLSUM.
 #include "common.h"
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 
@@ -26,69 +24,6 @@ constexpr int CS_LD = 68, CS_WAVE_BYTES = 64 * CS_LD * 4;  // 17408: per-wave ep
 constexpr int LDS_BYTES = 163840;                          // all of LDS: 3 A + 2 B tiles; the epilogue patches need 139264
 
 typedef __attribute__((address_space(3))) void *lptr_t;
-
-// ---- fast DMA path: buffer_load ... lds with a per-lane byte offset computed ONCE per output tile and the K advance in
-// the scalar offset -> zero VALU per piece (the generic path above spends ~15 VALU ops + a 64-bit address per piece).
-// Out-of-range rows fall beyond the descriptor's num_records and read as zero (hardware bounds check), so no clamping.
-// Valid when no piece can straddle a row end: K % 64 == 0 for K-contiguous operands, MN % 256 == 0 for k-major ones.
-typedef int v4i32 __attribute__((ext_vector_type(4)));
-struct FastOp {
-    __amdgpu_buffer_rsrc_t rsrc;
-    int voff[4];
-};
-template <bool KC>
-__device__ __forceinline__ FastOp fast_setup(const bf16_t *P, int64_t ld, int mn0, int MN, int kend, int wave, int lane) {
-    FastOp f;
-    // k-major operands: rows >= kend (the split's end) must read as zero -> shrink the descriptor to kend rows
-    const uint32_t bytes = KC ? (uint32_t)((int64_t)MN * ld * 2) : (uint32_t)((int64_t)kend * ld * 2);
-    f.rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)P, 0, bytes, 0x00020000);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int j = wave * 4 + i;
-        if constexpr (KC) {
-            const int r = j * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ ((r >> 1) & 7);
-            f.voff[i] = (int)(((int64_t)(mn0 + r) * ld + c * 8) * 2);
-        } else {
-            const int kr = j * 2 + (lane >> 5);
-            const int c = (lane & 31) ^ ((kr & 3) << 2);
-            f.voff[i] = (int)(((int64_t)kr * ld + mn0 + c * 8) * 2);
-        }
-    }
-    return f;
-}
-template <bool KC, int I0 = 0, int I1 = 4>
-__device__ __forceinline__ void fast_dma(const FastOp &f, int64_t ld, int k0, char *tile, int wave) {
-    const int soff = KC ? k0 * 2 : (int)((int64_t)k0 * ld * 2);
-#pragma unroll
-    for (int i = I0; i < I1; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(f.rsrc, (lptr_t)(tile + (wave * 4 + i) * 1024), 16, f.voff[i], soff, 0, 0);
-}
-
-// fragment: element j of lane (r = lane&31, h = lane>>5) = X[mn = base + r][k = 16*ks + 8h + j]
-template <bool KC> __device__ __forceinline__ bf16x8 frag(const char *tile, int mn_base, int ks, int lane) {
-    if constexpr (KC) {
-        const int row = mn_base + (lane & 31);
-        return *reinterpret_cast<const bf16x8 *>(tile + row * 128 + (((ks * 2 + (lane >> 5)) ^ ((row >> 1) & 7)) << 4));
-    } else {
-        const int g = lane >> 4, i = lane & 15;
-        const int colb = (mn_base + (g & 1) * 16 + (i & 3) * 4) * 2;
-        const int k = ks * 16 + (g >> 1) * 8 + (i >> 2);  // k and k+4 share (k&3)
-        const char *p = tile + k * 512 + (colb ^ ((k & 3) << 6));
-        // Inline asm, not the builtin: with an LDS-DMA in flight hipcc's waitcnt pass cannot prove that the builtin's read does not
-        // alias the DMA's destination and drains vmcnt(0) in front of it -- which serialised every K-tile's prefetch of the k-major
-        // layouts (found in the ISA: `s_waitcnt vmcnt(0)` right after the 8 `buffer_load ... lds` of a phase).  Every caller already
-        // orders these reads by hand (s_waitcnt lgkmcnt(0) + sched_barrier before the consuming MFMAs / the barrier).
-        const uint32_t pa = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)p;
-        bf16x4 lo, hi;
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(pa) : "memory");
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "=v"(hi) : "v"(pa) : "memory");
-        const u32x2 ul = __builtin_bit_cast(u32x2, lo), uh = __builtin_bit_cast(u32x2, hi);
-        u32x4 u;
-        u[0] = ul[0]; u[1] = ul[1]; u[2] = uh[0]; u[3] = uh[1];
-        return __builtin_bit_cast(bf16x8, u);
-    }
-}
 
 __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
     const int q = nblk >> 3, r = nblk & 7, x = bid & 7, j = bid >> 3;
@@ -239,121 +174,12 @@ __device__ __forceinline__ void epilogue_store(f32x16 (&acc)[4][2], char *smem, 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Weight-gradient kernel ("TQ": both operands k-major, split-K): the Q kernel's streaming discipline on the k-major images.
-// One (K-slice, tile) item per block; A tiles ([64 k][256 m], 32 KiB) two K-tiles ahead in a 3-slot ring, B tiles one ahead in
-// 2 slots (5 x 32 KiB = all of LDS); a K-tile = four 16-deep phases (12 transposed reads + 2 DMA pieces | 8 MFMAs of 32x32x16),
-// one counted vmcnt(4) per K-tile, waves 4-7 one barrier behind waves 0-3.  The whole-tile schedule it replaces drained
-// vmcnt(0) once per K-tile and wave half (64 KiB in flight at most): both operands of this layout are pure HBM streams.
-template <typename TO>
-__global__ __launch_bounds__(512, 2) void gemm_wgrad_kernel(ecgvit_gemm_desc d, EpiParams e, SplitK2 sk, int tiles_m, int tiles_n) {
-    __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
-    const int ntile = tiles_m * tiles_n;
-    int split, tid;
-    if (sk.splits > 1 && (sk.splits & 7) == 0) {
-        const int r = sk.splits >> 3, x = blockIdx.x & 7, q = blockIdx.x >> 3;
-        split = x + 8 * (q % r);
-        tid = q / r;
-    } else if (sk.splits > 1) {
-        const int gid = xcd_remap(blockIdx.x, ntile * sk.splits);
-        split = gid / ntile;
-        tid = gid - split * ntile;
-    } else {
-        split = 0;
-        tid = xcd_remap(blockIdx.x, ntile);
-    }
-    const int tm = tid / tiles_n, tn = tid - tm * tiles_n;
-    const int m0 = tm * BM, n0 = tn * BN;
-    const int kbeg = split * sk.k_per_split;
-    const int kend = min(d.K, kbeg + sk.k_per_split);
-    const int nk = (kend - kbeg + BK - 1) / BK;
-    const bf16_t *A = reinterpret_cast<const bf16_t *>(d.A);
-    const bf16_t *B = reinterpret_cast<const bf16_t *>(d.B);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const bool late = wm == 1;
-
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const FastOp fa = fast_setup<false>(A, d.lda, m0, d.M, kend, wave, lane);
-    const FastOp fb = fast_setup<false>(B, d.ldb, n0, d.N, kend, wave, lane);
-    char *const ringA = smem, *const ringB = smem + 3 * TILE_BYTES;
-    // prologue: A(0), B(0), A(1)
-    fast_dma<false>(fa, d.lda, kbeg, ringA, wave);
-    fast_dma<false>(fb, d.ldb, kbeg, ringB, wave);
-    if (nk > 1) {
-        fast_dma<false>(fa, d.lda, kbeg + BK, ringA + TILE_BYTES, wave);
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    if (late) __builtin_amdgcn_s_barrier();
-
-    int ga = 0, gb = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        const char *sa = ringA + ga * TILE_BYTES;
-        const char *sb = ringB + gb * TILE_BYTES;
-        char *nA = ringA + (ga == 0 ? 2 : ga - 1) * TILE_BYTES;   // slot of K-tile kt+2
-        char *nB = ringB + (gb ^ 1) * TILE_BYTES;                 // slot of K-tile kt+1
-        const bool b_ok = kt + 1 < nk, a_ok = kt + 2 < nk;
-        const int kB = kbeg + (kt + 1) * BK, kA = kbeg + (kt + 2) * BK;
-#pragma unroll
-        for (int ks = 0; ks < BK / 16; ++ks) {
-            bf16x8 a[4], b[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) b[j] = frag<false>(sb, wn * 64 + j * 32, ks, lane);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a[i] = frag<false>(sa, wm * 128 + i * 32, ks, lane);
-            if (ks == 0) { if (b_ok) fast_dma<false, 0, 2>(fb, d.ldb, kB, nB, wave); }
-            else if (ks == 1) { if (b_ok) fast_dma<false, 2, 4>(fb, d.ldb, kB, nB, wave); }
-            else if (ks == 2) { if (a_ok) fast_dma<false, 0, 2>(fa, d.lda, kA, nA, wave); }
-            else {
-                // the K-tile's one counted wait: everything but A(kt+2) (4 pieces per wave) has landed
-                if (a_ok) { fast_dma<false, 2, 4>(fa, d.lda, kA, nA, wave); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                // WAR by construction: the leading group refills this K-tile's B slot in its NEXT phase (phase 0 of kt+1), which runs
-                // while the trailing group is still in this phase's MFMA half -- so this phase's reads retire BEFORE the barrier
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        ga = ga == 2 ? 0 : ga + 1;
-        gb ^= 1;
-    }
-    if (!late) __builtin_amdgcn_s_barrier();   // re-align the two groups
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    epilogue_store<TO>(acc, smem, d, e, sk, split, m0, n0, wave, lane);
-}
-
-
-// ------------------------------------------------------------------------------------------------------------------
-// gemm_wgrad_kernel_4w: the same items, images, ring, counted waits and epilogue with FOUR waves -- one per SIMD, each owning a 128 x 128
-// block of the tile in 256 accumulator registers (4 x 4 tiles of v_mfma_f32_32x32x16_bf16).  A 16-deep k-step is ONE instruction stream
-// of 16 MFMAs (512 cycles) with the next k-step's 16 transposed fragment reads and four DMA pieces placed between them in a fixed
-// order; 64 instead of 96 fragment reads per k-step and CU, ONE workgroup barrier per K-tile instead of eight (it stands between
-// k-steps 2 and 3: behind it K-tile kt+1 is visible and nobody reads K-tile kt from LDS any more, so B(kt+2) and A(kt+3) may go out).
-// Same MFMA, same K order per accumulator: results are bit-identical to gemm_wgrad_kernel's.
+// gemm_wgrad_kernel_4w: FOUR waves -- one per SIMD, each owning a 128 x 128 block of the tile in 256 accumulator registers (4 x 4 tiles of
+// v_mfma_f32_32x32x16_bf16).  A 16-deep k-step is ONE instruction stream of 16 MFMAs (512 cycles) with the next k-step's 16 transposed
+// fragment reads and four DMA pieces placed between them in a fixed order.  Against the eight-wave kernel it replaced (2 x 4 waves of
+// 128 x 64, four 16-deep phases per K-tile, waves 4-7 one barrier behind waves 0-3): 64 instead of 96 fragment reads per k-step and CU,
+// ONE workgroup barrier per K-tile instead of eight (it stands between k-steps 2 and 3: behind it K-tile kt+1 is visible and nobody reads
+// K-tile kt from LDS any more, so B(kt+2) and A(kt+3) may go out), and bit-identical results (same MFMA, same K order per accumulator).
 template <int... X, typename F>
 __device__ __forceinline__ void w4_static_for_impl(std::integer_sequence<int, X...>, F &&f) { (f(std::integral_constant<int, X>{}), ...); }
 template <int N, typename F>
@@ -525,8 +351,7 @@ __global__ __launch_bounds__(256, 1) void gemm_wgrad_kernel_4w(ecgvit_gemm_desc 
 // The same kernel on 8-BIT operands (fp8_linear; BASELINE.json configs[4]): dW = dY8^T . X8 with dY8 in e5m2 (or e4m3) and X8 in e4m3,
 // both k-major ([token rows][features], one byte per element -- the copies the forward / input-gradient products already own), on the
 // block-scaled v_mfma_scale_f32_32x32x64_f8f6f4 with unit block scales (twice the bf16 MFMA rate).  A K-tile is 128 token rows deep in
-// the same 32-KiB tile ([128 k][256 mn] bytes, 256-B rows): the same DMA pieces, barriers and counted waits as above, four phases of
-// 4 MFMAs (64 cycles each) per K-tile, i.e. twice the K per byte that crosses the CU's memory path.
+// the same 32-KiB tile ([128 k][256 mn] bytes, 256-B rows), i.e. twice the K per byte that crosses the CU's memory path.
 // Fragments come from `ds_read_b64_tr_b8` (probed on the device, tools/probe_tr8.hip): in a 16-lane group source lane s supplies the
 // 8 bytes at ITS address and result lane i receives byte (i & 7) of source lanes 2j + (i >> 3), j = 0..7 -- with source lane s pointing
 // at k-row s >> 1, bytes 8 (s & 1) .. +7 of a 16-byte column chunk, lane i ends up with 8 consecutive k of column i.  Four such reads
@@ -535,24 +360,6 @@ __global__ __launch_bounds__(256, 1) void gemm_wgrad_kernel_4w(ecgvit_gemm_desc 
 // read cycle touches land on 16 distinct 16-B slots of the 256-B bank row.
 typedef int i32x8_t __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ FastOp fast_setup8(const uint8_t *P, int64_t ld, int mn0, int kend, int wave, int lane) {
-    FastOp f;
-    f.rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)P, 0, (uint32_t)((int64_t)kend * ld), 0x00020000);   // rows >= kend read as zero
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int kr = (wave * 4 + i) * 4 + (lane >> 4);          // k-row of this lane inside the K-tile (a piece = 4 rows x 256 B)
-        const int c = (lane & 15) ^ ((kr & 7) << 1);
-        f.voff[i] = (int)((int64_t)kr * ld + mn0 + c * 16);
-    }
-    return f;
-}
-template <int I0 = 0, int I1 = 4>
-__device__ __forceinline__ void fast_dma8(const FastOp &f, int64_t ld, int k0, char *tile, int wave) {
-    const int soff = (int)((int64_t)k0 * ld);
-#pragma unroll
-    for (int i = I0; i < I1; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(f.rsrc, (lptr_t)(tile + (wave * 4 + i) * 1024), 16, f.voff[i], soff, 0, 0);
-}
 // per-lane byte offset (inside a tile image) of the lane's first transposed read for a 32-column block starting at column mn_base (a
 // multiple of 32); read t of k-step ks adds 16384 ks + 2048 t
 __device__ __forceinline__ uint32_t frag8_lane_off(int mn_base, int lane) {
@@ -560,126 +367,9 @@ __device__ __forceinline__ uint32_t frag8_lane_off(int mn_base, int lane) {
     const int chunk = (mn_base >> 4) + ((lane >> 4) & 1);
     return (uint32_t)((32 * (lane >> 5) + j) * 256 + ((chunk ^ (j << 1)) << 4) + 8 * (s & 1));
 }
-template <int KS> __device__ __forceinline__ i32x8_t frag8(uint32_t lds_addr) {
-    u32x2 t0, t1, t2, t3;
-    asm volatile("ds_read_b64_tr_b8 %0, %1 offset:%2" : "=v"(t0) : "v"(lds_addr), "n"(KS * 16384) : "memory");
-    asm volatile("ds_read_b64_tr_b8 %0, %1 offset:%2" : "=v"(t1) : "v"(lds_addr), "n"(KS * 16384 + 2048) : "memory");
-    asm volatile("ds_read_b64_tr_b8 %0, %1 offset:%2" : "=v"(t2) : "v"(lds_addr), "n"(KS * 16384 + 4096) : "memory");
-    asm volatile("ds_read_b64_tr_b8 %0, %1 offset:%2" : "=v"(t3) : "v"(lds_addr), "n"(KS * 16384 + 6144) : "memory");
-    return i32x8_t{(int)t0[0], (int)t0[1], (int)t1[0], (int)t1[1], (int)t2[0], (int)t2[1], (int)t3[0], (int)t3[1]};
-}
-
-template <int AFMT>   // format of A (= dY): 0 e4m3, 1 e5m2; B (= X) is e4m3
-__global__ __launch_bounds__(512, 2) void gemm_wgrad8_kernel(ecgvit_gemm_desc d, EpiParams e, SplitK2 sk, int tiles_m, int tiles_n) {
-    __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
-    constexpr int BK8 = 128;
-    const int ntile = tiles_m * tiles_n;
-    int split, tid;
-    if (sk.splits > 1 && (sk.splits & 7) == 0) {
-        const int r = sk.splits >> 3, x = blockIdx.x & 7, q = blockIdx.x >> 3;
-        split = x + 8 * (q % r);
-        tid = q / r;
-    } else if (sk.splits > 1) {
-        const int gid = xcd_remap(blockIdx.x, ntile * sk.splits);
-        split = gid / ntile;
-        tid = gid - split * ntile;
-    } else {
-        split = 0;
-        tid = xcd_remap(blockIdx.x, ntile);
-    }
-    const int tm = tid / tiles_n, tn = tid - tm * tiles_n;
-    const int m0 = tm * BM, n0 = tn * BN;
-    const int kbeg = split * sk.k_per_split;
-    const int kend = min(d.K, kbeg + sk.k_per_split);
-    const int nk = (kend - kbeg + BK8 - 1) / BK8;
-    const uint8_t *A = reinterpret_cast<const uint8_t *>(d.A);
-    const uint8_t *B = reinterpret_cast<const uint8_t *>(d.B);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const bool late = wm == 1;
-    if (d.scale_a) e.alpha *= *d.scale_a;     // per-tensor scales of the 8-bit operands (device scalars); the split-K reducer applies them
-    if (d.scale_b) e.alpha *= *d.scale_b;     // itself when the partial sums go through slabs
-
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const FastOp fa = fast_setup8(A, d.lda, m0, kend, wave, lane);
-    const FastOp fb = fast_setup8(B, d.ldb, n0, kend, wave, lane);
-    char *const ringA = smem, *const ringB = smem + 3 * TILE_BYTES;
-    uint32_t offA[4], offB[2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) offA[i] = frag8_lane_off(wm * 128 + i * 32, lane);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) offB[j] = frag8_lane_off(wn * 64 + j * 32, lane);
-    // prologue: A(0), B(0), A(1)
-    fast_dma8(fa, d.lda, kbeg, ringA, wave);
-    fast_dma8(fb, d.ldb, kbeg, ringB, wave);
-    if (nk > 1) {
-        fast_dma8(fa, d.lda, kbeg + BK8, ringA + TILE_BYTES, wave);
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    if (late) __builtin_amdgcn_s_barrier();
-
-    int ga = 0, gb = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        const uint32_t sa = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)(ringA + ga * TILE_BYTES);
-        const uint32_t sb = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)(ringB + gb * TILE_BYTES);
-        char *nA = ringA + (ga == 0 ? 2 : ga - 1) * TILE_BYTES;   // slot of K-tile kt+2
-        char *nB = ringB + (gb ^ 1) * TILE_BYTES;                 // slot of K-tile kt+1
-        const bool b_ok = kt + 1 < nk, a_ok = kt + 2 < nk;
-        const int kB = kbeg + (kt + 1) * BK8, kA = kbeg + (kt + 2) * BK8;
-        i32x8_t b[2];
-        // phase p: k-step p >> 1 (64 token rows), A row blocks 2 (p & 1) .. +1: 16 or 8 transposed reads + 2 DMA pieces | 4 MFMAs
-#define W8_PHASE(P)                                                                                                          \
-        {                                                                                                                    \
-            constexpr int KS = (P) >> 1, IH = (P) & 1;                                                                       \
-            i32x8_t a[2];                                                                                                    \
-            if (IH == 0) { b[0] = frag8<KS>(sb + offB[0]); b[1] = frag8<KS>(sb + offB[1]); }                                 \
-            a[0] = frag8<KS>(sa + offA[2 * IH]); a[1] = frag8<KS>(sa + offA[2 * IH + 1]);                                    \
-            if ((P) == 0) { if (b_ok) fast_dma8<0, 2>(fb, d.ldb, kB, nB, wave); }                                            \
-            else if ((P) == 1) { if (b_ok) fast_dma8<2, 4>(fb, d.ldb, kB, nB, wave); }                                       \
-            else if ((P) == 2) { if (a_ok) fast_dma8<0, 2>(fa, d.lda, kA, nA, wave); }                                       \
-            else {                                                                                                           \
-                if (a_ok) { fast_dma8<2, 4>(fa, d.lda, kA, nA, wave); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }     \
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                        \
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                           \
-            }                                                                                                                \
-            __builtin_amdgcn_sched_barrier(0);                                                                               \
-            __builtin_amdgcn_s_barrier();                                                                                    \
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                               \
-            __builtin_amdgcn_sched_barrier(0);                                                                               \
-            __builtin_amdgcn_s_setprio(1);                                                                                   \
-            _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                      \
-                acc[2 * IH + i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[i], b[j], acc[2 * IH + i][j], AFMT, 0, 0, 0x7F7F7F7F, 0, 0x7F7F7F7F); \
-            __builtin_amdgcn_s_setprio(0);                                                                                   \
-            __builtin_amdgcn_sched_barrier(0);                                                                               \
-            __builtin_amdgcn_s_barrier();                                                                                    \
-            __builtin_amdgcn_sched_barrier(0);                                                                               \
-        }
-        W8_PHASE(0) W8_PHASE(1) W8_PHASE(2) W8_PHASE(3)
-#undef W8_PHASE
-        ga = ga == 2 ? 0 : ga + 1;
-        gb ^= 1;
-    }
-    if (!late) __builtin_amdgcn_s_barrier();   // re-align the two groups
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    epilogue_store<float>(acc, smem, d, e, sk, split, m0, n0, wave, lane);
-}
-
-// gemm_wgrad8_kernel_4w: the 8-bit weight-gradient kernel with FOUR waves (one per SIMD, 128 x 128 per wave in 256 accumulator registers),
-// as gemm_wgrad_kernel_4w is to gemm_wgrad_kernel: a 64-deep k-step is one instruction stream of 16 MFMAs (v_mfma_scale_f32_32x32x64_f8f6f4,
-// 64 cycles each) with the next k-step's 32 transposed reads and eight DMA pieces between them; one barrier per 128-deep K-tile, between its
-// two k-steps.  Bit-identical to gemm_wgrad8_kernel.
+// gemm_wgrad8_kernel_4w: the 8-bit weight-gradient kernel with FOUR waves (one per SIMD, 128 x 128 per wave in 256 accumulator registers):
+// a 64-deep k-step is one instruction stream of 16 MFMAs (v_mfma_scale_f32_32x32x64_f8f6f4, 64 cycles each) with the next k-step's 32
+// transposed reads and eight DMA pieces between them; one barrier per 128-deep K-tile, between its two k-steps.
 template <int AFMT>
 __global__ __launch_bounds__(256, 1) void gemm_wgrad8_kernel_4w(ecgvit_gemm_desc d, EpiParams e, SplitK2 sk, int tiles_m, int tiles_n) {
     __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
@@ -919,10 +609,6 @@ int64_t ecgvit_gemm_wgrad_workspace(const ecgvit_gemm_desc *d) {
     return s > 1 ? (int64_t)s * d->M * d->N * 4 : 0;
 }
 
-#ifdef ECGVIT_TOOLS
-static int g_tools_wgrad_8w = 0;
-extern "C" void ecgvit_tools_wgrad_body(int eight_wave) { g_tools_wgrad_8w = eight_wave; }   // tools/wgrad_ab.py: which body the next launches take
-#endif
 // argument validation is done by the caller (ecgvit_gemm_bf16_launch)
 int ecgvit_gemm_wgrad_launch(const ecgvit_gemm_desc *d, hipStream_t s) {
     const int tiles_m = d->M / BM, tiles_n = d->N / BN, ntile = tiles_m * tiles_n;
@@ -941,33 +627,16 @@ int ecgvit_gemm_wgrad_launch(const ecgvit_gemm_desc *d, hipStream_t s) {
         }
     }
     const EpiParams e = make_epi(d);
-    const dim3 grid((unsigned)(ntile * sk.splits));
-    [[maybe_unused]] const dim3 block(512);   // the eight-wave kernels (tools build)
+    const dim3 grid((unsigned)(ntile * sk.splits)), block(256);
     const bool f8 = d->dtype == ECGVIT_FP8_E4M3 || d->dtype == ECGVIT_BF8_E5M2;
     if (f8) {
         // 8-bit K-tiles are 128 token rows deep: slice boundaries on multiples of 128
         if (sk.splits > 1) sk.k_per_split = (((d->K + 127) / 128 + sk.splits - 1) / sk.splits) * 128;
-        const dim3 block4(256);
-#ifdef ECGVIT_TOOLS   // A/B against the eight-wave kernels (tools/wgrad_ab.py, ECGVIT_WGRAD_8W=1): the shipped library does not carry them
-        static const int env8 = [] { const char *e_ = getenv("ECGVIT_WGRAD_8W"); return e_ ? atoi(e_) : 0; }();
-        if (env8 || g_tools_wgrad_8w) {
-            if (d->dtype == ECGVIT_BF8_E5M2) hipLaunchKernelGGL(gemm_wgrad8_kernel<1>, grid, block, 0, s, *d, e, sk, tiles_m, tiles_n);
-            else hipLaunchKernelGGL(gemm_wgrad8_kernel<0>, grid, block, 0, s, *d, e, sk, tiles_m, tiles_n);
-        } else
-#endif
-        if (d->dtype == ECGVIT_BF8_E5M2) hipLaunchKernelGGL(gemm_wgrad8_kernel_4w<1>, grid, block4, 0, s, *d, e, sk, tiles_m, tiles_n);
-        else hipLaunchKernelGGL(gemm_wgrad8_kernel_4w<0>, grid, block4, 0, s, *d, e, sk, tiles_m, tiles_n);
+        if (d->dtype == ECGVIT_BF8_E5M2) hipLaunchKernelGGL(gemm_wgrad8_kernel_4w<1>, grid, block, 0, s, *d, e, sk, tiles_m, tiles_n);
+        else hipLaunchKernelGGL(gemm_wgrad8_kernel_4w<0>, grid, block, 0, s, *d, e, sk, tiles_m, tiles_n);
     } else {
-        const dim3 block4(256);
-#ifdef ECGVIT_TOOLS
-        static const int env8 = [] { const char *e_ = getenv("ECGVIT_WGRAD_8W"); return e_ ? atoi(e_) : 0; }();
-        if (env8 || g_tools_wgrad_8w) {
-            if (d->out_dtype == ECGVIT_BF16) hipLaunchKernelGGL(gemm_wgrad_kernel<bf16_t>, grid, block, 0, s, *d, e, sk, tiles_m, tiles_n);
-            else hipLaunchKernelGGL(gemm_wgrad_kernel<float>, grid, block, 0, s, *d, e, sk, tiles_m, tiles_n);
-        } else
-#endif
-        if (d->out_dtype == ECGVIT_BF16) hipLaunchKernelGGL(gemm_wgrad_kernel_4w<bf16_t>, grid, block4, 0, s, *d, e, sk, tiles_m, tiles_n);
-        else hipLaunchKernelGGL(gemm_wgrad_kernel_4w<float>, grid, block4, 0, s, *d, e, sk, tiles_m, tiles_n);
+        if (d->out_dtype == ECGVIT_BF16) hipLaunchKernelGGL(gemm_wgrad_kernel_4w<bf16_t>, grid, block, 0, s, *d, e, sk, tiles_m, tiles_n);
+        else hipLaunchKernelGGL(gemm_wgrad_kernel_4w<float>, grid, block, 0, s, *d, e, sk, tiles_m, tiles_n);
     }
     ECGVIT_CHECK_LAUNCH();
     if (sk.splits > 1) {

@@ -154,7 +154,7 @@ class HipTrainStep:
             self._xchg.begin(model._gflat)
             eng.on_grads_ready = self._xchg.bucket_ready if self.overlap else None
             # RCCL kernels will hold CUs while the rest of the backward runs: hand the GEMM tiles out in small chunks instead of
-            # static per-CU shares (tools/contention.py: 8 held CUs cost a static launch +52 %, a chunked one +9 %) -- an argument of
+            # static per-CU shares (profiles/r02_contention.txt: 8 held CUs cost a static launch +52 %, a chunked one +9 %) -- an argument of
             # THIS backward pass, not process state
             return 2 if self.overlap else 0
         eng.on_grads_ready = None

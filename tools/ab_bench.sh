@@ -3,7 +3,7 @@
 #   bash tools/ab_bench.sh VAR "v1 v2 ..." [reps] [extra bench args]
 # VAR starting with "--" is a bench.py flag (e.g. --hip-lib with two builds of the library:
 #   bash tools/ab_bench.sh --hip-lib "$PWD/ecg-representation-learning_amd/csrc/build/libecgvit_hip_prev.so $PWD/ecg-representation-learning_amd/libecgvit_hip.so");
-# anything else is an environment variable read by the tools build (ECGVIT_NT_G, ECGVIT_NT_DIAG; add --hip-lib .../libecgvit_hip_tools.so).
+# anything else is an environment variable, set for bench.py's process.
 if [ $# -lt 2 ]; then echo "usage: $0 VAR \"v1 v2 ...\" [reps] [extra bench args]" >&2; exit 2; fi
 VAR=$1; VALS=$2; REPS=${3:-2}
 shift $(( $# < 3 ? $# : 3 ))

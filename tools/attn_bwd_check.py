@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""where does the shipped attention backward differ from the one-item kernel (tools library)?  python tools/attn_bwd_check.py B h N p"""
+"""where does the shipped attention backward differ from the one-item kernel (tools library)?  python tools/attn_bwd_check.py B h N p [lib]
+(lib: another build of the product library to check instead of the shipped one)"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ecg_representation_learning_amd import hip
 from ecg_representation_learning_amd.hip import lib, check, ptr, stream
 from toolslib import tools_lib
-if os.environ.get('ECGVIT_AB_LIB'):
-    hip.use_library(os.environ['ECGVIT_AB_LIB'])
+if len(sys.argv) > 5:
+    hip.use_library(sys.argv[5])
 B, h, N, p = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]), float(sys.argv[4])
 dh = 64; d = h * dh; bf = torch.bfloat16
 g = torch.Generator().manual_seed(5)
