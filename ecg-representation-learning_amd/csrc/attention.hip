@@ -18,6 +18,8 @@
 //   -> ds_read_b64_tr_b16 reads of 4 consecutive rows x 64 B land in the 4 different 64-B quarters of the bank row.
 #include "attn_common.h"
 #include <cstdlib>
+#include <map>
+#include <mutex>
 
 namespace {
 
@@ -1374,6 +1376,34 @@ int ecgvit_attention_probs(const void *qkv, const float *lse, float *probs, int 
     return ECGVIT_OK;
 }
 
+// The current device's CU count (it picks the streamed forward), after the forward kernels' dynamic-LDS limits have been raised on that device:
+// once per device, under a lock.  0 if a query or an attribute call failed (nothing is recorded then; the next call tries again).
+static int attn_fwd_device_cus() {
+    static std::mutex mu;
+    static std::map<int, int> cus;   // device id -> CU count
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    std::lock_guard<std::mutex> lock(mu);
+    const auto it = cus.find(dev);
+    if (it != cus.end()) return it->second;
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 0;
+#define SATTR(K, BYTES) if (hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES) != hipSuccess) return 0
+    SATTR((attn_fwd_stream_kernel<true, false, 1>), 128 * 1024); SATTR((attn_fwd_stream_kernel<false, false, 1>), 128 * 1024);
+    SATTR((attn_fwd_stream_kernel<true, true, 1>), 128 * 1024); SATTR((attn_fwd_stream_kernel<false, true, 1>), 128 * 1024);
+#ifdef ECGVIT_TOOLS
+    SATTR((attn_fwd_stream_kernel<true, false, 2>), 128 * 1024); SATTR((attn_fwd_stream_kernel<false, false, 2>), 128 * 1024);
+    SATTR((attn_fwd_stream_kernel<true, true, 2>), 128 * 1024); SATTR((attn_fwd_stream_kernel<false, true, 2>), 128 * 1024);
+    SATTR((attn_fwd_stream_kernel<true, false, 3>), 128 * 1024); SATTR((attn_fwd_stream_kernel<false, false, 3>), 128 * 1024);
+    SATTR((attn_fwd_stream_kernel<true, true, 3>), 128 * 1024); SATTR((attn_fwd_stream_kernel<false, true, 3>), 128 * 1024);
+#endif
+    SATTR(attn_fwd_bf16_kernel<true>, 160 * 1024); SATTR(attn_fwd_bf16_kernel<false>, 160 * 1024);
+    SATTR((attn_fwd_bf16_kernel<true, true>), 160 * 1024); SATTR((attn_fwd_bf16_kernel<false, true>), 160 * 1024);
+#undef SATTR
+    cus[dev] = v;
+    return v;
+}
+
 static int attention_fwd_launch(const void *qkv, void *out, float *lse, int B, int N, int h, int dh, float scale, float dropout_p,
                                 uint64_t seed, int dtype, void *stream, void *out8, const float *q8_scale, float *q8_amax) {
     if (dtype != ECGVIT_BF16 || dh != 64 || N < 1 || N > 512 || B < 1 || h < 1) return ECGVIT_EINVAL;
@@ -1387,12 +1417,8 @@ static int attention_fwd_launch(const void *qkv, void *out, float *lse, int B, i
     // kernel, whose B*h workgroups spread over more CUs.  Up to 256 tokens the one-item kernel stays (512 x 12 x 251: 215 against 236 us streamed -- with two
     // items side by side a window is four key tiles, and the sixteen waves meet at a barrier every four tiles)
     {
-        static int n_cu = 0;
-        if (!n_cu) {
-            int dev = 0, v = 0;
-            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return ECGVIT_ELAUNCH;
-            n_cu = v;
-        }
+        const int n_cu = attn_fwd_device_cus();
+        if (n_cu <= 0) return ECGVIT_ELAUNCH;
         // (MODE 2 / 3 -- the two forms for up to 256 tokens, both slower than the one-item kernel there -- exist in the TOOLS build only: tools/attn_fwd_ab.py,
         // tests/test_gpu_ops.py hold them bit for bit against the one-item kernel)
         int mode = 1;
@@ -1406,17 +1432,6 @@ static int attention_fwd_launch(const void *qkv, void *out, float *lse, int B, i
         if (g_tools_attn_fwd_variant >= 1) stream_form = (int64_t)N * 3 * h * 64 * 2 < (1ll << 31);
 #endif
         if (stream_form) {
-            static bool sattr = false;
-            if (!sattr) {
-#define SATTR(DR, Q, G) if (hipFuncSetAttribute((const void *)attn_fwd_stream_kernel<DR, Q, G>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess) return ECGVIT_ELAUNCH
-                SATTR(true, false, 1); SATTR(false, false, 1); SATTR(true, true, 1); SATTR(false, true, 1);
-#ifdef ECGVIT_TOOLS
-                SATTR(true, false, 2); SATTR(false, false, 2); SATTR(true, true, 2); SATTR(false, true, 2);
-                SATTR(true, false, 3); SATTR(false, false, 3); SATTR(true, true, 3); SATTR(false, true, 3);
-#endif
-#undef SATTR
-                sattr = true;
-            }
             const int slots = mode == 3 ? 2 * n_cu : n_cu;
             const dim3 sg((unsigned)(nsuper < slots ? nsuper : slots)), sb(mode == 3 ? 512 : 1024);
             const size_t slds = mode == 3 ? 64 * 1024 : 128 * 1024;
@@ -1437,14 +1452,6 @@ static int attention_fwd_launch(const void *qkv, void *out, float *lse, int B, i
     const bool split = N > 256;   // two 256-key windows through 64 KiB of images, one workgroup per 256-query half
     dim3 grid((unsigned)(B * h * (split ? (N + 255) / 256 : 1)));
     const size_t lds = split ? (size_t)256 * 128 * 2 : (size_t)((N + 31) / 32) * 32 * 128 * 2;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void *)attn_fwd_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return ECGVIT_ELAUNCH;
-        if (hipFuncSetAttribute((const void *)attn_fwd_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return ECGVIT_ELAUNCH;
-        if (hipFuncSetAttribute((const void *)attn_fwd_bf16_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return ECGVIT_ELAUNCH;
-        if (hipFuncSetAttribute((const void *)attn_fwd_bf16_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return ECGVIT_ELAUNCH;
-        attr_set = true;
-    }
 #define FWD(DR, Q, SP) hipLaunchKernelGGL((attn_fwd_bf16_kernel<DR, Q, SP>), grid, dim3(512), lds, as_stream(stream), (const bf16_t *)qkv, (bf16_t *)out, lse, N, h, scale, seed, th, ik, (uint8_t *)out8, q8_scale, q8_amax)
     if (split) {
         if (out8) { if (th) FWD(true, true, true); else FWD(false, true, true); }

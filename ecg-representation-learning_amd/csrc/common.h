@@ -329,10 +329,9 @@ template <typename TO> __device__ __forceinline__ float epilogue_value(float acc
     return v;
 }
 
-// mask row pitch of the launch in flight (ecgvit_gemm_rowpitch): output row m draws the dropout bits of row m * pitch, so a product over a
-// compact subset of rows (one per record) applies exactly the mask a full launch applies to those rows.  1 everywhere else
-inline thread_local int g_mask_row_pitch = 1;
-static inline EpiParams make_epi(const ecgvit_gemm_desc *d) {
+// mask_row_pitch (ecgvit_gemm_rowpitch): output row m draws the dropout bits of row m * pitch, so a product over a compact subset of rows
+// (one per record) applies exactly the mask a full launch applies to those rows.  1 everywhere else
+static inline EpiParams make_epi(const ecgvit_gemm_desc *d, int mask_row_pitch) {
     EpiParams e;
     e.flags = d->epilogue;
     e.bias = d->bias;
@@ -346,11 +345,6 @@ static inline EpiParams make_epi(const ecgvit_gemm_desc *d) {
     const bool q8 = d->out_dtype == ECGVIT_BF16;
     e.drop_thresh = q8 ? dropout_threshold8(d->dropout_p) : dropout_threshold(d->dropout_p);
     e.inv_keep = d->dropout_p > 0.f ? (q8 ? dropout_inv_keep8(d->dropout_p) : 1.0f / (1.0f - d->dropout_p)) : 1.0f;
-    e.N = d->N * g_mask_row_pitch;   // m * (N * pitch) + n == (m * pitch) * N + n
+    e.N = d->N * mask_row_pitch;   // m * (N * pitch) + n == (m * pitch) * N + n
     return e;
 }
-
-// internal launchers (defined in gemm_f32.hip / gemm_bf16.hip).  route != nullptr: launch nothing, report the kernel family
-// (ECGVIT_KERNEL_*) the same arguments would run on -- one dispatch, whether it is executed or asked about (ecgvit_gemm_kernel)
-int ecgvit_gemm_f32_launch(const ecgvit_gemm_desc *d, hipStream_t s, int *route = nullptr);
-int ecgvit_gemm_bf16_launch(const ecgvit_gemm_desc *d, hipStream_t s, int *route = nullptr);

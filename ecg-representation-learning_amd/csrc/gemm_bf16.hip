@@ -16,12 +16,12 @@
 //   residual applied in f32, so C, aux and residual traffic is full-line.
 // Block order: 1-D grid remapped so that the 8 XCDs each own a contiguous run of tiles, N fastest: the blocks
 //   sharing an activation row-panel run on one XCD's L2; the (small) weight matrix streams from L2/MALL.
-#include "common.h"
+#include "gemm_plan.h"
 #include <cstdlib>
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64;
+constexpr int BM = GEMM_BF16_TILE, BN = GEMM_BF16_TILE, BK = GEMM_BK;
 constexpr int KC_TILE_BYTES = BM * BK * 2;   // 16 KiB
 constexpr int MN_ROW_BYTES = 320;            // 256 B of data + 64 B pad
 constexpr int MN_TILE_BYTES = BK * MN_ROW_BYTES;  // 20 KiB
@@ -290,84 +290,20 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restr
     }
 }
 
-inline int choose_splits(const ecgvit_gemm_desc *d, int ntile) {
-    if (d->layout != ECGVIT_GEMM_TN) return 1;
-    const int ksteps = (d->K + BK - 1) / BK;
-    int s = (768 + ntile - 1) / ntile;  // aim for ~3 waves of blocks over 256 CUs
-    s = std::min(s, std::max(1, ksteps / 8));  // keep >= 8 K-steps per split
-    return std::max(1, std::min(s, 64));
-}
-
 }  // namespace
 
-// large weight-gradient products (gemm_wgrad.hip) and large A . B^T products (gemm_nt.hip)
-bool ecgvit_gemm_wgrad_applicable(const ecgvit_gemm_desc *d);
-int64_t ecgvit_gemm_wgrad_workspace(const ecgvit_gemm_desc *d);
-int ecgvit_gemm_wgrad_launch(const ecgvit_gemm_desc *d, hipStream_t s);
-bool ecgvit_gemm_nt_applicable(const ecgvit_gemm_desc *d);
-int ecgvit_gemm_nt_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g);
-int ecgvit_gemm_nt4w_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g, bool nt_stores);   // gemm_nt.hip: the four-wave body
-
-extern "C" int64_t ecgvit_gemm_workspace(const ecgvit_gemm_desc *d) {
-    if ((d->dtype == ECGVIT_FP8_E4M3 || d->dtype == ECGVIT_BF8_E5M2) && d->layout == ECGVIT_GEMM_TN) return ecgvit_gemm_wgrad_workspace(d);
-    if (d->dtype != ECGVIT_BF16 || d->layout != ECGVIT_GEMM_TN) return 0;
-    const int ntile = ((d->M + BM - 1) / BM) * ((d->N + BN - 1) / BN);
-    const int s = choose_splits(d, ntile);
-    const int64_t v1 = s > 1 ? (int64_t)s * d->M * d->N * 4 : 0;
-    return std::max(v1, ecgvit_gemm_wgrad_workspace(d));
-}
-
-int ecgvit_gemm_bf16_launch(const ecgvit_gemm_desc *d, hipStream_t s, int *route) {
-    if (d->dtype != ECGVIT_BF16) return ECGVIT_EINVAL;
-    if (d->out_dtype != ECGVIT_BF16 && d->out_dtype != ECGVIT_F32) return ECGVIT_EINVAL;
-    if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch1 != 1 || d->batch2 != 1) return ECGVIT_EINVAL;
-    if (d->N % 8 != 0 || d->lda % 8 != 0 || d->ldb % 8 != 0 || d->ldc % 8 != 0) return ECGVIT_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(d->A) | reinterpret_cast<uintptr_t>(d->B) | reinterpret_cast<uintptr_t>(d->C)) % 16) return ECGVIT_EINVAL;
-    const bool a_kc = d->layout != ECGVIT_GEMM_TN, b_kc = d->layout == ECGVIT_GEMM_NT;
-    if ((a_kc || b_kc) && d->K % 8 != 0) return ECGVIT_EINVAL;      // K-contiguous operands move 8-element chunks
-    if (!a_kc && d->M % 8 != 0) return ECGVIT_EINVAL;
-    if (d->out_dtype == ECGVIT_F32 &&
-        (d->epilogue & (ECGVIT_EPI_GELU | ECGVIT_EPI_GELU_BWD | ECGVIT_EPI_MUL_AUX | ECGVIT_EPI_RESIDUAL | ECGVIT_EPI_DROPOUT)))
-        return ECGVIT_EINVAL;
-    if ((d->epilogue & ECGVIT_EPI_BIAS) && (reinterpret_cast<uintptr_t>(d->bias) % 16)) return ECGVIT_EINVAL;
-    if ((d->epilogue & (ECGVIT_EPI_GELU | ECGVIT_EPI_GELU_BWD | ECGVIT_EPI_MUL_AUX)) && (!d->aux || d->ldaux % 8 || reinterpret_cast<uintptr_t>(d->aux) % 16)) return ECGVIT_EINVAL;
-    if ((d->epilogue & ECGVIT_EPI_RESIDUAL) && (!d->residual || d->ldr % 8 || reinterpret_cast<uintptr_t>(d->residual) % 16)) return ECGVIT_EINVAL;
-
-    if (d->layout != ECGVIT_GEMM_NT && d->layout != ECGVIT_GEMM_NN && d->layout != ECGVIT_GEMM_TN) return ECGVIT_EINVAL;
-    if (ecgvit_gemm_nt_applicable(d)) {
-        if (route) { *route = ECGVIT_KERNEL_GEMM_NT; return ECGVIT_OK; }
-        return ecgvit_gemm_nt_launch(d, s, 0);
-    }
-    if (ecgvit_gemm_wgrad_applicable(d)) {
-        if (route) { *route = ECGVIT_KERNEL_GEMM_WGRAD; return ECGVIT_OK; }
-        return ecgvit_gemm_wgrad_launch(d, s);
-    }
-    if (route) { *route = ECGVIT_KERNEL_GEMM_BF16; return ECGVIT_OK; }
-    const int tiles_m = (d->M + BM - 1) / BM, tiles_n = (d->N + BN - 1) / BN, ntile = tiles_m * tiles_n;
+int gemm_bf16_launch(const GemmPlan &p, const ecgvit_gemm_desc *d, hipStream_t s) {
     SplitK sk;
-    sk.splits = 1;
-    sk.slabs = nullptr;
-    sk.k_per_split = ((d->K + BK - 1) / BK) * BK;
-    if (d->workspace && d->layout == ECGVIT_GEMM_TN) {
-        int sp = choose_splits(d, ntile);
-        while (sp > 1 && (int64_t)sp * d->M * d->N * 4 > d->workspace_bytes) --sp;
-        if (sp > 1 && ((int64_t)d->M * d->N) % 4 == 0 &&
-            !(d->epilogue & ~(ECGVIT_EPI_BIAS | ECGVIT_EPI_ACCUM))) {
-            const int ksteps = (d->K + BK - 1) / BK;
-            sk.splits = sp;
-            sk.k_per_split = ((ksteps + sp - 1) / sp) * BK;
-            sk.slabs = reinterpret_cast<float *>(d->workspace);
-        }
-    }
-    EpiParams e = make_epi(d);
-    dim3 grid((unsigned)(ntile * sk.splits)), block(256);
-#define LAUNCH(AK, BKC, TO) hipLaunchKernelGGL((gemm_bf16_kernel<AK, BKC, TO>), grid, block, 0, s, *d, e, sk, tiles_m, tiles_n)
+    sk.splits = p.splits;
+    sk.k_per_split = p.k_per_split;
+    sk.slabs = p.splits > 1 ? reinterpret_cast<float *>(d->workspace) : nullptr;
+    const EpiParams e = make_epi(d, p.mask_row_pitch);
+#define LAUNCH(AK, BKC, TO) hipLaunchKernelGGL((gemm_bf16_kernel<AK, BKC, TO>), p.grid, dim3(256), 0, s, *d, e, sk, p.tiles_m, p.tiles_n)
     const bool obf = d->out_dtype == ECGVIT_BF16;
     switch (d->layout) {
         case ECGVIT_GEMM_NT: if (obf) LAUNCH(true, true, bf16_t); else LAUNCH(true, true, float); break;
         case ECGVIT_GEMM_NN: if (obf) LAUNCH(true, false, bf16_t); else LAUNCH(true, false, float); break;
-        case ECGVIT_GEMM_TN: if (obf) LAUNCH(false, false, bf16_t); else LAUNCH(false, false, float); break;
-        default: return ECGVIT_EINVAL;
+        default: if (obf) LAUNCH(false, false, bf16_t); else LAUNCH(false, false, float); break;
     }
 #undef LAUNCH
     ECGVIT_CHECK_LAUNCH();
@@ -380,78 +316,3 @@ int ecgvit_gemm_bf16_launch(const ecgvit_gemm_desc *d, hipStream_t s, int *route
     }
     return ECGVIT_OK;
 }
-
-// the one dispatch of ecgvit_gemm: executed (route == nullptr) or only asked about (route receives ECGVIT_KERNEL_*)
-static int gemm_dispatch(const ecgvit_gemm_desc *d, void *stream, int *route) {
-    if (!d) return ECGVIT_EINVAL;
-    if ((d->epilogue & ECGVIT_EPI_AUX8) && !ecgvit_gemm_nt_applicable(d)) return ECGVIT_EINVAL;   // the e4m3 saved tensor exists on the large A.B^T kernel only
-    if ((d->epilogue & ECGVIT_EPI_DROPOUT) && d->dropout_p > 0.f && d->out_dtype == ECGVIT_BF16 && dropout_threshold8(d->dropout_p) == 0u)
-        return ECGVIT_EINVAL;   // 16-bit outputs draw 8 bits per element: 0 < p < 1/512 would silently round to no dropout
-    if (d->epilogue & ECGVIT_EPI_NO_OUT) {   // no-output form: the 8-bit A . B^T kernel's emitting FFN-wide bodies only (ecgvit_gemm_nt_applicable holds the list)
-        const bool f8 = d->dtype == ECGVIT_FP8_E4M3 || d->dtype == ECGVIT_BF8_E5M2;
-        if (!f8 || d->layout != ECGVIT_GEMM_NT || !(d->epilogue & ECGVIT_EPI_QUANT_OUT) || !d->A || !d->B || !d->aux ||
-            (reinterpret_cast<uintptr_t>(d->A) | reinterpret_cast<uintptr_t>(d->B) | reinterpret_cast<uintptr_t>(d->C)) % 16)
-            return ECGVIT_EINVAL;
-    }
-    if (d->epilogue & ECGVIT_EPI_COLSUM) {
-        if (!d->colsum_out || !d->workspace || d->batch1 != 1 || d->batch2 != 1) return ECGVIT_EINVAL;
-        if (d->dtype == ECGVIT_BF16 && ecgvit_gemm_nt_applicable(d)) return ecgvit_gemm_bf16_launch(d, as_stream(stream), route);   // fused column sums
-        if ((d->dtype == ECGVIT_FP8_E4M3 || d->dtype == ECGVIT_BF8_E5M2) && ecgvit_gemm_nt_applicable(d)) {
-            if (route) { *route = ECGVIT_KERNEL_GEMM_NT; return ECGVIT_OK; }
-            return ecgvit_gemm_nt_launch(d, as_stream(stream), 0);
-        }
-        // generic path: plain GEMM, then the stand-alone column-sum kernel over the stored output
-        if (d->workspace_bytes < ecgvit_colsum_workspace(d->M, d->N)) return ECGVIT_EINVAL;
-        ecgvit_gemm_desc g = *d;
-        g.epilogue &= ~ECGVIT_EPI_COLSUM;
-        const int rc = gemm_dispatch(&g, stream, route);
-        if (rc != ECGVIT_OK || route) return rc;
-        return ecgvit_colsum(d->C, d->ldc, d->colsum_out, d->workspace, d->M, d->N, d->out_dtype, stream);
-    }
-    if (d->dtype == ECGVIT_F32) return ecgvit_gemm_f32_launch(d, as_stream(stream), route);
-    if (d->dtype == ECGVIT_BF16) return ecgvit_gemm_bf16_launch(d, as_stream(stream), route);
-    if ((d->dtype == ECGVIT_FP8_E4M3 || d->dtype == ECGVIT_BF8_E5M2) && d->layout == ECGVIT_GEMM_TN) {
-        // 8-bit weight gradients dW = dY8^T . X8 (A in `dtype`, B e4m3, f32 output): the streaming split-K kernel only
-        if (!d->C || reinterpret_cast<uintptr_t>(d->C) % 16 || d->ldc % 4 || !ecgvit_gemm_wgrad_applicable(d)) return ECGVIT_EINVAL;
-        if (route) { *route = ECGVIT_KERNEL_GEMM_WGRAD; return ECGVIT_OK; }
-        return ecgvit_gemm_wgrad_launch(d, as_stream(stream));
-    }
-    if (d->dtype == ECGVIT_FP8_E4M3 || d->dtype == ECGVIT_BF8_E5M2) {   // 8-bit operands: the large A . B^T kernel only (no small-shape fallback)
-        if (!d->A || !d->B || (!d->C && !(d->epilogue & ECGVIT_EPI_NO_OUT)) ||
-            (reinterpret_cast<uintptr_t>(d->A) | reinterpret_cast<uintptr_t>(d->B) | reinterpret_cast<uintptr_t>(d->C)) % 16)
-            return ECGVIT_EINVAL;
-        if ((d->epilogue & ECGVIT_EPI_BIAS) && (!d->bias || reinterpret_cast<uintptr_t>(d->bias) % 16)) return ECGVIT_EINVAL;
-        if ((d->epilogue & (ECGVIT_EPI_GELU | ECGVIT_EPI_GELU_BWD | ECGVIT_EPI_MUL_AUX)) && (!d->aux || d->ldaux % 8 || reinterpret_cast<uintptr_t>(d->aux) % 16)) return ECGVIT_EINVAL;
-        if ((d->epilogue & ECGVIT_EPI_RESIDUAL) && (!d->residual || d->ldr % 8 || reinterpret_cast<uintptr_t>(d->residual) % 16)) return ECGVIT_EINVAL;
-        if (d->ldc % 8 != 0 || !ecgvit_gemm_nt_applicable(d)) return ECGVIT_EINVAL;
-        if (route) { *route = ECGVIT_KERNEL_GEMM_NT; return ECGVIT_OK; }
-        return ecgvit_gemm_nt_launch(d, as_stream(stream), 0);
-    }
-    return ECGVIT_EINVAL;
-}
-
-extern "C" int ecgvit_gemm(const ecgvit_gemm_desc *d, void *stream) { return gemm_dispatch(d, stream, nullptr); }
-
-extern "C" int ecgvit_gemm_rowpitch(const ecgvit_gemm_desc *d, int mask_row_pitch, void *stream) {
-    if (!d || mask_row_pitch < 1 || (int64_t)d->N * mask_row_pitch >= (1ll << 31)) return ECGVIT_EINVAL;
-    g_mask_row_pitch = mask_row_pitch;
-    const int rc = gemm_dispatch(d, stream, nullptr);
-    g_mask_row_pitch = 1;
-    return rc;
-}
-
-extern "C" int ecgvit_gemm_kernel(const ecgvit_gemm_desc *d) {
-    int route = ECGVIT_KERNEL_NONE;
-    return gemm_dispatch(d, nullptr, &route) == ECGVIT_OK ? route : ECGVIT_KERNEL_NONE;
-}
-
-#ifdef ECGVIT_TOOLS
-// tools build only (libecgvit_hip_tools.so): one A . B^T call with column groups of raster_g n-tiles (0 = the built-in order) on
-// gemm_nt_kernel's dispatch (kernel 2) or on the four-wave body with default-policy stores (kernel 3): tools/gemm_ab.py
-extern "C" int ecgvit_tools_gemm(const ecgvit_gemm_desc *d, void *stream, int kernel, int raster_g) {
-    if (!d) return ECGVIT_EINVAL;
-    if (kernel == 2) return ecgvit_gemm_nt_applicable(d) ? ecgvit_gemm_nt_launch(d, as_stream(stream), raster_g) : ECGVIT_EINVAL;
-    if (kernel == 3) return ecgvit_gemm_nt_applicable(d) ? ecgvit_gemm_nt4w_launch(d, as_stream(stream), raster_g, false) : ECGVIT_EINVAL;
-    return ecgvit_gemm(d, stream);
-}
-#endif

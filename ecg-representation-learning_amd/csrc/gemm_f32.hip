@@ -8,11 +8,11 @@
 // Tile 128x128x16, 256 threads = 4 waves (2x2), each wave 64x64 = 2x2 MFMA 32x32 accumulators.
 // LDS images are k-major ([k][m]), so a fragment read is 32 consecutive floats per half-wave
 // (conflict-free ds_read_b32); operands that are K-contiguous in memory are transposed on the LDS write.
-#include "common.h"
+#include "gemm_plan.h"
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 16, LDT = BM + 4;  // +4 floats: keeps 16-B alignment for b128 writes
+constexpr int BM = GEMM_F32_TILE, BN = GEMM_F32_TILE, BK = 16, LDT = BM + 4;  // +4 floats: keeps 16-B alignment for b128 writes
 
 // Stage one operand tile into registers. KCONTIG: memory is [mn][k] (k fastest); else [k][mn] (mn fastest).
 template <bool KCONTIG>
@@ -142,26 +142,13 @@ inline bool vec_ok(const void *p, int64_t ld, int64_t s1, int64_t s2) {
 
 }  // namespace
 
-int ecgvit_gemm_f32_launch(const ecgvit_gemm_desc *d, hipStream_t s, int *route) {
-    if (d->dtype != ECGVIT_F32 || d->out_dtype != ECGVIT_F32) return ECGVIT_EINVAL;
-    if (d->M <= 0 || d->N <= 0 || d->K < 0 || d->batch1 < 1 || d->batch2 < 1) return ECGVIT_EINVAL;
-    const int64_t nz = (int64_t)d->batch1 * d->batch2;
-    if (nz > 65535) return ECGVIT_EINVAL;
-    if (nz > 1 && (d->epilogue & (ECGVIT_EPI_GELU | ECGVIT_EPI_GELU_BWD | ECGVIT_EPI_RESIDUAL | ECGVIT_EPI_DROPOUT)))
-        return ECGVIT_EINVAL;
-    if (route) {
-        if (d->layout != ECGVIT_GEMM_NT && d->layout != ECGVIT_GEMM_NN && d->layout != ECGVIT_GEMM_TN) return ECGVIT_EINVAL;
-        *route = ECGVIT_KERNEL_GEMM_F32;
-        return ECGVIT_OK;
-    }
-    dim3 grid((d->N + BN - 1) / BN, (d->M + BM - 1) / BM, (unsigned)nz), block(256);
-    EpiParams e = make_epi(d);
+int gemm_f32_launch(const GemmPlan &p, const ecgvit_gemm_desc *d, hipStream_t s) {
+    const EpiParams e = make_epi(d, p.mask_row_pitch);
     const bool va = vec_ok(d->A, d->lda, d->strideA1, d->strideA2), vb = vec_ok(d->B, d->ldb, d->strideB1, d->strideB2);
     switch (d->layout) {
-        case ECGVIT_GEMM_NT: hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, block, 0, s, *d, e, va, vb); break;
-        case ECGVIT_GEMM_NN: hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, block, 0, s, *d, e, va, vb); break;
-        case ECGVIT_GEMM_TN: hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, block, 0, s, *d, e, va, vb); break;
-        default: return ECGVIT_EINVAL;
+        case ECGVIT_GEMM_NT: hipLaunchKernelGGL((gemm_f32_kernel<true, true>), p.grid, dim3(256), 0, s, *d, e, va, vb); break;
+        case ECGVIT_GEMM_NN: hipLaunchKernelGGL((gemm_f32_kernel<true, false>), p.grid, dim3(256), 0, s, *d, e, va, vb); break;
+        default: hipLaunchKernelGGL((gemm_f32_kernel<false, false>), p.grid, dim3(256), 0, s, *d, e, va, vb); break;
     }
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;

@@ -22,13 +22,13 @@
 //     conflict-free for their ds_read_b128 fragment patterns (rows 16t + (lane&15) / the permuted rows above).
 //   * epilogue flags are a template parameter for the combinations the train step uses (branch-free bodies); any other
 //     combination runs the same kernel with run-time flags.
-#include "common.h"
+#include "gemm_plan.h"
 #include "nt_tiles.h"
 #include <type_traits>
 
 namespace {
 
-constexpr int BM = 256, BN = 256, BK = 64;
+constexpr int BM = GEMM_NT_TILE, BK = GEMM_BK;
 constexpr int HALF_BYTES = 16384;
 constexpr int LDS_BYTES = 163840;
 
@@ -954,175 +954,47 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_kernel_4w(ecgvit_gemm_desc d, 
 
 }  // namespace
 
-static int nt_default_group(int tiles_n) { return tiles_n <= 8 ? tiles_n : 6; }   // n-tiles per column group of the built-in tile walk (ecgvit_gemm_nt_launch)
-
-bool ecgvit_gemm_nt_applicable(const ecgvit_gemm_desc *d) {
-    const bool f8 = d->dtype == ECGVIT_FP8_E4M3 || d->dtype == ECGVIT_BF8_E5M2;
-    if (d->layout != ECGVIT_GEMM_NT || !(d->dtype == ECGVIT_BF16 || f8)) return false;
-    if (d->batch1 != 1 || d->batch2 != 1) return false;
-    if (d->M < 2048 || d->N < 128 || d->N % 8 != 0) return false;
-    if (f8 ? (d->K % 128 != 0 || d->K < 384 || d->lda % 16 != 0 || d->ldb % 16 != 0 || d->out_dtype != ECGVIT_BF16) : (d->K % 64 != 0 || d->K < 192)) return false;
-    const int es = f8 ? 1 : 2;
-    if ((int64_t)d->M * d->lda * es + 65536 * d->lda >= (1ll << 31) || (int64_t)d->N * d->ldb * es + 65536 * d->ldb >= (1ll << 31)) return false;
-    const int64_t esz = d->out_dtype == ECGVIT_BF16 ? 2 : 4, rows = (int64_t)d->M + 256;   // epilogue offsets are 32-bit byte offsets
-    if (rows * d->ldc * esz >= (1ll << 31) || rows * d->ldr * 2 >= (1ll << 31) || rows * d->ldaux * 2 >= (1ll << 31)) return false;
-    if (d->epilogue & ECGVIT_EPI_NO_OUT) {   // only the emitting FFN-wide bodies of the 8-bit kernel have a no-output form
-        const int fl = d->epilogue & ~(ECGVIT_EPI_NO_OUT | ECGVIT_EPI_DROPOUT | ECGVIT_EPI_AUX8);
-        const int up = ECGVIT_EPI_BIAS | ECGVIT_EPI_GELU | ECGVIT_EPI_GELU_GRAD_AUX | ECGVIT_EPI_QUANT_OUT, dh = ECGVIT_EPI_MUL_AUX | ECGVIT_EPI_COLSUM | ECGVIT_EPI_QUANT_OUT;
-        if (!((d->dtype == ECGVIT_FP8_E4M3 && fl == up) || (d->dtype == ECGVIT_BF8_E5M2 && (d->epilogue & ~ECGVIT_EPI_AUX8) == (dh | ECGVIT_EPI_NO_OUT)))) return false;
-    } else if (!d->C) {
-        return false;
-    }
-    if (d->epilogue & ECGVIT_EPI_AUX8) {   // the e4m3 saved tensor: the two FFN-wide bodies (bf16 operands, or 8-bit operands with their emitting forms)
-        const int fl = d->epilogue & ~(ECGVIT_EPI_AUX8 | ECGVIT_EPI_DROPOUT | ECGVIT_EPI_QUANT_OUT | ECGVIT_EPI_NO_OUT);
-        const int up = ECGVIT_EPI_BIAS | ECGVIT_EPI_GELU | ECGVIT_EPI_GELU_GRAD_AUX, dh = ECGVIT_EPI_MUL_AUX | ECGVIT_EPI_COLSUM;
-        if (d->out_dtype != ECGVIT_BF16 || !d->aux || d->ldaux % 8 || reinterpret_cast<uintptr_t>(d->aux) % 8) return false;
-        if (d->dtype == ECGVIT_BF16 && (d->epilogue & (ECGVIT_EPI_QUANT_OUT | ECGVIT_EPI_NO_OUT))) return false;
-        const bool is_up = fl == up && d->dtype != ECGVIT_BF8_E5M2, is_dh = fl == dh && !(d->epilogue & ECGVIT_EPI_DROPOUT) && d->dtype != ECGVIT_FP8_E4M3;
-        if (!(is_up || is_dh)) return false;
-    }
-    if (d->epilogue & ECGVIT_EPI_QUANT_OUT) {
-        if (!f8 || !d->q8_out || !d->q8_scale || !d->q8_amax || d->ldq8 % 8 || reinterpret_cast<uintptr_t>(d->q8_out) % 8 ||
-            (d->q8_format != ECGVIT_FP8_E4M3 && d->q8_format != ECGVIT_BF8_E5M2) || rows * d->ldq8 >= (1ll << 31))
-            return false;
-    }
-    if (d->epilogue & ECGVIT_EPI_COLSUM) {
-        if (d->out_dtype != ECGVIT_BF16 || !d->workspace || !d->colsum_out ||
-            d->workspace_bytes < (int64_t)8 * ((d->M + BM - 1) / BM) * d->N)
-            return false;
-    }
-    return true;
-}
-
 void ecgvit_colsum_reduce_launch(const float *partial, int nparts, int N, float *out, hipStream_t s);   // gemm_wgrad.hip
 
-int ecgvit_gemm_nt4w_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g, bool nt_stores);
-// argument validation is done by the caller (ecgvit_gemm_bf16_launch); raster_g <= 0 selects the built-in choice
-int ecgvit_gemm_nt_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g) {
-    const int tiles_m = (d->M + BM - 1) / BM, tiles_n = (d->N + BN - 1) / BN, ntile = tiles_m * tiles_n;
-    // Built-in tile walk: column groups of 6 n-tiles (m-major inside a group).  Measured inside the train step against the plain
-    // n-fastest order (profiles/r02_raster_step.txt): the same step time (+-0.02 %) with 13 % fewer bytes
-    // fetched from beyond L2 per launch (1.08 -> 0.94 GB); groups of 3 fetch 0.97 GB at -0.1 %, groups of 4 cost 0.6 % of the step.
-    // Up to 8 n-tiles (N <= 2048: the FFN-wide products of EcgVit-small) stay ONE group -- a 6 + 2 split costs that step 0.9 % (round 4).
-    const int G = raster_g > 0 ? std::min(raster_g, tiles_n) : nt_default_group(tiles_n);
-    const EpiParams e = make_epi(d);
-    // persistent (one workgroup per CU, static shares) unless the caller asks for dispatcher-balanced chunks of ~k tiles
-    const int tpw = d->tiles_per_workgroup;
-    const dim3 grid((unsigned)(tpw > 0 ? std::max(std::min(ntile, 256), (ntile + tpw - 1) / tpw) : std::min(ntile, 256))), block(512);
-    const int fl = d->epilogue;
-    constexpr int F_LIN = ECGVIT_EPI_BIAS | ECGVIT_EPI_RESIDUAL;
-    constexpr int F_UP = ECGVIT_EPI_BIAS | ECGVIT_EPI_GELU | ECGVIT_EPI_GELU_GRAD_AUX;
-    constexpr int F_DH = ECGVIT_EPI_MUL_AUX | ECGVIT_EPI_COLSUM;
-#define NT_LAUNCH(TO, FL) hipLaunchKernelGGL((gemm_nt_kernel<TO, FL>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile)
-#define NT_LAUNCH8(FL, OPS) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, FL, OPS>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile)
-    // plain 8-bit products whose bf16 output does not fit the 256-MB Infinity Cache (EcgVit-large: the QKV forward's 788 MB) store it non-temporally, as
-    // the bf16 QKV forward does since round 3: written through L2 the output evicts the operand panels the tile's neighbours are about to re-read
-    // (profiles/r06_fp8_nt_stores.txt at 256 x 501 token rows, default -> non-temporal: QKV forward K = 1024, 752 MB: 403.8 -> 350.5 us; the 250-MB outputs: K = 1024
-    // 145.5 -> 133.8, K = 3072 323.0 -> 338.1, K = 4096 411.8 -> 422.9: a long main loop re-reads its panels from L2 often enough to want the cache's help)
-    const bool nt8 = (int64_t)d->M * d->N * 2 > (320ll << 20) || ((int64_t)d->M * d->N * 2 > (240ll << 20) && d->K <= 1024);
-#define NT_LAUNCH8_NT(OPS) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, 0, OPS, 2>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile)
-    if (d->dtype == ECGVIT_FP8_E4M3) {          // forward products: e4m3 activations x e4m3 weights
-        switch (fl) {
-            case 0: if (nt8) NT_LAUNCH8_NT(3); else NT_LAUNCH8(0, 3); break;
-            case F_LIN: NT_LAUNCH8(F_LIN, 3); break;
-            case F_LIN | ECGVIT_EPI_DROPOUT: NT_LAUNCH8(F_LIN | ECGVIT_EPI_DROPOUT, 3); break;
-            case F_UP: NT_LAUNCH8(F_UP, 3); break;
-            case F_UP | ECGVIT_EPI_DROPOUT: NT_LAUNCH8(F_UP | ECGVIT_EPI_DROPOUT, 3); break;
-            case F_UP | ECGVIT_EPI_QUANT_OUT: NT_LAUNCH8(F_UP | ECGVIT_EPI_QUANT_OUT, 3); break;
-            case F_UP | ECGVIT_EPI_DROPOUT | ECGVIT_EPI_QUANT_OUT: NT_LAUNCH8(F_UP | ECGVIT_EPI_DROPOUT | ECGVIT_EPI_QUANT_OUT, 3); break;
-            case F_UP | ECGVIT_EPI_QUANT_OUT | ECGVIT_EPI_NO_OUT: NT_LAUNCH8(F_UP | ECGVIT_EPI_QUANT_OUT | ECGVIT_EPI_NO_OUT, 3); break;
-            case F_UP | ECGVIT_EPI_DROPOUT | ECGVIT_EPI_QUANT_OUT | ECGVIT_EPI_NO_OUT: NT_LAUNCH8(F_UP | ECGVIT_EPI_DROPOUT | ECGVIT_EPI_QUANT_OUT | ECGVIT_EPI_NO_OUT, 3); break;
-#define A8 ECGVIT_EPI_AUX8
-            case F_UP | A8: NT_LAUNCH8(F_UP | A8, 3); break;
-            case F_UP | ECGVIT_EPI_DROPOUT | A8: NT_LAUNCH8(F_UP | ECGVIT_EPI_DROPOUT | A8, 3); break;
-            case F_UP | ECGVIT_EPI_QUANT_OUT | A8: NT_LAUNCH8(F_UP | ECGVIT_EPI_QUANT_OUT | A8, 3); break;
-            case F_UP | ECGVIT_EPI_DROPOUT | ECGVIT_EPI_QUANT_OUT | A8: NT_LAUNCH8(F_UP | ECGVIT_EPI_DROPOUT | ECGVIT_EPI_QUANT_OUT | A8, 3); break;
-            case F_UP | ECGVIT_EPI_QUANT_OUT | ECGVIT_EPI_NO_OUT | A8: NT_LAUNCH8(F_UP | ECGVIT_EPI_QUANT_OUT | ECGVIT_EPI_NO_OUT | A8, 3); break;
-            case F_UP | ECGVIT_EPI_DROPOUT | ECGVIT_EPI_QUANT_OUT | ECGVIT_EPI_NO_OUT | A8: NT_LAUNCH8(F_UP | ECGVIT_EPI_DROPOUT | ECGVIT_EPI_QUANT_OUT | ECGVIT_EPI_NO_OUT | A8, 3); break;
-            default: if (fl & A8) return ECGVIT_EINVAL; NT_LAUNCH8(-1, 3); break;
-        }
-    } else if (d->dtype == ECGVIT_BF8_E5M2) {   // input-gradient products: e5m2 gradients x e4m3 transposed weights
-        switch (fl) {
-            case 0: if (nt8) NT_LAUNCH8_NT(4); else NT_LAUNCH8(0, 4); break;
-            case F_DH: NT_LAUNCH8(F_DH, 4); break;
-            case F_DH | ECGVIT_EPI_QUANT_OUT: NT_LAUNCH8(F_DH | ECGVIT_EPI_QUANT_OUT, 4); break;
-            case F_DH | ECGVIT_EPI_QUANT_OUT | ECGVIT_EPI_NO_OUT: NT_LAUNCH8(F_DH | ECGVIT_EPI_QUANT_OUT | ECGVIT_EPI_NO_OUT, 4); break;
-            case F_DH | A8: NT_LAUNCH8(F_DH | A8, 4); break;
-            case F_DH | ECGVIT_EPI_QUANT_OUT | A8: NT_LAUNCH8(F_DH | ECGVIT_EPI_QUANT_OUT | A8, 4); break;
-            case F_DH | ECGVIT_EPI_QUANT_OUT | ECGVIT_EPI_NO_OUT | A8: NT_LAUNCH8(F_DH | ECGVIT_EPI_QUANT_OUT | ECGVIT_EPI_NO_OUT | A8, 4); break;
-#undef A8
-            default: if (fl & ECGVIT_EPI_AUX8) return ECGVIT_EINVAL; NT_LAUNCH8(-1, 4); break;
-        }
-    } else if (d->out_dtype == ECGVIT_BF16) {
-        if (fl == 0) {
-            // plain products.  K >= 1536 (the QKV and FFN-up input gradients): the four-wave body (alpha 1 only).
-            // Outputs that do not fit the 256 MB Infinity Cache (QKV forward: 592 MB) are stored non-temporally: written through L2 they
-            // evict the operand panels the tile's neighbours are about to re-read (main loop 3,020 -> 2,620 cycles per K-tile, launch
-            // -6...-10 %); smaller outputs (197 MB) are absorbed by the cache and nt costs them 2-3 % (profiles/r03_gemm_4w.txt)
-            const bool big_out = (int64_t)d->M * d->N * 2 > (256ll << 20);
-            if (d->K >= 1536 && e.alpha == 1.f && !d->scale_a && !d->scale_b) return ecgvit_gemm_nt4w_launch(d, s, raster_g, big_out);
-            if (big_out) hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, 0, 0, 2>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile);
-            else NT_LAUNCH(bf16_t, 0);
-            ECGVIT_CHECK_LAUNCH();
-            return ECGVIT_OK;
-        }
-        // the two residual launches (bias + residual [+ dropout]: attn-out and FFN-down forward) with K >= 768: the four-wave body as well --
-        // its shorter main loop outweighs the one-wave epilogue (launch -2 % at K = 768, -3 % at K = 3072; step +0.2...0.3 %)
-        if ((fl & ~ECGVIT_EPI_DROPOUT) == F_LIN && d->K >= 768 && e.alpha == 1.f && !d->scale_a && !d->scale_b)
-            return ecgvit_gemm_nt4w_launch(d, s, raster_g, false);
-        switch (fl) {
-            case ECGVIT_EPI_BIAS: NT_LAUNCH(bf16_t, ECGVIT_EPI_BIAS); break;   // the masked objective's pixel head
-            case F_LIN: NT_LAUNCH(bf16_t, F_LIN); break;
-            case F_LIN | ECGVIT_EPI_DROPOUT: NT_LAUNCH(bf16_t, F_LIN | ECGVIT_EPI_DROPOUT); break;
-            case F_UP: NT_LAUNCH(bf16_t, F_UP); break;
-            case F_UP | ECGVIT_EPI_DROPOUT: NT_LAUNCH(bf16_t, F_UP | ECGVIT_EPI_DROPOUT); break;
-            case F_DH: NT_LAUNCH(bf16_t, F_DH); break;
-            case F_UP | ECGVIT_EPI_AUX8: NT_LAUNCH(bf16_t, F_UP | ECGVIT_EPI_AUX8); break;
-            case F_UP | ECGVIT_EPI_DROPOUT | ECGVIT_EPI_AUX8: NT_LAUNCH(bf16_t, F_UP | ECGVIT_EPI_DROPOUT | ECGVIT_EPI_AUX8); break;
-            case F_DH | ECGVIT_EPI_AUX8: NT_LAUNCH(bf16_t, F_DH | ECGVIT_EPI_AUX8); break;
-            default: if (fl & ECGVIT_EPI_AUX8) return ECGVIT_EINVAL; NT_LAUNCH(bf16_t, -1); break;
-        }
-    } else {
-        if (fl == 0) NT_LAUNCH(float, 0);
-        else NT_LAUNCH(float, -1);
+namespace {
+// the eight-wave body (512 threads), OPS: 0 bf16 operands, 3 e4m3 x e4m3, 4 e5m2 x e4m3.  Exactly the flag sets of `sets` (and, for bf16 outputs, the
+// non-temporal plain form) have their own instantiation; every other set runs on run-time flags
+template <typename TO, int OPS, typename Sets>
+void nt8w_go(Sets sets, const GemmPlan &p, const ecgvit_gemm_desc *d, const EpiParams &e, hipStream_t s) {
+    const int ntile = p.tiles_m * p.tiles_n;
+    auto go = [&](auto fl, auto caux) {
+        hipLaunchKernelGGL((gemm_nt_kernel<TO, decltype(fl)::value, OPS, decltype(caux)::value>), p.grid, dim3(512), 0, s, *d, e, p.tiles_m, p.tiles_n, p.group, ntile);
+    };
+    if constexpr (sizeof(TO) == 2) {
+        if (p.nt_stores) return go(std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
     }
-#undef NT_LAUNCH
-#undef NT_LAUNCH8
-#undef NT_LAUNCH8_NT
+    if (!epi_dispatch(sets, p.fl, [&](auto fl) { go(fl, std::integral_constant<int, 0>{}); }))
+        go(std::integral_constant<int, -1>{}, std::integral_constant<int, 0>{});
+}
+}  // namespace
+
+int gemm_nt_launch(const GemmPlan &p, const ecgvit_gemm_desc *d, hipStream_t s) {
+    const EpiParams e = make_epi(d, p.mask_row_pitch);
+    if (p.body == GemmBody::NT4W) {   // the four-wave body (bf16 products, alpha 1): 256 threads
+        const int ntile = p.tiles_m * p.tiles_n;
+        auto go = [&](auto fl, auto caux) {
+            hipLaunchKernelGGL((gemm_nt_kernel_4w<bf16_t, decltype(fl)::value, decltype(caux)::value>), p.grid, dim3(256), 0, s, *d, e, p.tiles_m, p.tiles_n, p.group, ntile);
+        };
+        if (p.nt_stores) go(std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
+        else epi_dispatch(epi_sets::FourWave{}, p.fl, [&](auto fl) { go(fl, std::integral_constant<int, 0>{}); });
+    } else if (d->dtype == ECGVIT_FP8_E4M3) {   // forward products: e4m3 activations x e4m3 weights
+        nt8w_go<bf16_t, 3>(epi_sets::E4m3{}, p, d, e, s);
+    } else if (d->dtype == ECGVIT_BF8_E5M2) {   // input-gradient products: e5m2 gradients x e4m3 transposed weights
+        nt8w_go<bf16_t, 4>(epi_sets::E5m2{}, p, d, e, s);
+    } else if (d->out_dtype == ECGVIT_BF16) {
+        nt8w_go<bf16_t, 0>(epi_sets::Bf16{}, p, d, e, s);
+    } else {
+        nt8w_go<float, 0>(epi_sets::F32Out{}, p, d, e, s);
+    }
     ECGVIT_CHECK_LAUNCH();
     if (d->epilogue & ECGVIT_EPI_COLSUM) {
-        ecgvit_colsum_reduce_launch((const float *)d->workspace, 2 * tiles_m, d->N, d->colsum_out, s);
+        ecgvit_colsum_reduce_launch((const float *)d->workspace, 2 * p.tiles_m, d->N, d->colsum_out, s);
         ECGVIT_CHECK_LAUNCH();
     }
     return ECGVIT_OK;
 }
-
-// the four-wave body (bf16 products, plain or bias + residual [+ dropout], alpha 1; persistent grid or dispatcher-balanced chunks); nt_stores: non-temporal
-// output stores (plain products only)
-int ecgvit_gemm_nt4w_launch(const ecgvit_gemm_desc *d, hipStream_t s, int raster_g, bool nt_stores) {
-    const EpiParams e = make_epi(d);
-    constexpr int F_LIN = ECGVIT_EPI_BIAS | ECGVIT_EPI_RESIDUAL;
-    const int fl = d->epilogue;
-    if (d->dtype != ECGVIT_BF16 || d->out_dtype != ECGVIT_BF16 || d->K < 192 || e.alpha != 1.f || d->scale_a || d->scale_b) return ECGVIT_EINVAL;
-    // (the FFN-down input gradient's body -- x aux, column sums -- measured 1,044 us on this body against 696: 288 B of spills, one wave's VALU)
-    constexpr int F_DH = ECGVIT_EPI_MUL_AUX | ECGVIT_EPI_COLSUM;
-    if (fl != 0 && fl != F_LIN && fl != (F_LIN | ECGVIT_EPI_DROPOUT) && fl != F_DH) return ECGVIT_EINVAL;
-    const int tiles_m = (d->M + BM - 1) / BM, tiles_n = (d->N + BN - 1) / BN, ntile = tiles_m * tiles_n;
-    const int G = raster_g > 0 ? std::min(raster_g, tiles_n) : nt_default_group(tiles_n);
-    const int tpw = d->tiles_per_workgroup;   // > 0: dispatcher-balanced chunks of ~tpw tiles, as in ecgvit_gemm_nt_launch
-    const dim3 grid((unsigned)(tpw > 0 ? std::max(std::min(ntile, 256), (ntile + tpw - 1) / tpw) : std::min(ntile, 256))), block(256);
-#define NT4W_GO(FL, CAUX) hipLaunchKernelGGL((gemm_nt_kernel_4w<bf16_t, FL, CAUX>), grid, block, 0, s, *d, e, tiles_m, tiles_n, G, ntile)
-    if (fl == F_LIN) NT4W_GO(F_LIN, 0);
-    else if (fl == (F_LIN | ECGVIT_EPI_DROPOUT)) NT4W_GO(F_LIN | ECGVIT_EPI_DROPOUT, 0);
-    else if (fl == F_DH) NT4W_GO(F_DH, 0);
-    else if (nt_stores) NT4W_GO(0, 2);
-    else NT4W_GO(0, 0);
-#undef NT4W_GO
-    ECGVIT_CHECK_LAUNCH();
-    if (fl & ECGVIT_EPI_COLSUM) {
-        ecgvit_colsum_reduce_launch((const float *)d->workspace, 2 * tiles_m, d->N, d->colsum_out, s);
-        ECGVIT_CHECK_LAUNCH();
-    }
-    return ECGVIT_OK;
-}
-

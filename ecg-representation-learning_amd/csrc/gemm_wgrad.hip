@@ -11,14 +11,14 @@
 // quarters of the bank row.  Rows beyond a slice's end fall outside the buffer descriptor and read as zero.
 // The transposed reads are inline asm: with an LDS-DMA in flight hipcc's waitcnt pass drains vmcnt(0) in front of the builtin.
 // Also here: the column-sum reducer shared with gemm_nt.hip's EPI_COLSUM.
-#include "common.h"
+#include "gemm_plan.h"
 #include <algorithm>
 #include <type_traits>
 #include <utility>
 
 namespace {
 
-constexpr int BM = 256, BN = 256, BK = 64;
+constexpr int BM = GEMM_WGRAD_TILE, BN = GEMM_WGRAD_TILE, BK = GEMM_BK;
 constexpr int TILE_BYTES = 32768;
 constexpr int CS_LD = 68, CS_WAVE_BYTES = 64 * CS_LD * 4;  // 17408: per-wave epilogue patch (64 rows x 64 f32 + pad)
 constexpr int LDS_BYTES = 163840;                          // all of LDS: 3 A + 2 B tiles; the epilogue patches need 139264
@@ -564,79 +564,25 @@ __global__ __launch_bounds__(1024) void colsum_reduce_kernel(const float *__rest
     }
 }
 
-inline int choose_splits2(const ecgvit_gemm_desc *d, int ntile) {
-    if (d->layout != ECGVIT_GEMM_TN) return 1;
-    const int ksteps = (d->K + BK - 1) / BK;
-    // one block per CU: fill ONE round of the 256 CUs (never 2.1 rounds); a multiple of 8 slices lets each XCD own whole K-slices
-    int s = 256 / ntile;
-    // a multiple of 8 slices lets each XCD own whole K-slices (best L2 locality), but only if the rounding leaves < 7 % of the CUs idle:
-    // 27 tiles x 8 slices = 216 blocks wastes 16 % of the chip for the whole launch, 27 x 9 = 243 (XCD-contiguous order) does not
-    if (s >= 8 && (s & ~7) * ntile * 100 >= s * ntile * 93) s &= ~7;
-    if (s < 1) s = 1;
-    // tiles_per_workgroup (launches that share the GPU with RCCL kernels) does NOT change the slicing here.  Three times as many,
-    // shorter slices would bound the tail of a block that finds its CU held, but they cost every launch: measured inside the step on
-    // a 1-rank RCCL group (bench.py --single-rank-collectives, profiles/r02_dp_single_rank.txt) +2.3 ms of gemm_wgrad and +1.1 ms of
-    // split-K reduce per step, against the ~8 % of the backward during which a bucket's all-reduce actually holds CUs.
-    s = std::min(s, std::max(1, ksteps / 16));   // keep >= 16 K-steps per slice
-    return std::max(1, std::min(s, 64));
-}
-
 }  // namespace
 
 void ecgvit_colsum_reduce_launch(const float *partial, int nparts, int N, float *out, hipStream_t s) {
     hipLaunchKernelGGL(colsum_reduce_kernel, dim3((N + 63) / 64), dim3(1024), 0, s, partial, nparts, N, out);
 }
 
-// large weight-gradient products only (both extents whole tiles, a long reduction); everything else stays on gemm_bf16.hip's 128^2 kernel
-bool ecgvit_gemm_wgrad_applicable(const ecgvit_gemm_desc *d) {
-    const bool f8 = d->dtype == ECGVIT_FP8_E4M3 || d->dtype == ECGVIT_BF8_E5M2;
-    if (d->layout != ECGVIT_GEMM_TN || !(d->dtype == ECGVIT_BF16 || f8) || d->batch1 != 1 || d->batch2 != 1) return false;
-    if (d->epilogue & ~(ECGVIT_EPI_BIAS | ECGVIT_EPI_ACCUM)) return false;
-    if (d->K < 4096 || d->M % 256 != 0 || d->N % 256 != 0) return false;
-    if (f8) {   // 8-bit operands: f32 output, 16-B aligned rows (one DMA lane = 16 bytes of a row)
-        if (d->out_dtype != ECGVIT_F32 || d->lda % 16 || d->ldb % 16 || !d->A || !d->B ||
-            (reinterpret_cast<uintptr_t>(d->A) | reinterpret_cast<uintptr_t>(d->B)) % 16)
-            return false;
-        return (int64_t)d->K * d->lda + 65536 * d->lda < (1ll << 31) && (int64_t)d->K * d->ldb + 65536 * d->ldb < (1ll << 31);
-    }
-    return (int64_t)d->K * d->lda * 2 + 65536 * d->lda < (1ll << 31) && (int64_t)d->K * d->ldb * 2 + 65536 * d->ldb < (1ll << 31);
-}
-
-int64_t ecgvit_gemm_wgrad_workspace(const ecgvit_gemm_desc *d) {
-    if (!ecgvit_gemm_wgrad_applicable(d)) return 0;
-    const int ntile = (d->M / BM) * (d->N / BN);
-    const int s = choose_splits2(d, ntile);
-    return s > 1 ? (int64_t)s * d->M * d->N * 4 : 0;
-}
-
-// argument validation is done by the caller (ecgvit_gemm_bf16_launch)
-int ecgvit_gemm_wgrad_launch(const ecgvit_gemm_desc *d, hipStream_t s) {
-    const int tiles_m = d->M / BM, tiles_n = d->N / BN, ntile = tiles_m * tiles_n;
-    const int ksteps = (d->K + BK - 1) / BK;
+int gemm_wgrad_launch(const GemmPlan &p, const ecgvit_gemm_desc *d, hipStream_t s) {
     SplitK2 sk;
-    sk.splits = 1;
-    sk.slabs = nullptr;
-    sk.k_per_split = ksteps * BK;
-    if (d->workspace) {
-        int sp = choose_splits2(d, ntile);
-        while (sp > 1 && (int64_t)sp * d->M * d->N * 4 > d->workspace_bytes) --sp;
-        if (sp > 1) {
-            sk.splits = sp;
-            sk.k_per_split = ((ksteps + sp - 1) / sp) * BK;
-            sk.slabs = reinterpret_cast<float *>(d->workspace);
-        }
-    }
-    const EpiParams e = make_epi(d);
-    const dim3 grid((unsigned)(ntile * sk.splits)), block(256);
-    const bool f8 = d->dtype == ECGVIT_FP8_E4M3 || d->dtype == ECGVIT_BF8_E5M2;
+    sk.splits = p.splits;
+    sk.k_per_split = p.k_per_split;
+    sk.slabs = p.splits > 1 ? reinterpret_cast<float *>(d->workspace) : nullptr;
+    const EpiParams e = make_epi(d, p.mask_row_pitch);
+    const bool f8 = p.body == GemmBody::WGRAD8;
     if (f8) {
-        // 8-bit K-tiles are 128 token rows deep: slice boundaries on multiples of 128
-        if (sk.splits > 1) sk.k_per_split = (((d->K + 127) / 128 + sk.splits - 1) / sk.splits) * 128;
-        if (d->dtype == ECGVIT_BF8_E5M2) hipLaunchKernelGGL(gemm_wgrad8_kernel_4w<1>, grid, block, 0, s, *d, e, sk, tiles_m, tiles_n);
-        else hipLaunchKernelGGL(gemm_wgrad8_kernel_4w<0>, grid, block, 0, s, *d, e, sk, tiles_m, tiles_n);
+        if (d->dtype == ECGVIT_BF8_E5M2) hipLaunchKernelGGL(gemm_wgrad8_kernel_4w<1>, p.grid, dim3(256), 0, s, *d, e, sk, p.tiles_m, p.tiles_n);
+        else hipLaunchKernelGGL(gemm_wgrad8_kernel_4w<0>, p.grid, dim3(256), 0, s, *d, e, sk, p.tiles_m, p.tiles_n);
     } else {
-        if (d->out_dtype == ECGVIT_BF16) hipLaunchKernelGGL(gemm_wgrad_kernel_4w<bf16_t>, grid, block, 0, s, *d, e, sk, tiles_m, tiles_n);
-        else hipLaunchKernelGGL(gemm_wgrad_kernel_4w<float>, grid, block, 0, s, *d, e, sk, tiles_m, tiles_n);
+        if (d->out_dtype == ECGVIT_BF16) hipLaunchKernelGGL(gemm_wgrad_kernel_4w<bf16_t>, p.grid, dim3(256), 0, s, *d, e, sk, p.tiles_m, p.tiles_n);
+        else hipLaunchKernelGGL(gemm_wgrad_kernel_4w<float>, p.grid, dim3(256), 0, s, *d, e, sk, p.tiles_m, p.tiles_n);
     }
     ECGVIT_CHECK_LAUNCH();
     if (sk.splits > 1) {

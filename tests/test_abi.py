@@ -106,6 +106,22 @@ def test_gemm_kernel_route_query_is_host_only():
     assert l.ecgvit_gemm_kernel(None) == hip.KERNEL_NONE
 
 
+def test_gemm_route_and_workspace_table():
+    """ecgvit_gemm_kernel and ecgvit_gemm_workspace over the descriptor sweep of tests/gemm_cases.py (every layout x operand / output type,
+    the engine's epilogue flag sets plus invalid ones, both sides of every routing threshold) against tests/golden/gemm_routes.json.
+    The fixture was recorded from the library before the GEMM planner; the calls that library routed and then failed or would have faulted
+    on (COLSUM off the fused bodies with N or ldc not a multiple of 8, or with no stored C; 8-bit COLSUM products with a null or misaligned
+    operand, or ldc / ldaux not a multiple of 8) were then set to ECGVIT_KERNEL_NONE.  Re-record: `python tests/gemm_cases.py [library]`."""
+    import gemm_cases
+    digest, want = gemm_cases.read_fixture()
+    cases = gemm_cases.cases()
+    assert len(cases) > 3000 and gemm_cases.labels_digest([label for label, _ in cases]) == digest
+    l = E.hip.lib()
+    bad = [(label, w, g) for (label, c), w in zip(cases, want) if (g := list(gemm_cases.query(l, c))) != w]
+    assert not bad, (len(bad), bad[:20])
+    assert l.ecgvit_gemm_workspace(None) == 0
+
+
 def test_binding_constants_are_the_headers():
     """every numeric #define of include/ecgvit_hip.h that the Python binding restates (dtype / layout / epilogue / kernel-family codes, error codes)
     has the same value there: `ECGVIT_X` <-> `hip.X`"""
