@@ -252,7 +252,11 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_bf16_kernel(const bf16_t *__r
 // form when an LDS-DMA is in flight: attn_common.h), requested at the top of a tile and consumed behind its softmax.
 // =====================================================================================================
 // MODE 1: 16 waves, one item, 256-key windows (N > 256).  MODE 2: 16 waves, two items side by side, 128-key windows (N <= 256).  MODE 3: 8 waves, one item,
-// 128-key windows, TWO workgroups per CU with a 2 x 32 KiB ring each (N <= 256): a workgroup's barrier joins its own eight waves only
+// 128-key windows, TWO workgroups per CU with a 2 x 32 KiB ring each (N <= 256): a workgroup's barrier joins its own eight waves only.
+// MODE 4 (512 < N <= 2048): MODE 1 with an item = (record, head, block of 512 queries): the window loop runs over all ceil(N / 256) key windows, the Q,
+//   output and LSE descriptors start at the block's first query (per-record 64-bit bases, 32-bit offsets inside a record).  The query blocks of one
+//   (record, head) are consecutive items, and consecutive items go to the workgroups of one XCD (workgroup j runs on XCD j % 8): the K / V rows an item
+//   re-reads were read by its neighbours on the same L2.
 template <bool DROP, bool Q8, int MODE>
 __global__ __launch_bounds__(MODE == 3 ? 512 : 1024, 4) void attn_fwd_stream_kernel(const bf16_t *__restrict__ qkv, bf16_t *__restrict__ out, float *__restrict__ lse, int N, int h,
                                                                float scale, uint64_t seed, uint32_t thresh, float inv_keep, int nitems,
@@ -261,7 +265,7 @@ __global__ __launch_bounds__(MODE == 3 ? 512 : 1024, 4) void attn_fwd_stream_ker
     extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 slots x 64 KiB
     constexpr int GROUPS = MODE == 2 ? 2 : 1, NWV = MODE == 3 ? 8 : 16;
     constexpr int WG_ = NWV / GROUPS;     // waves = 32-query blocks per item
-    constexpr int WK = MODE == 1 ? 256 : 128;   // keys per window
+    constexpr int WK = (MODE == 1 || MODE == 4) ? 256 : 128;   // keys per window
     constexpr int SLOT = GROUPS * WK * 256;     // bytes of a ring slot
     constexpr int TPW = WK / 32;          // key tiles per window
     constexpr int GB = WK * 256;          // bytes of one group's K + V images inside a slot
@@ -270,7 +274,16 @@ __global__ __launch_bounds__(MODE == 3 ? 512 : 1024, 4) void attn_fwd_stream_ker
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int group = GROUPS == 2 ? wave >> 3 : 0, wq = GROUPS == 2 ? wave & 7 : wave;
     const int nkt = (N + 31) >> 5, nw = (nkt + TPW - 1) / TPW;
-    const int nsuper = (nitems + GROUPS - 1) / GROUPS;
+    const int nqb5 = MODE == 4 ? (N + 511) >> 9 : 1;           // MODE 4: 512-query blocks per (record, head)
+    // MODE 4 with a grid of whole XCDs: round r of the grid runs items r G .. r G + G - 1, and workgroup j takes item r G + (j % 8) (G / 8) + j / 8 -- the
+    // rounds are padded to whole grids (the last one's surplus workgroups keep the barriers company)
+    const bool xcd_order = MODE == 4 && (gridDim.x & 7) == 0;
+    const int nsuper = xcd_order ? (nitems + (int)gridDim.x - 1) / (int)gridDim.x * (int)gridDim.x : (nitems + GROUPS - 1) / GROUPS;
+    auto item_of = [&](int s_) __attribute__((always_inline)) {
+        if (!xcd_order) return s_ * GROUPS + group;
+        const int G = (int)gridDim.x, r = s_ / G, j = s_ - r * G;
+        return r * G + (j & 7) * (G >> 3) + (j >> 3);
+    };
     const int d = h * 64;
     const int d3 = 3 * d;
     const int lr = lane & 31, lh = lane >> 5;
@@ -286,9 +299,9 @@ __global__ __launch_bounds__(MODE == 3 ? 512 : 1024, 4) void attn_fwd_stream_ker
 
     // pieces of window w of super-item s -> slot; my group's item only (an item past the end: nothing is issued, its waves keep the barriers company)
     auto issue = [&](int s, int w, int slot) __attribute__((always_inline)) {
-        const int item = s * GROUPS + group;
+        const int item = item_of(s);
         if (item >= nitems) return;
-        const int b = item / h, hd = item - b * h;
+        const int ibh = item / nqb5, b = ibh / h, hd = ibh - b * h;
         const bf16_t *base = qkv + (int64_t)b * N * d3 + hd * 64;
         const int k0 = w * WK, nv = min(WK, N - k0), rp = ((nv + 31) >> 5) << 5;
         char *Kimg = smem + slot * SLOT + group * GB;
@@ -299,11 +312,13 @@ __global__ __launch_bounds__(MODE == 3 ? 512 : 1024, 4) void attn_fwd_stream_ker
     // tile, draining the next window's pieces in front of the window they are supposed to land under; issued this way the pass does not see them, and the
     // counted wait at the item's first window (vmcnt(NST): they are older than the stores) orders them by hand
     auto load_q = [&](int s, bf16x8 (&qf)[4]) __attribute__((always_inline)) {
-        const int item = s * GROUPS + group;
+        const int item = item_of(s);
         if (item >= nitems) return;
-        const int b = item / h, hd = item - b * h;
-        const uint64_t pa = (uint64_t)(uintptr_t)(qkv + (int64_t)b * N * d3 + hd * 64);
-        const i32x4_t rq = i32x4_t{(int)(uint32_t)pa, (int)((pa >> 32) & 0xFFFFu), (int)bytes_q, 0x00020000};
+        const int ibh = item / nqb5, b = ibh / h, hd = ibh - b * h;
+        const int q0 = (item - ibh * nqb5) * 512;   // (0 below MODE 4)
+        const uint64_t pa = (uint64_t)(uintptr_t)(qkv + ((int64_t)b * N + q0) * d3 + hd * 64);
+        const uint32_t bq = MODE == 4 ? (uint32_t)(((int64_t)(N - q0 - 1) * d3 + 64) * 2) : bytes_q;
+        const i32x4_t rq = i32x4_t{(int)(uint32_t)pa, (int)((pa >> 32) & 0xFFFFu), (int)bq, 0x00020000};
         asm volatile("buffer_load_dwordx4 %0, %4, %5, 0 offen\n\tbuffer_load_dwordx4 %1, %4, %5, 0 offen offset:32\n\t"
                      "buffer_load_dwordx4 %2, %4, %5, 0 offen offset:64\n\tbuffer_load_dwordx4 %3, %4, %5, 0 offen offset:96"
                      : "=&v"(qf[0]), "=&v"(qf[1]), "=&v"(qf[2]), "=&v"(qf[3]) : "v"(qoff), "s"(rq) : "memory");
@@ -318,12 +333,14 @@ __global__ __launch_bounds__(MODE == 3 ? 512 : 1024, 4) void attn_fwd_stream_ker
     load_q(s, qf);
     int t = 0;                                        // windows this workgroup has started: slot = t & 1
     for (; s < nsuper; s += gridDim.x) {
-        const int item = s * GROUPS + group;
+        const int item = item_of(s);
         const bool live = item < nitems;
-        const int bh = live ? item : 0;
+        const int bh = live ? item / nqb5 : 0;
         const int b = bh / h, hd = bh - b * h;
+        const int q0 = live ? (item - bh * nqb5) * 512 : 0;   // first query of the item (0 below MODE 4)
+        const int qg = q0 + q;                                // my query of the record
         const int snext = s + (int)gridDim.x;
-        const uint32_t rowquad = ((uint32_t)bh * (uint32_t)N + (uint32_t)(q < N ? q : N - 1)) * (uint32_t)((N + 3) >> 2);
+        const uint32_t rowquad = ((uint32_t)bh * (uint32_t)N + (uint32_t)(qg < N ? qg : N - 1)) * (uint32_t)((N + 3) >> 2);
         f32x16 o[2];
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
@@ -402,7 +419,8 @@ __global__ __launch_bounds__(MODE == 3 ? 512 : 1024, 4) void attn_fwd_stream_ker
             const float inv = inv_keep / l;
             [[maybe_unused]] float q8_inv = 0.f;
             if constexpr (Q8) { const float sc8 = *q8_scale; q8_inv = sc8 > 0.f ? 1.0f / sc8 : 0.f; }
-            const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)(out + (int64_t)b * N * d + hd * 64), 0, bytes_o, 0x00020000);
+            const uint32_t bo = MODE == 4 ? (uint32_t)(((int64_t)(N - q0 - 1) * d + 64) * 2) : bytes_o;
+            const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)(out + ((int64_t)b * N + q0) * d + hd * 64), 0, bo, 0x00020000);
             const int ooff = (q * d + 16 * lh) * 2;
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) {
@@ -424,7 +442,7 @@ __global__ __launch_bounds__(MODE == 3 ? 512 : 1024, 4) void attn_fwd_stream_ker
 #pragma unroll
                             for (int k = 0; k < 4; ++k) {
                                 f[k] = (float)v[k];
-                                qmax = fmaxf(qmax, q < N ? fabsf(f[k]) : 0.f);
+                                qmax = fmaxf(qmax, qg < N ? fabsf(f[k]) : 0.f);
                                 f[k] = __builtin_amdgcn_fmed3f(f[k] * q8_inv, -448.f, 448.f);
                             }
                             int wv = 0;
@@ -446,11 +464,11 @@ __global__ __launch_bounds__(MODE == 3 ? 512 : 1024, 4) void attn_fwd_stream_ker
                     }
                 }
                 if constexpr (Q8) {
-                    const __amdgpu_buffer_rsrc_t rout8 = __builtin_amdgcn_make_buffer_rsrc((void *)(out8 + (int64_t)b * N * d + hd * 64), 0, bytes_o / 2, 0x00020000);
+                    const __amdgpu_buffer_rsrc_t rout8 = __builtin_amdgcn_make_buffer_rsrc((void *)(out8 + ((int64_t)b * N + q0) * d + hd * 64), 0, bo / 2, 0x00020000);
                     __builtin_amdgcn_raw_buffer_store_b128(w8, rout8, q * d + 16 * lh + dt * 32, 0, 0);
                 }
             }
-            const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void *)(lse + (int64_t)bh * N), 0, (uint32_t)N * 4u, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void *)(lse + (int64_t)bh * N + q0), 0, (uint32_t)(N - q0) * 4u, 0x00020000);
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(m * scale + logf(l)), rl, lh == 0 ? q * 4 : 0x7FFFFFF0, 0, 0);
         }
     }
@@ -685,7 +703,10 @@ __global__ __launch_bounds__(NKT * 64) void attn_bwd_bf16_kernel(const bf16_t *_
 // Q8 (fp8_linear; bit 0: dK / dV, bit 1: dQ): additionally dqkv8 = saturate(dqkv as stored / *q8_scale) in e5m2 (same [B*N, 3*h*dh] layout, one
 // byte per element) -- the A operand of the QKV projection's two backward products, written here instead of by a quantise pass over
 // dqkv -- and *q8_amax = max(*q8_amax, max |dqkv|).  With two key windows the first launch emits its dK / dV only (dQ is final in the second).
-template <bool DROP, bool ACCUM, bool STAGGER = true, int Q8 = 0>
+// NQ = 2048 (512 < N <= 2048: one launch per 256-key window, up to eight; every launch after the first adds its dQ to the bf16 dQ in dqkv): the LSE row
+// of an item (8 KiB) is held ONCE -- the next item's row travels in four registers per lane from its query block 1 and is written behind the item's last
+// barrier, after the last read of the current row -- so that the LDS stays inside 160 KiB (two 8-KiB rows would not: 160.25 KiB)
+template <bool DROP, bool ACCUM, bool STAGGER = true, int Q8 = 0, int NQ = 512>
 __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__restrict__ qkv, const bf16_t *__restrict__ out,
                                                             const bf16_t *__restrict__ dout, const float *__restrict__ lse,
                                                             bf16_t *__restrict__ dqkv, int N, int h, float scale, uint64_t seed,
@@ -696,10 +717,12 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
     constexpr int SF = (Q8 & 1) ? 16 : 8;    // dK / dV stores of one item's flush
     [[maybe_unused]] float q8_inv = 0.f, qmax = 0.f;
     if constexpr (Q8 != 0) { const float sc = *q8_scale; q8_inv = sc > 0.f ? 1.0f / sc : 0.f; }
-    constexpr int NQ = 512, IMG = 32768, DSB = 16384, SLAB = 12288;
-    __shared__ __attribute__((aligned(1024))) char smem[2 * IMG + 4 * SLAB + 2 * DSB + 2 * NQ * 4 + 2 * 32 * 4];
+    constexpr int IMG = 32768, DSB = 16384, SLAB = 12288;
+    constexpr int LBUF = NQ == 512 ? 2 : 1, LPL = NQ / 512;   // LSE row buffers; LSE values per lane (loads of the next item's row)
+    static_assert(NQ == 512 || NQ == 2048, "NQ");
+    __shared__ __attribute__((aligned(1024))) char smem[2 * IMG + 4 * SLAB + 2 * DSB + LBUF * NQ * 4 + 2 * 32 * 4];
     char *const Kimg0 = smem, *const slab0 = smem + 2 * IMG, *const dSimg = slab0 + 4 * SLAB;
-    float *const lse_s = reinterpret_cast<float *>(dSimg + 2 * DSB), *const delta_s = lse_s + 2 * NQ;
+    float *const lse_s = reinterpret_cast<float *>(dSimg + 2 * DSB), *const delta_s = lse_s + LBUF * NQ;
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -777,6 +800,12 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
         const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void *)(lse + (int64_t)x.bh * N), 0, (uint32_t)N * 4u, 0x00020000);
         return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rl, (int)threadIdx.x * 4, 0, 0));   // scaled by log2(e) when stored
     };
+    auto load_lse_long = [&](const Item &x, float (&l)[LPL]) {   // NQ = 2048: queries threadIdx.x + 512 i, LPL loads
+        const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void *)(lse + (int64_t)x.bh * N), 0, (uint32_t)N * 4u, 0x00020000);
+#pragma unroll
+        for (int i = 0; i < LPL; ++i)
+            l[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rl, ((int)threadIdx.x + 512 * i) * 4, 0, 0));
+    };
     // delta of the slab in ring slot `slot` -> delta_s[buf][32]: wave w owns rows 4w..4w+3, 16 lanes per row, 4 elements per lane
     auto slab_delta = [&](int slot, int buf) {
         const int row = wave * 4 + (lane >> 4), e = (lane & 15) * 4;
@@ -797,15 +826,24 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
     Item cur = make_item(it), nxt = cur;
     bf16x8 vf[4], vfn[4];
     float lse_n = 0.f;
+    [[maybe_unused]] float lse_nl[LPL];   // NQ = 2048: the next item's row, LPL values per lane
     // ---- prologue of the block's first item: K, V, LSE, slabs 0..2
     dma_k(cur, Kimg0);
     load_v(cur, vf);
-    {
+    if constexpr (NQ == 512) {
         const float l0 = load_lse(cur);
         dma_slab(cur, 0, 0);
         dma_slab(cur, 1, 1);
         dma_slab(cur, 2, 2);
         lse_s[threadIdx.x] = log2_ik - l0 * 1.44269504088896340736f;   // -LSE' = log2(1 / (1 - p_drop)) - LSE log2 e: the exponential returns p / (1 - p_drop)
+    } else {
+        float l0[LPL];
+        load_lse_long(cur, l0);
+        dma_slab(cur, 0, 0);
+        dma_slab(cur, 1, 1);
+        dma_slab(cur, 2, 2);
+#pragma unroll
+        for (int i = 0; i < LPL; ++i) lse_s[threadIdx.x + 512 * i] = log2_ik - l0[i] * 1.44269504088896340736f;
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -822,7 +860,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
         const bool has_next = next_it < nitems;
         if (has_next) nxt = make_item(next_it);
         const char *Kimg = Kimg0 + par * IMG;
-        const float *lse_c = lse_s + par * NQ;
+        const float *lse_c = lse_s + (LBUF == 2 ? par * NQ : 0);
         f32x16 dKt[2], dVt[2];
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
@@ -857,7 +895,8 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
             // ---- feed the stream: next item's K / V / LSE once, slab qb+3 (of this item or the first slabs of the next)
             if (has_next && qb == 1) {
                 dma_k(nxt, Kimg0 + (par ^ 1) * IMG);
-                lse_n = load_lse(nxt);
+                if constexpr (NQ == 512) lse_n = load_lse(nxt);
+                else load_lse_long(nxt, lse_nl);
             }
             if (qb + 3 < nqb) dma_slab(cur, qb + 3, (sl + 3) & 3);
             else if (has_next) dma_slab(nxt, qb + 3 - nqb, (sl + 3) & 3);
@@ -974,6 +1013,8 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
             // allowed in flight (youngest first), with SQ = stores of a dQ tile and SF = dK / dV stores of an item's flush:
             //   leading:  this block's 2 slab pieces [+ K / LSE prefetch 5 at qb == 1] + the previous dQ tile's SQ stores [qb == 0: + SF + SQ of the previous item]
             //   trailing: 1 slab piece [+ 5] + SQ [qb == 0: + SF + SQ]
+            //   (NQ = 2048: the LSE prefetch is LPL = 4 loads, XL = 3 more in flight at qb == 1)
+            constexpr int XL = LPL - 1;
             //   ACCUM: this block's dQ request is OLDER than its pieces and must have landed: leading 2 [+ 5]; trailing 1 + SQ [+ 5]; on an
             //   item's first block it is YOUNGER than the previous item's stores: 2 / 1
 #define ATTN_WAIT(N_) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N_) : "memory")
@@ -983,15 +1024,15 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
                 // (lockstep order: the trailing waves' dQ stores of the previous block are OLDER than this block's request)
                 constexpr int SQL = (ACCUM && !STAGGER) ? 0 : SQ;
                 if (qb == 0) { if (ACCUM) ATTN_WAIT(1); else ATTN_WAIT(1 + SF + SQ); }
-                else if (qb == 1) ATTN_WAIT(6 + SQL);
+                else if (qb == 1) ATTN_WAIT(6 + XL + SQL);
                 else ATTN_WAIT(1 + SQL);
             } else if (!ACCUM) {
                 if (qb == 0) ATTN_WAIT(2 + SF + SQ);
-                else if (qb == 1) ATTN_WAIT(7 + SQ);
+                else if (qb == 1) ATTN_WAIT(7 + XL + SQ);
                 else ATTN_WAIT(2 + SQ);
             } else {
                 if (qb == 0) ATTN_WAIT(2);
-                else if (qb == 1) ATTN_WAIT(7);
+                else if (qb == 1) ATTN_WAIT(7 + XL);
                 else ATTN_WAIT(2);
             }
 #undef ATTN_WAIT
@@ -1153,7 +1194,12 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
         // ---- switch to the next item: its K image and LSE row were fetched during query block 1, its V fragments during the drain
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) vf[ks] = vfn[ks];
-        lse_s[(par ^ 1) * NQ + threadIdx.x] = log2_ik - lse_n * 1.44269504088896340736f;
+        if constexpr (NQ == 512) {
+            lse_s[(par ^ 1) * NQ + threadIdx.x] = log2_ik - lse_n * 1.44269504088896340736f;
+        } else {   // the one row buffer: every read of the current row is behind the item's last barrier
+#pragma unroll
+            for (int i = 0; i < LPL; ++i) lse_s[threadIdx.x + 512 * i] = log2_ik - lse_nl[i] * 1.44269504088896340736f;
+        }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                 // patches drained (the next dS write may reuse them); LSE row visible
         par ^= 1;
@@ -1261,10 +1307,11 @@ template <bool MAX> __device__ __forceinline__ float cls_block_reduce(float v, f
     return r;
 }
 
-template <bool DROP>
+// NMAX: keys the score array holds (512; 2048 is launched for N > 512 only)
+template <bool DROP, int NMAX = 512>
 __global__ __launch_bounds__(CLS_THREADS) void attn_cls_fwd_kernel(const bf16_t *__restrict__ qkv, bf16_t *__restrict__ out, float *__restrict__ lse,
                                                                    int N, int h, float scale, uint64_t seed, uint32_t thresh, float inv_keep) {
-    __shared__ float sp[512];                    // scores, then dropped probabilities, per key
+    __shared__ float sp[NMAX];                   // scores, then dropped probabilities, per key
     __shared__ float ored[CLS_SLOTS][65];        // per-slot partial outputs (+1: no bank conflicts on the column sums)
     __shared__ float red[4];
     const int bh = blockIdx.x, b = bh / h, head = bh % h;
@@ -1391,6 +1438,8 @@ static int attn_fwd_device_cus() {
 #define SATTR(K, BYTES) if (hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES) != hipSuccess) return 0
     SATTR((attn_fwd_stream_kernel<true, false, 1>), 128 * 1024); SATTR((attn_fwd_stream_kernel<false, false, 1>), 128 * 1024);
     SATTR((attn_fwd_stream_kernel<true, true, 1>), 128 * 1024); SATTR((attn_fwd_stream_kernel<false, true, 1>), 128 * 1024);
+    SATTR((attn_fwd_stream_kernel<true, false, 4>), 128 * 1024); SATTR((attn_fwd_stream_kernel<false, false, 4>), 128 * 1024);
+    SATTR((attn_fwd_stream_kernel<true, true, 4>), 128 * 1024); SATTR((attn_fwd_stream_kernel<false, true, 4>), 128 * 1024);
 #ifdef ECGVIT_TOOLS
     SATTR((attn_fwd_stream_kernel<true, false, 2>), 128 * 1024); SATTR((attn_fwd_stream_kernel<false, false, 2>), 128 * 1024);
     SATTR((attn_fwd_stream_kernel<true, true, 2>), 128 * 1024); SATTR((attn_fwd_stream_kernel<false, true, 2>), 128 * 1024);
@@ -1406,7 +1455,7 @@ static int attn_fwd_device_cus() {
 
 static int attention_fwd_launch(const void *qkv, void *out, float *lse, int B, int N, int h, int dh, float scale, float dropout_p,
                                 uint64_t seed, int dtype, void *stream, void *out8, const float *q8_scale, float *q8_amax) {
-    if (dtype != ECGVIT_BF16 || dh != 64 || N < 1 || N > 512 || B < 1 || h < 1) return ECGVIT_EINVAL;
+    if (dtype != ECGVIT_BF16 || dh != 64 || N < 1 || N > ECGVIT_ATTN_MAX_N || B < 1 || h < 1) return ECGVIT_EINVAL;
     if ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(out)) % 16) return ECGVIT_EINVAL;
     if (out8 && (!q8_scale || !q8_amax || reinterpret_cast<uintptr_t>(out8) % 16)) return ECGVIT_EINVAL;   // (16-B stores)
     if (dropout_p > 0.f && dropout_threshold8(dropout_p) == 0) return ECGVIT_EINVAL;   // p < 1/512 would silently round to no dropout
@@ -1416,7 +1465,27 @@ static int attention_fwd_launch(const void *qkv, void *out, float *lse, int B, i
     // is an item per CU (256 x 16 x 501: 494 against 533 us, 8-bit emitting 523 against 575; profiles/r06_attn_fwd_stream.txt); below that the one-item
     // kernel, whose B*h workgroups spread over more CUs.  Up to 256 tokens the one-item kernel stays (512 x 12 x 251: 215 against 236 us streamed -- with two
     // items side by side a window is four key tiles, and the sixteen waves meet at a barrier every four tiles)
-    {
+    // Records of more than 512 tokens: the streamed form with an item per (record, head, 512-query block) (MODE 4) once there is an item per CU; below
+    // that the split one-item kernel below, which is general in N (one workgroup per 256 queries, all keys in 256-key windows: B*h*ceil(N / 256)
+    // workgroups, two per CU, spread over more CUs than the B*h*ceil(N / 512) items of the streamed form would)
+    if (N > 512) {
+        const int n_cu = attn_fwd_device_cus();
+        if (n_cu <= 0) return ECGVIT_ELAUNCH;
+        const int64_t nitems = (int64_t)B * h * ((N + 511) / 512);
+        bool stream_form = nitems >= n_cu && nitems < (1ll << 31) && (int64_t)N * 3 * h * 64 * 2 < (1ll << 31);
+#ifdef ECGVIT_TOOLS
+        if (g_tools_attn_fwd_variant == 0) stream_form = false;   // (tests hold the two forms against each other bit for bit)
+#endif
+        if (stream_form) {
+#define LFWD(DR, Q) hipLaunchKernelGGL((attn_fwd_stream_kernel<DR, Q, 4>), dim3((unsigned)n_cu), dim3(1024), 128 * 1024, as_stream(stream), (const bf16_t *)qkv, \
+                                       (bf16_t *)out, lse, N, h, scale, seed, th, ik, (int)nitems, (uint8_t *)out8, q8_scale, q8_amax)
+            if (out8) { if (th) LFWD(true, true); else LFWD(false, true); }
+            else { if (th) LFWD(true, false); else LFWD(false, false); }
+#undef LFWD
+            ECGVIT_CHECK_LAUNCH();
+            return ECGVIT_OK;
+        }
+    } else {
         const int n_cu = attn_fwd_device_cus();
         if (n_cu <= 0) return ECGVIT_ELAUNCH;
         // (MODE 2 / 3 -- the two forms for up to 256 tokens, both slower than the one-item kernel there -- exist in the TOOLS build only: tools/attn_fwd_ab.py,
@@ -1475,7 +1544,7 @@ int ecgvit_attention_fwd_q8(const void *qkv, void *out, float *lse, int B, int N
 }
 
 static int attention_bwd_args_ok(const void *qkv, const void *out, const void *dout, void *dqkv, int B, int N, int h, int dh, int dtype) {
-    if (dtype != ECGVIT_BF16 || dh != 64 || N < 1 || N > 512 || B < 1 || h < 1) return 0;
+    if (dtype != ECGVIT_BF16 || dh != 64 || N < 1 || N > ECGVIT_ATTN_MAX_N || B < 1 || h < 1) return 0;
     return (reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(dqkv)) % 16 == 0;
 }
 
@@ -1506,6 +1575,7 @@ static int attention_bwd_launch(const void *qkv, const void *out, const void *do
     }
     if (dqkv8 && (!q8_scale || !q8_amax || reinterpret_cast<uintptr_t>(dqkv8) % 8)) return ECGVIT_EINVAL;
     if (dropout_p > 0.f && dropout_threshold8(dropout_p) == 0) return ECGVIT_EINVAL;   // p < 1/512 would silently round to no dropout
+    if (N > 512 && dqkv8) return ECGVIT_EINVAL;   // (no 8-bit emission above 512 tokens: the caller quantises dqkv itself)
     const uint32_t th = dropout_threshold8(dropout_p);
     const float ik = dropout_inv_keep8(dropout_p);
     const int nitems = B * h;
@@ -1520,6 +1590,18 @@ static int attention_bwd_launch(const void *qkv, const void *out, const void *do
 // tables replaced by the wave's one offset -- and it still spilled those four (the peak is inside the block's vector phase, not in what lives across it),
 // while the other instantiations got 1.6-2 % SLOWER with the different allocation: taken out again)
 #define PERS8(DR, AC, K0, Q) hipLaunchKernelGGL((attn_bwd_pers_kernel<DR, AC, !(DR && AC && Q == 3), Q>), PERS_ARGS(K0), (uint8_t *)dqkv8, q8_scale, q8_amax)
+    if (N > 512) {
+        // one launch per 256-key window (up to eight): dK / dV of a window are final in its launch; dQ is stored by the first and read, added to and
+        // stored again in bf16 by every later one, in stream order (tests/test_gpu_long_attention.py holds the sum of eight windows against fp64)
+#define PERSL(DR, AC, K0) hipLaunchKernelGGL((attn_bwd_pers_kernel<DR, AC, !(DR && AC), 0, 2048>), PERS_ARGS(K0))
+        for (int k0 = 0; k0 < N; k0 += 256) {
+            if (k0 == 0) { if (th) PERSL(true, false, 0); else PERSL(false, false, 0); }
+            else { if (th) PERSL(true, true, k0); else PERSL(false, true, k0); }
+            ECGVIT_CHECK_LAUNCH();
+        }
+#undef PERSL
+        return ECGVIT_OK;
+    }
     if (dqkv8) {
         // one window: dK / dV / dQ all final in this launch; two windows: the first emits its dK / dV, the second its dK / dV and the final dQ
         if (N <= 256) { if (th) PERS8(true, false, 0, 3); else PERS8(false, false, 0, 3); }
@@ -1554,7 +1636,7 @@ int ecgvit_attention_bwd_q8(const void *qkv, const void *out, const void *dout, 
     return attention_bwd_launch(qkv, out, dout, lse, dqkv, B, N, h, dh, scale, dropout_p, seed, ECGVIT_BF16, stream, dqkv8, q8_scale, q8_amax);
 }
 
-static int attention_cls_args_ok(int B, int N, int h, int dh) { return dh == 64 && N >= 1 && N <= 512 && B >= 1 && h >= 1 && (int64_t)B * h < (1ll << 31); }
+static int attention_cls_args_ok(int B, int N, int h, int dh) { return dh == 64 && N >= 1 && N <= ECGVIT_ATTN_MAX_N && B >= 1 && h >= 1 && (int64_t)B * h < (1ll << 31); }
 
 int ecgvit_attention_cls_fwd(const void *qkv, void *out_cls, float *lse_cls, int B, int N, int h, int dh, float scale, float dropout_p, uint64_t seed,
                              int dtype, void *stream) {
@@ -1563,8 +1645,10 @@ int ecgvit_attention_cls_fwd(const void *qkv, void *out_cls, float *lse_cls, int
     if (dropout_p > 0.f && dropout_threshold8(dropout_p) == 0) return ECGVIT_EINVAL;   // p < 1/512 would silently round to no dropout
     const uint32_t th = dropout_threshold8(dropout_p);
     const float ik = dropout_inv_keep8(dropout_p);
-    if (th) hipLaunchKernelGGL(attn_cls_fwd_kernel<true>, dim3(B * h), dim3(CLS_THREADS), 0, as_stream(stream), (const bf16_t *)qkv, (bf16_t *)out_cls, lse_cls, N, h, scale, seed, th, ik);
-    else hipLaunchKernelGGL(attn_cls_fwd_kernel<false>, dim3(B * h), dim3(CLS_THREADS), 0, as_stream(stream), (const bf16_t *)qkv, (bf16_t *)out_cls, lse_cls, N, h, scale, seed, th, ik);
+#define CLS_FWD(DR, NM) hipLaunchKernelGGL((attn_cls_fwd_kernel<DR, NM>), dim3(B * h), dim3(CLS_THREADS), 0, as_stream(stream), (const bf16_t *)qkv, (bf16_t *)out_cls, lse_cls, N, h, scale, seed, th, ik)
+    if (N <= 512) { if (th) CLS_FWD(true, 512); else CLS_FWD(false, 512); }
+    else { if (th) CLS_FWD(true, 2048); else CLS_FWD(false, 2048); }
+#undef CLS_FWD
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
 }

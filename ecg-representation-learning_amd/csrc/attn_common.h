@@ -7,6 +7,9 @@
 #pragma once
 #include "common.h"
 
+// longest record (tokens) the fused bf16 attention covers: the forward, backward and CLS-row entry points return ECGVIT_EINVAL above it
+#define ECGVIT_ATTN_MAX_N 2048
+
 namespace {
 
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;

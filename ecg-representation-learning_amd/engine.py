@@ -98,8 +98,8 @@ class VitEngine:
         if dtype == torch.bfloat16:
             if self.dh != 64:
                 raise ValueError(f'bf16 fused attention needs head dim 64 (got {self.dh}); use dtype=torch.float32')
-            if self.N > 512:
-                raise ValueError(f'bf16 fused attention covers <= 512 tokens (got {self.N}); use dtype=torch.float32')
+            if self.N > 2048:
+                raise ValueError(f'bf16 fused attention covers <= 2048 tokens (got {self.N}); use dtype=torch.float32')
             for nm, pv in (('hidden_dropout_prob', self.p_hidden), ('attention_probs_dropout_prob (the embedding dropout: reference ecg_vit.py:113)', self.p_emb)):
                 if 0.0 < pv < 1.0 / 512:
                     # every dropout site of the bf16 path draws 8 random bits per element: p is applied as round(256 p) / 256 (0.1 -> 0.1016)
