@@ -1,4 +1,4 @@
-// Fused multi-head self-attention core for the bf16 path (dh = 64, N <= 256 tokens): scores never touch HBM.
+// Fused multi-head self-attention core for the bf16 path (dh = 64, N <= 256 tokens): scores never touch HBM.  (dh = 128: attention_h128.hip.)
 //
 // One workgroup owns one (record, head): its whole K/V (<= 256 x 64 bf16 = 32 KiB each) sits in LDS, so softmax
 // is single-pass (no online rescale) and the backward needs no atomics -- dQ, dK, dV of a head are all produced
@@ -17,6 +17,7 @@
 //   -> ds_read_b128 row reads (MFMA K-contiguous operand) hit 16 distinct slots per 16-lane group, and
 //   -> ds_read_b64_tr_b16 reads of 4 consecutive rows x 64 B land in the 4 different 64-B quarters of the bank row.
 #include "attn_common.h"
+#include "attn_h128.h"
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -1455,12 +1456,16 @@ static int attn_fwd_device_cus() {
 
 static int attention_fwd_launch(const void *qkv, void *out, float *lse, int B, int N, int h, int dh, float scale, float dropout_p,
                                 uint64_t seed, int dtype, void *stream, void *out8, const float *q8_scale, float *q8_amax) {
-    if (dtype != ECGVIT_BF16 || dh != 64 || N < 1 || N > ECGVIT_ATTN_MAX_N || B < 1 || h < 1) return ECGVIT_EINVAL;
+    if (dtype != ECGVIT_BF16 || (dh != 64 && dh != 128) || N < 1 || N > ECGVIT_ATTN_MAX_N || B < 1 || h < 1) return ECGVIT_EINVAL;
     if ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(out)) % 16) return ECGVIT_EINVAL;
     if (out8 && (!q8_scale || !q8_amax || reinterpret_cast<uintptr_t>(out8) % 16)) return ECGVIT_EINVAL;   // (16-B stores)
     if (dropout_p > 0.f && dropout_threshold8(dropout_p) == 0) return ECGVIT_EINVAL;   // p < 1/512 would silently round to no dropout
     const uint32_t th = dropout_threshold8(dropout_p);
     const float ik = dropout_inv_keep8(dropout_p);
+    if (dh == 128) {   // attention_h128.hip (no 8-bit emission: the caller quantises `out` itself)
+        if (out8) return ECGVIT_EINVAL;
+        return attn_h128_fwd(qkv, out, lse, B, N, h, scale, seed, th, ik, stream);
+    }
     // the STREAMED form (one persistent 16-wave workgroup per CU, K / V windows through a two-slot ring) for records of more than 256 tokens once there
     // is an item per CU (256 x 16 x 501: 494 against 533 us, 8-bit emitting 523 against 575; profiles/r06_attn_fwd_stream.txt); below that the one-item
     // kernel, whose B*h workgroups spread over more CUs.  Up to 256 tokens the one-item kernel stays (512 x 12 x 251: 215 against 236 us streamed -- with two
@@ -1544,7 +1549,7 @@ int ecgvit_attention_fwd_q8(const void *qkv, void *out, float *lse, int B, int N
 }
 
 static int attention_bwd_args_ok(const void *qkv, const void *out, const void *dout, void *dqkv, int B, int N, int h, int dh, int dtype) {
-    if (dtype != ECGVIT_BF16 || dh != 64 || N < 1 || N > ECGVIT_ATTN_MAX_N || B < 1 || h < 1) return 0;
+    if (dtype != ECGVIT_BF16 || (dh != 64 && dh != 128) || N < 1 || N > ECGVIT_ATTN_MAX_N || B < 1 || h < 1) return 0;
     return (reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(dqkv)) % 16 == 0;
 }
 
@@ -1552,7 +1557,7 @@ static int attention_bwd_args_ok(const void *qkv, const void *out, const void *d
 // sequences (N <= 128) and the independent implementation the tests hold the persistent kernel against (exported by the tools library).
 static int attention_bwd_oneitem(const void *qkv, const void *out, const void *dout, const float *lse, void *dqkv, int B, int N, int h,
                                  int dh, float scale, float dropout_p, uint64_t seed, int dtype, void *stream) {
-    if (!attention_bwd_args_ok(qkv, out, dout, dqkv, B, N, h, dh, dtype) || N > 256) return ECGVIT_EINVAL;
+    if (!attention_bwd_args_ok(qkv, out, dout, dqkv, B, N, h, dh, dtype) || dh != 64 || N > 256) return ECGVIT_EINVAL;
     if (dropout_p > 0.f && dropout_threshold8(dropout_p) == 0) return ECGVIT_EINVAL;   // p < 1/512 would silently round to no dropout
     const uint32_t th = dropout_threshold8(dropout_p);
     const float ik = dropout_inv_keep8(dropout_p);
@@ -1569,6 +1574,11 @@ static int attention_bwd_launch(const void *qkv, const void *out, const void *do
                                 int dh, float scale, float dropout_p, uint64_t seed, int dtype, void *stream, void *dqkv8, const float *q8_scale,
                                 float *q8_amax) {
     if (!attention_bwd_args_ok(qkv, out, dout, dqkv, B, N, h, dh, dtype)) return ECGVIT_EINVAL;
+    if (dh == 128) {   // attention_h128.hip (no 8-bit emission: the caller quantises dqkv itself)
+        if (dqkv8) return ECGVIT_EINVAL;
+        if (dropout_p > 0.f && dropout_threshold8(dropout_p) == 0) return ECGVIT_EINVAL;
+        return attn_h128_bwd(qkv, out, dout, lse, dqkv, B, N, h, scale, seed, dropout_threshold8(dropout_p), dropout_inv_keep8(dropout_p), stream);
+    }
     if (N <= 128 || (int64_t)N * 3 * h * 64 * 2 >= (1ll << 31)) {   // short sequences / 32-bit buffer offsets exhausted
         if (dqkv8) return ECGVIT_EINVAL;   // the one-item kernel has no 8-bit emission: the caller quantises dqkv itself
         return attention_bwd_oneitem(qkv, out, dout, lse, dqkv, B, N, h, dh, scale, dropout_p, seed, dtype, stream);
@@ -1636,7 +1646,7 @@ int ecgvit_attention_bwd_q8(const void *qkv, const void *out, const void *dout, 
     return attention_bwd_launch(qkv, out, dout, lse, dqkv, B, N, h, dh, scale, dropout_p, seed, ECGVIT_BF16, stream, dqkv8, q8_scale, q8_amax);
 }
 
-static int attention_cls_args_ok(int B, int N, int h, int dh) { return dh == 64 && N >= 1 && N <= ECGVIT_ATTN_MAX_N && B >= 1 && h >= 1 && (int64_t)B * h < (1ll << 31); }
+static int attention_cls_args_ok(int B, int N, int h, int dh) { return (dh == 64 || dh == 128) && N >= 1 && N <= ECGVIT_ATTN_MAX_N && B >= 1 && h >= 1 && (int64_t)B * h < (1ll << 31); }
 
 int ecgvit_attention_cls_fwd(const void *qkv, void *out_cls, float *lse_cls, int B, int N, int h, int dh, float scale, float dropout_p, uint64_t seed,
                              int dtype, void *stream) {
@@ -1645,6 +1655,7 @@ int ecgvit_attention_cls_fwd(const void *qkv, void *out_cls, float *lse_cls, int
     if (dropout_p > 0.f && dropout_threshold8(dropout_p) == 0) return ECGVIT_EINVAL;   // p < 1/512 would silently round to no dropout
     const uint32_t th = dropout_threshold8(dropout_p);
     const float ik = dropout_inv_keep8(dropout_p);
+    if (dh == 128) return attn_h128_cls_fwd(qkv, out_cls, lse_cls, B, N, h, scale, seed, th, ik, stream);
 #define CLS_FWD(DR, NM) hipLaunchKernelGGL((attn_cls_fwd_kernel<DR, NM>), dim3(B * h), dim3(CLS_THREADS), 0, as_stream(stream), (const bf16_t *)qkv, (bf16_t *)out_cls, lse_cls, N, h, scale, seed, th, ik)
     if (N <= 512) { if (th) CLS_FWD(true, 512); else CLS_FWD(false, 512); }
     else { if (th) CLS_FWD(true, 2048); else CLS_FWD(false, 2048); }
@@ -1661,6 +1672,7 @@ int ecgvit_attention_cls_bwd(const void *qkv, const void *out_cls, const void *d
     if (dropout_p > 0.f && dropout_threshold8(dropout_p) == 0) return ECGVIT_EINVAL;
     const uint32_t th = dropout_threshold8(dropout_p);
     const float ik = dropout_inv_keep8(dropout_p);
+    if (dh == 128) return attn_h128_cls_bwd(qkv, out_cls, dout_cls, lse_cls, dqkv, dq_cls, B, N, h, scale, seed, th, ik, stream);
 #define CLS_BWD(DR) hipLaunchKernelGGL(attn_cls_bwd_kernel<DR>, dim3(B * h), dim3(CLS_THREADS), 0, as_stream(stream), (const bf16_t *)qkv, \
                                        (const bf16_t *)out_cls, (const bf16_t *)dout_cls, lse_cls, (bf16_t *)dqkv, (bf16_t *)dq_cls, N, h, scale, seed, th, ik)
     if (th) CLS_BWD(true); else CLS_BWD(false);

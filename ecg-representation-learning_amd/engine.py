@@ -96,8 +96,8 @@ class VitEngine:
         if h == 1:
             raise NotImplementedError('heads == 1 (vit_pytorch drops to_out) is not covered by the HIP path')
         if dtype == torch.bfloat16:
-            if self.dh != 64:
-                raise ValueError(f'bf16 fused attention needs head dim 64 (got {self.dh}); use dtype=torch.float32')
+            if self.dh not in (64, 128):
+                raise ValueError(f'bf16 fused attention needs head dim 64 or 128 (got {self.dh}); use dtype=torch.float32')
             if self.N > 2048:
                 raise ValueError(f'bf16 fused attention covers <= 2048 tokens (got {self.N}); use dtype=torch.float32')
             for nm, pv in (('hidden_dropout_prob', self.p_hidden), ('attention_probs_dropout_prob (the embedding dropout: reference ecg_vit.py:113)', self.p_emb)):
@@ -521,7 +521,7 @@ class VitEngine:
             self._linear(8 * i + 0, L['xn1'], lp + '0.fn.to_qkv.weight', L['qkv'], M, 3 * d, d, a8=L.get('xn1_8'), prequant=q1)
             qa = False   # fp8_linear: the attention kernel wrote the e4m3 copy of its output itself
             if self.dtype == torch.bfloat16:
-                if f8 and (8 * i + 1) in self._f8_seen:
+                if f8 and (8 * i + 1) in self._f8_seen and dh == 64:   # (dh = 128: no 8-bit emission, _linear quantises attn)
                     check(l.ecgvit_attention_fwd_q8(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), B, N, h, dh, self.scale, ph, s0 + 1, ptr(L['attn_8']),
                                                     ptr(self.f8_scale[8 * i + 1:8 * i + 2]), ptr(self.f8_amax[8 * i + 1:8 * i + 2]), st), 'attention_fwd_q8')
                     qa = True
@@ -832,7 +832,7 @@ class VitEngine:
             self._dgrad(dY, lp + '0.fn.to_out.0.weight', a['dattn'], M, d, d, site=8 * i + 6, pre=g6)
             pq7 = False   # fp8_linear: the attention backward wrote the e5m2 copy of dqkv itself (into the operand scratch)
             if self.dtype == torch.bfloat16:
-                if f8 and (8 * i + 7) in self._f8_seen and 128 < N <= 512 and N * 3 * d * 2 < 2 ** 31:
+                if f8 and (8 * i + 7) in self._f8_seen and dh == 64 and 128 < N <= 512 and N * 3 * d * 2 < 2 ** 31:   # (dh = 128: _grad8 quantises dqkv)
                     check(l.ecgvit_attention_bwd_q8(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), B, N, h, dh, self.scale,
                                                     ph, s0 + 1, ptr(a['q8']), ptr(self.f8_scale[8 * i + 7:8 * i + 8]), ptr(self.f8_amax[8 * i + 7:8 * i + 8]), st),
                           'attention_bwd_q8')

@@ -220,8 +220,10 @@ int ecgvit_colsum(const void *in, int64_t ld, float *out, void *partial, int64_t
  * Multi-head self-attention core, fused (bf16 path).  replaces vit_pytorch Attention.forward between
  * to_qkv and to_out: split heads, dots = q k^T * dh^-0.5, softmax, (dropout), attn v, merge heads.
  * qkv: [B*N, 3*h*dh] (columns [q | k | v], head-major inside each) ; out: [B*N, h*dh] ; lse: [B,h,N] f32.
- * bf16 path requires dh == 64 and N <= 2048 (online softmax over 32-key tiles; the backward takes N > 256 as one launch per 256-key window,
- * each window after the first adding its dQ to the bf16 dQ already in dqkv).  Dropout hash index (bh N + q) ceil(N/4) + key/4 is uint32 and
+ * bf16 path requires dh == 64 or dh == 128 and N <= 2048; every other dh returns ECGVIT_EINVAL.  dh == 64: online softmax over 32-key tiles;
+ * the backward takes N > 256 as one launch per 256-key window, each window after the first adding its dQ to the bf16 dQ already in dqkv.
+ * dh == 128: online softmax over 64-key windows; the backward is two launches (dK / dV per 128-key block, then dQ with P recomputed), no
+ * accumulation across launches.  Same layouts, LSE convention and dropout bits for both head dims.  Dropout hash index (bh N + q) ceil(N/4) + key/4 is uint32 and
  * wraps for B h N ceil(N/4) >= 2^32 (e.g. B h = 8192 at N > ~1 450): deterministic, a mask repeats there.
  * Probability dropout of the fused kernels: one 8-bit hash per 4 consecutive keys, so the probability APPLIED is
  * round(256 p) / 256 (p = 0.1 -> 26/256 = 0.1016), kept values rescaled by the exact 256 / (256 - round(256 p)); 0 < p < 1/512 cannot be
@@ -229,14 +231,14 @@ int ecgvit_colsum(const void *in, int64_t ld, float *out, void *partial, int64_t
  * ------------------------------------------------------------------------------------------------ */
 int ecgvit_attention_fwd(const void *qkv, void *out, float *lse, int B, int N, int h, int dh, float scale,
                          float dropout_p, uint64_t seed, int dtype, void *stream);
-/* fp8 operand path: the same forward that also writes out8 = saturate(out as stored / *q8_scale) in e4m3 (same [B*N, h*dh] layout, one byte
+/* fp8 operand path (dh == 64 only: ECGVIT_EINVAL for dh == 128, the caller quantises `out` itself): the same forward that also writes out8 = saturate(out as stored / *q8_scale) in e4m3 (same [B*N, h*dh] layout, one byte
  * per element, 16-byte aligned) and accumulates *q8_amax = max(*q8_amax, max |out|): the 8-bit operand of the out-projection's product, without a quantise pass */
 int ecgvit_attention_fwd_q8(const void *qkv, void *out, float *lse, int B, int N, int h, int dh, float scale, float dropout_p,
                             uint64_t seed, void *out8, const float *q8_scale, float *q8_amax, void *stream);
 int ecgvit_attention_bwd(const void *qkv, const void *out, const void *dout, const float *lse, void *dqkv,
                          int B, int N, int h, int dh, float scale, float dropout_p, uint64_t seed, int dtype,
                          void *stream);
-/* fp8 operand path (128 < N <= 512 only: ECGVIT_EINVAL otherwise -- also for 512 < N <= 2048 -- the caller then quantises dqkv itself): the same backward that also writes
+/* fp8 operand path (dh == 64 and 128 < N <= 512 only: ECGVIT_EINVAL otherwise -- also for 512 < N <= 2048 -- the caller then quantises dqkv itself): the same backward that also writes
  * dqkv8 = saturate(dqkv as stored / *q8_scale) in e5m2 (same [B*N, 3*h*dh] layout, one byte per element) and accumulates
  * *q8_amax = max(*q8_amax, max |dqkv|): the 8-bit operand of the QKV projection's two backward products, without a quantise pass */
 int ecgvit_attention_bwd_q8(const void *qkv, const void *out, const void *dout, const float *lse, void *dqkv,
@@ -244,7 +246,7 @@ int ecgvit_attention_bwd_q8(const void *qkv, const void *out, const void *dout, 
                             const float *q8_scale, float *q8_amax, void *stream);
 /* CLS-row attention (the pruned last block of the supervised step: the classifier reads row 0 of each record only).  Query row 0 of every
  * (record, head) against all N keys of `qkv` (layout as above): out_cls [B, h*dh] compact = row 0 of ecgvit_attention_fwd's out,
- * lse_cls [B, h] = its log-sum-exp, the same attention-dropout bits (bf16, dh == 64, N <= 2048). */
+ * lse_cls [B, h] = its log-sum-exp, the same attention-dropout bits (bf16, dh == 64 or 128, N <= 2048). */
 int ecgvit_attention_cls_fwd(const void *qkv, void *out_cls, float *lse_cls, int B, int N, int h, int dh, float scale, float dropout_p,
                              uint64_t seed, int dtype, void *stream);
 /* its backward for an upstream gradient dout_cls [B, h*dh] on row 0 only: writes the K and V columns of dqkv for EVERY row (what

@@ -1,0 +1,65 @@
+"""CPU: the bf16 engine takes 128-wide attention heads (dh = 128, the kernels of attention_h128.hip) at 1 to 2048 tokens, still rejects every other
+head dim but 64, and the dh = 128 kernels are spill-free and inside the budgets their comments state (code-object metadata, tools/code_objects.py;
+no GPU)."""
+import os
+import sys
+
+import pytest
+import torch
+
+from conftest import ROOT
+
+from ecg_representation_learning_amd.engine import VitEngine
+
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+LIB = os.path.join(ROOT, 'ecg-representation-learning_amd', 'libecgvit_hip.so')
+
+
+def _engine(N, d, h, **kw):
+    P = 4
+    return VitEngine(C=12, L=P * (N - 1), P=P, d=d, h=h, f=4 * d, Ly=2, K=5, p_hidden=0.1, p_emb=0.1, dtype=torch.bfloat16, layout=None, **kw)
+
+
+@pytest.mark.parametrize('N', [41, 251, 501, 1251, 2048])
+@pytest.mark.parametrize('d,h', [(256, 2), (768, 6), (1024, 8)])
+def test_bf16_engine_takes_head_dim_128(N, d, h):
+    eng = _engine(N, d, h)
+    assert eng.N == N and eng.dh == 128
+
+
+@pytest.mark.parametrize('N', [251, 1251])
+def test_bf16_fp8_engine_takes_head_dim_128(N):
+    eng = _engine(N, 1024, 8, fp8_linear=True)
+    assert eng.N == N and eng.dh == 128 and eng.fp8
+
+
+@pytest.mark.parametrize('d,h', [(256, 16), (384, 12), (1024, 4)])   # dh 16, 32, 256
+def test_bf16_engine_rejects_other_head_dims(d, h):
+    with pytest.raises(ValueError, match='head dim'):
+        _engine(251, d, h)
+
+
+# kernel-name stem -> (VGPR budget stated in attention_h128.hip, LDS bytes)
+BUDGETS = {'attn128_fwd_kernel': (168, 32768), 'attn128_bwd_dkv_kernel': (256, 49408), 'attn128_bwd_dq_kernel': (256, 32768),
+           'attn128_cls_fwd_kernel': (128, 16464), 'attn128_cls_bwd_kernel': (128, 8256)}
+
+
+@pytest.fixture(scope='module')
+def kernels():
+    import code_objects
+    if not os.path.exists(code_objects.READELF):
+        pytest.skip('llvm-readelf not in this image')
+    return code_objects.kernels(LIB)
+
+
+def test_head_dim_128_kernels_spill_free_and_inside_budget(kernels):
+    seen = {}
+    for name, k in kernels.items():
+        for stem, (vgprs, lds) in BUDGETS.items():
+            if stem in name:
+                seen[stem] = seen.get(stem, 0) + 1
+                assert k['vgpr_spill_count'] == 0 and k['sgpr_spill_count'] == 0, (name, k)
+                assert k['private_segment_fixed_size'] == 0, (name, k)
+                assert k['vgpr_count'] <= vgprs, (name, k['vgpr_count'], vgprs)
+                assert k['group_segment_fixed_size'] <= lds, (name, k['group_segment_fixed_size'], lds)
+    assert seen == {stem: 2 for stem in BUDGETS}, seen   # with and without dropout
