@@ -170,11 +170,11 @@ class _EcgVitFunction(torch.autograd.Function):
     """One autograd node for the whole model: forward and backward are the engine's kernel schedules."""
 
     @staticmethod
-    def forward(ctx, model, x, labels, weight, reduction, *params):
+    def forward(ctx, model, x, labels, weight, reduction, lengths, *params):
         eng = model._engine()
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if (model.training and model._has_dropout) else 0
         logits, loss_elem, loss_mean = eng.forward(x, labels, weight, training=model.training, seed=seed,
-                                                   want_mean=(reduction == 'mean'))
+                                                   want_mean=(reduction == 'mean'), lengths=lengths)
         model._fwd_id += 1
         ctx.model, ctx.fwd_id, ctx.reduction, ctx.has_labels = model, model._fwd_id, reduction, labels is not None
         ctx.set_materialize_grads(False)
@@ -198,7 +198,7 @@ class _EcgVitFunction(torch.autograd.Function):
         eng = model._engine()
         B, K = eng.saved['B'], eng.K
         if (gloss is None or not ctx.has_labels) and glogits is None:
-            return (None,) * (5 + len(model._own_list))
+            return (None,) * (6 + len(model._own_list))
         keep, aliased = _grads_living_in_flat_buffer(model, model._own_names, model._own_list)
         if gloss is not None and ctx.has_labels:
             if glogits is not None:
@@ -209,7 +209,7 @@ class _EcgVitFunction(torch.autograd.Function):
                 eng.backward(gelem=gloss.contiguous().float(), gscale=1.0)
         else:
             eng.backward(glogits=glogits.contiguous().float())
-        return (None, None, None, None, None) + _grads_out(model, model._own_names, keep, aliased)
+        return (None, None, None, None, None, None) + _grads_out(model, model._own_names, keep, aliased)
 
 
 def _grads_living_in_flat_buffer(model, names, params):
@@ -306,7 +306,11 @@ class EcgVit(nn.Module):
     def loss_reduction(self, r):
         self.loss_fn.reduction = self._loss_reduction = r
 
-    def forward(self, sample_values: torch.FloatTensor, labels: torch.LongTensor = None):
+    def forward(self, sample_values: torch.FloatTensor, labels: torch.LongTensor = None, lengths: torch.Tensor = None):
+        """sample_values (B, C, L'): L' <= max_signal_length, a multiple of patch_size (position rows 0..L'/P, as vit-pytorch slices them).
+        lengths: optional (B,) integer tensor (host or device) of per-record sample counts inside sample_values, each a positive multiple of
+        patch_size and at most L': record b's logits, loss terms and gradient contribution are those of sample_values[b:b+1, :, :lengths[b]]
+        alone (dropout 0; up to summation order); samples past lengths[b] are never read.  Not with fp8_linear or a fused input transform."""
         if not sample_values.is_cuda:
             raise RuntimeError('EcgVit (HIP) runs on an MI355X device only: move the model and inputs to "cuda" '
                                '(there is deliberately no CPU fallback)')
@@ -316,7 +320,7 @@ class EcgVit(nn.Module):
             y = labels.contiguous().float()
             if self.loss_weight:  # reference :144-147: per-element weight looked up by the label value
                 w = torch.tensor(self.loss_weight, device=y.device, dtype=torch.float32)[y.long()].contiguous()
-        loss, logits = _EcgVitFunction.apply(self, x, y, w, self._loss_reduction, *self._own_list)
+        loss, logits = _EcgVitFunction.apply(self, x, y, w, self._loss_reduction, lengths, *self._own_list)
         return ModelOutput(loss=loss if labels is not None else None, logits=logits)
 
     # ------------------------------------------------------------------ flat HBM layout of the parameters
@@ -406,6 +410,7 @@ class EcgVit(nn.Module):
         eng = self._engine()
         x = sample_values.contiguous().float()
         B = x.shape[0]
+        eng._set_width(x.shape[2])
         eng._alloc(B)
         a = eng.act
         hip.check(hip.lib().ecgvit_patch_gather(x.data_ptr(), a['patches'].data_ptr(), B, eng.C, eng.L, eng.P, eng.CP,

@@ -73,6 +73,29 @@ class ParamLayout:
         return [(k, v) for k, v in out if v]
 
 
+def check_lengths(lengths, B, P, width):
+    """Per-record sample counts of a (B, C, width) batch -> int32 token counts n_tok = lengths / P + 1 on the lengths' own device, or None when
+    every record fills the width (the uniform kernels then run).  Each entry must be a positive multiple of P and at most `width`, else
+    ValueError.  Host tensors are checked on the host (no device round trip); device tensors with device reductions (blocking reads)."""
+    if not isinstance(lengths, torch.Tensor):
+        raise ValueError(f'lengths must be a (B,) integer tensor, got {type(lengths).__name__}')
+    if lengths.dim() != 1 or lengths.shape[0] != B:
+        raise ValueError(f'lengths must have shape (batch={B},), got {tuple(lengths.shape)}')
+    if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
+        raise ValueError(f'lengths must be an integer tensor, got {lengths.dtype}')
+    t = lengths.to(torch.int64)
+    lo, hi = (int(t.min()), int(t.max())) if B > 0 else (width, width)
+    if lo <= 0:
+        raise ValueError(f'lengths must be positive (got {lo})')
+    if hi > width:
+        raise ValueError(f'lengths must not exceed the batch width {width} (got {hi})')
+    if bool((t % P != 0).any()):
+        raise ValueError(f'lengths must be multiples of patch_size={P}')
+    if lo == width:
+        return None
+    return (t // P + 1).to(torch.int32).contiguous()
+
+
 class VitEngine:
     """Forward / backward of EcgVit for one activation dtype (torch.float32 = parity path, torch.bfloat16 =
     throughput path). Caller provides the flat buffers; all activations are allocated here, once per batch size."""
@@ -82,6 +105,9 @@ class VitEngine:
         self.C, self.L, self.P, self.d, self.h, self.f, self.Ly, self.K = C, L, P, d, h, f, Ly, K
         self.n = L // P
         self.N = self.n + 1
+        # the configured record length is the maximum: a pass over a narrower batch (L' <= L, L' % P == 0) runs at N' = L'/P + 1 tokens
+        # (`_set_width`); L / n / N below always describe the current pass
+        self.L_max, self.n_max, self.N_max = self.L, self.n, self.N
         self.dh = d // h
         self.CP = C * P
         self.p_hidden, self.p_emb = float(p_hidden), float(p_emb)
@@ -138,6 +164,16 @@ class VitEngine:
         self.input_transform = None  # FusedInputTransform: forward() then takes RAW (B, C, L_raw) records
         self.on_grads_ready = None   # callback(tag): a gradient bucket ('head' | 'layer{i}' | 'embed' | 'pretrain') is final
         self._tpw = 0                # ecgvit_gemm_desc.tiles_per_workgroup of the launches in flight (set by backward(..., tiles_per_workgroup=))
+
+    def _set_width(self, width):
+        """token geometry of the next pass: `width` samples per record (<= the configured max_signal_length, a multiple of P)"""
+        if width == self.L:
+            return
+        if not 0 < width <= self.L_max or width % self.P:
+            raise ValueError(f'a batch of {width} samples per record: must be a positive multiple of patch_size={self.P} '
+                             f'and at most max_signal_length={self.L_max}')
+        self.L, self.n = width, width // self.P
+        self.N = self.n + 1
 
     def _gemm(self, *a, **kw):
         """every product of this engine: `tiles_per_workgroup` is per-engine, per-pass state (never a process-wide setting)"""
@@ -335,7 +371,7 @@ class VitEngine:
         through prefix views: a loop that alternates train (B = 512) and eval (B = 64) batches, or ends an epoch on a short batch, re-slices instead
         of freeing and re-requesting ~40 GB (base) from the allocator on each switch.  The pool grows PER SLAB and never shrinks inside a token
         geometry; it is dropped only when the objective changes (supervised <-> masked, or another mask count)."""
-        key = (B, masked, m, self._aux8(B * (self.n if masked else self.N)))
+        key = (B, masked, m, self._aux8(B * (self.n if masked else self.N)), self.N)
         if self._alloc_key == key and self.act is not None:
             return
         self._alloc_key = key
@@ -495,6 +531,9 @@ class VitEngine:
             self._xf_keep = (mean, inv_std, t0, tl)   # keep the int32 spans alive until the kernel has run
             check(lib().ecgvit_patch_gather_transform(ptr(x), ptr(a['patches']), B, self.C, x.shape[2], self.L, self.P, self.CP, ptr(mean),
                                                       ptr(inv_std), ptr(t0), ptr(tl), T, stream()), 'patch_gather_transform')
+        elif self.saved is not None and self.saved.get('ntok') is not None:   # zero patches past each record's length
+            check(lib().ecgvit_patch_gather_varlen(ptr(x), ptr(a['patches']), ptr(self.saved['ntok']), B, self.C, self.L, self.P, self.CP, T, stream()),
+                  'patch_gather_varlen')
         else:
             check(lib().ecgvit_patch_gather(ptr(x), ptr(a['patches']), B, self.C, self.L, self.P, self.CP, T, stream()), 'patch_gather')
         self._gemm(GEMM_NT, a['patches'], W[pre + 'to_patch_embedding.1.weight'], a['tok'], B * self.n, self.d, self.CP, self.CP,
@@ -520,7 +559,11 @@ class VitEngine:
                               y8=L.get('xn1_8'))
             self._linear(8 * i + 0, L['xn1'], lp + '0.fn.to_qkv.weight', L['qkv'], M, 3 * d, d, a8=L.get('xn1_8'), prequant=q1)
             qa = False   # fp8_linear: the attention kernel wrote the e4m3 copy of its output itself
-            if self.dtype == torch.bfloat16:
+            ntok = self.saved.get('ntok')
+            if self.dtype == torch.bfloat16 and ntok is not None:
+                check(l.ecgvit_attention_varlen_fwd(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), ptr(ntok), B, N, h, dh, self.scale, ph, s0 + 1, st),
+                      'attention_varlen_fwd')
+            elif self.dtype == torch.bfloat16:
                 if f8 and (8 * i + 1) in self._f8_seen and dh == 64:   # (dh = 128: no 8-bit emission, _linear quantises attn)
                     check(l.ecgvit_attention_fwd_q8(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), B, N, h, dh, self.scale, ph, s0 + 1, ptr(L['attn_8']),
                                                     ptr(self.f8_scale[8 * i + 1:8 * i + 2]), ptr(self.f8_amax[8 * i + 1:8 * i + 2]), st), 'attention_fwd_q8')
@@ -562,8 +605,13 @@ class VitEngine:
         wqkv = W[lp + '0.fn.to_qkv.weight']   # [3d, d]: rows [q | k | v]
         self._gemm(GEMM_NT, L['xn1'], wqkv, L['qkv'], M, 2 * d, d, d, d, 3 * d, b_off=d * d, c_off=d)   # K, V of every row
         self._gemm(GEMM_NT, L['xn1'], wqkv, L['qkv'], B, d, d, N * d, d, N * 3 * d)                       # Q of the CLS rows, in place
-        check(l.ecgvit_attention_cls_fwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_lse']), B, N, h, dh, self.scale, ph, s0 + 1, T, st),
-              'attention_cls_fwd')
+        ntok = self.saved.get('ntok')
+        if ntok is not None:
+            check(l.ecgvit_attention_varlen_cls_fwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_lse']), ptr(ntok), B, N, h, dh, self.scale, ph, s0 + 1,
+                                                    st), 'attention_varlen_cls_fwd')
+        else:
+            check(l.ecgvit_attention_cls_fwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_lse']), B, N, h, dh, self.scale, ph, s0 + 1, T, st),
+                  'attention_cls_fwd')
         drop = EPI_DROPOUT if ph > 0 else 0
         self._gemm(GEMM_NT, a['cls_attn'], W[lp + '0.fn.to_out.0.weight'], a['cls_x1'], B, d, d, d, d, d, epilogue=EPI_BIAS | EPI_RESIDUAL | drop,
                    bias=P[lp + '0.fn.to_out.0.bias'], residual=X, ldr=N * d, dropout_p=ph, seed=s0 + 2, mask_row_pitch=N)
@@ -575,27 +623,44 @@ class VitEngine:
                    bias=P[lp + '1.fn.net.3.bias'], residual=a['cls_x1'], ldr=d, dropout_p=ph, seed=s0 + 4, mask_row_pitch=N)
         return a['cls_x2']
 
-    def forward(self, x, labels=None, weight=None, training=True, seed=0, want_mean=True, cls_only_last=False):
+    def forward(self, x, labels=None, weight=None, training=True, seed=0, want_mean=True, cls_only_last=False, lengths=None):
         """x: (B, C, L) f32 contiguous device tensor. Returns (logits (B,K) f32, loss_elem (B,K) f32 | None, loss_mean (1,) | None).
         cls_only_last: compute the last block for the CLS rows only (past its K / V), the rows the classifier reads -- same loss, logits and
         gradients, 1/12 of the base trunk less work.  bf16 engine without fp8_linear; the last block's other rows are then not computed
-        (attention_probs of that layer is unavailable until the next full forward)."""
+        (attention_probs of that layer is unavailable until the next full forward).
+        x may be narrower than max_signal_length (a multiple of P): the pass then runs at L'/P + 1 tokens with position rows 0..L'/P.
+        lengths: (B,) integer tensor (host or device) of per-record sample counts inside x (`check_lengths`); record b then gives what it
+        would give alone at x[b:b+1, :, :lengths[b]] (dropout 0; up to summation order).  Not with fp8_linear or a fused input transform."""
         B = x.shape[0]
         assert x.shape[1] == self.C and x.dtype == torch.float32 and x.is_contiguous()
         if self.input_transform is None:
-            assert x.shape[2] == self.L
+            width = x.shape[2]
+            if width != self.L_max and self.fp8:
+                raise ValueError(f'fp8_linear runs full-width batches only (max_signal_length={self.L_max}, got {width} samples)')
         else:
-            assert self.input_transform.padded_length(x.shape[2]) == self.L, 'config.max_signal_length must be the padded length'
+            if lengths is not None:
+                raise ValueError('per-record lengths are not supported with a fused input transform (its TimeEndPad pads every record)')
+            assert self.input_transform.padded_length(x.shape[2]) == self.L_max, 'config.max_signal_length must be the padded length'
+            width = self.L_max
+        if lengths is not None and self.fp8:
+            raise ValueError('per-record lengths are not supported with fp8_linear')
         cls_only_last = bool(cls_only_last)
         if cls_only_last and (self.dtype != torch.bfloat16 or self.fp8):
             raise ValueError('cls_only_last needs the bf16 engine without fp8_linear')
+        self._set_width(width)
+        ntok = None
+        if lengths is not None:
+            ntok = check_lengths(lengths, B, self.P, width)
+            if ntok is not None and not ntok.is_cuda:
+                ntok = ntok.pin_memory().to(x.device, non_blocking=True)
         self._alloc(B)
         a, T = self.act, hip.code(self.dtype)
         l, st = lib(), stream()
         d, N, n = self.d, self.N, self.n
         ph = self.p_hidden if training else 0.0
         pe = self.p_emb if training else 0.0
-        self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, labels=labels, weight=weight, masked=False, training=training, cls_only_last=cls_only_last)
+        self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, labels=labels, weight=weight, masked=False, training=training, cls_only_last=cls_only_last,
+                          ntok=ntok, lengths=lengths is not None)
         if self.fp8:
             # EVERY forward, eval included, starts from the scales of the pass before it (delayed scaling with a history of one pass): an
             # inference-only model otherwise keeps its first batch's scales forever and clamps larger activations silently.  No backward can be
@@ -626,6 +691,7 @@ class VitEngine:
         mask_token; + pos[1:n+1]; trunk on n tokens (no CLS); masked rows -> Linear(d, C*P); L1 vs the raw masked patches.
         x (B,C,L) f32; idx (B,m) int32 distinct patch indices per record. Returns (pred (B*m, C*P), loss (1,) f32)."""
         B, m = idx.shape
+        self._set_width(self.L_max)   # the masked objective runs full-width records only
         assert idx.dtype == torch.int32 and idx.is_contiguous() and 0 < m <= self.n
         self._alloc(B, masked=True, m=m)
         a, W, T = self.act, self.W, hip.code(self.dtype)
@@ -701,7 +767,11 @@ class VitEngine:
         sq = (N * 3 * d, dh)
         self._gemm(GEMM_NT, qkv, qkv, S, N, N, dh, 3 * d, 3 * d, N, alpha=self.scale, batch=(B, h), strideA=sq, strideB=sq,
                  strideC=(h * N * N, N * N), b_off=d)
-        check(lib().ecgvit_softmax_rows(ptr(S), B * h * N, N, N, stream()), 'softmax_rows')
+        ntok = self.saved.get('ntok')
+        if ntok is not None:   # keys past each record's length get probability 0, its padded query rows all zeros
+            check(lib().ecgvit_softmax_rows_varlen(ptr(S), ptr(ntok), B, h, N, N, stream()), 'softmax_rows_varlen')
+        else:
+            check(lib().ecgvit_softmax_rows(ptr(S), B * h * N, N, N, stream()), 'softmax_rows')
         Pd = S
         if ph > 0:
             Pd = self.act['pd']
@@ -765,6 +835,8 @@ class VitEngine:
         # ---- embedding backward
         check(l.ecgvit_embed_bwd(ptr(dX), ptr(a['dtok']), ptr(G[pre + 'cls_token']), ptr(G[pre + 'pos_embedding']), B, n, d, pe,
                                  seed + 1, T, st), 'embed_bwd')
+        if N < self.N_max:   # a narrower pass: embed_bwd wrote position rows < N only, the rest take no part
+            G[pre + 'pos_embedding'].view(-1, d)[N:].zero_()
         self._colsum(a['dtok'], d, G[pre + 'to_patch_embedding.1.bias'], Mp, d)
         self._wgrad(a['dtok'], a['patches'], pre + 'to_patch_embedding.1.weight', d, self.CP, Mp)
         self._ready('embed')
@@ -831,7 +903,11 @@ class VitEngine:
             self._wgrad(dY, L['attn'], lp + '0.fn.to_out.0.weight', d, d, M, pre=g6, x8=L.get('attn_8'), xsite=8 * i + 1)
             self._dgrad(dY, lp + '0.fn.to_out.0.weight', a['dattn'], M, d, d, site=8 * i + 6, pre=g6)
             pq7 = False   # fp8_linear: the attention backward wrote the e5m2 copy of dqkv itself (into the operand scratch)
-            if self.dtype == torch.bfloat16:
+            ntok = sv.get('ntok')
+            if self.dtype == torch.bfloat16 and ntok is not None:
+                check(l.ecgvit_attention_varlen_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), ptr(ntok), B, N, h,
+                                                    dh, self.scale, ph, s0 + 1, st), 'attention_varlen_bwd')
+            elif self.dtype == torch.bfloat16:
                 if f8 and (8 * i + 7) in self._f8_seen and dh == 64 and 128 < N <= 512 and N * 3 * d * 2 < 2 ** 31:   # (dh = 128: _grad8 quantises dqkv)
                     check(l.ecgvit_attention_bwd_q8(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), B, N, h, dh, self.scale,
                                                     ph, s0 + 1, ptr(a['q8']), ptr(self.f8_scale[8 * i + 7:8 * i + 8]), ptr(self.f8_amax[8 * i + 7:8 * i + 8]), st),
@@ -895,8 +971,13 @@ class VitEngine:
         dY = a['cls_dxm'] if ph > 0 else a['cls_dx1']
         self._gemm(GEMM_TN, dY, a['cls_attn'], G[lp + '0.fn.to_out.0.weight'], d, d, B, d, d, d, workspace=ws)
         self._gemm(GEMM_NN, dY, W[lp + '0.fn.to_out.0.weight'], a['cls_dattn'], B, d, d, d, d, d)
-        check(l.ecgvit_attention_cls_bwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_dattn']), ptr(a['cls_lse']), ptr(a['dqkv']), ptr(a['cls_dq']),
-                                         B, N, h, dh, self.scale, ph, s0 + 1, T, st), 'attention_cls_bwd')
+        ntok = self.saved.get('ntok')
+        if ntok is not None:
+            check(l.ecgvit_attention_varlen_cls_bwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_dattn']), ptr(a['cls_lse']), ptr(a['dqkv']),
+                                                    ptr(a['cls_dq']), ptr(ntok), B, N, h, dh, self.scale, ph, s0 + 1, st), 'attention_varlen_cls_bwd')
+        else:
+            check(l.ecgvit_attention_cls_bwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_dattn']), ptr(a['cls_lse']), ptr(a['dqkv']), ptr(a['cls_dq']),
+                                             B, N, h, dh, self.scale, ph, s0 + 1, T, st), 'attention_cls_bwd')
         # to_qkv: dW[K|V] = dKV^T . xn1 over every row, dW[Q] = dQ^T . xn1 over the CLS rows; d(xn1) = dKV . W[K|V] (+ dQ . W[Q] on the CLS rows)
         name = lp + '0.fn.to_qkv.weight'
         self._gemm(GEMM_TN, a['dqkv'], L['xn1'], G[name], 2 * d, d, M, 3 * d, d, d, workspace=ws, a_off=d, c_off=d * d)
@@ -950,6 +1031,8 @@ class VitEngine:
     def attention_probs(self, layer):
         """Post-softmax attention of `layer` for the last forward, (B, h, N, N) f32 -- what vit_pytorch's Recorder hooks
         (reference ecg_vit.py:176-194). The f32 path keeps them; the fused bf16 path rebuilds them from its saved qkv + log-sum-exp."""
+        if self.saved.get('lengths'):
+            raise RuntimeError('the last forward ran with per-record lengths: its attention probabilities are not available')
         B, L = self.saved['B'], self.act['layers'][layer]
         if self.saved.get('cls_only_last') and layer % self.Ly == self.Ly - 1:
             raise RuntimeError('the last forward ran with cls_only_last: its last block computed the CLS query only')

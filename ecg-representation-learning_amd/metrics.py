@@ -75,8 +75,9 @@ class HipEvaluator:
     def __init__(self, model, eval_batch_size=64, id2code=None, gather=False, process_group=None):
         self.model, self.bsz, self.id2code, self.gather, self.pg = model, int(eval_batch_size), id2code, gather, process_group
 
-    def evaluate(self, sample_values, labels, return_predictions=False):
-        """sample_values: (n, C, L) f32 device tensor (this rank's shard), labels: (n, K) f32"""
+    def evaluate(self, sample_values, labels, return_predictions=False, lengths=None):
+        """sample_values: (n, C, L) f32 device tensor (this rank's shard), labels: (n, K) f32; lengths: optional (n,) per-record sample
+        counts (EcgVit.forward), sliced with the batches"""
         model = self.model
         training = model.training
         model.eval()
@@ -85,7 +86,8 @@ class HipEvaluator:
         losses = []
         with torch.no_grad():
             for s in range(0, n, self.bsz):
-                out = model(sample_values=sample_values[s:s + self.bsz], labels=labels[s:s + self.bsz])
+                out = model(sample_values=sample_values[s:s + self.bsz], labels=labels[s:s + self.bsz],
+                            lengths=None if lengths is None else lengths[s:s + self.bsz])
                 logits[s:s + self.bsz] = out.logits
                 losses.append(out.loss.detach().reshape(()))
         loss = torch.stack(losses).mean()

@@ -229,7 +229,8 @@ class HipTrainStep:
         if self.sync_nonfinite:
             self._raise_if_flagged(wait=True)
 
-    def step(self, sample_values, labels):
+    def step(self, sample_values, labels, lengths=None):
+        """one fused training step; lengths: optional (B,) per-record sample counts (EcgVit.forward)"""
         model = self.model
         if not model.training:
             raise RuntimeError('train step on a model in eval mode')
@@ -245,7 +246,7 @@ class HipTrainStep:
         # the classifier reads the CLS rows only: the last block skips the other rows past its K / V (bf16 engine; the fp8 step keeps the
         # full block -- its 512-row products would fall below the 8-bit kernels' gates and change the delayed-scaling sites)
         cls_only = eng.dtype == torch.bfloat16 and not eng.fp8
-        logits, _, loss_mean = eng.forward(x, y, w, training=True, seed=seed, want_mean=True, cls_only_last=cls_only)
+        logits, _, loss_mean = eng.forward(x, y, w, training=True, seed=seed, want_mean=True, cls_only_last=cls_only, lengths=lengths)
         model._fwd_id += 1
         B, K = x.shape[0], eng.K
         tpw = self._arm_overlap(model)

@@ -159,6 +159,10 @@ int ecgvit_patch_gather(const float *x, void *patches, int B, int C, int L, int 
 int ecgvit_patch_gather_transform(const float *x_raw, void *patches, int B, int C, int L_raw, int L, int P, int64_t ld,
                                   const float *mean, const float *inv_std, const int32_t *timeout_start,
                                   const int32_t *timeout_len, int dtype, void *stream);
+/* Same gather for variable-length records (attention_varlen.hip): n_tok int32 [B] on the device; patch p of record b is gathered for
+ * p < n_tok[b] - 1 and zero past it (the samples there are never read). */
+int ecgvit_patch_gather_varlen(const float *x, void *patches, const int32_t *n_tok, int B, int C, int L, int P, int64_t ld, int dtype,
+                               void *stream);
 /* X[b*N + 0] = cls + pos[0];  X[b*N + 1 + p] = tok[b*n + p] + pos[1 + p]   (N = n + 1; ViT.forward: cat CLS, += pos)
  * optional embedding dropout (p = emb_dropout_p, mask = f(seed, element index in X)). cls/pos are f32. */
 int ecgvit_embed_finish(const void *tok, const float *cls, const float *pos, void *X, int B, int n, int d,
@@ -259,9 +263,26 @@ int ecgvit_attention_cls_bwd(const void *qkv, const void *out_cls, const void *d
  * materialises the scores anyway); visualisation-time, not tuned. B*h <= 65535. */
 int ecgvit_attention_probs(const void *qkv, const float *lse, float *probs, int B, int N, int h, int dh, float scale, int dtype,
                            void *stream);
+/* Variable-length records (attention_varlen.hip): the same fused attention for a batch whose records hold n_tok[b] valid tokens, n_tok an int32
+ * [B] DEVICE array with 1 <= n_tok[b] <= N; the row stride per record stays N.  Keys >= n_tok[b] take no part, rows >= n_tok[b] of out and
+ * of all three parts of dqkv are written as exact zeros (their lse: 0), and the dropout bits are those of the uniform kernels for the batch N
+ * (so a record's mask differs from the one it would draw alone at its own length).  bf16, dh == 64 or 128, N <= 2048.  The CLS forms are
+ * ecgvit_attention_cls_fwd / _cls_bwd over the n_tok[b] keys; the backward writes zeros into the K / V rows >= n_tok[b]. */
+int ecgvit_attention_varlen_fwd(const void *qkv, void *out, float *lse, const int32_t *n_tok, int B, int N, int h, int dh, float scale,
+                                float dropout_p, uint64_t seed, void *stream);
+int ecgvit_attention_varlen_bwd(const void *qkv, const void *out, const void *dout, const float *lse, void *dqkv, const int32_t *n_tok,
+                                int B, int N, int h, int dh, float scale, float dropout_p, uint64_t seed, void *stream);
+int ecgvit_attention_varlen_cls_fwd(const void *qkv, void *out_cls, float *lse_cls, const int32_t *n_tok, int B, int N, int h, int dh,
+                                    float scale, float dropout_p, uint64_t seed, void *stream);
+int ecgvit_attention_varlen_cls_bwd(const void *qkv, const void *out_cls, const void *dout_cls, const float *lse_cls, void *dqkv,
+                                    void *dq_cls, const int32_t *n_tok, int B, int N, int h, int dh, float scale, float dropout_p,
+                                    uint64_t seed, void *stream);
 /* f32 parity path pieces (scores materialised; the GEMMs are ecgvit_gemm batched calls):
  * in-place row softmax of S[rows, ld] over the first N columns; optional export is the buffer itself. */
 int ecgvit_softmax_rows(float *S, int64_t rows, int N, int64_t ld, void *stream);
+/* the f32 path's softmax for variable-length records: S[(b h + head) N + q][ld] over the first n_tok[b] columns (n_tok: int32 [B] on the
+ * device); columns >= n_tok[b] and whole rows q >= n_tok[b] become 0, so ecgvit_softmax_bwd_rows gives dS = 0 there. */
+int ecgvit_softmax_rows_varlen(float *S, const int32_t *n_tok, int B, int h, int N, int64_t ld, void *stream);
 /* dS = P * (dP - rowsum(P*dP)) * scale, written over dP */
 int ecgvit_softmax_bwd_rows(const float *P, float *dP, int64_t rows, int N, int64_t ld, float scale, void *stream);
 
