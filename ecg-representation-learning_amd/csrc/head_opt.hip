@@ -219,6 +219,67 @@ __global__ __launch_bounds__(256) void clip_scale_kernel(float *__restrict__ g, 
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) g[i] *= coef;
 }
 
+// ---- the same two passes over a span table (frozen parameters): spans[3s..3s+2] = {element offset, count, step offset}.  Every block walks
+//      the spans in table order with the same grid-stride pattern, so the partial sums, and hence the two-stage total, are deterministic.
+__global__ __launch_bounds__(256) void sumsq_spans_partial_kernel(const float *__restrict__ g, const int64_t *__restrict__ spans, int nspan,
+                                                                  float *__restrict__ partial) {
+    __shared__ float red[4];
+    float s = 0.f;
+    const int64_t stride = (int64_t)gridDim.x * 256, tid = blockIdx.x * 256ll + threadIdx.x;
+    for (int k = 0; k < nspan; ++k) {
+        const int64_t off = spans[3 * k], count = spans[3 * k + 1];
+        const float *gs = g + off;
+        int64_t head = 0;
+        if ((off & 3) == 0) {   // 16-B aligned span: vector body, scalar tail
+            head = count / 4 * 4;
+            const f32x4 *gv = reinterpret_cast<const f32x4 *>(gs);
+            for (int64_t i = tid; i < count / 4; i += stride) {
+                const f32x4 v = gv[i];
+                s += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+            }
+        }
+        for (int64_t i = head + tid; i < count; i += stride) s += gs[i] * gs[i];
+    }
+    const float tot = block_sum<4>(s, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(256) void adamw_spans_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                                          float *__restrict__ v, bf16_t *__restrict__ plow, const int64_t *__restrict__ spans,
+                                                          int nspan, const float *__restrict__ sumsq, float grad_scale, float max_norm,
+                                                          float lr, float b1, float b2, float eps, float wd, int step, int decoupled,
+                                                          float *__restrict__ norm_out) {
+    float nrm;
+    bool fin;
+    const float coef = clip_coef(sumsq, grad_scale, max_norm, &nrm, &fin) * grad_scale;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) { norm_out[0] = nrm; norm_out[1] = fin ? 1.0f : 0.0f; }
+    if (!fin) return;
+    for (int k = 0; k < nspan; ++k) {
+        const int64_t off = spans[3 * k], count = spans[3 * k + 1];
+        const int st = step + (int)spans[3 * k + 2];   // this span's own optimiser step (torch: state['step'] per parameter)
+        if (st < 1) continue;                          // (the host never builds such a span)
+        // bias corrections as ecgvit_adamw_step forms them on the host: in double, then rounded to f32 (beta^step by squaring: within a few
+        // double ulps of pow(), far below the f32 rounding; a library pow() here costs SGPR spills)
+        double p1 = 1.0, p2 = 1.0, q1 = b1, q2 = b2;
+        for (int e = st; e; e >>= 1, q1 *= q1, q2 *= q2)
+            if (e & 1) { p1 *= q1; p2 *= q2; }
+        const float bc1 = (float)(1.0 - p1), bc2_sqrt = (float)sqrt(1.0 - p2);
+        const float step_size = lr / bc1;
+        for (int64_t j = blockIdx.x * 256ll + threadIdx.x; j < count; j += (int64_t)gridDim.x * 256) {
+            const int64_t i = off + j;
+            float pi = p[i], gi = g[i] * coef, mi = m[i], vi = v[i];
+            if (decoupled) pi *= 1.0f - lr * wd;
+            else gi += wd * pi;
+            mi = b1 * mi + (1.0f - b1) * gi;
+            vi = b2 * vi + (1.0f - b2) * gi * gi;
+            const float denom = sqrtf(vi) / bc2_sqrt + eps;
+            pi -= step_size * (mi / denom);
+            p[i] = pi; m[i] = mi; v[i] = vi;
+            if (plow) plow[i] = (bf16_t)pi;
+        }
+    }
+}
+
 // ---- batched transpose of bf16 matrices that live at the SAME offsets in two flat buffers (shadow weights -> transposed shadows):
 //      table[4i..4i+3] = {element offset, rows, cols, index of the matrix's first 64x64 tile}; dst holds cols x rows row-major.
 //      One 64 x 64 tile per 256-thread block through LDS; 16-B accesses on both sides when the tile is interior.
@@ -348,6 +409,28 @@ int ecgvit_adamw_step(float *p, const float *g, float *m, float *v, void *p_lowp
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
     hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(count)), dim3(256), 0, as_stream(stream), p, g, m, v, (bf16_t *)p_lowp, count, sumsq,
                        grad_scale, max_norm, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), decoupled, norm_out);
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
+}
+
+int64_t ecgvit_sumsq_spans_workspace(int nspan) { (void)nspan; return (int64_t)SUMSQ_BLOCKS * 4; }
+
+int ecgvit_sumsq_spans(const float *g, const int64_t *spans, int nspan, int64_t total, float *out, void *partial, void *stream) {
+    if (nspan <= 0 || total <= 0 || !spans || !partial || (reinterpret_cast<uintptr_t>(g) % 16) != 0) return ECGVIT_EINVAL;
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((total / 4 + 255) / 256, SUMSQ_BLOCKS));
+    hipLaunchKernelGGL(sumsq_spans_partial_kernel, dim3(nb), dim3(256), 0, as_stream(stream), g, spans, nspan, (float *)partial);
+    ECGVIT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, as_stream(stream), (const float *)partial, nb, out);
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
+}
+
+int ecgvit_adamw_step_spans(float *p, const float *g, float *m, float *v, void *p_lowp, const int64_t *spans, int nspan, int64_t total,
+                            const float *sumsq, float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
+                            float weight_decay, int step, int decoupled, float *norm_out, void *stream) {
+    if (nspan <= 0 || total <= 0 || !spans || !sumsq) return ECGVIT_EINVAL;
+    hipLaunchKernelGGL(adamw_spans_kernel, dim3(ew_grid(total)), dim3(256), 0, as_stream(stream), p, g, m, v, (bf16_t *)p_lowp, spans, nspan,
+                       sumsq, grad_scale, max_norm, lr, beta1, beta2, eps, weight_decay, step, decoupled, norm_out);
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
 }

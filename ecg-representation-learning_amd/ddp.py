@@ -9,6 +9,8 @@ single RCCL all-reduce(sum) over that buffer; the 1/world scaling is folded into
 
 Device-agnostic on purpose: the world_size-2 `gloo` tests exercise exactly these functions on CPU tensors.
 """
+import zlib
+
 import torch
 import torch.distributed as dist
 
@@ -50,6 +52,24 @@ def broadcast_flat_(pflat: torch.Tensor, src: int = 0, group=None, single_rank: 
     """make every rank start from rank `src`'s weights (one collective over the flat parameter buffer)"""
     if dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or single_rank):
         dist.broadcast(pflat, src=src, group=group)
+
+
+def check_same_frozen_set(flags, group=None, device=None, single_rank=False):
+    """Every rank must freeze the same parameters (`requires_grad` flags, in parameter order): the backward pass of a rank reports only the
+    gradient buckets that hold a trainable parameter, so ranks that disagreed would post different collective sequences and hang.  One
+    all-reduce of two int64 (a digest of the flags and its negation, MAX): every rank sees max == min exactly when all digests agree, and
+    every rank raises ValueError otherwise.  Call it whenever the set may have changed, before any gradient bucket is sent."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return
+    if dist.get_world_size(group) == 1 and not single_rank:
+        return
+    digest = zlib.crc32(bytes(1 if f else 0 for f in flags)) | (len(flags) << 32)
+    t = torch.tensor([digest, -digest], dtype=torch.int64, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+    hi, neg_lo = t.tolist()
+    if hi != -neg_lo:
+        raise ValueError('data-parallel ranks disagree on which parameters are frozen (requires_grad=False): every rank must freeze the '
+                         'same parameters at the same step')
 
 
 class GradExchange:

@@ -200,15 +200,16 @@ class _EcgVitFunction(torch.autograd.Function):
         if (gloss is None or not ctx.has_labels) and glogits is None:
             return (None,) * (6 + len(model._own_list))
         keep, aliased = _grads_living_in_flat_buffer(model, model._own_names, model._own_list)
+        tr = model.trainable_names()
         if gloss is not None and ctx.has_labels:
             if glogits is not None:
                 raise NotImplementedError('gradients through both loss and logits of one forward')
             if ctx.reduction == 'mean':
-                eng.backward(gscalar=gloss.contiguous().float(), gscale=1.0 / (B * K))
+                eng.backward(gscalar=gloss.contiguous().float(), gscale=1.0 / (B * K), trainable=tr)
             else:
-                eng.backward(gelem=gloss.contiguous().float(), gscale=1.0)
+                eng.backward(gelem=gloss.contiguous().float(), gscale=1.0, trainable=tr)
         else:
-            eng.backward(glogits=glogits.contiguous().float())
+            eng.backward(glogits=glogits.contiguous().float(), trainable=tr)
         return (None, None, None, None, None, None) + _grads_out(model, model._own_names, keep, aliased)
 
 
@@ -323,6 +324,14 @@ class EcgVit(nn.Module):
         loss, logits = _EcgVitFunction.apply(self, x, y, w, self._loss_reduction, lengths, *self._own_list)
         return ModelOutput(loss=loss if labels is not None else None, logits=logits)
 
+    def trainable_names(self):
+        """names of the parameters with requires_grad=True (attached pre-train parameters included), or None when every parameter is trainable.
+        The backward passes skip the work only frozen parameters need (`engine.BackwardPlan`); their `.grad` stays None."""
+        flags = [p.requires_grad for p in self._param_list]
+        if all(flags):
+            return None
+        return [n for n, f in zip(self._param_names, flags) if f]
+
     # ------------------------------------------------------------------ flat HBM layout of the parameters
     def _flatten(self):
         """(Re)pack all parameters into one flat f32 buffer on their current device; params become views of it."""
@@ -362,7 +371,7 @@ class EcgVit(nn.Module):
                                   h=c.num_attention_heads, f=c.intermediate_size, Ly=c.num_hidden_layers, K=self.num_class,
                                   p_hidden=c.hidden_dropout_prob, p_emb=c.attention_probs_dropout_prob,
                                   dtype=self.compute_dtype, layout=self._layout, fp8_linear=self.fp8_linear, saved_ffn_e4m3=self.saved_ffn_e4m3)
-            self._wlow_t = self._tr_table = None
+            self._wlow_t = self._tr_table = self._tr_sub = None
             if self.compute_dtype == torch.bfloat16:
                 self._wlow = torch.empty(self._layout.total, dtype=torch.bfloat16, device=self._pflat.device)
                 self._wlow_version = -1
@@ -385,13 +394,22 @@ class EcgVit(nn.Module):
             self.refresh_transposed_weights()
             self._wlow_version = ver
 
-    def refresh_transposed_weights(self):
-        """W^T shadows of the block Linears (input-gradient GEMMs then run on the forward kernel); call after `_wlow` changed"""
+    def refresh_transposed_weights(self, only=None):
+        """W^T shadows of the block Linears (input-gradient GEMMs then run on the forward kernel); call after `_wlow` changed.
+        only: the names of the parameters that changed (the trainable ones after a fused step with frozen parameters; None = all): the
+        other matrices keep their shadows (a filtered table)"""
         if getattr(self, '_wlow_t', None) is not None:
-            hip.check(hip.lib().ecgvit_transpose_bf16_batched(self._wlow.data_ptr(), self._wlow_t.data_ptr(), self._tr_table.data_ptr(),
-                                                              self._tr_nmat, self._tr_tiles, hip.stream()), 'transpose_bf16_batched')
+            table, nmat, tiles = self._tr_table, self._tr_nmat, self._tr_tiles
+            if only is not None:
+                key = frozenset(only)
+                if getattr(self, '_tr_sub', None) is None or self._tr_sub[0] != key:
+                    self._tr_sub = (key,) + self._eng.transposed_weight_table(self._pflat.device, only=key)
+                table, nmat, tiles = self._tr_sub[1:]
+            if nmat:
+                hip.check(hip.lib().ecgvit_transpose_bf16_batched(self._wlow.data_ptr(), self._wlow_t.data_ptr(), table.data_ptr(),
+                                                                  nmat, tiles, hip.stream()), 'transpose_bf16_batched')
         if self._eng is not None and getattr(self._eng, 'fp8', False):
-            self._eng.refresh_fp8_weights()
+            self._eng.refresh_fp8_weights(only)
 
     def set_input_transform(self, transform):
         """f2: give the model RAW records; Normalize / TimeEndPad / TimeOut run fused inside the patch-embed load
@@ -483,7 +501,7 @@ class _MaskedFunction(torch.autograd.Function):
         if gloss is None:
             return (None,) * (3 + len(enc._param_list))
         keep, aliased = _grads_living_in_flat_buffer(enc, enc._param_names, enc._param_list)
-        enc._engine().backward_masked(gscalar=gloss.contiguous().float().reshape(1))
+        enc._engine().backward_masked(gscalar=gloss.contiguous().float().reshape(1), trainable=enc.trainable_names())
         return (None, None, None) + _grads_out(enc, enc._param_names, keep, aliased)
 
 

@@ -73,6 +73,68 @@ class ParamLayout:
         return [(k, v) for k, v in out if v]
 
 
+class BackwardPlan:
+    """Which parts of a backward pass run when only some parameters are trainable (frozen: `requires_grad=False`).
+
+    The backward is a chain of input-gradient stages: 0 = the objective's head (classification head backward | reconstruction product and
+    row scatter), then per block i from the top, at base = 1 + 7 (Ly-1-i): +0 FFN-down input gradient, +1 FFN-up input gradient, +2 LayerNorm-2
+    backward, +3 out-projection input gradient, +4 attention backward, +5 QKV input gradient, +6 LayerNorm-1 backward; last, 1 + 7 Ly = the
+    embedding backward.  A parameter's gradient needs every stage up to `need(name)`; the pass runs stages 0..`depth` (the deepest need of a
+    trainable parameter) and stops there.
+      wgrad  -- the Linear weights whose weight-gradient product runs (the trainable ones)
+      live   -- the gradient buckets (`ParamLayout.buckets_in_ready_order` tags) holding a trainable parameter: the only ones reported ready
+    A plan with `depth` = the embedding stage and every Linear weight trainable is the full pass."""
+
+    def __init__(self, names, n_layers, trainable, masked=False):
+        trainable = set(trainable)
+        unknown = trainable - set(names)
+        if unknown:
+            raise ValueError(f'unknown parameter names: {sorted(unknown)}')
+        if not trainable:
+            raise ValueError('no trainable parameter: every parameter has requires_grad=False')
+        self.n_layers, self.masked = n_layers, masked
+        self.trainable = frozenset(trainable)
+        self.embed_stage = 1 + 7 * n_layers
+        self.depth = max(self.need(n) for n in trainable)
+        self.wgrad = frozenset(n for n in trainable if n.endswith('.weight') and self._is_linear(n))
+        self.live = frozenset(self.bucket(n) for n in trainable)
+
+    @staticmethod
+    def _is_linear(name):
+        return name.startswith('vit.transformer.layers.') and '.fn.' in name or name in (
+            'vit.to_patch_embedding.1.weight', 'pretrain.to_pixels.weight')
+
+    @staticmethod
+    def bucket(name):
+        if name.startswith('vit.mlp_head.'):
+            return 'head'
+        if name.startswith('vit.transformer.layers.'):
+            return 'layer' + name.split('.')[3]
+        if name.startswith('pretrain.'):
+            return 'pretrain'
+        return 'embed'
+
+    def need(self, name):
+        """the last stage the gradient of `name` depends on (-1: none -- written before stage 0, or zero for this objective)"""
+        if name.startswith('vit.mlp_head.'):
+            return -1 if self.masked else 0
+        if name == 'vit.cls_token':
+            return -1 if self.masked else self.embed_stage
+        if name.startswith('pretrain.'):
+            return self.embed_stage if (self.masked and name == 'pretrain.mask_token') else -1
+        if not name.startswith('vit.transformer.layers.'):
+            return self.embed_stage   # position embedding, patch embedding
+        parts = name.split('.')
+        base = 1 + 7 * (self.n_layers - 1 - int(parts[3]))
+        rest = '.'.join(parts[4:])
+        return base + {'1.fn.net.3.weight': -1, '1.fn.net.3.bias': -1, '1.fn.net.0.weight': 0, '1.fn.net.0.bias': 0, '1.norm.weight': 2,
+                       '1.norm.bias': 2, '0.fn.to_out.0.bias': 2, '0.fn.to_out.0.weight': 2, '0.fn.to_qkv.weight': 4, '0.norm.weight': 6,
+                       '0.norm.bias': 6}[rest]
+
+    def reach(self, stage):
+        return stage <= self.depth
+
+
 def check_lengths(lengths, B, P, width):
     """Per-record sample counts of a (B, C, width) batch -> int32 token counts n_tok = lengths / P + 1 on the lengths' own device, or None when
     every record fills the width (the uniform kernels then run).  Each entry must be a positive multiple of P and at most `width`, else
@@ -224,16 +286,28 @@ class VitEngine:
             self._f8_last_training, self._f8_scale_train = None, None
 
     # ---------------------------------------------------------------- fp8 operand path
-    def refresh_fp8_weights(self):
+    def refresh_fp8_weights(self, only=None):
         """e4m3 shadows of the block Linears' weights and of their transposes, one scale per matrix from its current amax: three
-        launches over the flat bf16 shadows (call after the optimiser rewrote them)"""
+        launches over the flat bf16 shadows (call after the optimiser rewrote them).  only: the names that changed (None = all): the
+        launches then cover each run of consecutive rows of the matrix table that holds only changed matrices"""
         l, st = lib(), stream()
         nm = len(self.w8_index)
-        check(l.ecgvit_fp8_amax(ptr(self._wlow), ptr(self.w8_table), nm, self.w8_count, ptr(self.w8_amax), st), 'fp8_amax')
-        check(l.ecgvit_fp8_scale_update(ptr(self.w8_scale), ptr(self.w8_amax), nm, None, hip.FP8_E4M3, st), 'fp8_scale_update')
-        for src, dst in ((self._wlow, self.w8), (self._wlow_t, self.w8t)):
-            check(l.ecgvit_fp8_quantize(ptr(src), ptr(dst), ptr(self.w8_table), nm, self.w8_count, hip.FP8_E4M3, ptr(self.w8_scale), None, st),
-                  'fp8_quantize')
+        runs = [(0, nm)]
+        if only is not None:
+            runs, r0 = [], None
+            for k, i in list(self.w8_index.items()) + [(None, nm)]:
+                if k is not None and k in only:
+                    r0 = i if r0 is None else r0
+                elif r0 is not None:
+                    runs.append((r0, i))
+                    r0 = None
+        for r0, r1 in runs:
+            tab, sc, am = self.w8_table[r0:r1], self.w8_scale[r0:r1], self.w8_amax[r0:r1]
+            check(l.ecgvit_fp8_amax(ptr(self._wlow), ptr(tab), r1 - r0, self.w8_count, ptr(am), st), 'fp8_amax')
+            check(l.ecgvit_fp8_scale_update(ptr(sc), ptr(am), r1 - r0, None, hip.FP8_E4M3, st), 'fp8_scale_update')
+            for src, dst in ((self._wlow, self.w8), (self._wlow_t, self.w8t)):
+                check(l.ecgvit_fp8_quantize(ptr(src), ptr(dst), ptr(tab), r1 - r0, self.w8_count, hip.FP8_E4M3, ptr(sc), None, st),
+                      'fp8_quantize')
 
     def fp8_begin_step(self, training=True):
         """delayed scaling: the scales of this pass come from the amax the previous pass's quantise kernels accumulated.
@@ -243,7 +317,9 @@ class VitEngine:
         first training step after every evaluation."""
         if self._f8_seen:
             if training and self._f8_last_training is False and self._f8_scale_train is not None:
-                self.f8_scale.copy_(self._f8_scale_train)
+                # (only where the snapshot holds a scale: a site first reached after it -- e.g. a gradient site of a block that was frozen
+                # until then -- keeps its own instead of taking scale 0, which would quantise it to zeros)
+                self.f8_scale.copy_(torch.where(self._f8_scale_train > 0, self._f8_scale_train, self.f8_scale))
                 self.f8_amax.zero_()
             else:
                 check(lib().ecgvit_fp8_scale_update(ptr(self.f8_scale), ptr(self.f8_amax), self.f8_scale.numel(), ptr(self.f8_fmt), 0, stream()),
@@ -326,10 +402,12 @@ class VitEngine:
                     out.append(lp + k)
         return out
 
-    def transposed_weight_table(self, device):
-        """(table tensor int64 [nmat, 4] on `device`, nmat, ntiles) for ecgvit_transpose_bf16_batched"""
+    def transposed_weight_table(self, device, only=None):
+        """(table tensor int64 [nmat, 4] on `device`, nmat, ntiles) for ecgvit_transpose_bf16_batched; only: a subset of the names"""
         rows_, t = [], 0
         for k in self.transposed_weight_names():
+            if only is not None and k not in only:
+                continue
             off, (r, c) = self.layout.entries[k][0], self.layout.entries[k][1]
             rows_.append([off, r, c, t])
             t += ((r + 63) // 64) * ((c + 63) // 64)
@@ -507,7 +585,9 @@ class VitEngine:
     def _wgrad(self, dY, X, name, Mout, Nin, rows, pre=None, x8=None, xsite=None):
         """dW[Mout, Nin] = dY[rows, Mout]^T . X[rows, Nin]  -> f32 gradient view (overwritten).  fp8_linear: pre = (e5m2 copy of dY,
         scale) from `_grad8`, x8 / xsite = the layer's persistent e4m3 copy of X and its site (scale): the product then runs on the
-        8-bit streaming kernel (both operands k-major, transposed 8-bit LDS reads)"""
+        8-bit streaming kernel (both operands k-major, transposed 8-bit LDS reads).  Nothing runs for a frozen weight (backward plan)."""
+        if not self._wants(name):
+            return
         if pre is not None and x8 is not None and Mout % 256 == 0 and Nin % 256 == 0 and rows >= 4096:
             q, sc = pre
             self._gemm(GEMM_TN, q, x8, self.G32[name], Mout, Nin, rows, Mout, Nin, Nin, workspace=self.act['ws'], fp8_format=hip.BF8_E5M2,
@@ -718,14 +798,17 @@ class VitEngine:
                                        self.CP, T, st), 'l1_loss')
         return a['pred'], a['mloss']
 
-    def backward_masked(self, gscalar=None, tiles_per_workgroup=0):
+    def backward_masked(self, gscalar=None, tiles_per_workgroup=0, trainable=None):
         """loss + every gradient of the masked objective (the L1 kernel produces loss and dpred in one pass).
-        tiles_per_workgroup: as `backward`"""
+        tiles_per_workgroup, trainable: as `backward`"""
         self._tpw = int(tiles_per_workgroup)
+        self._begin_plan(trainable, masked=True)
         try:
             self._backward_masked(gscalar)
+            self._ready_rest()
         finally:
             self._tpw = 0
+            self._plan = None
 
     def _backward_masked(self, gscalar):
         a, W, T = self.act, self.W, hip.code(self.dtype)
@@ -745,11 +828,15 @@ class VitEngine:
         self._ready('head')
         self._colsum(a['dpred'], self.CP, G['pretrain.to_pixels.bias'], B * m, self.CP)
         self._wgrad(a['dpred'], a['rows'], 'pretrain.to_pixels.weight', self.CP, d, B * m)
+        if not self._reach(0):
+            return
         self._gemm(GEMM_NN, a['dpred'], W['pretrain.to_pixels.weight'], a['drows'], B * m, d, self.CP, self.CP, d, d)
         dX = a['dxa']
         dX.zero_()
         check(l.ecgvit_scatter_rows(ptr(a['drows']), ptr(idx), ptr(dX), B, n, m, d, d, d, T, st), 'scatter_rows')
         dX = self._trunk_bwd(dX, a['dxb'])
+        if dX is None or not self._reach(self._stage(-1, 0)):
+            return
         if pe > 0:
             self._drop_apply(dX, dX, B * n * d, pe, seed + 1)
         check(l.ecgvit_mask_embed_bwd(ptr(dX), ptr(a['flag']), ptr(a['dtok']), ptr(a['dmasked']), ptr(G['vit.pos_embedding']), B, n, d,
@@ -789,16 +876,60 @@ class VitEngine:
             raise ValueError('f32 attention dropout needs B*h*N*N to be a multiple of 8')
 
     # ---------------------------------------------------------------- backward
-    def backward(self, gscalar=None, gelem=None, gscale=1.0, glogits=None, tiles_per_workgroup=0):
+    def backward(self, gscalar=None, gelem=None, gscale=1.0, glogits=None, tiles_per_workgroup=0, trainable=None):
         """Overwrites every gradient view in gflat. Upstream: `gscalar` (1,) for the mean loss, or `gelem` (B,K) for
         reduction='none'; gscale folds the 1/(B*K) of the mean. `glogits` (B,K): extra upstream gradient on the logits.
         tiles_per_workgroup > 0: this pass's large A.B^T launches run as dispatcher-balanced chunks of about that many tiles (the
-        caller overlaps RCCL collectives with the pass, whose kernels hold CUs); the setting ends with the pass, exception or not."""
+        caller overlaps RCCL collectives with the pass, whose kernels hold CUs); the setting ends with the pass, exception or not.
+        trainable: the names of the trainable parameters (None = all: the full pass).  Otherwise (`BackwardPlan`) only the gradients of
+        those parameters are guaranteed: no weight-gradient product runs for a frozen Linear weight, and the pass stops after the last
+        stage a trainable parameter needs (nothing below it is launched; only buckets holding a trainable parameter are reported to
+        `on_grads_ready`).  The fused by-products of stages that do run are still written, frozen or not: the bias gradients reduced in GEMM
+        epilogues and colsum passes (FFN-up / FFN-down / out-projection / patch-embedding biases), the LayerNorm gamma / beta of the fused
+        LayerNorm backward, the classification head's four gradients, and the zeroed gradients of parameters outside the objective.  The
+        gradients of frozen parameters are otherwise left as they were."""
         self._tpw = int(tiles_per_workgroup)
+        self._begin_plan(trainable, masked=False)
         try:
             self._backward(gscalar, gelem, gscale, glogits)
+            self._ready_rest()
         finally:
             self._tpw = 0
+            self._plan = None
+
+    _plan = None
+
+    def _begin_plan(self, trainable, masked):
+        """the backward plan of this pass: None (full pass) when `trainable` is None or names every parameter"""
+        self._reported = set()
+        if trainable is None:
+            self._plan = None
+            return
+        key = (frozenset(trainable), masked)
+        if len(key[0]) == len(self.layout.entries) and key[0] == set(self.layout.entries):
+            self._plan = None
+            return
+        if getattr(self, '_plan_key', None) != key:
+            self._plan_cached = BackwardPlan(list(self.layout.entries), self.Ly, key[0], masked=masked)
+            self._plan_key = key
+        self._plan = self._plan_cached
+
+    def _stage(self, i, k):
+        """BackwardPlan stage index of step k of block i (i = -1: the embedding backward)"""
+        return 1 + 7 * self.Ly if i < 0 else 1 + 7 * (self.Ly - 1 - i) + k
+
+    def _reach(self, stage):
+        return self._plan is None or stage <= self._plan.depth
+
+    def _wants(self, name):
+        """does the weight-gradient product of Linear weight `name` run in this pass"""
+        return self._plan is None or name in self._plan.wgrad
+
+    def _ready_rest(self):
+        """a pass that a plan stopped early: every live bucket not reported yet is final (nothing more will write it)"""
+        if self._plan is not None:
+            for tag, _ in self.layout.buckets_in_ready_order(self.Ly):
+                self._ready(tag)
 
     def _backward(self, gscalar, gelem, gscale, glogits):
         a, W, T = self.act, self.W, hip.code(self.dtype)
@@ -821,6 +952,9 @@ class VitEngine:
             raise ValueError('backward needs an upstream gradient')
         cls = sv.get('cls_only_last', False)
         dX = a['cls_dx'] if cls else a['dxa']   # (cls_only_last: the gradient of the CLS rows only, compact)
+        if not self._reach(0):   # frozen parameters: nothing trainable takes part in this objective's backward
+            self._zero_pretrain_grads()
+            return
         check(l.ecgvit_head_bwd(ptr(dlog), ptr(a['xhat']), ptr(a['hrstd']), ptr(self.P32[pre + 'mlp_head.0.weight']),
                                 ptr(self.P32[pre + 'mlp_head.0.bias']), ptr(self.P32[pre + 'mlp_head.1.weight']),
                                 ptr(G[pre + 'mlp_head.1.weight']), ptr(G[pre + 'mlp_head.1.bias']),
@@ -828,10 +962,9 @@ class VitEngine:
                                 T, st), 'head_bwd')
         self._ready('head')
         dX = self._trunk_bwd(dX, a['dxb'], cls_only_last=cls)
-        for k in G:
-            if k.startswith('pretrain.'):
-                G[k].zero_()   # the masked-objective head takes no part in the supervised step
-        self._ready('pretrain')
+        self._zero_pretrain_grads()
+        if dX is None or not self._reach(self._stage(-1, 0)):
+            return
         # ---- embedding backward
         check(l.ecgvit_embed_bwd(ptr(dX), ptr(a['dtok']), ptr(G[pre + 'cls_token']), ptr(G[pre + 'pos_embedding']), B, n, d, pe,
                                  seed + 1, T, st), 'embed_bwd')
@@ -841,13 +974,23 @@ class VitEngine:
         self._wgrad(a['dtok'], a['patches'], pre + 'to_patch_embedding.1.weight', d, self.CP, Mp)
         self._ready('embed')
 
+    def _zero_pretrain_grads(self):
+        for k in self.G32:
+            if k.startswith('pretrain.'):
+                self.G32[k].zero_()   # the masked-objective head takes no part in the supervised step
+        self._ready('pretrain')
+
     def _ready(self, tag):
+        if self._plan is not None:   # frozen parameters: buckets without a trainable parameter are never reported, the others once
+            if tag not in self._plan.live or tag in self._reported:
+                return
+            self._reported.add(tag)
         if self.on_grads_ready is not None:
             self.on_grads_ready(tag)
 
     def _trunk_bwd(self, dX, other, cls_only_last=False):
         """backward of _trunk_fwd: consumes dX = d(loss)/d(x_L) ([B*T, d]; cls_only_last: [B, d], the CLS rows), fills every layer's
-        parameter gradients, returns d(x_0)"""
+        parameter gradients, returns d(x_0) -- or None when a backward plan (frozen parameters) stopped the pass inside the trunk"""
         a, W, T = self.act, self.W, hip.code(self.dtype)
         l, st = lib(), stream()
         sv = self.saved
@@ -865,6 +1008,8 @@ class VitEngine:
         if cls_only_last:
             top -= 1
             dX, other = self._cls_block_bwd(dX, a['dxa'], other, B, ph, seed)
+            if dX is None:
+                return None
             have, dY = True, (a['dxm'] if ph > 0 else dX)
         for i in reversed(range(top)):
             L = a['layers'][i]
@@ -879,30 +1024,41 @@ class VitEngine:
                     dY = a['dxm']
                 self._colsum(dY, d, G[lp + '1.fn.net.3.bias'], M, d)
             f8 = self.fp8 and M >= 2048
-            g4 = self._grad8(8 * i + 4, dY, M * d, prequant='q8' if pq4 else False) if f8 else None
+            b = self._stage(i, 0)   # frozen parameters: the pass stops before the first input-gradient stage nothing trainable needs
+            g4 = self._grad8(8 * i + 4, dY, M * d, prequant='q8' if pq4 else False) if f8 and (self._wants(lp + '1.fn.net.3.weight') or self._reach(b)) else None
             self._wgrad(dY, L['hact'], lp + '1.fn.net.3.weight', d, f, M, pre=g4, x8=L.get('hact_8'), xsite=8 * i + 3)
             # dgrad with GELU' (+ dropout mask) epilogue; the epilogue also reduces the columns = gradient of the FFN-up bias
             if self.dtype == torch.bfloat16:
                 epi, pdrop = EPI_MUL_AUX | EPI_COLSUM | (hip.EPI_AUX8 if self._aux8(M) else 0), 0.0
             else:
                 epi, pdrop = EPI_GELU_BWD | EPI_COLSUM | (EPI_DROPOUT if ph > 0 else 0), ph
+            if not self._reach(b):
+                return None
             dq = self._dgrad(dY, lp + '1.fn.net.3.weight', a['dh'], M, f, d, site=8 * i + 4, emit_site=8 * i + 5, pre=g4, emit_only8=self._only8(M),
                              epilogue=epi, aux=L['hpre'],
                              ldaux=f, dropout_p=pdrop, seed=s0 + 3, workspace=a['ws'], colsum_out=G[lp + '1.fn.net.0.bias'])
-            g5 = self._grad8(8 * i + 5, a['dh'], M * f, prequant=bool(dq)) if f8 else None
+            g5 = self._grad8(8 * i + 5, a['dh'], M * f, prequant=bool(dq)) if f8 and (self._wants(lp + '1.fn.net.0.weight') or self._reach(b + 1)) else None
             self._wgrad(a['dh'], L['xn2'], lp + '1.fn.net.0.weight', f, d, M, pre=g5, x8=L.get('xn2_8'), xsite=8 * i + 2)
+            if not self._reach(b + 1):
+                return None
             self._dgrad(a['dh'], lp + '1.fn.net.0.weight', a['dxn'], M, d, f, site=8 * i + 5, pre=g5)
             # LN2 backward; its output feeds the attention out-projection site (mask seed s0+2, bias to_out.0.bias)
+            if not self._reach(b + 2):
+                return None
             pq6 = self._ln_bwd_fused(a['dxn'], L['x1'], self.P32[lp + '1.norm.weight'], L['mean2'], L['rstd2'], dX, other,
                                      G[lp + '1.norm.weight'], G[lp + '1.norm.bias'], M, a['dxm'], G[lp + '0.fn.to_out.0.bias'], ph, s0 + 2,
                                      q8_site=8 * i + 6)
             dX, other = other, dX  # dX = d(x1)
             dY = a['dxm'] if ph > 0 else dX
             # ---- Attention backward: x1 = drop(attn Wo^T + bo) + x
-            g6 = self._grad8(8 * i + 6, dY, M * d, prequant='q8' if pq6 else False) if f8 else None
+            g6 = self._grad8(8 * i + 6, dY, M * d, prequant='q8' if pq6 else False) if f8 and (self._wants(lp + '0.fn.to_out.0.weight') or self._reach(b + 3)) else None
             self._wgrad(dY, L['attn'], lp + '0.fn.to_out.0.weight', d, d, M, pre=g6, x8=L.get('attn_8'), xsite=8 * i + 1)
+            if not self._reach(b + 3):
+                return None
             self._dgrad(dY, lp + '0.fn.to_out.0.weight', a['dattn'], M, d, d, site=8 * i + 6, pre=g6)
             pq7 = False   # fp8_linear: the attention backward wrote the e5m2 copy of dqkv itself (into the operand scratch)
+            if not self._reach(b + 4):
+                return None
             ntok = sv.get('ntok')
             if self.dtype == torch.bfloat16 and ntok is not None:
                 check(l.ecgvit_attention_varlen_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), ptr(ntok), B, N, h,
@@ -918,9 +1074,13 @@ class VitEngine:
                                                  dh, self.scale, ph, s0 + 1, T, st), 'attention_bwd')
             else:
                 self._attn_bwd_f32(L, B, ph, s0 + 1)
-            g7 = self._grad8(8 * i + 7, a['dqkv'], M * 3 * d, prequant='q8' if pq7 else False) if f8 else None
+            g7 = self._grad8(8 * i + 7, a['dqkv'], M * 3 * d, prequant='q8' if pq7 else False) if f8 and (self._wants(lp + '0.fn.to_qkv.weight') or self._reach(b + 5)) else None
             self._wgrad(a['dqkv'], L['xn1'], lp + '0.fn.to_qkv.weight', 3 * d, d, M, pre=g7, x8=L.get('xn1_8'), xsite=8 * i)
+            if not self._reach(b + 5):
+                return None
             self._dgrad(a['dqkv'], lp + '0.fn.to_qkv.weight', a['dxn'], M, d, 3 * d, site=8 * i + 7, pre=g7)
+            if not self._reach(b + 6):
+                return None
             if i > 0:
                 # LN1 backward; its output feeds layer i-1's FFN-down site (mask seed of layer i-1, bias net.3.bias)
                 lq = f'{pre}transformer.layers.{i - 1}.'
@@ -942,7 +1102,7 @@ class VitEngine:
         rows; the CLS attention backward writes dK / dV of every row and the compact dQ; the K / V products over every row, the Q products
         over the CLS rows.  LayerNorm 1's backward runs over every row as in `_trunk_bwd`, its residual gradient d(x1) being non-zero on
         the CLS rows only (scattered into the zeroed `dres`).  Fills the layer's gradients and releases its bucket; returns (d(x_in) = out,
-        the free full slab = dres)"""
+        the free full slab = dres), or (None, None) when a backward plan (frozen parameters) stopped the pass inside the block"""
         a, W, P, G = self.act, self.W, self.P32, self.G32
         l, st = lib(), stream()
         d, f, h, dh, N = self.d, self.f, self.h, self.dh, self.T
@@ -958,19 +1118,33 @@ class VitEngine:
             check(l.ecgvit_dropout_apply_rows(ptr(dXc), ptr(a['cls_dy']), B, d, N, ph, s0 + 4, T, st), 'dropout_apply_rows')
             dY = a['cls_dy']
         self._colsum(dY, d, G[lp + '1.fn.net.3.bias'], B, d)
-        self._gemm(GEMM_TN, dY, a['cls_hact'], G[lp + '1.fn.net.3.weight'], d, f, B, d, f, f, workspace=ws)
+        if self._wants(lp + '1.fn.net.3.weight'):
+            self._gemm(GEMM_TN, dY, a['cls_hact'], G[lp + '1.fn.net.3.weight'], d, f, B, d, f, f, workspace=ws)
+        b = self._stage(i, 0)   # frozen parameters: the pass stops before the first input-gradient stage nothing trainable needs
+        if not self._reach(b):
+            return None, None
         self._gemm(GEMM_NN, dY, W[lp + '1.fn.net.3.weight'], a['cls_dh'], B, f, d, d, f, f, epilogue=EPI_MUL_AUX | EPI_COLSUM, aux=a['cls_hpre'],
                    ldaux=f, workspace=ws, colsum_out=G[lp + '1.fn.net.0.bias'])
-        self._gemm(GEMM_TN, a['cls_dh'], a['cls_xn2'], G[lp + '1.fn.net.0.weight'], f, d, B, f, d, d, workspace=ws)
+        if self._wants(lp + '1.fn.net.0.weight'):
+            self._gemm(GEMM_TN, a['cls_dh'], a['cls_xn2'], G[lp + '1.fn.net.0.weight'], f, d, B, f, d, d, workspace=ws)
+        if not self._reach(b + 1):
+            return None, None
         self._gemm(GEMM_NN, a['cls_dh'], W[lp + '1.fn.net.0.weight'], a['cls_dxn'], B, d, f, f, d, d)
+        if not self._reach(b + 2):
+            return None, None
         check(l.ecgvit_layernorm_bwd_fused_rowpitch(ptr(a['cls_dxn']), ptr(a['cls_x1']), ptr(P[lp + '1.norm.weight']), ptr(a['cls_mean2']),
                                                     ptr(a['cls_rstd2']), ptr(dXc), ptr(a['cls_dx1']), ptr(G[lp + '1.norm.weight']),
                                                     ptr(G[lp + '1.norm.bias']), ptr(ws), B, d, ptr(a['cls_dxm']), ptr(G[lp + '0.fn.to_out.0.bias']),
                                                     ph, s0 + 2, N, T, st), 'layernorm_bwd_fused_rowpitch')
         # ---- Attention: x1 = drop(attn Wo^T + bo) + x, the CLS rows
         dY = a['cls_dxm'] if ph > 0 else a['cls_dx1']
-        self._gemm(GEMM_TN, dY, a['cls_attn'], G[lp + '0.fn.to_out.0.weight'], d, d, B, d, d, d, workspace=ws)
+        if self._wants(lp + '0.fn.to_out.0.weight'):
+            self._gemm(GEMM_TN, dY, a['cls_attn'], G[lp + '0.fn.to_out.0.weight'], d, d, B, d, d, d, workspace=ws)
+        if not self._reach(b + 3):
+            return None, None
         self._gemm(GEMM_NN, dY, W[lp + '0.fn.to_out.0.weight'], a['cls_dattn'], B, d, d, d, d, d)
+        if not self._reach(b + 4):
+            return None, None
         ntok = self.saved.get('ntok')
         if ntok is not None:
             check(l.ecgvit_attention_varlen_cls_bwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_dattn']), ptr(a['cls_lse']), ptr(a['dqkv']),
@@ -980,14 +1154,19 @@ class VitEngine:
                                              B, N, h, dh, self.scale, ph, s0 + 1, T, st), 'attention_cls_bwd')
         # to_qkv: dW[K|V] = dKV^T . xn1 over every row, dW[Q] = dQ^T . xn1 over the CLS rows; d(xn1) = dKV . W[K|V] (+ dQ . W[Q] on the CLS rows)
         name = lp + '0.fn.to_qkv.weight'
-        self._gemm(GEMM_TN, a['dqkv'], L['xn1'], G[name], 2 * d, d, M, 3 * d, d, d, workspace=ws, a_off=d, c_off=d * d)
-        self._gemm(GEMM_TN, a['cls_dq'], L['xn1'], G[name], d, d, B, d, N * d, d, workspace=ws)
+        if self._wants(name):
+            self._gemm(GEMM_TN, a['dqkv'], L['xn1'], G[name], 2 * d, d, M, 3 * d, d, d, workspace=ws, a_off=d, c_off=d * d)
+            self._gemm(GEMM_TN, a['cls_dq'], L['xn1'], G[name], d, d, B, d, N * d, d, workspace=ws)
+        if not self._reach(b + 5):
+            return None, None
         wt = self.WT.get(name)
         if wt is not None and M >= 2048:
             self._gemm(GEMM_NT, a['dqkv'], wt, a['dxn'], M, d, 2 * d, 3 * d, 3 * d, d, a_off=d, b_off=d)
         else:
             self._gemm(GEMM_NN, a['dqkv'], W[name], a['dxn'], M, d, 2 * d, 3 * d, d, d, a_off=d, b_off=d * d)
         self._gemm(GEMM_NN, a['cls_dq'], W[name], a['dxn'], B, d, d, d, d, N * d, epilogue=hip.EPI_ACCUM)
+        if not self._reach(b + 6):
+            return None, None
         dres.zero_()
         check(l.ecgvit_scatter_rows(ptr(a['cls_dx1']), ptr(self._cls_rows(B)), ptr(dres), B, N, 1, d, d, d, T, st), 'scatter_rows')
         if i > 0:

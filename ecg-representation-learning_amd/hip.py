@@ -93,6 +93,9 @@ SIGNATURES = {
     'ecgvit_sumsq_workspace': (c_int64, [_L]),
     'ecgvit_sumsq': (c_int, [_P, _L, _P, _P, _P]),
     'ecgvit_adamw_step': (c_int, [_P, _P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _F, _F, _I, _I, _P, _P]),
+    'ecgvit_sumsq_spans_workspace': (c_int64, [_I]),
+    'ecgvit_sumsq_spans': (c_int, [_P, _P, _I, _L, _P, _P, _P]),
+    'ecgvit_adamw_step_spans': (c_int, [_P, _P, _P, _P, _P, _P, _I, _L, _P, _F, _F, _F, _F, _F, _F, _F, _I, _I, _P, _P]),
     'ecgvit_clip_scale': (c_int, [_P, _L, _P, _F, _P, _P]),
     'ecgvit_cast_f32_to_bf16': (c_int, [_P, _P, _L, _P]),
     'ecgvit_cast_bf16_to_f32': (c_int, [_P, _P, _L, _P]),

@@ -109,6 +109,13 @@ class HipTrainStep:
         self.comm_dtype = grad_comm_dtype
         self._xchg = self._xchg_layout = None
         self._replicas_synced = False
+        # frozen parameters (requires_grad=False), read every step: the flags the span table below was built for, per-parameter step offsets
+        # (a parameter's own optimiser step = step_count + lag, as torch keeps state['step'] per parameter), the span table
+        self._flags = None
+        self._flags_dirty = False
+        self._lag = None
+        self._spans = None          # None: every parameter trainable at the global step -> the whole-buffer kernels
+        self._trainable = None      # names (None = all), for the backward plan and the weight-shadow refresh
 
     # -- lr as the reference logs it: scheduler.get_last_lr() after `step_count` scheduler steps
     def get_last_lr(self):
@@ -128,12 +135,47 @@ class HipTrainStep:
             self.sumsq = torch.zeros(1, device=m._pflat.device, dtype=torch.float32)
             self.ws = torch.empty(hip.lib().ecgvit_sumsq_workspace(m._pflat.numel()), device=m._pflat.device, dtype=torch.uint8)
             self._replicas_synced = False
+            self._flags_dirty = True
         if self.collectives and not self._replicas_synced:
             # data-parallel replicas must start from the same weights whatever each rank's RNG produced: rank 0's flat buffer wins
             ddp.broadcast_flat_(m._pflat, src=0, group=self.pg, single_rank=True)
             if m._wlow is not None:
                 m.refresh_low_precision_weights(force=True)
             self._replicas_synced = True
+
+    # -- frozen parameters: host work only, every step
+    def _read_flags(self, model):
+        """read the requires_grad flags (before any launch: a step with no trainable parameter raises ValueError); a changed set is
+        applied by `_apply_flags` once the buffers exist"""
+        flags = tuple(p.requires_grad for p in model._param_list)
+        if not any(flags):
+            raise ValueError('no trainable parameter: every parameter has requires_grad=False')
+        if self._lag is None or len(self._lag) != len(flags):
+            self._lag = [0] * len(flags)
+            self._flags = None
+        if flags != self._flags:
+            self._flags, self._flags_dirty = flags, True
+
+    def _apply_flags(self, model):
+        """the frozen set changed: agree on it with the other ranks, rebuild the span table, the trainable names and the exchange layout"""
+        if not self._flags_dirty:
+            return
+        flags = self._flags
+        if self.collectives:
+            # every rank's bucket sequence follows its frozen set: ranks that disagreed would post mismatched collectives and hang
+            ddp.check_same_frozen_set(flags, group=self.pg, device=model._pflat.device, single_rank=True)
+        names = model._param_names
+        rows = span_table(model._layout, names, flags, self._lag)
+        if rows is None:
+            self._spans, self._trainable = None, None
+        else:
+            self._spans = (torch.tensor(rows, dtype=torch.int64, device=model._pflat.device), len(rows), sum(r[1] for r in rows))
+            self._trainable = [n for n, f in zip(names, flags) if f]
+            need = hip.lib().ecgvit_sumsq_spans_workspace(len(rows))
+            if need > self.ws.numel():
+                self.ws = torch.empty(need, device=model._pflat.device, dtype=torch.uint8)
+        self._xchg = None   # the exchange layout follows the frozen set
+        self._flags_dirty = False
 
     def _dropout_seed(self, model):
         """one fresh seed per step from the host RNG; the rank is folded in so that replicas seeded identically (as DDP scripts
@@ -148,7 +190,10 @@ class HipTrainStep:
         eng = model._engine()
         if self.collectives:
             if self._xchg is None or self._xchg_layout is not model._layout:
-                self._xchg = ddp.GradExchange(model._layout.buckets_in_ready_order(eng.Ly), group=self.pg, overlap=self.overlap,
+                ranges = model._layout.buckets_in_ready_order(eng.Ly)
+                if self._trainable is not None:   # frozen parameters: only the trainable part of a bucket travels; frozen buckets never do
+                    ranges = trainable_ranges(model._layout, ranges, self._trainable)
+                self._xchg = ddp.GradExchange(ranges, group=self.pg, overlap=self.overlap,
                                               comm_dtype=self.comm_dtype, single_rank_collectives=True)
                 self._xchg_layout = model._layout
             self._xchg.begin(model._gflat)
@@ -165,7 +210,9 @@ class HipTrainStep:
         wrapper, model = self.model, self.model.encoder
         if not model.training:
             raise RuntimeError('train step on a model in eval mode')
+        self._read_flags(model)
         self._state()
+        self._apply_flags(model)
         self._raise_if_flagged()
         eng = model._engine()
         seed = self._dropout_seed(model)
@@ -192,7 +239,7 @@ class HipTrainStep:
         model._fwd_id += 1
         tpw = self._arm_overlap(model)
         try:
-            eng.backward_masked(tiles_per_workgroup=tpw)
+            eng.backward_masked(tiles_per_workgroup=tpw, trainable=self._trainable)
         finally:
             eng.on_grads_ready = None
         loss, pred = loss.clone(), pred.clone()   # the engine reuses its buffers next step: hand out copies
@@ -206,7 +253,12 @@ class HipTrainStep:
             self._xchg.finish()
         l = hip.lib()
         st = hip.stream()
-        hip.check(l.ecgvit_sumsq(gflat.data_ptr(), gflat.numel(), self.sumsq.data_ptr(), self.ws.data_ptr(), st), 'sumsq')
+        spans = self._spans
+        if spans is None:
+            hip.check(l.ecgvit_sumsq(gflat.data_ptr(), gflat.numel(), self.sumsq.data_ptr(), self.ws.data_ptr(), st), 'sumsq')
+        else:   # frozen parameters: the norm of the trainable gradients only
+            hip.check(l.ecgvit_sumsq_spans(gflat.data_ptr(), spans[0].data_ptr(), spans[1], spans[2], self.sumsq.data_ptr(), self.ws.data_ptr(), st),
+                      'sumsq_spans')
         # The non-finite decision needs only the sum of squares (the optimiser kernel's test is isfinite(sqrt(sumsq) * |1/world|)): its
         # readback goes out HERE, ahead of the optimiser and the weight-shadow transposes, so that the same-step check below lets the host
         # go on ~0.8 ms before the device has finished the step -- the Python prelude of the next step then runs under those kernels instead
@@ -216,12 +268,22 @@ class HipTrainStep:
         self._flag_event.record()
         self.step_count += 1
         lr = self.lr0 * self.mult(self.step_count - 1)  # lr in effect for this optimiser step
-        hip.check(l.ecgvit_adamw_step(
-            model._pflat.data_ptr(), gflat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-            model._wlow.data_ptr() if model._wlow is not None else None, gflat.numel(), self.sumsq.data_ptr(),
-            1.0 / self.world, self.max_grad_norm, lr, 0.9, 0.999, 1e-8, self.wd, self.step_count, 1 if self.decoupled else 0,
-            self.norm_out.data_ptr(), st), 'adamw_step')
-        model.refresh_transposed_weights()   # the optimiser kernel rewrote the bf16 shadows
+        wlow = model._wlow.data_ptr() if model._wlow is not None else None
+        if spans is None:
+            hip.check(l.ecgvit_adamw_step(
+                model._pflat.data_ptr(), gflat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), wlow, gflat.numel(), self.sumsq.data_ptr(),
+                1.0 / self.world, self.max_grad_norm, lr, 0.9, 0.999, 1e-8, self.wd, self.step_count, 1 if self.decoupled else 0,
+                self.norm_out.data_ptr(), st), 'adamw_step')
+        else:
+            # frozen parameters: no update, no decay, no moment update; each span at its own step (the lr follows the global one)
+            hip.check(l.ecgvit_adamw_step_spans(
+                model._pflat.data_ptr(), gflat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), wlow, spans[0].data_ptr(), spans[1], spans[2],
+                self.sumsq.data_ptr(), 1.0 / self.world, self.max_grad_norm, lr, 0.9, 0.999, 1e-8, self.wd, self.step_count,
+                1 if self.decoupled else 0, self.norm_out.data_ptr(), st), 'adamw_step_spans')
+            for i, f in enumerate(self._flags):
+                if not f:
+                    self._lag[i] -= 1   # a frozen parameter's own step count stands still
+        model.refresh_transposed_weights(only=self._trainable)   # the optimiser kernel rewrote the bf16 shadows (of the trainable weights)
         # non-blocking readback of (norm, finite flag) as the kernel computed them: only read if the early check fires (the message's norm)
         self.norm_host.copy_(self.norm_out, non_blocking=True)
         self._norm_event.record()
@@ -234,7 +296,9 @@ class HipTrainStep:
         model = self.model
         if not model.training:
             raise RuntimeError('train step on a model in eval mode')
+        self._read_flags(model)
         self._state()
+        self._apply_flags(model)
         self._raise_if_flagged()
         eng = model._engine()
         seed = self._dropout_seed(model)
@@ -251,7 +315,7 @@ class HipTrainStep:
         B, K = x.shape[0], eng.K
         tpw = self._arm_overlap(model)
         try:
-            eng.backward(gscalar=self._one(x.device), gscale=1.0 / (B * K), tiles_per_workgroup=tpw)
+            eng.backward(gscalar=self._one(x.device), gscale=1.0 / (B * K), tiles_per_workgroup=tpw, trainable=self._trainable)
         finally:
             eng.on_grads_ready = None
         loss_mean, logits = loss_mean.clone(), logits.clone()   # the engine reuses its buffers next step: hand out copies
@@ -289,6 +353,39 @@ class HipTrainStep:
         self._raise_if_flagged(wait=True)
 
 
+def span_table(layout, names, flags, lag):
+    """rows {element offset, count, step offset} of the flat buffers that a fused step with frozen parameters counts and updates: runs of
+    consecutive trainable parameters (in the flat layout's order: embedding, blocks 0..L-1, head, pre-train head) with equal step offsets
+    merge into one span (the 64-B alignment padding between them holds zeros and stays zero).  None when every parameter is trainable at
+    the global step (the whole-buffer kernels then run, exactly as without frozen parameters)."""
+    if all(flags) and not any(lag):
+        return None
+    lag_of = {n: (f, g) for n, f, g in zip(names, flags, lag)}
+    rows, joined = [], False   # joined: the previous parameter in the layout is trainable (its span may grow)
+    for n, (off, _, cnt) in layout.entries.items():
+        f, g = lag_of[n]
+        if f and joined and rows[-1][2] == g:
+            rows[-1][1] = off + cnt - rows[-1][0]
+        elif f:
+            rows.append([off, cnt, g])
+        joined = f
+    if not rows:
+        raise ValueError('no trainable parameter: every parameter has requires_grad=False')
+    return rows
+
+
+def trainable_ranges(layout, buckets, trainable):
+    """the gradient exchange's buckets with frozen parameters: per bucket, the element range from its first to its last trainable parameter;
+    buckets without one are dropped (never reported by the backward, never exchanged)"""
+    trainable = set(trainable)
+    out = []
+    for tag, (lo, hi) in buckets:
+        sel = [(o, o + c) for n, (o, _, c) in layout.entries.items() if n in trainable and lo <= o < hi]
+        if sel:
+            out.append((tag, (min(a for a, _ in sel), min(hi, (max(b for _, b in sel) + 15) // 16 * 16))))
+    return out
+
+
 def clip_grad_norm_(model, max_norm=1.0, error_if_nonfinite=True):
     """`nn.utils.clip_grad_norm_` for the torch-optimizer interop path, on the model's flat gradient buffer (one
     sum-of-squares pass + one scale pass instead of ~150 per-parameter launches). Requires `p.grad` to be the
@@ -302,7 +399,14 @@ def clip_grad_norm_(model, max_norm=1.0, error_if_nonfinite=True):
     ws = torch.empty(l.ecgvit_sumsq_workspace(g.numel()), device=g.device, dtype=torch.uint8)
     sumsq = torch.empty(1, device=g.device, dtype=torch.float32)
     out = torch.empty(2, device=g.device, dtype=torch.float32)
-    hip.check(l.ecgvit_sumsq(g.data_ptr(), g.numel(), sumsq.data_ptr(), ws.data_ptr(), hip.stream()), 'sumsq')
+    has = [p.grad is not None for p in model._param_list]
+    if all(has):
+        hip.check(l.ecgvit_sumsq(g.data_ptr(), g.numel(), sumsq.data_ptr(), ws.data_ptr(), hip.stream()), 'sumsq')
+    else:   # as torch: parameters without a gradient (frozen ones) are not counted; their part of the buffer is not a gradient
+        rows = span_table(model._layout, model._param_names, has, [0] * len(has))
+        spans = torch.tensor(rows, dtype=torch.int64, device=g.device)
+        hip.check(l.ecgvit_sumsq_spans(g.data_ptr(), spans.data_ptr(), len(rows), sum(r[1] for r in rows), sumsq.data_ptr(), ws.data_ptr(),
+                                       hip.stream()), 'sumsq_spans')
     hip.check(l.ecgvit_clip_scale(g.data_ptr(), g.numel(), sumsq.data_ptr(), float(max_norm), out.data_ptr(), hip.stream()),
               'clip_scale')
     norm, finite = out.tolist()

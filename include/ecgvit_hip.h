@@ -320,6 +320,17 @@ int ecgvit_sumsq(const float *g, int64_t count, float *out, void *partial, void 
 int ecgvit_adamw_step(float *p, const float *g, float *m, float *v, void *p_lowp, int64_t count,
                       const float *sumsq, float grad_scale, float max_norm, float lr, float beta1, float beta2,
                       float eps, float weight_decay, int step, int decoupled, float *norm_out, void *stream);
+/* The same two passes over a SPAN TABLE of the flat buffers (frozen parameters: only trainable ones are counted and updated).
+ * spans (DEVICE, int64 [nspan][3]) = {element offset, count, step offset}; total = the sum of the counts (sizes the grid).
+ * ecgvit_sumsq_spans: out[0] = sum of g^2 over the spans (f32, deterministic two-stage; `partial` = ecgvit_sumsq_spans_workspace bytes).
+ * ecgvit_adamw_step_spans: ecgvit_adamw_step restricted to the spans; span s takes its bias corrections at step + spans[s][2] (its own
+ * optimiser step count, as torch keeps state['step'] per parameter); lr is the caller's, from the global step.  Elements outside the
+ * spans are neither read nor written.  Non-finite norm: nothing is updated, norm_out[1] = 0. */
+int64_t ecgvit_sumsq_spans_workspace(int nspan);
+int ecgvit_sumsq_spans(const float *g, const int64_t *spans, int nspan, int64_t total, float *out, void *partial, void *stream);
+int ecgvit_adamw_step_spans(float *p, const float *g, float *m, float *v, void *p_lowp, const int64_t *spans, int nspan, int64_t total,
+                            const float *sumsq, float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
+                            float weight_decay, int step, int decoupled, float *norm_out, void *stream);
 /* g *= min(1, max_norm/(norm+1e-6)) in place (torch-optimizer interop path); norm_out as above */
 int ecgvit_clip_scale(float *g, int64_t count, const float *sumsq, float max_norm, float *norm_out, void *stream);
 int ecgvit_cast_f32_to_bf16(const float *src, void *dst, int64_t count, void *stream);
