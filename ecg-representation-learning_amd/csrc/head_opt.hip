@@ -2,6 +2,8 @@
 // global-norm clip + AdamW step over flat f32 buffers.  Small or HBM-bound; all f32 except the
 // activation tensor X / dX (template T) and the optional bf16 shadow weights.
 #include "common.h"
+#include <map>
+#include <mutex>
 
 namespace {
 
@@ -280,6 +282,52 @@ __global__ __launch_bounds__(256) void adamw_spans_kernel(float *__restrict__ p,
     }
 }
 
+// ---- micro-batch gradient accumulation over a span table (same format as above): MODE INIT acc = s*g, ADD acc += s*g, FOLD g = s*g + acc.
+//      Every element of a span is read and written by exactly one thread (no reduction, no atomics), so the result does not depend on the
+//      grid.  Spans whose offset is a multiple of 4 take 16-B accesses; the layout's offsets are multiples of 16 (the host checks it), the
+//      element path only covers a count's tail.
+template <int MODE>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float *__restrict__ acc, float *__restrict__ g, const int64_t *__restrict__ spans,
+                                                              int nspan, float scale) {
+    const int64_t stride = (int64_t)gridDim.x * 256, tid = blockIdx.x * 256ll + threadIdx.x;
+    for (int k = 0; k < nspan; ++k) {
+        const int64_t off = spans[3 * k], count = spans[3 * k + 1];
+        float *a = acc + off, *x = g + off;
+        int64_t head = 0;
+        if ((off & 3) == 0) {
+            head = count / 4 * 4;
+            f32x4 *av = reinterpret_cast<f32x4 *>(a), *xv = reinterpret_cast<f32x4 *>(x);
+            for (int64_t i = tid; i < count / 4; i += stride) {
+                const f32x4 gv = xv[i] * scale;
+                if (MODE == ECGVIT_ACC_INIT) av[i] = gv;
+                else if (MODE == ECGVIT_ACC_ADD) av[i] = av[i] + gv;
+                else xv[i] = gv + av[i];
+            }
+        }
+        for (int64_t i = head + tid; i < count; i += stride) {
+            const float gv = x[i] * scale;
+            if (MODE == ECGVIT_ACC_INIT) a[i] = gv;
+            else if (MODE == ECGVIT_ACC_ADD) a[i] = a[i] + gv;
+            else x[i] = gv + a[i];
+        }
+    }
+}
+
+// CUs of the current device (cached per device): the accumulate pass launches a fixed number of workgroups per CU
+int device_cus() {
+    static std::mutex mu;
+    static std::map<int, int> cus;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    std::lock_guard<std::mutex> lock(mu);
+    const auto it = cus.find(dev);
+    if (it != cus.end()) return it->second;
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 0;
+    cus[dev] = v;
+    return v;
+}
+
 // ---- batched transpose of bf16 matrices that live at the SAME offsets in two flat buffers (shadow weights -> transposed shadows):
 //      table[4i..4i+3] = {element offset, rows, cols, index of the matrix's first 64x64 tile}; dst holds cols x rows row-major.
 //      One 64 x 64 tile per 256-thread block through LDS; 16-B accesses on both sides when the tile is interior.
@@ -431,6 +479,25 @@ int ecgvit_adamw_step_spans(float *p, const float *g, float *m, float *v, void *
     if (nspan <= 0 || total <= 0 || !spans || !sumsq) return ECGVIT_EINVAL;
     hipLaunchKernelGGL(adamw_spans_kernel, dim3(ew_grid(total)), dim3(256), 0, as_stream(stream), p, g, m, v, (bf16_t *)p_lowp, spans, nspan,
                        sumsq, grad_scale, max_norm, lr, beta1, beta2, eps, weight_decay, step, decoupled, norm_out);
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
+}
+
+int ecgvit_grad_accumulate(float *acc, float *g, const int64_t *spans, int nspan, int64_t total, int mode, float scale, void *stream) {
+    if (nspan <= 0 || total <= 0 || !spans || !acc || !g || (reinterpret_cast<uintptr_t>(acc) % 16) != 0 ||
+        (reinterpret_cast<uintptr_t>(g) % 16) != 0)
+        return ECGVIT_EINVAL;
+    const int n_cu = device_cus();
+    if (n_cu <= 0) return ECGVIT_ELAUNCH;
+    // 8 workgroups of 256 lanes per CU, fewer for a small pass (a whole span table in one launch: 16 B per lane and trip)
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((total / 4 + 255) / 256, 8ll * n_cu));
+    hipStream_t s = as_stream(stream);
+    switch (mode) {
+    case ECGVIT_ACC_INIT: hipLaunchKernelGGL(grad_accumulate_kernel<ECGVIT_ACC_INIT>, dim3(nb), dim3(256), 0, s, acc, g, spans, nspan, scale); break;
+    case ECGVIT_ACC_ADD: hipLaunchKernelGGL(grad_accumulate_kernel<ECGVIT_ACC_ADD>, dim3(nb), dim3(256), 0, s, acc, g, spans, nspan, scale); break;
+    case ECGVIT_ACC_FOLD: hipLaunchKernelGGL(grad_accumulate_kernel<ECGVIT_ACC_FOLD>, dim3(nb), dim3(256), 0, s, acc, g, spans, nspan, scale); break;
+    default: return ECGVIT_EINVAL;
+    }
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
 }

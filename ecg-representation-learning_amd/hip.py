@@ -20,6 +20,7 @@ GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
 EPI_BIAS, EPI_GELU, EPI_GELU_BWD, EPI_RESIDUAL, EPI_ACCUM, EPI_DROPOUT, EPI_COLSUM = 1, 2, 4, 8, 16, 32, 64
 EPI_GELU_GRAD_AUX, EPI_MUL_AUX, EPI_QUANT_OUT, EPI_NO_OUT, EPI_AUX8 = 128, 256, 512, 1024, 2048
 
+ACC_INIT, ACC_ADD, ACC_FOLD = 0, 1, 2   # ecgvit_grad_accumulate modes
 KERNEL_NONE, KERNEL_GEMM_F32, KERNEL_GEMM_BF16, KERNEL_GEMM_NT, KERNEL_GEMM_WGRAD = 0, 1, 2, 3, 4
 
 _ERR = {1: 'ECGVIT_EINVAL (unsupported shape / argument)', 2: 'ECGVIT_ELAUNCH (HIP launch failure)'}
@@ -96,6 +97,7 @@ SIGNATURES = {
     'ecgvit_sumsq_spans_workspace': (c_int64, [_I]),
     'ecgvit_sumsq_spans': (c_int, [_P, _P, _I, _L, _P, _P, _P]),
     'ecgvit_adamw_step_spans': (c_int, [_P, _P, _P, _P, _P, _P, _I, _L, _P, _F, _F, _F, _F, _F, _F, _F, _I, _I, _P, _P]),
+    'ecgvit_grad_accumulate': (c_int, [_P, _P, _P, _I, _L, _I, _F, _P]),
     'ecgvit_clip_scale': (c_int, [_P, _L, _P, _F, _P, _P]),
     'ecgvit_cast_f32_to_bf16': (c_int, [_P, _P, _L, _P]),
     'ecgvit_cast_bf16_to_f32': (c_int, [_P, _P, _L, _P]),

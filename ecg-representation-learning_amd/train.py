@@ -19,6 +19,7 @@ exchange overlaps the remaining backward.
 Logging / TensorBoard / sklearn metrics / datasets of MyTrainer are host-side and out of scope here.
 """
 import math
+import numbers
 import sys
 
 import torch
@@ -27,9 +28,12 @@ import torch.distributed as dist
 from .check_args import ca
 from . import hip
 from . import ddp
+from .engine import check_lengths
 
 
 def get_train_args(args=None, n_train=None):
+    """the reference's defaults, key for key.  One key of this project rides along when given: micro_batch_size (the default of
+    HipTrainStep.step / step_masked; absent = None, the whole batch in one pass) -- the reference's TODO at train.py:431"""
     default_args = dict(
         num_train_epoch=3,
         train_batch_size=64,
@@ -56,6 +60,7 @@ def get_train_args(args=None, n_train=None):
     args_['steps_per_epoch'] = steps_per_epoch = math.ceil((n_train or int(sys.maxsize)) // args_['train_batch_size'])
     args_['n_step'] = steps_per_epoch * args_['num_train_epoch']
     ca(optimizer=args_['optimizer'], schedule=args_['schedule'])
+    check_micro_batch_size(args_.get('micro_batch_size'))
     return args_
 
 
@@ -73,11 +78,28 @@ def lr_multiplier(schedule, n_warmup, n_step):
     return f
 
 
+def check_micro_batch_size(value):
+    """None (the whole batch in one pass) or a positive int, else ValueError"""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or value <= 0:
+        raise ValueError(f'micro_batch_size must be a positive int or None, got {value!r}')
+    return int(value)
+
+
 class HipTrainStep:
     """
     step(sample_values, labels) == reference train.py:271-283 for one batch, fused.
 
-    args: dict as produced by `get_train_args` (uses optimizer, learning_rate, weight_decay, warmup_ratio, schedule, n_step).
+    args: dict as produced by `get_train_args` (uses optimizer, learning_rate, weight_decay, warmup_ratio, schedule, n_step, and
+    micro_batch_size: the default of `step` / `step_masked`).
+
+    Gradient accumulation (micro_batch_size=m < B): the batch of one optimiser step runs as ceil(B/m) forward + backward passes over the
+    consecutive slices [s, s+m) (the last may be shorter), the activation memory of m records, then ONE clip + AdamW update.  Each backward
+    pass overwrites the flat gradient buffer as usual; `ecgvit_grad_accumulate` sums it into a second flat buffer (`gacc`, allocated on the
+    first split batch) and folds the sum back before the norm, the data-parallel exchange (last pass only) and the optimiser.  Up to f32
+    summation order this is the full batch's step when dropout is 0.  With dropout every pass draws its own seed, so the masks are not those
+    of the unsplit batch.
     """
 
     def __init__(self, model, args=None, max_grad_norm=1.0, sync_nonfinite=True, process_group=None, overlap_allreduce=True,
@@ -116,6 +138,10 @@ class HipTrainStep:
         self._lag = None
         self._spans = None          # None: every parameter trainable at the global step -> the whole-buffer kernels
         self._trainable = None      # names (None = all), for the backward plan and the weight-shadow refresh
+        # gradient accumulation: the default micro-batch size, the accumulator (flat f32, the gradient buffer's layout), its span tables
+        self.micro_batch_size = check_micro_batch_size(self.args.get('micro_batch_size'))
+        self.gacc = None
+        self._acc_tables = None     # (key, whole table, {bucket tag: table}) -- a table is (device int64 [n][3], n, total)
 
     # -- lr as the reference logs it: scheduler.get_last_lr() after `step_count` scheduler steps
     def get_last_lr(self):
@@ -205,8 +231,10 @@ class HipTrainStep:
         eng.on_grads_ready = None
         return 0
 
-    def step_masked(self, sample_values, mask_idx):
-        """the same fused step for the masked pre-train objective; `self.model` must be a MaskedEcgVit"""
+    def step_masked(self, sample_values, mask_idx, micro_batch_size=None):
+        """the same fused step for the masked pre-train objective; `self.model` must be a MaskedEcgVit.
+        micro_batch_size: as `step` (None: the default given in args); the loss is the whole batch's mean"""
+        mb = self._micro_batch_size(micro_batch_size)
         wrapper, model = self.model, self.model.encoder
         if not model.training:
             raise RuntimeError('train step on a model in eval mode')
@@ -215,26 +243,12 @@ class HipTrainStep:
         self._apply_flags(model)
         self._raise_if_flagged()
         eng = model._engine()
+        if mb is not None and mb < sample_values.shape[0]:
+            return self._step_masked_micro(wrapper, model, eng, sample_values, mask_idx, mb)
         seed = self._dropout_seed(model)
         x = sample_values.contiguous().float()
         wrapper.check_mask_indices(mask_idx, x.shape[0])
-        if mask_idx.is_cuda:
-            idx = mask_idx.to(dtype=torch.int32).contiguous()
-        else:
-            # host indices (checked on the host above) travel through a pinned staging buffer: a pageable-memory copy would block the host until
-            # the device has drained the stream, i.e. once per step.  The buffer is rewritten only after its last copy has left it (an event:
-            # normally long past -- with the deferred non-finite check the host may be a step ahead)
-            st = getattr(self, '_mask_stage', None)
-            if st is None or st[0].shape != mask_idx.shape:
-                st = (torch.empty(mask_idx.shape, dtype=torch.int32).pin_memory(), torch.empty(mask_idx.shape, dtype=torch.int32, device=x.device),
-                      torch.cuda.Event())
-                self._mask_stage = st
-            else:
-                st[2].synchronize()
-            st[0].copy_(mask_idx)
-            st[1].copy_(st[0], non_blocking=True)
-            st[2].record()
-            idx = st[1]
+        idx = self._device_mask_idx(mask_idx, x.device)
         pred, loss = eng.forward_masked(x, idx, training=True, seed=seed)
         model._fwd_id += 1
         tpw = self._arm_overlap(model)
@@ -246,6 +260,25 @@ class HipTrainStep:
         self._update(model)
         self.last_loss = loss
         return loss, pred
+
+    def _device_mask_idx(self, mask_idx, device):
+        """the (B, m) mask indices as a contiguous int32 device tensor"""
+        if mask_idx.is_cuda:
+            return mask_idx.to(dtype=torch.int32).contiguous()
+        # host indices (checked on the host by the caller) travel through a pinned staging buffer: a pageable-memory copy would block the host
+        # until the device has drained the stream, i.e. once per step.  The buffer is rewritten only after its last copy has left it (an event:
+        # normally long past -- with the deferred non-finite check the host may be a step ahead)
+        st = getattr(self, '_mask_stage', None)
+        if st is None or st[0].shape != mask_idx.shape:
+            st = (torch.empty(mask_idx.shape, dtype=torch.int32).pin_memory(), torch.empty(mask_idx.shape, dtype=torch.int32, device=device),
+                  torch.cuda.Event())
+            self._mask_stage = st
+        else:
+            st[2].synchronize()
+        st[0].copy_(mask_idx)
+        st[1].copy_(st[0], non_blocking=True)
+        st[2].record()
+        return st[1]
 
     def _update(self, model):
         gflat = model._gflat
@@ -291,8 +324,12 @@ class HipTrainStep:
         if self.sync_nonfinite:
             self._raise_if_flagged(wait=True)
 
-    def step(self, sample_values, labels, lengths=None):
-        """one fused training step; lengths: optional (B,) per-record sample counts (EcgVit.forward)"""
+    def step(self, sample_values, labels, lengths=None, micro_batch_size=None):
+        """one fused training step; lengths: optional (B,) per-record sample counts (EcgVit.forward).
+        micro_batch_size: None (the default given in args) or a positive int m; m < B accumulates the gradient of ceil(B/m) passes into one
+        optimiser step (see the class docstring; with dropout each pass draws its own masks).  Returns (loss_mean, logits (B, K)) of the
+        whole batch either way."""
+        mb = self._micro_batch_size(micro_batch_size)
         model = self.model
         if not model.training:
             raise RuntimeError('train step on a model in eval mode')
@@ -301,15 +338,17 @@ class HipTrainStep:
         self._apply_flags(model)
         self._raise_if_flagged()
         eng = model._engine()
+        # the classifier reads the CLS rows only: the last block skips the other rows past its K / V (bf16 engine; the fp8 step keeps the
+        # full block -- its 512-row products would fall below the 8-bit kernels' gates and change the delayed-scaling sites)
+        cls_only = eng.dtype == torch.bfloat16 and not eng.fp8
+        if mb is not None and mb < sample_values.shape[0]:
+            return self._step_micro(model, eng, sample_values, labels, lengths, mb, cls_only)
         seed = self._dropout_seed(model)
         x = sample_values.contiguous().float()
         y = labels.contiguous().float()
         w = None
         if model.loss_weight:
             w = torch.tensor(model.loss_weight, device=y.device, dtype=torch.float32)[y.long()].contiguous()
-        # the classifier reads the CLS rows only: the last block skips the other rows past its K / V (bf16 engine; the fp8 step keeps the
-        # full block -- its 512-row products would fall below the 8-bit kernels' gates and change the delayed-scaling sites)
-        cls_only = eng.dtype == torch.bfloat16 and not eng.fp8
         logits, _, loss_mean = eng.forward(x, y, w, training=True, seed=seed, want_mean=True, cls_only_last=cls_only, lengths=lengths)
         model._fwd_id += 1
         B, K = x.shape[0], eng.K
@@ -322,6 +361,141 @@ class HipTrainStep:
         self._update(model)
         self.last_loss = loss_mean
         return loss_mean, logits
+
+    # -- gradient accumulation over micro-batches
+    def _micro_batch_size(self, value):
+        return self.micro_batch_size if value is None else check_micro_batch_size(value)
+
+    def _step_micro(self, model, eng, sample_values, labels, lengths, mb, cls_only):
+        """`step` over consecutive slices of mb records: per slice a forward (its own dropout seed) and a backward with the WHOLE batch's
+        1/(B*K); the slices' logits are gathered and the loss is one BCE pass over all of them (equal logits -> the unsplit step's loss bit for
+        bit).  The labels, the loss_weight element weights and the lengths travel with their records."""
+        x = sample_values.contiguous().float()
+        y = labels.contiguous().float()
+        B, K = x.shape[0], eng.K
+        w = None
+        if model.loss_weight:
+            w = torch.tensor(model.loss_weight, device=y.device, dtype=torch.float32)[y.long()].contiguous()
+        if lengths is not None and eng.input_transform is None:
+            check_lengths(lengths, B, eng.P, x.shape[2])   # the whole batch's lengths are valid before the first pass
+        logits_all = torch.empty((B, K), device=x.device, dtype=torch.float32)
+        one = self._one(x.device)
+        starts = list(range(0, B, mb))
+        for j, s in enumerate(starts):
+            e = min(s + mb, B)
+            seed = self._dropout_seed(model)
+            logits, _, _ = eng.forward(x[s:e], y[s:e], None if w is None else w[s:e], training=True, seed=seed, want_mean=False,
+                                       cls_only_last=cls_only, lengths=None if lengths is None else lengths[s:e])
+            model._fwd_id += 1
+            logits_all[s:e].copy_(logits)
+            self._micro_backward(model, eng, j, j == len(starts) - 1,
+                                 lambda tpw: eng.backward(gscalar=one, gscale=1.0 / (B * K), tiles_per_workgroup=tpw, trainable=self._trainable))
+        if getattr(self, '_bce_elem', None) is None or self._bce_elem.shape != (B, K) or self._bce_elem.device != x.device:
+            self._bce_elem = torch.empty((B, K), device=x.device, dtype=torch.float32)
+        loss_mean = torch.empty(1, device=x.device, dtype=torch.float32)
+        hip.check(hip.lib().ecgvit_bce_fwd(logits_all.data_ptr(), y.data_ptr(), hip.ptr(w), self._bce_elem.data_ptr(), loss_mean.data_ptr(),
+                                           B * K, hip.stream()), 'bce_fwd')
+        self._update(model)
+        self.last_loss = loss_mean
+        return loss_mean, logits_all
+
+    def _step_masked_micro(self, wrapper, model, eng, sample_values, mask_idx, mb):
+        """`step_masked` over consecutive slices of mb records (records and mask indices together): slice j's L1 mean enters the loss and
+        the upstream gradient with weight B_j / B, so the sum is the whole batch's mean"""
+        x = sample_values.contiguous().float()
+        B = x.shape[0]
+        wrapper.check_mask_indices(mask_idx, B)
+        idx = self._device_mask_idx(mask_idx, x.device)   # staged once, sliced on the device
+        m = idx.shape[1]
+        l, st = hip.lib(), hip.stream()
+        loss = torch.empty(1, device=x.device, dtype=torch.float32)
+        one_span = self._const(x.device, 'one span', [[0, 1, 0]], torch.int64)   # the loss: a one-element span
+        pred_all = None
+        starts = list(range(0, B, mb))
+        for j, s in enumerate(starts):
+            e = min(s + mb, B)
+            seed = self._dropout_seed(model)
+            pred, mloss = eng.forward_masked(x[s:e], idx[s:e], training=True, seed=seed)
+            model._fwd_id += 1
+            if pred_all is None:
+                pred_all = torch.empty((B * m,) + tuple(pred.shape[1:]), device=x.device, dtype=pred.dtype)
+            pred_all[s * m:e * m].copy_(pred)
+            wj = (e - s) / B
+            hip.check(l.ecgvit_grad_accumulate(loss.data_ptr(), mloss.data_ptr(), one_span.data_ptr(), 1, 1,
+                                               hip.ACC_INIT if j == 0 else hip.ACC_ADD, wj, st), 'grad_accumulate')
+            gs = self._const(x.device, ('upstream', wj), [wj], torch.float32)
+            self._micro_backward(model, eng, j, j == len(starts) - 1,
+                                 lambda tpw: eng.backward_masked(gscalar=gs, tiles_per_workgroup=tpw, trainable=self._trainable))
+        self._update(model)
+        self.last_loss = loss
+        return loss, pred_all
+
+    def _const(self, device, key, values, dtype):
+        """a small constant device tensor, made once per key"""
+        cache = self.__dict__.setdefault('_consts', {})
+        if (key, device) not in cache:
+            cache[(key, device)] = torch.tensor(values, dtype=dtype, device=device)
+        return cache[(key, device)]
+
+    def _acc_state(self, model):
+        """the accumulator and its span tables: the whole table (the trainable spans, or one whole-buffer span) and, with an overlapped
+        exchange, one table per exchanged bucket (its range inside the trainable spans), rebuilt with the span table or the exchange"""
+        g = model._gflat
+        if self.gacc is None or self.gacc.numel() != g.numel() or self.gacc.device != g.device:
+            self.gacc = torch.zeros_like(g)
+        xchg = self._xchg if (self.collectives and self.overlap) else None
+        t = self._acc_tables
+        if t is None or t[0] is not self._spans or t[1] is not xchg or t[2] != g.numel():
+            rows = [[0, g.numel(), 0]] if self._spans is None else self._spans[0].tolist()
+            assert all(r[0] % 8 == 0 for r in rows), 'accumulator spans must start on 8-element boundaries'
+            whole = (torch.tensor(rows, dtype=torch.int64, device=g.device), len(rows), sum(r[1] for r in rows))
+            per = {}
+            if xchg is not None:
+                for tag, (lo, hi) in xchg.ranges.items():
+                    br = [[max(o, lo), min(o + c, hi) - max(o, lo), 0] for o, c, _ in rows if max(o, lo) < min(o + c, hi)]
+                    if br:
+                        assert all(r[0] % 8 == 0 for r in br), 'bucket ranges must start on 8-element boundaries'
+                        per[tag] = (torch.tensor(br, dtype=torch.int64, device=g.device), len(br), sum(r[1] for r in br))
+                # the buckets are disjoint; every trainable parameter must lie in one of them, or part of its gradient would never be folded
+                trainable = None if self._trainable is None else set(self._trainable)
+                folded = [(lo, lo + c) for tab in per.values() for lo, c, _ in tab[0].tolist()]
+                for n, (o, _, c) in model._layout.entries.items():
+                    if trainable is None or n in trainable:
+                        assert any(a <= o and o + c <= b for a, b in folded), f'{n} lies in no exchanged bucket'
+            self._acc_tables = (self._spans, xchg, g.numel(), whole, per)
+        return self._acc_tables[3], self._acc_tables[4]
+
+    def _accumulate(self, model, mode, table):
+        hip.check(hip.lib().ecgvit_grad_accumulate(self.gacc.data_ptr(), model._gflat.data_ptr(), table[0].data_ptr(), table[1], table[2], mode,
+                                                   1.0, hip.stream()), 'grad_accumulate')
+
+    def _micro_backward(self, model, eng, j, last, run):
+        """backward pass j of a split batch (`run(tiles_per_workgroup)`).  Before the last one: no exchange, then acc = g (j = 0) or acc += g.
+        The last one: armed for the exchange; g += acc over each bucket as the backward reports it final, right before its all-reduce goes out
+        (overlapped exchange), else over every span after the pass.  The number of collectives per optimiser step does not change."""
+        if not last:
+            eng.on_grads_ready = None
+            run(0)
+            whole, _ = self._acc_state(model)
+            self._accumulate(model, hip.ACC_INIT if j == 0 else hip.ACC_ADD, whole)
+            return
+        tpw = self._arm_overlap(model)
+        whole, per = self._acc_state(model)
+        if self.collectives and self.overlap:
+            folded = set()
+
+            def fold_then_send(tag):
+                if tag in per and tag not in folded:
+                    folded.add(tag)
+                    self._accumulate(model, hip.ACC_FOLD, per[tag])
+                self._xchg.bucket_ready(tag)
+            eng.on_grads_ready = fold_then_send
+        try:
+            run(tpw)
+        finally:
+            eng.on_grads_ready = None
+        if not (self.collectives and self.overlap):
+            self._accumulate(model, hip.ACC_FOLD, whole)
 
     def _one(self, device):
         if getattr(self, '_one_t', None) is None or self._one_t.device != device:

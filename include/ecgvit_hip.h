@@ -331,6 +331,18 @@ int ecgvit_sumsq_spans(const float *g, const int64_t *spans, int nspan, int64_t 
 int ecgvit_adamw_step_spans(float *p, const float *g, float *m, float *v, void *p_lowp, const int64_t *spans, int nspan, int64_t total,
                             const float *sumsq, float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,
                             float weight_decay, int step, int decoupled, float *norm_out, void *stream);
+/* Gradient accumulation over micro-batches (HipTrainStep.step(..., micro_batch_size=)); replaces what the reference left as
+ * `# TODO: gradient accumulation not supported` (models/train.py:431).  Each backward pass overwrites g (the flat gradient buffer); acc is
+ * a second flat f32 buffer of the same layout.  Over the spans (the span table above; step offsets unused):
+ *   ECGVIT_ACC_INIT  acc = scale * g          (after the first micro-batch)
+ *   ECGVIT_ACC_ADD   acc += scale * g         (after each middle micro-batch)
+ *   ECGVIT_ACC_FOLD  g = scale * g + acc      (the last micro-batch: g then holds the whole batch's gradient for the norm, the exchange and AdamW)
+ * scale = 1 for gradients (exact); total = the sum of the counts (sizes the grid).  acc and g 16-B aligned; span offsets should be multiples
+ * of 8 elements (16-B accesses; others take the element path).  Elements outside the spans are neither read nor written. */
+#define ECGVIT_ACC_INIT 0
+#define ECGVIT_ACC_ADD 1
+#define ECGVIT_ACC_FOLD 2
+int ecgvit_grad_accumulate(float *acc, float *g, const int64_t *spans, int nspan, int64_t total, int mode, float scale, void *stream);
 /* g *= min(1, max_norm/(norm+1e-6)) in place (torch-optimizer interop path); norm_out as above */
 int ecgvit_clip_scale(float *g, int64_t count, const float *sumsq, float max_norm, float *norm_out, void *stream);
 int ecgvit_cast_f32_to_bf16(const float *src, void *dst, int64_t count, void *stream);

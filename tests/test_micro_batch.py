@@ -1,0 +1,76 @@
+"""CPU: gradient accumulation over micro-batches in the fused train step -- the host side.  micro_batch_size is checked before any device
+work, get_train_args carries it, the accumulate entry point is bound (tests/test_abi.py then checks the export), and its kernel does not
+spill."""
+import os
+import sys
+
+import pytest
+import torch
+
+from conftest import ROOT
+import ecg_representation_learning_amd as E
+
+CONF = dict(max_signal_length=400, patch_size=20, hidden_size=64, num_hidden_layers=2, num_attention_heads=2, intermediate_size=128)
+BAD = (0, -1, 2.5, '4', True)
+
+
+@pytest.mark.parametrize('bad', BAD)
+def test_step_rejects_bad_micro_batch_size_without_a_device(bad):
+    m = E.EcgVit(config=E.EcgVitConfig(**CONF))
+    st = E.HipTrainStep(m)
+    x, y = torch.zeros(4, 12, 400), torch.zeros(4, 71)
+    with pytest.raises(ValueError, match='micro_batch_size'):
+        st.step(x, y, micro_batch_size=bad)
+    with pytest.raises(ValueError, match='micro_batch_size'):
+        st.step(x, y, lengths=torch.full((4,), 400), micro_batch_size=bad)
+
+
+@pytest.mark.parametrize('bad', BAD)
+def test_step_masked_rejects_bad_micro_batch_size_without_a_device(bad):
+    w = E.MaskedEcgVit(E.EcgVit(config=E.EcgVitConfig(**CONF)))
+    st = E.HipTrainStep(w)
+    x = torch.zeros(4, 12, 400)
+    with pytest.raises(ValueError, match='micro_batch_size'):
+        st.step_masked(x, w.random_mask_indices(4), micro_batch_size=bad)
+
+
+@pytest.mark.parametrize('bad', BAD)
+def test_constructor_rejects_bad_default(bad):
+    m = E.EcgVit(config=E.EcgVitConfig(**CONF))
+    with pytest.raises(ValueError, match='micro_batch_size'):
+        E.HipTrainStep(m, dict(micro_batch_size=bad))
+
+
+def test_train_args_carry_micro_batch_size():
+    # (absent by default: get_train_args keeps the reference's dict key for key, tests/test_host_contract.py)
+    assert E.get_train_args().get('micro_batch_size') is None
+    assert E.get_train_args(dict(micro_batch_size=32))['micro_batch_size'] == 32
+    with pytest.raises(ValueError, match='micro_batch_size'):
+        E.get_train_args(dict(micro_batch_size=0))
+    m = E.EcgVit(config=E.EcgVitConfig(**CONF))
+    assert E.HipTrainStep(m).micro_batch_size is None
+    assert E.HipTrainStep(m, E.get_train_args(dict(micro_batch_size=32))).micro_batch_size == 32
+    assert E.HipTrainStep(m, dict(micro_batch_size=8)).gacc is None   # the accumulator is allocated by the first split batch only
+
+
+def test_accumulate_entry_point_is_bound():
+    assert 'ecgvit_grad_accumulate' in E.hip.SIGNATURES
+    assert (E.hip.ACC_INIT, E.hip.ACC_ADD, E.hip.ACC_FOLD) == (0, 1, 2)
+    src = open(os.path.join(ROOT, 'include', 'ecgvit_hip.h')).read()
+    for k, v in (('INIT', 0), ('ADD', 1), ('FOLD', 2)):
+        assert f'#define ECGVIT_ACC_{k} {v}' in src
+
+
+def test_accumulate_kernel_does_not_spill():
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    import code_objects
+    if not os.path.exists(code_objects.READELF):
+        pytest.skip('llvm-readelf not in this image')
+    lib = os.path.join(ROOT, 'ecg-representation-learning_amd', 'libecgvit_hip.so')
+    if not os.path.exists(lib):
+        import __graft_entry__
+        __graft_entry__.build()
+    ks = {n: k for n, k in code_objects.kernels(lib).items() if 'grad_accumulate_kernel' in n}
+    assert len(ks) == 3, sorted(ks)   # INIT, ADD, FOLD
+    for n, k in ks.items():
+        assert k['vgpr_spill_count'] == 0 and k['private_segment_fixed_size'] == 0 and k['sgpr_spill_count'] == 0, (n, k)
