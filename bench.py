@@ -13,11 +13,14 @@ clip + AdamW [+ RCCL gradient all-reduce for N > 1], dropout active at the refer
 Workload at every N: EcgVit-base, bf16 MFMA path, 512 records x 12 leads x 5000 samples per GPU, patch 20 (251 tokens)
 (BASELINE.json configs[2]/[3]; weak scaling: global batch = 512 * N).
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run measures the headline figure and nothing else: it sets up, runs W untimed and K timed steps,
+writes --dump-outputs if asked and prints the line, with
   roofline      dominant kernel (gemm_nt_kernel: the bf16 MFMA A.B^T GEMM of the Linear forward and input-gradient products):
                 algorithmic FLOPs of its launches / their HIP-event time measured inside the timed region, against the
                 2.5 PFLOP/s dense bf16 peak; `traffic` = HBM bytes per launch from the committed rocprofv3 --pmc passes, null
                 (with the reason in `traffic_source`) when the kernel sources changed since that profile was taken.
+  dumped_outputs  (--dump-outputs DIR) the directory and the shape of every array written there.
+--full adds the measurements that take runs of their own, after the headline run (each can be left out with its --no-* flag):
   bf16_saved_tensor  (N = 1, default workload) the SAME step with the saved FFN tensor kept in bf16 (saved_ffn_e4m3=False) instead of e4m3 bytes: the headline
                 step stores one backward-only tensor per layer narrower than the metric's dtype; this is the pure-bf16-storage figure beside it.
   masked        (N = 1, default workload) the build's masked pre-train step timed in the same process: value, ms_per_step, model TFLOP/s at its own
@@ -25,8 +28,7 @@ Rank 0 prints ONE JSON line.  Extra objects:
   small         (N = 1, default workload) BASELINE.json configs[1]: EcgVit-small bf16, 251 tokens, 256 records: value, ms_per_step, roofline.
   fp8_large     (N = 1, default workload) BASELINE.json configs[4] on one GPU: EcgVit-large / 501 tokens with fp8 Linear operands, and the
                 same step with bf16 operands back to back on the same device (value, ms_per_step, fp8_over_bf16, roofline vs 5 PFLOP/s).
-  cpu_baseline  the CPU oracle's train step (torch eager f32, all host cores) on a bounded sample of the same workload.
-  dumped_outputs  (--dump-outputs DIR) the directory and the shape of every array written there.
+  cpu_baseline  (N = 1) the CPU oracle's train step (torch eager f32, all host cores) on a bounded sample of the same workload.
 
 --dump-outputs DIR: after the timed steps of the headline run, rank 0 writes what its LAST timed step returned to the caller, float32,
 one DIR/<name>.npy each (at most 64 MB in all): loss, logits (pred for --objective masked), grad_norm (the pre-clip global norm) and params
@@ -309,12 +311,15 @@ def parse_args(argv=None):
     ap.add_argument('--dropout', type=float, default=None, help='override (default: reference config default 0.1)')
     ap.add_argument('--objective', default='supervised', choices=['supervised', 'masked'],
                     help="'supervised' = the reference's BCE step; 'masked' = the build's SimMIM-style masked pre-train step (seq = n patches, no CLS)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline run, also measure what it does not need: the nested bf16_saved_tensor, masked, small and fp8_large '
+                         'runs and the CPU baseline (default: the headline figure only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--no-probe', action='store_true')
-    ap.add_argument('--no-masked', action='store_true', help='skip the nested masked pre-train measurement')
-    ap.add_argument('--no-bf16-saved', action='store_true', help='skip the nested measurement of the same step with the saved FFN tensor in bf16')
-    ap.add_argument('--no-small', action='store_true', help='skip the nested EcgVit-small measurement (BASELINE.json configs[1])')
-    ap.add_argument('--no-fp8-large', action='store_true', help='skip the nested EcgVit-large fp8 / bf16 measurement (BASELINE.json configs[4] on one GPU)')
+    ap.add_argument('--no-masked', action='store_true', help='--full: skip the nested masked pre-train measurement')
+    ap.add_argument('--no-bf16-saved', action='store_true', help='--full: skip the nested measurement of the same step with the saved FFN tensor in bf16')
+    ap.add_argument('--no-small', action='store_true', help='--full: skip the nested EcgVit-small measurement (BASELINE.json configs[1])')
+    ap.add_argument('--no-fp8-large', action='store_true', help='--full: skip the nested EcgVit-large fp8 / bf16 measurement (BASELINE.json configs[4] on one GPU)')
     ap.add_argument('--defer-nonfinite', action='store_true', help="read the optimiser's non-finite flag one step late (no per-step host sync)")
     ap.add_argument('--single-rank-collectives', action='store_true',
                     help='diagnostic, --gpus 1 only: a 1-rank RCCL group with the N > 1 code path switched on (self-launcher, start broadcast, '
@@ -331,6 +336,23 @@ def parse_args(argv=None):
     if args.steps < 1 or args.warmup < 0:
         ap.error('--steps must be >= 1 and --warmup >= 0')
     return args
+
+
+def extra_measurements(args, world):
+    """which measurements besides the headline run this run takes: none without --full; with it, the nested runs that apply to the
+    workload (the default supervised base workload on one GPU) and the CPU baseline (one GPU), less those switched off by --no-*"""
+    if not args.full:
+        return set()
+    base = args.objective == 'supervised' and world == 1 and args.config == 'base'
+    bf16 = args.dtype == 'bf16'
+    wanted = {
+        'masked': base and not args.no_masked,
+        'bf16_saved_tensor': base and bf16 and not args.no_bf16_saved and not args.bf16_aux,
+        'small': base and bf16 and not args.no_small,
+        'fp8_large': base and bf16 and not args.no_fp8_large,
+        'cpu_baseline': world == 1 and not args.no_cpu_baseline,
+    }
+    return {k for k, v in wanted.items() if v}
 
 
 def free_port():
@@ -505,8 +527,9 @@ def main():
         }
 
     dt, final_loss, pres, rank_ms, dumped = timed_run(args.objective, args.steps, args.warmup, dump=args.dump_outputs)   # the headline run: its own per-rank times
+    extra = extra_measurements(args, world)   # --full only
     masked_line = None
-    if args.objective == 'supervised' and world == 1 and args.config == 'base' and not args.no_masked:
+    if 'masked' in extra:
         # the build's own masked pre-train objective (absent from the reference: SURVEY 0), driver-timed next to the headline step
         msteps = min(args.steps, 20)
         mdt, mloss, mres, _, _ = timed_run('masked', msteps, min(args.warmup, 3))
@@ -521,7 +544,7 @@ def main():
             'roofline': roofline_of(mres, 'masked'),
         }
     bf16_saved_line = None
-    if args.objective == 'supervised' and world == 1 and args.config == 'base' and args.dtype == 'bf16' and not args.no_bf16_saved and not args.bf16_aux:
+    if 'bf16_saved_tensor' in extra:
         # the headline step keeps ONE backward-only tensor per layer (gelu'(pre) x dropout multiplier, [tokens, 3072]) as e4m3 bytes; this is the same
         # step with that tensor in bf16 -- every stored tensor then has the metric's dtype -- timed by the same caller, same steps
         bdt, bloss, _, _, _ = timed_run('supervised', args.steps, args.warmup, saved_e4m3=False)
@@ -533,7 +556,7 @@ def main():
         }
 
     small_line = None
-    if args.objective == 'supervised' and world == 1 and args.config == 'base' and args.dtype == 'bf16' and not args.no_small:
+    if 'small' in extra:
         # BASELINE.json configs[1]: EcgVit-small, 250 patches (251 tokens), 256 records, driver-timed next to the headline step
         sconf, sbatch = make_config(E, 'small', args.patch, args.length, args.dropout)
         ssteps = min(args.steps, 20)
@@ -549,7 +572,7 @@ def main():
         }
 
     fp8_line = None
-    if args.objective == 'supervised' and world == 1 and args.config == 'base' and args.dtype == 'bf16' and not args.no_fp8_large:
+    if 'fp8_large' in extra:
         # BASELINE.json configs[4] on one GPU, driver-timed next to the headline step: EcgVit-large, patch 10 (501 tokens), 256 records,
         # fp8 (e4m3 / e5m2) Linear operands -- and the same step with bf16 operands, back to back on this device, for the ratio
         import gc
@@ -626,7 +649,7 @@ def main():
             out['fp8_large'] = fp8_line
         if dumped:
             out['dumped_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
-        if not args.no_cpu_baseline and world == 1:
+        if 'cpu_baseline' in extra:
             out['cpu_baseline'] = cpu_baseline(conf, masked=args.objective == 'masked')
         print(json.dumps(out), flush=True)
     if world > 1 or args.single_rank_collectives:
