@@ -139,6 +139,93 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const T *__restrict__ dX
     }
 }
 
+// ragged batch (packed rows): record b's tokens are rows tok_off[b] .. tok_off[b] + n_tok[b] - 1 of X and its patch tokens rows
+// tok_off[b] - b .. tok_off[b] - b + n_tok[b] - 2 of tok (tok_off[b] = off_b / P + b); N = the widest record's token count.  Embedding
+// dropout draws its bits by packed element index.  Forward: one grid row per record, its tokens strided over the blocks.
+template <typename T>
+__global__ __launch_bounds__(256) void embed_finish_ragged_kernel(const T *__restrict__ tok, const float *__restrict__ cls,
+                                                                  const float *__restrict__ pos, T *__restrict__ X, const int32_t *__restrict__ n_tok,
+                                                                  const int32_t *__restrict__ tok_off, int N, int d, uint64_t seed, uint32_t thresh,
+                                                                  float inv_keep) {
+    constexpr int VN = Vec16<T>::N;
+    const int b = blockIdx.y, dv = d / VN;
+    const int nb = min(n_tok[b], N);
+    const int64_t r0 = tok_off[b], total = (int64_t)nb * dv;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int t = (int)(i / dv), c0 = (int)(i - (int64_t)t * dv) * VN;
+        const int64_t row = r0 + t;
+        Vec16<T> o;
+        if (t == 0) {
+#pragma unroll
+            for (int k = 0; k < VN; ++k) o.set(k, cls[c0 + k] + pos[c0 + k]);
+        } else {
+            const Vec16<T> v = ld16(tok + (r0 - b - 1 + t) * (int64_t)d + c0);
+#pragma unroll
+            for (int k = 0; k < VN; ++k) o.set(k, v.get(k) + pos[(int64_t)t * d + c0 + k]);
+        }
+        if (thresh) {
+            float mk[VN];
+            dropout_maskN<VN, sizeof(T) == 2>(seed, (uint32_t)row * (uint32_t)d + (uint32_t)c0, thresh, inv_keep, mk);
+#pragma unroll
+            for (int k = 0; k < VN; ++k) o.set(k, o.get(k) * mk[k]);
+        }
+        st16(X + row * d + c0, o);
+    }
+}
+
+// its backward, laid out as embed_bwd_kernel: one block per (token t < N, group of 8 column chunks), 32 batch lanes walking their residue
+// classes over the records that hold token t, then the fixed-order LDS tree: dpos[t] = sum over those records, gathered per position in a
+// fixed order (no atomics, bit-reproducible); dcls = dpos[0]; dtok of every patch token.
+template <typename T>
+__global__ __launch_bounds__(256) void embed_bwd_ragged_kernel(const T *__restrict__ dX, T *__restrict__ dtok, float *__restrict__ dcls,
+                                                               float *__restrict__ dpos, const int32_t *__restrict__ n_tok,
+                                                               const int32_t *__restrict__ tok_off, int B, int d, uint64_t seed, uint32_t thresh,
+                                                               float inv_keep) {
+    constexpr int VN = Vec16<T>::N;
+    __shared__ float red[32][8 * VN + 1];
+    const int dv = d / VN, groups = (dv + 7) / 8;
+    const int t = blockIdx.x / groups, cg = blockIdx.x - t * groups;
+    const int cc = threadIdx.x & 7, bl = threadIdx.x >> 3;
+    const int chunk = cg * 8 + cc;
+    const bool live = chunk < dv;
+    const int c0 = chunk * VN;
+    float acc[VN];
+#pragma unroll
+    for (int k = 0; k < VN; ++k) acc[k] = 0.f;
+    if (live) {
+        for (int b = bl; b < B; b += 32) {
+            if (t >= n_tok[b]) continue;
+            const int64_t r0 = tok_off[b], row = r0 + t;
+            Vec16<T> v = ld16(dX + row * d + c0);
+            if (thresh) {
+                float mk[VN];
+                dropout_maskN<VN, sizeof(T) == 2>(seed, (uint32_t)row * (uint32_t)d + (uint32_t)c0, thresh, inv_keep, mk);
+#pragma unroll
+                for (int k = 0; k < VN; ++k) v.set(k, v.get(k) * mk[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < VN; ++k) acc[k] += v.get(k);
+            if (t > 0) st16(dtok + (r0 - b - 1 + t) * d + c0, v);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < VN; ++k) red[bl][cc * VN + k] = acc[k];
+    __syncthreads();
+    if (threadIdx.x < 8 * VN) {
+        const int col = cg * 8 * VN + threadIdx.x;
+        if (col < d) {
+            float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int r = 0; r < 32; r += 4) {
+                s[0] += red[r][threadIdx.x]; s[1] += red[r + 1][threadIdx.x]; s[2] += red[r + 2][threadIdx.x]; s[3] += red[r + 3][threadIdx.x];
+            }
+            const float tot = (s[0] + s[1]) + (s[2] + s[3]);
+            dpos[(int64_t)t * d + col] = tot;
+            if (t == 0) dcls[col] = tot;
+        }
+    }
+}
+
 // =====================================================================================================
 // LayerNorm: one row per wave, row cached in registers (d <= 64 * VN * MAXV)
 // =====================================================================================================
@@ -706,6 +793,44 @@ int ecgvit_embed_bwd(const void *dX, void *dtok, float *dcls, float *dpos, int B
         hipLaunchKernelGGL(embed_bwd_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), (const float *)dX, (float *)dtok, dcls, dpos, B, n, d, seed, th, ik);
     else if (dtype == ECGVIT_BF16)
         hipLaunchKernelGGL(embed_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), (const bf16_t *)dX, (bf16_t *)dtok, dcls, dpos, B, n, d, seed, th, ik);
+    else return ECGVIT_EINVAL;
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
+}
+
+int ecgvit_embed_finish_ragged(const void *tok, const float *cls, const float *pos, void *X, const int32_t *n_tok, const int32_t *tok_off, int B,
+                               int N, int d, float dropout_p, uint64_t seed, int dtype, void *stream) {
+    if (B <= 0 || B > 65535 || N <= 0 || d <= 0 || d % 8 != 0 || !n_tok || !tok_off) return ECGVIT_EINVAL;
+    uint32_t th;
+    float ik;
+    if (!dropout_site_params(dropout_p, dtype == ECGVIT_BF16, th, ik)) return ECGVIT_EINVAL;
+    const int64_t per = (int64_t)N * d / (dtype == ECGVIT_F32 ? 4 : 8);
+    const dim3 grid((unsigned)std::min<int64_t>((per + 255) / 256, 1024), (unsigned)B);
+    if (dtype == ECGVIT_F32)
+        hipLaunchKernelGGL(embed_finish_ragged_kernel<float>, grid, dim3(256), 0, as_stream(stream), (const float *)tok, cls, pos, (float *)X, n_tok,
+                           tok_off, N, d, seed, th, ik);
+    else if (dtype == ECGVIT_BF16)
+        hipLaunchKernelGGL(embed_finish_ragged_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), (const bf16_t *)tok, cls, pos, (bf16_t *)X, n_tok,
+                           tok_off, N, d, seed, th, ik);
+    else return ECGVIT_EINVAL;
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
+}
+
+int ecgvit_embed_bwd_ragged(const void *dX, void *dtok, float *dcls, float *dpos, const int32_t *n_tok, const int32_t *tok_off, int B, int N, int d,
+                            float dropout_p, uint64_t seed, int dtype, void *stream) {
+    if (B <= 0 || N <= 0 || d <= 0 || d % 8 != 0 || !n_tok || !tok_off) return ECGVIT_EINVAL;
+    uint32_t th;
+    float ik;
+    if (!dropout_site_params(dropout_p, dtype == ECGVIT_BF16, th, ik)) return ECGVIT_EINVAL;
+    const int dv = d / (dtype == ECGVIT_F32 ? 4 : 8);
+    const int grid = N * ((dv + 7) / 8);   // one block per (token, group of 8 column chunks)
+    if (dtype == ECGVIT_F32)
+        hipLaunchKernelGGL(embed_bwd_ragged_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), (const float *)dX, (float *)dtok, dcls, dpos,
+                           n_tok, tok_off, B, d, seed, th, ik);
+    else if (dtype == ECGVIT_BF16)
+        hipLaunchKernelGGL(embed_bwd_ragged_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), (const bf16_t *)dX, (bf16_t *)dtok, dcls, dpos,
+                           n_tok, tok_off, B, d, seed, th, ik);
     else return ECGVIT_EINVAL;
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;

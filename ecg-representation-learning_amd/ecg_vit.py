@@ -311,11 +311,19 @@ class EcgVit(nn.Module):
         """sample_values (B, C, L'): L' <= max_signal_length, a multiple of patch_size (position rows 0..L'/P, as vit-pytorch slices them).
         lengths: optional (B,) integer tensor (host or device) of per-record sample counts inside sample_values, each a positive multiple of
         patch_size and at most L': record b's logits, loss terms and gradient contribution are those of sample_values[b:b+1, :, :lengths[b]]
-        alone (dropout 0; up to summation order); samples past lengths[b] are never read.  Not with fp8_linear or a fused input transform."""
+        alone (dropout 0; up to summation order); samples past lengths[b] are never read.  Not with fp8_linear or a fused input transform.
+        Ragged batch: sample_values (C, S) = torch.cat(records, dim=1) with lengths (B,) required (sum(lengths) == S, each a positive multiple
+        of patch_size, at most max_signal_length); record b is sample_values[:, off_b : off_b + lengths[b]] (off_b = the exclusive prefix sum)
+        and gives what it gives alone at (1, C, lengths[b]) -- no padded rows are computed.  bf16 engine only (not with fp8_linear or a fused
+        input transform); hidden-dropout masks differ from those of the padded batch of the same records."""
         if not sample_values.is_cuda:
             raise RuntimeError('EcgVit (HIP) runs on an MI355X device only: move the model and inputs to "cuda" '
                                '(there is deliberately no CPU fallback)')
+        if sample_values.dim() not in (2, 3):
+            raise ValueError(f'sample_values must be (B, C, L) or a ragged (C, S) batch, got {tuple(sample_values.shape)}')
         x = sample_values.contiguous().float()
+        if x.dim() == 2:   # validated once, before anything launches; the engine takes the RaggedBatch
+            lengths = self._engine().check_ragged_input(x, lengths, labels)
         y = w = None
         if labels is not None:
             y = labels.contiguous().float()
@@ -559,6 +567,8 @@ class MaskedEcgVit(nn.Module):
     def forward(self, sample_values, mask_idx):
         if not sample_values.is_cuda:
             raise RuntimeError('MaskedEcgVit (HIP) runs on an MI355X device only (no CPU fallback)')
+        if sample_values.dim() != 3:
+            raise ValueError('MaskedEcgVit takes (B, C, L) batches of full-width records: ragged (C, S) batches are not supported')
         x = sample_values.contiguous().float()
         self.check_mask_indices(mask_idx, x.shape[0])
         idx = mask_idx.to(device=x.device, dtype=torch.int32).contiguous()

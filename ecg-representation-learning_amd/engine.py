@@ -158,6 +158,74 @@ def check_lengths(lengths, B, P, width):
     return (t // P + 1).to(torch.int32).contiguous()
 
 
+class RaggedBatch:
+    """Token geometry of a ragged batch: B records concatenated along time, (C, S) with S = sum(lengths) (`check_ragged`).
+      n_tok   -- int32 [B]: tokens of record b, lengths[b] / P + 1 (its CLS row included)
+      tok_off -- int32 [B]: first packed token row of record b, off_b / P + b (off_b = exclusive prefix sum of lengths): its CLS row
+      M       -- packed token rows, S / P + B;  N -- the widest record's tokens;  S -- samples
+      lengths -- the validated sample counts, int64 on the host: slicing by record range (`records`) reads nothing from the device"""
+
+    def __init__(self, lengths, P, device):
+        t = lengths
+        n_tok = t // P + 1
+        tok_off = torch.cumsum(n_tok, 0) - n_tok   # = off_b / P + b
+        pack = torch.stack([n_tok, tok_off]).to(torch.int32)
+        if device.type == 'cuda':
+            pack = pack.pin_memory().to(device, non_blocking=True)
+        self.lengths, self.P, self.device = t, P, device
+        self.n_tok, self.tok_off = pack[0], pack[1]
+        self.S = int(t.sum())
+        self.M, self.N = self.S // P + t.shape[0], int(t.max()) // P + 1
+
+    @property
+    def B(self):
+        return self.lengths.shape[0]
+
+    def records(self, b0, b1):
+        """records b0 .. b1 - 1: (s0, s1) = their sample range in the (C, S) batch, and their RaggedBatch"""
+        s0, s1 = int(self.lengths[:b0].sum()), int(self.lengths[:b1].sum())
+        return (s0, s1), RaggedBatch(self.lengths[b0:b1], self.P, self.device)
+
+
+def check_ragged(lengths, S, P, max_len, device=None):
+    """Per-record sample counts of a ragged (C, S) batch -> RaggedBatch with n_tok / tok_off as int32 tensors on `device` (default: the
+    lengths' own device).  lengths is required, a (B,) integer tensor whose entries are positive multiples of P, at most `max_len`, and sum to
+    S; anything else raises ValueError.  The values are read on the host once (a blocking read for a device tensor, as `check_lengths`)."""
+    if lengths is None:
+        raise ValueError('a ragged (C, S) batch needs lengths: the (B,) per-record sample counts')
+    if not isinstance(lengths, torch.Tensor):
+        raise ValueError(f'lengths must be a (B,) integer tensor, got {type(lengths).__name__}')
+    if lengths.dim() != 1 or lengths.shape[0] < 1:
+        raise ValueError(f'lengths must have shape (B,) with B >= 1, got {tuple(lengths.shape)}')
+    if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
+        raise ValueError(f'lengths must be an integer tensor, got {lengths.dtype}')
+    t = lengths.detach().to('cpu', torch.int64)
+    lo, hi, tot = int(t.min()), int(t.max()), int(t.sum())
+    if lo <= 0:
+        raise ValueError(f'lengths must be positive (got {lo})')
+    if hi > max_len:
+        raise ValueError(f'lengths must not exceed max_signal_length={max_len} (got {hi})')
+    if bool((t % P != 0).any()):
+        raise ValueError(f'lengths must be multiples of patch_size={P}')
+    if tot != S:
+        raise ValueError(f'lengths must sum to the ragged batch width S={S} (got {tot})')
+    return RaggedBatch(t, P, lengths.device if device is None else torch.device(device))
+
+
+def ragged_slice(x, lengths, b0, b1):
+    """records b0 .. b1 - 1 of a ragged (C, S) batch as a ragged batch of their own: (x[:, off_b0 : off_b1] contiguous, their lengths).
+    How micro-batches and the evaluator cut a ragged batch by record range.  lengths: a validated RaggedBatch (nothing is read from the
+    device; the slice is a RaggedBatch) or a (B,) tensor (one host read; the slice is lengths[b0:b1])."""
+    if isinstance(lengths, RaggedBatch):
+        (s0, s1), rg = lengths.records(b0, b1)
+        return x[:, s0:s1].contiguous(), rg
+    if not isinstance(lengths, torch.Tensor):
+        raise ValueError('a ragged (C, S) batch needs lengths: the (B,) per-record sample counts')
+    t = lengths.detach().to('cpu', torch.int64)
+    s0, s1 = int(t[:b0].sum()), int(t[:b1].sum())
+    return x[:, s0:s1].contiguous(), lengths[b0:b1]
+
+
 class VitEngine:
     """Forward / backward of EcgVit for one activation dtype (torch.float32 = parity path, torch.bfloat16 =
     throughput path). Caller provides the flat buffers; all activations are allocated here, once per batch size."""
@@ -444,17 +512,20 @@ class VitEngine:
         else:
             self._gemm(GEMM_NN, dY, self.W[name], dX, M, kin, nout, nout, kin, kin, **kw)
 
-    def _alloc(self, B, masked=False, m=0):
-        """Activation slabs for a pass over B records.  Every slab's leading dimension is proportional to B, so ONE pool serves every batch size
+    def _alloc(self, B, masked=False, m=0, rows=None):
+        """Activation slabs for a pass over B records (rows: the packed token rows of a ragged batch; None = B x tokens per record).  Every slab's leading dimension is proportional to B, so ONE pool serves every batch size
         through prefix views: a loop that alternates train (B = 512) and eval (B = 64) batches, or ends an epoch on a short batch, re-slices instead
         of freeing and re-requesting ~40 GB (base) from the allocator on each switch.  The pool grows PER SLAB and never shrinks inside a token
         geometry; it is dropped only when the objective changes (supervised <-> masked, or another mask count)."""
-        key = (B, masked, m, self._aux8(B * (self.n if masked else self.N)), self.N)
+        key = (B, masked, m, self._aux8(rows if rows is not None else B * (self.n if masked else self.N)), self.N, rows)
         if self._alloc_key == key and self.act is not None:
             return
         self._alloc_key = key
         self.T = self.n if masked else self.N   # tokens per record: no CLS row in the masked-pretrain trunk
-        spec = self._act_spec(B, masked, m)
+        spec = self._act_spec(B, masked, m, rows)
+        # a ragged pass reserves what a padded pass of the same B at max_signal_length takes: steps of equal B and any S then re-slice the
+        # same slabs (and never hold more than that padded pass would)
+        reserve = self._act_spec(B, masked, m, N=self.N_max) if rows is not None else {}
         group = (masked, m)
         if self._pool_group != group:
             self.act = self._pool = None           # another token geometry: nothing of the old pool fits
@@ -470,6 +541,9 @@ class VitEngine:
         for k, (sh, dt) in spec.items():
             pdt = torch.uint8 if k.endswith('.hpre') else dt
             need = _numel(sh) * (dt.itemsize if pdt != dt else 1)
+            if k in reserve:
+                rsh, rdt = reserve[k]
+                need = max(need, _numel(rsh) * (rdt.itemsize if pdt != rdt else 1))
             have = pool.get(k)
             if have is None or have.dtype != pdt or have.numel() < need:
                 if self.act is not None:
@@ -490,12 +564,16 @@ class VitEngine:
         a['layers'] = layers
         self.act, self.B = a, B
 
-    def _act_spec(self, B, masked, m):
-        """name -> (shape, dtype) of every activation / scratch slab of a pass over B records (layer slabs as 'L{i}.{name}')"""
+    def _act_spec(self, B, masked, m, rows=None, N=None):
+        """name -> (shape, dtype) of every activation / scratch slab of a pass over B records (layer slabs as 'L{i}.{name}'); rows: the packed
+        token rows of a ragged batch; N: tokens per record (default: the current pass's)"""
         T = self.dtype
         f32, u8 = torch.float32, torch.uint8
-        N = self.n if masked else self.N
-        M, Mp = B * N, B * self.n
+        if N is None:
+            N = self.n if masked else self.N
+        M, Mp = B * N, B * (N if masked else N - 1)
+        if rows is not None:
+            M, Mp = rows, rows - B
         d, f, h = self.d, self.f, self.h
         sp = OrderedDict()
         sp.update(patches=((Mp, self.CP), T), tok=((Mp, d), T), x0=((M, d), T))
@@ -625,7 +703,8 @@ class VitEngine:
         a, W, T = self.act, self.W, hip.code(self.dtype)
         l, st = lib(), stream()
         d, f, h, dh, N = self.d, self.f, self.h, self.dh, self.T
-        M = B * N
+        M = self._pass_rows(B)
+        rg = self.saved.get('ragged')
         pre = 'vit.'
         X = a['x0']
         for i, L in enumerate(a['layers']):
@@ -640,7 +719,10 @@ class VitEngine:
             self._linear(8 * i + 0, L['xn1'], lp + '0.fn.to_qkv.weight', L['qkv'], M, 3 * d, d, a8=L.get('xn1_8'), prequant=q1)
             qa = False   # fp8_linear: the attention kernel wrote the e4m3 copy of its output itself
             ntok = self.saved.get('ntok')
-            if self.dtype == torch.bfloat16 and ntok is not None:
+            if rg is not None:
+                check(l.ecgvit_attention_ragged_fwd(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), ptr(rg.n_tok), ptr(rg.tok_off), B, N, h, dh, self.scale,
+                                                    ph, s0 + 1, st), 'attention_ragged_fwd')
+            elif self.dtype == torch.bfloat16 and ntok is not None:
                 check(l.ecgvit_attention_varlen_fwd(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), ptr(ntok), B, N, h, dh, self.scale, ph, s0 + 1, st),
                       'attention_varlen_fwd')
             elif self.dtype == torch.bfloat16:
@@ -711,6 +793,8 @@ class VitEngine:
         x may be narrower than max_signal_length (a multiple of P): the pass then runs at L'/P + 1 tokens with position rows 0..L'/P.
         lengths: (B,) integer tensor (host or device) of per-record sample counts inside x (`check_lengths`); record b then gives what it
         would give alone at x[b:b+1, :, :lengths[b]] (dropout 0; up to summation order).  Not with fp8_linear or a fused input transform."""
+        if x.dim() == 2:
+            return self._forward_ragged(x, labels, weight, training, seed, want_mean, lengths)
         B = x.shape[0]
         assert x.shape[1] == self.C and x.dtype == torch.float32 and x.is_contiguous()
         if self.input_transform is None:
@@ -740,7 +824,7 @@ class VitEngine:
         ph = self.p_hidden if training else 0.0
         pe = self.p_emb if training else 0.0
         self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, labels=labels, weight=weight, masked=False, training=training, cls_only_last=cls_only_last,
-                          ntok=ntok, lengths=lengths is not None)
+                          ntok=ntok, lengths=lengths is not None, ragged=None)
         if self.fp8:
             # EVERY forward, eval included, starts from the scales of the pass before it (delayed scaling with a history of one pass): an
             # inference-only model otherwise keeps its first batch's scales forever and clamps larger activations silently.  No backward can be
@@ -764,6 +848,71 @@ class VitEngine:
         check(l.ecgvit_bce_fwd(ptr(a['logits']), ptr(labels), ptr(weight), ptr(a['loss_elem']),
                                ptr(a['loss_mean']) if want_mean else None, B * self.K, st), 'bce_fwd')
         return a['logits'], a['loss_elem'], (a['loss_mean'] if want_mean else None)
+
+    def check_ragged_input(self, x, lengths, labels=None):
+        """validate a ragged (C, S) batch for this engine before anything launches -> RaggedBatch (`check_ragged`).  lengths may already be
+        the RaggedBatch of x (validated once by the caller: no second read of the lengths); labels, when given, must hold one row per record"""
+        if self.input_transform is not None:
+            raise ValueError('ragged batches are not supported with a fused input transform (its TimeEndPad pads every record)')
+        if self.fp8:
+            raise ValueError('ragged batches are not supported with fp8_linear')
+        if self.dtype != torch.bfloat16:
+            raise ValueError('ragged batches need the bf16 engine (the f32 parity path materialises padded (B, h, N, N) scores)')
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != self.C:
+            raise ValueError(f'a ragged batch is a ({self.C}, S) tensor, got {tuple(getattr(x, "shape", ()))}')
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError('a ragged batch must be a contiguous float32 tensor')
+        if isinstance(lengths, RaggedBatch):
+            if lengths.S != x.shape[1] or lengths.P != self.P or lengths.device != x.device:
+                raise ValueError(f'the RaggedBatch describes S={lengths.S} samples at patch_size={lengths.P} on {lengths.device}, '
+                                 f'the batch is ({x.shape[0]}, {x.shape[1]}) on {x.device} at patch_size={self.P}')
+            rg = lengths
+        else:
+            rg = check_ragged(lengths, x.shape[1], self.P, self.L_max, device=x.device)
+        if labels is not None and labels.shape[0] != rg.B:
+            raise ValueError(f'labels must hold one row per record: {rg.B} records, got {labels.shape[0]} label rows')
+        return rg
+
+    def _forward_ragged(self, x, labels, weight, training, seed, want_mean, lengths):
+        """`forward` of a ragged batch: x (C, S) = the records concatenated along time, lengths (B,) their sample counts.  Every row-wise
+        kernel runs over the M = S / P + B packed token rows; attention per record on the packed rows; the classifier reads the CLS rows
+        tok_off[b].  The last block always runs in full (no cls_only_last).  Hidden and embedding dropout draw their bits by packed element
+        index, so a ragged step does not draw the masks of the padded step of the same records (attention dropout does, on the valid region)."""
+        rg = self.check_ragged_input(x, lengths, labels)
+        B, M = rg.B, rg.M
+        self._set_width((rg.N - 1) * self.P)
+        self._alloc(B, rows=M)
+        a, T = self.act, hip.code(self.dtype)
+        l, st = lib(), stream()
+        d, N = self.d, self.N
+        ph = self.p_hidden if training else 0.0
+        pe = self.p_emb if training else 0.0
+        self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, labels=labels, weight=weight, masked=False, training=training, cls_only_last=False,
+                          ntok=None, lengths=True, ragged=rg)
+        pre = 'vit.'
+        # a4: the packed patch gather is the uniform one over the concatenation: patch row off_b / P + j is patch j of record b
+        check(lib().ecgvit_patch_gather(ptr(x), ptr(a['patches']), 1, self.C, rg.S, self.P, self.CP, T, st), 'patch_gather')
+        self._gemm(GEMM_NT, a['patches'], self.W[pre + 'to_patch_embedding.1.weight'], a['tok'], M - B, d, self.CP, self.CP, self.CP, d,
+                   epilogue=EPI_BIAS, bias=self.P32[pre + 'to_patch_embedding.1.bias'])
+        check(l.ecgvit_embed_finish_ragged(ptr(a['tok']), ptr(self.P32[pre + 'cls_token']), ptr(self.P32[pre + 'pos_embedding']), ptr(a['x0']),
+                                           ptr(rg.n_tok), ptr(rg.tok_off), B, N, d, pe, seed + 1, T, st), 'embed_finish_ragged')
+        X = self._trunk_fwd(B, ph, seed)
+        self.saved['xL'] = X
+        # a10: the CLS rows tok_off[b], gathered compact, -> LayerNorm -> Linear(d, K)
+        check(l.ecgvit_gather_rows(ptr(X), ptr(rg.tok_off), ptr(a['cls_x2']), 1, M, B, d, d, d, T, st), 'gather_rows')
+        check(l.ecgvit_head_fwd(ptr(a['cls_x2']), 1, ptr(self.P32[pre + 'mlp_head.0.weight']), ptr(self.P32[pre + 'mlp_head.0.bias']),
+                                ptr(self.P32[pre + 'mlp_head.1.weight']), ptr(self.P32[pre + 'mlp_head.1.bias']),
+                                ptr(a['logits']), ptr(a['xhat']), ptr(a['hrstd']), B, d, self.K, LN_EPS, T, st), 'head_fwd')
+        if labels is None:
+            return a['logits'], None, None
+        check(l.ecgvit_bce_fwd(ptr(a['logits']), ptr(labels), ptr(weight), ptr(a['loss_elem']),
+                               ptr(a['loss_mean']) if want_mean else None, B * self.K, st), 'bce_fwd')
+        return a['logits'], a['loss_elem'], (a['loss_mean'] if want_mean else None)
+
+    def _pass_rows(self, B):
+        """token rows of the current pass: B x tokens per record, or the packed rows of a ragged batch"""
+        rg = self.saved.get('ragged') if self.saved is not None else None
+        return rg.M if rg is not None else B * self.T
 
     # ---------------------------------------------------------------- masked pre-train objective (SURVEY 8 a15)
     def forward_masked(self, x, idx, training=True, seed=0):
@@ -937,7 +1086,9 @@ class VitEngine:
         sv = self.saved
         B, ph, pe, seed = sv['B'], sv['ph'], sv['pe'], sv['seed']
         d, f, h, dh, N, n = self.d, self.f, self.h, self.dh, self.N, self.n
-        M, Mp = B * N, B * n
+        rg = sv.get('ragged')
+        M = self._pass_rows(B)
+        Mp = M - B
         pre = 'vit.'
         G = self.G32
         if sv['labels'] is not None and (gscalar is not None or gelem is not None):
@@ -958,16 +1109,23 @@ class VitEngine:
         check(l.ecgvit_head_bwd(ptr(dlog), ptr(a['xhat']), ptr(a['hrstd']), ptr(self.P32[pre + 'mlp_head.0.weight']),
                                 ptr(self.P32[pre + 'mlp_head.0.bias']), ptr(self.P32[pre + 'mlp_head.1.weight']),
                                 ptr(G[pre + 'mlp_head.1.weight']), ptr(G[pre + 'mlp_head.1.bias']),
-                                ptr(G[pre + 'mlp_head.0.weight']), ptr(G[pre + 'mlp_head.0.bias']), ptr(dX), 1 if cls else N, B, d, self.K,
-                                T, st), 'head_bwd')
+                                ptr(G[pre + 'mlp_head.0.weight']), ptr(G[pre + 'mlp_head.0.bias']),
+                                ptr(a['cls_dx'] if rg is not None else dX), 1 if (cls or rg is not None) else N, B, d, self.K, T, st), 'head_bwd')
+        if rg is not None:   # the CLS rows' gradient, compact -> rows tok_off[b]; every other row 0
+            dX[:M].zero_()
+            check(l.ecgvit_scatter_rows(ptr(a['cls_dx']), ptr(rg.tok_off), ptr(dX), 1, M, B, d, d, d, T, st), 'scatter_rows')
         self._ready('head')
         dX = self._trunk_bwd(dX, a['dxb'], cls_only_last=cls)
         self._zero_pretrain_grads()
         if dX is None or not self._reach(self._stage(-1, 0)):
             return
         # ---- embedding backward
-        check(l.ecgvit_embed_bwd(ptr(dX), ptr(a['dtok']), ptr(G[pre + 'cls_token']), ptr(G[pre + 'pos_embedding']), B, n, d, pe,
-                                 seed + 1, T, st), 'embed_bwd')
+        if rg is not None:
+            check(l.ecgvit_embed_bwd_ragged(ptr(dX), ptr(a['dtok']), ptr(G[pre + 'cls_token']), ptr(G[pre + 'pos_embedding']), ptr(rg.n_tok),
+                                            ptr(rg.tok_off), B, N, d, pe, seed + 1, T, st), 'embed_bwd_ragged')
+        else:
+            check(l.ecgvit_embed_bwd(ptr(dX), ptr(a['dtok']), ptr(G[pre + 'cls_token']), ptr(G[pre + 'pos_embedding']), B, n, d, pe,
+                                     seed + 1, T, st), 'embed_bwd')
         if N < self.N_max:   # a narrower pass: embed_bwd wrote position rows < N only, the rest take no part
             G[pre + 'pos_embedding'].view(-1, d)[N:].zero_()
         self._colsum(a['dtok'], d, G[pre + 'to_patch_embedding.1.bias'], Mp, d)
@@ -996,7 +1154,8 @@ class VitEngine:
         sv = self.saved
         B, ph, seed = sv['B'], sv['ph'], sv['seed']
         d, f, h, dh, N = self.d, self.f, self.h, self.dh, self.T
-        M = B * N
+        M = self._pass_rows(B)
+        rg = sv.get('ragged')
         pre = 'vit.'
         G = self.G32
         # dY = gradient entering the current `dropout(Linear + bias) + residual` site (masked copy of dX when dropout is on);
@@ -1060,7 +1219,10 @@ class VitEngine:
             if not self._reach(b + 4):
                 return None
             ntok = sv.get('ntok')
-            if self.dtype == torch.bfloat16 and ntok is not None:
+            if rg is not None:
+                check(l.ecgvit_attention_ragged_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), ptr(rg.n_tok),
+                                                    ptr(rg.tok_off), B, N, h, dh, self.scale, ph, s0 + 1, st), 'attention_ragged_bwd')
+            elif self.dtype == torch.bfloat16 and ntok is not None:
                 check(l.ecgvit_attention_varlen_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), ptr(ntok), B, N, h,
                                                     dh, self.scale, ph, s0 + 1, st), 'attention_varlen_bwd')
             elif self.dtype == torch.bfloat16:
@@ -1210,6 +1372,8 @@ class VitEngine:
     def attention_probs(self, layer):
         """Post-softmax attention of `layer` for the last forward, (B, h, N, N) f32 -- what vit_pytorch's Recorder hooks
         (reference ecg_vit.py:176-194). The f32 path keeps them; the fused bf16 path rebuilds them from its saved qkv + log-sum-exp."""
+        if self.saved.get('ragged') is not None:
+            raise RuntimeError('the last forward ran on a ragged batch: its attention probabilities are not available')
         if self.saved.get('lengths'):
             raise RuntimeError('the last forward ran with per-record lengths: its attention probabilities are not available')
         B, L = self.saved['B'], self.act['layers'][layer]

@@ -28,7 +28,7 @@ import torch.distributed as dist
 from .check_args import ca
 from . import hip
 from . import ddp
-from .engine import check_lengths
+from .engine import check_lengths, ragged_slice
 
 
 def get_train_args(args=None, n_train=None):
@@ -235,6 +235,8 @@ class HipTrainStep:
         """the same fused step for the masked pre-train objective; `self.model` must be a MaskedEcgVit.
         micro_batch_size: as `step` (None: the default given in args); the loss is the whole batch's mean"""
         mb = self._micro_batch_size(micro_batch_size)
+        if sample_values.dim() != 3:
+            raise ValueError('step_masked takes (B, C, L) batches of full-width records: ragged (C, S) batches are not supported')
         wrapper, model = self.model, self.model.encoder
         if not model.training:
             raise RuntimeError('train step on a model in eval mode')
@@ -328,7 +330,9 @@ class HipTrainStep:
         """one fused training step; lengths: optional (B,) per-record sample counts (EcgVit.forward).
         micro_batch_size: None (the default given in args) or a positive int m; m < B accumulates the gradient of ceil(B/m) passes into one
         optimiser step (see the class docstring; with dropout each pass draws its own masks).  Returns (loss_mean, logits (B, K)) of the
-        whole batch either way."""
+        whole batch either way.
+        sample_values may be a ragged (C, S) batch with its (B,) lengths (EcgVit.forward); micro-batches are then record ranges, each a
+        ragged batch of its own.  The last block then runs in full (no CLS-only pruning)."""
         mb = self._micro_batch_size(micro_batch_size)
         model = self.model
         if not model.training:
@@ -341,7 +345,11 @@ class HipTrainStep:
         # the classifier reads the CLS rows only: the last block skips the other rows past its K / V (bf16 engine; the fp8 step keeps the
         # full block -- its 512-row products would fall below the 8-bit kernels' gates and change the delayed-scaling sites)
         cls_only = eng.dtype == torch.bfloat16 and not eng.fp8
-        if mb is not None and mb < sample_values.shape[0]:
+        ragged = sample_values.dim() == 2
+        if ragged:   # (C, S): validated once, before anything launches (the RaggedBatch travels on); B = the number of records
+            sample_values = sample_values.contiguous().float()
+            lengths = eng.check_ragged_input(sample_values, lengths, labels)
+        if mb is not None and mb < (labels.shape[0] if ragged else sample_values.shape[0]):
             return self._step_micro(model, eng, sample_values, labels, lengths, mb, cls_only)
         seed = self._dropout_seed(model)
         x = sample_values.contiguous().float()
@@ -351,7 +359,7 @@ class HipTrainStep:
             w = torch.tensor(model.loss_weight, device=y.device, dtype=torch.float32)[y.long()].contiguous()
         logits, _, loss_mean = eng.forward(x, y, w, training=True, seed=seed, want_mean=True, cls_only_last=cls_only, lengths=lengths)
         model._fwd_id += 1
-        B, K = x.shape[0], eng.K
+        B, K = y.shape[0], eng.K
         tpw = self._arm_overlap(model)
         try:
             eng.backward(gscalar=self._one(x.device), gscale=1.0 / (B * K), tiles_per_workgroup=tpw, trainable=self._trainable)
@@ -372,11 +380,12 @@ class HipTrainStep:
         bit).  The labels, the loss_weight element weights and the lengths travel with their records."""
         x = sample_values.contiguous().float()
         y = labels.contiguous().float()
-        B, K = x.shape[0], eng.K
+        B, K = y.shape[0], eng.K
+        ragged = x.dim() == 2   # (validated by `step`)
         w = None
         if model.loss_weight:
             w = torch.tensor(model.loss_weight, device=y.device, dtype=torch.float32)[y.long()].contiguous()
-        if lengths is not None and eng.input_transform is None:
+        if lengths is not None and eng.input_transform is None and not ragged:
             check_lengths(lengths, B, eng.P, x.shape[2])   # the whole batch's lengths are valid before the first pass
         logits_all = torch.empty((B, K), device=x.device, dtype=torch.float32)
         one = self._one(x.device)
@@ -384,8 +393,12 @@ class HipTrainStep:
         for j, s in enumerate(starts):
             e = min(s + mb, B)
             seed = self._dropout_seed(model)
-            logits, _, _ = eng.forward(x[s:e], y[s:e], None if w is None else w[s:e], training=True, seed=seed, want_mean=False,
-                                       cls_only_last=cls_only, lengths=None if lengths is None else lengths[s:e])
+            if ragged:   # records s .. e - 1: a ragged batch of their own (host offsets, no device read)
+                xs, ls = ragged_slice(x, lengths, s, e)
+            else:
+                xs, ls = x[s:e], None if lengths is None else lengths[s:e]
+            logits, _, _ = eng.forward(xs, y[s:e], None if w is None else w[s:e], training=True, seed=seed, want_mean=False,
+                                       cls_only_last=cls_only, lengths=ls)
             model._fwd_id += 1
             logits_all[s:e].copy_(logits)
             self._micro_backward(model, eng, j, j == len(starts) - 1,

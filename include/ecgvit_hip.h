@@ -170,6 +170,17 @@ int ecgvit_embed_finish(const void *tok, const float *cls, const float *pos, voi
 /* backward of embed_finish: dtok[b*n+p] = dX[b*N+1+p] ; dpos[t] = sum_b dX[b*N+t] ; dcls = sum_b dX[b*N] (f32 grads, overwritten) */
 int ecgvit_embed_bwd(const void *dX, void *dtok, float *dcls, float *dpos, int B, int n, int d,
                      float dropout_p, uint64_t seed, int dtype, void *stream);
+/* Ragged batch (records packed along the token rows, no padding): record b's tokens are rows tok_off[b] .. tok_off[b] + n_tok[b] - 1 of X
+ * and its patch tokens rows tok_off[b] - b .. tok_off[b] - b + n_tok[b] - 2 of tok (n_tok, tok_off: int32 [B] on the device; tok_off[b] =
+ * off_b / P + b for the sample offset off_b of record b).  N = the widest record's token count (n_tok[b] <= N).  The packed patch gather is
+ * ecgvit_patch_gather with B = 1 over the (C, S) concatenation: patch row off_b / P + j of it is patch j of record b.
+ * X[tok_off[b]] = cls + pos[0];  X[tok_off[b] + t] = tok[tok_off[b] - b - 1 + t] + pos[t];  embedding dropout by packed element index. */
+int ecgvit_embed_finish_ragged(const void *tok, const float *cls, const float *pos, void *X, const int32_t *n_tok, const int32_t *tok_off,
+                               int B, int N, int d, float dropout_p, uint64_t seed, int dtype, void *stream);
+/* its backward: dtok of every patch token; dpos[t] = sum over the records with n_tok[b] > t of dX[tok_off[b] + t] for t < N (a fixed-order
+ * gather per position: bit-reproducible); dcls = dpos[0] (f32 grads, overwritten; rows >= N of dpos are not touched) */
+int ecgvit_embed_bwd_ragged(const void *dX, void *dtok, float *dcls, float *dpos, const int32_t *n_tok, const int32_t *tok_off, int B, int N,
+                            int d, float dropout_p, uint64_t seed, int dtype, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm (eps 1e-5, biased variance, affine).  replaces: vit_pytorch PreNorm.norm / mlp_head[0].
@@ -277,6 +288,18 @@ int ecgvit_attention_varlen_cls_fwd(const void *qkv, void *out_cls, float *lse_c
 int ecgvit_attention_varlen_cls_bwd(const void *qkv, const void *out_cls, const void *dout_cls, const float *lse_cls, void *dqkv,
                                     void *dq_cls, const int32_t *n_tok, int B, int N, int h, int dh, float scale, float dropout_p,
                                     uint64_t seed, void *stream);
+/* Ragged batch (attention_varlen.hip, the same kernel bodies): record b's n_tok[b] tokens are the rows tok_off[b] .. tok_off[b] + n_tok[b] - 1
+ * of qkv / out / dqkv (packed, no padded rows: nothing else is read or written).  N = the widest record's token count: it sets the lse layout
+ * ((b h + head) N + q, rows >= n_tok[b] not written) and the dropout bits, which are those of ecgvit_attention_varlen_* at that N. */
+int ecgvit_attention_ragged_fwd(const void *qkv, void *out, float *lse, const int32_t *n_tok, const int32_t *tok_off, int B, int N, int h,
+                                int dh, float scale, float dropout_p, uint64_t seed, void *stream);
+int ecgvit_attention_ragged_bwd(const void *qkv, const void *out, const void *dout, const float *lse, void *dqkv, const int32_t *n_tok,
+                                const int32_t *tok_off, int B, int N, int h, int dh, float scale, float dropout_p, uint64_t seed, void *stream);
+int ecgvit_attention_ragged_cls_fwd(const void *qkv, void *out_cls, float *lse_cls, const int32_t *n_tok, const int32_t *tok_off, int B,
+                                    int N, int h, int dh, float scale, float dropout_p, uint64_t seed, void *stream);
+int ecgvit_attention_ragged_cls_bwd(const void *qkv, const void *out_cls, const void *dout_cls, const float *lse_cls, void *dqkv,
+                                    void *dq_cls, const int32_t *n_tok, const int32_t *tok_off, int B, int N, int h, int dh, float scale,
+                                    float dropout_p, uint64_t seed, void *stream);
 /* f32 parity path pieces (scores materialised; the GEMMs are ecgvit_gemm batched calls):
  * in-place row softmax of S[rows, ld] over the first N columns; optional export is the buffer itself. */
 int ecgvit_softmax_rows(float *S, int64_t rows, int N, int64_t ld, void *stream);
