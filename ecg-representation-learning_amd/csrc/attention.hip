@@ -1,4 +1,5 @@
-// Fused multi-head self-attention core for the bf16 path (dh = 64, N <= 256 tokens): scores never touch HBM.  (dh = 128: attention_h128.hip.)
+// Fused multi-head self-attention core for the bf16 path (dh = 64, N <= 256 tokens): scores never touch HBM.  (dh = 128 and the
+// CLS-row kernels: attention_varlen.hip.)
 //
 // One workgroup owns one (record, head): its whole K/V (<= 256 x 64 bf16 = 32 KiB each) sits in LDS, so softmax
 // is single-pass (no online rescale) and the backward needs no atomics -- dQ, dK, dV of a head are all produced
@@ -17,7 +18,6 @@
 //   -> ds_read_b128 row reads (MFMA K-contiguous operand) hit 16 distinct slots per 16-lane group, and
 //   -> ds_read_b64_tr_b16 reads of 4 consecutive rows x 64 B land in the 4 different 64-B quarters of the bank row.
 #include "attn_common.h"
-#include "attn_h128.h"
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -1281,133 +1281,6 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const bf16_t *__restric
     }
 }
 
-// ---- CLS-row attention (the pruned last block of the supervised step): query row 0 of each record against its N keys.  The
-// classifier reads x[:, 0] only, so after the last block's K / V nothing else of that block reaches the loss.  One workgroup per (record,
-// head); 256 threads = 32 key slots x 8 lanes, each lane owning 8 of the 64 head dimensions (one 16-B load per key row and operand).  The
-// launch streams K and V once (395 MB at 512 x 12 x 251): a bandwidth kernel, no MFMA.  The dropout bits are the full kernels' for query 0:
-// quad = (bh * N + 0) * ceil(N / 4) + key / 4, byte = key & 3, keep iff byte >= thresh.
-constexpr int CLS_THREADS = 256, CLS_SLOTS = 32;
-__device__ __forceinline__ float group8_sum(float v) {   // sum over the 8 lanes that share a key slot
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    return v;
-}
-template <bool DROP> __device__ __forceinline__ float cls_mult(uint32_t smix, uint32_t quad0, int key, uint32_t thresh, float inv_keep) {
-    if constexpr (!DROP) return 1.f;
-    const uint32_t hsh = quad_hash(smix, quad0 + (uint32_t)(key >> 2));
-    return ((hsh >> (8 * (key & 3))) & 0xFFu) >= thresh ? inv_keep : 0.f;
-}
-// block-wide reduction of one value per thread (max or sum); every thread gets the result.  red: >= 4 floats of LDS, free on entry
-template <bool MAX> __device__ __forceinline__ float cls_block_reduce(float v, float *red) {
-    v = MAX ? wave_max(v) : wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float r = MAX ? fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) : (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return r;
-}
-
-// NMAX: keys the score array holds (512; 2048 is launched for N > 512 only)
-template <bool DROP, int NMAX = 512>
-__global__ __launch_bounds__(CLS_THREADS) void attn_cls_fwd_kernel(const bf16_t *__restrict__ qkv, bf16_t *__restrict__ out, float *__restrict__ lse,
-                                                                   int N, int h, float scale, uint64_t seed, uint32_t thresh, float inv_keep) {
-    __shared__ float sp[NMAX];                   // scores, then dropped probabilities, per key
-    __shared__ float ored[CLS_SLOTS][65];        // per-slot partial outputs (+1: no bank conflicts on the column sums)
-    __shared__ float red[4];
-    const int bh = blockIdx.x, b = bh / h, head = bh % h;
-    const int g = threadIdx.x & 7, slot = threadIdx.x >> 3;
-    const int64_t ld = 3 * (int64_t)h * 64, dm = (int64_t)h * 64;
-    const bf16_t *rec = qkv + (int64_t)b * N * ld + head * 64 + g * 8;
-    const Vec16<bf16_t> q = ld16(rec);
-    float smax = -INFINITY;
-    for (int k = slot; k < N; k += CLS_SLOTS) {
-        const Vec16<bf16_t> kv = ld16(rec + (int64_t)k * ld + dm);
-        float acc = 0.f;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) acc = fmaf(q.get(t), kv.get(t), acc);
-        acc = group8_sum(acc) * scale;
-        if (g == 0) sp[k] = acc;
-        smax = fmaxf(smax, acc);
-    }
-    const float m = cls_block_reduce<true>(smax, red);   // (also orders the sp stores before the reads below)
-    float ssum = 0.f;
-    for (int k = threadIdx.x; k < N; k += CLS_THREADS) ssum += __expf(sp[k] - m);
-    const float l = m + __logf(cls_block_reduce<false>(ssum, red));
-    const uint32_t smix = seed_mix(seed), quad0 = (uint32_t)bh * (uint32_t)N * (uint32_t)((N + 3) >> 2);
-    for (int k = threadIdx.x; k < N; k += CLS_THREADS) sp[k] = __expf(sp[k] - l) * cls_mult<DROP>(smix, quad0, k, thresh, inv_keep);
-    __syncthreads();
-    float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int k = slot; k < N; k += CLS_SLOTS) {
-        const Vec16<bf16_t> vv = ld16(rec + (int64_t)k * ld + 2 * dm);
-        const float p = sp[k];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) o[t] = fmaf(p, vv.get(t), o[t]);
-    }
-#pragma unroll
-    for (int t = 0; t < 8; ++t) ored[slot][g * 8 + t] = o[t];
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        float s = 0.f;
-#pragma unroll 8
-        for (int j = 0; j < CLS_SLOTS; ++j) s += ored[j][threadIdx.x];
-        out[(int64_t)b * dm + head * 64 + threadIdx.x] = (bf16_t)s;
-        if (threadIdx.x == 0) lse[bh] = l;
-    }
-}
-
-// backward of attn_cls_fwd_kernel: D = dO . O ; per key k: P = exp(scale q.k - lse), m = dropout multiplier, dS = P (m dO.v - D);
-// dV_k = P m dO and dK_k = scale dS q (written into the K / V columns of dqkv for every row), dQ = scale sum_k dS k (compact [B, d])
-template <bool DROP>
-__global__ __launch_bounds__(CLS_THREADS) void attn_cls_bwd_kernel(const bf16_t *__restrict__ qkv, const bf16_t *__restrict__ o_cls,
-                                                                   const bf16_t *__restrict__ do_cls, const float *__restrict__ lse,
-                                                                   bf16_t *__restrict__ dqkv, bf16_t *__restrict__ dq_cls, int N, int h, float scale,
-                                                                   uint64_t seed, uint32_t thresh, float inv_keep) {
-    __shared__ float qred[CLS_SLOTS][65];
-    const int bh = blockIdx.x, b = bh / h, head = bh % h;
-    const int g = threadIdx.x & 7, slot = threadIdx.x >> 3;
-    const int64_t ld = 3 * (int64_t)h * 64, dm = (int64_t)h * 64;
-    const int64_t roff = (int64_t)b * N * ld + head * 64 + g * 8;
-    const bf16_t *rec = qkv + roff;
-    bf16_t *drec = dqkv + roff;
-    const Vec16<bf16_t> q = ld16(rec), dO = ld16(do_cls + (int64_t)b * dm + head * 64 + g * 8), O = ld16(o_cls + (int64_t)b * dm + head * 64 + g * 8);
-    float D = 0.f;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) D = fmaf(dO.get(t), O.get(t), D);
-    D = group8_sum(D);
-    const float l = lse[bh];
-    const uint32_t smix = seed_mix(seed), quad0 = (uint32_t)bh * (uint32_t)N * (uint32_t)((N + 3) >> 2);
-    float dq[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int k = slot; k < N; k += CLS_SLOTS) {
-        const Vec16<bf16_t> kv = ld16(rec + (int64_t)k * ld + dm), vv = ld16(rec + (int64_t)k * ld + 2 * dm);
-        float s = 0.f, dp = 0.f;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) { s = fmaf(q.get(t), kv.get(t), s); dp = fmaf(dO.get(t), vv.get(t), dp); }
-        s = group8_sum(s);
-        dp = group8_sum(dp);
-        const float p = __expf(s * scale - l), mlt = cls_mult<DROP>(smix, quad0, k, thresh, inv_keep);
-        const float ds = p * (dp * mlt - D), pm = p * mlt;
-        Vec16<bf16_t> dk, dv;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            dq[t] = fmaf(ds, kv.get(t), dq[t]);
-            dk.set(t, scale * ds * q.get(t));
-            dv.set(t, pm * dO.get(t));
-        }
-        st16(drec + (int64_t)k * ld + dm, dk);
-        st16(drec + (int64_t)k * ld + 2 * dm, dv);
-    }
-#pragma unroll
-    for (int t = 0; t < 8; ++t) qred[slot][g * 8 + t] = dq[t];
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        float s = 0.f;
-#pragma unroll 8
-        for (int j = 0; j < CLS_SLOTS; ++j) s += qred[j][threadIdx.x];
-        dq_cls[(int64_t)b * dm + head * 64 + threadIdx.x] = (bf16_t)(s * scale);
-    }
-}
-
 }  // namespace
 
 #ifdef ECGVIT_TOOLS
@@ -1462,9 +1335,9 @@ static int attention_fwd_launch(const void *qkv, void *out, float *lse, int B, i
     if (dropout_p > 0.f && dropout_threshold8(dropout_p) == 0) return ECGVIT_EINVAL;   // p < 1/512 would silently round to no dropout
     const uint32_t th = dropout_threshold8(dropout_p);
     const float ik = dropout_inv_keep8(dropout_p);
-    if (dh == 128) {   // attention_h128.hip (no 8-bit emission: the caller quantises `out` itself)
+    if (dh == 128) {   // attention_varlen.hip, uniform form (no 8-bit emission: the caller quantises `out` itself)
         if (out8) return ECGVIT_EINVAL;
-        return attn_h128_fwd(qkv, out, lse, B, N, h, scale, seed, th, ik, stream);
+        return attn_fwd_run(qkv, out, lse, nullptr, nullptr, B, N, h, dh, scale, dropout_p, seed, stream);
     }
     // the STREAMED form (one persistent 16-wave workgroup per CU, K / V windows through a two-slot ring) for records of more than 256 tokens once there
     // is an item per CU (256 x 16 x 501: 494 against 533 us, 8-bit emitting 523 against 575; profiles/r06_attn_fwd_stream.txt); below that the one-item
@@ -1574,10 +1447,9 @@ static int attention_bwd_launch(const void *qkv, const void *out, const void *do
                                 int dh, float scale, float dropout_p, uint64_t seed, int dtype, void *stream, void *dqkv8, const float *q8_scale,
                                 float *q8_amax) {
     if (!attention_bwd_args_ok(qkv, out, dout, dqkv, B, N, h, dh, dtype)) return ECGVIT_EINVAL;
-    if (dh == 128) {   // attention_h128.hip (no 8-bit emission: the caller quantises dqkv itself)
+    if (dh == 128) {   // attention_varlen.hip, uniform form (no 8-bit emission: the caller quantises dqkv itself)
         if (dqkv8) return ECGVIT_EINVAL;
-        if (dropout_p > 0.f && dropout_threshold8(dropout_p) == 0) return ECGVIT_EINVAL;
-        return attn_h128_bwd(qkv, out, dout, lse, dqkv, B, N, h, scale, seed, dropout_threshold8(dropout_p), dropout_inv_keep8(dropout_p), stream);
+        return attn_bwd_run(qkv, out, dout, lse, dqkv, nullptr, nullptr, B, N, h, dh, scale, dropout_p, seed, stream);
     }
     if (N <= 128 || (int64_t)N * 3 * h * 64 * 2 >= (1ll << 31)) {   // short sequences / 32-bit buffer offsets exhausted
         if (dqkv8) return ECGVIT_EINVAL;   // the one-item kernel has no 8-bit emission: the caller quantises dqkv itself
@@ -1644,41 +1516,6 @@ int ecgvit_attention_bwd_q8(const void *qkv, const void *out, const void *dout, 
                             int dh, float scale, float dropout_p, uint64_t seed, void *dqkv8, const float *q8_scale, float *q8_amax, void *stream) {
     if (!dqkv8) return ECGVIT_EINVAL;
     return attention_bwd_launch(qkv, out, dout, lse, dqkv, B, N, h, dh, scale, dropout_p, seed, ECGVIT_BF16, stream, dqkv8, q8_scale, q8_amax);
-}
-
-static int attention_cls_args_ok(int B, int N, int h, int dh) { return (dh == 64 || dh == 128) && N >= 1 && N <= ECGVIT_ATTN_MAX_N && B >= 1 && h >= 1 && (int64_t)B * h < (1ll << 31); }
-
-int ecgvit_attention_cls_fwd(const void *qkv, void *out_cls, float *lse_cls, int B, int N, int h, int dh, float scale, float dropout_p, uint64_t seed,
-                             int dtype, void *stream) {
-    if (dtype != ECGVIT_BF16 || !attention_cls_args_ok(B, N, h, dh) || !qkv || !out_cls || !lse_cls ||
-        (reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(out_cls)) % 16) return ECGVIT_EINVAL;
-    if (dropout_p > 0.f && dropout_threshold8(dropout_p) == 0) return ECGVIT_EINVAL;   // p < 1/512 would silently round to no dropout
-    const uint32_t th = dropout_threshold8(dropout_p);
-    const float ik = dropout_inv_keep8(dropout_p);
-    if (dh == 128) return attn_h128_cls_fwd(qkv, out_cls, lse_cls, B, N, h, scale, seed, th, ik, stream);
-#define CLS_FWD(DR, NM) hipLaunchKernelGGL((attn_cls_fwd_kernel<DR, NM>), dim3(B * h), dim3(CLS_THREADS), 0, as_stream(stream), (const bf16_t *)qkv, (bf16_t *)out_cls, lse_cls, N, h, scale, seed, th, ik)
-    if (N <= 512) { if (th) CLS_FWD(true, 512); else CLS_FWD(false, 512); }
-    else { if (th) CLS_FWD(true, 2048); else CLS_FWD(false, 2048); }
-#undef CLS_FWD
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
-}
-
-int ecgvit_attention_cls_bwd(const void *qkv, const void *out_cls, const void *dout_cls, const float *lse_cls, void *dqkv, void *dq_cls, int B, int N,
-                             int h, int dh, float scale, float dropout_p, uint64_t seed, int dtype, void *stream) {
-    if (dtype != ECGVIT_BF16 || !attention_cls_args_ok(B, N, h, dh) || !qkv || !out_cls || !dout_cls || !lse_cls || !dqkv || !dq_cls ||
-        (reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(out_cls) | reinterpret_cast<uintptr_t>(dout_cls) |
-         reinterpret_cast<uintptr_t>(dqkv) | reinterpret_cast<uintptr_t>(dq_cls)) % 16) return ECGVIT_EINVAL;
-    if (dropout_p > 0.f && dropout_threshold8(dropout_p) == 0) return ECGVIT_EINVAL;
-    const uint32_t th = dropout_threshold8(dropout_p);
-    const float ik = dropout_inv_keep8(dropout_p);
-    if (dh == 128) return attn_h128_cls_bwd(qkv, out_cls, dout_cls, lse_cls, dqkv, dq_cls, B, N, h, scale, seed, th, ik, stream);
-#define CLS_BWD(DR) hipLaunchKernelGGL(attn_cls_bwd_kernel<DR>, dim3(B * h), dim3(CLS_THREADS), 0, as_stream(stream), (const bf16_t *)qkv, \
-                                       (const bf16_t *)out_cls, (const bf16_t *)dout_cls, lse_cls, (bf16_t *)dqkv, (bf16_t *)dq_cls, N, h, scale, seed, th, ik)
-    if (th) CLS_BWD(true); else CLS_BWD(false);
-#undef CLS_BWD
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
 }
 
 #ifdef ECGVIT_TOOLS   // declared in tools/ecgvit_hip_tools.h, exported by build/libecgvit_hip_tools.so only

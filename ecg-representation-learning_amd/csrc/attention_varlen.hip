@@ -1,22 +1,29 @@
-// Variable-length records: fused bf16 attention with a per-record token count, the f32 path's masked row softmax, and the patch gather that
-// zeroes the patches past each record's length (ecgvit_attention_varlen_* / ecgvit_softmax_rows_varlen / ecgvit_patch_gather_varlen).
+// The fused bf16 attention that is not the tuned dh = 64 full-row path of attention.hip, from one kernel text (attn_varlen_kernels.h) in three
+// forms: the uniform batch at dh = 128 (ecgvit_attention_fwd / _bwd call attn_fwd_run / attn_bwd_run) and the CLS-row kernels at dh = 64 and
+// 128 (ecgvit_attention_cls_*); variable-length records (ecgvit_attention_varlen_*); ragged batches (ecgvit_attention_ragged_*).  Also the f32
+// path's masked row softmax and the patch gather that zeroes the patches past each record's length (ecgvit_softmax_rows_varlen /
+// ecgvit_patch_gather_varlen).
 //
-// A batch keeps one row stride N (the widest record); record b holds n_tok[b] valid tokens, 1 <= n_tok[b] <= N, read once per workgroup as a
-// scalar.  Key loops end at n_tok[b] (the ragged last window masks keys >= n_tok[b] as the uniform kernels mask keys >= N), query / key blocks
-// that lie entirely past n_tok[b] only zero-fill, and rows >= n_tok[b] of out and of all three parts of dqkv are written as exact zeros: the
-// padded rows then add exactly 0 to every weight gradient, and a record's valid outputs do not depend on what its padded rows of qkv hold.
+// Templated on HI, the number of 64-wide head images (1: dh = 64, 2: dh = 128): every [row][64 HI x bf16] operand sits in LDS as HI standard
+// [row][64] images (attn_common.h swizzle and fragment readers).
+// forward   one 4-wave workgroup per (record, head, 128-query block); each wave owns 32 queries (query on the lane), online softmax over 64-key
+//           windows of K and V staged in LDS (S^T = K Q^T, O^T += V^T P^T, lazy running maximum as in attention.hip).
+// backward  two kernels, deterministic without atomics: dK / dV per 128-key block (key on the lane, loop over 32-query blocks of Q / dO staged
+//           in LDS, the 2 HI dK^T / dV^T accumulators in registers) and dQ per 128-query block (P recomputed from the stored LSE).
+// CLS row   VALU kernels for query row 0 only (the pruned last block of the supervised step).
 //
-// The design is that of attention_h128.hip, templated on HI, the number of 64-wide head images (1: dh = 64, 2: dh = 128): every
-// [row][64 HI x bf16] operand sits in LDS as HI standard [row][64] images (attn_common.h swizzle and fragment readers).
-// Contract shared with the uniform kernels: same qkv / out / lse / dqkv layouts, LSE = m scale + log(sum p) in natural-log units, the same
-// dropout bits indexed with the batch N -- element (bh, q, key): quad = (bh N + q) ceil(N / 4) + key / 4, byte key & 3, keep iff
+// Variable-length records: a batch keeps one row stride N (the widest record); record b holds n_tok[b] valid tokens, 1 <= n_tok[b] <= N, read
+// once per workgroup as a scalar.  Key loops end at n_tok[b] (the ragged last window masks keys >= n_tok[b] as the uniform form masks keys
+// >= N), query / key blocks that lie entirely past n_tok[b] only zero-fill, and rows >= n_tok[b] of out and of all three parts of dqkv are
+// written as exact zeros: the padded rows then add exactly 0 to every weight gradient, and a record's valid outputs do not depend on what its
+// padded rows of qkv hold.  The LSE of a padded row is 0.
+// Ragged batches: record b owns rows [tok_off[b], tok_off[b] + n_tok[b]) -- the records' tokens follow one another with no padded rows, so
+// nothing past n_tok[b] is read or written (no zero-fill).  N is then the widest record's token count: it sets the grid, the LSE layout
+// (bh N + q) and the dropout hashing, which are therefore those of the padded pass on the valid region.
+// Contract shared with attention.hip's kernels: same qkv / out / lse / dqkv layouts, LSE = m scale + log(sum p) in natural-log units, the
+// same dropout bits indexed with the batch N -- element (bh, q, key): quad = (bh N + q) ceil(N / 4) + key / 4, byte key & 3, keep iff
 // byte >= round(256 p), kept values scaled by 256 / (256 - round(256 p)) -- so the mask of the valid region is what the uniform kernel draws.
-// The LSE of a padded row is 0.  No atomics: every output element is written by exactly one lane, so launches are bit-reproducible.
-//
-// Ragged batches (ecgvit_attention_ragged_*): the same kernel text (attn_varlen_kernels.h), instantiated on where a record's rows start (PK).  Padded: record b
-// owns rows [b N, b N + N) of qkv / out / dqkv.  Packed: it owns rows [tok_off[b], tok_off[b] + n_tok[b]) -- the records' tokens follow
-// one another with no padded rows, so nothing past n_tok[b] is read or written (no zero-fill).  N is then the widest record's token count:
-// it sets the grid, the LSE layout (bh N + q) and the dropout hashing, which are therefore those of the padded pass on the valid region.
+// No atomics: every output element is written by exactly one lane, so launches are bit-reproducible.
 #include "attn_common.h"
 
 namespace {
@@ -107,12 +114,15 @@ template <bool MAX> __device__ __forceinline__ float avc_block_reduce(float v, f
 }
 
 
-#define AV_PACKED 0
+#define AV_FORM 0
 #include "attn_varlen_kernels.h"
-#undef AV_PACKED
-#define AV_PACKED 1
+#undef AV_FORM
+#define AV_FORM 1
 #include "attn_varlen_kernels.h"
-#undef AV_PACKED
+#undef AV_FORM
+#define AV_FORM 2
+#include "attn_varlen_kernels.h"
+#undef AV_FORM
 
 // =====================================================================================================
 // f32 parity path: in-place row softmax of the scores S[(b h + head) N + q][ld] over the first n_tok[b] columns; columns >= n_tok[b] and
@@ -167,148 +177,164 @@ __global__ __launch_bounds__(256) void patch_gather_varlen_kernel(const float *_
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
-extern "C" {
-
-static int attn_varlen_args_ok(int B, int N, int h, int dh, float dropout_p, const void *n_tok) {
-    if ((dh != 64 && dh != 128) || N < 1 || N > ECGVIT_ATTN_MAX_N || B < 1 || h < 1 || !n_tok) return 0;
-    if (dropout_p > 0.f && dropout_threshold8(dropout_p) == 0) return 0;   // p < 1/512 would silently round to no dropout
-    return (int64_t)B * h * ((N + 127) / 128) < (1ll << 31);
+// One launcher per operation for the three forms: n_tok == nullptr -> uniform (attnu_*), tok_off == nullptr -> padded (attnv_*), else packed
+// (attnr_*).  Each checks what every entry point of the operation checks, then launches K<HI, DROP> for dh = 64 HI and the dropout threshold.
+// The uniform fwd / bwd serve dh = 128 only (the dh = 128 branches of ecgvit_attention_fwd / _bwd): dh = 64 runs the tuned kernels of attention.hip.
+static bool attn_args_ok(int B, int N, int h, int dh, float dropout_p) {
+    if ((dh != 64 && dh != 128) || N < 1 || N > ECGVIT_ATTN_MAX_N || B < 1 || h < 1) return false;
+    return !(dropout_p > 0.f && dropout_threshold8(dropout_p) == 0);   // p < 1/512 would silently round to no dropout
 }
+static bool attn_grid_ok(int B, int N, int h) { return (int64_t)B * h * ((N + 127) / 128) < (1ll << 31); }   // the fwd / bwd grid
 static bool aligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
-int ecgvit_attention_varlen_fwd(const void *qkv, void *out, float *lse, const int32_t *n_tok, int B, int N, int h, int dh, float scale,
-                                float dropout_p, uint64_t seed, void *stream) {
-    if (!attn_varlen_args_ok(B, N, h, dh, dropout_p, n_tok) || !aligned16(qkv) || !aligned16(out)) return ECGVIT_EINVAL;
+#define AV_DROP(K, HI, G, ...)                                                                                  \
+    do {                                                                                                        \
+        if (th) hipLaunchKernelGGL((K<HI, true>), G, dim3(256), 0, as_stream(stream), __VA_ARGS__);           \
+        else hipLaunchKernelGGL((K<HI, false>), G, dim3(256), 0, as_stream(stream), __VA_ARGS__);             \
+    } while (0)
+#define AV_HI_DROP(K, G, ...)                                          \
+    do {                                                               \
+        if (dh == 64) AV_DROP(K, 1, G, __VA_ARGS__);                   \
+        else AV_DROP(K, 2, G, __VA_ARGS__);                            \
+    } while (0)
+
+int attn_fwd_run(const void *qkv, void *out, float *lse, const int32_t *n_tok, const int32_t *tok_off, int B, int N, int h, int dh, float scale,
+                 float dropout_p, uint64_t seed, void *stream) {
+    if (!attn_args_ok(B, N, h, dh, dropout_p) || !attn_grid_ok(B, N, h) || (!n_tok && dh != 128) || !aligned16(qkv) || !aligned16(out))
+        return ECGVIT_EINVAL;
     const uint32_t th = dropout_threshold8(dropout_p);
     const float ik = dropout_inv_keep8(dropout_p);
     const dim3 grid((unsigned)(B * h * ((N + 127) / 128)));
-#define FWD(HI, DR) hipLaunchKernelGGL((attnv_fwd_kernel<HI, DR>), grid, dim3(256), 0, as_stream(stream), (const bf16_t *)qkv, (bf16_t *)out, lse, n_tok, \
-                                       N, h, scale, seed, th, ik)
-    if (dh == 64) { if (th) FWD(1, true); else FWD(1, false); }
-    else { if (th) FWD(2, true); else FWD(2, false); }
-#undef FWD
+    const bf16_t *q = (const bf16_t *)qkv;
+    bf16_t *o = (bf16_t *)out;
+    if (!n_tok) AV_DROP(attnu_fwd_kernel, 2, grid, q, o, lse, N, h, scale, seed, th, ik);
+    else if (!tok_off) AV_HI_DROP(attnv_fwd_kernel, grid, q, o, lse, n_tok, N, h, scale, seed, th, ik);
+    else AV_HI_DROP(attnr_fwd_kernel, grid, q, o, lse, n_tok, tok_off, N, h, scale, seed, th, ik);
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
 }
 
-int ecgvit_attention_varlen_bwd(const void *qkv, const void *out, const void *dout, const float *lse, void *dqkv, const int32_t *n_tok, int B, int N,
-                                int h, int dh, float scale, float dropout_p, uint64_t seed, void *stream) {
-    if (!attn_varlen_args_ok(B, N, h, dh, dropout_p, n_tok) || !aligned16(qkv) || !aligned16(out) || !aligned16(dout) || !aligned16(dqkv))
+int attn_bwd_run(const void *qkv, const void *out, const void *dout, const float *lse, void *dqkv, const int32_t *n_tok, const int32_t *tok_off,
+                 int B, int N, int h, int dh, float scale, float dropout_p, uint64_t seed, void *stream) {
+    if (!attn_args_ok(B, N, h, dh, dropout_p) || !attn_grid_ok(B, N, h) || (!n_tok && dh != 128) || !aligned16(qkv) || !aligned16(out) ||
+        !aligned16(dout) || !aligned16(dqkv))
         return ECGVIT_EINVAL;
     const uint32_t th = dropout_threshold8(dropout_p);
     const float ik = dropout_inv_keep8(dropout_p);
     const dim3 grid((unsigned)(B * h * ((N + 127) / 128)));   // 128-key blocks (dK / dV) = 128-query blocks (dQ)
-#define BWD(K, HI, DR) hipLaunchKernelGGL((K<HI, DR>), grid, dim3(256), 0, as_stream(stream), (const bf16_t *)qkv, (const bf16_t *)out, \
-                                          (const bf16_t *)dout, lse, (bf16_t *)dqkv, n_tok, N, h, scale, seed, th, ik)
-    if (dh == 64) { if (th) BWD(attnv_bwd_dkv_kernel, 1, true); else BWD(attnv_bwd_dkv_kernel, 1, false); }
-    else { if (th) BWD(attnv_bwd_dkv_kernel, 2, true); else BWD(attnv_bwd_dkv_kernel, 2, false); }
+    const bf16_t *q = (const bf16_t *)qkv, *o = (const bf16_t *)out, *dO = (const bf16_t *)dout;
+    bf16_t *dq = (bf16_t *)dqkv;
+    if (!n_tok) AV_DROP(attnu_bwd_dkv_kernel, 2, grid, q, o, dO, lse, dq, N, h, scale, seed, th, ik);
+    else if (!tok_off) AV_HI_DROP(attnv_bwd_dkv_kernel, grid, q, o, dO, lse, dq, n_tok, N, h, scale, seed, th, ik);
+    else AV_HI_DROP(attnr_bwd_dkv_kernel, grid, q, o, dO, lse, dq, n_tok, tok_off, N, h, scale, seed, th, ik);
     ECGVIT_CHECK_LAUNCH();
-    if (dh == 64) { if (th) BWD(attnv_bwd_dq_kernel, 1, true); else BWD(attnv_bwd_dq_kernel, 1, false); }
-    else { if (th) BWD(attnv_bwd_dq_kernel, 2, true); else BWD(attnv_bwd_dq_kernel, 2, false); }
+    if (!n_tok) AV_DROP(attnu_bwd_dq_kernel, 2, grid, q, o, dO, lse, dq, N, h, scale, seed, th, ik);
+    else if (!tok_off) AV_HI_DROP(attnv_bwd_dq_kernel, grid, q, o, dO, lse, dq, n_tok, N, h, scale, seed, th, ik);
+    else AV_HI_DROP(attnr_bwd_dq_kernel, grid, q, o, dO, lse, dq, n_tok, tok_off, N, h, scale, seed, th, ik);
     ECGVIT_CHECK_LAUNCH();
-#undef BWD
     return ECGVIT_OK;
+}
+
+// (the padded / packed CLS entry points have always held B h to the fwd / bwd grid limit as well)
+static int attn_cls_fwd_run(const void *qkv, void *out_cls, float *lse_cls, const int32_t *n_tok, const int32_t *tok_off, int B, int N, int h,
+                            int dh, float scale, float dropout_p, uint64_t seed, void *stream) {
+    if (!attn_args_ok(B, N, h, dh, dropout_p) || (int64_t)B * h >= (1ll << 31) || (n_tok && !attn_grid_ok(B, N, h)) || !aligned16(qkv) ||
+        !aligned16(out_cls))
+        return ECGVIT_EINVAL;
+    const uint32_t th = dropout_threshold8(dropout_p);
+    const float ik = dropout_inv_keep8(dropout_p);
+    const dim3 grid((unsigned)(B * h));
+    const bf16_t *q = (const bf16_t *)qkv;
+    bf16_t *o = (bf16_t *)out_cls;
+    if (!n_tok) AV_HI_DROP(attnu_cls_fwd_kernel, grid, q, o, lse_cls, N, h, scale, seed, th, ik);
+    else if (!tok_off) AV_HI_DROP(attnv_cls_fwd_kernel, grid, q, o, lse_cls, n_tok, N, h, scale, seed, th, ik);
+    else AV_HI_DROP(attnr_cls_fwd_kernel, grid, q, o, lse_cls, n_tok, tok_off, N, h, scale, seed, th, ik);
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
+}
+
+static int attn_cls_bwd_run(const void *qkv, const void *out_cls, const void *dout_cls, const float *lse_cls, void *dqkv, void *dq_cls,
+                            const int32_t *n_tok, const int32_t *tok_off, int B, int N, int h, int dh, float scale, float dropout_p, uint64_t seed,
+                            void *stream) {
+    if (!attn_args_ok(B, N, h, dh, dropout_p) || (int64_t)B * h >= (1ll << 31) || (n_tok && !attn_grid_ok(B, N, h)) || !aligned16(qkv) ||
+        !aligned16(out_cls) || !aligned16(dout_cls) || !aligned16(dqkv) || !aligned16(dq_cls))
+        return ECGVIT_EINVAL;
+    const uint32_t th = dropout_threshold8(dropout_p);
+    const float ik = dropout_inv_keep8(dropout_p);
+    const dim3 grid((unsigned)(B * h));
+    const bf16_t *q = (const bf16_t *)qkv, *o = (const bf16_t *)out_cls, *dO = (const bf16_t *)dout_cls;
+    bf16_t *dk = (bf16_t *)dqkv, *dq = (bf16_t *)dq_cls;
+    if (!n_tok) AV_HI_DROP(attnu_cls_bwd_kernel, grid, q, o, dO, lse_cls, dk, dq, N, h, scale, seed, th, ik);
+    else if (!tok_off) AV_HI_DROP(attnv_cls_bwd_kernel, grid, q, o, dO, lse_cls, dk, dq, n_tok, N, h, scale, seed, th, ik);
+    else AV_HI_DROP(attnr_cls_bwd_kernel, grid, q, o, dO, lse_cls, dk, dq, n_tok, tok_off, N, h, scale, seed, th, ik);
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
+}
+#undef AV_HI_DROP
+#undef AV_DROP
+
+extern "C" {
+
+int ecgvit_attention_cls_fwd(const void *qkv, void *out_cls, float *lse_cls, int B, int N, int h, int dh, float scale, float dropout_p, uint64_t seed,
+                             int dtype, void *stream) {
+    if (dtype != ECGVIT_BF16 || !qkv || !out_cls || !lse_cls) return ECGVIT_EINVAL;
+    return attn_cls_fwd_run(qkv, out_cls, lse_cls, nullptr, nullptr, B, N, h, dh, scale, dropout_p, seed, stream);
+}
+
+int ecgvit_attention_cls_bwd(const void *qkv, const void *out_cls, const void *dout_cls, const float *lse_cls, void *dqkv, void *dq_cls, int B, int N,
+                             int h, int dh, float scale, float dropout_p, uint64_t seed, int dtype, void *stream) {
+    if (dtype != ECGVIT_BF16 || !qkv || !out_cls || !dout_cls || !lse_cls || !dqkv || !dq_cls) return ECGVIT_EINVAL;
+    return attn_cls_bwd_run(qkv, out_cls, dout_cls, lse_cls, dqkv, dq_cls, nullptr, nullptr, B, N, h, dh, scale, dropout_p, seed, stream);
+}
+
+int ecgvit_attention_varlen_fwd(const void *qkv, void *out, float *lse, const int32_t *n_tok, int B, int N, int h, int dh, float scale,
+                                float dropout_p, uint64_t seed, void *stream) {
+    if (!n_tok) return ECGVIT_EINVAL;
+    return attn_fwd_run(qkv, out, lse, n_tok, nullptr, B, N, h, dh, scale, dropout_p, seed, stream);
+}
+
+int ecgvit_attention_varlen_bwd(const void *qkv, const void *out, const void *dout, const float *lse, void *dqkv, const int32_t *n_tok, int B, int N,
+                                int h, int dh, float scale, float dropout_p, uint64_t seed, void *stream) {
+    if (!n_tok) return ECGVIT_EINVAL;
+    return attn_bwd_run(qkv, out, dout, lse, dqkv, n_tok, nullptr, B, N, h, dh, scale, dropout_p, seed, stream);
 }
 
 int ecgvit_attention_varlen_cls_fwd(const void *qkv, void *out_cls, float *lse_cls, const int32_t *n_tok, int B, int N, int h, int dh, float scale,
                                     float dropout_p, uint64_t seed, void *stream) {
-    if (!attn_varlen_args_ok(B, N, h, dh, dropout_p, n_tok) || !aligned16(qkv) || !aligned16(out_cls) || (int64_t)B * h >= (1ll << 31))
-        return ECGVIT_EINVAL;
-    const uint32_t th = dropout_threshold8(dropout_p);
-    const float ik = dropout_inv_keep8(dropout_p);
-#define CLS_FWD(HI, DR) hipLaunchKernelGGL((attnv_cls_fwd_kernel<HI, DR>), dim3(B * h), dim3(256), 0, as_stream(stream), (const bf16_t *)qkv, \
-                                           (bf16_t *)out_cls, lse_cls, n_tok, N, h, scale, seed, th, ik)
-    if (dh == 64) { if (th) CLS_FWD(1, true); else CLS_FWD(1, false); }
-    else { if (th) CLS_FWD(2, true); else CLS_FWD(2, false); }
-#undef CLS_FWD
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    if (!n_tok) return ECGVIT_EINVAL;
+    return attn_cls_fwd_run(qkv, out_cls, lse_cls, n_tok, nullptr, B, N, h, dh, scale, dropout_p, seed, stream);
 }
 
 int ecgvit_attention_varlen_cls_bwd(const void *qkv, const void *out_cls, const void *dout_cls, const float *lse_cls, void *dqkv, void *dq_cls,
                                     const int32_t *n_tok, int B, int N, int h, int dh, float scale, float dropout_p, uint64_t seed, void *stream) {
-    if (!attn_varlen_args_ok(B, N, h, dh, dropout_p, n_tok) || !aligned16(qkv) || !aligned16(out_cls) || !aligned16(dout_cls) || !aligned16(dqkv) ||
-        !aligned16(dq_cls) || (int64_t)B * h >= (1ll << 31))
-        return ECGVIT_EINVAL;
-    const uint32_t th = dropout_threshold8(dropout_p);
-    const float ik = dropout_inv_keep8(dropout_p);
-#define CLS_BWD(HI, DR) hipLaunchKernelGGL((attnv_cls_bwd_kernel<HI, DR>), dim3(B * h), dim3(256), 0, as_stream(stream), (const bf16_t *)qkv, \
-                                           (const bf16_t *)out_cls, (const bf16_t *)dout_cls, lse_cls, (bf16_t *)dqkv, (bf16_t *)dq_cls, n_tok, N, h, \
-                                           scale, seed, th, ik)
-    if (dh == 64) { if (th) CLS_BWD(1, true); else CLS_BWD(1, false); }
-    else { if (th) CLS_BWD(2, true); else CLS_BWD(2, false); }
-#undef CLS_BWD
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    if (!n_tok) return ECGVIT_EINVAL;
+    return attn_cls_bwd_run(qkv, out_cls, dout_cls, lse_cls, dqkv, dq_cls, n_tok, nullptr, B, N, h, dh, scale, dropout_p, seed, stream);
 }
 
 // ragged batch: record b's rows start at tok_off[b] (int32 [B] on the device, with n_tok); N = the widest record's token count
 int ecgvit_attention_ragged_fwd(const void *qkv, void *out, float *lse, const int32_t *n_tok, const int32_t *tok_off, int B, int N, int h, int dh,
                                 float scale, float dropout_p, uint64_t seed, void *stream) {
-    if (!attn_varlen_args_ok(B, N, h, dh, dropout_p, n_tok) || !tok_off || !aligned16(qkv) || !aligned16(out)) return ECGVIT_EINVAL;
-    const uint32_t th = dropout_threshold8(dropout_p);
-    const float ik = dropout_inv_keep8(dropout_p);
-    const dim3 grid((unsigned)(B * h * ((N + 127) / 128)));
-#define FWD(HI, DR) hipLaunchKernelGGL((attnr_fwd_kernel<HI, DR>), grid, dim3(256), 0, as_stream(stream), (const bf16_t *)qkv, (bf16_t *)out, lse, n_tok, \
-                                       tok_off, N, h, scale, seed, th, ik)
-    if (dh == 64) { if (th) FWD(1, true); else FWD(1, false); }
-    else { if (th) FWD(2, true); else FWD(2, false); }
-#undef FWD
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    if (!n_tok || !tok_off) return ECGVIT_EINVAL;
+    return attn_fwd_run(qkv, out, lse, n_tok, tok_off, B, N, h, dh, scale, dropout_p, seed, stream);
 }
 
 int ecgvit_attention_ragged_bwd(const void *qkv, const void *out, const void *dout, const float *lse, void *dqkv, const int32_t *n_tok,
                                 const int32_t *tok_off, int B, int N, int h, int dh, float scale, float dropout_p, uint64_t seed, void *stream) {
-    if (!attn_varlen_args_ok(B, N, h, dh, dropout_p, n_tok) || !tok_off || !aligned16(qkv) || !aligned16(out) || !aligned16(dout) ||
-        !aligned16(dqkv))
-        return ECGVIT_EINVAL;
-    const uint32_t th = dropout_threshold8(dropout_p);
-    const float ik = dropout_inv_keep8(dropout_p);
-    const dim3 grid((unsigned)(B * h * ((N + 127) / 128)));
-#define BWD(K, HI, DR) hipLaunchKernelGGL((K<HI, DR>), grid, dim3(256), 0, as_stream(stream), (const bf16_t *)qkv, (const bf16_t *)out, \
-                                          (const bf16_t *)dout, lse, (bf16_t *)dqkv, n_tok, tok_off, N, h, scale, seed, th, ik)
-    if (dh == 64) { if (th) BWD(attnr_bwd_dkv_kernel, 1, true); else BWD(attnr_bwd_dkv_kernel, 1, false); }
-    else { if (th) BWD(attnr_bwd_dkv_kernel, 2, true); else BWD(attnr_bwd_dkv_kernel, 2, false); }
-    ECGVIT_CHECK_LAUNCH();
-    if (dh == 64) { if (th) BWD(attnr_bwd_dq_kernel, 1, true); else BWD(attnr_bwd_dq_kernel, 1, false); }
-    else { if (th) BWD(attnr_bwd_dq_kernel, 2, true); else BWD(attnr_bwd_dq_kernel, 2, false); }
-    ECGVIT_CHECK_LAUNCH();
-#undef BWD
-    return ECGVIT_OK;
+    if (!n_tok || !tok_off) return ECGVIT_EINVAL;
+    return attn_bwd_run(qkv, out, dout, lse, dqkv, n_tok, tok_off, B, N, h, dh, scale, dropout_p, seed, stream);
 }
 
 int ecgvit_attention_ragged_cls_fwd(const void *qkv, void *out_cls, float *lse_cls, const int32_t *n_tok, const int32_t *tok_off, int B, int N, int h,
                                     int dh, float scale, float dropout_p, uint64_t seed, void *stream) {
-    if (!attn_varlen_args_ok(B, N, h, dh, dropout_p, n_tok) || !tok_off || !aligned16(qkv) || !aligned16(out_cls) || (int64_t)B * h >= (1ll << 31))
-        return ECGVIT_EINVAL;
-    const uint32_t th = dropout_threshold8(dropout_p);
-    const float ik = dropout_inv_keep8(dropout_p);
-#define CLS_FWD(HI, DR) hipLaunchKernelGGL((attnr_cls_fwd_kernel<HI, DR>), dim3(B * h), dim3(256), 0, as_stream(stream), (const bf16_t *)qkv, \
-                                           (bf16_t *)out_cls, lse_cls, n_tok, tok_off, N, h, scale, seed, th, ik)
-    if (dh == 64) { if (th) CLS_FWD(1, true); else CLS_FWD(1, false); }
-    else { if (th) CLS_FWD(2, true); else CLS_FWD(2, false); }
-#undef CLS_FWD
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    if (!n_tok || !tok_off) return ECGVIT_EINVAL;
+    return attn_cls_fwd_run(qkv, out_cls, lse_cls, n_tok, tok_off, B, N, h, dh, scale, dropout_p, seed, stream);
 }
 
 int ecgvit_attention_ragged_cls_bwd(const void *qkv, const void *out_cls, const void *dout_cls, const float *lse_cls, void *dqkv, void *dq_cls,
                                     const int32_t *n_tok, const int32_t *tok_off, int B, int N, int h, int dh, float scale, float dropout_p,
                                     uint64_t seed, void *stream) {
-    if (!attn_varlen_args_ok(B, N, h, dh, dropout_p, n_tok) || !tok_off || !aligned16(qkv) || !aligned16(out_cls) || !aligned16(dout_cls) ||
-        !aligned16(dqkv) || !aligned16(dq_cls) || (int64_t)B * h >= (1ll << 31))
-        return ECGVIT_EINVAL;
-    const uint32_t th = dropout_threshold8(dropout_p);
-    const float ik = dropout_inv_keep8(dropout_p);
-#define CLS_BWD(HI, DR) hipLaunchKernelGGL((attnr_cls_bwd_kernel<HI, DR>), dim3(B * h), dim3(256), 0, as_stream(stream), (const bf16_t *)qkv, \
-                                           (const bf16_t *)out_cls, (const bf16_t *)dout_cls, lse_cls, (bf16_t *)dqkv, (bf16_t *)dq_cls, n_tok, tok_off, \
-                                           N, h, scale, seed, th, ik)
-    if (dh == 64) { if (th) CLS_BWD(1, true); else CLS_BWD(1, false); }
-    else { if (th) CLS_BWD(2, true); else CLS_BWD(2, false); }
-#undef CLS_BWD
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    if (!n_tok || !tok_off) return ECGVIT_EINVAL;
+    return attn_cls_bwd_run(qkv, out_cls, dout_cls, lse_cls, dqkv, dq_cls, n_tok, tok_off, B, N, h, dh, scale, dropout_p, seed, stream);
 }
 
 int ecgvit_softmax_rows_varlen(float *S, const int32_t *n_tok, int B, int h, int N, int64_t ld, void *stream) {

@@ -1,4 +1,5 @@
-// Shared device helpers of the fused attention kernels (attention.hip: the forward kernels, the one-item and the persistent backward):
+// Shared device helpers of the fused attention kernels (attention.hip: the forward kernels, the one-item and the persistent backward;
+// attention_varlen.hip: the kernels of attn_varlen_kernels.h):
 // the swizzled [row][64 x bf16] LDS image, its row / transposed fragment reads, the dS^T image slot swizzle.
 //
 // LDS image for every [row][64 x bf16] tile (128-B rows):  16-B chunk index ^= bitrev3((row>>1)&7)
@@ -9,6 +10,14 @@
 
 // longest record (tokens) the fused bf16 attention covers: the forward, backward and CLS-row entry points return ECGVIT_EINVAL above it
 #define ECGVIT_ATTN_MAX_N 2048
+
+// The fused attention of attention_varlen.hip for a uniform (n_tok == nullptr, dh = 128 only), padded (tok_off == nullptr) or packed batch; the
+// dh = 128 branches of ecgvit_attention_fwd / _bwd (attention.hip) call them.  Library-internal: hidden, not part of the C-ABI.
+__attribute__((visibility("hidden"))) int attn_fwd_run(const void *qkv, void *out, float *lse, const int32_t *n_tok, const int32_t *tok_off, int B,
+                                                       int N, int h, int dh, float scale, float dropout_p, uint64_t seed, void *stream);
+__attribute__((visibility("hidden"))) int attn_bwd_run(const void *qkv, const void *out, const void *dout, const float *lse, void *dqkv,
+                                                       const int32_t *n_tok, const int32_t *tok_off, int B, int N, int h, int dh, float scale,
+                                                       float dropout_p, uint64_t seed, void *stream);
 
 namespace {
 

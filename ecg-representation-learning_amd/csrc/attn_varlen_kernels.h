@@ -1,17 +1,23 @@
-// The fused attention kernels of attention_varlen.hip, written once and included twice (no include guard):
-//   AV_PACKED 0 -> attnv_*: padded batch, record b owns rows [b N, b N + N) of qkv / out / dqkv (rows >= n_tok[b] are padding, written as zeros);
-//   AV_PACKED 1 -> attnr_*: ragged batch, record b owns rows [tok_off[b], tok_off[b] + n_tok[b]) -- packed, no padded rows: nothing past
-//                  n_tok[b] is read or written.  N is then the widest record's token count (grid, LSE layout, dropout hashing).
-// Each form is its own __global__ body, so the padded kernels compile exactly as they did before the packed form existed (a shared __device__
-// body inlined into two kernels does not: the inlined code is scheduled and allocated differently).
-#if AV_PACKED
-#define AV_KERNEL(name) attnr_##name
-#define AV_TOK_OFF const int32_t *__restrict__ tok_off,
-#define AV_ROW_BASE constexpr bool PK = true;
-#else
+// The fused attention kernels of attention_varlen.hip, written once and included three times (no include guard):
+//   AV_FORM 0 -> attnu_*: uniform batch, record b owns rows [b N, b N + N) of qkv / out / dqkv and n = N (no n_tok / tok_off argument: the
+//                padding branches fold away at compile time);
+//   AV_FORM 1 -> attnv_*: padded batch, the same rows, rows >= n_tok[b] are padding, written as zeros;
+//   AV_FORM 2 -> attnr_*: ragged batch, record b owns rows [tok_off[b], tok_off[b] + n_tok[b]) -- packed, no padded rows: nothing past
+//                n_tok[b] is read or written.  N is then the widest record's token count (grid, LSE layout, dropout hashing).
+// Each form is its own __global__ body, so each compiles exactly as it would alone (a shared __device__ body inlined into several kernels does
+// not: the inlined code is scheduled and allocated differently).
+#if AV_FORM == 0
+#define AV_KERNEL(name) attnu_##name
+#define AV_LENGTHS
+#define AV_ROW_BASE constexpr bool UN = true, PK = false; const int32_t *const n_tok = nullptr, *const tok_off = nullptr;
+#elif AV_FORM == 1
 #define AV_KERNEL(name) attnv_##name
-#define AV_TOK_OFF
-#define AV_ROW_BASE constexpr bool PK = false; const int32_t *const tok_off = nullptr;
+#define AV_LENGTHS const int32_t *__restrict__ n_tok,
+#define AV_ROW_BASE constexpr bool UN = false, PK = false; const int32_t *const tok_off = nullptr;
+#else
+#define AV_KERNEL(name) attnr_##name
+#define AV_LENGTHS const int32_t *__restrict__ n_tok, const int32_t *__restrict__ tok_off,
+#define AV_ROW_BASE constexpr bool UN = false, PK = true;
 #endif
 
 // =====================================================================================================
@@ -20,7 +26,7 @@
 // =====================================================================================================
 template <int HI, bool DROP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HI == 1 ? 4 : 3))) void AV_KERNEL(fwd_kernel)(
-    const bf16_t *__restrict__ qkv, bf16_t *__restrict__ out, float *__restrict__ lse, const int32_t *__restrict__ n_tok, AV_TOK_OFF int N, int h,
+    const bf16_t *__restrict__ qkv, bf16_t *__restrict__ out, float *__restrict__ lse, AV_LENGTHS int N, int h,
     float scale, uint64_t seed, uint32_t thresh, float inv_keep) {
     AV_ROW_BASE
     constexpr int HB = AV_WK * 128, DH = 64 * HI;
@@ -29,10 +35,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HI == 1 ? 4
     const int nqb = (N + 127) >> 7;
     const int bh = blockIdx.x / nqb, qb = blockIdx.x - bh * nqb;
     const int b = bh / h, hd = bh - b * h;
-    const int n = n_tok[b];
+    const int n = UN ? N : n_tok[b];
     const int d = h * DH;
     const int64_t d3 = 3 * (int64_t)d;
-    if (qb * 128 >= n) {   // every query of the block is padding (packed: does not exist)
+    if (!UN && qb * 128 >= n) {   // every query of the block is padding (packed: does not exist)
         if constexpr (!PK) {
             const int r1 = min(qb * 128 + 128, N);
             av_zero_rows<DH>(out + (int64_t)b * N * d + hd * DH, d, qb * 128, r1);
@@ -101,7 +107,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HI == 1 ? 4
     }
     l += __shfl_xor(l, 32, 64);
     if (q < (PK ? n : N)) {
-        const bool valid = q < n;
+        const bool valid = UN || q < n;
         const float inv = inv_keep / l;   // inv_keep = 1 without dropout
         bf16_t *orow = PK ? out + ((int64_t)tok_off[b] + q) * d + hd * DH : out + ((int64_t)b * N + q) * d + hd * DH;
 #pragma unroll
@@ -123,7 +129,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HI == 1 ? 4
 template <int HI, bool DROP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void AV_KERNEL(bwd_dkv_kernel)(
     const bf16_t *__restrict__ qkv, const bf16_t *__restrict__ out, const bf16_t *__restrict__ dout, const float *__restrict__ lse,
-    bf16_t *__restrict__ dqkv, const int32_t *__restrict__ n_tok, AV_TOK_OFF int N, int h, float scale, uint64_t seed, uint32_t thresh, float inv_keep) {
+    bf16_t *__restrict__ dqkv, AV_LENGTHS int N, int h, float scale, uint64_t seed, uint32_t thresh, float inv_keep) {
     AV_ROW_BASE
     constexpr int DH = 64 * HI;
     __shared__ __attribute__((aligned(16))) char smem[2 * HI * 4096 + 2 * 32 * 4 + HI * 128 * 128];
@@ -133,10 +139,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void A
     const int nkb = (N + 127) >> 7;
     const int bh = blockIdx.x / nkb, kb = blockIdx.x - bh * nkb;
     const int b = bh / h, hd = bh - b * h;
-    const int n = n_tok[b];
+    const int n = UN ? N : n_tok[b];
     const int d = h * DH;
     const int64_t d3 = 3 * (int64_t)d;
-    if (kb * 128 >= n) {   // every key of the block is padding: dK = dV = 0 (packed: does not exist)
+    if (!UN && kb * 128 >= n) {   // every key of the block is padding: dK = dV = 0 (packed: does not exist)
         if constexpr (!PK) {
             const int r1 = min(kb * 128 + 128, N);
             bf16_t *dk = dqkv + (int64_t)b * N * d3 + d + hd * DH;
@@ -183,12 +189,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void A
         {   // delta = rowsum(dO * O) and LSE (log2 units) of the block's rows: 8 lanes per row, 8 HI dims each; rows >= n: 0 (their Q / dO rows are 0)
             const int row = threadIdx.x >> 3, part = threadIdx.x & 7;
             const int r = q0 + row, rc = r < n ? r : n - 1;
-            float acc = 0.f;
+            Vec16<bf16_t> a[HI], o[HI];
 #pragma unroll
             for (int i = 0; i < HI; ++i) {
-                const Vec16<bf16_t> a = ld16(dobase + (int64_t)rc * d + part * 8 * HI + 8 * i), o = ld16(obase + (int64_t)rc * d + part * 8 * HI + 8 * i);
+                a[i] = ld16(dobase + (int64_t)rc * d + part * 8 * HI + 8 * i);
+                o[i] = ld16(obase + (int64_t)rc * d + part * 8 * HI + 8 * i);
+            }
+            float acc = 0.f;   // (one expression per k: the summation order every form shares)
 #pragma unroll
-                for (int k = 0; k < 8; ++k) acc += a.get(k) * o.get(k);
+            for (int k = 0; k < 8; ++k) {
+                if constexpr (HI == 1) acc += a[0].get(k) * o[0].get(k);
+                else acc += a[0].get(k) * o[0].get(k) + a[1].get(k) * o[1].get(k);
             }
             acc += __shfl_xor(acc, 1, 64);
             acc += __shfl_xor(acc, 2, 64);
@@ -251,7 +262,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void A
         }
     }
     if (mykey < (PK ? n : N)) {   // lane = key, accumulator rows = dims dt * 32 + 8 g + 4 lh + 0..3
-        const bool valid = mykey < n;
+        const bool valid = UN || mykey < n;
         bf16_t *dk = PK ? dqkv + ((int64_t)tok_off[b] + mykey) * d3 + d + hd * DH : dqkv + ((int64_t)b * N + mykey) * d3 + d + hd * DH;
 #pragma unroll
         for (int dt = 0; dt < 2 * HI; ++dt)
@@ -271,7 +282,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void A
 template <int HI, bool DROP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void AV_KERNEL(bwd_dq_kernel)(
     const bf16_t *__restrict__ qkv, const bf16_t *__restrict__ out, const bf16_t *__restrict__ dout, const float *__restrict__ lse,
-    bf16_t *__restrict__ dqkv, const int32_t *__restrict__ n_tok, AV_TOK_OFF int N, int h, float scale, uint64_t seed, uint32_t thresh, float inv_keep) {
+    bf16_t *__restrict__ dqkv, AV_LENGTHS int N, int h, float scale, uint64_t seed, uint32_t thresh, float inv_keep) {
     AV_ROW_BASE
     constexpr int HB = AV_WK * 128, DH = 64 * HI;
     __shared__ __attribute__((aligned(16))) char smem[2 * HI * HB];
@@ -279,10 +290,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void A
     const int nqb = (N + 127) >> 7;
     const int bh = blockIdx.x / nqb, qb = blockIdx.x - bh * nqb;
     const int b = bh / h, hd = bh - b * h;
-    const int n = n_tok[b];
+    const int n = UN ? N : n_tok[b];
     const int d = h * DH;
     const int64_t d3 = 3 * (int64_t)d;
-    if (qb * 128 >= n) {   // every query of the block is padding: dQ = 0 (packed: does not exist)
+    if (!UN && qb * 128 >= n) {   // every query of the block is padding: dQ = 0 (packed: does not exist)
         if constexpr (!PK) av_zero_rows<DH>(dqkv + (int64_t)b * N * d3 + hd * DH, d3, qb * 128, min(qb * 128 + 128, N));
         return;
     }
@@ -365,7 +376,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void A
         }
     }
     if (q < (PK ? n : N)) {
-        const bool valid = q < n;
+        const bool valid = UN || q < n;
         bf16_t *dq = PK ? dqkv + ((int64_t)tok_off[b] + q) * d3 + hd * DH : dqkv + ((int64_t)b * N + q) * d3 + hd * DH;
 #pragma unroll
         for (int dt = 0; dt < 2 * HI; ++dt)
@@ -378,12 +389,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void A
 }
 
 // =====================================================================================================
-// CLS row (query 0 of each record) against its n_tok keys: one workgroup per (record, head), 256 threads = AVC_SLOTS key slots x 8 HI lanes of 8
-// dims; bandwidth kernels, no MFMA.  Budget: <= 128 VGPRs, no scratch; LDS fwd 8 KiB + slots x (DH + 1) floats, bwd slots x (DH + 1) floats.
+// CLS row (query 0 of each record) against its n keys -- the pruned last block of the supervised step: the classifier reads x[:, 0] only, so
+// after the last block's K / V nothing else of that block reaches the loss.  One workgroup per (record, head), 256 threads = 256 / (8 HI) key
+// slots x 8 HI lanes of 8 dims (one 16-B load per key row and operand); bandwidth kernels, no MFMA.  The dropout bits are the full kernels'
+// for query 0.  The backward writes dK / dV of every key row and a compact dQ.  Budget: <= 128 VGPRs, no scratch; LDS fwd 8 KiB (the
+// ECGVIT_ATTN_MAX_N-key score array, at every N) + slots x (DH + 1) floats, bwd slots x (DH + 1) floats.
 // =====================================================================================================
 template <int HI, bool DROP>
 __global__ __launch_bounds__(256) void AV_KERNEL(cls_fwd_kernel)(const bf16_t *__restrict__ qkv, bf16_t *__restrict__ out, float *__restrict__ lse,
-                                                        const int32_t *__restrict__ n_tok, AV_TOK_OFF int N, int h, float scale, uint64_t seed,
+                                                        AV_LENGTHS int N, int h, float scale, uint64_t seed,
                                                         uint32_t thresh, float inv_keep) {
     AV_ROW_BASE
     constexpr int DH = 64 * HI, G = 8 * HI, SLOTS = 256 / G;
@@ -391,7 +405,7 @@ __global__ __launch_bounds__(256) void AV_KERNEL(cls_fwd_kernel)(const bf16_t *_
     __shared__ float ored[SLOTS][DH + 1];   // per-slot partial outputs
     __shared__ float red[4];
     const int bh = blockIdx.x, b = bh / h, head = bh % h;
-    const int n = n_tok[b];
+    const int n = UN ? N : n_tok[b];
     const int g = threadIdx.x % G, slot = threadIdx.x / G;
     const int64_t dm = (int64_t)h * DH, ld = 3 * dm;
     const bf16_t *rec = PK ? qkv + (int64_t)tok_off[b] * ld + head * DH + g * 8 : qkv + (int64_t)b * N * ld + head * DH + g * 8;
@@ -435,16 +449,16 @@ __global__ __launch_bounds__(256) void AV_KERNEL(cls_fwd_kernel)(const bf16_t *_
 template <int HI, bool DROP>
 __global__ __launch_bounds__(256) void AV_KERNEL(cls_bwd_kernel)(const bf16_t *__restrict__ qkv, const bf16_t *__restrict__ o_cls,
                                                         const bf16_t *__restrict__ do_cls, const float *__restrict__ lse,
-                                                        bf16_t *__restrict__ dqkv, bf16_t *__restrict__ dq_cls, const int32_t *__restrict__ n_tok,
-                                                        AV_TOK_OFF int N, int h, float scale, uint64_t seed, uint32_t thresh, float inv_keep) {
+                                                        bf16_t *__restrict__ dqkv, bf16_t *__restrict__ dq_cls, AV_LENGTHS int N, int h,
+                                                        float scale, uint64_t seed, uint32_t thresh, float inv_keep) {
     AV_ROW_BASE
     constexpr int DH = 64 * HI, G = 8 * HI, SLOTS = 256 / G;
     __shared__ float qred[SLOTS][DH + 1];
     const int bh = blockIdx.x, b = bh / h, head = bh % h;
-    const int n = n_tok[b];
+    const int n = UN ? N : n_tok[b];
     const int g = threadIdx.x % G, slot = threadIdx.x / G;
     const int64_t dm = (int64_t)h * DH, ld = 3 * dm;
-    if constexpr (!PK) {   // rows >= n: dK = dV = 0
+    if constexpr (!UN && !PK) {   // rows >= n: dK = dV = 0
         av_zero_rows<DH>(dqkv + (int64_t)b * N * ld + dm + head * DH, ld, n, N);
         av_zero_rows<DH>(dqkv + (int64_t)b * N * ld + 2 * dm + head * DH, ld, n, N);
     }
@@ -490,5 +504,5 @@ __global__ __launch_bounds__(256) void AV_KERNEL(cls_bwd_kernel)(const bf16_t *_
 }
 
 #undef AV_KERNEL
-#undef AV_TOK_OFF
+#undef AV_LENGTHS
 #undef AV_ROW_BASE

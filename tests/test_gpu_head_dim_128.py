@@ -1,4 +1,4 @@
-"""-m gpu: the fused bf16 attention for 128-wide heads (dh = 128, attention_h128.hip).
+"""-m gpu: the fused bf16 attention for 128-wide heads (dh = 128, the uniform form of attn_varlen_kernels.h).
 
 Held here: outputs, LSE and dQ / dK / dV against fp64 at 1 to 2048 tokens, repeated launches bit for bit; the dropout mask of the dh = 128 forward
 equal to the dh = 64 kernel's (`hiputil._attn_prob_mult_bf16`) and the forward / backward under it; the CLS-row kernels against row 0 of the full

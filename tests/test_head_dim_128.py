@@ -1,4 +1,4 @@
-"""CPU: the bf16 engine takes 128-wide attention heads (dh = 128, the kernels of attention_h128.hip) at 1 to 2048 tokens, still rejects every other
+"""CPU: the bf16 engine takes 128-wide attention heads (dh = 128, the uniform-form kernels of attention_varlen.hip) at 1 to 2048 tokens, still rejects every other
 head dim but 64, and the dh = 128 kernels are spill-free and inside the budgets their comments state (code-object metadata, tools/code_objects.py;
 no GPU)."""
 import os
@@ -39,9 +39,9 @@ def test_bf16_engine_rejects_other_head_dims(d, h):
         _engine(251, d, h)
 
 
-# kernel-name stem -> (VGPR budget stated in attention_h128.hip, LDS bytes)
-BUDGETS = {'attn128_fwd_kernel': (168, 32768), 'attn128_bwd_dkv_kernel': (256, 49408), 'attn128_bwd_dq_kernel': (256, 32768),
-           'attn128_cls_fwd_kernel': (128, 16464), 'attn128_cls_bwd_kernel': (128, 8256)}
+# kernel-name stem (the uniform form at HI = 2 head images) -> (VGPR budget stated in attn_varlen_kernels.h, LDS bytes)
+BUDGETS = {'attnu_fwd_kernelILi2E': (168, 32768), 'attnu_bwd_dkv_kernelILi2E': (256, 49408), 'attnu_bwd_dq_kernelILi2E': (256, 32768),
+           'attnu_cls_fwd_kernelILi2E': (128, 16464), 'attnu_cls_bwd_kernelILi2E': (128, 8256)}
 
 
 @pytest.fixture(scope='module')
@@ -52,7 +52,7 @@ def kernels():
     return code_objects.kernels(LIB)
 
 
-def test_head_dim_128_kernels_spill_free_and_inside_budget(kernels):
+def test_head_dim_128_uniform_kernels_spill_free_and_inside_budget(kernels):
     seen = {}
     for name, k in kernels.items():
         for stem, (vgprs, lds) in BUDGETS.items():

@@ -45,12 +45,13 @@ def kernels():
     return code_objects.kernels(LIB)
 
 
-def test_long_record_kernels_are_spill_free_and_within_budget(kernels):
+def test_long_record_kernels_and_uniform_cls_forward_are_spill_free_and_within_budget(kernels):
     """the instantiations only N > 512 launches: the streamed forward's MODE 4 (<= 128 VGPRs: four waves per SIMD), the persistent backward with
-    the 2048-query LSE row (<= 256: two waves per SIMD, and inside 160 KiB of LDS), the CLS-row forward with the 2048-key score array"""
+    the 2048-query LSE row (<= 256: two waves per SIMD, and inside 160 KiB of LDS), the dh = 64 CLS-row forward (uniform form; its score array
+    holds 2048 keys at every N: <= 128 VGPRs, LDS 8 KiB + 32 x 65 floats + 16 B)"""
     fwd = [n for n in kernels if re.search(r'attn_fwd_stream_kernelILb[01]ELb[01]ELi4EE', n)]
     bwd = [n for n in kernels if 'attn_bwd_pers_kernel' in n and 'Li2048EE' in n]
-    cls = [n for n in kernels if 'attn_cls_fwd_kernel' in n and 'Li2048EE' in n]
+    cls = [n for n in kernels if 'attnu_cls_fwd_kernelILi1E' in n]
     assert len(fwd) == 4 and len(bwd) == 4 and len(cls) == 2, (fwd, bwd, cls)
     for n in fwd + bwd + cls:
         k = kernels[n]
@@ -60,3 +61,5 @@ def test_long_record_kernels_are_spill_free_and_within_budget(kernels):
     for n in bwd:
         assert kernels[n]['vgpr_count'] + kernels[n]['agpr_count'] <= 256, (n, kernels[n])
         assert kernels[n]['group_segment_fixed_size'] <= 160 * 1024, (n, kernels[n])
+    for n in cls:
+        assert kernels[n]['vgpr_count'] <= 128 and kernels[n]['group_segment_fixed_size'] <= 16528, (n, kernels[n])

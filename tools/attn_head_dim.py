@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """128-wide against 64-wide attention heads at equal (B, N, d), in ONE process on one device: the fused forward and backward per launch (dh = 128:
-attention_h128.hip; dh = 64: attention.hip) at 512 x 251 (d 768), 256 x 501 and 64 x 1251 (d 1024), then one whole supervised step of EcgVit-base
+the uniform form of attn_varlen_kernels.h; dh = 64: attention.hip) at 512 x 251 (d 768), 256 x 501 and 64 x 1251 (d 1024), then one whole supervised step of EcgVit-base
 (d 768, 12 heads) against the same model with 6 heads through HipTrainStep.step at 251 and 1251 tokens.
 usage: python tools/attn_head_dim.py [reps] [p]      (output: profiles/r09_attn_head_dim.txt)"""
 import os
