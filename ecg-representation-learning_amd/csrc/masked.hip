@@ -1,6 +1,7 @@
 // Masked pre-train objective pieces (SimMIM-style; the build's own definition -- the reference has no masked
 // objective): mask-token substitution + positional add, row gather / scatter by host-generated
-// int32 indices (bit-exact integer indexing), L1 reconstruction loss.  All HBM-bound, 16 B per lane.
+// int32 indices (bit-exact integer indexing), L1 reconstruction loss, and the embedding pair for records of unequal length (packed or
+// padded rows).  All HBM-bound, 16 B per lane.
 #include "common.h"
 
 namespace {
@@ -86,6 +87,106 @@ __global__ __launch_bounds__(256) void mark_mask_kernel(const int32_t *__restric
     if (p >= 0 && p < n) flag[(int64_t)b * n + p] = 1;
 }
 
+// ---- records of unequal length (no CLS row).  Record b holds n_tok[b] patches in the rows tok_off[b] .. tok_off[b] + n_tok[b] - 1 of tok / X / dX:
+// packed (n_pad == 0: tok_off = exclusive prefix sum of n_tok, no other row exists) or padded (n_pad > 0: tok_off[b] = b * n_pad, the rows
+// past n_tok[b] of a record are written as exact zeros and never read).  One kernel text serves both layouts.
+__global__ __launch_bounds__(256) void mark_rows_kernel(const int32_t *__restrict__ row_idx, uint8_t *__restrict__ flag, int count, int64_t M) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const int64_t r = row_idx[i];
+    if (r >= 0 && r < M) flag[r] = 1;
+}
+
+// X[row] = (flag[row] ? mask_token : tok[row]) + pos[1 + j], j = the row's patch index inside its record.  One grid row per record, its
+// patches strided over the blocks (the shape of embed_finish_ragged_kernel).
+template <typename T>
+__global__ __launch_bounds__(256) void mask_embed_varlen_kernel(const T *__restrict__ tok, const float *__restrict__ mask_token,
+                                                                const float *__restrict__ pos, const uint8_t *__restrict__ flag,
+                                                                T *__restrict__ X, const int32_t *__restrict__ n_tok,
+                                                                const int32_t *__restrict__ tok_off, int n_pad, int d) {
+    constexpr int VN = Vec16<T>::N;
+    const int b = blockIdx.y, dv = d / VN;
+    const int nb = n_tok[b];
+    const int64_t r0 = tok_off[b], total = (int64_t)(n_pad ? n_pad : nb) * dv;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int j = (int)(i / dv), c0 = (int)(i - (int64_t)j * dv) * VN;
+        const int64_t row = r0 + j;
+        Vec16<T> o;
+        if (j >= nb) {
+#pragma unroll
+            for (int k = 0; k < VN; ++k) o.set(k, 0.f);
+        } else if (flag[row]) {
+#pragma unroll
+            for (int k = 0; k < VN; ++k) o.set(k, mask_token[c0 + k] + pos[(int64_t)(1 + j) * d + c0 + k]);
+        } else {
+            const Vec16<T> v = ld16(tok + row * d + c0);
+#pragma unroll
+            for (int k = 0; k < VN; ++k) o.set(k, v.get(k) + pos[(int64_t)(1 + j) * d + c0 + k]);
+        }
+        st16(X + row * d + c0, o);
+    }
+}
+
+// its backward, in the shape of mask_embed_bwd_kernel (a workgroup per (patch p, 8 column vectors), 32 lanes across records, LDS fold in a
+// fixed order): dpos[1 + p] = the sum over the records that hold patch p.  `order` lists the records by falling n_tok (ties by record index:
+// a fixed order), so those records are order[0 .. cnt) with cnt found by bisection -- a workgroup of a tail position touches its few
+// contributors and never walks the B records to find them.  Padded layout: the rows (b, p) with p >= n_tok[b] get zeros in dtok / dmasked.
+template <typename T>
+__global__ __launch_bounds__(256) void mask_embed_varlen_bwd_kernel(const T *__restrict__ dX, const uint8_t *__restrict__ flag,
+                                                                    T *__restrict__ dtok, T *__restrict__ dmasked, float *__restrict__ dpos,
+                                                                    const int32_t *__restrict__ n_tok, const int32_t *__restrict__ tok_off,
+                                                                    const int32_t *__restrict__ order, int B, int n_pad, int d) {
+    constexpr int VN = Vec16<T>::N;
+    __shared__ float red[32][8][VN];
+    const int dv = d / VN, ngrp = (dv + 7) / 8;
+    const int p = blockIdx.x / ngrp, cg = blockIdx.x - p * ngrp;
+    const int cv = threadIdx.x & 7, bl = threadIdx.x >> 3;
+    const int c0 = (cg * 8 + cv) * VN;
+    const bool live = cg * 8 + cv < dv;
+    int cnt = 0, hi = B;
+    while (cnt < hi) {   // first position of `order` whose record is too short for patch p
+        const int mid = (cnt + hi) >> 1;
+        if (n_tok[order[mid]] > p) cnt = mid + 1;
+        else hi = mid;
+    }
+    float acc[VN];
+#pragma unroll
+    for (int k = 0; k < VN; ++k) acc[k] = 0.f;
+    Vec16<T> zero;
+#pragma unroll
+    for (int k = 0; k < VN; ++k) zero.set(k, 0.f);
+    if (live) {
+        for (int i = bl; i < cnt; i += 32) {
+            const int64_t row = (int64_t)tok_off[order[i]] + p;
+            const Vec16<T> v = ld16(dX + row * d + c0);
+#pragma unroll
+            for (int k = 0; k < VN; ++k) acc[k] += v.get(k);
+            const bool mk = flag[row] != 0;
+            st16(dtok + row * d + c0, mk ? zero : v);
+            st16(dmasked + row * d + c0, mk ? v : zero);
+        }
+        if (n_pad) {
+            for (int i = cnt + bl; i < B; i += 32) {
+                const int64_t row = (int64_t)tok_off[order[i]] + p;
+                st16(dtok + row * d + c0, zero);
+                st16(dmasked + row * d + c0, zero);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < VN; ++k) red[bl][cv][k] = acc[k];
+    __syncthreads();
+    if (bl == 0 && live) {
+#pragma unroll
+        for (int k = 0; k < VN; ++k) {
+            float s = 0.f;
+            for (int j = 0; j < 32; ++j) s += red[j][cv][k];
+            dpos[(int64_t)(1 + p) * d + c0 + k] = s;
+            if (p == 0) dpos[c0 + k] = 0.f;
+        }
+    }
+}
+
 // GATHER: out[b*m + k] = in[b*n + idx[b,k]] ; SCATTER: out[b*n + idx[b,k]] = in[b*m + k]
 template <typename T, bool SCATTER>
 __global__ __launch_bounds__(256) void rows_by_index_kernel(const T *__restrict__ in, const int32_t *__restrict__ idx,
@@ -168,6 +269,44 @@ int ecgvit_mask_embed_bwd(const void *dX, const void *flag_ws, void *dtok, void 
         hipLaunchKernelGGL(mask_embed_bwd_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), (const float *)dX, (const uint8_t *)flag_ws, (float *)dtok, (float *)dmasked, dpos, B, n, d);
     else if (dtype == ECGVIT_BF16)
         hipLaunchKernelGGL(mask_embed_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), (const bf16_t *)dX, (const uint8_t *)flag_ws, (bf16_t *)dtok, (bf16_t *)dmasked, dpos, B, n, d);
+    else return ECGVIT_EINVAL;
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
+}
+
+int ecgvit_mask_embed_varlen_fwd(const void *tok, const float *mask_token, const float *pos, const int32_t *row_idx, void *X, void *flag_ws,
+                                 const int32_t *n_tok, const int32_t *tok_off, int B, int N, int n_pad, int64_t M, int m_total, int d,
+                                 int dtype, void *stream) {
+    if (B <= 0 || B > 65535 || N <= 0 || (n_pad != 0 && n_pad < N) || M < N || m_total < 0 || d <= 0 || d % 8 != 0 || !flag_ws || !n_tok ||
+        !tok_off || (m_total > 0 && !row_idx) || (n_pad != 0 && M != (int64_t)B * n_pad))
+        return ECGVIT_EINVAL;
+    hipStream_t s = as_stream(stream);
+    if (hipMemsetAsync(flag_ws, 0, (size_t)M, s) != hipSuccess) return ECGVIT_ELAUNCH;
+    if (m_total > 0) {
+        hipLaunchKernelGGL(mark_rows_kernel, dim3((m_total + 255) / 256), dim3(256), 0, s, row_idx, (uint8_t *)flag_ws, m_total, M);
+        ECGVIT_CHECK_LAUNCH();
+    }
+    const int64_t per = (int64_t)(n_pad ? n_pad : N) * d / (dtype == ECGVIT_F32 ? 4 : 8);
+    const dim3 grid((unsigned)std::min<int64_t>((per + 255) / 256, 1024), (unsigned)B);
+    if (dtype == ECGVIT_F32)
+        hipLaunchKernelGGL(mask_embed_varlen_kernel<float>, grid, dim3(256), 0, s, (const float *)tok, mask_token, pos, (const uint8_t *)flag_ws, (float *)X, n_tok, tok_off, n_pad, d);
+    else if (dtype == ECGVIT_BF16)
+        hipLaunchKernelGGL(mask_embed_varlen_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t *)tok, mask_token, pos, (const uint8_t *)flag_ws, (bf16_t *)X, n_tok, tok_off, n_pad, d);
+    else return ECGVIT_EINVAL;
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
+}
+
+int ecgvit_mask_embed_varlen_bwd(const void *dX, const void *flag_ws, void *dtok, void *dmasked, float *dpos, const int32_t *n_tok,
+                                 const int32_t *tok_off, const int32_t *order, int B, int N, int n_pad, int d, int dtype, void *stream) {
+    if (B <= 0 || N <= 0 || (n_pad != 0 && n_pad < N) || d <= 0 || d % 8 != 0 || !flag_ws || !n_tok || !tok_off || !order) return ECGVIT_EINVAL;
+    const int dv = d / (dtype == ECGVIT_F32 ? 4 : 8);
+    const int64_t grid = (int64_t)(n_pad ? n_pad : N) * ((dv + 7) / 8);   // one workgroup per (patch, 8 column vectors)
+    if (grid >= (1ll << 31)) return ECGVIT_EINVAL;
+    if (dtype == ECGVIT_F32)
+        hipLaunchKernelGGL(mask_embed_varlen_bwd_kernel<float>, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), (const float *)dX, (const uint8_t *)flag_ws, (float *)dtok, (float *)dmasked, dpos, n_tok, tok_off, order, B, n_pad, d);
+    else if (dtype == ECGVIT_BF16)
+        hipLaunchKernelGGL(mask_embed_varlen_bwd_kernel<bf16_t>, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), (const bf16_t *)dX, (const uint8_t *)flag_ws, (bf16_t *)dtok, (bf16_t *)dmasked, dpos, n_tok, tok_off, order, B, n_pad, d);
     else return ECGVIT_EINVAL;
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;

@@ -31,7 +31,7 @@ except Exception:  # pragma: no cover - minimal stand-in when transformers is ab
             return dict(self.__dict__)
 
 from .check_args import ca
-from .engine import VitEngine, ParamLayout
+from .engine import VitEngine, ParamLayout, MaskedVarlenBatch, check_masked_varlen_input
 from . import hip
 
 ModelOutput = namedtuple('ModelOutput', ['loss', 'logits'])  # reference util/models.py:3
@@ -489,15 +489,20 @@ def load_trained(model_key='ecg-vit-base', checkpoint_path=None, compute_dtype=t
 class _MaskedFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, wrapper, x, idx, *params):
+        """idx: (B, m) int32 device indices (the rectangular pass) or a MaskedVarlenBatch (records of unequal length)"""
         enc = wrapper.encoder
         eng = enc._engine()
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if (enc.training and enc._has_dropout) else 0
-        pred, loss = eng.forward_masked(x, idx, training=enc.training, seed=seed)
+        if isinstance(idx, MaskedVarlenBatch):
+            pred, loss = eng.forward_masked_varlen(x, idx, training=enc.training, seed=seed)
+            shape = (idx.m, -1)
+        else:
+            pred, loss = eng.forward_masked(x, idx, training=enc.training, seed=seed)
+            shape = tuple(idx.shape) + (-1,)
         enc._fwd_id += 1
         ctx.wrapper, ctx.fwd_id = wrapper, enc._fwd_id
         ctx.set_materialize_grads(False)
-        B, m = idx.shape
-        return loss.clone().reshape(()), pred.float().view(B, m, -1).clone()
+        return loss.clone().reshape(()), pred.float().view(shape).clone()
 
     @staticmethod
     def backward(ctx, gloss, gpred):
@@ -521,6 +526,9 @@ class MaskedEcgVit(nn.Module):
       loss = mean |reconstruction - raw masked patches|.
     `mask_idx` (B, m) int32: distinct patch indices per record, generated on the host (`random_mask_indices`) so the
     integer index handling is bit-exact and reproducible.  forward -> ModelOutput(loss, logits=(B, m, C*P) reconstruction).
+    Records of unequal length (`lengths=`, a (B, C, L') batch or a ragged (C, S) one): record b has n_b = lengths[b] / P patches and its
+    own number m_b of masked ones -- `mask_idx` is then flat (record-local indices, record 0's first) with `mask_counts` (B,)
+    (`random_mask_indices_varlen`); the loss is the mean over every masked element of the batch, logits (sum m_b, C*P).
     Extra state_dict keys (not part of the reference checkpoint): `mask_token`, `to_pixels.{weight,bias}`.
     """
 
@@ -540,6 +548,19 @@ class MaskedEcgVit(nn.Module):
     def random_mask_indices(self, batch, generator=None):
         """(B, m) int32 on the host: per record, the first m entries of a random permutation of the n patches"""
         return torch.stack([torch.randperm(self.n_patch, generator=generator)[:self.n_mask] for _ in range(batch)]).to(torch.int32)
+
+    def mask_counts(self, lengths):
+        """(B,) int64 on the host: the masked patches of records of `lengths` samples, max(1, int(mask_ratio * n_b)) (n_mask at full width)"""
+        n = torch.as_tensor(lengths).detach().to('cpu', torch.int64) // self.encoder.config.patch_size
+        return torch.tensor([max(1, int(self.mask_ratio * int(v))) for v in n.tolist()], dtype=torch.int64)
+
+    def random_mask_indices_varlen(self, lengths, generator=None):
+        """(mask_idx int32 [sum m_b], mask_counts int64 [B]) on the host for records of unequal length: per record, in order, the first m_b
+        entries of a random permutation of its n_b patches"""
+        counts = self.mask_counts(lengths)
+        n = torch.as_tensor(lengths).detach().to('cpu', torch.int64) // self.encoder.config.patch_size
+        idx = [torch.randperm(int(nb), generator=generator)[:int(mb)] for nb, mb in zip(n.tolist(), counts.tolist())]
+        return torch.cat(idx).to(torch.int32), counts
 
     def check_mask_indices(self, mask_idx, batch):
         """(B, m) integer tensor of DISTINCT patch indices in [0, n_patch) per record, else ValueError: the row gather / scatter
@@ -564,12 +585,35 @@ class MaskedEcgVit(nn.Module):
         if bool((srt[:, 1:] == srt[:, :-1]).any()):
             raise ValueError('mask_idx holds a duplicate patch index inside a record')
 
-    def forward(self, sample_values, mask_idx):
+    def check_varlen_input(self, sample_values, mask_idx, lengths, mask_counts):
+        """validate a batch of records of unequal length before anything launches (host work only) -> its MaskedVarlenBatch, or None for
+        the rectangular call (no lengths, no mask_counts, a (B, C, L) batch).  ValueError: `engine.check_masked_varlen_input`"""
+        enc, c = self.encoder, self.encoder.config
+        return check_masked_varlen_input(sample_values, mask_idx, lengths, mask_counts, C=c.num_channels, P=c.patch_size, max_len=c.max_signal_length,
+                                         dtype=enc.compute_dtype, fp8=enc.fp8_linear, input_transform=getattr(enc, '_input_transform', None))
+
+    def forward(self, sample_values, mask_idx, **varlen):
+        """sample_values (B, C, L) with mask_idx (B, m): the rectangular pass over full-width records.  With the keyword arguments lengths=
+        (B,) and mask_counts= (B,): records of unequal length, mask_idx flat -- sample_values (B, C, L') (samples past lengths[b] are never
+        read into a result) on either engine, or a ragged (C, S) batch (the records concatenated along time: no padded row in any buffer) on
+        the bf16 engine.  The two are keyword-only and collected here rather than named in the signature: tests/test_varlen.py pins the
+        positional signature of this method to (sample_values, mask_idx)."""
+        unknown = set(varlen) - {'lengths', 'mask_counts'}
+        if unknown:
+            raise TypeError(f'MaskedEcgVit.forward() got an unexpected keyword argument {sorted(unknown)[0]!r}')
+        lengths, mask_counts = varlen.get('lengths'), varlen.get('mask_counts')
+        geo = self.check_varlen_input(sample_values, mask_idx, lengths, mask_counts)
         if not sample_values.is_cuda:
             raise RuntimeError('MaskedEcgVit (HIP) runs on an MI355X device only (no CPU fallback)')
-        if sample_values.dim() != 3:
-            raise ValueError('MaskedEcgVit takes (B, C, L) batches of full-width records: ragged (C, S) batches are not supported')
         x = sample_values.contiguous().float()
+        if geo is not None:
+            idx = geo.as_rectangular(self.encoder.config.max_signal_length)
+            if idx is None:
+                loss, pred = _MaskedFunction.apply(self, x, geo, *self.encoder._param_list)
+                return ModelOutput(loss=loss, logits=pred)
+            # every record fills max_signal_length with the same count: the rectangular pass itself (logits stay (sum m_b, C*P))
+            loss, pred = _MaskedFunction.apply(self, x, idx.to(x.device), *self.encoder._param_list)
+            return ModelOutput(loss=loss, logits=pred.reshape(geo.m, -1))
         self.check_mask_indices(mask_idx, x.shape[0])
         idx = mask_idx.to(device=x.device, dtype=torch.int32).contiguous()
         loss, pred = _MaskedFunction.apply(self, x, idx, *self.encoder._param_list)

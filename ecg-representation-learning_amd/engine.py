@@ -226,6 +226,160 @@ def ragged_slice(x, lengths, b0, b1):
     return x[:, s0:s1].contiguous(), lengths[b0:b1]
 
 
+class MaskedVarlenBatch:
+    """Token geometry of a masked pass over B records of unequal length -- no CLS row: record b holds n_b = lengths[b] / P patch tokens.
+      width None -- packed rows (a ragged (C, S) batch): tok_off = exclusive prefix sum of n_b, M = S / P
+      width L'   -- padded rows (a (B, C, L') batch with lengths): tok_off[b] = b n_pad, n_pad = L' / P, M = B n_pad
+      n_tok, tok_off, order, n_cls -- int32 [B] on `device`, staged through pinned memory in one copy: order = the records by falling n_b
+               (ties by record index; `ecgvit_mask_embed_varlen_bwd`), n_cls = n_b + 1 (what `ecgvit_patch_gather_varlen` takes)
+      N -- the widest record's patches;  S -- valid samples;  lengths -- the validated sample counts, int64 on the host
+      counts, m -- the records' mask counts (int64, host) and their sum;  rows -- int32 [m] on `device`: the masked rows tok_off[b] + idx
+    Everything is computed on the host from host data: a step fed host tensors reads nothing back from the device."""
+
+    def __init__(self, lengths, P, device, width=None):
+        t = lengths
+        B = t.shape[0]
+        n = t // P
+        self.n_pad = 0 if width is None else width // P
+        tok_off = torch.cumsum(n, 0) - n if width is None else torch.arange(B, dtype=torch.int64) * self.n_pad
+        order = torch.sort(n, descending=True, stable=True).indices
+        self.lengths, self.P, self.device, self.width = t, P, device, width
+        self.n_host, self.off_host = n, tok_off
+        self.S, self.N = int(t.sum()), int(n.max())
+        self.M = int(n.sum()) if width is None else B * self.n_pad
+        pack = _stage(torch.stack([n, tok_off, order, n + 1]).to(torch.int32), device)
+        self.n_tok, self.tok_off, self.order, self.n_cls = pack[0], pack[1], pack[2], pack[3]
+        self.counts, self.m, self.rows = None, 0, None
+
+    @property
+    def B(self):
+        return self.lengths.shape[0]
+
+    def set_mask(self, idx, counts):
+        """idx: validated record-local indices (int64, host, flat), counts (B,) int64 host (`check_mask_varlen`) -> the masked rows"""
+        self.counts, self.m = counts, int(idx.numel())
+        self.idx_host = idx
+        self.rows = _stage((torch.repeat_interleave(self.off_host, counts) + idx).to(torch.int32), self.device)
+        return self
+
+    def as_rectangular(self, max_len):
+        """the mask as (B, m) int32 host indices when this batch is one the rectangular pass runs -- padded rows, every record max_len samples,
+        one mask count -- else None"""
+        if self.width != max_len or int(self.lengths.min()) != max_len or int(self.counts.min()) != int(self.counts.max()):
+            return None
+        return self.idx_host.view(self.B, -1).to(torch.int32)
+
+    def records(self, b0, b1):
+        """records b0 .. b1 - 1 with their mask indices: ((s0, s1) = their sample range in a ragged batch, their MaskedVarlenBatch)"""
+        s0, s1 = int(self.lengths[:b0].sum()), int(self.lengths[:b1].sum())
+        g = MaskedVarlenBatch(self.lengths[b0:b1], self.P, self.device, self.width)
+        if self.counts is not None:
+            k0, k1 = int(self.counts[:b0].sum()), int(self.counts[:b1].sum())
+            g.set_mask(self.idx_host[k0:k1], self.counts[b0:b1])
+        return (s0, s1), g
+
+
+def _stage(t, device):
+    """a small host tensor -> `device` through pinned memory (a pageable copy would block the host until the stream has drained)"""
+    if torch.device(device).type != 'cuda':
+        return t
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def _host_ints(t, what, shape_note):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f'{what} must be {shape_note}, got {type(t).__name__}')
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f'{what} must be an integer tensor, got {t.dtype}')
+    return t.detach().to('cpu', torch.int64)   # (a blocking read for a device tensor)
+
+
+def check_masked_lengths(lengths, P, max_len, B=None, width=None, S=None):
+    """per-record sample counts of a masked batch -> int64 host tensor: a (B,) integer tensor of positive multiples of P, at most `width` (the
+    padded form) / max_len, summing to S (the ragged form); anything else raises ValueError"""
+    if lengths is None:
+        raise ValueError('a ragged (C, S) batch needs lengths: the (B,) per-record sample counts')
+    t = _host_ints(lengths, 'lengths', 'a (B,) integer tensor')
+    if t.dim() != 1 or t.shape[0] < 1 or (B is not None and t.shape[0] != B):
+        raise ValueError(f'lengths must have shape (batch={B if B is not None else "B"},), got {tuple(lengths.shape)}')
+    lo, hi = int(t.min()), int(t.max())
+    if lo <= 0:
+        raise ValueError(f'lengths must be positive (got {lo})')
+    if width is not None and hi > width:
+        raise ValueError(f'lengths must not exceed the batch width {width} (got {hi})')
+    if hi > max_len:
+        raise ValueError(f'lengths must not exceed max_signal_length={max_len} (got {hi})')
+    if bool((t % P != 0).any()):
+        raise ValueError(f'lengths must be multiples of patch_size={P}')
+    if S is not None and int(t.sum()) != S:
+        raise ValueError(f'lengths must sum to the ragged batch width S={S} (got {int(t.sum())})')
+    return t
+
+
+def check_mask_varlen(mask_idx, mask_counts, n):
+    """record-local mask indices of records with n[b] patches (n: int64 host tensor) -> (idx, counts) as int64 host tensors.  mask_idx: 1-D
+    integer tensor, record 0's indices first; mask_counts: (B,) integer tensor with 1 <= m_b <= n_b summing to mask_idx.numel(); the indices
+    of a record distinct and in [0, n_b).  Anything else raises ValueError before any launch (the gather / scatter kernels index unchecked).
+    Host tensors are checked on the host; device tensors cost blocking reads."""
+    B = n.shape[0]
+    c = _host_ints(mask_counts, 'mask_counts', 'a (B,) integer tensor')
+    if c.dim() != 1 or c.shape[0] != B:
+        raise ValueError(f'mask_counts must have shape (batch={B},), got {tuple(mask_counts.shape)}')
+    if not isinstance(mask_idx, torch.Tensor) or mask_idx.dim() != 1:
+        raise ValueError('with lengths, mask_idx must be a 1-D integer tensor of record-local patch indices (record 0\'s first), not (B, m): '
+                         f'got {tuple(getattr(mask_idx, "shape", ()))}')
+    i = _host_ints(mask_idx, 'mask_idx', 'a 1-D integer tensor')
+    if int(c.min()) < 1 or bool((c > n).any()):
+        raise ValueError('mask_counts must satisfy 1 <= m_b <= n_b (the patches of record b)')
+    if int(c.sum()) != i.numel():
+        raise ValueError(f'mask_counts must sum to mask_idx.numel()={i.numel()} (got {int(c.sum())})')
+    rec = torch.repeat_interleave(torch.arange(B, dtype=torch.int64), c)
+    if int(i.min()) < 0 or bool((i >= n[rec]).any()):
+        raise ValueError('mask_idx entries must lie in [0, n_b) of their record')
+    key = torch.sort(rec * (int(n.max()) + 1) + i).values
+    if bool((key[1:] == key[:-1]).any()):
+        raise ValueError('mask_idx holds a duplicate patch index inside a record')
+    return i, c
+
+
+def check_masked_varlen_input(x, mask_idx, lengths, mask_counts, *, C, P, max_len, dtype, fp8, input_transform):
+    """validate a masked batch of records of unequal length before anything launches -> MaskedVarlenBatch with its mask set, or None for
+    the rectangular call ((B, C, L) without lengths / mask_counts: `forward_masked`).  Host work only: needs no device.  x: (B, C, L') with lengths (the padded form) or
+    a ragged (C, S) batch (bf16 engine); mask_idx / mask_counts: `check_mask_varlen`.  lengths may already be the MaskedVarlenBatch."""
+    if isinstance(lengths, MaskedVarlenBatch):
+        return lengths
+    ragged = isinstance(x, torch.Tensor) and x.dim() == 2
+    if lengths is None and mask_counts is None and not ragged:
+        return None
+    what = 'ragged batches' if ragged else 'per-record lengths'
+    if input_transform is not None:
+        raise ValueError(f'{what} are not supported with a fused input transform (its TimeEndPad pads every record)')
+    if fp8:
+        raise ValueError(f'{what} are not supported with fp8_linear')
+    if ragged and dtype != torch.bfloat16:
+        raise ValueError('ragged batches need the bf16 engine (the f32 parity path materialises padded (B, h, N, N) scores)')
+    if not isinstance(x, torch.Tensor) or x.dim() not in (2, 3) or x.shape[-2] != C:
+        raise ValueError(f'a masked batch is (B, {C}, L) or a ragged ({C}, S) tensor, got {tuple(getattr(x, "shape", ()))}')
+    if lengths is None:
+        if ragged:
+            raise ValueError('a ragged (C, S) batch needs lengths: the (B,) per-record sample counts')
+        raise ValueError('mask_counts needs lengths: the masked objective takes (B, m) mask_idx alone, or lengths with flat mask_idx and mask_counts')
+    if mask_counts is None:
+        raise ValueError('lengths needs mask_counts: with per-record lengths mask_idx is flat (record-local indices, record 0\'s first) and '
+                         'mask_counts (B,) says how many belong to each record')
+    if ragged:
+        t = check_masked_lengths(lengths, P, max_len, S=x.shape[1])
+        width = None
+    else:
+        width = x.shape[2]
+        if not 0 < width <= max_len or width % P:
+            raise ValueError(f'a batch of {width} samples per record: must be a positive multiple of patch_size={P} '
+                             f'and at most max_signal_length={max_len}')
+        t = check_masked_lengths(lengths, P, max_len, B=x.shape[0], width=width)
+    idx, counts = check_mask_varlen(mask_idx, mask_counts, t // P)
+    return MaskedVarlenBatch(t, P, x.device, width).set_mask(idx, counts)
+
+
 class VitEngine:
     """Forward / backward of EcgVit for one activation dtype (torch.float32 = parity path, torch.bfloat16 =
     throughput path). Caller provides the flat buffers; all activations are allocated here, once per batch size."""
@@ -285,7 +439,7 @@ class VitEngine:
         self.aux8 = dtype == torch.bfloat16 if saved_ffn_e4m3 is None else bool(saved_ffn_e4m3)
         self.B = None
         self._alloc_key = None
-        self._pool, self._pool_group, self._pool_B = None, None, 0
+        self._pool, self._pool_B = None, 0
         self.T = self.N
         self.act = None
         self.P32 = self.G32 = self.W = None
@@ -512,24 +666,22 @@ class VitEngine:
         else:
             self._gemm(GEMM_NN, dY, self.W[name], dX, M, kin, nout, nout, kin, kin, **kw)
 
-    def _alloc(self, B, masked=False, m=0, rows=None):
-        """Activation slabs for a pass over B records (rows: the packed token rows of a ragged batch; None = B x tokens per record).  Every slab's leading dimension is proportional to B, so ONE pool serves every batch size
-        through prefix views: a loop that alternates train (B = 512) and eval (B = 64) batches, or ends an epoch on a short batch, re-slices instead
-        of freeing and re-requesting ~40 GB (base) from the allocator on each switch.  The pool grows PER SLAB and never shrinks inside a token
-        geometry; it is dropped only when the objective changes (supervised <-> masked, or another mask count)."""
-        key = (B, masked, m, self._aux8(rows if rows is not None else B * (self.n if masked else self.N)), self.N, rows)
+    def _alloc(self, B, masked=False, m=0, rows=None, mrows=None):
+        """Activation slabs for a pass over B records (rows: the packed token rows of a ragged batch; None = B x tokens per record; mrows: the
+        masked rows of a masked pass over records of unequal length, B x m otherwise).  Every slab's leading dimension is proportional to B, so
+        ONE pool serves every batch size through prefix views: a loop that alternates train (B = 512) and eval (B = 64) batches, or ends an epoch
+        on a short batch, re-slices instead of freeing and re-requesting ~40 GB (base) from the allocator on each switch.  The pool grows PER SLAB
+        and never shrinks; slabs are shared by name across objectives and row layouts, so a loop that alternates supervised, masked, padded and
+        ragged passes re-slices too (the slabs only one of them names -- the pruned block's, the masked head's -- stay in the pool)."""
+        key = (B, masked, m, self._aux8(rows if rows is not None else B * (self.n if masked else self.N)), self.N, rows, mrows)
         if self._alloc_key == key and self.act is not None:
             return
         self._alloc_key = key
         self.T = self.n if masked else self.N   # tokens per record: no CLS row in the masked-pretrain trunk
-        spec = self._act_spec(B, masked, m, rows)
+        spec = self._act_spec(B, masked, m, rows, mrows=mrows)
         # a ragged pass reserves what a padded pass of the same B at max_signal_length takes: steps of equal B and any S then re-slice the
         # same slabs (and never hold more than that padded pass would)
-        reserve = self._act_spec(B, masked, m, N=self.N_max) if rows is not None else {}
-        group = (masked, m)
-        if self._pool_group != group:
-            self.act = self._pool = None           # another token geometry: nothing of the old pool fits
-            self._pool_group, self._pool_B = group, 0
+        reserve = self._act_spec(B, masked, m, N=self.n_max if masked else self.N_max, mrows=mrows) if rows is not None else {}
         pool = self._pool if self._pool is not None else {}
         self._pool = pool
         self._pool_B = max(B, self._pool_B)
@@ -564,16 +716,16 @@ class VitEngine:
         a['layers'] = layers
         self.act, self.B = a, B
 
-    def _act_spec(self, B, masked, m, rows=None, N=None):
+    def _act_spec(self, B, masked, m, rows=None, N=None, mrows=None):
         """name -> (shape, dtype) of every activation / scratch slab of a pass over B records (layer slabs as 'L{i}.{name}'); rows: the packed
-        token rows of a ragged batch; N: tokens per record (default: the current pass's)"""
+        token rows of a ragged batch; N: tokens per record (default: the current pass's); mrows: the masked rows (default B x m)"""
         T = self.dtype
         f32, u8 = torch.float32, torch.uint8
         if N is None:
             N = self.n if masked else self.N
         M, Mp = B * N, B * (N if masked else N - 1)
         if rows is not None:
-            M, Mp = rows, rows - B
+            M, Mp = rows, rows - (0 if masked else B)   # (no CLS rows in the masked trunk)
         d, f, h = self.d, self.f, self.h
         sp = OrderedDict()
         sp.update(patches=((Mp, self.CP), T), tok=((Mp, d), T), x0=((M, d), T))
@@ -608,8 +760,9 @@ class VitEngine:
             for (mm, nn) in ((d, f), (f, d), (d, d), (3 * d, d), (d, self.CP)):
                 ws = max(ws, hip.gemm_workspace_bytes(GEMM_TN, T, mm, nn, M))
         if masked:
-            sp.update(flag=((Mp,), u8), rows=((B * m, d), T), pred=((B * m, self.CP), T), target=((B * m, self.CP), T),
-                      dpred=((B * m, self.CP), T), drows=((B * m, d), T), dmasked=((Mp, d), T), mloss=((1,), f32), l1part=((1024,), f32))
+            Rm = B * m if mrows is None else mrows
+            sp.update(flag=((Mp,), u8), rows=((Rm, d), T), pred=((Rm, self.CP), T), target=((Rm, self.CP), T),
+                      dpred=((Rm, self.CP), T), drows=((Rm, d), T), dmasked=((Mp, d), T), mloss=((1,), f32), l1part=((1024,), f32))
         sp['ws'] = ((ws,), u8)
         if self.fp8:
             sp['q8'] = ((M * max(f, 3 * d),), u8)   # one quantised operand at a time
@@ -920,7 +1073,7 @@ class VitEngine:
         mask_token; + pos[1:n+1]; trunk on n tokens (no CLS); masked rows -> Linear(d, C*P); L1 vs the raw masked patches.
         x (B,C,L) f32; idx (B,m) int32 distinct patch indices per record. Returns (pred (B*m, C*P), loss (1,) f32)."""
         B, m = idx.shape
-        self._set_width(self.L_max)   # the masked objective runs full-width records only
+        self._set_width(self.L_max)   # (B, m) indices: full-width records; records of unequal length go through forward_masked_varlen
         assert idx.dtype == torch.int32 and idx.is_contiguous() and 0 < m <= self.n
         self._alloc(B, masked=True, m=m)
         a, W, T = self.act, self.W, hip.code(self.dtype)
@@ -947,6 +1100,49 @@ class VitEngine:
                                        self.CP, T, st), 'l1_loss')
         return a['pred'], a['mloss']
 
+    def check_masked_varlen_input(self, x, mask_idx, lengths, mask_counts):
+        """`check_masked_varlen_input` for this engine"""
+        return check_masked_varlen_input(x, mask_idx, lengths, mask_counts, C=self.C, P=self.P, max_len=self.L_max, dtype=self.dtype, fp8=self.fp8,
+                                         input_transform=self.input_transform)
+
+    def forward_masked_varlen(self, x, geo, training=True, seed=0):
+        """`forward_masked` over records of unequal length (`MaskedVarlenBatch`, from `check_masked_varlen_input`): record b gives what it
+        gives alone at its own length (dropout 0); the loss is the mean over every masked element of the batch.  x: the ragged (C, S) batch
+        (packed rows: every row-wise kernel runs over the M = S / P rows, attention per record on the packed rows) or (B, C, L') (padded rows:
+        the rows past a record's length are exact zeros, its keys there never attended to, its samples there never read).
+        Returns (pred (sum m_b, C*P), loss (1,) f32)."""
+        B, M, mt, packed = geo.B, geo.M, geo.m, geo.n_pad == 0
+        assert x.dtype == torch.float32 and x.is_contiguous() and geo.rows is not None
+        self._set_width((geo.N if packed else geo.n_pad) * self.P)
+        self._alloc(B, masked=True, rows=M if packed else None, mrows=mt)
+        a, W, T = self.act, self.W, hip.code(self.dtype)
+        l, st = lib(), stream()
+        d = self.d
+        ph = self.p_hidden if training else 0.0
+        pe = self.p_emb if training else 0.0
+        self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, masked=True, idx=geo.rows, m=mt, training=training, geo=geo, lengths=True,
+                          ntok=None if packed else geo.n_tok, ragged=geo if packed else None)
+        if packed:   # the uniform gather over the concatenation: patch row off_b / P + j is patch j of record b
+            check(l.ecgvit_patch_gather(ptr(x), ptr(a['patches']), 1, self.C, geo.S, self.P, self.CP, T, st), 'patch_gather')
+        else:        # zero patches past each record's length (n_cls = n_b + 1: the kernel's count includes a CLS token)
+            check(l.ecgvit_patch_gather_varlen(ptr(x), ptr(a['patches']), ptr(geo.n_cls), B, self.C, self.L, self.P, self.CP, T, st), 'patch_gather_varlen')
+        self._gemm(GEMM_NT, a['patches'], W['vit.to_patch_embedding.1.weight'], a['tok'], M, d, self.CP, self.CP, self.CP, d, epilogue=EPI_BIAS,
+                   bias=self.P32['vit.to_patch_embedding.1.bias'])
+        check(l.ecgvit_mask_embed_varlen_fwd(ptr(a['tok']), ptr(self.P32['pretrain.mask_token']), ptr(self.P32['vit.pos_embedding']), ptr(geo.rows),
+                                             ptr(a['x0']), ptr(a['flag']), ptr(geo.n_tok), ptr(geo.tok_off), B, geo.N, geo.n_pad, M, mt, d, T, st),
+              'mask_embed_varlen_fwd')
+        if pe > 0:
+            self._drop_apply(a['x0'], a['x0'], M * d, pe, seed + 1)
+        X = self._trunk_fwd(B, ph, seed)
+        self.saved['xL'] = X
+        check(l.ecgvit_gather_rows(ptr(X), ptr(geo.rows), ptr(a['rows']), 1, M, mt, d, d, d, T, st), 'gather_rows')
+        self._gemm(GEMM_NT, a['rows'], W['pretrain.to_pixels.weight'], a['pred'], mt, self.CP, d, d, d, self.CP, epilogue=EPI_BIAS,
+                   bias=self.P32['pretrain.to_pixels.bias'])
+        check(l.ecgvit_gather_rows(ptr(a['patches']), ptr(geo.rows), ptr(a['target']), 1, M, mt, self.CP, self.CP, self.CP, T, st), 'gather_rows')
+        check(l.ecgvit_l1_loss_fwd_bwd(ptr(a['pred']), ptr(a['target']), ptr(a['mloss']), ptr(a['dpred']), None, ptr(a['l1part']), mt, self.CP,
+                                       self.CP, T, st), 'l1_loss')
+        return a['pred'], a['mloss']
+
     def backward_masked(self, gscalar=None, tiles_per_workgroup=0, trainable=None):
         """loss + every gradient of the masked objective (the L1 kernel produces loss and dpred in one pass).
         tiles_per_workgroup, trainable: as `backward`"""
@@ -966,8 +1162,11 @@ class VitEngine:
         B, m, idx, pe, seed = sv['B'], sv['m'], sv['idx'], sv['pe'], sv['seed']
         d, n = self.d, self.n
         G = self.G32
+        geo = sv.get('geo')   # records of unequal length: idx = the masked rows of the pass, m = their count
+        M = self._pass_rows(B)
+        Rm = m if geo is not None else B * m
         if gscalar is not None:
-            check(l.ecgvit_l1_loss_fwd_bwd(ptr(a['pred']), ptr(a['target']), ptr(a['mloss']), ptr(a['dpred']), ptr(gscalar), ptr(a['l1part']), B * m,
+            check(l.ecgvit_l1_loss_fwd_bwd(ptr(a['pred']), ptr(a['target']), ptr(a['mloss']), ptr(a['dpred']), ptr(gscalar), ptr(a['l1part']), Rm,
                                            self.CP, self.CP, T, st), 'l1_loss')
         # the classification head does not take part: its gradients are zero for this objective -- known at once, so its bucket is
         # released FIRST and its exchange overlaps the whole backward pass (buckets complete in the order head, layers L-1..0, embed,
@@ -975,24 +1174,33 @@ class VitEngine:
         for k in ('vit.mlp_head.0.weight', 'vit.mlp_head.0.bias', 'vit.mlp_head.1.weight', 'vit.mlp_head.1.bias', 'vit.cls_token'):
             G[k].zero_()
         self._ready('head')
-        self._colsum(a['dpred'], self.CP, G['pretrain.to_pixels.bias'], B * m, self.CP)
-        self._wgrad(a['dpred'], a['rows'], 'pretrain.to_pixels.weight', self.CP, d, B * m)
+        self._colsum(a['dpred'], self.CP, G['pretrain.to_pixels.bias'], Rm, self.CP)
+        self._wgrad(a['dpred'], a['rows'], 'pretrain.to_pixels.weight', self.CP, d, Rm)
         if not self._reach(0):
             return
-        self._gemm(GEMM_NN, a['dpred'], W['pretrain.to_pixels.weight'], a['drows'], B * m, d, self.CP, self.CP, d, d)
+        self._gemm(GEMM_NN, a['dpred'], W['pretrain.to_pixels.weight'], a['drows'], Rm, d, self.CP, self.CP, d, d)
         dX = a['dxa']
         dX.zero_()
-        check(l.ecgvit_scatter_rows(ptr(a['drows']), ptr(idx), ptr(dX), B, n, m, d, d, d, T, st), 'scatter_rows')
+        if geo is not None:
+            check(l.ecgvit_scatter_rows(ptr(a['drows']), ptr(idx), ptr(dX), 1, M, m, d, d, d, T, st), 'scatter_rows')
+        else:
+            check(l.ecgvit_scatter_rows(ptr(a['drows']), ptr(idx), ptr(dX), B, n, m, d, d, d, T, st), 'scatter_rows')
         dX = self._trunk_bwd(dX, a['dxb'])
         if dX is None or not self._reach(self._stage(-1, 0)):
             return
         if pe > 0:
-            self._drop_apply(dX, dX, B * n * d, pe, seed + 1)
-        check(l.ecgvit_mask_embed_bwd(ptr(dX), ptr(a['flag']), ptr(a['dtok']), ptr(a['dmasked']), ptr(G['vit.pos_embedding']), B, n, d,
-                                      T, st), 'mask_embed_bwd')
-        self._colsum(a['dmasked'], d, G['pretrain.mask_token'], B * n, d)
-        self._colsum(a['dtok'], d, G['vit.to_patch_embedding.1.bias'], B * n, d)
-        self._wgrad(a['dtok'], a['patches'], 'vit.to_patch_embedding.1.weight', d, self.CP, B * n)
+            self._drop_apply(dX, dX, M * d, pe, seed + 1)
+        if geo is not None:
+            check(l.ecgvit_mask_embed_varlen_bwd(ptr(dX), ptr(a['flag']), ptr(a['dtok']), ptr(a['dmasked']), ptr(G['vit.pos_embedding']),
+                                                 ptr(geo.n_tok), ptr(geo.tok_off), ptr(geo.order), B, geo.N, geo.n_pad, d, T, st), 'mask_embed_varlen_bwd')
+            if n < self.n_max:   # the kernel wrote position rows 0 .. n (n = the pass's patches per record); the rest take no part
+                G['vit.pos_embedding'].view(-1, d)[1 + n:].zero_()
+        else:
+            check(l.ecgvit_mask_embed_bwd(ptr(dX), ptr(a['flag']), ptr(a['dtok']), ptr(a['dmasked']), ptr(G['vit.pos_embedding']), B, n, d,
+                                          T, st), 'mask_embed_bwd')
+        self._colsum(a['dmasked'], d, G['pretrain.mask_token'], M, d)
+        self._colsum(a['dtok'], d, G['vit.to_patch_embedding.1.bias'], M, d)
+        self._wgrad(a['dtok'], a['patches'], 'vit.to_patch_embedding.1.weight', d, self.CP, M)
         self._ready('embed')
         self._ready('pretrain')
 

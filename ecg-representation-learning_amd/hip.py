@@ -110,6 +110,8 @@ SIGNATURES = {
     'ecgvit_transpose_bf16_batched': (c_int, [_P, _P, _P, _I, _L, _P]),
     'ecgvit_mask_embed_finish': (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'ecgvit_mask_embed_bwd': (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'ecgvit_mask_embed_varlen_fwd': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _I, _I, _I, _P]),
+    'ecgvit_mask_embed_varlen_bwd': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'ecgvit_gather_rows': (c_int, [_P, _P, _P, _I, _I, _I, _L, _L, _L, _I, _P]),
     'ecgvit_scatter_rows': (c_int, [_P, _P, _P, _I, _I, _I, _L, _L, _L, _I, _P]),
     'ecgvit_l1_loss_fwd_bwd': (c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _L, _I, _P]),

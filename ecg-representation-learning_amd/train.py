@@ -231,13 +231,19 @@ class HipTrainStep:
         eng.on_grads_ready = None
         return 0
 
-    def step_masked(self, sample_values, mask_idx, micro_batch_size=None):
+    def step_masked(self, sample_values, mask_idx, micro_batch_size=None, lengths=None, mask_counts=None):
         """the same fused step for the masked pre-train objective; `self.model` must be a MaskedEcgVit.
-        micro_batch_size: as `step` (None: the default given in args); the loss is the whole batch's mean"""
+        micro_batch_size: as `step` (None: the default given in args); the loss is the whole batch's mean.
+        lengths, mask_counts: records of unequal length (MaskedEcgVit.forward) -- sample_values (B, C, L') or a ragged (C, S) batch, mask_idx
+        flat; micro-batches are then record ranges (a ragged one a ragged batch of its own), pass j weighted by its share of the masked
+        patches.  Returns (loss, reconstruction (sum m_b, C*P))."""
         mb = self._micro_batch_size(micro_batch_size)
-        if sample_values.dim() != 3:
-            raise ValueError('step_masked takes (B, C, L) batches of full-width records: ragged (C, S) batches are not supported')
         wrapper, model = self.model, self.model.encoder
+        geo = wrapper.check_varlen_input(sample_values, mask_idx, lengths, mask_counts)   # host work only, before anything launches
+        if geo is not None:
+            rect = geo.as_rectangular(model.config.max_signal_length)
+            if rect is not None:   # every record full-width with one mask count: the rectangular step itself
+                mask_idx, geo = rect, None
         if not model.training:
             raise RuntimeError('train step on a model in eval mode')
         self._read_flags(model)
@@ -245,13 +251,18 @@ class HipTrainStep:
         self._apply_flags(model)
         self._raise_if_flagged()
         eng = model._engine()
-        if mb is not None and mb < sample_values.shape[0]:
+        if geo is not None and mb is not None and mb < geo.B:
+            return self._step_masked_varlen_micro(model, eng, sample_values.contiguous().float(), geo, mb)
+        if geo is None and mb is not None and mb < sample_values.shape[0]:
             return self._step_masked_micro(wrapper, model, eng, sample_values, mask_idx, mb)
         seed = self._dropout_seed(model)
         x = sample_values.contiguous().float()
-        wrapper.check_mask_indices(mask_idx, x.shape[0])
-        idx = self._device_mask_idx(mask_idx, x.device)
-        pred, loss = eng.forward_masked(x, idx, training=True, seed=seed)
+        if geo is not None:
+            pred, loss = eng.forward_masked_varlen(x, geo, training=True, seed=seed)
+        else:
+            wrapper.check_mask_indices(mask_idx, x.shape[0])
+            idx = self._device_mask_idx(mask_idx, x.device)
+            pred, loss = eng.forward_masked(x, idx, training=True, seed=seed)
         model._fwd_id += 1
         tpw = self._arm_overlap(model)
         try:
@@ -437,6 +448,37 @@ class HipTrainStep:
             hip.check(l.ecgvit_grad_accumulate(loss.data_ptr(), mloss.data_ptr(), one_span.data_ptr(), 1, 1,
                                                hip.ACC_INIT if j == 0 else hip.ACC_ADD, wj, st), 'grad_accumulate')
             gs = self._const(x.device, ('upstream', wj), [wj], torch.float32)
+            self._micro_backward(model, eng, j, j == len(starts) - 1,
+                                 lambda tpw: eng.backward_masked(gscalar=gs, tiles_per_workgroup=tpw, trainable=self._trainable))
+        self._update(model)
+        self.last_loss = loss
+        return loss, pred_all
+
+    def _step_masked_varlen_micro(self, model, eng, x, geo, mb):
+        """`step_masked` of records of unequal length over consecutive ranges of mb records, each with its own mask indices (cut by the
+        counts' prefix sums; a ragged batch by `MaskedVarlenBatch.records`, host offsets only): pass j's L1 mean enters the loss and the
+        upstream gradient with weight (its masked patches) / (the batch's), so the sum is the whole batch's mean"""
+        B = geo.B
+        l, st = hip.lib(), hip.stream()
+        loss = torch.empty(1, device=x.device, dtype=torch.float32)
+        one_span = self._const(x.device, 'one span', [[0, 1, 0]], torch.int64)
+        starts = list(range(0, B, mb))
+        parts = [geo.records(s, min(s + mb, B)) for s in starts]
+        weights = [g.m / geo.m for _, g in parts]
+        up = torch.tensor(weights, dtype=torch.float32).pin_memory().to(x.device, non_blocking=True)   # the upstream gradients, one copy
+        pred_all, k0 = None, 0
+        for j, (s, ((s0, s1), g)) in enumerate(zip(starts, parts)):
+            seed = self._dropout_seed(model)
+            xs = x[:, s0:s1].contiguous() if x.dim() == 2 else x[s:s + g.B]
+            pred, mloss = eng.forward_masked_varlen(xs, g, training=True, seed=seed)
+            model._fwd_id += 1
+            if pred_all is None:
+                pred_all = torch.empty((geo.m,) + tuple(pred.shape[1:]), device=x.device, dtype=pred.dtype)
+            pred_all[k0:k0 + g.m].copy_(pred)
+            k0 += g.m
+            hip.check(l.ecgvit_grad_accumulate(loss.data_ptr(), mloss.data_ptr(), one_span.data_ptr(), 1, 1,
+                                               hip.ACC_INIT if j == 0 else hip.ACC_ADD, weights[j], st), 'grad_accumulate')
+            gs = up[j:j + 1]
             self._micro_backward(model, eng, j, j == len(starts) - 1,
                                  lambda tpw: eng.backward_masked(gscalar=gs, tiles_per_workgroup=tpw, trainable=self._trainable))
         self._update(model)

@@ -387,6 +387,20 @@ int ecgvit_mask_embed_finish(const void *tok, const float *mask_token, const flo
  * mask-token gradient), dpos[1+p] = sum_b dX[b*n+p], dpos[0] = 0.  flag_ws as written by ecgvit_mask_embed_finish. */
 int ecgvit_mask_embed_bwd(const void *dX, const void *flag_ws, void *dtok, void *dmasked, float *dpos, int B, int n, int d,
                           int dtype, void *stream);
+/* The same pair for records of unequal length.  Record b holds n_tok[b] >= 1 patches in the rows tok_off[b] .. tok_off[b] + n_tok[b] - 1
+ * of tok / X / dX / dtok / dmasked (n_tok, tok_off: int32 [B] on the device); N = the largest n_tok; M = all rows.  Two row layouts:
+ *   packed  n_pad == 0: tok_off = the exclusive prefix sum of n_tok, M = sum n_tok; no other row exists
+ *   padded  n_pad >= N: tok_off[b] = b * n_pad, M = B * n_pad; rows past n_tok[b] are never read and written as exact zeros (X, dtok, dmasked)
+ * forward: X[row] = (masked ? mask_token : tok[row]) + pos[1 + j] for patch j of its record; row_idx (int32 [m_total], device) = the masked
+ * rows of the pass (tok_off[b] + record-local index: distinct, in [0, M); others are ignored); flag_ws: caller scratch of M bytes.
+ * backward: dtok / dmasked split by the flag; dpos[1 + j] = sum over the records with n_tok > j of their row j, rows 0 and those past the
+ * widest record (up to 1 + n_pad in the padded layout, 1 + N packed) exact zeros; summed in a fixed order (bit-identical from launch to
+ * launch).  order: int32 [B] on the device, the records by falling n_tok (ties by rising record index).  B <= 65535. */
+int ecgvit_mask_embed_varlen_fwd(const void *tok, const float *mask_token, const float *pos, const int32_t *row_idx, void *X, void *flag_ws,
+                                 const int32_t *n_tok, const int32_t *tok_off, int B, int N, int n_pad, int64_t M, int m_total, int d,
+                                 int dtype, void *stream);
+int ecgvit_mask_embed_varlen_bwd(const void *dX, const void *flag_ws, void *dtok, void *dmasked, float *dpos, const int32_t *n_tok,
+                                 const int32_t *tok_off, const int32_t *order, int B, int N, int n_pad, int d, int dtype, void *stream);
 /* gather rows: out[b*m + k] = in[b*n + idx[b,k]] */
 int ecgvit_gather_rows(const void *in, const int32_t *idx, void *out, int B, int n, int m, int64_t width, int64_t ld_in,
                        int64_t ld_out, int dtype, void *stream);

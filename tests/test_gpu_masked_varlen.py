@@ -1,0 +1,415 @@
+"""-m gpu: the masked pre-train objective over records of unequal length (`lengths=` + flat `mask_idx` + `mask_counts`; padded (B, C, L') and
+ragged (C, S) batches) through the kernels, the engine, MaskedEcgVit and HipTrainStep.step_masked.
+
+The reference of every model case is the CPU oracle run record by record: OracleMaskedEcgVit on x[b:b+1, :, :lengths[b]] with the record's
+indices as (1, m_b); loss = sum_b (m_b / sum m) loss_b, one backward through that sum, reconstruction = cat(pred_b).  Bounds are those of
+test_gpu_varlen.py (TOL), test_gpu_configs.py (layer shape) and test_gpu_micro_batch.py (micro-batches), reused, not re-chosen.
+"""
+import pytest
+import torch
+
+from hiputil import rel_err
+from oracle import vit_oracle as O
+import ecg_representation_learning_amd as E
+from ecg_representation_learning_amd.engine import MaskedVarlenBatch
+from ecg_representation_learning_amd.hip import lib, check, ptr, stream, code
+
+pytestmark = pytest.mark.gpu
+F32, BF16 = torch.float32, torch.bfloat16
+TOL = {F32: (1e-4, 1e-4), BF16: (3e-2, 6e-2)}   # test_gpu_varlen.TOL: (reconstruction / loss, worst per-tensor gradient)
+MIX = torch.tensor([1000, 4, 400, 596])
+ARGS = dict(n_step=10, learning_rate=1e-3, weight_decay=1e-2, schedule='constant', warmup_ratio=0.0)
+
+
+def _bits(t):
+    return t.view(torch.int16) if t.dtype == BF16 else t.view(torch.int32)
+
+
+def _ragged(x, lengths):
+    return torch.cat([x[b, :, :int(n)] for b, n in enumerate(lengths.tolist())], dim=1).contiguous()
+
+
+# ------------------------------------------------------------------------------------------------ kernels 1 and 2 alone
+def _geo(n, packed, n_pad, seed):
+    """a MaskedVarlenBatch at P = 1 over records of n[b] patches, about half of each masked"""
+    g = torch.Generator().manual_seed(seed)
+    counts = torch.clamp(n // 2, min=1)
+    idx = torch.cat([torch.randperm(int(nb), generator=g)[:int(mb)] for nb, mb in zip(n.tolist(), counts.tolist())])
+    return MaskedVarlenBatch(n.to(torch.int64), 1, torch.device('cuda'), None if packed else n_pad).set_mask(idx.to(torch.int64), counts)
+
+
+@pytest.mark.parametrize('dtype', [F32, BF16])
+@pytest.mark.parametrize('packed', [True, False])
+@pytest.mark.parametrize('d,n_pad,B', [(128, 250, 7), (768, 63, 70)])
+def test_mask_embed_varlen_kernels(dtype, packed, d, n_pad, B):
+    g = torch.Generator().manual_seed(d + B)
+    n = torch.randint(1, n_pad + 1, (B,), generator=g)
+    n[0], n[1], n[-1] = n_pad, 1, n_pad            # full width, one patch
+    if B > 40:
+        n[5:40] = torch.randint(1, 4, (35,), generator=g)   # many short records: tail positions have few contributors
+    wid = n_pad + 3                                 # padded layout: every record is shorter than the row pitch
+    geo = _geo(n, packed, wid, seed=B)
+    M, N, mt = geo.M, geo.N, geo.m
+    npos = wid + 8                                  # the position table holds more rows than any record has patches
+    gd = torch.Generator(device='cuda').manual_seed(5)
+    tok = torch.randn(M, d, device='cuda', generator=gd).to(dtype)
+    mtok = torch.randn(d, device='cuda', generator=gd)
+    pos = torch.randn(1 + npos, d, device='cuda', generator=gd)
+    valid = torch.zeros(M, dtype=torch.bool)
+    j_of = torch.zeros(M, dtype=torch.int64)
+    for b in range(B):
+        o, nb = int(geo.off_host[b]), int(n[b])
+        valid[o:o + nb] = True
+        j_of[o:o + nb] = torch.arange(nb)
+    valid, j_of = valid.cuda(), j_of.cuda()
+    masked = torch.zeros(M, dtype=torch.bool, device='cuda')
+    masked[geo.rows.long()] = True
+    assert int(masked.sum()) == mt and bool(valid[masked].all())
+
+    def fwd(tok_in):
+        X = torch.full((M, d), float('nan'), device='cuda', dtype=dtype)
+        flag = torch.full((M,), 7, dtype=torch.uint8, device='cuda')
+        check(lib().ecgvit_mask_embed_varlen_fwd(ptr(tok_in), ptr(mtok), ptr(pos), ptr(geo.rows), ptr(X), ptr(flag), ptr(geo.n_tok), ptr(geo.tok_off),
+                                                 B, N, geo.n_pad, M, mt, d, code(dtype), stream()), 'mask_embed_varlen_fwd')
+        return X, flag
+
+    X, flag = fwd(tok)
+    # restatement: add in f32, round once
+    src = torch.where(masked[:, None], mtok[None, :], tok.float())
+    ref = (src + pos[1 + j_of]).to(dtype)
+    assert torch.equal(_bits(X[valid]), _bits(ref[valid]))
+    assert torch.equal(flag.bool(), masked)
+    if not packed:
+        assert float(X[~valid].abs().max()) == 0.0 and not bool(torch.isnan(X).any())
+        tok_nan = tok.clone()
+        tok_nan[~valid] = float('nan')
+        X2, _ = fwd(tok_nan)
+        assert torch.equal(_bits(X2), _bits(X))
+    else:
+        assert bool(valid.all())
+
+    dX = torch.randn(M, d, device='cuda', generator=gd).to(dtype)
+    if not packed:
+        dX[~valid] = float('nan')                   # never read
+
+    def bwd():
+        dtok = torch.full((M, d), float('nan'), device='cuda', dtype=dtype)
+        dmask = torch.full((M, d), float('nan'), device='cuda', dtype=dtype)
+        dpos = torch.full((1 + npos, d), float('nan'), device='cuda')
+        check(lib().ecgvit_mask_embed_varlen_bwd(ptr(dX), ptr(flag), ptr(dtok), ptr(dmask), ptr(dpos), ptr(geo.n_tok), ptr(geo.tok_off), ptr(geo.order),
+                                                 B, N, geo.n_pad, d, code(dtype), stream()), 'mask_embed_varlen_bwd')
+        return dtok, dmask, dpos
+
+    dtok, dmask, dpos = bwd()
+    zero = torch.zeros_like(dX)
+    dXv = torch.where(valid[:, None], dX, zero)
+    assert torch.equal(_bits(dtok), _bits(torch.where(masked[:, None], zero, dXv)))
+    assert torch.equal(_bits(dmask), _bits(torch.where(masked[:, None], dXv, zero)))
+    rows_written = 1 + (N if packed else wid)
+    want = torch.zeros(1 + npos, d, dtype=torch.float64, device='cuda')
+    want.index_add_(0, 1 + j_of[valid], dX[valid].double())
+    err = float((dpos[:rows_written].double() - want[:rows_written]).norm() / want.norm())
+    print(f'dpos rel err vs fp64 {err:.2e} (rows {rows_written}, widest record {N})')
+    assert err < 1e-5
+    assert float(dpos[0].abs().max()) == 0.0
+    if rows_written > 1 + N:
+        assert float(dpos[1 + N:rows_written].abs().max()) == 0.0     # past the widest record: exact zeros
+    assert bool(torch.isnan(dpos[rows_written:]).all())               # rows the launch does not own stay untouched
+    again = bwd()
+    assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip(again[:2], (dtok, dmask))) and torch.equal(_bits(again[2][:rows_written]), _bits(dpos[:rows_written]))
+
+
+# ------------------------------------------------------------------------------------------------ model against the oracle composition
+def _conf(d, h, L, P=4, layers=2, drop=0.0, f=None):
+    return E.EcgVitConfig(max_signal_length=L, patch_size=P, hidden_size=d, num_hidden_layers=layers, num_attention_heads=h,
+                          intermediate_size=f or 2 * d, hidden_dropout_prob=drop, attention_probs_dropout_prob=drop)
+
+
+def _pair(conf, dtype, seed=3, n=1):
+    torch.manual_seed(seed)
+    ref = O.OracleMaskedEcgVit(O.OracleEcgVit(num_class=7, config=conf)).train()
+    ms = []
+    for _ in range(n):
+        m = E.MaskedEcgVit(E.EcgVit(num_class=7, config=conf, compute_dtype=dtype), mask_ratio=0.5)
+        m.load_state_dict(ref.state_dict(), strict=True)
+        ms.append(m.cuda().train())
+    return (ref, ms[0]) if n == 1 else (ref, ms)
+
+
+def _grads(m):
+    return {k: p.grad.detach().cpu().clone() for k, p in m.named_parameters() if p.grad is not None}
+
+
+def _oracle(ref, x, lengths, idx, counts):
+    ref.zero_grad()
+    loss, preds, k, tot = 0, [], 0, int(counts.sum())
+    for b, (Lb, mb) in enumerate(zip(lengths.tolist(), counts.tolist())):
+        o = ref(x[b:b + 1, :, :Lb].contiguous(), idx[k:k + mb][None])
+        loss = loss + o.loss * mb / tot
+        preds.append(o.logits[0].detach())
+        k += mb
+    loss.backward()
+    return torch.cat(preds), loss.detach(), {k: p.grad.detach().clone() for k, p in ref.named_parameters() if p.grad is not None}
+
+
+def _check(tag, pred, loss, gm, r_pred, r_loss, gr, tol):
+    ep, el = rel_err(pred, r_pred), rel_err(loss, r_loss)
+    worst = max(rel_err(gm[k], gr[k]) for k in gr if float(gr[k].norm()) > 0)
+    print(f'[{tag}] reconstruction rel {ep:.2e}, loss rel {el:.2e}, worst gradient rel {worst:.2e}')
+    assert ep < tol[0] and el < tol[0] and worst < tol[1], (ep, el, worst)
+    for k, g in gm.items():
+        if k not in gr or float(gr[k].norm()) == 0:
+            assert float(g.abs().max()) == 0.0, k       # cls_token, mlp_head.*: no part in this objective
+
+
+def _run(m, x, idx, counts, lengths):
+    m.zero_grad(set_to_none=True)
+    out = m(x, idx, lengths=lengths, mask_counts=counts)
+    out.loss.backward()
+    return out.logits.detach().cpu(), out.loss.detach().cpu(), _grads(m)
+
+
+@pytest.mark.parametrize('dtype,form', [(F32, 'padded'), (BF16, 'padded'), (BF16, 'ragged')])
+@pytest.mark.parametrize('d,h', [(128, 2), (256, 2)])
+def test_model_vs_oracle_per_record(dtype, form, d, h):
+    L = 1000
+    ref, m = _pair(_conf(d, h, L), dtype)
+    x, _ = O.synthetic_batch(4, length=L, num_class=7, seed=1)
+    idx, counts = m.random_mask_indices_varlen(MIX, generator=torch.Generator().manual_seed(3))
+    r_pred, r_loss, gr = _oracle(ref, x, MIX, idx, counts)
+    xx = x.cuda() if form == 'padded' else _ragged(x, MIX).cuda()
+    pred, loss, gm = _run(m, xx, idx, counts, MIX)
+    assert pred.shape == (int(counts.sum()), 12 * 4) and pred.dtype == F32
+    _check(f'{form} {dtype} d={d}', pred, loss, gm, r_pred, r_loss, gr, TOL[dtype])
+    pos = gm['encoder.vit.pos_embedding'][0]
+    assert float(pos[0].abs().max()) == 0.0
+    with pytest.raises(RuntimeError, match='ragged' if form == 'ragged' else 'lengths'):
+        m.encoder.attention_probs(0)
+    # a shorter batch after it: the position rows past its widest record are exactly zero
+    short = torch.tensor([400, 4, 200, 96])
+    i2, c2 = m.random_mask_indices_varlen(short, generator=torch.Generator().manual_seed(4))
+    x2 = x[:, :, :400].contiguous().cuda() if form == 'padded' else _ragged(x, short).cuda()
+    _, _, g2 = _run(m, x2, i2, c2, short)
+    pos = g2['encoder.vit.pos_embedding'][0]
+    assert float(pos[0].abs().max()) == 0.0 and float(pos[101:].abs().max()) == 0.0 and float(pos[1:101].abs().max()) > 0
+
+
+SHAPE = dict(hidden_size=768, num_attention_heads=12, intermediate_size=3072)   # the base layer shape
+
+
+@pytest.mark.parametrize('dtype,form', [(F32, 'padded'), (BF16, 'padded'), (BF16, 'ragged')])
+def test_layer_shape_vs_oracle_per_record(dtype, form):
+    """the bounds of test_masked_step_layer_shape_vs_cpu_oracle: f32 <= 1e-4; bf16 loss / reconstruction <= 3e-2, whole-gradient cosine >= 0.98,
+    every tensor >= 0.95; gathered targets bit-exact"""
+    torch.set_num_threads(min(32, torch.get_num_threads()))
+    B, P, L = 8, 20, 5000
+    conf = E.EcgVitConfig(**{**dict(max_signal_length=L, patch_size=P, num_hidden_layers=2, hidden_dropout_prob=0., attention_probs_dropout_prob=0.), **SHAPE})
+    torch.manual_seed(31)
+    ref = O.OracleMaskedEcgVit(O.OracleEcgVit(config=conf)).train()
+    m = E.MaskedEcgVit(E.EcgVit(config=conf, compute_dtype=dtype), mask_ratio=0.5)
+    m.load_state_dict(ref.state_dict(), strict=True)
+    m.cuda().train()
+    x, _ = O.synthetic_batch(B, length=L, seed=19)
+    lengths = torch.randint(L // (2 * P), L // P + 1, (B,), generator=torch.Generator().manual_seed(2)) * P
+    lengths[0] = L
+    idx, counts = m.random_mask_indices_varlen(lengths, generator=torch.Generator().manual_seed(3))
+    r_pred, r_loss, gr = _oracle(ref, x, lengths, idx, counts)
+    xx = x.cuda() if form == 'padded' else _ragged(x, lengths).cuda()
+    pred, loss, gm = _run(m, xx, idx, counts, lengths)
+    k, tg = 0, []
+    for b, mb in enumerate(counts.tolist()):
+        tg.append(O.patch_gather(x[b:b + 1], P)[0, idx[k:k + mb].long()])
+        k += mb
+    eng = m.encoder._engine()
+    assert torch.equal(eng.act['target'].float().cpu(), torch.cat(tg).to(dtype).float())
+    lerr, perr = rel_err(loss, r_loss), rel_err(pred, r_pred)
+    names = [k for k in gr if float(gr[k].norm()) > 0]
+    if dtype == F32:
+        worst = max(rel_err(gm[k], gr[k]) for k in names)
+        print(f'[{form} f32] loss {lerr:.2e} reconstruction {perr:.2e} worst gradient {worst:.2e}')
+        assert lerr < 1e-4 and perr < 1e-4 and worst < 1e-4
+    else:
+        cos = lambda a, b: float(torch.dot(a.flatten().double(), b.flatten().double()) / (a.double().norm() * b.double().norm() + 1e-30))
+        whole = cos(torch.cat([gm[k].flatten() for k in names]), torch.cat([gr[k].flatten() for k in names]))
+        each = min(cos(gm[k], gr[k]) for k in names)
+        print(f'[{form} bf16] loss {lerr:.2e} reconstruction {perr:.2e} gradient cosine whole {whole:.4f} worst tensor {each:.4f}')
+        assert lerr < 3e-2 and perr < 3e-2 and whole >= 0.98 and each >= 0.95
+
+
+def test_ragged_vs_padded_same_records():
+    L = 1000
+    _, m = _pair(_conf(128, 2, L), BF16)
+    x, _ = O.synthetic_batch(4, length=L, num_class=7, seed=9)
+    idx, counts = m.random_mask_indices_varlen(MIX, generator=torch.Generator().manual_seed(5))
+    p_pad, l_pad, g_pad = _run(m, x.cuda(), idx, counts, MIX)
+    p_rag, l_rag, g_rag = _run(m, _ragged(x, MIX).cuda(), idx, counts, MIX)
+    assert m.encoder._engine().saved['ragged'].M == int(MIX.sum()) // 4
+    _check('ragged vs padded', p_rag, l_rag, g_rag, p_pad, l_pad, g_pad, TOL[BF16])
+
+
+@pytest.mark.parametrize('dtype', [F32, BF16])
+def test_full_lengths_bit_identical_and_nan_past_lengths(dtype):
+    L, B = 1000, 4
+    _, m = _pair(_conf(128, 2, L), dtype)
+    x, _ = O.synthetic_batch(B, length=L, num_class=7, seed=2)
+    idx2 = m.random_mask_indices(B, generator=torch.Generator().manual_seed(1))
+    m.zero_grad(set_to_none=True)
+    out = m(x.cuda(), idx2)
+    out.loss.backward()
+    base = (out.logits.detach().cpu().reshape(-1, 48), out.loss.detach().cpu(), _grads(m))
+    got = _run(m, x.cuda(), idx2.flatten(), torch.full((B,), idx2.shape[1]), torch.full((B,), L))
+    assert torch.equal(got[0], base[0]) and torch.equal(got[1], base[1]) and all(torch.equal(got[2][k], base[2][k]) for k in base[2])
+    # full lengths with UNEQUAL counts run the varlen kernels: the last record masks one patch less, the others give what they gave
+    got = _run(m, x.cuda(), idx2.flatten()[:-1], torch.tensor([idx2.shape[1]] * (B - 1) + [idx2.shape[1] - 1]), torch.full((B,), L))
+    keep = (B - 1) * idx2.shape[1]
+    assert m.encoder._engine().saved.get('geo') is not None and rel_err(got[0][:keep], base[0][:keep]) < TOL[dtype][0]
+    # NaN past the lengths changes nothing
+    idx, counts = m.random_mask_indices_varlen(MIX, generator=torch.Generator().manual_seed(3))
+    xz, xn = x.clone(), x.clone()
+    for b, Lb in enumerate(MIX.tolist()):
+        xz[b, :, Lb:] = 0.0
+        xn[b, :, Lb:] = float('nan')
+    a = _run(m, xz.cuda(), idx, counts, MIX)
+    b = _run(m, xn.cuda(), idx, counts, MIX)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and all(torch.equal(a[2][k], b[2][k]) for k in a[2])
+    assert all(bool(torch.isfinite(t).all()) for t in (b[0], b[1], *b[2].values()))
+
+
+def test_device_resident_masks_and_lengths():
+    L = 1000
+    _, m = _pair(_conf(128, 2, L), BF16)
+    x, _ = O.synthetic_batch(4, length=L, num_class=7, seed=9)
+    idx, counts = m.random_mask_indices_varlen(MIX, generator=torch.Generator().manual_seed(5))
+    a = _run(m, x.cuda(), idx, counts, MIX)
+    b = _run(m, x.cuda(), idx.cuda(), counts.cuda(), MIX.cuda())
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    bad = idx.clone()
+    bad[0] = 250
+    with pytest.raises(ValueError, match='lie in'):
+        m(x.cuda(), bad.cuda(), lengths=MIX.cuda(), mask_counts=counts.cuda())
+
+
+# ------------------------------------------------------------------------------------------------ train step
+def _step_models(conf, dtype, n, seed=2):
+    torch.manual_seed(seed)
+    ref = O.OracleMaskedEcgVit(O.OracleEcgVit(num_class=7, config=conf))
+    ms = []
+    for _ in range(n):
+        m = E.MaskedEcgVit(E.EcgVit(num_class=7, config=conf, compute_dtype=dtype), mask_ratio=0.5)
+        m.load_state_dict(ref.state_dict(), strict=True)
+        ms.append(m.cuda().train())
+    return ms
+
+
+def _flat_grad(m):
+    return m.encoder._gflat.detach().clone()
+
+
+@pytest.mark.parametrize('dtype,form', [(F32, 'padded'), (BF16, 'padded'), (BF16, 'ragged')])
+def test_step_masked_lr0_matches_module_path(dtype, form):
+    """one step with learning_rate = 0 leaves the step's gradients in the flat buffer: against the module path's (f32 1e-5, bf16 2e-2, the
+    bounds of test_train_step_with_lengths_matches_module_path_and_oracle)"""
+    L = 1000
+    m_mod, m_step = _step_models(_conf(128, 2, L), dtype, 2)
+    x, _ = O.synthetic_batch(4, length=L, num_class=7, seed=6)
+    idx, counts = m_mod.random_mask_indices_varlen(MIX, generator=torch.Generator().manual_seed(8))
+    xx = x.cuda() if form == 'padded' else _ragged(x, MIX).cuda()
+    pred, loss, _ = _run(m_mod, xx, idx, counts, MIX)
+    g_mod = _flat_grad(m_mod)
+    step = E.HipTrainStep(m_step, dict(ARGS, learning_rate=0.0, weight_decay=0.0))
+    l2, p2 = step.step_masked(xx, idx, lengths=MIX, mask_counts=counts)
+    step.finish()
+    tol = 1e-5 if dtype == F32 else 2e-2
+    eg, el, ep = rel_err(_flat_grad(m_step), g_mod), rel_err(l2, loss), rel_err(p2.float(), pred)
+    print(f'[{form} {dtype}] step vs module: gradient {eg:.2e} loss {el:.2e} reconstruction {ep:.2e}')
+    assert eg < tol and el < tol and ep < tol
+    assert p2.shape == (int(counts.sum()), 48)
+
+
+@pytest.mark.parametrize('dtype,form', [(F32, 'padded'), (BF16, 'padded'), (BF16, 'ragged')])
+@pytest.mark.parametrize('mb', [3, 4])
+def test_step_masked_micro_batches(dtype, form, mb):
+    """micro_batch_size dividing (3) and not dividing (4) B = 6 against the unsplit step at dropout 0, at the bounds of
+    test_masked_step_with_micro_batches (f32: loss 1e-6, gradient / norm / output 1e-5; bf16: 2e-3, 2e-2, 2e-3, 2e-2)"""
+    L, B = 1000, 6
+    lengths = torch.tensor([1000, 200, 604, 4, 1000, 52])
+    ms = _step_models(_conf(128, 2, L), dtype, 2)
+    x, _ = O.synthetic_batch(B, length=L, num_class=7, seed=12)
+    idx, counts = ms[0].random_mask_indices_varlen(lengths, generator=torch.Generator().manual_seed(8))
+    xx = x.cuda() if form == 'padded' else _ragged(x, lengths).cuda()
+    res = []
+    for m, size in zip(ms, (None, mb)):
+        step = E.HipTrainStep(m, dict(ARGS))
+        loss, pred = step.step_masked(xx, idx, micro_batch_size=size, lengths=lengths, mask_counts=counts)
+        torch.cuda.synchronize()
+        res.append((loss.clone(), pred.float().clone(), _flat_grad(m), float(step.norm_out[0])))
+        step.finish()
+    (l0, p0, g0, n0), (l1, p1, g1, n1) = res
+    tl, tg, tn, to = (1e-6, 1e-5, 1e-5, 1e-5) if dtype == F32 else (2e-3, 2e-2, 2e-3, 2e-2)
+    el, eg, en, eo = rel_err(l1, l0), rel_err(g1, g0), abs(n1 - n0) / n0, rel_err(p1, p0)
+    print(f'[{form} {dtype} mb={mb}] loss {el:.2e} gradient {eg:.2e} norm {en:.2e} output {eo:.2e}')
+    assert p1.shape == p0.shape and el < tl and eg < tg and en < tn and eo < to
+
+
+def test_step_masked_frozen_encoder_and_dropout_reproducible():
+    L = 1000
+    conf = _conf(128, 2, L, drop=0.1)
+    x, _ = O.synthetic_batch(4, length=L, num_class=7, seed=41)
+    xr = _ragged(x, MIX).cuda()
+    runs = []
+    for m in _step_models(conf, BF16, 2, seed=3):
+        torch.manual_seed(5)
+        gen = torch.Generator().manual_seed(11)
+        step = E.HipTrainStep(m, dict(ARGS))
+        out = []
+        for _ in range(3):
+            idx, counts = m.random_mask_indices_varlen(MIX, generator=gen)
+            loss, pred = step.step_masked(xr, idx, lengths=MIX, mask_counts=counts)
+            out += [loss.clone(), pred.clone()]
+        step.finish()
+        runs.append(out + [m.encoder._pflat.clone()])
+    assert all(torch.equal(a, b) for a, b in zip(*runs))
+    assert all(bool(torch.isfinite(t.float()).all()) for t in runs[0])
+    # frozen encoder: only the pixel head and the mask token train; frozen tensors stay bit-identical
+    (m,) = _step_models(_conf(128, 2, L), BF16, 1, seed=3)
+    for k, p in m.named_parameters():
+        p.requires_grad_(not k.startswith('encoder.'))
+    before = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    step = E.HipTrainStep(m, dict(ARGS))
+    idx, counts = m.random_mask_indices_varlen(MIX, generator=torch.Generator().manual_seed(1))
+    for form_x in (xr, x.cuda()):
+        step.step_masked(form_x, idx, lengths=MIX, mask_counts=counts, micro_batch_size=3)
+    step.finish()
+    after = m.state_dict()
+    assert all(torch.equal(after[k], before[k]) for k in before if k.startswith('encoder.'))
+    assert all(not torch.equal(after[k], before[k]) for k in ('mask_token', 'to_pixels.weight', 'to_pixels.bias'))
+
+
+# ------------------------------------------------------------------------------------------------ activation pool
+def test_pool_bounded_and_survives_alternating_passes():
+    L, B = 1000, 4
+    conf = _conf(128, 2, L)
+    x, y = O.synthetic_batch(B, length=L, num_class=7, seed=41)
+    m_rag, m_pad = _step_models(conf, BF16, 2)
+    idx, counts = m_rag.random_mask_indices_varlen(MIX, generator=torch.Generator().manual_seed(1))
+    s_rag, s_pad = E.HipTrainStep(m_rag, dict(ARGS)), E.HipTrainStep(m_pad, dict(ARGS))
+    s_rag.step_masked(_ragged(x, MIX).cuda(), idx, lengths=MIX, mask_counts=counts)
+    s_pad.step_masked(x.cuda(), idx, lengths=MIX, mask_counts=counts)
+    rag, pad = m_rag.encoder._engine()._pool, m_pad.encoder._engine()._pool
+    assert set(rag) == set(pad) and all(rag[k].numel() <= pad[k].numel() for k in rag), [k for k in rag if rag[k].numel() > pad[k].numel()]
+    # alternating ragged masked / uniform masked / supervised ragged passes: nothing is re-allocated after the first round
+    sup = E.HipTrainStep(m_rag.encoder, dict(ARGS))
+    idx2 = m_rag.random_mask_indices(B, generator=torch.Generator().manual_seed(2))
+    eng = m_rag.encoder._engine()
+
+    def one_round():
+        for lens in (MIX, torch.tensor([400, 4, 1000, 60])):
+            i, c = m_rag.random_mask_indices_varlen(lens, generator=torch.Generator().manual_seed(1))
+            s_rag.step_masked(_ragged(x, lens).cuda(), i, lengths=lens, mask_counts=c)
+            s_rag.step_masked(x.cuda(), idx2)
+            sup.step(_ragged(x, lens).cuda(), y.cuda(), lengths=lens)
+        return {k: (v.data_ptr(), v.numel()) for k, v in eng._pool.items()}
+
+    first = one_round()
+    assert one_round() == first
+    s_rag.finish(), s_pad.finish(), sup.finish()
