@@ -53,6 +53,56 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(const float *__restri
     }
 }
 
+// The same transforms PER RECORD, for records of unequal raw length (the reference applies them to one record at a time:
+// ptb_dataset.py:132-149): record b holds raw_len[b] samples per lead starting at x + src_off[b] (lead c at + c * lead_stride), is
+// zero-padded in normalised space to n_patch[b] * P samples, TimeOut zeroes [t0[b], t0[b] + tlen[b]) of the padded record, and its patch
+// rows go to out rows row_off[b] ...  One kernel text for both row layouts: nrows = 0 -- packed rows, record b writes its n_patch[b] rows;
+// nrows > 0 -- padded rows, record b writes nrows rows, exact zeros past n_patch[b].  A block whose patches all lie past n_patch[b] never
+// reads x.  Record starts fall on arbitrary sample offsets, so the loads are scalar (consecutive lanes, consecutive samples of one lead:
+// coalesced); the record base is 64-bit, offsets inside a record 32-bit.
+template <typename T>
+__global__ __launch_bounds__(256) void patch_gather_transform_varlen_kernel(const float *__restrict__ x, T *__restrict__ out,
+                                                                            const int64_t *__restrict__ src_off, int64_t lead_stride,
+                                                                            const int32_t *__restrict__ raw_len, const int32_t *__restrict__ n_patch,
+                                                                            const int32_t *__restrict__ row_off, int nrows, int n_max, int C, int P,
+                                                                            int PB, int64_t ld, const float *__restrict__ mean,
+                                                                            const float *__restrict__ inv_std, const int32_t *__restrict__ t0,
+                                                                            const int32_t *__restrict__ tlen) {
+    extern __shared__ __attribute__((aligned(16))) float tile[];  // [C][PB*P+1]
+    const int b = blockIdx.y, p0 = blockIdx.x * PB;
+    const int nb = min(n_patch[b], nrows > 0 ? nrows : n_max);   // (a table entry past the rows the launch was sized for never writes there)
+    const int rows = nrows > 0 ? nrows : nb;
+    if (p0 >= rows) return;
+    const int np = min(PB, rows - p0), W = np * P, WS = PB * P + 1;
+    const int CP = C * P;
+    T *ob = out + ((int64_t)row_off[b] + p0) * ld;
+    if (p0 >= nb) {   // padded rows past the record: zeros, x is not read
+        for (int idx = threadIdx.x; idx < np * (int)ld; idx += 256) ob[idx] = from_f32<T>(0.f);
+        return;
+    }
+    const int lb = min(raw_len[b], nb * P);
+    const float *xb = x + src_off[b];
+    int z0 = 0, z1 = 0;
+    if (t0) { z0 = t0[b]; z1 = z0 + tlen[b]; }
+    for (int idx = threadIdx.x; idx < C * W; idx += 256) {
+        const int c = idx / W, s = idx - c * W;
+        const int pos = p0 * P + s;
+        float v = 0.f;
+        if (pos < lb && !(pos >= z0 && pos < z1)) v = (xb[(int64_t)c * lead_stride + pos] - mean[c]) * inv_std[c];
+        tile[c * WS + s] = v;
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < np * (int)ld; idx += 256) {
+        const int pp = idx / (int)ld, f = idx - pp * (int)ld;
+        float v = 0.f;
+        if (f < CP) {
+            const int j = f / C, c = f - j * C;
+            v = tile[c * WS + pp * P + j];
+        }
+        ob[(int64_t)pp * ld + f] = from_f32<T>(v);
+    }
+}
+
 // =====================================================================================================
 // CLS concat + positional add (+ embedding dropout)
 // =====================================================================================================
@@ -762,6 +812,30 @@ int ecgvit_patch_gather_transform(const float *x_raw, void *patches, int B, int 
                                   const float *mean, const float *inv_std, const int32_t *timeout_start, const int32_t *timeout_len,
                                   int dtype, void *stream) {
     return patch_gather_launch(x_raw, patches, B, C, L, P, ld, dtype, stream, true, L_raw, mean, inv_std, timeout_start, timeout_len);
+}
+
+int ecgvit_patch_gather_transform_varlen(const float *x, void *patches, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len,
+                                         const int32_t *n_patch, const int32_t *row_off, int n_rows_per_record, int n_max, int B, int C, int P,
+                                         int64_t ld, const float *mean, const float *inv_std, const int32_t *timeout_start,
+                                         const int32_t *timeout_len, int dtype, void *stream) {
+    if (B <= 0 || C <= 0 || P <= 0 || n_max <= 0 || n_rows_per_record < 0 || lead_stride <= 0 || ld < (int64_t)C * P) return ECGVIT_EINVAL;
+    if (!x || !patches || !src_off || !raw_len || !n_patch || !row_off || !mean || !inv_std) return ECGVIT_EINVAL;
+    if ((timeout_start == nullptr) != (timeout_len == nullptr)) return ECGVIT_EINVAL;
+    if (n_rows_per_record > 0 && n_rows_per_record < n_max) return ECGVIT_EINVAL;
+    if (dtype != ECGVIT_F32 && dtype != ECGVIT_BF16) return ECGVIT_EINVAL;
+    if (B > 65535 || (int64_t)n_max * ld > INT32_MAX) return ECGVIT_EINVAL;   // (grid.y; 32-bit offsets inside a record)
+    int PB = std::max(1, 256 / P);
+    while (PB > 1 && (size_t)C * (PB * P + 1) * 4 > 48 * 1024) PB >>= 1;
+    const size_t lds = (size_t)C * (PB * P + 1) * 4;
+    if (lds > 64 * 1024) return ECGVIT_EINVAL;
+    const int rows = n_rows_per_record > 0 ? n_rows_per_record : n_max;
+    dim3 grid((rows + PB - 1) / PB, B);
+#define PGV(T) hipLaunchKernelGGL((patch_gather_transform_varlen_kernel<T>), grid, dim3(256), lds, as_stream(stream), x, (T *)patches, src_off, \
+                                  lead_stride, raw_len, n_patch, row_off, n_rows_per_record, n_max, C, P, PB, ld, mean, inv_std, timeout_start, timeout_len)
+    if (dtype == ECGVIT_F32) PGV(float); else PGV(bf16_t);
+#undef PGV
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
 }
 
 int ecgvit_embed_finish(const void *tok, const float *cls, const float *pos, void *X, int B, int n, int d, float dropout_p,

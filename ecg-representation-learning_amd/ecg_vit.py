@@ -315,7 +315,12 @@ class EcgVit(nn.Module):
         Ragged batch: sample_values (C, S) = torch.cat(records, dim=1) with lengths (B,) required (sum(lengths) == S, each a positive multiple
         of patch_size, at most max_signal_length); record b is sample_values[:, off_b : off_b + lengths[b]] (off_b = the exclusive prefix sum)
         and gives what it gives alone at (1, C, lengths[b]) -- no padded rows are computed.  bf16 engine only (not with fp8_linear or a fused
-        input transform); hidden-dropout masks differ from those of the padded batch of the same records."""
+        input transform); hidden-dropout masks differ from those of the padded batch of the same records.
+        Under a per-record input transform (`set_input_transform(FusedInputTransform(..., per_record=True))`) sample_values holds RAW records
+        and lengths their RAW sample counts l_b (any integer >= 1; None: every record holds L' samples): (B, C, L') with any L' >= max l_b,
+        or a ragged (C, S_raw) batch with sum(lengths) == S_raw.  Record b is normalised, zero-padded to padded_length(l_b) and (training)
+        TimeOut-masked inside the patch load, exactly as the reference transforms it alone, and counts padded_length(l_b) / patch_size
+        patches; every padded length must be <= max_signal_length.  Not with fp8_linear; the ragged form on the bf16 engine only."""
         if not sample_values.is_cuda:
             raise RuntimeError('EcgVit (HIP) runs on an MI355X device only: move the model and inputs to "cuda" '
                                '(there is deliberately no CPU fallback)')
@@ -549,16 +554,26 @@ class MaskedEcgVit(nn.Module):
         """(B, m) int32 on the host: per record, the first m entries of a random permutation of the n patches"""
         return torch.stack([torch.randperm(self.n_patch, generator=generator)[:self.n_mask] for _ in range(batch)]).to(torch.int32)
 
-    def mask_counts(self, lengths):
-        """(B,) int64 on the host: the masked patches of records of `lengths` samples, max(1, int(mask_ratio * n_b)) (n_mask at full width)"""
-        n = torch.as_tensor(lengths).detach().to('cpu', torch.int64) // self.encoder.config.patch_size
+    def patch_counts(self, lengths, raw=None):
+        """(B,) int64 on the host: the patches n_b of records of `lengths` samples -- lengths / P, or, for RAW lengths under a per-record input
+        transform, padded_length(l_b) / P.  raw: None = raw exactly when the encoder's input transform has per_record set; True / False"""
+        t = torch.as_tensor(lengths).detach().to('cpu', torch.int64)
+        P = self.encoder.config.patch_size
+        if raw is None:
+            raw = bool(getattr(getattr(self.encoder, '_input_transform', None), 'per_record', False))
+        return (t + (P - t % P)) // P if raw else t // P
+
+    def mask_counts(self, lengths, raw=None):
+        """(B,) int64 on the host: the masked patches of records of `lengths` samples, max(1, int(mask_ratio * n_b)) (n_mask at full width);
+        raw: the lengths are raw sample counts under a per-record input transform (`patch_counts`)"""
+        n = self.patch_counts(lengths, raw)
         return torch.tensor([max(1, int(self.mask_ratio * int(v))) for v in n.tolist()], dtype=torch.int64)
 
-    def random_mask_indices_varlen(self, lengths, generator=None):
+    def random_mask_indices_varlen(self, lengths, generator=None, raw=None):
         """(mask_idx int32 [sum m_b], mask_counts int64 [B]) on the host for records of unequal length: per record, in order, the first m_b
-        entries of a random permutation of its n_b patches"""
-        counts = self.mask_counts(lengths)
-        n = torch.as_tensor(lengths).detach().to('cpu', torch.int64) // self.encoder.config.patch_size
+        entries of a random permutation of its n_b patches; raw: as `patch_counts`"""
+        counts = self.mask_counts(lengths, raw)
+        n = self.patch_counts(lengths, raw)
         idx = [torch.randperm(int(nb), generator=generator)[:int(mb)] for nb, mb in zip(n.tolist(), counts.tolist())]
         return torch.cat(idx).to(torch.int32), counts
 

@@ -158,14 +158,64 @@ def check_lengths(lengths, B, P, width):
     return (t // P + 1).to(torch.int32).contiguous()
 
 
+def check_raw_lengths(lengths, xf, max_len, B=None, width=None, S=None):
+    """RAW per-record sample counts under a per-record input transform (`FusedInputTransform(per_record=True)`) -> (raw, padded) int64 host
+    tensors, padded[b] = xf.padded_length(raw[b]) (a full extra patch when raw[b] is a multiple of the patch).  lengths: a (B,) integer
+    tensor, every entry >= 1 (no multiple-of-P rule), at most `width` (a padded (B, C, width) batch) / summing to S (a ragged (C, S) batch),
+    and every padded length at most max_len; anything else raises ValueError.  Host work only (one blocking read for a device tensor)."""
+    if lengths is None:
+        raise ValueError('a ragged (C, S) batch needs lengths: the (B,) per-record sample counts')
+    t = _host_ints(lengths, 'lengths', 'a (B,) integer tensor')
+    if t.dim() != 1 or t.shape[0] < 1 or (B is not None and t.shape[0] != B):
+        raise ValueError(f'lengths must have shape (batch={B if B is not None else "B"},) with B >= 1, got {tuple(lengths.shape)}')
+    lo, hi = int(t.min()), int(t.max())
+    if lo <= 0:
+        raise ValueError(f'lengths must be positive (got {lo})')
+    if width is not None and hi > width:
+        raise ValueError(f'lengths must not exceed the batch width {width} (got {hi})')
+    padded = t + (xf.k - t % xf.k)   # FusedInputTransform.padded_length, elementwise
+    if int(padded.max()) > max_len:
+        raise ValueError(f'padded record lengths must not exceed max_signal_length={max_len}: a raw record of {hi} samples pads to '
+                         f'{xf.padded_length(hi)} (TimeEndPad adds a full patch to a multiple of patch_size={xf.k})')
+    if S is not None and int(t.sum()) != S:
+        raise ValueError(f'lengths must sum to the ragged batch width S={S} (got {int(t.sum())})')
+    return t, padded
+
+
+class RawSide:
+    """The raw side of a batch under a per-record input transform: what `ecgvit_patch_gather_transform_varlen` reads.
+      raw, padded -- int64 [B] on the host: raw sample counts l_b and padded lengths n_b P
+      src_off (int64), raw_len, n_patch, row_off (int32) -- [B] on `device`, staged through pinned memory in one copy: first sample of
+               record b's lead 0, l_b, n_b, first patch row of record b
+      lead_stride -- samples between the leads of one record (W of a padded batch, S_raw of a ragged one)
+      nrows -- patch rows per record of the padded row layout (rows past n_b are written as zeros), 0 = packed rows;  n_max = max n_b"""
+
+    def __init__(self, raw, padded, P, src_off, row_off, lead_stride, nrows, device):
+        B = raw.shape[0]
+        n = padded // P
+        pack = torch.cat([src_off.to(torch.int64).contiguous().view(torch.int32), raw.to(torch.int32), n.to(torch.int32), row_off.to(torch.int32)])
+        pack = _stage(pack, device)
+        self.raw, self.padded, self.B = raw, padded, B
+        self.src_off = pack[:2 * B].view(torch.int64)
+        self.raw_len, self.n_patch, self.row_off = pack[2 * B:3 * B], pack[3 * B:4 * B], pack[4 * B:5 * B]
+        self.lead_stride, self.nrows, self.n_max = int(lead_stride), int(nrows), int(n.max())
+        self.src_off_host, self.row_off_host = src_off, row_off
+
+
+def _excl_cumsum(t):
+    return torch.cumsum(t, 0) - t
+
+
 class RaggedBatch:
     """Token geometry of a ragged batch: B records concatenated along time, (C, S) with S = sum(lengths) (`check_ragged`).
       n_tok   -- int32 [B]: tokens of record b, lengths[b] / P + 1 (its CLS row included)
       tok_off -- int32 [B]: first packed token row of record b, off_b / P + b (off_b = exclusive prefix sum of lengths): its CLS row
       M       -- packed token rows, S / P + B;  N -- the widest record's tokens;  S -- samples
-      lengths -- the validated sample counts, int64 on the host: slicing by record range (`records`) reads nothing from the device"""
+      lengths -- the validated sample counts, int64 on the host: slicing by record range (`records`) reads nothing from the device
+    Under a per-record input transform (`raw`: the raw sample counts, `check_raw_lengths`) lengths are the PADDED lengths, the batch itself
+    is (C, S_raw) with S_raw = sum(raw), and `rawside` (`RawSide`) says where each record's samples lie; S_raw = S otherwise."""
 
-    def __init__(self, lengths, P, device):
+    def __init__(self, lengths, P, device, raw=None):
         t = lengths
         n_tok = t // P + 1
         tok_off = torch.cumsum(n_tok, 0) - n_tok   # = off_b / P + b
@@ -176,15 +226,47 @@ class RaggedBatch:
         self.n_tok, self.tok_off = pack[0], pack[1]
         self.S = int(t.sum())
         self.M, self.N = self.S // P + t.shape[0], int(t.max()) // P + 1
+        self.raw, self.rawside, self.S_raw = raw, None, self.S
+        if raw is not None:
+            self.S_raw = int(raw.sum())
+            # patch rows carry no CLS row: record b's first is tok_off[b] - b = (padded offset of b) / P
+            self.rawside = RawSide(raw, t, P, _excl_cumsum(raw), _excl_cumsum(n_tok - 1), self.S_raw, 0, device)
 
     @property
     def B(self):
         return self.lengths.shape[0]
 
     def records(self, b0, b1):
-        """records b0 .. b1 - 1: (s0, s1) = their sample range in the (C, S) batch, and their RaggedBatch"""
-        s0, s1 = int(self.lengths[:b0].sum()), int(self.lengths[:b1].sum())
-        return (s0, s1), RaggedBatch(self.lengths[b0:b1], self.P, self.device)
+        """records b0 .. b1 - 1: (s0, s1) = their sample range in the (C, S) batch (RAW offsets under a per-record transform), and their
+        RaggedBatch"""
+        src = self.lengths if self.raw is None else self.raw
+        s0, s1 = int(src[:b0].sum()), int(src[:b1].sum())
+        return (s0, s1), RaggedBatch(self.lengths[b0:b1], self.P, self.device, None if self.raw is None else self.raw[b0:b1])
+
+
+class RawPaddedBatch:
+    """Geometry of a padded (B, C, W) batch of RAW records under a per-record input transform (`VitEngine.check_raw_input`): record b holds
+    raw[b] <= W samples, counts n_b = padded[b] / P patches, and the pass runs at `width` = max padded length (N' = width / P + 1 tokens).
+      ntok -- int32 [B] on `device`, n_b + 1, or None when every record fills the width (the uniform kernels then run, as `check_lengths`)
+      rawside -- `RawSide`: src_off[b] = b C W, row_off[b] = b width / P, width / P patch rows per record (zeros past n_b)
+    A slice by record range (`records`: micro-batches, the evaluator) keeps the whole batch's width."""
+
+    def __init__(self, raw, padded, P, C, W, device, width=None):
+        B = raw.shape[0]
+        self.raw, self.padded, self.P, self.C, self.W, self.device = raw, padded, P, C, W, device
+        self.width = int(padded.max()) if width is None else width
+        n = self.width // P
+        self.ntok = None if int(padded.min()) == self.width else _stage((padded // P + 1).to(torch.int32), device)
+        ar = torch.arange(B, dtype=torch.int64)
+        self.rawside = RawSide(raw, padded, P, ar * (C * W), ar * n, W, n, device)
+
+    @property
+    def B(self):
+        return self.raw.shape[0]
+
+    def records(self, b0, b1):
+        """records b0 .. b1 - 1 (x[b0:b1] of the batch) at the same pass width"""
+        return RawPaddedBatch(self.raw[b0:b1], self.padded[b0:b1], self.P, self.C, self.W, self.device, self.width)
 
 
 def check_ragged(lengths, S, P, max_len, device=None):
@@ -234,9 +316,12 @@ class MaskedVarlenBatch:
                (ties by record index; `ecgvit_mask_embed_varlen_bwd`), n_cls = n_b + 1 (what `ecgvit_patch_gather_varlen` takes)
       N -- the widest record's patches;  S -- valid samples;  lengths -- the validated sample counts, int64 on the host
       counts, m -- the records' mask counts (int64, host) and their sum;  rows -- int32 [m] on `device`: the masked rows tok_off[b] + idx
-    Everything is computed on the host from host data: a step fed host tensors reads nothing back from the device."""
+    Everything is computed on the host from host data: a step fed host tensors reads nothing back from the device.
+    Under a per-record input transform (`raw` = (raw sample counts, lead stride, record stride | None): `check_raw_lengths`) lengths are the
+    PADDED lengths and `rawside` (`RawSide`) says where each record's raw samples lie: in a ragged (C, S_raw) batch at the raw offsets
+    (record stride None), in a padded (B, C, W) batch at b C W (lead stride W, record stride C W; width = the widest padded length)."""
 
-    def __init__(self, lengths, P, device, width=None):
+    def __init__(self, lengths, P, device, width=None, raw=None):
         t = lengths
         B = t.shape[0]
         n = t // P
@@ -250,6 +335,11 @@ class MaskedVarlenBatch:
         pack = _stage(torch.stack([n, tok_off, order, n + 1]).to(torch.int32), device)
         self.n_tok, self.tok_off, self.order, self.n_cls = pack[0], pack[1], pack[2], pack[3]
         self.counts, self.m, self.rows = None, 0, None
+        self.raw, self.rawside = raw, None
+        if raw is not None:
+            r, lead, rec = raw
+            src = _excl_cumsum(r) if rec is None else torch.arange(B, dtype=torch.int64) * rec
+            self.rawside = RawSide(r, t, P, src, tok_off, lead, self.n_pad, device)
 
     @property
     def B(self):
@@ -265,14 +355,22 @@ class MaskedVarlenBatch:
     def as_rectangular(self, max_len):
         """the mask as (B, m) int32 host indices when this batch is one the rectangular pass runs -- padded rows, every record max_len samples,
         one mask count -- else None"""
+        if self.raw is not None:   # raw records: only the per-record gather reads them
+            return None
         if self.width != max_len or int(self.lengths.min()) != max_len or int(self.counts.min()) != int(self.counts.max()):
             return None
         return self.idx_host.view(self.B, -1).to(torch.int32)
 
     def records(self, b0, b1):
-        """records b0 .. b1 - 1 with their mask indices: ((s0, s1) = their sample range in a ragged batch, their MaskedVarlenBatch)"""
-        s0, s1 = int(self.lengths[:b0].sum()), int(self.lengths[:b1].sum())
-        g = MaskedVarlenBatch(self.lengths[b0:b1], self.P, self.device, self.width)
+        """records b0 .. b1 - 1 with their mask indices: ((s0, s1) = their sample range in a ragged batch -- RAW offsets under a per-record
+        transform --, their MaskedVarlenBatch)"""
+        src, raw = self.lengths, None
+        if self.raw is not None:
+            src = self.raw[0]
+            b = int(src[b0:b1].sum())
+            raw = (src[b0:b1], b if self.raw[2] is None else self.raw[1], self.raw[2])   # (a ragged slice: its own S_raw is the lead stride)
+        s0, s1 = int(src[:b0].sum()), int(src[:b1].sum())
+        g = MaskedVarlenBatch(self.lengths[b0:b1], self.P, self.device, self.width, raw)
         if self.counts is not None:
             k0, k1 = int(self.counts[:b0].sum()), int(self.counts[:b1].sum())
             g.set_mask(self.idx_host[k0:k1], self.counts[b0:b1])
@@ -352,8 +450,10 @@ def check_masked_varlen_input(x, mask_idx, lengths, mask_counts, *, C, P, max_le
     if lengths is None and mask_counts is None and not ragged:
         return None
     what = 'ragged batches' if ragged else 'per-record lengths'
-    if input_transform is not None:
-        raise ValueError(f'{what} are not supported with a fused input transform (its TimeEndPad pads every record)')
+    per_record = input_transform is not None and input_transform.per_record
+    if input_transform is not None and not per_record:
+        raise ValueError(f'{what} are not supported with a fused input transform (its TimeEndPad pads every record) '
+                         f'unless it is built with per_record=True')
     if fp8:
         raise ValueError(f'{what} are not supported with fp8_linear')
     if ragged and dtype != torch.bfloat16:
@@ -367,6 +467,15 @@ def check_masked_varlen_input(x, mask_idx, lengths, mask_counts, *, C, P, max_le
     if mask_counts is None:
         raise ValueError('lengths needs mask_counts: with per-record lengths mask_idx is flat (record-local indices, record 0\'s first) and '
                          'mask_counts (B,) says how many belong to each record')
+    if per_record:   # lengths are RAW sample counts; the token geometry is that of the padded lengths
+        if ragged:
+            raw, t = check_raw_lengths(lengths, input_transform, max_len, S=x.shape[1])
+            width, rawinfo = None, (raw, x.shape[1], None)
+        else:
+            raw, t = check_raw_lengths(lengths, input_transform, max_len, B=x.shape[0], width=x.shape[2])
+            width, rawinfo = int(t.max()), (raw, x.shape[2], C * x.shape[2])
+        idx, counts = check_mask_varlen(mask_idx, mask_counts, t // P)
+        return MaskedVarlenBatch(t, P, x.device, width, rawinfo).set_mask(idx, counts)
     if ragged:
         t = check_masked_lengths(lengths, P, max_len, S=x.shape[1])
         width = None
@@ -834,7 +943,9 @@ class VitEngine:
         pre = 'vit.'
         # a4: patch Rearrange (integer gather) + Linear(C*P, d)   [+ f2: Normalize / TimeEndPad / TimeOut fused into the load]
         xf = self.input_transform
-        if xf is not None:
+        if self.saved is not None and self.saved.get('raw') is not None:   # f2 per record: raw records of unequal length
+            self._gather_raw(x, self.saved['raw'], self.saved.get('training', True))
+        elif xf is not None:
             mean, inv_std = xf.device_stats(x.device)
             t0 = tl = None
             if xf.timeout and self.saved is not None and self.saved.get('training', True):
@@ -849,6 +960,42 @@ class VitEngine:
             check(lib().ecgvit_patch_gather(ptr(x), ptr(a['patches']), B, self.C, self.L, self.P, self.CP, T, stream()), 'patch_gather')
         self._gemm(GEMM_NT, a['patches'], W[pre + 'to_patch_embedding.1.weight'], a['tok'], B * self.n, self.d, self.CP, self.CP,
                  self.CP, self.d, epilogue=EPI_BIAS, bias=self.P32[pre + 'to_patch_embedding.1.bias'])
+
+    def _gather_raw(self, x, rs, training):
+        """f2 per record (`FusedInputTransform(per_record=True)`): Normalize / TimeEndPad / TimeOut of every record at its own raw length,
+        fused into the patch gather (reference: one record at a time on the host, ptb_dataset.py:132-149) -> act['patches'], rows as `rs`
+        (`RawSide`) lays them out.  TimeOut (training passes): the spans are drawn here, per record in batch order, so consecutive
+        micro-batches consume the generator as the unsplit batch does; two int32 per record through pinned memory."""
+        xf = self.input_transform
+        mean, inv_std = xf.device_stats(x.device)
+        t0 = tl = None
+        if xf.timeout and training:
+            span = _stage(xf.draw_timeout_records(rs.padded), x.device)
+            t0, tl = span[0], span[1]
+        self._xf_keep = (mean, inv_std, t0, tl, rs)   # keep the tables alive until the kernel has run
+        check(lib().ecgvit_patch_gather_transform_varlen(ptr(x), ptr(self.act['patches']), ptr(rs.src_off), rs.lead_stride, ptr(rs.raw_len),
+                                                         ptr(rs.n_patch), ptr(rs.row_off), rs.nrows, rs.n_max, rs.B, self.C, self.P, self.CP,
+                                                         ptr(mean), ptr(inv_std), ptr(t0), ptr(tl), hip.code(self.dtype), stream()),
+              'patch_gather_transform_varlen')
+
+    def check_raw_input(self, x, lengths):
+        """validate a padded (B, C, W) batch of RAW records for this engine's per-record input transform before anything launches ->
+        RawPaddedBatch.  lengths: the (B,) raw sample counts (`check_raw_lengths`; None = every record holds W samples), or the
+        RawPaddedBatch of x itself (validated once by the caller)."""
+        if self.fp8:
+            raise ValueError('per-record lengths are not supported with fp8_linear')
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != self.C or x.shape[0] < 1:
+            raise ValueError(f'a batch of raw records is (B, {self.C}, W), got {tuple(getattr(x, "shape", ()))}')
+        if isinstance(lengths, RawPaddedBatch):
+            if lengths.B != x.shape[0] or lengths.W != x.shape[2] or lengths.P != self.P or lengths.device != x.device:
+                raise ValueError(f'the RawPaddedBatch describes {lengths.B} records of width {lengths.W} at patch_size={lengths.P} on '
+                                 f'{lengths.device}, the batch is {tuple(x.shape)} on {x.device} at patch_size={self.P}')
+            return lengths
+        B, W = x.shape[0], x.shape[2]
+        if lengths is None:
+            lengths = torch.full((B,), W, dtype=torch.int64)
+        raw, padded = check_raw_lengths(lengths, self.input_transform, self.L_max, B=B, width=W)
+        return RawPaddedBatch(raw, padded, self.P, self.C, W, x.device)
 
     def _trunk_fwd(self, B, ph, seed, cls_only_last=False):
         """L x { x = Attn(LN(x)) + x ; x = FF(LN(x)) + x } on act['x0'] ([B*T, d]); returns the output slab (cls_only_last: the last
@@ -950,13 +1097,18 @@ class VitEngine:
             return self._forward_ragged(x, labels, weight, training, seed, want_mean, lengths)
         B = x.shape[0]
         assert x.shape[1] == self.C and x.dtype == torch.float32 and x.is_contiguous()
+        rp = None
         if self.input_transform is None:
             width = x.shape[2]
             if width != self.L_max and self.fp8:
                 raise ValueError(f'fp8_linear runs full-width batches only (max_signal_length={self.L_max}, got {width} samples)')
+        elif self.input_transform.per_record:   # RAW records: lengths are raw sample counts, the pass runs at the widest padded length
+            rp = self.check_raw_input(x, lengths)
+            width, lengths = rp.width, None
         else:
             if lengths is not None:
-                raise ValueError('per-record lengths are not supported with a fused input transform (its TimeEndPad pads every record)')
+                raise ValueError('per-record lengths are not supported with a fused input transform (its TimeEndPad pads every record) '
+                                 'unless it is built with per_record=True')
             assert self.input_transform.padded_length(x.shape[2]) == self.L_max, 'config.max_signal_length must be the padded length'
             width = self.L_max
         if lengths is not None and self.fp8:
@@ -970,6 +1122,8 @@ class VitEngine:
             ntok = check_lengths(lengths, B, self.P, width)
             if ntok is not None and not ntok.is_cuda:
                 ntok = ntok.pin_memory().to(x.device, non_blocking=True)
+        if rp is not None:
+            ntok = rp.ntok
         self._alloc(B)
         a, T = self.act, hip.code(self.dtype)
         l, st = lib(), stream()
@@ -977,7 +1131,7 @@ class VitEngine:
         ph = self.p_hidden if training else 0.0
         pe = self.p_emb if training else 0.0
         self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, labels=labels, weight=weight, masked=False, training=training, cls_only_last=cls_only_last,
-                          ntok=ntok, lengths=lengths is not None, ragged=None)
+                          ntok=ntok, lengths=lengths is not None or ntok is not None, ragged=None, raw=None if rp is None else rp.rawside)
         if self.fp8:
             # EVERY forward, eval included, starts from the scales of the pass before it (delayed scaling with a history of one pass): an
             # inference-only model otherwise keeps its first batch's scales forever and clamps larger activations silently.  No backward can be
@@ -1005,8 +1159,11 @@ class VitEngine:
     def check_ragged_input(self, x, lengths, labels=None):
         """validate a ragged (C, S) batch for this engine before anything launches -> RaggedBatch (`check_ragged`).  lengths may already be
         the RaggedBatch of x (validated once by the caller: no second read of the lengths); labels, when given, must hold one row per record"""
-        if self.input_transform is not None:
-            raise ValueError('ragged batches are not supported with a fused input transform (its TimeEndPad pads every record)')
+        xf = self.input_transform
+        per_record = xf is not None and xf.per_record
+        if xf is not None and not per_record:
+            raise ValueError('ragged batches are not supported with a fused input transform (its TimeEndPad pads every record) '
+                             'unless it is built with per_record=True')
         if self.fp8:
             raise ValueError('ragged batches are not supported with fp8_linear')
         if self.dtype != torch.bfloat16:
@@ -1016,10 +1173,14 @@ class VitEngine:
         if x.dtype != torch.float32 or not x.is_contiguous():
             raise ValueError('a ragged batch must be a contiguous float32 tensor')
         if isinstance(lengths, RaggedBatch):
-            if lengths.S != x.shape[1] or lengths.P != self.P or lengths.device != x.device:
-                raise ValueError(f'the RaggedBatch describes S={lengths.S} samples at patch_size={lengths.P} on {lengths.device}, '
+            if lengths.S_raw != x.shape[1] or lengths.P != self.P or lengths.device != x.device or (lengths.raw is not None) != per_record:
+                raise ValueError(f'the RaggedBatch describes S={lengths.S_raw} samples at patch_size={lengths.P} on {lengths.device}'
+                                 f'{" (raw records)" if lengths.raw is not None else ""}, '
                                  f'the batch is ({x.shape[0]}, {x.shape[1]}) on {x.device} at patch_size={self.P}')
             rg = lengths
+        elif per_record:   # (C, S_raw): lengths are RAW sample counts, the packed token rows those of the padded lengths
+            raw, padded = check_raw_lengths(lengths, xf, self.L_max, S=x.shape[1])
+            rg = RaggedBatch(padded, self.P, x.device, raw)
         else:
             rg = check_ragged(lengths, x.shape[1], self.P, self.L_max, device=x.device)
         if labels is not None and labels.shape[0] != rg.B:
@@ -1044,7 +1205,10 @@ class VitEngine:
                           ntok=None, lengths=True, ragged=rg)
         pre = 'vit.'
         # a4: the packed patch gather is the uniform one over the concatenation: patch row off_b / P + j is patch j of record b
-        check(lib().ecgvit_patch_gather(ptr(x), ptr(a['patches']), 1, self.C, rg.S, self.P, self.CP, T, st), 'patch_gather')
+        if rg.rawside is not None:   # raw records: transformed per record on the way, rows at the padded offsets
+            self._gather_raw(x, rg.rawside, training)
+        else:
+            check(lib().ecgvit_patch_gather(ptr(x), ptr(a['patches']), 1, self.C, rg.S, self.P, self.CP, T, st), 'patch_gather')
         self._gemm(GEMM_NT, a['patches'], self.W[pre + 'to_patch_embedding.1.weight'], a['tok'], M - B, d, self.CP, self.CP, self.CP, d,
                    epilogue=EPI_BIAS, bias=self.P32[pre + 'to_patch_embedding.1.bias'])
         check(l.ecgvit_embed_finish_ragged(ptr(a['tok']), ptr(self.P32[pre + 'cls_token']), ptr(self.P32[pre + 'pos_embedding']), ptr(a['x0']),
@@ -1122,7 +1286,9 @@ class VitEngine:
         pe = self.p_emb if training else 0.0
         self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, masked=True, idx=geo.rows, m=mt, training=training, geo=geo, lengths=True,
                           ntok=None if packed else geo.n_tok, ragged=geo if packed else None)
-        if packed:   # the uniform gather over the concatenation: patch row off_b / P + j is patch j of record b
+        if geo.rawside is not None:   # raw records under a per-record transform: either row layout, transformed on the way
+            self._gather_raw(x, geo.rawside, training)
+        elif packed:   # the uniform gather over the concatenation: patch row off_b / P + j is patch j of record b
             check(l.ecgvit_patch_gather(ptr(x), ptr(a['patches']), 1, self.C, geo.S, self.P, self.CP, T, st), 'patch_gather')
         else:        # zero patches past each record's length (n_cls = n_b + 1: the kernel's count includes a CLS token)
             check(l.ecgvit_patch_gather_varlen(ptr(x), ptr(a['patches']), ptr(geo.n_cls), B, self.C, self.L, self.P, self.CP, T, st), 'patch_gather_varlen')

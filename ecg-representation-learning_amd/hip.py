@@ -85,6 +85,7 @@ SIGNATURES = {
     'ecgvit_attention_varlen_cls_bwd': (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _U, _P]),
     'ecgvit_softmax_rows_varlen': (c_int, [_P, _P, _I, _I, _I, _L, _P]),
     'ecgvit_patch_gather_varlen': (c_int, [_P, _P, _P, _I, _I, _I, _I, _L, _I, _P]),
+    'ecgvit_patch_gather_transform_varlen': (c_int, [_P, _P, _P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _I, _P]),
     'ecgvit_attention_ragged_fwd': (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _U, _P]),
     'ecgvit_attention_ragged_bwd': (c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _U, _P]),
     'ecgvit_attention_ragged_cls_fwd': (c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _U, _P]),

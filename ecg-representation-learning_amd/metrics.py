@@ -16,7 +16,7 @@ dataset metadata is out of scope here, so pass `id2code` (a list of 71 names) or
 import torch
 
 from . import hip
-from .engine import ragged_slice
+from .engine import ragged_slice, RawPaddedBatch
 from .hip import lib, check, ptr, stream
 
 
@@ -79,7 +79,8 @@ class HipEvaluator:
     def evaluate(self, sample_values, labels, return_predictions=False, lengths=None):
         """sample_values: (n, C, L) f32 device tensor (this rank's shard), labels: (n, K) f32; lengths: optional (n,) per-record sample
         counts (EcgVit.forward), sliced with the batches.  A ragged (C, S) batch with its (n,) lengths is cut by record range: eval_batch_size
-        records per call, each a ragged batch of its own."""
+        records per call, each a ragged batch of its own.  Under a per-record input transform sample_values holds RAW records and lengths their
+        raw sample counts (the ragged form is then cut at the raw offsets); evaluation draws no TimeOut."""
         model = self.model
         training = model.training
         model.eval()
@@ -87,12 +88,17 @@ class HipEvaluator:
         if sample_values.dim() == 2:   # ragged: validated once, then cut by record range on the host offsets
             sample_values = sample_values.contiguous().float()
             lengths = model._engine().check_ragged_input(sample_values, lengths, labels)
+        elif getattr(getattr(model, '_input_transform', None), 'per_record', False):
+            # RAW records (n, C, W) with raw lengths: validated once, every batch runs at the set's pass width (eval: no TimeOut)
+            lengths = model._engine().check_raw_input(sample_values, lengths)
         logits = torch.empty(n, K, dtype=torch.float32, device=labels.device)
         losses = []
         with torch.no_grad():
             for s in range(0, n, self.bsz):
                 if sample_values.dim() == 2:
                     xs, ls = ragged_slice(sample_values, lengths, s, min(s + self.bsz, n))
+                elif isinstance(lengths, RawPaddedBatch):
+                    xs, ls = sample_values[s:s + self.bsz], lengths.records(s, min(s + self.bsz, n))
                 else:
                     xs, ls = sample_values[s:s + self.bsz], None if lengths is None else lengths[s:s + self.bsz]
                 out = model(sample_values=xs, labels=labels[s:s + self.bsz], lengths=ls)

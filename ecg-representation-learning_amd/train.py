@@ -28,7 +28,7 @@ import torch.distributed as dist
 from .check_args import ca
 from . import hip
 from . import ddp
-from .engine import check_lengths, ragged_slice
+from .engine import check_lengths, ragged_slice, RawPaddedBatch
 
 
 def get_train_args(args=None, n_train=None):
@@ -236,7 +236,8 @@ class HipTrainStep:
         micro_batch_size: as `step` (None: the default given in args); the loss is the whole batch's mean.
         lengths, mask_counts: records of unequal length (MaskedEcgVit.forward) -- sample_values (B, C, L') or a ragged (C, S) batch, mask_idx
         flat; micro-batches are then record ranges (a ragged one a ragged batch of its own), pass j weighted by its share of the masked
-        patches.  Returns (loss, reconstruction (sum m_b, C*P))."""
+        patches.  Under a per-record input transform lengths are RAW sample counts and record b has padded_length(l_b) / P patches; the
+        targets are the transformed patches.  Returns (loss, reconstruction (sum m_b, C*P))."""
         mb = self._micro_batch_size(micro_batch_size)
         wrapper, model = self.model, self.model.encoder
         geo = wrapper.check_varlen_input(sample_values, mask_idx, lengths, mask_counts)   # host work only, before anything launches
@@ -343,7 +344,10 @@ class HipTrainStep:
         optimiser step (see the class docstring; with dropout each pass draws its own masks).  Returns (loss_mean, logits (B, K)) of the
         whole batch either way.
         sample_values may be a ragged (C, S) batch with its (B,) lengths (EcgVit.forward); micro-batches are then record ranges, each a
-        ragged batch of its own.  The last block then runs in full (no CLS-only pruning)."""
+        ragged batch of its own.  The last block then runs in full (no CLS-only pruning).
+        Under a per-record input transform (`FusedInputTransform(per_record=True)`) sample_values holds RAW records -- (B, C, W) or a ragged
+        (C, S_raw) batch -- and lengths their raw sample counts; TimeOut spans are drawn per record in batch order, micro-batch by
+        micro-batch, so the draws of a split step are those of the unsplit one."""
         mb = self._micro_batch_size(micro_batch_size)
         model = self.model
         if not model.training:
@@ -360,6 +364,9 @@ class HipTrainStep:
         if ragged:   # (C, S): validated once, before anything launches (the RaggedBatch travels on); B = the number of records
             sample_values = sample_values.contiguous().float()
             lengths = eng.check_ragged_input(sample_values, lengths, labels)
+        elif eng.input_transform is not None and eng.input_transform.per_record:
+            # RAW records (B, C, W): validated once (the RawPaddedBatch travels on, micro-batches keep the whole batch's pass width)
+            lengths = eng.check_raw_input(sample_values, lengths)
         if mb is not None and mb < (labels.shape[0] if ragged else sample_values.shape[0]):
             return self._step_micro(model, eng, sample_values, labels, lengths, mb, cls_only)
         seed = self._dropout_seed(model)
@@ -406,6 +413,8 @@ class HipTrainStep:
             seed = self._dropout_seed(model)
             if ragged:   # records s .. e - 1: a ragged batch of their own (host offsets, no device read)
                 xs, ls = ragged_slice(x, lengths, s, e)
+            elif isinstance(lengths, RawPaddedBatch):
+                xs, ls = x[s:e], lengths.records(s, e)
             else:
                 xs, ls = x[s:e], None if lengths is None else lengths[s:e]
             logits, _, _ = eng.forward(xs, y[s:e], None if w is None else w[s:e], training=True, seed=seed, want_mean=False,

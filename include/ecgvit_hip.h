@@ -159,6 +159,18 @@ int ecgvit_patch_gather(const float *x, void *patches, int B, int C, int L, int 
 int ecgvit_patch_gather_transform(const float *x_raw, void *patches, int B, int C, int L_raw, int L, int P, int64_t ld,
                                   const float *mean, const float *inv_std, const int32_t *timeout_start,
                                   const int32_t *timeout_len, int dtype, void *stream);
+/* The fused transforms PER RECORD, for records of unequal raw length -- what the reference does to one record at a time on the host
+ * (preprocess/ptb_dataset.py:132-149: Normalize, TimeEndPad(patch_size), TimeOut; preprocess/transform.py:18-35, :140-154, :175-185).
+ * Record b: raw_len[b] samples per lead, lead c at x + src_off[b] + c * lead_stride (lead_stride = W of a padded (B, C, W) batch with
+ * src_off[b] = b C W, or S_raw of a ragged (C, S_raw) batch with src_off[b] = the raw sample offset); normalised, zero-padded in
+ * normalised space to n_patch[b] * P samples, samples [timeout_start[b], + timeout_len[b]) of the padded record zeroed; its patch rows
+ * are rows row_off[b] .. of `patches`.  n_rows_per_record = 0: packed rows, record b writes n_patch[b] rows; > 0 (>= n_max): padded rows,
+ * record b writes that many, exact zeros past n_patch[b].  n_max >= every n_patch[b] (sizes the launch; a larger table entry is clamped).
+ * Samples at or past raw_len[b] are never read.  Tables: device pointers, [B]; timeout_*: both NULL (eval) or both set. */
+int ecgvit_patch_gather_transform_varlen(const float *x, void *patches, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len,
+                                         const int32_t *n_patch, const int32_t *row_off, int n_rows_per_record, int n_max, int B, int C, int P,
+                                         int64_t ld, const float *mean, const float *inv_std, const int32_t *timeout_start,
+                                         const int32_t *timeout_len, int dtype, void *stream);
 /* Same gather for variable-length records (attention_varlen.hip): n_tok int32 [B] on the device; patch p of record b is gathered for
  * p < n_tok[b] - 1 and zero past it (the samples there are never read). */
 int ecgvit_patch_gather_varlen(const float *x, void *patches, const int32_t *n_tok, int B, int C, int L, int P, int64_t ld, int dtype,
