@@ -337,6 +337,34 @@ class EcgVit(nn.Module):
         loss, logits = _EcgVitFunction.apply(self, x, y, w, self._loss_reduction, lengths, *self._own_list)
         return ModelOutput(loss=loss if labels is not None else None, logits=logits)
 
+    def encode(self, sample_values: torch.FloatTensor, lengths: torch.Tensor = None, pool: str = 'cls', norm: bool = True) -> torch.Tensor:
+        """One vector per record: (B, hidden_size) float32 on the device, a fresh tensor without autograd history.
+        sample_values / lengths: every batch form `forward` takes on this engine -- (B, C, L'), `lengths=`, a ragged (C, S) batch, raw records
+        under `FusedInputTransform(per_record=True)` -- with the same validation and the same refusals.
+        Always an EVAL pass (no dropout, no TimeOut), whatever `self.training` says, which is left as it was; runs under `torch.no_grad()`.
+        pool='cls': the record's CLS row of the trunk output; with norm=True exactly what the classifier's Linear reads, so
+        `F.linear(encode(x), vit.mlp_head[1].weight, vit.mlp_head[1].bias)` is `self(x).logits` in eval mode.  On the bf16 engine without
+        fp8_linear a (B, C, L') batch runs its last block for the CLS rows only; ragged batches and fp8_linear run it in full.
+        pool='mean': the mean over the record's own tokens, CLS row included (`pool='mean'` of vit_pytorch); always the full last block.
+        norm=True: through `vit.mlp_head.0` (LayerNorm);  norm=False: the pooled residual-stream vector (what `HipProbeStep.step` takes).
+        Like any forward it overwrites the engine's activations: a backward still pending from an earlier forward then raises "a later forward
+        overwrote the activations" -- call `backward()` first."""
+        if pool not in VitEngine.POOL_MODES:
+            raise ValueError(f"pool must be 'cls' or 'mean', got {pool!r}")
+        if not sample_values.is_cuda:
+            raise RuntimeError('EcgVit (HIP) runs on an MI355X device only: move the model and inputs to "cuda" '
+                               '(there is deliberately no CPU fallback)')
+        if sample_values.dim() not in (2, 3):
+            raise ValueError(f'sample_values must be (B, C, L) or a ragged (C, S) batch, got {tuple(sample_values.shape)}')
+        x = sample_values.detach().contiguous().float()
+        with torch.no_grad():
+            eng = self._engine()
+            if x.dim() == 2:   # validated once, before anything launches; the engine takes the RaggedBatch
+                lengths = eng.check_ragged_input(x, lengths)
+            out = eng.encode(x, lengths=lengths, pool=pool, norm=norm)
+        self._fwd_id += 1   # the activations of an earlier forward are gone: its pending backward raises
+        return out
+
     def trainable_names(self):
         """names of the parameters with requires_grad=True (attached pre-train parameters included), or None when every parameter is trainable.
         The backward passes skip the work only frozen parameters need (`engine.BackwardPlan`); their `.grad` stays None."""

@@ -1095,6 +1095,26 @@ class VitEngine:
         would give alone at x[b:b+1, :, :lengths[b]] (dropout 0; up to summation order).  Not with fp8_linear or a fused input transform."""
         if x.dim() == 2:
             return self._forward_ragged(x, labels, weight, training, seed, want_mean, lengths)
+        B, X = self._trunk_pass(x, labels, weight, training, seed, cls_only_last, lengths)
+        a, T = self.act, hip.code(self.dtype)
+        l, st = lib(), stream()
+        d, N = self.d, self.N
+        pre = 'vit.'
+        cls_only_last = self.saved['cls_only_last']
+        # a10: x[:, 0] -> LayerNorm -> Linear(d, K)   (cls_only_last: X holds the CLS rows only)
+        check(l.ecgvit_head_fwd(ptr(X), 1 if cls_only_last else N, ptr(self.P32[pre + 'mlp_head.0.weight']), ptr(self.P32[pre + 'mlp_head.0.bias']),
+                                ptr(self.P32[pre + 'mlp_head.1.weight']), ptr(self.P32[pre + 'mlp_head.1.bias']),
+                                ptr(a['logits']), ptr(a['xhat']), ptr(a['hrstd']), B, d, self.K, LN_EPS, T, st), 'head_fwd')
+        if labels is None:
+            return a['logits'], None, None
+        # a11: BCEWithLogitsLoss
+        check(l.ecgvit_bce_fwd(ptr(a['logits']), ptr(labels), ptr(weight), ptr(a['loss_elem']),
+                               ptr(a['loss_mean']) if want_mean else None, B * self.K, st), 'bce_fwd')
+        return a['logits'], a['loss_elem'], (a['loss_mean'] if want_mean else None)
+
+    def _trunk_pass(self, x, labels, weight, training, seed, cls_only_last, lengths):
+        """`forward` of a (B, C, L') batch up to the trunk's output: validation, geometry, slabs, patch embedding, the L blocks.  Returns
+        (B, X) with X = saved['xL'], the last block's output ([B * N, d], or the compact CLS rows [B, d] under cls_only_last)"""
         B = x.shape[0]
         assert x.shape[1] == self.C and x.dtype == torch.float32 and x.is_contiguous()
         rp = None
@@ -1145,16 +1165,7 @@ class VitEngine:
                                     ptr(a['x0']), B, n, d, pe, seed + 1, T, st), 'embed_finish')
         X = self._trunk_fwd(B, ph, seed, cls_only_last)
         self.saved['xL'] = X
-        # a10: x[:, 0] -> LayerNorm -> Linear(d, K)   (cls_only_last: X holds the CLS rows only)
-        check(l.ecgvit_head_fwd(ptr(X), 1 if cls_only_last else N, ptr(self.P32[pre + 'mlp_head.0.weight']), ptr(self.P32[pre + 'mlp_head.0.bias']),
-                                ptr(self.P32[pre + 'mlp_head.1.weight']), ptr(self.P32[pre + 'mlp_head.1.bias']),
-                                ptr(a['logits']), ptr(a['xhat']), ptr(a['hrstd']), B, d, self.K, LN_EPS, T, st), 'head_fwd')
-        if labels is None:
-            return a['logits'], None, None
-        # a11: BCEWithLogitsLoss
-        check(l.ecgvit_bce_fwd(ptr(a['logits']), ptr(labels), ptr(weight), ptr(a['loss_elem']),
-                               ptr(a['loss_mean']) if want_mean else None, B * self.K, st), 'bce_fwd')
-        return a['logits'], a['loss_elem'], (a['loss_mean'] if want_mean else None)
+        return B, X
 
     def check_ragged_input(self, x, lengths, labels=None):
         """validate a ragged (C, S) batch for this engine before anything launches -> RaggedBatch (`check_ragged`).  lengths may already be
@@ -1192,6 +1203,25 @@ class VitEngine:
         kernel runs over the M = S / P + B packed token rows; attention per record on the packed rows; the classifier reads the CLS rows
         tok_off[b].  The last block always runs in full (no cls_only_last).  Hidden and embedding dropout draw their bits by packed element
         index, so a ragged step does not draw the masks of the padded step of the same records (attention dropout does, on the valid region)."""
+        rg, X = self._trunk_pass_ragged(x, labels, weight, training, seed, lengths)
+        B, M = rg.B, rg.M
+        a, T = self.act, hip.code(self.dtype)
+        l, st = lib(), stream()
+        d = self.d
+        pre = 'vit.'
+        # a10: the CLS rows tok_off[b], gathered compact, -> LayerNorm -> Linear(d, K)
+        check(l.ecgvit_gather_rows(ptr(X), ptr(rg.tok_off), ptr(a['cls_x2']), 1, M, B, d, d, d, T, st), 'gather_rows')
+        check(l.ecgvit_head_fwd(ptr(a['cls_x2']), 1, ptr(self.P32[pre + 'mlp_head.0.weight']), ptr(self.P32[pre + 'mlp_head.0.bias']),
+                                ptr(self.P32[pre + 'mlp_head.1.weight']), ptr(self.P32[pre + 'mlp_head.1.bias']),
+                                ptr(a['logits']), ptr(a['xhat']), ptr(a['hrstd']), B, d, self.K, LN_EPS, T, st), 'head_fwd')
+        if labels is None:
+            return a['logits'], None, None
+        check(l.ecgvit_bce_fwd(ptr(a['logits']), ptr(labels), ptr(weight), ptr(a['loss_elem']),
+                               ptr(a['loss_mean']) if want_mean else None, B * self.K, st), 'bce_fwd')
+        return a['logits'], a['loss_elem'], (a['loss_mean'] if want_mean else None)
+
+    def _trunk_pass_ragged(self, x, labels, weight, training, seed, lengths):
+        """`_forward_ragged` up to the trunk's output -> (RaggedBatch, X) with X = saved['xL'], the packed rows [M, d]"""
         rg = self.check_ragged_input(x, lengths, labels)
         B, M = rg.B, rg.M
         self._set_width((rg.N - 1) * self.P)
@@ -1215,16 +1245,52 @@ class VitEngine:
                                            ptr(rg.n_tok), ptr(rg.tok_off), B, N, d, pe, seed + 1, T, st), 'embed_finish_ragged')
         X = self._trunk_fwd(B, ph, seed)
         self.saved['xL'] = X
-        # a10: the CLS rows tok_off[b], gathered compact, -> LayerNorm -> Linear(d, K)
-        check(l.ecgvit_gather_rows(ptr(X), ptr(rg.tok_off), ptr(a['cls_x2']), 1, M, B, d, d, d, T, st), 'gather_rows')
-        check(l.ecgvit_head_fwd(ptr(a['cls_x2']), 1, ptr(self.P32[pre + 'mlp_head.0.weight']), ptr(self.P32[pre + 'mlp_head.0.bias']),
-                                ptr(self.P32[pre + 'mlp_head.1.weight']), ptr(self.P32[pre + 'mlp_head.1.bias']),
-                                ptr(a['logits']), ptr(a['xhat']), ptr(a['hrstd']), B, d, self.K, LN_EPS, T, st), 'head_fwd')
-        if labels is None:
-            return a['logits'], None, None
-        check(l.ecgvit_bce_fwd(ptr(a['logits']), ptr(labels), ptr(weight), ptr(a['loss_elem']),
-                               ptr(a['loss_mean']) if want_mean else None, B * self.K, st), 'bce_fwd')
-        return a['logits'], a['loss_elem'], (a['loss_mean'] if want_mean else None)
+        return rg, X
+
+    # ---------------------------------------------------------------- pooled representations (EcgVit.encode)
+    POOL_MODES = {'cls': hip.POOL_CLS, 'mean': hip.POOL_MEAN}
+
+    def encode(self, x, lengths=None, pool='cls', norm=True):
+        """One vector per record, (B, d) f32 in a fresh tensor: an EVAL pass (no dropout, no TimeOut) of `forward` up to the trunk's output,
+        then one `ecgvit_pool_records` launch.  x / lengths: every batch form `forward` takes, with its validation and refusals.
+        pool 'cls': the record's CLS row (bf16 engine without fp8_linear, padded batches: the last block runs for the CLS rows only);
+        'mean': the mean over the record's own tokens, CLS row included (the full last block).  norm: through vit.mlp_head.0 (LayerNorm).
+        Overwrites the activations like any forward."""
+        if pool not in self.POOL_MODES:
+            raise ValueError(f"pool must be 'cls' or 'mean', got {pool!r}")
+        if x.dim() == 2:
+            self._trunk_pass_ragged(x, None, None, False, 0, lengths)
+        else:
+            prune = pool == 'cls' and self.dtype == torch.bfloat16 and not self.fp8
+            self._trunk_pass(x, None, None, False, 0, prune, lengths)
+        return self.pool_saved(pool, norm)
+
+    def pool_saved(self, pool='cls', norm=True):
+        """pool the trunk output of the LAST supervised forward (saved['xL']) on its own row base: the padded rows with the per-record token
+        counts, the packed rows of a ragged batch, or the compact CLS rows of a pruned last block (which hold no other row: pool='mean' then
+        raises ValueError)"""
+        if pool not in self.POOL_MODES:
+            raise ValueError(f"pool must be 'cls' or 'mean', got {pool!r}")
+        sv = self.saved
+        if sv is None or sv.get('masked') or sv.get('xL') is None:
+            raise RuntimeError('pool_saved needs the trunk output of a supervised forward')
+        rg = sv.get('ragged')
+        n_tok = tok_off = None
+        N = self.N
+        if sv.get('cls_only_last'):
+            if pool != 'cls':
+                raise ValueError("pool='mean' needs every token row: the last forward computed the last block's CLS rows only (cls_only_last)")
+            N = 1
+        elif rg is not None:
+            n_tok, tok_off = rg.n_tok, rg.tok_off
+        else:
+            n_tok = sv.get('ntok')
+        B, pre = sv['B'], 'vit.'
+        out = torch.empty((B, self.d), dtype=torch.float32, device=sv['xL'].device)
+        g, b = (self.P32[pre + 'mlp_head.0.weight'], self.P32[pre + 'mlp_head.0.bias']) if norm else (None, None)
+        check(lib().ecgvit_pool_records(ptr(sv['xL']), ptr(out), ptr(n_tok), ptr(tok_off), B, N, self.d, self.POOL_MODES[pool], ptr(g), ptr(b),
+                                        LN_EPS, hip.code(self.dtype), stream()), 'pool_records')
+        return out
 
     def _pass_rows(self, B):
         """token rows of the current pass: B x tokens per record, or the packed rows of a ragged batch"""

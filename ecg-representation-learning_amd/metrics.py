@@ -131,3 +131,41 @@ class HipEvaluator:
         if training:
             model.train()
         return dict(metrics=d, predictions=dict(labels=lb, logits=logits)) if return_predictions else d
+
+
+class HipEncoder:
+    """Pooled representations of a resident data set (`EcgVit.encode`), `batch_size` records per encoder pass: the feature cache of a linear
+    probe on frozen features (`HipProbeStep`), of clustering or retrieval.  pool / norm: as `EcgVit.encode`."""
+
+    def __init__(self, model, batch_size=64, pool='cls', norm=True):
+        if pool not in ('cls', 'mean'):
+            raise ValueError(f"pool must be 'cls' or 'mean', got {pool!r}")
+        self.model, self.bsz, self.pool, self.norm = model, int(batch_size), pool, bool(norm)
+        if self.bsz <= 0:
+            raise ValueError(f'batch_size must be positive, got {batch_size!r}')
+
+    def encode(self, sample_values, lengths=None):
+        """sample_values: (n, C, L') f32 device tensor with optional (n,) lengths, sliced with the batches, or a ragged (C, S) batch with its
+        (n,) lengths, cut by record range as `HipEvaluator.evaluate` cuts it (raw records and raw lengths under a per-record input transform).
+        Returns (n, hidden_size) f32 on the device, row r = record r."""
+        model = self.model
+        ragged = sample_values.dim() == 2
+        if ragged:   # validated once, then cut by record range on the host offsets
+            sample_values = sample_values.contiguous().float()
+            lengths = model._engine().check_ragged_input(sample_values, lengths)
+            n = lengths.B
+        else:
+            n = sample_values.shape[0]
+            if getattr(getattr(model, '_input_transform', None), 'per_record', False):
+                lengths = model._engine().check_raw_input(sample_values, lengths)   # every batch runs at the set's pass width
+        out = torch.empty(n, model.config.hidden_size, dtype=torch.float32, device=sample_values.device)
+        for s in range(0, n, self.bsz):
+            e = min(s + self.bsz, n)
+            if ragged:
+                xs, ls = ragged_slice(sample_values, lengths, s, e)
+            elif isinstance(lengths, RawPaddedBatch):
+                xs, ls = sample_values[s:e], lengths.records(s, e)
+            else:
+                xs, ls = sample_values[s:e], None if lengths is None else lengths[s:e]
+            out[s:e] = model.encode(xs, lengths=ls, pool=self.pool, norm=self.norm)
+        return out

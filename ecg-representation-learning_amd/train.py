@@ -28,7 +28,7 @@ import torch.distributed as dist
 from .check_args import ca
 from . import hip
 from . import ddp
-from .engine import check_lengths, ragged_slice, RawPaddedBatch
+from .engine import check_lengths, ragged_slice, RawPaddedBatch, LN_EPS
 
 
 def get_train_args(args=None, n_train=None):
@@ -589,6 +589,107 @@ class HipTrainStep:
     def finish(self):
         """drain the deferred non-finite check (call after the last step)"""
         self._raise_if_flagged(wait=True)
+
+
+class HipProbeStep(HipTrainStep):
+    """
+    The linear probe on CACHED features: `step(features, labels)` is the step `HipTrainStep.step` takes with every parameter but
+    `vit.mlp_head.*` frozen and dropout 0, started after the encoder instead of before it.  features: (B, hidden_size) f32 as
+    `EcgVit.encode(..., norm=False)` / `HipEncoder(model, norm=False).encode` return them (the pooled residual-stream vector: the head's own
+    LayerNorm is part of what is trained).
+
+    One step: `ecgvit_head_fwd` over one row per record, BCE with the model's `loss_weight` and 'mean' reduction, `ecgvit_head_bwd`, the
+    global clip at `max_grad_norm` with the non-finite error, AdamW (torch defaults) and the warm-up / cosine schedule of `args` -- the
+    kernels, hyper-parameters and `get_last_lr()` / `grad_norm()` / `finish()` surface of `HipTrainStep`, over the head's range of the flat
+    buffers only (its optimiser moments are the only state this class allocates).  The encoder parameters are neither read nor written and
+    need not be frozen; no encoder activation is touched, so a step never invalidates a pending backward.  Single device; no micro-batches.
+    """
+
+    def __init__(self, model, args=None, max_grad_norm=1.0, sync_nonfinite=True):
+        super().__init__(model, args, max_grad_norm=max_grad_norm, sync_nonfinite=sync_nonfinite)
+        self.world, self.rank, self.collectives = 1, 0, False   # single device by definition
+        self._buf = None
+
+    def step_masked(self, *a, **kw):
+        raise TypeError('HipProbeStep trains the classification head on cached features: it has no masked step')
+
+    def _state(self):
+        model = self.model
+        model._engine()
+        lo, hi = model._layout.span(lambda n: n.startswith('vit.mlp_head.'))
+        dev = model._pflat.device
+        if self.m is None or self.m.device != dev or self.m.numel() != hi - lo:
+            self.m = torch.zeros(hi - lo, device=dev, dtype=torch.float32)
+            self.v = torch.zeros_like(self.m)
+            self.norm_out = torch.zeros(2, device=dev, dtype=torch.float32)
+            self.norm_host = torch.ones(2, dtype=torch.float32).pin_memory()
+            self.sumsq_host = torch.zeros(1, dtype=torch.float32).pin_memory()
+            self._flag_event = torch.cuda.Event()
+            self._norm_event = torch.cuda.Event()
+            self.sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
+            self.ws = torch.empty(hip.lib().ecgvit_sumsq_workspace(hi - lo), device=dev, dtype=torch.uint8)
+        return lo, hi
+
+    def step(self, features, labels):
+        """features (B, hidden_size) f32 on the device, labels (B, K).  Returns (loss_mean, logits (B, K)), fresh tensors."""
+        model = self.model
+        if not features.is_cuda:
+            raise RuntimeError('HipProbeStep runs on the device (no CPU fallback exists): pass device tensors')
+        d, K = model.config.hidden_size, model.num_class
+        if features.dim() != 2 or features.shape[1] != d:
+            raise ValueError(f'features must be (B, hidden_size={d}) as EcgVit.encode(..., norm=False) returns them, got {tuple(features.shape)}')
+        if labels.dim() != 2 or tuple(labels.shape) != (features.shape[0], K):
+            raise ValueError(f'labels must be (B={features.shape[0]}, {K}), got {tuple(labels.shape)}')
+        lo, hi = self._state()
+        self._raise_if_flagged()
+        eng = model._engine()
+        x = features.detach().contiguous().float()
+        y = labels.contiguous().float()
+        B = x.shape[0]
+        w = None
+        if model.loss_weight:
+            w = torch.tensor(model.loss_weight, device=y.device, dtype=torch.float32)[y.long()].contiguous()
+        if self._buf is None or self._buf['xhat'].shape[0] != B or self._buf['xhat'].device != x.device:
+            f32 = dict(device=x.device, dtype=torch.float32)
+            self._buf = dict(xhat=torch.empty((B, d), **f32), hrstd=torch.empty(B, **f32), loss_elem=torch.empty((B, K), **f32),
+                             dlogits=torch.empty((B, K), **f32), dx=torch.empty((B, d), **f32))
+        a = self._buf
+        logits = torch.empty((B, K), device=x.device, dtype=torch.float32)
+        loss = torch.empty(1, device=x.device, dtype=torch.float32)
+        l, st, ptr = hip.lib(), hip.stream(), hip.ptr
+        P, G, pre = eng.P32, eng.G32, 'vit.mlp_head.'
+        hip.check(l.ecgvit_head_fwd(ptr(x), 1, ptr(P[pre + '0.weight']), ptr(P[pre + '0.bias']), ptr(P[pre + '1.weight']), ptr(P[pre + '1.bias']),
+                                    ptr(logits), ptr(a['xhat']), ptr(a['hrstd']), B, d, K, LN_EPS, hip.F32, st), 'head_fwd')
+        hip.check(l.ecgvit_bce_fwd(ptr(logits), ptr(y), ptr(w), ptr(a['loss_elem']), ptr(loss), B * K, st), 'bce_fwd')
+        hip.check(l.ecgvit_bce_bwd(ptr(logits), ptr(y), ptr(w), ptr(self._one(x.device)), None, 1.0 / (B * K), ptr(a['dlogits']), B * K, st),
+                  'bce_bwd')
+        hip.check(l.ecgvit_head_bwd(ptr(a['dlogits']), ptr(a['xhat']), ptr(a['hrstd']), ptr(P[pre + '0.weight']), ptr(P[pre + '0.bias']),
+                                    ptr(P[pre + '1.weight']), ptr(G[pre + '1.weight']), ptr(G[pre + '1.bias']), ptr(G[pre + '0.weight']),
+                                    ptr(G[pre + '0.bias']), ptr(a['dx']), 1, B, d, K, hip.F32, st), 'head_bwd')
+        self._keep = (x, y, w)   # alive until the kernels that read them have run
+        self._update_head(model, lo, hi)
+        self.last_loss = loss
+        return loss, logits
+
+    def _update_head(self, model, lo, hi):
+        """`HipTrainStep._update` over the head's range [lo, hi) of the flat buffers (the alignment padding inside it holds zeros and stays
+        zero): the norm of the head's gradient, the early read of it, clip + AdamW at the head's own step count, the bf16 shadow of the head"""
+        l, st = hip.lib(), hip.stream()
+        g, p = model._gflat[lo:hi], model._pflat[lo:hi]
+        hip.check(l.ecgvit_sumsq(g.data_ptr(), hi - lo, self.sumsq.data_ptr(), self.ws.data_ptr(), st), 'sumsq')
+        self.sumsq_host.copy_(self.sumsq, non_blocking=True)
+        self._flag_event.record()
+        self.step_count += 1
+        lr = self.lr0 * self.mult(self.step_count - 1)  # lr in effect for this optimiser step
+        wlow = model._wlow[lo:hi].data_ptr() if model._wlow is not None else None
+        hip.check(l.ecgvit_adamw_step(p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), wlow, hi - lo, self.sumsq.data_ptr(),
+                                      1.0, self.max_grad_norm, lr, 0.9, 0.999, 1e-8, self.wd, self.step_count, 1 if self.decoupled else 0,
+                                      self.norm_out.data_ptr(), st), 'adamw_step')
+        self.norm_host.copy_(self.norm_out, non_blocking=True)
+        self._norm_event.record()
+        self._flag_pending = True
+        if self.sync_nonfinite:
+            self._raise_if_flagged(wait=True)
 
 
 def span_table(layout, names, flags, lag):

@@ -435,6 +435,19 @@ int ecgvit_l1_loss_fwd_bwd(const void *pred, const void *target, float *loss, vo
 int ecgvit_eval_counts(const float *scores, int64_t ld_scores, const float *labels, int64_t ld_labels, int64_t B, int K, int from_logits,
                        int with_auc, uint64_t *counts, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * record pooling (EcgVit.encode): one f32 vector per record from its token rows.  Additive entry point: the ABI version stays 6.
+ * x: token rows [*, d] (dtype bf16 / f32); record b holds n_tok[b] rows (N when n_tok is NULL; 1 <= n_tok[b] <= N) starting at row
+ * tok_off[b] (b * N when tok_off is NULL) -- int32 device arrays, the convention of ecgvit_attention_ragged_* / ecgvit_embed_finish_ragged.
+ * mode 0: the record's row 0 (the CLS row);  mode 1: the mean over its n_tok[b] rows, CLS row included (vit_pytorch pool='mean').
+ * Rows at or past n_tok[b] are never read.  gamma / beta non-NULL (both or neither): LayerNorm over d (biased variance, eps) of the pooled
+ * f32 vector before the store (vit.mlp_head.0: what the classifier's Linear reads).  out: [B, d] f32, compact.
+ * d a multiple of 8, at most 2048.  f32 accumulation in an order fixed by the record's own row count: no atomics, bit-reproducible, and
+ * independent of B, of the other records and of the row base (packed and padded rows pool to the same bits).
+ * ------------------------------------------------------------------------------------------------ */
+int ecgvit_pool_records(const void *x, float *out, const int32_t *n_tok, const int32_t *tok_off, int B, int N, int d, int mode,
+                        const float *gamma, const float *beta, float eps, int dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
