@@ -35,6 +35,7 @@ from .engine import VitEngine, ParamLayout, MaskedVarlenBatch, check_masked_varl
 from . import hip
 
 ModelOutput = namedtuple('ModelOutput', ['loss', 'logits'])  # reference util/models.py:3
+RolloutOutput = namedtuple('RolloutOutput', ['logits', 'maps', 'patch_counts'])  # EcgVit.attention_rollout_batch
 
 
 def log_dict_p(d):
@@ -364,6 +365,35 @@ class EcgVit(nn.Module):
             out = eng.encode(x, lengths=lengths, pool=pool, norm=norm)
         self._fwd_id += 1   # the activations of an earlier forward are gone: its pending backward raises
         return out
+
+    def attention_rollout_batch(self, sample_values: torch.FloatTensor, lengths: torch.Tensor = None) -> 'RolloutOutput':
+        """The attention map of `attention_rollout` for every record of a batch: RolloutOutput(logits (B, K), maps (B, layers, n_max) f32 on the
+        device, patch_counts (B,) int64 on the host).  Row b of `maps` is the map the reference's visualiser derives for record b alone
+        (ecg_vit.py:164-194: head-averaged attention + identity, row-normalised, multiplied with the layer below, CLS row, scaled by the
+        record's own maximum), with exact zeros past its patch_counts[b] patches; n_max = max(patch_counts).
+        sample_values / lengths: every batch form `forward` takes on this engine -- (B, C, L'), `lengths=`, a ragged (C, S) batch, raw records
+        under `FusedInputTransform(per_record=True)` -- with the same validation and the same refusals.
+        Always an EVAL pass (no dropout, no TimeOut), whatever `self.training` says, which is left as it was; runs under `torch.no_grad()`.
+        No (N, N) matrix is held on the bf16 engine: the weighted column sums the map consists of are rebuilt tile by tile from the qkv and
+        log-sum-exp of the pass, so the extra memory is O(B h N).  Like any forward it overwrites the engine's activations: a backward still
+        pending from an earlier forward then raises "a later forward overwrote the activations" -- call `backward()` first."""
+        if sample_values.dim() not in (2, 3):
+            raise ValueError(f'sample_values must be (B, C, L) or a ragged (C, S) batch, got {tuple(sample_values.shape)}')
+        if not sample_values.is_cuda:
+            raise RuntimeError('EcgVit (HIP) runs on an MI355X device only: move the model and inputs to "cuda" '
+                               '(there is deliberately no CPU fallback)')
+        x = sample_values.detach().contiguous().float()
+        with torch.no_grad():
+            eng = self._engine()
+            if x.dim() == 2:   # validated once, before anything launches; the engine takes the RaggedBatch
+                lengths = eng.check_ragged_input(x, lengths)
+            logits = eng.forward(x, None, None, training=False, seed=0, lengths=lengths)[0].clone()
+            maps, counts = eng.attention_rollout_saved()
+        self._fwd_id += 1   # the activations of an earlier forward are gone: its pending backward raises
+        n_max = int(counts.max())
+        if n_max != maps.shape[2]:   # a `lengths=` batch wider than its widest record
+            maps = maps[:, :, :n_max].contiguous()
+        return RolloutOutput(logits=logits, maps=maps, patch_counts=counts)
 
     def trainable_names(self):
         """names of the parameters with requires_grad=True (attached pre-train parameters included), or None when every parameter is trainable.

@@ -1808,6 +1808,60 @@ class VitEngine:
         self._gemm(GEMM_NN, dP, qkv, dqkv, N, dh, N, N, 3 * d, 3 * d, batch=(B, h), strideA=sp, strideB=sq, strideC=sq, b_off=d)
         self._gemm(GEMM_TN, dP, qkv, dqkv, N, dh, N, N, 3 * d, 3 * d, batch=(B, h), strideA=sp, strideB=sq, strideC=sq, c_off=d)
 
+    # ---------------------------------------------------------------- attention rollout of a whole batch (f3)
+    def attention_rollout_saved(self):
+        """The reference visualiser's CLS-to-patch attention map (ecg_vit.py:164-194) of EVERY record of the last supervised forward, from the
+        activations it left behind: one `ecgvit_rollout_cls` per layer, one `ecgvit_rollout_colsum` per layer pair (i, i - 1), one
+        `ecgvit_rollout_finish`.  No (N, N) matrix is built on the bf16 engine (P is rebuilt tile by tile from qkv / lse); the f32 engine reads
+        the probabilities it keeps.  The row layout is the forward's own: packed rows of a ragged batch, per-record token counts, or neither.
+        Returns (maps (B, Ly, N_pass - 1) f32 in a fresh tensor, exact zeros past each record's patches and each record scaled to a maximum of
+        1, patch counts (B,) int64 on the host)."""
+        sv = self.saved
+        if sv is None:
+            raise RuntimeError('attention rollout needs the activations of a supervised forward')
+        if sv.get('masked'):
+            raise RuntimeError('the last forward ran the masked objective: its attention rollout is not available')
+        if sv.get('cls_only_last'):
+            raise RuntimeError('the last forward ran with cls_only_last: its last block computed the CLS query only')
+        rg = sv.get('ragged')
+        n_tok = tok_off = None
+        if rg is not None:
+            n_tok, tok_off = rg.n_tok, rg.tok_off
+        else:
+            n_tok = sv.get('ntok')
+        B, N, h, dh, Ly = sv['B'], self.T, self.h, self.dh, self.Ly
+        layers = self.act['layers']
+        dev = layers[0]['qkv'].device
+        bf16 = self.dtype == torch.bfloat16
+        T = hip.code(self.dtype)
+        l, st = lib(), stream()
+        f32 = torch.float32
+        maps = torch.empty(B, Ly, N - 1, dtype=f32, device=dev)
+        c, r = torch.empty(B, N, dtype=f32, device=dev), torch.empty(B, N, dtype=f32, device=dev)
+        ws = torch.empty(l.ecgvit_rollout_workspace(B, N, h), dtype=torch.uint8, device=dev)
+
+        def src(L):   # (qkv, lse, probs) of a layer as the entry points take them
+            return (ptr(L['qkv']), ptr(L['lse']), None) if bf16 else (None, None, ptr(L['probs']))
+        for i in range(Ly):
+            check(l.ecgvit_rollout_cls(*src(layers[i]), ptr(c), ptr(n_tok), ptr(tok_off), B, N, h, dh, self.scale, T, st), 'rollout_cls')
+            row = c
+            if i > 0:
+                check(l.ecgvit_rollout_colsum(*src(layers[i - 1]), ptr(c), ptr(r), ptr(ws), ptr(n_tok), ptr(tok_off), B, N, h, dh, self.scale, T, st),
+                      'rollout_colsum')
+                row = r
+            maps[:, i].copy_(row[:, 1:])   # (a strided device copy: layer i of every record is row[1:])
+        check(l.ecgvit_rollout_finish(ptr(maps), ptr(n_tok), B, Ly, N, st), 'rollout_finish')
+        P = self.P
+        if rg is not None:
+            counts = rg.lengths // P
+        elif sv.get('raw') is not None:
+            counts = sv['raw'].padded // P
+        elif n_tok is not None:
+            counts = n_tok.to('cpu', torch.int64) - 1
+        else:
+            counts = torch.full((B,), N - 1, dtype=torch.int64)
+        return maps, counts.to(torch.int64).clone()
+
     # ---------------------------------------------------------------- per-layer attention probabilities (f3)
     def attention_probs(self, layer):
         """Post-softmax attention of `layer` for the last forward, (B, h, N, N) f32 -- what vit_pytorch's Recorder hooks

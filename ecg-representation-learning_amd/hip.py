@@ -119,6 +119,10 @@ SIGNATURES = {
     'ecgvit_l1_loss_fwd_bwd': (c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _L, _I, _P]),
     'ecgvit_eval_counts': (c_int, [_P, _L, _P, _L, _L, _I, _I, _I, _P, _P]),
     'ecgvit_pool_records': (c_int, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _F, _I, _P]),
+    'ecgvit_rollout_workspace': (c_int64, [_I, _I, _I]),
+    'ecgvit_rollout_cls': (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
+    'ecgvit_rollout_colsum': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
+    'ecgvit_rollout_finish': (c_int, [_P, _P, _I, _I, _I, _P]),
 }
 
 _lib = None

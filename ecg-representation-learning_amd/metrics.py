@@ -169,3 +169,47 @@ class HipEncoder:
                 xs, ls = sample_values[s:e], None if lengths is None else lengths[s:e]
             out[s:e] = model.encode(xs, lengths=ls, pool=self.pool, norm=self.norm)
         return out
+
+
+class HipRollout:
+    """Attention maps of a resident data set (`EcgVit.attention_rollout_batch`), `batch_size` records per pass: what the reference derives one
+    record at a time for the low / median / high-loss records of an evaluation (models/evaluate.py:31-55), for as many records as are asked."""
+
+    def __init__(self, model, batch_size=64):
+        self.model, self.bsz = model, int(batch_size)
+        if self.bsz <= 0:
+            raise ValueError(f'batch_size must be positive, got {batch_size!r}')
+
+    def rollout(self, sample_values, lengths=None):
+        """sample_values / lengths: as `HipEncoder.encode` takes and cuts them.  Returns (logits (n, K), maps (n, layers, n_max) f32 with
+        n_max = the patches of the set's widest record and exact zeros past each record's own, patch_counts (n,) int64 on the host)."""
+        model = self.model
+        if sample_values.dim() not in (2, 3):
+            raise ValueError(f'sample_values must be (n, C, L) or a ragged (C, S) batch, got {tuple(sample_values.shape)}')
+        ragged = sample_values.dim() == 2
+        if ragged:   # validated once, then cut by record range on the host offsets
+            sample_values = sample_values.contiguous().float()
+            lengths = model._engine().check_ragged_input(sample_values, lengths)
+            n = lengths.B
+        else:
+            n = sample_values.shape[0]
+            if getattr(getattr(model, '_input_transform', None), 'per_record', False):
+                lengths = model._engine().check_raw_input(sample_values, lengths)   # every batch runs at the set's pass width
+        parts = []
+        for s in range(0, n, self.bsz):
+            e = min(s + self.bsz, n)
+            if ragged:
+                xs, ls = ragged_slice(sample_values, lengths, s, e)
+            elif isinstance(lengths, RawPaddedBatch):
+                xs, ls = sample_values[s:e], lengths.records(s, e)
+            else:
+                xs, ls = sample_values[s:e], None if lengths is None else lengths[s:e]
+            parts.append(model.attention_rollout_batch(xs, lengths=ls))
+        counts = torch.cat([p.patch_counts for p in parts])
+        logits = torch.cat([p.logits for p in parts])
+        maps = torch.zeros(n, parts[0].maps.shape[1], int(counts.max()), dtype=torch.float32, device=logits.device)
+        s = 0
+        for p in parts:
+            maps[s:s + p.maps.shape[0], :, :p.maps.shape[2]] = p.maps
+            s += p.maps.shape[0]
+        return logits, maps, counts

@@ -448,6 +448,35 @@ int ecgvit_eval_counts(const float *scores, int64_t ld_scores, const float *labe
 int ecgvit_pool_records(const void *x, float *out, const int32_t *n_tok, const int32_t *tok_off, int B, int N, int d, int mode,
                         const float *gamma, const float *beta, float eps, int dtype, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * attention rollout for whole batches (EcgVit.attention_rollout_batch; next row f3).  replaces: the map EcgVitVisualizer derives per record
+ * from vit_pytorch's Recorder (reference ecg_vit.py:164-194, :306-326), without an N x N matrix: with A_i = mean_head P_i of layer i and the
+ * row sums of A_i + I taken as exactly 2 (softmax rows sum to 1), the reference's res[i][0, 1:] is
+ *   c_i[k] = (A_i[0,k] + [k == 0]) / 2 ;  r_0 = c_0 ;  r_i[k] = (sum_q c_i[q] A_{i-1}[q,k] + c_i[k]) / 2 ;  map[i][k-1] = r_i[k] / max r.
+ * Additive entry points: the ABI version stays 6.
+ * qkv, lse, n_tok, tok_off, N, scale: exactly as ecgvit_attention_fwd / _varlen_fwd / _ragged_fwd take and leave them (lse natural-log units,
+ * as ecgvit_attention_probs reads it).  n_tok == NULL: every record holds N tokens; tok_off != NULL: packed rows (lse at (b h + head) N + q).
+ * Rows q >= n_tok[b] and keys k >= n_tok[b] are never read as data.  c, w, r: f32 [B, N]; entries at k >= n_tok[b] are written as 0.
+ * dtype ECGVIT_BF16: P is rebuilt from qkv / lse (probs must be NULL): dh == 64 or 128, N <= 2048, all three row layouts; S tiles by bf16 MFMA
+ * with f32 accumulation, exp, weighting and the sum over q in f32.  dtype ECGVIT_F32: P is read from the materialised probs [B,h,N,N] of the
+ * f32 path (qkv, lse, tok_off must be NULL; any dh): uniform and n_tok batches.  Anything else: ECGVIT_EINVAL, nothing launched.
+ * No atomics: heads and query tiles are added in a fixed order that is a function of the record's own n_tok[b] and of h alone, so a record's
+ * rows of c and r are bit-identical in a padded, a n_tok and a packed batch, alone or among others (as ecgvit_pool_records).
+ * ------------------------------------------------------------------------------------------------ */
+/* bytes of `workspace` ecgvit_rollout_colsum needs: the per-head column sums [B, h, N] f32 that its second stage adds in head order */
+int64_t ecgvit_rollout_workspace(int B, int N, int h);
+/* c[b,k] = (mean_head P[b,head,0,k] + [k == 0]) / 2: the row-normalised CLS row of (A + I) */
+int ecgvit_rollout_cls(const void *qkv, const float *lse, const float *probs, float *c, const int32_t *n_tok, const int32_t *tok_off, int B, int N,
+                       int h, int dh, float scale, int dtype, void *stream);
+/* r[b,k] = ((1/h) sum_head sum_{q < n_tok[b]} w[b,q] P[b,head,q,k] + w[b,k]) / 2: the row vector w times the row-normalised (A + I) of the layer
+ * whose qkv / lse (probs) are passed.  w != r.  Two launches: per (record, head, key block), then over the heads. */
+int ecgvit_rollout_colsum(const void *qkv, const float *lse, const float *probs, const float *w, float *r, void *workspace, const int32_t *n_tok,
+                          const int32_t *tok_off, int B, int N, int h, int dh, float scale, int dtype, void *stream);
+/* maps: f32 [B, layers, N - 1], layer i of record b = r_i[1:] with zeros past n_tok[b] - 1.  Divides record b's rows by the maximum over its own
+ * layers x (n_tok[b] - 1) entries (IEEE division: that maximum becomes exactly 1.0); entries past n_tok[b] - 1 are not touched, a record of one
+ * token (an empty map) is left as it is. */
+int ecgvit_rollout_finish(float *maps, const int32_t *n_tok, int B, int layers, int N, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
