@@ -23,6 +23,7 @@ EPI_GELU_GRAD_AUX, EPI_MUL_AUX, EPI_QUANT_OUT, EPI_NO_OUT, EPI_AUX8 = 128, 256, 
 ACC_INIT, ACC_ADD, ACC_FOLD = 0, 1, 2   # ecgvit_grad_accumulate modes
 KERNEL_NONE, KERNEL_GEMM_F32, KERNEL_GEMM_BF16, KERNEL_GEMM_NT, KERNEL_GEMM_WGRAD = 0, 1, 2, 3, 4
 POOL_CLS, POOL_MEAN = 0, 1   # ecgvit_pool_records modes
+FIT_TARGETS, FIT_BINS = 16, 256   # ecgvit_fit_histogram / ecgvit_fit_select: targets per lead, bins per pass
 
 _ERR = {1: 'ECGVIT_EINVAL (unsupported shape / argument)', 2: 'ECGVIT_ELAUNCH (HIP launch failure)'}
 
@@ -123,6 +124,10 @@ SIGNATURES = {
     'ecgvit_rollout_cls': (c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
     'ecgvit_rollout_colsum': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P]),
     'ecgvit_rollout_finish': (c_int, [_P, _P, _I, _I, _I, _P]),
+    'ecgvit_fit_workspace': (c_int64, [_I, _I]),
+    'ecgvit_fit_moments': (c_int, [_P, _P, _L, _P, _I, _I, _P, _P, _P, _P]),
+    'ecgvit_fit_histogram': (c_int, [_P, _P, _L, _P, _I, _I, _P, _I, _I, _P, _P]),
+    'ecgvit_fit_select': (c_int, [_P, _P, _I, _I, _I, _P]),
 }
 
 _lib = None

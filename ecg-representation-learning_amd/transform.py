@@ -15,6 +15,9 @@ concatenated).  Record b is transformed as the reference transforms it alone -- 
 counts `padded_length(l_b) / patch_size` patches from there on.  Without `per_record` (the default) per-record lengths and ragged batches
 are refused as before: the rectangular kernel pads every record to one length.
 """
+import math
+
+import numpy as np
 import torch
 
 
@@ -61,3 +64,335 @@ class FusedInputTransform:
         if self._dev is None or self._dev[0].device != device:
             self._dev = (self.mean.to(device), self.inv_std.to(device))
         return self._dev
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Fitting the statistics: the reference's DynamicNormalize (preprocess/transform.py:38-137), on the device
+# ------------------------------------------------------------------------------------------------------------------------------------
+SCHEMES = ('global', 'std', 'norm', 'none')
+MAX_TARGETS = 16   # order statistics per lead of one fit (hip.FIT_TARGETS)
+
+
+def parse_normalize(normalize):
+    """The reference's `NormArg` -> [(scheme, arg or None), ...], by the reference's own rules (transform.py:119-124, :53-65): a scheme name, a
+    (scheme, arg) TUPLE, or a sequence whose first element is a tuple, of tuples and names.  arg defaults to 1 for 'std' and 2 for 'norm' and
+    is dropped for 'global' / 'none'.  ValueError where the reference asserts (unknown scheme, non-numeric arg, a pair of the wrong length)
+    and, beyond it, for an arg <= 0 or non-finite: the divisor of every stage must be positive."""
+    if isinstance(normalize, str) or (isinstance(normalize, (tuple, list)) and len(normalize) > 0 and not isinstance(normalize[0], tuple)):
+        norm_args = [normalize]
+    else:
+        norm_args = normalize
+    if not isinstance(norm_args, (tuple, list)) or len(norm_args) == 0:
+        raise ValueError(f'normalize: a scheme name, a (scheme, arg) tuple or a sequence of them is expected, got {normalize!r}')
+    out = []
+    for pr in norm_args:
+        pr = pr if isinstance(pr, tuple) else (pr,)
+        if len(pr) not in (1, 2):
+            raise ValueError(f'normalize: {pr!r} is not (scheme,) or (scheme, arg)')
+        scheme, arg = pr[0], (pr[1] if len(pr) == 2 else None)
+        if not isinstance(scheme, str) or scheme not in SCHEMES:
+            raise ValueError(f'normalize: unknown scheme {scheme!r} (one of {SCHEMES})')
+        if scheme in ('std', 'norm'):
+            if arg is None:
+                arg = 1 if scheme == 'std' else 2
+            elif not isinstance(arg, (float, int)):
+                raise ValueError(f'normalize: the arg of {scheme!r} must be a number, got {arg!r}')
+            if not (math.isfinite(arg) and arg > 0):
+                raise ValueError(f'normalize: the arg of {scheme!r} must be positive and finite, got {arg!r}')
+        else:
+            arg = None
+        out.append((scheme, arg))
+    return out
+
+
+def norm_percentile(arg):
+    """p = 100 Phi(arg) in f64 (the reference: scipy.stats.norm().cdf(arg) * 100, transform.py:79)"""
+    return 100.0 * (0.5 * (1.0 + math.erf(float(arg) / math.sqrt(2.0))))
+
+
+def percentile_targets(q, n):
+    """np.nanpercentile's default ('linear') for percentile q over n valid samples: the two neighbouring 0-based ranks of the virtual index
+    (n - 1) q / 100 and the interpolation weight, in f64 as numpy computes them -> (lo, hi, gamma)"""
+    vi = (n - 1) * (q / 100.0)
+    lo = int(math.floor(vi))
+    lo = min(max(lo, 0), n - 1)
+    hi = min(lo + 1, n - 1)
+    return lo, hi, vi - lo
+
+
+def lerp(a, b, t):
+    """numpy's _lerp (lib/_function_base_impl.py) on f64 scalars"""
+    d = b - a
+    return b - d * (1.0 - t) if t >= 0.5 else a + d * t
+
+
+class RawStats:
+    """What one sweep of the data gives, per lead (f64 / exact): count, nan_count, mean, std (ddof 0; None unless a 'std' stage asked for them),
+    and `order`: {rank-spec: (12,) f64} with rank-specs 'min', 'max' and ('q', percentile) -- the already interpolated percentile.
+    `ranks` / `values`: the (12, T) 0-based ranks selected on the device and the (12, T) f32 order statistics found there."""
+
+    def __init__(self, count, nan_count, mean=None, std=None, order=None, ranks=None, values=None):
+        self.count, self.nan_count, self.mean, self.std = count, nan_count, mean, std
+        self.order, self.ranks, self.values = order or {}, ranks, values
+
+
+class NormStage:
+    def __init__(self, scheme, arg, norm_meta):
+        self.scheme, self.arg, self.norm_meta = scheme, arg, norm_meta   # norm_meta: two (12,) f32 arrays, None for 'none'
+
+    def __repr__(self):
+        return f'<NormStage {self.scheme} arg={self.arg}>'
+
+
+def plan_order_stats(stages):
+    """the raw order statistics the stages need, in table order: 'min', 'max' if any stage is 'global', then ('q', 100 - p), ('q', p) per
+    distinct 'norm' arg"""
+    specs = []
+    if any(s == 'global' for s, _ in stages):
+        specs += ['min', 'max']
+    for s, a in stages:
+        if s == 'norm':
+            p = norm_percentile(a)
+            for spec in (('q', 100.0 - p), ('q', p)):
+                if spec not in specs:
+                    specs.append(spec)
+    return specs
+
+
+def compose_stages(stages, raw, lead_names=None):
+    """The stage-composition algebra, on the host in f64.  Stage j of the reference is fitted on the output of stages < j, each a per-lead
+    affine map x -> (x - sub) / div with div > 0 taken from that stage's F32-ROUNDED norm_meta (transform.py:86-100).  Under such a map the
+    mean, minimum, maximum and every percentile follow the map and the standard deviation is divided by div, so stage j's statistics are
+    those of the raw samples (`raw`: RawStats) pushed through the composite (A, D) of the earlier stages: x_j = (x - A) / D, and after a stage
+    with (sub, div): A += sub D, D *= div.  -> ([NormStage], mean (12,) f32, std (12,) f32) with (x - mean) / std the whole chain.
+    ValueError, naming the lead, where a divisor is not positive and finite (the reference hands back inf / NaN there)."""
+    C = len(raw.count)
+    A, D = np.zeros(C, np.float64), np.ones(C, np.float64)
+    out = []
+    for scheme, arg in stages:
+        if scheme == 'none':
+            out.append(NormStage(scheme, None, None))
+            continue
+        if scheme == 'global':
+            a, b = (raw.order['min'] - A) / D, (raw.order['max'] - A) / D
+        elif scheme == 'norm':
+            p = norm_percentile(arg)
+            a, b = (raw.order[('q', 100.0 - p)] - A) / D, (raw.order[('q', p)] - A) / D
+        else:
+            a, b = (raw.mean - A) / D, raw.std / D * arg
+        a, b = a.astype(np.float32), b.astype(np.float32)                   # transform.py:85-86
+        with np.errstate(invalid='ignore', over='ignore'):
+            sub, div = (a, b) if scheme == 'std' else (a, b - a)            # f32 - f32 = f32, as the reference's `ma - mi`
+        bad = ~(np.isfinite(div) & (div > 0) & np.isfinite(sub))
+        if bad.any():
+            c = int(np.flatnonzero(bad)[0])
+            name = lead_names[c] if lead_names is not None else c
+            raise ValueError(f'lead {name} has no finite spread under {scheme!r} (sub {sub[c]!r}, div {div[c]!r}): the reference would normalise it to inf / NaN')
+        out.append(NormStage(scheme, arg, (a, b)))
+        A = A + sub.astype(np.float64) * D
+        D = D * div.astype(np.float64)
+    return out, A.astype(np.float32), D.astype(np.float32)
+
+
+class DynamicNormalizeFit:
+    """Result of `fit_dynamic_normalize`: `.stages` (per stage scheme, arg and the reference's `norm_meta` as two (12,) f32 arrays), `.mean` /
+    `.std` ((12,) f32: the composite affine, (x - mean) / std is the whole chain), `.count` / `.nan_count` per lead, `.raw` (RawStats)."""
+
+    def __init__(self, stages, mean, std, raw):
+        self.stages, self.mean, self.std, self.raw = stages, mean, std, raw
+        self.count, self.nan_count = raw.count, raw.nan_count
+
+    def to_transform(self, patch_size, timeout=False, per_record=False):
+        return FusedInputTransform(self.mean, self.std, patch_size, timeout=timeout, per_record=per_record)
+
+    def __repr__(self):
+        return f'<DynamicNormalizeFit stages={self.stages}>'
+
+
+def _key_to_f32(keys):
+    keys = np.asarray(keys, dtype=np.uint32)
+    bits = np.where(keys & np.uint32(0x80000000), keys ^ np.uint32(0x80000000), ~keys)
+    return bits.astype(np.uint32).view(np.float32)
+
+
+def _record_tables(records, offsets, idxs):
+    """-> (rectangular?, n records, C, src_off int64 (R,), raw_len int64 (R,), lead_stride) for the selected records"""
+    shape = tuple(records.shape)
+    if len(shape) == 3:
+        if offsets is not None:
+            raise ValueError('offsets come with a ragged (12, S_total) store, not with (n, 12, L) records')
+        n, C, L = shape
+        if L < 1 or L > 2 ** 31 - 1:
+            raise ValueError(f'records of {L} samples')
+        off_all, len_all, stride = np.arange(n, dtype=np.int64) * (C * L), np.full(n, L, np.int64), L
+    elif len(shape) == 2:
+        if offsets is None:
+            raise ValueError('a ragged (12, S_total) store needs offsets, an (n + 1,) table')
+        C, S = shape
+        off = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets).astype(np.int64)
+        if off.ndim != 1 or len(off) < 2 or off[0] != 0 or off[-1] != S or (np.diff(off) <= 0).any():
+            raise ValueError('offsets must be (n + 1,) strictly increasing from 0 to S_total')
+        if int(np.diff(off).max()) > 2 ** 31 - 1:
+            raise ValueError('a record is longer than 2^31 - 1 samples')
+        n, off_all, len_all, stride = len(off) - 1, off[:-1], np.diff(off), S
+    else:
+        raise ValueError(f'records must be (n, 12, L) or a ragged (12, S_total) store with offsets, got shape {shape}')
+    if C != 12:
+        raise ValueError(f'records must hold 12 leads, got {C}')   # transform.py:26
+    if idxs is None:
+        sel = np.arange(n, dtype=np.int64)
+    else:
+        sel = np.asarray(idxs.cpu() if isinstance(idxs, torch.Tensor) else idxs)
+        if sel.dtype == bool or sel.ndim != 1 or not np.issubdtype(sel.dtype, np.integer):
+            raise ValueError('idxs must be a 1-D integer array of record indices')
+        sel = sel.astype(np.int64)
+        if len(sel) and (sel.min() < 0 or sel.max() >= n):
+            raise ValueError(f'idxs out of range for {n} records')
+    if len(sel) == 0:
+        raise ValueError('no record selected')
+    return len(shape) == 3, n, C, off_all[sel], len_all[sel], stride, sel
+
+
+class _DeviceSweep:
+    """the launches of one pass over the selected records: in place on a device store, or chunk by chunk through a staging buffer for a host one"""
+
+    def __init__(self, records, rect, src_off, raw_len, stride, sel, chunk_records, device):
+        from . import hip
+        self.hip, self.C, self.device = hip, 12, device
+        self.on_device = isinstance(records, torch.Tensor) and records.is_cuda
+        if self.on_device:
+            if records.dtype != torch.float32:
+                raise ValueError(f'a device store must be float32, got {records.dtype} (fitting on other sample types is not supported)')
+            if not records.is_contiguous():
+                raise ValueError('a device store must be contiguous')
+            R = len(sel)
+            self.chunks = [(records, torch.from_numpy(src_off).to(device), torch.from_numpy(raw_len.astype(np.int32)).to(device), stride, R)]
+            self.ws = torch.empty(max(8, hip.lib().ecgvit_fit_workspace(R, self.C) // 8), dtype=torch.float64, device=device)
+            return
+        self.records = records.numpy() if isinstance(records, torch.Tensor) else records
+        self.rect, self.sel, self.host_off, self.host_len = rect, sel, src_off, raw_len
+        if chunk_records is None:   # about 256 MB of f32 per chunk
+            chunk_records = max(1, int(64 * 2 ** 20 // (self.C * max(1, int(raw_len.max())))))
+        if int(chunk_records) < 1:
+            raise ValueError('chunk_records must be at least 1')
+        self.step = int(chunk_records)
+        self.ws = torch.empty(max(8, hip.lib().ecgvit_fit_workspace(min(self.step, len(sel)), self.C) // 8), dtype=torch.float64, device=device)
+        self.chunks = None
+
+    def _host_chunks(self):
+        C = self.C
+        for lo in range(0, len(self.sel), self.step):
+            ids, lens = self.sel[lo:lo + self.step], self.host_len[lo:lo + self.step]
+            if self.rect:
+                L = int(lens[0])
+                buf = np.ascontiguousarray(self.records[ids], dtype=np.float32)   # (k, C, L)
+                off = np.arange(len(ids), dtype=np.int64) * (C * L)
+                stride = L
+            else:
+                S = int(lens.sum())
+                buf = np.empty((C, S), np.float32)
+                off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+                for o, s, l in zip(off.tolist(), self.host_off[lo:lo + self.step].tolist(), lens.tolist()):
+                    buf[:, o:o + l] = self.records[:, s:s + l]      # (float64 -> float32 happens in this assignment, as in the feeders)
+                stride = S
+            yield (torch.from_numpy(buf).to(self.device), torch.from_numpy(off).to(self.device),
+                   torch.from_numpy(lens.astype(np.int32)).to(self.device), stride, len(ids))
+
+    def run(self, *launches):
+        """every launch of `launches` (callables of (x, src_off, raw_len, stride, R)) over every chunk, the chunks uploaded once per call"""
+        for chunk in (self.chunks if self.on_device else self._host_chunks()):
+            for fn in launches:
+                fn(*chunk)
+
+
+def device_raw_stats(records, specs, want_std, offsets=None, idxs=None, chunk_records=None, device=None):
+    """One sweep of the per-lead raw statistics on the device -> RawStats.  specs: `plan_order_stats` rank-specs; want_std: the second moments
+    pass.  Passes: counts + sum together with the top-digit histogram; the squared deviations together with the second digit; the last two
+    digits -- a host store is uploaded four times (twice without order statistics), a device store is read in place."""
+    from . import hip
+    from .hip import lib, check, ptr, stream
+    rect, n, C, src_off, raw_len, stride, sel = _record_tables(records, offsets, idxs)
+    if len(specs) and 2 * len(specs) > MAX_TARGETS + (2 if 'min' in specs else 0):
+        raise ValueError(f'{len(specs)} order statistics per lead need more than {MAX_TARGETS} ranks: fit fewer distinct percentiles at once')
+    if isinstance(records, torch.Tensor) and records.is_cuda:
+        device = records.device
+    else:
+        device = torch.device(device if device is not None else 'cuda')
+        if device.type != 'cuda' or not torch.cuda.is_available():
+            raise RuntimeError('fit_dynamic_normalize runs on the device (no CPU fallback exists)')
+    with torch.cuda.device(device):
+        sweep = _DeviceSweep(records, rect, src_off, raw_len, stride, sel, chunk_records, device)
+        state = torch.zeros(C, 4, dtype=torch.int64, device=device)
+        hist = torch.zeros(4, C, hip.FIT_TARGETS, hip.FIT_BINS, dtype=torch.int64, device=device)
+        selt = torch.zeros(C, hip.FIT_TARGETS, 4, dtype=torch.int64, device=device)
+        ws = sweep.ws
+
+        def moments(mean):
+            return lambda x, so, rl, st, R: check(lib().ecgvit_fit_moments(ptr(x), ptr(so), st, ptr(rl), R, C, ptr(mean), ptr(ws), ptr(state), stream()), 'fit_moments')
+
+        def histogram(p, T):
+            return lambda x, so, rl, st, R: check(lib().ecgvit_fit_histogram(ptr(x), ptr(so), st, ptr(rl), R, C, ptr(selt), T, p, ptr(hist[p]), stream()), 'fit_histogram')
+
+        sweep.run(moments(None), *([histogram(0, 0)] if specs else []))
+        st = state.cpu().numpy()
+        count, nan_count = st[:, 0].copy(), st[:, 1].copy()
+        if (count == 0).any():
+            c = int(np.flatnonzero(count == 0)[0])
+            raise ValueError(f'lead {c} has no finite spread: every selected sample is NaN')
+        mean = st[:, 2].copy().view(np.float64) / count
+        raw = RawStats(count, nan_count, mean=mean)
+        # the rank table: per spec the two neighbouring ranks ('min' / 'max': one each)
+        ranks, plan = [], []
+        for spec in specs:
+            if spec == 'min':
+                plan.append((len(ranks), None)); ranks.append(np.zeros(C, np.int64))
+            elif spec == 'max':
+                plan.append((len(ranks), None)); ranks.append(count - 1)
+            else:
+                tg = [percentile_targets(spec[1], int(k)) for k in count]
+                plan.append((len(ranks), np.array([t[2] for t in tg])))
+                ranks += [np.array([t[0] for t in tg], np.int64), np.array([t[1] for t in tg], np.int64)]
+        T = len(ranks)
+        mean_dev = torch.from_numpy(mean).to(device) if want_std else None
+        if T:
+            host_sel = np.zeros((C, hip.FIT_TARGETS, 4), np.int64)
+            host_sel[:, :T, 0] = np.stack(ranks, 1)
+            selt.copy_(torch.from_numpy(host_sel))
+            check(lib().ecgvit_fit_select(ptr(hist[0]), ptr(selt), C, T, 0, stream()), 'fit_select')
+            for p in (1, 2, 3):
+                sweep.run(histogram(p, T), *([moments(mean_dev)] if (want_std and p == 1) else []))
+                check(lib().ecgvit_fit_select(ptr(hist[p]), ptr(selt), C, T, p, stream()), 'fit_select')
+            out = selt.cpu().numpy()
+            if (out[:, :T, 3] == 0).any():
+                raise RuntimeError('radix select: a rank lies past the count of its lead')
+            vals = _key_to_f32(out[:, :T, 1].astype(np.uint64).astype(np.uint32))
+            raw.ranks, raw.values = np.stack(ranks, 1), vals
+            v64 = vals.astype(np.float64)
+            for spec, (j, gamma) in zip(specs, plan):
+                raw.order[spec] = v64[:, j] if gamma is None else np.array([lerp(v64[c, j], v64[c, j + 1], gamma[c]) for c in range(C)])
+        elif want_std:
+            sweep.run(moments(mean_dev))
+        if want_std:
+            raw.std = np.sqrt(state.cpu().numpy()[:, 3].copy().view(np.float64) / count)
+    return raw
+
+
+def fit_dynamic_normalize(records, normalize=(('norm', 3), ('std', 1)), offsets=None, idxs=None, chunk_records=None):
+    """The reference's `DynamicNormalize(sig, normalize)` (preprocess/transform.py:108-137; fitted on the training split at util/config.py:296-308)
+    with the sweeps over the data done by HIP kernels on the device: per lead the count, the NaN count, the two-pass f64 mean / standard
+    deviation and EXACT order statistics by radix select, NaN samples left out as np.nanmean / nanstd / nanmin / nanmax / nanpercentile leave
+    them out -> `DynamicNormalizeFit`; `.to_transform(patch_size, ...)` is the `FusedInputTransform` of the whole chain.
+
+    records: (n, 12, L), or a ragged (12, S_total) store with `offsets` (the (n + 1,) table `RaggedDeviceFeeder` takes).  A float32 device
+    tensor is read in place -- `idxs` (record indices, e.g. the training fold) only builds an address table, nothing is copied.  A host
+    array / memmap / tensor of any float type is moved to the device `chunk_records` records at a time (rounded to float32 as the feeders round),
+    once per pass.  A ragged corpus has no rectangle: its statistics are those of the records padded to the longest with NaN.
+    normalize: what the reference's `NormArg` accepts (`parse_normalize`).  A sequence of stages costs ONE sweep: every stage is a per-lead
+    affine map, so its statistics follow from the raw ones (`compose_stages`).
+    A lead with no finite spread -- all NaN, constant under 'std', max == min or equal percentiles -- raises ValueError naming the lead; the
+    reference hands back a transform that maps it to inf / NaN."""
+    stages = parse_normalize(normalize)
+    specs = plan_order_stats(stages)
+    raw = device_raw_stats(records, specs, any(s == 'std' for s, _ in stages), offsets=offsets, idxs=idxs, chunk_records=chunk_records)
+    st, mean, std = compose_stages(stages, raw)
+    return DynamicNormalizeFit(st, mean, std, raw)

@@ -477,6 +477,37 @@ int ecgvit_rollout_colsum(const void *qkv, const float *lse, const float *probs,
  * token (an empty map) is left as it is. */
 int ecgvit_rollout_finish(float *maps, const int32_t *n_tok, int B, int layers, int N, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * per-lead statistics of a record store (transform.fit_dynamic_normalize; next row f2).  replaces: the np.nanmean / nanstd / nanmin / nanmax /
+ * nanpercentile sweeps DynamicNormalize makes over an (n, 12, L) host array (reference preprocess/transform.py:38-137, fitted at
+ * util/config.py:296-308).  Additive entry points: the ABI version stays 6.
+ * Records are addressed as ecgvit_patch_gather_transform_varlen addresses them: lead c of record r (r < R) = raw_len[r] f32 samples at
+ * x + src_off[r] + c * lead_stride (src_off int64 [R], raw_len int32 [R], device arrays; raw_len[r] <= 0 skips the record).  A rectangular
+ * (n, C, L) store, a ragged (C, S_total) one and any subset of either are tables over the same buffer; a record's first sample may sit at any
+ * 4-byte address.  NaN samples are counted and otherwise left out, as the nan-functions leave them out; +-0, denormals and +-inf are ordinary
+ * values.  Every entry point ADDS to state the caller owns and zeroes: a store larger than one launch is a sequence of launches per pass.
+ * ------------------------------------------------------------------------------------------------ */
+/* bytes of `workspace` ecgvit_fit_moments needs for R records (the per-workgroup partials its second stage adds in a fixed order) */
+int64_t ecgvit_fit_workspace(int R, int C);
+/* state: per lead 32 bytes { uint64 count of non-NaN samples, uint64 count of NaN samples, double sum, double sum of squared deviations }.
+ * mean == NULL: the first three are added to; mean != NULL (double [C], device): sum (x - mean[c])^2 is added to the fourth alone (np.nanstd is
+ * two-pass, ddof 0).  f64 throughout, two stages in a fixed order, no floating-point atomics: the same launches give the same bits. */
+int ecgvit_fit_moments(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, const double *mean,
+                       void *workspace, void *state, void *stream);
+/* Exact order statistics by radix select on the monotone uint32 key of the f32 bit pattern (k = bits ^ (bits < 0 ? ~0 : 0x80000000): -0.0 sorts
+ * directly below +0.0), 8 bits per pass, passes 0..3.  sel: uint64 [C][16][4] per (lead, target) { rank, key prefix, slot, count of the chosen
+ * bin }; the caller writes the rank of each of its ntarget <= 16 targets (0-based among the lead's non-NaN samples) and zeroes the rest.
+ * hist: uint64 [C][16][256], zeroed by the caller before each pass.  Pass p:
+ *   ecgvit_fit_histogram (once per launch of the store) counts digit p of every non-NaN sample whose key starts with a target's decided prefix
+ *     (pass 0: every sample, slot 0); targets that share a prefix share a slot.  Integer atomics only: exact, independent of order;
+ *   ecgvit_fit_select then finds, per target, the bin holding its rank, appends it to the prefix and leaves the rank within the bin -- on the
+ *     device, so the passes queue without a host round trip.
+ * After pass 3 the prefix is the key of the exact order statistic (bits = key & 0x80000000 ? key ^ 0x80000000 : ~key); a count of 0 there
+ * means the rank was not below the lead's count. */
+int ecgvit_fit_histogram(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, const uint64_t *sel,
+                         int ntarget, int pass, uint64_t *hist, void *stream);
+int ecgvit_fit_select(const uint64_t *hist, uint64_t *sel, int C, int ntarget, int pass, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
