@@ -40,9 +40,7 @@ class ParamLayout:
         self.entries = OrderedDict()
         off = 0
         for name, shape in named_shapes:
-            n = 1
-            for s in shape:
-                n *= s
+            n = _numel(shape)
             self.entries[name] = (off, tuple(shape), n)
             off = _align(off + n, 16)
         self.total = off
@@ -135,27 +133,58 @@ class BackwardPlan:
         return stage <= self.depth
 
 
+def _stage(t, device):
+    """a small host tensor -> `device` through pinned memory (a pageable copy would block the host until the stream has drained)"""
+    if torch.device(device).type != 'cuda':
+        return t
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def _host_ints(t, what, shape_note):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f'{what} must be {shape_note}, got {type(t).__name__}')
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f'{what} must be an integer tensor, got {t.dtype}')
+    return t.detach().to('cpu', torch.int64)   # (a blocking read for a device tensor)
+
+
+def _check_lengths(lengths, *, needed=False, B=None, allow_empty=False, width=None, max_len=None, pad=None, P=None, S=None):
+    """The one validator of per-record sample counts (`check_lengths`, `check_ragged`, `check_masked_lengths`, `check_raw_lengths`) -> their
+    int64 host copy (the one blocking read of a device tensor); anything else raises ValueError.  One fixed order, each check on when its
+    keyword is given: present (needed), a tensor, integer dtype, 1-D with B >= 1 entries (B: exactly B; allow_empty: B = 0 passes), positive,
+    <= width, <= max_len (pad = k: RAW counts, held to max_len after TimeEndPad to the next multiple of k), multiples of P, summing to S."""
+    if needed and lengths is None:
+        raise ValueError('a ragged (C, S) batch needs lengths: the (B,) per-record sample counts')
+    t = _host_ints(lengths, 'lengths', 'a (B,) integer tensor')
+    if t.dim() != 1 or (B is not None and t.shape[0] != B) or (t.shape[0] < 1 and not allow_empty):
+        raise ValueError(f'lengths must have shape (batch={"B" if B is None else B},){"" if allow_empty else " with B >= 1"}, got {tuple(lengths.shape)}')
+    if t.shape[0] == 0:
+        return t
+    lo, hi = int(t.min()), int(t.max())
+    if lo <= 0:
+        raise ValueError(f'lengths must be positive (got {lo})')
+    if width is not None and hi > width:
+        raise ValueError(f'lengths must not exceed the batch width {width} (got {hi})')
+    if max_len is not None and pad is None and hi > max_len:
+        raise ValueError(f'lengths must not exceed max_signal_length={max_len} (got {hi})')
+    if max_len is not None and pad is not None and hi + (pad - hi % pad) > max_len:
+        raise ValueError(f'padded record lengths must not exceed max_signal_length={max_len}: a raw record of {hi} samples pads to '
+                         f'{hi + (pad - hi % pad)} (TimeEndPad adds a full patch to a multiple of patch_size={pad})')
+    if P is not None and bool((t % P != 0).any()):
+        raise ValueError(f'lengths must be multiples of patch_size={P}')
+    if S is not None and int(t.sum()) != S:
+        raise ValueError(f'lengths must sum to the ragged batch width S={S} (got {int(t.sum())})')
+    return t
+
+
 def check_lengths(lengths, B, P, width):
     """Per-record sample counts of a (B, C, width) batch -> int32 token counts n_tok = lengths / P + 1 on the lengths' own device, or None when
     every record fills the width (the uniform kernels then run).  Each entry must be a positive multiple of P and at most `width`, else
-    ValueError.  Host tensors are checked on the host (no device round trip); device tensors with device reductions (blocking reads)."""
-    if not isinstance(lengths, torch.Tensor):
-        raise ValueError(f'lengths must be a (B,) integer tensor, got {type(lengths).__name__}')
-    if lengths.dim() != 1 or lengths.shape[0] != B:
-        raise ValueError(f'lengths must have shape (batch={B},), got {tuple(lengths.shape)}')
-    if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
-        raise ValueError(f'lengths must be an integer tensor, got {lengths.dtype}')
-    t = lengths.to(torch.int64)
-    lo, hi = (int(t.min()), int(t.max())) if B > 0 else (width, width)
-    if lo <= 0:
-        raise ValueError(f'lengths must be positive (got {lo})')
-    if hi > width:
-        raise ValueError(f'lengths must not exceed the batch width {width} (got {hi})')
-    if bool((t % P != 0).any()):
-        raise ValueError(f'lengths must be multiples of patch_size={P}')
-    if lo == width:
+    ValueError.  The values are checked on the host (one blocking read for a device tensor)."""
+    t = _check_lengths(lengths, B=B, allow_empty=True, width=width, P=P)
+    if B == 0 or int(t.min()) == width:
         return None
-    return (t // P + 1).to(torch.int32).contiguous()
+    return _stage((t // P + 1).to(torch.int32), lengths.device)
 
 
 def check_raw_lengths(lengths, xf, max_len, B=None, width=None, S=None):
@@ -163,23 +192,8 @@ def check_raw_lengths(lengths, xf, max_len, B=None, width=None, S=None):
     tensors, padded[b] = xf.padded_length(raw[b]) (a full extra patch when raw[b] is a multiple of the patch).  lengths: a (B,) integer
     tensor, every entry >= 1 (no multiple-of-P rule), at most `width` (a padded (B, C, width) batch) / summing to S (a ragged (C, S) batch),
     and every padded length at most max_len; anything else raises ValueError.  Host work only (one blocking read for a device tensor)."""
-    if lengths is None:
-        raise ValueError('a ragged (C, S) batch needs lengths: the (B,) per-record sample counts')
-    t = _host_ints(lengths, 'lengths', 'a (B,) integer tensor')
-    if t.dim() != 1 or t.shape[0] < 1 or (B is not None and t.shape[0] != B):
-        raise ValueError(f'lengths must have shape (batch={B if B is not None else "B"},) with B >= 1, got {tuple(lengths.shape)}')
-    lo, hi = int(t.min()), int(t.max())
-    if lo <= 0:
-        raise ValueError(f'lengths must be positive (got {lo})')
-    if width is not None and hi > width:
-        raise ValueError(f'lengths must not exceed the batch width {width} (got {hi})')
-    padded = t + (xf.k - t % xf.k)   # FusedInputTransform.padded_length, elementwise
-    if int(padded.max()) > max_len:
-        raise ValueError(f'padded record lengths must not exceed max_signal_length={max_len}: a raw record of {hi} samples pads to '
-                         f'{xf.padded_length(hi)} (TimeEndPad adds a full patch to a multiple of patch_size={xf.k})')
-    if S is not None and int(t.sum()) != S:
-        raise ValueError(f'lengths must sum to the ragged batch width S={S} (got {int(t.sum())})')
-    return t, padded
+    t = _check_lengths(lengths, needed=True, B=B, width=width, max_len=max_len, pad=xf.k, S=S)
+    return t, t + (xf.k - t % xf.k)   # FusedInputTransform.padded_length, elementwise
 
 
 class RawSide:
@@ -218,10 +232,8 @@ class RaggedBatch:
     def __init__(self, lengths, P, device, raw=None):
         t = lengths
         n_tok = t // P + 1
-        tok_off = torch.cumsum(n_tok, 0) - n_tok   # = off_b / P + b
-        pack = torch.stack([n_tok, tok_off]).to(torch.int32)
-        if device.type == 'cuda':
-            pack = pack.pin_memory().to(device, non_blocking=True)
+        tok_off = _excl_cumsum(n_tok)   # = off_b / P + b
+        pack = _stage(torch.stack([n_tok, tok_off]).to(torch.int32), device)
         self.lengths, self.P, self.device = t, P, device
         self.n_tok, self.tok_off = pack[0], pack[1]
         self.S = int(t.sum())
@@ -273,24 +285,7 @@ def check_ragged(lengths, S, P, max_len, device=None):
     """Per-record sample counts of a ragged (C, S) batch -> RaggedBatch with n_tok / tok_off as int32 tensors on `device` (default: the
     lengths' own device).  lengths is required, a (B,) integer tensor whose entries are positive multiples of P, at most `max_len`, and sum to
     S; anything else raises ValueError.  The values are read on the host once (a blocking read for a device tensor, as `check_lengths`)."""
-    if lengths is None:
-        raise ValueError('a ragged (C, S) batch needs lengths: the (B,) per-record sample counts')
-    if not isinstance(lengths, torch.Tensor):
-        raise ValueError(f'lengths must be a (B,) integer tensor, got {type(lengths).__name__}')
-    if lengths.dim() != 1 or lengths.shape[0] < 1:
-        raise ValueError(f'lengths must have shape (B,) with B >= 1, got {tuple(lengths.shape)}')
-    if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
-        raise ValueError(f'lengths must be an integer tensor, got {lengths.dtype}')
-    t = lengths.detach().to('cpu', torch.int64)
-    lo, hi, tot = int(t.min()), int(t.max()), int(t.sum())
-    if lo <= 0:
-        raise ValueError(f'lengths must be positive (got {lo})')
-    if hi > max_len:
-        raise ValueError(f'lengths must not exceed max_signal_length={max_len} (got {hi})')
-    if bool((t % P != 0).any()):
-        raise ValueError(f'lengths must be multiples of patch_size={P}')
-    if tot != S:
-        raise ValueError(f'lengths must sum to the ragged batch width S={S} (got {tot})')
+    t = _check_lengths(lengths, needed=True, max_len=max_len, P=P, S=S)
     return RaggedBatch(t, P, lengths.device if device is None else torch.device(device))
 
 
@@ -326,7 +321,7 @@ class MaskedVarlenBatch:
         B = t.shape[0]
         n = t // P
         self.n_pad = 0 if width is None else width // P
-        tok_off = torch.cumsum(n, 0) - n if width is None else torch.arange(B, dtype=torch.int64) * self.n_pad
+        tok_off = _excl_cumsum(n) if width is None else torch.arange(B, dtype=torch.int64) * self.n_pad
         order = torch.sort(n, descending=True, stable=True).indices
         self.lengths, self.P, self.device, self.width = t, P, device, width
         self.n_host, self.off_host = n, tok_off
@@ -377,41 +372,10 @@ class MaskedVarlenBatch:
         return (s0, s1), g
 
 
-def _stage(t, device):
-    """a small host tensor -> `device` through pinned memory (a pageable copy would block the host until the stream has drained)"""
-    if torch.device(device).type != 'cuda':
-        return t
-    return t.pin_memory().to(device, non_blocking=True)
-
-
-def _host_ints(t, what, shape_note):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f'{what} must be {shape_note}, got {type(t).__name__}')
-    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
-        raise ValueError(f'{what} must be an integer tensor, got {t.dtype}')
-    return t.detach().to('cpu', torch.int64)   # (a blocking read for a device tensor)
-
-
 def check_masked_lengths(lengths, P, max_len, B=None, width=None, S=None):
     """per-record sample counts of a masked batch -> int64 host tensor: a (B,) integer tensor of positive multiples of P, at most `width` (the
     padded form) / max_len, summing to S (the ragged form); anything else raises ValueError"""
-    if lengths is None:
-        raise ValueError('a ragged (C, S) batch needs lengths: the (B,) per-record sample counts')
-    t = _host_ints(lengths, 'lengths', 'a (B,) integer tensor')
-    if t.dim() != 1 or t.shape[0] < 1 or (B is not None and t.shape[0] != B):
-        raise ValueError(f'lengths must have shape (batch={B if B is not None else "B"},), got {tuple(lengths.shape)}')
-    lo, hi = int(t.min()), int(t.max())
-    if lo <= 0:
-        raise ValueError(f'lengths must be positive (got {lo})')
-    if width is not None and hi > width:
-        raise ValueError(f'lengths must not exceed the batch width {width} (got {hi})')
-    if hi > max_len:
-        raise ValueError(f'lengths must not exceed max_signal_length={max_len} (got {hi})')
-    if bool((t % P != 0).any()):
-        raise ValueError(f'lengths must be multiples of patch_size={P}')
-    if S is not None and int(t.sum()) != S:
-        raise ValueError(f'lengths must sum to the ragged batch width S={S} (got {int(t.sum())})')
-    return t
+    return _check_lengths(lengths, needed=True, B=B, width=width, max_len=max_len, P=P, S=S)
 
 
 def check_mask_varlen(mask_idx, mask_counts, n):
@@ -938,28 +902,34 @@ class VitEngine:
         self._gemm(GEMM_TN, dY, X, self.G32[name], Mout, Nin, rows, Mout, Nin, Nin, workspace=self.act['ws'])
 
     # ---------------------------------------------------------------- forward
-    def _patch_embed(self, x, B):
-        a, W, T = self.act, self.W, hip.code(self.dtype)
-        pre = 'vit.'
-        # a4: patch Rearrange (integer gather) + Linear(C*P, d)   [+ f2: Normalize / TimeEndPad / TimeOut fused into the load]
+    def _patch_rows(self, x):
+        """a4: patch Rearrange (integer gather) + Linear(C*P, d) over the patch rows of the current pass (`saved`), whatever its row layout
+        [+ f2: Normalize / TimeEndPad / TimeOut fused into the load]"""
+        a, sv, T = self.act, self.saved, hip.code(self.dtype)
+        B, rg, geo, ntok = sv['B'], sv.get('ragged'), sv.get('geo'), sv.get('ntok')
         xf = self.input_transform
-        if self.saved is not None and self.saved.get('raw') is not None:   # f2 per record: raw records of unequal length
-            self._gather_raw(x, self.saved['raw'], self.saved.get('training', True))
+        if sv.get('raw') is not None:   # f2 per record: raw records of unequal length, either row layout
+            self._gather_raw(x, sv['raw'], sv['training'])
         elif xf is not None:
             mean, inv_std = xf.device_stats(x.device)
             t0 = tl = None
-            if xf.timeout and self.saved is not None and self.saved.get('training', True):
+            if xf.timeout and sv['training']:
                 t0, tl = xf.draw_timeout(B, self.L, x.device)
             self._xf_keep = (mean, inv_std, t0, tl)   # keep the int32 spans alive until the kernel has run
             check(lib().ecgvit_patch_gather_transform(ptr(x), ptr(a['patches']), B, self.C, x.shape[2], self.L, self.P, self.CP, ptr(mean),
                                                       ptr(inv_std), ptr(t0), ptr(tl), T, stream()), 'patch_gather_transform')
-        elif self.saved is not None and self.saved.get('ntok') is not None:   # zero patches past each record's length
-            check(lib().ecgvit_patch_gather_varlen(ptr(x), ptr(a['patches']), ptr(self.saved['ntok']), B, self.C, self.L, self.P, self.CP, T, stream()),
+        elif rg is not None:   # packed rows: the uniform gather over the concatenation (patch row off_b / P + j is patch j of record b)
+            check(lib().ecgvit_patch_gather(ptr(x), ptr(a['patches']), 1, self.C, rg.S, self.P, self.CP, T, stream()), 'patch_gather')
+        elif ntok is not None:   # zero patches past each record's length.  The kernel's count includes a CLS token: the masked padded
+            # form, whose ntok = n_b counts patches only, passes n_cls = n_b + 1
+            cnt = ntok if geo is None else geo.n_cls
+            check(lib().ecgvit_patch_gather_varlen(ptr(x), ptr(a['patches']), ptr(cnt), B, self.C, self.L, self.P, self.CP, T, stream()),
                   'patch_gather_varlen')
         else:
             check(lib().ecgvit_patch_gather(ptr(x), ptr(a['patches']), B, self.C, self.L, self.P, self.CP, T, stream()), 'patch_gather')
-        self._gemm(GEMM_NT, a['patches'], W[pre + 'to_patch_embedding.1.weight'], a['tok'], B * self.n, self.d, self.CP, self.CP,
-                 self.CP, self.d, epilogue=EPI_BIAS, bias=self.P32[pre + 'to_patch_embedding.1.bias'])
+        rows = self._pass_rows(B) - (0 if sv['masked'] else B)   # (no CLS rows among the patch rows)
+        self._gemm(GEMM_NT, a['patches'], self.W['vit.to_patch_embedding.1.weight'], a['tok'], rows, self.d, self.CP, self.CP, self.CP, self.d,
+                   epilogue=EPI_BIAS, bias=self.P32['vit.to_patch_embedding.1.bias'])
 
     def _gather_raw(self, x, rs, training):
         """f2 per record (`FusedInputTransform(per_record=True)`): Normalize / TimeEndPad / TimeOut of every record at its own raw length,
@@ -1000,11 +970,9 @@ class VitEngine:
     def _trunk_fwd(self, B, ph, seed, cls_only_last=False):
         """L x { x = Attn(LN(x)) + x ; x = FF(LN(x)) + x } on act['x0'] ([B*T, d]); returns the output slab (cls_only_last: the last
         block's CLS rows only, compact [B, d] -- see `_cls_block_fwd`)"""
-        a, W, T = self.act, self.W, hip.code(self.dtype)
-        l, st = lib(), stream()
-        d, f, h, dh, N = self.d, self.f, self.h, self.dh, self.T
+        a = self.act
+        d, f = self.d, self.f
         M = self._pass_rows(B)
-        rg = self.saved.get('ragged')
         pre = 'vit.'
         X = a['x0']
         for i, L in enumerate(a['layers']):
@@ -1013,28 +981,10 @@ class VitEngine:
             if cls_only_last and i == self.Ly - 1:
                 return self._cls_block_fwd(L, X, B, ph, s0, lp)
             # a6/a7: PreNorm(Attention)
-            f8 = self.fp8 and M >= 2048
             q1 = self._ln_fwd(X, self.P32[lp + '0.norm.weight'], self.P32[lp + '0.norm.bias'], L['xn1'], L['mean1'], L['rstd1'], M, q8_site=8 * i,
                               y8=L.get('xn1_8'))
             self._linear(8 * i + 0, L['xn1'], lp + '0.fn.to_qkv.weight', L['qkv'], M, 3 * d, d, a8=L.get('xn1_8'), prequant=q1)
-            qa = False   # fp8_linear: the attention kernel wrote the e4m3 copy of its output itself
-            ntok = self.saved.get('ntok')
-            if rg is not None:
-                check(l.ecgvit_attention_ragged_fwd(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), ptr(rg.n_tok), ptr(rg.tok_off), B, N, h, dh, self.scale,
-                                                    ph, s0 + 1, st), 'attention_ragged_fwd')
-            elif self.dtype == torch.bfloat16 and ntok is not None:
-                check(l.ecgvit_attention_varlen_fwd(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), ptr(ntok), B, N, h, dh, self.scale, ph, s0 + 1, st),
-                      'attention_varlen_fwd')
-            elif self.dtype == torch.bfloat16:
-                if f8 and (8 * i + 1) in self._f8_seen and dh == 64:   # (dh = 128: no 8-bit emission, _linear quantises attn)
-                    check(l.ecgvit_attention_fwd_q8(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), B, N, h, dh, self.scale, ph, s0 + 1, ptr(L['attn_8']),
-                                                    ptr(self.f8_scale[8 * i + 1:8 * i + 2]), ptr(self.f8_amax[8 * i + 1:8 * i + 2]), st), 'attention_fwd_q8')
-                    qa = True
-                else:
-                    check(l.ecgvit_attention_fwd(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), B, N, h, dh, self.scale, ph, s0 + 1,
-                                                 T, st), 'attention_fwd')
-            else:
-                self._attn_fwd_f32(L, B, ph, s0 + 1)
+            qa = self._attention_fwd(L, i, B, ph, s0 + 1)
             epi = EPI_BIAS | EPI_RESIDUAL | (EPI_DROPOUT if ph > 0 else 0)
             self._linear(8 * i + 1, L['attn'], lp + '0.fn.to_out.0.weight', L['x1'], M, d, d, a8=L.get('attn_8'), prequant=qa, epilogue=epi,
                          bias=self.P32[lp + '0.fn.to_out.0.bias'], residual=X, ldr=d, dropout_p=ph, seed=s0 + 2)
@@ -1055,25 +1005,90 @@ class VitEngine:
             X = L['x2']
         return X
 
+    def _attention_fwd(self, L, i, B, ph, seed):
+        """a7: softmax(q k^T * scale) v of block i, qkv -> attn, on the kernel the current pass calls for.  Returns True when the kernel also
+        wrote the e4m3 copy of its output (fp8_linear, once site 8 i + 1 has a scale)"""
+        sv, l, st = self.saved, lib(), stream()
+        h, dh, N = self.h, self.dh, self.T
+        rg, ntok = sv.get('ragged'), sv.get('ntok')
+        site = 8 * i + 1
+        if rg is not None:
+            check(l.ecgvit_attention_ragged_fwd(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), ptr(rg.n_tok), ptr(rg.tok_off), B, N, h, dh, self.scale,
+                                                ph, seed, st), 'attention_ragged_fwd')
+        elif self.dtype == torch.bfloat16 and ntok is not None:
+            check(l.ecgvit_attention_varlen_fwd(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), ptr(ntok), B, N, h, dh, self.scale, ph, seed, st),
+                  'attention_varlen_fwd')
+        elif self.dtype == torch.bfloat16:
+            if self.fp8 and self._pass_rows(B) >= 2048 and site in self._f8_seen and dh == 64:   # (dh = 128: no 8-bit emission, _linear quantises attn)
+                check(l.ecgvit_attention_fwd_q8(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), B, N, h, dh, self.scale, ph, seed, ptr(L['attn_8']),
+                                                ptr(self.f8_scale[site:site + 1]), ptr(self.f8_amax[site:site + 1]), st), 'attention_fwd_q8')
+                return True
+            check(l.ecgvit_attention_fwd(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), B, N, h, dh, self.scale, ph, seed, hip.BF16, st), 'attention_fwd')
+        else:
+            self._attn_fwd_f32(L, B, ph, seed)
+        return False
+
+    def _attention_bwd(self, L, i, B, ph, seed):
+        """backward of `_attention_fwd`: dattn -> dqkv.  Returns True when the kernel also wrote the e5m2 copy of dqkv (operand scratch)"""
+        a, sv, l, st = self.act, self.saved, lib(), stream()
+        d, h, dh, N = self.d, self.h, self.dh, self.T
+        rg, ntok = sv.get('ragged'), sv.get('ntok')
+        site = 8 * i + 7
+        if rg is not None:
+            check(l.ecgvit_attention_ragged_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), ptr(rg.n_tok),
+                                                ptr(rg.tok_off), B, N, h, dh, self.scale, ph, seed, st), 'attention_ragged_bwd')
+        elif self.dtype == torch.bfloat16 and ntok is not None:
+            check(l.ecgvit_attention_varlen_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), ptr(ntok), B, N, h,
+                                                dh, self.scale, ph, seed, st), 'attention_varlen_bwd')
+        elif self.dtype == torch.bfloat16:
+            if (self.fp8 and self._pass_rows(B) >= 2048 and site in self._f8_seen and dh == 64 and 128 < N <= 512
+                    and N * 3 * d * 2 < 2 ** 31):   # (dh = 128: _grad8 quantises dqkv)
+                check(l.ecgvit_attention_bwd_q8(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), B, N, h, dh, self.scale,
+                                                ph, seed, ptr(a['q8']), ptr(self.f8_scale[site:site + 1]), ptr(self.f8_amax[site:site + 1]), st),
+                      'attention_bwd_q8')
+                return True
+            check(l.ecgvit_attention_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), B, N, h, dh, self.scale, ph,
+                                         seed, hip.BF16, st), 'attention_bwd')
+        else:
+            self._attn_bwd_f32(L, B, ph, seed)
+        return False
+
+    def _attention_cls_fwd(self, L, B, ph, seed):
+        """the CLS query of every record against all its keys (the pruned last block): qkv -> act['cls_attn'], act['cls_lse']"""
+        a, l, st = self.act, lib(), stream()
+        h, dh, N = self.h, self.dh, self.T
+        ntok = self.saved.get('ntok')
+        if ntok is not None:
+            check(l.ecgvit_attention_varlen_cls_fwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_lse']), ptr(ntok), B, N, h, dh, self.scale, ph, seed,
+                                                    st), 'attention_varlen_cls_fwd')
+        else:
+            check(l.ecgvit_attention_cls_fwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_lse']), B, N, h, dh, self.scale, ph, seed,
+                                             hip.code(self.dtype), st), 'attention_cls_fwd')
+
+    def _attention_cls_bwd(self, L, B, ph, seed):
+        """backward of `_attention_cls_fwd`: act['cls_dattn'] -> dK / dV of every row in act['dqkv'], the compact dQ in act['cls_dq']"""
+        a, l, st = self.act, lib(), stream()
+        h, dh, N = self.h, self.dh, self.T
+        ntok = self.saved.get('ntok')
+        if ntok is not None:
+            check(l.ecgvit_attention_varlen_cls_bwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_dattn']), ptr(a['cls_lse']), ptr(a['dqkv']),
+                                                    ptr(a['cls_dq']), ptr(ntok), B, N, h, dh, self.scale, ph, seed, st), 'attention_varlen_cls_bwd')
+        else:
+            check(l.ecgvit_attention_cls_bwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_dattn']), ptr(a['cls_lse']), ptr(a['dqkv']), ptr(a['cls_dq']),
+                                             B, N, h, dh, self.scale, ph, seed, hip.code(self.dtype), st), 'attention_cls_bwd')
+
     def _cls_block_fwd(self, L, X, B, ph, s0, lp):
         """the last block when only its CLS rows are consumed (the classifier reads x[:, 0]): LayerNorm 1 and the K / V columns of to_qkv
         over every row (the CLS query attends to all keys), everything after them over one row per record.  The compact launches draw the
         dropout bits of the rows they stand for (mask row pitch T), so the result is the full block's row 0.  Returns x2 of the CLS rows [B, d]"""
         a, W, P = self.act, self.W, self.P32
-        l, st = lib(), stream()
-        d, f, h, dh, N = self.d, self.f, self.h, self.dh, self.T
-        M, T = B * N, hip.code(self.dtype)
+        d, f, N = self.d, self.f, self.T
+        M = B * N
         self._ln_fwd(X, P[lp + '0.norm.weight'], P[lp + '0.norm.bias'], L['xn1'], L['mean1'], L['rstd1'], M)
         wqkv = W[lp + '0.fn.to_qkv.weight']   # [3d, d]: rows [q | k | v]
         self._gemm(GEMM_NT, L['xn1'], wqkv, L['qkv'], M, 2 * d, d, d, d, 3 * d, b_off=d * d, c_off=d)   # K, V of every row
         self._gemm(GEMM_NT, L['xn1'], wqkv, L['qkv'], B, d, d, N * d, d, N * 3 * d)                       # Q of the CLS rows, in place
-        ntok = self.saved.get('ntok')
-        if ntok is not None:
-            check(l.ecgvit_attention_varlen_cls_fwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_lse']), ptr(ntok), B, N, h, dh, self.scale, ph, s0 + 1,
-                                                    st), 'attention_varlen_cls_fwd')
-        else:
-            check(l.ecgvit_attention_cls_fwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_lse']), B, N, h, dh, self.scale, ph, s0 + 1, T, st),
-                  'attention_cls_fwd')
+        self._attention_cls_fwd(L, B, ph, s0 + 1)
         drop = EPI_DROPOUT if ph > 0 else 0
         self._gemm(GEMM_NT, a['cls_attn'], W[lp + '0.fn.to_out.0.weight'], a['cls_x1'], B, d, d, d, d, d, epilogue=EPI_BIAS | EPI_RESIDUAL | drop,
                    bias=P[lp + '0.fn.to_out.0.bias'], residual=X, ldr=N * d, dropout_p=ph, seed=s0 + 2, mask_row_pitch=N)
@@ -1093,28 +1108,40 @@ class VitEngine:
         x may be narrower than max_signal_length (a multiple of P): the pass then runs at L'/P + 1 tokens with position rows 0..L'/P.
         lengths: (B,) integer tensor (host or device) of per-record sample counts inside x (`check_lengths`); record b then gives what it
         would give alone at x[b:b+1, :, :lengths[b]] (dropout 0; up to summation order).  Not with fp8_linear or a fused input transform."""
-        if x.dim() == 2:
-            return self._forward_ragged(x, labels, weight, training, seed, want_mean, lengths)
-        B, X = self._trunk_pass(x, labels, weight, training, seed, cls_only_last, lengths)
-        a, T = self.act, hip.code(self.dtype)
+        return self._head_loss(self._trunk_pass(x, labels, weight, training, seed, cls_only_last, lengths), want_mean)
+
+    def _head_loss(self, X, want_mean):
+        """the tail of a supervised forward: a10 x[:, 0] -> LayerNorm -> Linear(d, K), a11 BCEWithLogitsLoss.  The head reads one row per
+        record at pitch saved['head_pitch']: N in the padded layout; 1 when X holds the CLS rows only (cls_only_last) or after gathering
+        the CLS rows tok_off[b] of a ragged batch compact.  Returns (logits, loss_elem | None, loss_mean | None)"""
+        a, sv, T = self.act, self.saved, hip.code(self.dtype)
         l, st = lib(), stream()
-        d, N = self.d, self.N
+        B, d, rg, labels = sv['B'], self.d, sv['ragged'], sv['labels']
         pre = 'vit.'
-        cls_only_last = self.saved['cls_only_last']
-        # a10: x[:, 0] -> LayerNorm -> Linear(d, K)   (cls_only_last: X holds the CLS rows only)
-        check(l.ecgvit_head_fwd(ptr(X), 1 if cls_only_last else N, ptr(self.P32[pre + 'mlp_head.0.weight']), ptr(self.P32[pre + 'mlp_head.0.bias']),
+        sv['head_pitch'] = 1 if (sv['cls_only_last'] or rg is not None) else self.N
+        if rg is not None:
+            check(l.ecgvit_gather_rows(ptr(X), ptr(rg.tok_off), ptr(a['cls_x2']), 1, rg.M, B, d, d, d, T, st), 'gather_rows')
+            X = a['cls_x2']
+        check(l.ecgvit_head_fwd(ptr(X), sv['head_pitch'], ptr(self.P32[pre + 'mlp_head.0.weight']), ptr(self.P32[pre + 'mlp_head.0.bias']),
                                 ptr(self.P32[pre + 'mlp_head.1.weight']), ptr(self.P32[pre + 'mlp_head.1.bias']),
                                 ptr(a['logits']), ptr(a['xhat']), ptr(a['hrstd']), B, d, self.K, LN_EPS, T, st), 'head_fwd')
         if labels is None:
             return a['logits'], None, None
-        # a11: BCEWithLogitsLoss
-        check(l.ecgvit_bce_fwd(ptr(a['logits']), ptr(labels), ptr(weight), ptr(a['loss_elem']),
+        check(l.ecgvit_bce_fwd(ptr(a['logits']), ptr(labels), ptr(sv['weight']), ptr(a['loss_elem']),
                                ptr(a['loss_mean']) if want_mean else None, B * self.K, st), 'bce_fwd')
         return a['logits'], a['loss_elem'], (a['loss_mean'] if want_mean else None)
 
     def _trunk_pass(self, x, labels, weight, training, seed, cls_only_last, lengths):
-        """`forward` of a (B, C, L') batch up to the trunk's output: validation, geometry, slabs, patch embedding, the L blocks.  Returns
-        (B, X) with X = saved['xL'], the last block's output ([B * N, d], or the compact CLS rows [B, d] under cls_only_last)"""
+        """`forward` up to the trunk's output: validation, geometry, slabs, patch embedding, the L blocks.  Returns X = saved['xL'], the last
+        block's output ([B * N, d], or the compact CLS rows [B, d] under cls_only_last).
+        A ragged batch: x (C, S) = the records concatenated along time, lengths (B,) their sample counts.  Every row-wise kernel runs over the
+        M = S / P + B packed token rows; attention per record on the packed rows; the classifier reads the CLS rows tok_off[b].  The last
+        block always runs in full (no cls_only_last).  Hidden and embedding dropout draw their bits by packed element index, so a ragged
+        step does not draw the masks of the padded step of the same records (attention dropout does, on the valid region).  X: [M, d]"""
+        if x.dim() == 2:
+            rg = self.check_ragged_input(x, lengths, labels)
+            self._set_width((rg.N - 1) * self.P)
+            return self._supervised_trunk(x, rg.B, labels, weight, training, seed, lengths=True, ragged=rg, raw=rg.rawside)
         B = x.shape[0]
         assert x.shape[1] == self.C and x.dtype == torch.float32 and x.is_contiguous()
         rp = None
@@ -1141,31 +1168,39 @@ class VitEngine:
         if lengths is not None:
             ntok = check_lengths(lengths, B, self.P, width)
             if ntok is not None and not ntok.is_cuda:
-                ntok = ntok.pin_memory().to(x.device, non_blocking=True)
+                ntok = _stage(ntok, x.device)
         if rp is not None:
             ntok = rp.ntok
-        self._alloc(B)
+        return self._supervised_trunk(x, B, labels, weight, training, seed, cls_only_last=cls_only_last, ntok=ntok,
+                                      lengths=lengths is not None or ntok is not None, raw=None if rp is None else rp.rawside)
+
+    def _supervised_trunk(self, x, B, labels, weight, training, seed, cls_only_last=False, ntok=None, lengths=False, ragged=None, raw=None):
+        """a validated supervised batch at the width already set, from the slabs to the trunk's output X = saved['xL'].  ragged: the
+        RaggedBatch of packed rows; ntok: per-record token counts of padded rows; raw: the `RawSide` of raw records"""
+        self._alloc(B, rows=None if ragged is None else ragged.M)
         a, T = self.act, hip.code(self.dtype)
         l, st = lib(), stream()
-        d, N, n = self.d, self.N, self.n
         ph = self.p_hidden if training else 0.0
         pe = self.p_emb if training else 0.0
         self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, labels=labels, weight=weight, masked=False, training=training, cls_only_last=cls_only_last,
-                          ntok=ntok, lengths=lengths is not None or ntok is not None, ragged=None, raw=None if rp is None else rp.rawside)
+                          ntok=ntok, lengths=lengths, ragged=ragged, raw=raw)
         if self.fp8:
             # EVERY forward, eval included, starts from the scales of the pass before it (delayed scaling with a history of one pass): an
             # inference-only model otherwise keeps its first batch's scales forever and clamps larger activations silently.  No backward can be
             # waiting for the old scales: a later forward overwrites the activations that backward reads (one live graph per model -- the
             # autograd node raises on a stale backward)
             self.fp8_begin_step(training)
-        pre = 'vit.'
-        self._patch_embed(x, B)
+        self._patch_rows(x)
         # a5: cat CLS, += pos_embedding[:, :n+1], emb dropout
-        check(l.ecgvit_embed_finish(ptr(a['tok']), ptr(self.P32[pre + 'cls_token']), ptr(self.P32[pre + 'pos_embedding']),
-                                    ptr(a['x0']), B, n, d, pe, seed + 1, T, st), 'embed_finish')
+        cls, pos = self.P32['vit.cls_token'], self.P32['vit.pos_embedding']
+        if ragged is not None:
+            check(l.ecgvit_embed_finish_ragged(ptr(a['tok']), ptr(cls), ptr(pos), ptr(a['x0']), ptr(ragged.n_tok), ptr(ragged.tok_off), B, self.N,
+                                               self.d, pe, seed + 1, T, st), 'embed_finish_ragged')
+        else:
+            check(l.ecgvit_embed_finish(ptr(a['tok']), ptr(cls), ptr(pos), ptr(a['x0']), B, self.n, self.d, pe, seed + 1, T, st), 'embed_finish')
         X = self._trunk_fwd(B, ph, seed, cls_only_last)
         self.saved['xL'] = X
-        return B, X
+        return X
 
     def check_ragged_input(self, x, lengths, labels=None):
         """validate a ragged (C, S) batch for this engine before anything launches -> RaggedBatch (`check_ragged`).  lengths may already be
@@ -1198,55 +1233,6 @@ class VitEngine:
             raise ValueError(f'labels must hold one row per record: {rg.B} records, got {labels.shape[0]} label rows')
         return rg
 
-    def _forward_ragged(self, x, labels, weight, training, seed, want_mean, lengths):
-        """`forward` of a ragged batch: x (C, S) = the records concatenated along time, lengths (B,) their sample counts.  Every row-wise
-        kernel runs over the M = S / P + B packed token rows; attention per record on the packed rows; the classifier reads the CLS rows
-        tok_off[b].  The last block always runs in full (no cls_only_last).  Hidden and embedding dropout draw their bits by packed element
-        index, so a ragged step does not draw the masks of the padded step of the same records (attention dropout does, on the valid region)."""
-        rg, X = self._trunk_pass_ragged(x, labels, weight, training, seed, lengths)
-        B, M = rg.B, rg.M
-        a, T = self.act, hip.code(self.dtype)
-        l, st = lib(), stream()
-        d = self.d
-        pre = 'vit.'
-        # a10: the CLS rows tok_off[b], gathered compact, -> LayerNorm -> Linear(d, K)
-        check(l.ecgvit_gather_rows(ptr(X), ptr(rg.tok_off), ptr(a['cls_x2']), 1, M, B, d, d, d, T, st), 'gather_rows')
-        check(l.ecgvit_head_fwd(ptr(a['cls_x2']), 1, ptr(self.P32[pre + 'mlp_head.0.weight']), ptr(self.P32[pre + 'mlp_head.0.bias']),
-                                ptr(self.P32[pre + 'mlp_head.1.weight']), ptr(self.P32[pre + 'mlp_head.1.bias']),
-                                ptr(a['logits']), ptr(a['xhat']), ptr(a['hrstd']), B, d, self.K, LN_EPS, T, st), 'head_fwd')
-        if labels is None:
-            return a['logits'], None, None
-        check(l.ecgvit_bce_fwd(ptr(a['logits']), ptr(labels), ptr(weight), ptr(a['loss_elem']),
-                               ptr(a['loss_mean']) if want_mean else None, B * self.K, st), 'bce_fwd')
-        return a['logits'], a['loss_elem'], (a['loss_mean'] if want_mean else None)
-
-    def _trunk_pass_ragged(self, x, labels, weight, training, seed, lengths):
-        """`_forward_ragged` up to the trunk's output -> (RaggedBatch, X) with X = saved['xL'], the packed rows [M, d]"""
-        rg = self.check_ragged_input(x, lengths, labels)
-        B, M = rg.B, rg.M
-        self._set_width((rg.N - 1) * self.P)
-        self._alloc(B, rows=M)
-        a, T = self.act, hip.code(self.dtype)
-        l, st = lib(), stream()
-        d, N = self.d, self.N
-        ph = self.p_hidden if training else 0.0
-        pe = self.p_emb if training else 0.0
-        self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, labels=labels, weight=weight, masked=False, training=training, cls_only_last=False,
-                          ntok=None, lengths=True, ragged=rg)
-        pre = 'vit.'
-        # a4: the packed patch gather is the uniform one over the concatenation: patch row off_b / P + j is patch j of record b
-        if rg.rawside is not None:   # raw records: transformed per record on the way, rows at the padded offsets
-            self._gather_raw(x, rg.rawside, training)
-        else:
-            check(lib().ecgvit_patch_gather(ptr(x), ptr(a['patches']), 1, self.C, rg.S, self.P, self.CP, T, st), 'patch_gather')
-        self._gemm(GEMM_NT, a['patches'], self.W[pre + 'to_patch_embedding.1.weight'], a['tok'], M - B, d, self.CP, self.CP, self.CP, d,
-                   epilogue=EPI_BIAS, bias=self.P32[pre + 'to_patch_embedding.1.bias'])
-        check(l.ecgvit_embed_finish_ragged(ptr(a['tok']), ptr(self.P32[pre + 'cls_token']), ptr(self.P32[pre + 'pos_embedding']), ptr(a['x0']),
-                                           ptr(rg.n_tok), ptr(rg.tok_off), B, N, d, pe, seed + 1, T, st), 'embed_finish_ragged')
-        X = self._trunk_fwd(B, ph, seed)
-        self.saved['xL'] = X
-        return rg, X
-
     # ---------------------------------------------------------------- pooled representations (EcgVit.encode)
     POOL_MODES = {'cls': hip.POOL_CLS, 'mean': hip.POOL_MEAN}
 
@@ -1258,11 +1244,8 @@ class VitEngine:
         Overwrites the activations like any forward."""
         if pool not in self.POOL_MODES:
             raise ValueError(f"pool must be 'cls' or 'mean', got {pool!r}")
-        if x.dim() == 2:
-            self._trunk_pass_ragged(x, None, None, False, 0, lengths)
-        else:
-            prune = pool == 'cls' and self.dtype == torch.bfloat16 and not self.fp8
-            self._trunk_pass(x, None, None, False, 0, prune, lengths)
+        prune = pool == 'cls' and x.dim() == 3 and self.dtype == torch.bfloat16 and not self.fp8
+        self._trunk_pass(x, None, None, False, 0, prune, lengths)
         return self.pool_saved(pool, norm)
 
     def pool_saved(self, pool='cls', norm=True):
@@ -1274,23 +1257,23 @@ class VitEngine:
         sv = self.saved
         if sv is None or sv.get('masked') or sv.get('xL') is None:
             raise RuntimeError('pool_saved needs the trunk output of a supervised forward')
-        rg = sv.get('ragged')
-        n_tok = tok_off = None
-        N = self.N
+        n_tok, tok_off, N = *self._row_tables(sv), self.N
         if sv.get('cls_only_last'):
             if pool != 'cls':
                 raise ValueError("pool='mean' needs every token row: the last forward computed the last block's CLS rows only (cls_only_last)")
-            N = 1
-        elif rg is not None:
-            n_tok, tok_off = rg.n_tok, rg.tok_off
-        else:
-            n_tok = sv.get('ntok')
+            n_tok, tok_off, N = None, None, 1
         B, pre = sv['B'], 'vit.'
         out = torch.empty((B, self.d), dtype=torch.float32, device=sv['xL'].device)
         g, b = (self.P32[pre + 'mlp_head.0.weight'], self.P32[pre + 'mlp_head.0.bias']) if norm else (None, None)
         check(lib().ecgvit_pool_records(ptr(sv['xL']), ptr(out), ptr(n_tok), ptr(tok_off), B, N, self.d, self.POOL_MODES[pool], ptr(g), ptr(b),
                                         LN_EPS, hip.code(self.dtype), stream()), 'pool_records')
         return out
+
+    @staticmethod
+    def _row_tables(sv):
+        """(n_tok, tok_off) of the pass `sv` describes: the packed rows of a ragged batch, per-record token counts of padded rows, or neither"""
+        rg = sv.get('ragged')
+        return (rg.n_tok, rg.tok_off) if rg is not None else (sv.get('ntok'), None)
 
     def _pass_rows(self, B):
         """token rows of the current pass: B x tokens per record, or the packed rows of a ragged batch"""
@@ -1306,28 +1289,35 @@ class VitEngine:
         self._set_width(self.L_max)   # (B, m) indices: full-width records; records of unequal length go through forward_masked_varlen
         assert idx.dtype == torch.int32 and idx.is_contiguous() and 0 < m <= self.n
         self._alloc(B, masked=True, m=m)
-        a, W, T = self.act, self.W, hip.code(self.dtype)
-        l, st = lib(), stream()
-        d, n = self.d, self.n
-        ph = self.p_hidden if training else 0.0
-        pe = self.p_emb if training else 0.0
-        self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, masked=True, idx=idx, m=m, training=training)
+        a, n, d = self.act, self.n, self.d
+        ph, pe = (self.p_hidden, self.p_emb) if training else (0.0, 0.0)
+        self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, masked=True, idx=idx, m=m, mrows=(B, n, m), training=training)
         if self.fp8:
             self.fp8_begin_step(training)
-        self._patch_embed(x, B)
-        check(l.ecgvit_mask_embed_finish(ptr(a['tok']), ptr(self.P32['pretrain.mask_token']), ptr(self.P32['vit.pos_embedding']),
-                                         ptr(idx), ptr(a['x0']), ptr(a['flag']), B, n, m, d, T, st), 'mask_embed_finish')
+        self._patch_rows(x)
+        check(lib().ecgvit_mask_embed_finish(ptr(a['tok']), ptr(self.P32['pretrain.mask_token']), ptr(self.P32['vit.pos_embedding']),
+                                             ptr(idx), ptr(a['x0']), ptr(a['flag']), B, n, m, d, hip.code(self.dtype), stream()), 'mask_embed_finish')
+        return self._masked_trunk_and_loss()
+
+    def _masked_trunk_and_loss(self):
+        """a masked pass from act['x0'] on: embedding dropout, the L blocks, masked rows -> Linear(d, C*P), L1 against the same rows of the
+        raw patches.  saved['mrows'] = (batches, rows per batch, indices per batch) is how saved['idx'] addresses the masked rows: (B, n, m)
+        for (B, m) record-local indices, (1, M, sum m_b) for row numbers of the whole pass.  Returns (pred, loss (1,))"""
+        a, sv, T = self.act, self.saved, hip.code(self.dtype)
+        l, st = lib(), stream()
+        B, pe, seed, idx, d, CP = sv['B'], sv['pe'], sv['seed'], sv['idx'], self.d, self.CP
+        nb, nrow, m = sv['mrows']
         if pe > 0:
-            self._drop_apply(a['x0'], a['x0'], B * n * d, pe, seed + 1)
-        X = self._trunk_fwd(B, ph, seed)
-        self.saved['xL'] = X
-        check(l.ecgvit_gather_rows(ptr(X), ptr(idx), ptr(a['rows']), B, n, m, d, d, d, T, st), 'gather_rows')
-        self._gemm(GEMM_NT, a['rows'], W['pretrain.to_pixels.weight'], a['pred'], B * m, self.CP, d, d, d, self.CP, epilogue=EPI_BIAS,
-                 bias=self.P32['pretrain.to_pixels.bias'])
-        check(l.ecgvit_gather_rows(ptr(a['patches']), ptr(idx), ptr(a['target']), B, n, m, self.CP, self.CP, self.CP, T, st), 'gather_rows')
+            self._drop_apply(a['x0'], a['x0'], self._pass_rows(B) * d, pe, seed + 1)
+        X = self._trunk_fwd(B, sv['ph'], seed)
+        sv['xL'] = X
+        check(l.ecgvit_gather_rows(ptr(X), ptr(idx), ptr(a['rows']), nb, nrow, m, d, d, d, T, st), 'gather_rows')
+        self._gemm(GEMM_NT, a['rows'], self.W['pretrain.to_pixels.weight'], a['pred'], nb * m, CP, d, d, d, CP, epilogue=EPI_BIAS,
+                   bias=self.P32['pretrain.to_pixels.bias'])
+        check(l.ecgvit_gather_rows(ptr(a['patches']), ptr(idx), ptr(a['target']), nb, nrow, m, CP, CP, CP, T, st), 'gather_rows')
         # L1 loss and d(loss)/d(pred) in one pass (upstream gradient 1; backward_masked re-runs it for any other upstream)
-        check(l.ecgvit_l1_loss_fwd_bwd(ptr(a['pred']), ptr(a['target']), ptr(a['mloss']), ptr(a['dpred']), None, ptr(a['l1part']), B * m, self.CP,
-                                       self.CP, T, st), 'l1_loss')
+        check(l.ecgvit_l1_loss_fwd_bwd(ptr(a['pred']), ptr(a['target']), ptr(a['mloss']), ptr(a['dpred']), None, ptr(a['l1part']), nb * m, CP, CP, T, st),
+              'l1_loss')
         return a['pred'], a['mloss']
 
     def check_masked_varlen_input(self, x, mask_idx, lengths, mask_counts):
@@ -1345,35 +1335,15 @@ class VitEngine:
         assert x.dtype == torch.float32 and x.is_contiguous() and geo.rows is not None
         self._set_width((geo.N if packed else geo.n_pad) * self.P)
         self._alloc(B, masked=True, rows=M if packed else None, mrows=mt)
-        a, W, T = self.act, self.W, hip.code(self.dtype)
-        l, st = lib(), stream()
-        d = self.d
-        ph = self.p_hidden if training else 0.0
-        pe = self.p_emb if training else 0.0
-        self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, masked=True, idx=geo.rows, m=mt, training=training, geo=geo, lengths=True,
-                          ntok=None if packed else geo.n_tok, ragged=geo if packed else None)
-        if geo.rawside is not None:   # raw records under a per-record transform: either row layout, transformed on the way
-            self._gather_raw(x, geo.rawside, training)
-        elif packed:   # the uniform gather over the concatenation: patch row off_b / P + j is patch j of record b
-            check(l.ecgvit_patch_gather(ptr(x), ptr(a['patches']), 1, self.C, geo.S, self.P, self.CP, T, st), 'patch_gather')
-        else:        # zero patches past each record's length (n_cls = n_b + 1: the kernel's count includes a CLS token)
-            check(l.ecgvit_patch_gather_varlen(ptr(x), ptr(a['patches']), ptr(geo.n_cls), B, self.C, self.L, self.P, self.CP, T, st), 'patch_gather_varlen')
-        self._gemm(GEMM_NT, a['patches'], W['vit.to_patch_embedding.1.weight'], a['tok'], M, d, self.CP, self.CP, self.CP, d, epilogue=EPI_BIAS,
-                   bias=self.P32['vit.to_patch_embedding.1.bias'])
-        check(l.ecgvit_mask_embed_varlen_fwd(ptr(a['tok']), ptr(self.P32['pretrain.mask_token']), ptr(self.P32['vit.pos_embedding']), ptr(geo.rows),
-                                             ptr(a['x0']), ptr(a['flag']), ptr(geo.n_tok), ptr(geo.tok_off), B, geo.N, geo.n_pad, M, mt, d, T, st),
-              'mask_embed_varlen_fwd')
-        if pe > 0:
-            self._drop_apply(a['x0'], a['x0'], M * d, pe, seed + 1)
-        X = self._trunk_fwd(B, ph, seed)
-        self.saved['xL'] = X
-        check(l.ecgvit_gather_rows(ptr(X), ptr(geo.rows), ptr(a['rows']), 1, M, mt, d, d, d, T, st), 'gather_rows')
-        self._gemm(GEMM_NT, a['rows'], W['pretrain.to_pixels.weight'], a['pred'], mt, self.CP, d, d, d, self.CP, epilogue=EPI_BIAS,
-                   bias=self.P32['pretrain.to_pixels.bias'])
-        check(l.ecgvit_gather_rows(ptr(a['patches']), ptr(geo.rows), ptr(a['target']), 1, M, mt, self.CP, self.CP, self.CP, T, st), 'gather_rows')
-        check(l.ecgvit_l1_loss_fwd_bwd(ptr(a['pred']), ptr(a['target']), ptr(a['mloss']), ptr(a['dpred']), None, ptr(a['l1part']), mt, self.CP,
-                                       self.CP, T, st), 'l1_loss')
-        return a['pred'], a['mloss']
+        a = self.act
+        ph, pe = (self.p_hidden, self.p_emb) if training else (0.0, 0.0)
+        self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, masked=True, idx=geo.rows, m=mt, mrows=(1, M, mt), training=training, geo=geo, lengths=True,
+                          ntok=None if packed else geo.n_tok, ragged=geo if packed else None, raw=geo.rawside)
+        self._patch_rows(x)
+        check(lib().ecgvit_mask_embed_varlen_fwd(ptr(a['tok']), ptr(self.P32['pretrain.mask_token']), ptr(self.P32['vit.pos_embedding']), ptr(geo.rows),
+                                                 ptr(a['x0']), ptr(a['flag']), ptr(geo.n_tok), ptr(geo.tok_off), B, geo.N, geo.n_pad, M, mt, self.d,
+                                                 hip.code(self.dtype), stream()), 'mask_embed_varlen_fwd')
+        return self._masked_trunk_and_loss()
 
     def backward_masked(self, gscalar=None, tiles_per_workgroup=0, trainable=None):
         """loss + every gradient of the masked objective (the L1 kernel produces loss and dpred in one pass).
@@ -1391,12 +1361,12 @@ class VitEngine:
         a, W, T = self.act, self.W, hip.code(self.dtype)
         l, st = lib(), stream()
         sv = self.saved
-        B, m, idx, pe, seed = sv['B'], sv['m'], sv['idx'], sv['pe'], sv['seed']
+        B, idx, pe, seed = sv['B'], sv['idx'], sv['pe'], sv['seed']
         d, n = self.d, self.n
         G = self.G32
-        geo = sv.get('geo')   # records of unequal length: idx = the masked rows of the pass, m = their count
         M = self._pass_rows(B)
-        Rm = m if geo is not None else B * m
+        nb, nrow, m = sv['mrows']   # how idx addresses the masked rows (`_masked_trunk_and_loss`)
+        Rm = nb * m
         if gscalar is not None:
             check(l.ecgvit_l1_loss_fwd_bwd(ptr(a['pred']), ptr(a['target']), ptr(a['mloss']), ptr(a['dpred']), ptr(gscalar), ptr(a['l1part']), Rm,
                                            self.CP, self.CP, T, st), 'l1_loss')
@@ -1413,15 +1383,13 @@ class VitEngine:
         self._gemm(GEMM_NN, a['dpred'], W['pretrain.to_pixels.weight'], a['drows'], Rm, d, self.CP, self.CP, d, d)
         dX = a['dxa']
         dX.zero_()
-        if geo is not None:
-            check(l.ecgvit_scatter_rows(ptr(a['drows']), ptr(idx), ptr(dX), 1, M, m, d, d, d, T, st), 'scatter_rows')
-        else:
-            check(l.ecgvit_scatter_rows(ptr(a['drows']), ptr(idx), ptr(dX), B, n, m, d, d, d, T, st), 'scatter_rows')
+        check(l.ecgvit_scatter_rows(ptr(a['drows']), ptr(idx), ptr(dX), nb, nrow, m, d, d, d, T, st), 'scatter_rows')
         dX = self._trunk_bwd(dX, a['dxb'])
         if dX is None or not self._reach(self._stage(-1, 0)):
             return
         if pe > 0:
             self._drop_apply(dX, dX, M * d, pe, seed + 1)
+        geo = sv.get('geo')   # records of unequal length
         if geo is not None:
             check(l.ecgvit_mask_embed_varlen_bwd(ptr(dX), ptr(a['flag']), ptr(a['dtok']), ptr(a['dmasked']), ptr(G['vit.pos_embedding']),
                                                  ptr(geo.n_tok), ptr(geo.tok_off), ptr(geo.order), B, geo.N, geo.n_pad, d, T, st), 'mask_embed_varlen_bwd')
@@ -1521,11 +1489,11 @@ class VitEngine:
                 self._ready(tag)
 
     def _backward(self, gscalar, gelem, gscale, glogits):
-        a, W, T = self.act, self.W, hip.code(self.dtype)
+        a, T = self.act, hip.code(self.dtype)
         l, st = lib(), stream()
         sv = self.saved
-        B, ph, pe, seed = sv['B'], sv['ph'], sv['pe'], sv['seed']
-        d, f, h, dh, N, n = self.d, self.f, self.h, self.dh, self.N, self.n
+        B, pe, seed = sv['B'], sv['pe'], sv['seed']
+        d, N, n = self.d, self.N, self.n
         rg = sv.get('ragged')
         M = self._pass_rows(B)
         Mp = M - B
@@ -1541,7 +1509,9 @@ class VitEngine:
             dlog = glogits
         else:
             raise ValueError('backward needs an upstream gradient')
-        cls = sv.get('cls_only_last', False)
+        cls, pitch = sv.get('cls_only_last', False), sv.get('head_pitch')   # (pitch 1: the head read compact CLS rows -- `_head_loss`)
+        if pitch is None:
+            raise RuntimeError('backward needs a supervised forward: the last pass (encode, or a hand-made `saved`) did not run the head')
         dX = a['cls_dx'] if cls else a['dxa']   # (cls_only_last: the gradient of the CLS rows only, compact)
         if not self._reach(0):   # frozen parameters: nothing trainable takes part in this objective's backward
             self._zero_pretrain_grads()
@@ -1550,7 +1520,7 @@ class VitEngine:
                                 ptr(self.P32[pre + 'mlp_head.0.bias']), ptr(self.P32[pre + 'mlp_head.1.weight']),
                                 ptr(G[pre + 'mlp_head.1.weight']), ptr(G[pre + 'mlp_head.1.bias']),
                                 ptr(G[pre + 'mlp_head.0.weight']), ptr(G[pre + 'mlp_head.0.bias']),
-                                ptr(a['cls_dx'] if rg is not None else dX), 1 if (cls or rg is not None) else N, B, d, self.K, T, st), 'head_bwd')
+                                ptr(a['cls_dx'] if pitch == 1 else dX), pitch, B, d, self.K, T, st), 'head_bwd')
         if rg is not None:   # the CLS rows' gradient, compact -> rows tok_off[b]; every other row 0
             dX[:M].zero_()
             check(l.ecgvit_scatter_rows(ptr(a['cls_dx']), ptr(rg.tok_off), ptr(dX), 1, M, B, d, d, d, T, st), 'scatter_rows')
@@ -1589,13 +1559,10 @@ class VitEngine:
     def _trunk_bwd(self, dX, other, cls_only_last=False):
         """backward of _trunk_fwd: consumes dX = d(loss)/d(x_L) ([B*T, d]; cls_only_last: [B, d], the CLS rows), fills every layer's
         parameter gradients, returns d(x_0) -- or None when a backward plan (frozen parameters) stopped the pass inside the trunk"""
-        a, W, T = self.act, self.W, hip.code(self.dtype)
-        l, st = lib(), stream()
-        sv = self.saved
+        a, sv = self.act, self.saved
         B, ph, seed = sv['B'], sv['ph'], sv['seed']
-        d, f, h, dh, N = self.d, self.f, self.h, self.dh, self.T
+        d, f = self.d, self.f
         M = self._pass_rows(B)
-        rg = sv.get('ragged')
         pre = 'vit.'
         G = self.G32
         # dY = gradient entering the current `dropout(Linear + bias) + residual` site (masked copy of dX when dropout is on);
@@ -1655,27 +1622,9 @@ class VitEngine:
             if not self._reach(b + 3):
                 return None
             self._dgrad(dY, lp + '0.fn.to_out.0.weight', a['dattn'], M, d, d, site=8 * i + 6, pre=g6)
-            pq7 = False   # fp8_linear: the attention backward wrote the e5m2 copy of dqkv itself (into the operand scratch)
             if not self._reach(b + 4):
                 return None
-            ntok = sv.get('ntok')
-            if rg is not None:
-                check(l.ecgvit_attention_ragged_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), ptr(rg.n_tok),
-                                                    ptr(rg.tok_off), B, N, h, dh, self.scale, ph, s0 + 1, st), 'attention_ragged_bwd')
-            elif self.dtype == torch.bfloat16 and ntok is not None:
-                check(l.ecgvit_attention_varlen_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), ptr(ntok), B, N, h,
-                                                    dh, self.scale, ph, s0 + 1, st), 'attention_varlen_bwd')
-            elif self.dtype == torch.bfloat16:
-                if f8 and (8 * i + 7) in self._f8_seen and dh == 64 and 128 < N <= 512 and N * 3 * d * 2 < 2 ** 31:   # (dh = 128: _grad8 quantises dqkv)
-                    check(l.ecgvit_attention_bwd_q8(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), B, N, h, dh, self.scale,
-                                                    ph, s0 + 1, ptr(a['q8']), ptr(self.f8_scale[8 * i + 7:8 * i + 8]), ptr(self.f8_amax[8 * i + 7:8 * i + 8]), st),
-                          'attention_bwd_q8')
-                    pq7 = True
-                else:
-                    check(l.ecgvit_attention_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), B, N, h,
-                                                 dh, self.scale, ph, s0 + 1, T, st), 'attention_bwd')
-            else:
-                self._attn_bwd_f32(L, B, ph, s0 + 1)
+            pq7 = self._attention_bwd(L, i, B, ph, s0 + 1)   # fp8_linear: True = it wrote the e5m2 copy of dqkv itself (operand scratch)
             g7 = self._grad8(8 * i + 7, a['dqkv'], M * 3 * d, prequant='q8' if pq7 else False) if f8 and (self._wants(lp + '0.fn.to_qkv.weight') or self._reach(b + 5)) else None
             self._wgrad(a['dqkv'], L['xn1'], lp + '0.fn.to_qkv.weight', 3 * d, d, M, pre=g7, x8=L.get('xn1_8'), xsite=8 * i)
             if not self._reach(b + 5):
@@ -1707,7 +1656,7 @@ class VitEngine:
         the free full slab = dres), or (None, None) when a backward plan (frozen parameters) stopped the pass inside the block"""
         a, W, P, G = self.act, self.W, self.P32, self.G32
         l, st = lib(), stream()
-        d, f, h, dh, N = self.d, self.f, self.h, self.dh, self.T
+        d, f, N = self.d, self.f, self.T
         M, T, ws = B * N, hip.code(self.dtype), a['ws']
         i = self.Ly - 1
         L = a['layers'][i]
@@ -1747,13 +1696,7 @@ class VitEngine:
         self._gemm(GEMM_NN, dY, W[lp + '0.fn.to_out.0.weight'], a['cls_dattn'], B, d, d, d, d, d)
         if not self._reach(b + 4):
             return None, None
-        ntok = self.saved.get('ntok')
-        if ntok is not None:
-            check(l.ecgvit_attention_varlen_cls_bwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_dattn']), ptr(a['cls_lse']), ptr(a['dqkv']),
-                                                    ptr(a['cls_dq']), ptr(ntok), B, N, h, dh, self.scale, ph, s0 + 1, st), 'attention_varlen_cls_bwd')
-        else:
-            check(l.ecgvit_attention_cls_bwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_dattn']), ptr(a['cls_lse']), ptr(a['dqkv']), ptr(a['cls_dq']),
-                                             B, N, h, dh, self.scale, ph, s0 + 1, T, st), 'attention_cls_bwd')
+        self._attention_cls_bwd(L, B, ph, s0 + 1)
         # to_qkv: dW[K|V] = dKV^T . xn1 over every row, dW[Q] = dQ^T . xn1 over the CLS rows; d(xn1) = dKV . W[K|V] (+ dQ . W[Q] on the CLS rows)
         name = lp + '0.fn.to_qkv.weight'
         if self._wants(name):
@@ -1824,11 +1767,7 @@ class VitEngine:
         if sv.get('cls_only_last'):
             raise RuntimeError('the last forward ran with cls_only_last: its last block computed the CLS query only')
         rg = sv.get('ragged')
-        n_tok = tok_off = None
-        if rg is not None:
-            n_tok, tok_off = rg.n_tok, rg.tok_off
-        else:
-            n_tok = sv.get('ntok')
+        n_tok, tok_off = self._row_tables(sv)
         B, N, h, dh, Ly = sv['B'], self.T, self.h, self.dh, self.Ly
         layers = self.act['layers']
         dev = layers[0]['qkv'].device
