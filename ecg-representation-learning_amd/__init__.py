@@ -9,6 +9,7 @@ from .check_args import ca, CheckArg
 from .ecg_vit import EcgVitConfig, EcgVit, ModelOutput, RolloutOutput, HipViT, MaskedEcgVit, load_trained
 from .train import get_train_args, lr_multiplier, HipTrainStep, HipProbeStep, clip_grad_norm_
 from .transform import FusedInputTransform, fit_dynamic_normalize, DynamicNormalizeFit
+from .tokenizer import EcgTokenizer
 from .metrics import get_accuracy, eval_counts, HipEvaluator, HipEncoder, HipRollout
 from .feed import DeviceFeeder, RaggedDeviceFeeder, ptbxl_splits, lbs2multi_hot, open_records
 from . import hip
@@ -16,4 +17,4 @@ from . import ddp
 from . import workload
 
 __all__ = ['ca', 'CheckArg', 'EcgVitConfig', 'EcgVit', 'ModelOutput', 'RolloutOutput', 'HipViT', 'MaskedEcgVit', 'load_trained', 'get_train_args', 'lr_multiplier',
-           'HipTrainStep', 'HipProbeStep', 'clip_grad_norm_', 'FusedInputTransform', 'fit_dynamic_normalize', 'DynamicNormalizeFit', 'get_accuracy', 'eval_counts', 'HipEvaluator', 'HipEncoder', 'HipRollout', 'DeviceFeeder', 'RaggedDeviceFeeder', 'ptbxl_splits', 'lbs2multi_hot', 'open_records', 'hip', 'ddp', 'workload']
+           'HipTrainStep', 'HipProbeStep', 'clip_grad_norm_', 'FusedInputTransform', 'fit_dynamic_normalize', 'DynamicNormalizeFit', 'EcgTokenizer', 'get_accuracy', 'eval_counts', 'HipEvaluator', 'HipEncoder', 'HipRollout', 'DeviceFeeder', 'RaggedDeviceFeeder', 'ptbxl_splits', 'lbs2multi_hot', 'open_records', 'hip', 'ddp', 'workload']

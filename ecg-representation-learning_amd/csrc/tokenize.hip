@@ -1,0 +1,373 @@
+// The segment tokenizer (tokenizer.EcgTokenizer; the reference's models/ecg_tokenizer.py): nearest-centre assignment, the Lloyd update and the
+// decode, over a record store addressed as fit_stats.hip addresses it.  Contract, padding rule and the order of every sum: include/ecgvit_hip.h.
+//
+// Work is laid out per lead: workgroup (b, c) takes positions [b * span, (b + 1) * span) of lead c's segments, a position finds its record by
+// a binary search in seg_cum.  The padding is applied in the segment load; no padded copy of the store exists.
+#include "common.h"
+
+#define TOK_THREADS 256
+#define TOK_NS 4                                        // groups of 32 segments per wave: four independent accumulators
+#define TOK_SPAN (TOK_THREADS / WAVE * TOK_NS * 32)     // segments per workgroup of the assign kernel (512)
+#define TOK_CHUNK 8192                                  // centre floats per LDS chunk: 32 KiB, + the norms; the table is streamed chunk by chunk
+
+typedef unsigned long long u64;
+
+struct TokStore {
+    const float *x;
+    const int64_t *src_off;
+    int64_t lead_stride;
+    const int32_t *raw_len;
+    const int64_t *seg_cum;
+    const int64_t *dst_off;
+    int64_t dst_stride;
+    int R, pad;
+};
+
+// the record of position p: the last r with seg_cum[r] <= p (seg_cum[0] = 0 <= p < seg_cum[R])
+__device__ __forceinline__ int tok_record(const int64_t *__restrict__ seg_cum, int R, int64_t p) {
+    int lo = 0, hi = R;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (seg_cum[mid] <= p) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+struct TokSeg { int r, len; int64_t s, dst; };
+
+__device__ __forceinline__ TokSeg tok_locate(const TokStore &st, int c, int64_t p) {
+    TokSeg g;
+    g.r = tok_record(st.seg_cum, st.R, p);
+    g.s = p - st.seg_cum[g.r];
+    g.len = st.raw_len[g.r];
+    g.dst = st.dst_off[g.r] + (int64_t)c * st.dst_stride + g.s;
+    return g;
+}
+
+// the K samples of a segment minus their mean -> v, returns the mean.  Every index read lies in [0, len): position i >= len is 0 ('zero')
+// or sample i - n_pad ('shift'), clamped into the run.
+template <int K> __device__ __forceinline__ float tok_load(const TokStore &st, int c, const TokSeg &g, float (&v)[K]) {
+    const float *__restrict__ base = st.x + st.src_off[g.r] + (int64_t)c * st.lead_stride;
+    const int64_t len = g.len, i0 = g.s * K;
+    const int64_t n_pad = K - (len % K);
+#pragma unroll
+    for (int e = 0; e < K; ++e) {
+        const int64_t i = i0 + e;
+        float t = 0.f;
+        if (len > 0) {
+            if (i < len) {
+                t = base[i];
+            } else if (st.pad == 1) {
+                int64_t j = i - n_pad;
+                j = j < 0 ? 0 : (j >= len ? len - 1 : j);
+                t = base[j];
+            }
+        }
+        v[e] = t;
+    }
+    float sum = v[0];
+#pragma unroll
+    for (int e = 1; e < K; ++e) sum = sum + v[e];
+    const float mean = sum * (1.0f / K);
+#pragma unroll
+    for (int e = 0; e < K; ++e) v[e] = v[e] - mean;
+    return mean;
+}
+
+// =====================================================================================================
+// assign.  D = A . B + C on v_mfma_f32_32x32x2_f32 with A = 32 centres (row i on lane i & 31, sample 2 kk + (lane >> 5)), B = 32 segments
+// times -2 (column j on lane j & 31, the same sample) and C = |c_i|^2 in every column: after K / 2 instructions register g of lane (j, h) is
+// the score of centre (g & 3) + 8 (g >> 2) + 4 h of the tile for segment j -- the segment's operand and its 16 scores sit on the same lane,
+// so the running (best score, best index) pair is two registers per segment group and never leaves the lane until the two halves meet at the
+// end.  Centres are visited in ascending order with a strict <: equal scores keep the smaller index.
+// LDS: the chunk of the table transposed, ct[sample][centre] (consecutive lanes read consecutive words), and its norms; rows past V are zero
+// with norm +inf: never below a finite score.
+// =====================================================================================================
+template <int K>
+__global__ __launch_bounds__(TOK_THREADS) void tok_assign_kernel(TokStore st, int64_t n_seg, const float *__restrict__ centers, int V,
+                                                                  const int32_t *prev_ids, int32_t *ids, float *__restrict__ means,
+                                                                  float *__restrict__ dist, u64 *__restrict__ changed) {
+    constexpr int KH = K / 2, VT = TOK_CHUNK / K;
+    __shared__ __attribute__((aligned(16))) float ct[K * VT];
+    __shared__ __attribute__((aligned(16))) float cn[VT];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 31, h = lane >> 5, c = blockIdx.y;
+    const uint32_t hmask = 0u - (uint32_t)h;
+    float b[TOK_NS][KH], mean[TOK_NS], best[TOK_NS];
+    int bi[TOK_NS];
+    int64_t dst[TOK_NS];
+    bool live[TOK_NS];
+#pragma unroll
+    for (int q = 0; q < TOK_NS; ++q) {
+        const int64_t p = (int64_t)blockIdx.x * TOK_SPAN + (wave * TOK_NS + q) * 32 + j;
+        live[q] = p < n_seg;
+        best[q] = __builtin_inff();
+        bi[q] = 0;
+        mean[q] = 0.f;
+        dst[q] = 0;
+#pragma unroll
+        for (int kk = 0; kk < KH; ++kk) b[q][kk] = 0.f;
+        if (live[q]) {
+            const TokSeg g = tok_locate(st, c, p);
+            float v[K];
+            mean[q] = tok_load<K>(st, c, g, v);
+            dst[q] = g.dst;
+#pragma unroll
+            for (int kk = 0; kk < KH; ++kk) {   // the lane half's sample of the pair, picked on the bits: both stay in registers
+                const uint32_t even = __float_as_uint(v[2 * kk]), odd = __float_as_uint(v[2 * kk + 1]);
+                b[q][kk] = -2.0f * __uint_as_float((odd & hmask) | (even & ~hmask));
+            }
+        }
+    }
+    for (int v0 = 0; v0 < V; v0 += VT) {
+        __syncthreads();   // the previous chunk has been read
+        for (int t = tid; t < VT; t += TOK_THREADS) {
+            const int row = v0 + t;
+            float n2 = __builtin_inff();
+            if (row < V) {
+                n2 = 0.f;
+#pragma unroll
+                for (int e = 0; e < K; ++e) {
+                    const float w = centers[(int64_t)row * K + e];
+                    ct[e * VT + t] = w;
+                    n2 = fmaf(w, w, n2);
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < K; ++e) ct[e * VT + t] = 0.f;
+            }
+            cn[t] = n2;
+        }
+        __syncthreads();
+        const int rows = V - v0 < VT ? V - v0 : VT;
+        for (int t0 = 0; t0 < rows; t0 += 32) {
+            f32x16 cinit;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 n4 = *reinterpret_cast<const f32x4 *>(&cn[t0 + 8 * g + 4 * h]);
+                cinit[4 * g] = n4[0]; cinit[4 * g + 1] = n4[1]; cinit[4 * g + 2] = n4[2]; cinit[4 * g + 3] = n4[3];
+            }
+            f32x16 acc[TOK_NS];
+#pragma unroll
+            for (int q = 0; q < TOK_NS; ++q) acc[q] = cinit;
+#pragma unroll
+            for (int kk = 0; kk < KH; ++kk) {
+                const float a = ct[(2 * kk + h) * VT + t0 + j];
+#pragma unroll
+                for (int q = 0; q < TOK_NS; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b[q][kk], acc[q], 0, 0, 0);
+            }
+            const int i0 = v0 + t0 + 4 * h;
+#pragma unroll
+            for (int q = 0; q < TOK_NS; ++q) {
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                    const float s = acc[q][g];
+                    const bool lt = s < best[q];
+                    best[q] = lt ? s : best[q];
+                    bi[q] = lt ? i0 + (g & 3) + 8 * (g >> 2) : bi[q];
+                }
+            }
+        }
+    }
+    u64 nchanged = 0;
+#pragma unroll
+    for (int q = 0; q < TOK_NS; ++q) {
+        const float ob = __shfl_xor(best[q], 32, 64);
+        const int oi = __shfl_xor(bi[q], 32, 64);
+        if (ob < best[q] || (ob == best[q] && oi < bi[q])) { best[q] = ob; bi[q] = oi; }
+        const int id = bi[q];   // < V: index 0 unless a finite score was seen
+        float part = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < KH; ++kk) {
+            const float d = -0.5f * b[q][kk] - centers[(int64_t)id * K + 2 * kk + h];
+            part = fmaf(d, d, part);
+        }
+        const float d2 = part + __shfl_xor(part, 32, 64);
+        const bool wr = live[q] && h == 0;
+        bool ch = false;
+        if (wr) {
+            if (prev_ids) ch = prev_ids[dst[q]] != id;
+            ids[dst[q]] = id;
+            means[dst[q]] = mean[q];
+            if (dist) dist[dst[q]] = d2;
+        }
+        nchanged += (u64)__popcll(__ballot(ch));
+    }
+    if (changed && lane == 0 && nchanged) atomicAdd(changed, nchanged);
+}
+
+// =====================================================================================================
+// update: one thread per segment.  Pass one: the absolute maximum of the mean-removed samples (non-negative floats order as integers).  Pass two:
+// every sample as a fixed-point integer at the scale the maximum sets, added to its centre's int64 sum.  Pass three: the division.
+// =====================================================================================================
+template <int K>
+__global__ __launch_bounds__(TOK_THREADS) void tok_amax_kernel(TokStore st, int64_t n_seg, uint32_t *__restrict__ amax) {
+    const int64_t p = (int64_t)blockIdx.x * TOK_THREADS + threadIdx.x;
+    float m = 0.f;
+    if (p < n_seg) {
+        const TokSeg g = tok_locate(st, blockIdx.y, p);
+        float v[K];
+        tok_load<K>(st, blockIdx.y, g, v);
+#pragma unroll
+        for (int e = 0; e < K; ++e) m = fmaxf(m, fabsf(v[e]));   // (fmaxf drops a NaN sample)
+    }
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(amax, __float_as_uint(m));
+}
+
+// 2^(31 - E) with 2^(E - 1) <= A < 2^E for the maximum's bit pattern (A = 0: any scale does)
+__device__ __forceinline__ int tok_shift(uint32_t amax_bits) {
+    const int ex = (int)(amax_bits >> 23);                 // biased exponent; 0 for a denormal maximum, 255 for inf / NaN
+    return 31 - ((ex ? ex : 1) - 127 + 1);
+}
+
+template <int K>
+__global__ __launch_bounds__(TOK_THREADS) void tok_accum_kernel(TokStore st, int64_t n_seg, const int32_t *__restrict__ ids, int V,
+                                                                 const uint32_t *__restrict__ amax, u64 *__restrict__ sums, u64 *__restrict__ counts) {
+    const int64_t p = (int64_t)blockIdx.x * TOK_THREADS + threadIdx.x;
+    if (p >= n_seg) return;
+    const TokSeg g = tok_locate(st, blockIdx.y, p);
+    const int id = ids[g.dst];
+    if (id < 0 || id >= V) return;
+    float v[K];
+    tok_load<K>(st, blockIdx.y, g, v);
+    const double scale = ldexp(1.0, tok_shift(*amax));
+    atomicAdd(counts + id, (u64)1);
+#pragma unroll
+    for (int e = 0; e < K; ++e) {
+        const long long q = __double2ll_rn((double)v[e] * scale);
+        if (q) atomicAdd(sums + (int64_t)id * K + e, (u64)q);   // two's complement: the unsigned sum is the signed one
+    }
+}
+
+__global__ __launch_bounds__(TOK_THREADS) void tok_finish_kernel(const u64 *__restrict__ sums, const u64 *__restrict__ counts,
+                                                                  const uint32_t *__restrict__ amax, int V, int K, float *__restrict__ centers,
+                                                                  int64_t *__restrict__ lens) {
+    const int t = blockIdx.x * TOK_THREADS + threadIdx.x;
+    if (t >= V * K) return;
+    const int jrow = t / K;
+    const u64 n = counts[jrow];
+    if (t % K == 0) lens[jrow] = (int64_t)n;
+    if (n) centers[t] = (float)(ldexp((double)(long long)sums[t], -tok_shift(*amax)) / (double)n);
+}
+
+// =====================================================================================================
+// decode: one thread per segment, written back in the store's layout and cut at the run's length
+// =====================================================================================================
+template <int K>
+__global__ __launch_bounds__(TOK_THREADS) void tok_decode_kernel(TokStore st, float *__restrict__ out, int64_t n_seg, const int32_t *__restrict__ ids,
+                                                                  const float *__restrict__ means, const float *__restrict__ centers, int V) {
+    const int64_t p = (int64_t)blockIdx.x * TOK_THREADS + threadIdx.x;
+    if (p >= n_seg) return;
+    const int c = blockIdx.y;
+    const TokSeg g = tok_locate(st, c, p);
+    const int id = ids[g.dst];
+    const bool ok = id >= 0 && id < V;
+    const float m = means[g.dst];
+    float *__restrict__ o = out + st.src_off[g.r] + (int64_t)c * st.lead_stride;
+#pragma unroll
+    for (int e = 0; e < K; ++e) {
+        const int64_t i = g.s * K + e;
+        if (i < g.len) o[i] = ok ? centers[(int64_t)id * K + e] + m : __builtin_nanf("");
+    }
+}
+
+// =====================================================================================================
+// entry points
+// =====================================================================================================
+static inline bool tok_al(const void *p, unsigned a) { return p && (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
+
+static bool tok_store_ok(const float *x, const int64_t *src_off, const int32_t *raw_len, const int64_t *seg_cum, const int64_t *dst_off, int R, int C,
+                         int64_t n_seg, int k, int pad) {
+    return tok_al(x, 4) && tok_al(src_off, 8) && tok_al(raw_len, 4) && tok_al(seg_cum, 8) && tok_al(dst_off, 8) && R >= 1 && C >= 1 && C <= 65535 &&
+           n_seg >= (int64_t)R && (k == 8 || k == 16 || k == 32) && (pad == 0 || pad == 1);
+}
+static inline bool tok_table_ok(int V) { return V >= 1 && V <= 65536; }
+
+static inline TokStore tok_store(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
+                                 const int64_t *dst_off, int64_t dst_stride, int R, int pad) {
+    TokStore st;
+    st.x = x; st.src_off = src_off; st.lead_stride = lead_stride; st.raw_len = raw_len; st.seg_cum = seg_cum; st.dst_off = dst_off;
+    st.dst_stride = dst_stride; st.R = R; st.pad = pad;
+    return st;
+}
+
+#define TOK_BY_K(k, launch)                      \
+    do {                                         \
+        if ((k) == 8) { launch(8); }             \
+        else if ((k) == 16) { launch(16); }      \
+        else { launch(32); }                     \
+    } while (0)
+
+int ecgvit_tok_assign(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
+                      const int64_t *dst_off, int64_t dst_stride, int R, int C, int64_t n_seg, int k, int pad, const float *centers, int V,
+                      const int32_t *prev_ids, int32_t *ids, float *means, float *dist, uint64_t *changed, void *stream) {
+    if (!tok_store_ok(x, src_off, raw_len, seg_cum, dst_off, R, C, n_seg, k, pad) || !tok_table_ok(V) || !tok_al(centers, 4) || !tok_al(ids, 4) ||
+        !tok_al(means, 4) || (dist && !tok_al(dist, 4)) || (prev_ids && !tok_al(prev_ids, 4)) || (changed && !tok_al(changed, 8)) ||
+        (prev_ids == nullptr) != (changed == nullptr))
+        return ECGVIT_EINVAL;
+    const int64_t blocks = (n_seg + TOK_SPAN - 1) / TOK_SPAN;
+    if (blocks > 0x7FFFFFFFll) return ECGVIT_EINVAL;
+    if (changed && hipMemsetAsync(changed, 0, sizeof(uint64_t), as_stream(stream)) != hipSuccess) return ECGVIT_ELAUNCH;
+    const TokStore st = tok_store(x, src_off, lead_stride, raw_len, seg_cum, dst_off, dst_stride, R, pad);
+#define TOK_LAUNCH(KK)                                                                                                                       \
+    hipLaunchKernelGGL(tok_assign_kernel<KK>, dim3((unsigned)blocks, C), dim3(TOK_THREADS), 0, as_stream(stream), st, n_seg, centers, V, prev_ids, ids, \
+                       means, dist, reinterpret_cast<u64 *>(changed))
+    TOK_BY_K(k, TOK_LAUNCH);
+#undef TOK_LAUNCH
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
+}
+
+int64_t ecgvit_tok_workspace(int V, int k) {
+    if (!tok_table_ok(V) || !(k == 8 || k == 16 || k == 32)) return 0;
+    return ((int64_t)V * k + V + 2) * 8;
+}
+
+int ecgvit_tok_update(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
+                      const int64_t *dst_off, int64_t dst_stride, int R, int C, int64_t n_seg, int k, int pad, const int32_t *ids,
+                      float *centers, int V, int64_t *lens, void *workspace, int keep_amax, void *stream) {
+    if (!tok_store_ok(x, src_off, raw_len, seg_cum, dst_off, R, C, n_seg, k, pad) || !tok_table_ok(V) || !tok_al(ids, 4) || !tok_al(centers, 4) ||
+        !tok_al(lens, 8) || !tok_al(workspace, 8) || (keep_amax != 0 && keep_amax != 1))
+        return ECGVIT_EINVAL;
+    if (n_seg > 0xFFFFFFFFll / C) return ECGVIT_EINVAL;   // C * n_seg >= 2^32: past what the fixed-point sums admit
+    const int64_t blocks = (n_seg + TOK_THREADS - 1) / TOK_THREADS;
+    if (blocks > 0x7FFFFFFFll) return ECGVIT_EINVAL;
+    u64 *sums = reinterpret_cast<u64 *>(workspace), *counts = sums + (int64_t)V * k;
+    uint32_t *amax = reinterpret_cast<uint32_t *>(counts + V);
+    // the sums and the counts always; the maximum (the last 16 bytes) only when it is taken anew
+    const size_t zero_bytes = (size_t)ecgvit_tok_workspace(V, k) - (keep_amax ? 16 : 0);
+    if (hipMemsetAsync(workspace, 0, zero_bytes, as_stream(stream)) != hipSuccess) return ECGVIT_ELAUNCH;
+    const TokStore st = tok_store(x, src_off, lead_stride, raw_len, seg_cum, dst_off, dst_stride, R, pad);
+    if (!keep_amax) {   // the maximum depends on the store alone, not on ids: one sweep serves every update of a fit
+#define TOK_LAUNCH(KK) hipLaunchKernelGGL(tok_amax_kernel<KK>, dim3((unsigned)blocks, C), dim3(TOK_THREADS), 0, as_stream(stream), st, n_seg, amax)
+        TOK_BY_K(k, TOK_LAUNCH);
+#undef TOK_LAUNCH
+        ECGVIT_CHECK_LAUNCH();
+    }
+#define TOK_LAUNCH(KK) \
+    hipLaunchKernelGGL(tok_accum_kernel<KK>, dim3((unsigned)blocks, C), dim3(TOK_THREADS), 0, as_stream(stream), st, n_seg, ids, V, amax, sums, counts)
+    TOK_BY_K(k, TOK_LAUNCH);
+#undef TOK_LAUNCH
+    ECGVIT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(tok_finish_kernel, dim3((V * k + TOK_THREADS - 1) / TOK_THREADS), dim3(TOK_THREADS), 0, as_stream(stream), sums, counts, amax, V, k,
+                       centers, lens);
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
+}
+
+int ecgvit_tok_decode(float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
+                      const int64_t *dst_off, int64_t dst_stride, int R, int C, int64_t n_seg, int k, const int32_t *ids, const float *means,
+                      const float *centers, int V, void *stream) {
+    if (!tok_store_ok(out, src_off, raw_len, seg_cum, dst_off, R, C, n_seg, k, 0) || !tok_table_ok(V) || !tok_al(ids, 4) || !tok_al(means, 4) ||
+        !tok_al(centers, 4))
+        return ECGVIT_EINVAL;
+    const int64_t blocks = (n_seg + TOK_THREADS - 1) / TOK_THREADS;
+    if (blocks > 0x7FFFFFFFll) return ECGVIT_EINVAL;
+    const TokStore st = tok_store(out, src_off, lead_stride, raw_len, seg_cum, dst_off, dst_stride, R, 0);
+#define TOK_LAUNCH(KK) \
+    hipLaunchKernelGGL(tok_decode_kernel<KK>, dim3((unsigned)blocks, C), dim3(TOK_THREADS), 0, as_stream(stream), st, out, n_seg, ids, means, centers, V)
+    TOK_BY_K(k, TOK_LAUNCH);
+#undef TOK_LAUNCH
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
+}

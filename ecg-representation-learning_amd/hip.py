@@ -128,6 +128,10 @@ SIGNATURES = {
     'ecgvit_fit_moments': (c_int, [_P, _P, _L, _P, _I, _I, _P, _P, _P, _P]),
     'ecgvit_fit_histogram': (c_int, [_P, _P, _L, _P, _I, _I, _P, _I, _I, _P, _P]),
     'ecgvit_fit_select': (c_int, [_P, _P, _I, _I, _I, _P]),
+    'ecgvit_tok_assign': (c_int, [_P, _P, _L, _P, _P, _P, _L, _I, _I, _L, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
+    'ecgvit_tok_workspace': (c_int64, [_I, _I]),
+    'ecgvit_tok_update': (c_int, [_P, _P, _L, _P, _P, _P, _L, _I, _I, _L, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
+    'ecgvit_tok_decode': (c_int, [_P, _P, _L, _P, _P, _P, _L, _I, _I, _L, _I, _P, _P, _P, _I, _P]),
 }
 
 _lib = None

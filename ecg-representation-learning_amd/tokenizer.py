@@ -1,0 +1,324 @@
+"""
+The reference's segment tokenizer (`ecg_transformer/models/ecg_tokenizer.py`: `EcgPadder` :88-137, `EcgTokenizer` :140-626) on the device:
+every lead is cut into k-sample segments, each segment loses its mean, the segments are clustered by k-means and a record is encoded as
+(token id, segment mean) per segment.  The three sweeps over the data -- nearest centre, the Lloyd update, the decode -- are HIP kernels
+(`csrc/tokenize.hip`) that read a resident record store in place; the host side here builds address tables, runs the Lloyd loop and keeps the
+vocabulary.  There is no CPU fallback: host tensors raise.
+
+Not built: `save` / pickling, the plots, the four non-k-means clusterings and k-means++ seeding (DESIGN.md says why).
+"""
+import numpy as np
+import torch
+
+from .transform import _record_tables
+
+SEGMENT_SIZES = (8, 16, 32)
+PADS = {'zero': 0, 'shift': 1}
+MAX_CLUSTERS = 65536
+D_CLS_TH = dict(hierarchical='distance_threshold', dbscan='eps', optics='max_eps', birch='threshold', kmeans='n_clusters')   # ecg_tokenizer.py:72-78
+
+
+class _Store:
+    """the device tables of one sweep: where every (record, lead) run starts, how long it is, where its segments' outputs go"""
+
+    def __init__(self, x, src_off, raw_len, lead_stride, C, ragged, k, pad):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            raise ValueError('the tokenizer runs on the device: pass a float32 device tensor (no CPU fallback exists)')
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError(f'signals must be a contiguous float32 tensor, got {x.dtype}, contiguous={x.is_contiguous()}')
+        raw_len = np.asarray(raw_len, np.int64)
+        nseg = raw_len // k + 1                       # a whole extra segment when k divides the length (EcgPadder never takes its n_pad == 0 branch)
+        self.seg_cum = np.concatenate([[0], np.cumsum(nseg)]).astype(np.int64)
+        self.x, self.k, self.pad, self.C, self.R, self.ragged = x, k, PADS[pad], int(C), len(raw_len), ragged
+        self.n_seg = int(self.seg_cum[-1])
+        self.lead_stride = int(lead_stride)
+        if ragged:
+            dst_off, self.dst_stride, self.out_shape = self.seg_cum[:-1], self.n_seg, (self.C, self.n_seg)
+        else:
+            T = int(nseg[0])
+            dst_off, self.dst_stride, self.out_shape = np.arange(self.R, dtype=np.int64) * (self.C * T), T, (self.R, self.C, T)
+        dev = x.device
+        self.src_off_h, self.raw_len_h = np.asarray(src_off, np.int64), raw_len
+        self.src_off = torch.from_numpy(self.src_off_h.copy()).to(dev)
+        self.raw_len_d = torch.from_numpy(raw_len.astype(np.int32)).to(dev)
+        self.seg_cum_d = torch.from_numpy(self.seg_cum).to(dev)
+        self.dst_off = torch.from_numpy(np.ascontiguousarray(dst_off, np.int64)).to(dev)
+
+    def args(self, x=None):
+        from .hip import ptr
+        return (ptr(self.x if x is None else x), ptr(self.src_off), self.lead_stride, ptr(self.raw_len_d), ptr(self.seg_cum_d), ptr(self.dst_off),
+                self.dst_stride, self.R, self.C, self.n_seg, self.k)
+
+    def new(self, dtype):
+        return torch.empty(self.out_shape, dtype=dtype, device=self.x.device)
+
+
+def check_lengths(lengths, k, pad):
+    """the one place run lengths are held to the padder's rule: 'shift' copies the n_pad = k - l % k samples before the end, so needs l >= n_pad"""
+    lengths = np.asarray(lengths, np.int64)
+    if lengths.size == 0 or int(lengths.min()) < 1:
+        raise ValueError('every record needs at least one sample')
+    if pad == 'shift':
+        bad = lengths < k - lengths % k
+        if bad.any():
+            l = int(lengths[bad][0])
+            raise ValueError(f"pad='shift' copies the last n_pad = k - l % k samples: l = {l} is shorter than n_pad = {k - l % k} (use pad='zero')")
+    return lengths
+
+
+class EcgTokenizer:
+    """`EcgTokenizer(k=8, pad='shift')`: `centers` (V, k) f32 and `lens` (V,) int64 numpy arrays, `fit_method`, `n_sig`, `cls_th` as the
+    reference sets them.  Signals are float32 device tensors: (…, C, L), or a ragged (12, S_total) store with `offsets`."""
+
+    def __init__(self, k=2 ** 3, pad='shift'):
+        if k not in SEGMENT_SIZES:
+            raise ValueError(f'k = {k}: the kernels are built for k in {SEGMENT_SIZES}')
+        if pad not in PADS:
+            raise ValueError(f"pad = {pad!r}: one of 'zero', 'shift'")
+        self.k, self.pad = k, pad
+        self._tables = {}     # (device, th) -> the device copy of the (cut) table
+        self._cut = {}        # th -> host rows kept (the reference's CustNN.data)
+        self.centers = self.lens = None
+        self.fit_method = self.n_sig = self.cls_th = None
+        self.n_iter_ = self.inertia_ = self.changed_ = None     # of the last fit: assign passes run, sum of dist, ids changed per pass
+
+    # the vocabulary: assigning either array drops every table derived from the old one (device copies, th cuts)
+    @property
+    def centers(self):
+        return self._centers
+
+    @centers.setter
+    def centers(self, v):
+        self._centers = v
+        self._tables.clear()
+        self._cut.clear()
+
+    @property
+    def lens(self):
+        return self._lens
+
+    @lens.setter
+    def lens(self, v):
+        self._lens = v
+        self._tables.clear()
+        self._cut.clear()
+
+    def __repr__(self):
+        return f'<{self.__class__.__qualname__} k={self.k} pad={self.pad}>'
+
+    def n_segments(self, l):
+        """segments of a run of l samples: l // k + 1 (16 samples at k = 8 pad to 24)"""
+        return int(l) // self.k + 1
+
+    @classmethod
+    def from_centers(cls, centers, lens, pad='shift'):
+        """a vocabulary fitted elsewhere: centers (V, k), lens (V,) cluster sizes"""
+        centers = np.ascontiguousarray(centers.detach().cpu().numpy() if isinstance(centers, torch.Tensor) else centers, dtype=np.float32)
+        lens = np.asarray(lens.detach().cpu().numpy() if isinstance(lens, torch.Tensor) else lens).astype(np.int64)
+        if centers.ndim != 2 or lens.shape != (centers.shape[0],):
+            raise ValueError(f'centers must be (V, k) and lens (V,), got {centers.shape} and {lens.shape}')
+        if not 1 <= centers.shape[0] <= MAX_CLUSTERS:
+            raise ValueError(f'{centers.shape[0]} centres: 1 to {MAX_CLUSTERS} are supported')
+        tok = cls(k=centers.shape[1], pad=pad)
+        tok.centers, tok.lens = centers, lens
+        return tok
+
+    # ---- the table ----------------------------------------------------------------------------------
+    def _rows(self, th):
+        """host rows of the table under threshold `th`: the reference's CustNN (:193-220).  An int is an absolute lower bound on the cluster
+        size.  For a float in (0, 1) the reference computes round(lens.sum() * th) but then compares `lens >= th` against the RAW fraction,
+        which keeps every non-empty cluster: that quirk is kept."""
+        if self.centers is None:
+            raise RuntimeError('the tokenizer has no vocabulary: call fit() or from_centers()')
+        if th is None:
+            return self.centers
+        if th not in self._cut:
+            if not isinstance(th, (int, np.integer)) and not (isinstance(th, float) and 0 < th < 1):
+                raise ValueError(f'th = {th!r}: an int, or a float in (0, 1)')
+            rows = np.ascontiguousarray(self.centers[self.lens >= th])
+            if len(rows) == 0:
+                raise ValueError(f'th = {th} removes every centre')
+            self._cut[th] = rows
+        return self._cut[th]
+
+    def _table(self, device, th):
+        key = (str(device), th)
+        if key not in self._tables:
+            self._tables[key] = torch.from_numpy(self._rows(th)).to(device)
+        return self._tables[key]
+
+    # ---- stores -------------------------------------------------------------------------------------
+    def _dense_store(self, sig):
+        """(…, L): every row is a run of its own (one lead per 'record'), so any number of leading dimensions serves"""
+        if not isinstance(sig, torch.Tensor) or sig.dim() < 1:
+            raise ValueError('signals must be a float32 device tensor of shape (…, C, L)')
+        L = int(sig.shape[-1])
+        check_lengths([L], self.k, self.pad)
+        rows = int(np.prod(sig.shape[:-1], dtype=np.int64))
+        if rows < 1:
+            raise ValueError('no signal given')
+        return _Store(sig, np.arange(rows, dtype=np.int64) * L, np.full(rows, L, np.int64), L, 1, False, self.k, self.pad)
+
+    def _record_store(self, sigs, offsets, idxs):
+        """(n, 12, L) records or a ragged (12, S_total) store with offsets, and a subset of either: `fit_dynamic_normalize`'s convention and validator"""
+        if not isinstance(sigs, torch.Tensor):
+            raise ValueError('signals must be a float32 device tensor (no CPU fallback exists)')
+        rect, n, C, src_off, raw_len, stride, sel = _record_tables(sigs, offsets, idxs)
+        check_lengths(raw_len, self.k, self.pad)
+        return _Store(sigs, src_off, raw_len, stride, C, not rect, self.k, self.pad)
+
+    # ---- kernels ------------------------------------------------------------------------------------
+    def _assign(self, st, table, ids, means, dist=None, prev_ids=None, changed=None):
+        from .hip import lib, check, ptr, stream
+        check(lib().ecgvit_tok_assign(*st.args(), st.pad, ptr(table), table.shape[0], ptr(prev_ids), ptr(ids), ptr(means), ptr(dist), ptr(changed),
+                                      stream()), 'ecgvit_tok_assign')
+
+    def _update(self, st, ids, table, lens, ws, keep_amax=False):
+        """keep_amax: `ws` was last used by an update over this very store, whose absolute maximum it still holds: that sweep is skipped"""
+        from .hip import lib, check, ptr, stream
+        check(lib().ecgvit_tok_update(*st.args(), st.pad, ptr(ids), ptr(table), table.shape[0], ptr(lens), ptr(ws), int(keep_amax), stream()),
+              'ecgvit_tok_update')
+
+    # ---- encode / decode ----------------------------------------------------------------------------
+    def __call__(self, sig, th=None, offsets=None):
+        """-> (ids, means): for (…, C, L) input both of shape (…, C, L // k + 1); for a ragged (12, S_total) store with `offsets` both (12, T_total)
+        and, third, `seg_offsets` ((n + 1,) int64: record r's segments are columns seg_offsets[r] : seg_offsets[r + 1]).  ids are int32 and means
+        float32 (the reference returns int64 / float64).  The caller's signal is NOT modified (the reference's `segs -= means` writes through a
+        view of it).  th: the reference's size threshold (`_rows`); ids then index the cut table, as `decode(ids, th)` reads them."""
+        if offsets is None:
+            st = self._dense_store(sig)
+            shape = tuple(sig.shape[:-1]) + (st.out_shape[-1],)
+        else:
+            st = self._record_store(sig, offsets, None)
+            shape = st.out_shape
+        with torch.cuda.device(sig.device):
+            table = self._table(sig.device, th)
+            ids, means = st.new(torch.int32), st.new(torch.float32)
+            self._assign(st, table, ids, means)
+        if offsets is None:
+            return ids.view(shape), means.view(shape)
+        return ids, means, torch.from_numpy(st.seg_cum.copy())
+
+    def decode(self, ids, th=None):
+        """centers[ids] (…, k): the reference's decode (:346-350); with `th`, rows of the cut table"""
+        if isinstance(ids, torch.Tensor):
+            if ids.is_cuda:
+                return self._table(ids.device, th)[ids.long()]
+            ids = ids.numpy()
+        return self._rows(th)[ids]
+
+    def reconstruct(self, ids, means, lengths, th=None):
+        """centers[ids] + means, cut to each run's length: what the reference plots beside the signal (:292).  lengths: an int L for
+        (…, C, T) ids -> (…, C, L); a (n,) array of record lengths for the (12, T_total) ids of a ragged store -> (12, S_total)."""
+        if not (isinstance(ids, torch.Tensor) and ids.is_cuda and isinstance(means, torch.Tensor) and means.is_cuda):
+            raise ValueError('ids and means must be device tensors (no CPU fallback exists)')
+        if ids.dtype != torch.int32 or means.dtype != torch.float32 or ids.shape != means.shape:
+            raise ValueError('ids (int32) and means (float32) must have one shape, as __call__ returns them')
+        ids, means = ids.contiguous(), means.contiguous()
+        dev = ids.device
+        if np.ndim(lengths) == 0:
+            L = int(lengths)
+            if ids.dim() < 1 or ids.shape[-1] != self.n_segments(L):
+                raise ValueError(f'{ids.shape[-1] if ids.dim() else 0} segments per run do not belong to runs of {L} samples at k = {self.k}')
+            out = torch.empty(tuple(ids.shape[:-1]) + (L,), dtype=torch.float32, device=dev)
+            st = self._dense_store(out)
+        else:
+            lengths = check_lengths(lengths, self.k, 'zero')
+            off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+            if ids.dim() != 2 or ids.shape[1] != int((lengths // self.k + 1).sum()):
+                raise ValueError('ids must be (12, T_total) with T_total the segments of the given lengths')
+            out = torch.empty((ids.shape[0], int(off[-1])), dtype=torch.float32, device=dev)
+            st = self._record_store(out, off, None)
+        from .hip import lib, check, ptr, stream
+        with torch.cuda.device(dev):
+            table = self._table(dev, th)
+            check(lib().ecgvit_tok_decode(*st.args(), ptr(ids), ptr(means), ptr(table), table.shape[0], stream()), 'ecgvit_tok_decode')
+        return out
+
+    # ---- fit ----------------------------------------------------------------------------------------
+    def _random_init(self, st, V, rng):
+        """V distinct segments of the store, mean removed, drawn by a seeded host generator"""
+        total = st.C * st.n_seg
+        if V > total:
+            raise ValueError(f'n_clusters = {V} exceeds the {total} segments of the store')
+        pick = rng.choice(total, size=V, replace=False)
+        c, p = pick // st.n_seg, pick % st.n_seg
+        r = np.searchsorted(st.seg_cum, p, side='right') - 1
+        l = st.raw_len_h[r][:, None]
+        i = ((p - st.seg_cum[r]) * self.k)[:, None] + np.arange(self.k)[None, :]
+        n_pad = self.k - l % self.k
+        keep = (i < l) | (st.pad == 1)
+        i = np.where(i < l, i, np.clip(i - n_pad, 0, l - 1))
+        flat = st.src_off_h[r][:, None] + c[:, None] * st.lead_stride + i
+        dev = st.x.device
+        seg = st.x.reshape(-1)[torch.from_numpy(flat).to(dev)]
+        seg = torch.where(torch.from_numpy(keep).to(dev), seg, torch.zeros_like(seg))      # (a select: a NaN at the clamped index stays out)
+        return (seg - seg.mean(dim=1, keepdim=True)).contiguous()
+
+    def _lloyd(self, st, table, max_iter, ws, ws_state):
+        """-> (centres, lens, inertia, ids changed per assign).  Every assign also writes `dist`, so no pass is spent on the inertia.  A run that
+        converges ends on an assign that changed nothing: ids, dist, centres and lens all belong together.  A run that ends at max_iter ends on
+        an update: centres and lens are the means and the counts of the last assign's labels -- how the reference builds them from `labels_`
+        (:489-490) -- and the inertia is that assign's, taken under the centres before the last update (an upper bound of the final one)."""
+        dev = st.x.device
+        ids, means, dist = st.new(torch.int32).fill_(-1), st.new(torch.float32), st.new(torch.float32)
+        changed = torch.zeros(1, dtype=torch.int64, device=dev)
+        lens = torch.zeros(table.shape[0], dtype=torch.int64, device=dev)
+        history = []
+        for _ in range(max_iter):
+            self._assign(st, table, ids, means, dist=dist, prev_ids=ids, changed=changed)
+            history.append(int(changed.item()))     # the iteration's one sync: 8 bytes
+            if history[-1] == 0:
+                break                               # the centres already are the means of these ids
+            self._update(st, ids, table, lens, ws, keep_amax=ws_state['amax'])     # the store's absolute maximum is swept once per fit
+            ws_state['amax'] = True
+        return table, lens, float(dist.sum(dtype=torch.float64)), history
+
+    def fit(self, sigs, method='kmeans', cls_kwargs=None, offsets=None, idxs=None):
+        """k-means over the mean-removed segments of `sigs`: (n, 12, L) float32 device records, or a ragged (12, S_total) store with `offsets`;
+        `idxs` selects records without a copy (the calling convention of `fit_dynamic_normalize`).
+        cls_kwargs: n_clusters (required), max_iter=256, n_init=1, random_state=None, init='random' (n_clusters distinct segments drawn by a
+        seeded host generator) or a (n_clusters, k) array (Lloyd from a given start is deterministic).  Lloyd iterations are assign then update;
+        they stop when an iteration changes no id, or at max_iter; n_init > 1 keeps the run of lowest inertia.  A centre that loses every
+        segment keeps its value with size 0.  Label order is the clustering's own, as in the reference; nothing is reordered."""
+        if method != 'kmeans':
+            if method in D_CLS_TH:
+                raise NotImplementedError(f"method = {method!r}: only 'kmeans' runs on the device (the hierarchical and density methods are not data-parallel in this form)")
+            raise ValueError(f'method = {method!r}: one of {sorted(D_CLS_TH)}')
+        kw = dict(max_iter=256, n_init=1, random_state=None, init='random')
+        kw.update(cls_kwargs or {})
+        unknown = set(kw) - {'n_clusters', 'max_iter', 'n_init', 'random_state', 'init'}
+        if unknown:
+            raise ValueError(f'cls_kwargs {sorted(unknown)} are not supported: n_clusters, max_iter, n_init, random_state, init')
+        if 'n_clusters' not in kw:
+            raise ValueError("cls_kwargs needs 'n_clusters'")
+        V, max_iter, n_init, init = int(kw['n_clusters']), int(kw['max_iter']), int(kw['n_init']), kw['init']
+        if not 1 <= V <= MAX_CLUSTERS:
+            raise ValueError(f'n_clusters = {V}: 1 to {MAX_CLUSTERS} are supported')
+        if max_iter < 1 or n_init < 1:
+            raise ValueError('max_iter and n_init must be at least 1')
+        fixed = None
+        if isinstance(init, str):
+            if init != 'random':
+                raise NotImplementedError(f"init = {init!r}: 'random' or a (n_clusters, k) array are supported (exact k-means++ seeding is n_clusters dependent passes over the store)")
+        else:
+            fixed = np.ascontiguousarray(init.detach().cpu().numpy() if isinstance(init, torch.Tensor) else init, dtype=np.float32)
+            if fixed.shape != (V, self.k):
+                raise ValueError(f'init must be ({V}, {self.k}), got {fixed.shape}')
+        st = self._record_store(sigs, offsets, idxs)
+        rng = np.random.default_rng(kw['random_state'])
+        best = None
+        with torch.cuda.device(sigs.device):
+            from .hip import lib
+            ws = torch.empty(lib().ecgvit_tok_workspace(V, self.k) // 8, dtype=torch.int64, device=sigs.device)
+            ws_state = dict(amax=False)
+            for _ in range(1 if fixed is not None else n_init):
+                table = torch.from_numpy(fixed.copy()).to(sigs.device) if fixed is not None else self._random_init(st, V, rng)
+                run = self._lloyd(st, table, max_iter, ws, ws_state)
+                if best is None or run[2] < best[2]:
+                    best = run
+        table, lens, inertia, history = best
+        self.fit_method, self.n_sig, self.cls_th = method, st.R, kw[D_CLS_TH[method]]
+        self.n_iter_, self.inertia_, self.changed_ = len(history), inertia, history
+        self.centers, self.lens = table.cpu().numpy(), lens.cpu().numpy()
+        return self

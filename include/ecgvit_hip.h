@@ -508,6 +508,47 @@ int ecgvit_fit_histogram(const float *x, const int64_t *src_off, int64_t lead_st
                          int ntarget, int pass, uint64_t *hist, void *stream);
 int ecgvit_fit_select(const uint64_t *hist, uint64_t *sel, int C, int ntarget, int pass, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * segment tokenizer (tokenizer.EcgTokenizer; the reference's symbolisation branch, models/ecg_tokenizer.py: EcgPadder :88-137, encode :222-258,
+ * decode :346-350, the k-means fit :352-490 through sklearn).  Additive entry points: the ABI version stays 6.
+ * The store is addressed as ecgvit_fit_moments addresses it (x, src_off, lead_stride, raw_len; a record starts at any 4-byte address).  Lead c of
+ * record r is cut into raw_len[r] / k + 1 segments of k samples (k in {8, 16, 32}), padded INSIDE the segment load as EcgPadder pads:
+ * n_pad = k - raw_len % k samples (a whole extra segment when k divides the length), pad == 0: zeros, pad == 1 ('shift'): position l + j holds
+ * sample l - n_pad + j (the caller guarantees l >= n_pad; the kernels clamp the index to the run, so nothing outside a run is ever read).
+ * The segments of one lead over the R records, in record order, are positions 0 .. n_seg - 1: seg_cum (int64 [R + 1], device, seg_cum[0] = 0,
+ * seg_cum[r + 1] - seg_cum[r] = raw_len[r] / k + 1, seg_cum[R] = n_seg) maps a position to its record.  Segment s of (r, c) has its id, mean and
+ * distance at element dst_off[r] + c * dst_stride + s of ids / means / dist (dst_off int64 [R], device): (n, C, T) outputs of a rectangle and
+ * the (C, T_total) outputs of a ragged store are tables again.
+ * Per segment: mean = (((x0 + x1) + x2) + ... ) * (1 / k) in f32, in that order whatever the layout or the batch; the segment minus its mean
+ * is what is clustered.
+ * ------------------------------------------------------------------------------------------------ */
+/* ids[.] = argmin_j |s - c_j|^2 over the V rows of centers (f32 [V][k], 1 <= V <= 65536), means[.] = the segment's mean, dist[.] (may be NULL)
+ * = sum_e (s_e - c_e)^2 for the chosen centre, recomputed directly.  The argmin is taken on score_j = |c_j|^2 - 2 s . c_j, an f32 fma chain
+ * in sample order on the matrix pipe (v_mfma_f32_32x32x2_f32, exact f32) that starts from |c_j|^2; equal scores go to the smaller index.
+ * prev_ids != NULL (may be ids itself): *changed (uint64, device; zeroed by this call) receives the number of segments whose id differs from
+ * prev_ids; prev_ids and changed come together or not at all.  Integer atomics only. */
+int ecgvit_tok_assign(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
+                      const int64_t *dst_off, int64_t dst_stride, int R, int C, int64_t n_seg, int k, int pad, const float *centers, int V,
+                      const int32_t *prev_ids, int32_t *ids, float *means, float *dist, uint64_t *changed, void *stream);
+/* bytes of `workspace` ecgvit_tok_update needs (int64 sums [V][k], uint64 counts [V], the absolute maximum); 0 for an unsupported (V, k) */
+int64_t ecgvit_tok_workspace(int V, int k);
+/* One Lloyd update: centers[j] = the mean of the mean-removed segments with ids[.] == j, lens[j] (int64 [V]) = their number; a centre that
+ * receives no segment keeps its value and reports 0; ids outside [0, V) are left out.  Three launches after zeroing the workspace: the absolute
+ * maximum A of the mean-removed samples (keep_amax == 1: that sweep is skipped and the maximum the previous call left in this workspace is used
+ * again -- it depends on the store and the padding alone, not on ids, so one sweep serves every update of a fit over one store; 0 or 1) (integer atomic max on the bits); per sample q = rint(v * 2^(31 - E)) with 2^(E - 1) <= A < 2^E, added
+ * to its centre's int64 sum by 64-bit integer atomics (addition of integers has no order: the same launches give the same bits); the division
+ * in f64.  |q| <= 2^31, so a sum holds 2^32 - 1 segments without overflow: C * n_seg >= 2^32 is refused with ECGVIT_EINVAL.  The rounding
+ * of q is at most A * 2^-31 per sample, and so per centre element (an absolute error: a centre element near zero has no relative bound; the
+ * tests hold max_e |c32 - c64| to 1e-6 max_e |c64| per centre). */
+int ecgvit_tok_update(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
+                      const int64_t *dst_off, int64_t dst_stride, int R, int C, int64_t n_seg, int k, int pad, const int32_t *ids,
+                      float *centers, int V, int64_t *lens, void *workspace, int keep_amax, void *stream);
+/* out (the store's own layout: lead c of record r at out + src_off[r] + c * lead_stride) = centers[ids] + means, truncated to raw_len[r]
+ * samples: the reference's decode plus the mean it adds back (:292).  A segment whose id lies outside [0, V) is written as NaN. */
+int ecgvit_tok_decode(float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
+                      const int64_t *dst_off, int64_t dst_stride, int R, int C, int64_t n_seg, int k, const int32_t *ids, const float *means,
+                      const float *centers, int V, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

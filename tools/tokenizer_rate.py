@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""The segment tokenizer's kernels (csrc/tokenize.hip) at corpus size, one GPU process:
+  (a) assign, update and one full Lloyd iteration (assign with the changed counter, its 8-byte read, update) on a resident
+      21 837 x 12 x 5 000 f32 store, at k = 8, V = 4 096 and at k = 16, V = 1 024: ms per launch, segments/s, and for assign the rate of the
+      score product alone (2 k FLOP per score) beside the board's f32 matrix peak -- the expectation to check is that assign is bound by that
+      rate, not by the running argmin;
+  (b) in the same process, a chunked `torch.cdist(...).argmin` on the same device over the same store and the same table: every whole
+      segment of every run (the padded last one of each run is left out, the time is scaled by the segment count; the mean is removed by
+      torch beforehand and not timed), and the share of those segments on which it agrees with assign's ids;
+  (c) sklearn's `KDTree.query` on the host over a 1 % sample of the segments, scaled by 100 (stated in the row; skipped when sklearn is absent).
+Writes profiles/r19_tokenizer.txt (--out).
+usage: python tools/tokenizer_rate.py [--reps 3] [--records 21837]"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import ecg_representation_learning_amd as E  # noqa: E402
+from ecg_representation_learning_amd.hip import lib  # noqa: E402
+
+C, L = 12, 5000
+F32_MATRIX_PEAK = 157.3e12      # FLOP/s, v_mfma_f32_32x32x2_f32 at the board's spec clock
+
+
+def timed(fn, reps, warmup=1):
+    """ms per call"""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(reps):
+        fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--records', type=int, default=21837)
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r19_tokenizer.txt'))
+    a = ap.parse_args()
+    import bench
+    n = a.records
+    g = torch.Generator(device='cuda').manual_seed(19)
+    x = torch.randn((n, C, L), device='cuda', generator=g).mul_(0.7).add_(0.3)
+    lines = [f'sources: bench.kernel_source_hash() = {bench.kernel_source_hash()}; {torch.cuda.get_device_name(0)}',
+             f'store: {n} x {C} x {L} f32 = {x.numel() * 4 / 1e9:.2f} GB, N(0.3, 0.7^2); {a.reps} launches after one warm-up']
+    for k, V in ((8, 4096), (16, 1024)):
+        tok = E.EcgTokenizer(k=k, pad='shift')
+        st = tok._record_store(x, None, None)
+        nseg = st.C * st.n_seg
+        table = tok._random_init(st, V, np.random.default_rng(19))
+        ids, means, dist = st.new(torch.int32), st.new(torch.float32), st.new(torch.float32)
+        changed = torch.zeros(1, dtype=torch.int64, device='cuda')
+        lens = torch.zeros(V, dtype=torch.int64, device='cuda')
+        ws = torch.empty(lib().ecgvit_tok_workspace(V, k) // 8, dtype=torch.int64, device='cuda')
+        work = table.clone()
+        t_assign = timed(lambda: tok._assign(st, table, ids, means), a.reps)
+        # (b) torch on the same device, same store, same table -- compared before anything below overwrites ids
+        T = st.dst_stride
+        segs = x[..., :(T - 1) * k].reshape(-1, k)
+        segs = (segs - segs.mean(dim=1, keepdim=True)).contiguous()
+        chunk = 65536
+        out = torch.empty(len(segs), dtype=torch.int64, device='cuda')
+
+        def by_torch():
+            for i in range(0, len(segs), chunk):
+                out[i:i + chunk] = torch.cdist(segs[i:i + chunk], table).argmin(dim=1)
+        t_torch = timed(by_torch, 1, warmup=0) * nseg / len(segs)
+        agree = float((out.view(n, C, T - 1) == ids[..., :T - 1]).float().mean())
+        t_update = timed(lambda: tok._update(st, ids, work, lens, ws), a.reps)
+        t_update_kept = timed(lambda: tok._update(st, ids, work, lens, ws, keep_amax=True), a.reps)
+
+        def lloyd():
+            tok._assign(st, work, ids, means, dist=dist, prev_ids=ids, changed=changed)
+            changed.item()
+            tok._update(st, ids, work, lens, ws, keep_amax=True)
+        t_lloyd = timed(lloyd, a.reps)
+        flops = 2.0 * k * V * nseg
+        lines.append(f'(a) k = {k}, V = {V}: {nseg} segments')
+        lines.append(f'    assign                   {t_assign:10.2f} ms  {nseg / t_assign / 1e3:9.1f} M segments/s  score product {flops / t_assign / 1e9:7.1f} TFLOP/s '
+                     f'= {flops / (t_assign * 1e-3) / F32_MATRIX_PEAK:.2f} of the f32 matrix peak')
+        lines.append(f'    update                   {t_update:10.2f} ms  {nseg / t_update / 1e3:9.1f} M segments/s  ({2 * x.numel() * 4 / 1e9 / (t_update * 1e-3):7.0f} GB/s over its two sweeps)')
+        lines.append(f'    update, maximum kept     {t_update_kept:10.2f} ms  {nseg / t_update_kept / 1e3:9.1f} M segments/s  (one sweep; what every update of a fit after the first costs)')
+        lines.append(f'    Lloyd iteration          {t_lloyd:10.2f} ms  (assign with dist and the changed counter + 8-byte read + update, maximum kept)')
+        print('\n'.join(lines[-7:]), flush=True)
+        lines.append(f'(b) torch.cdist(...).argmin, chunks of {chunk} segments, {len(segs)} whole segments scaled to {nseg}: {t_torch:10.2f} ms = x {t_torch / t_assign:.1f} assign')
+        lines.append(f'    (same ids as assign against the same table on {agree:.6f} of those segments)')
+        # (c) the reference's route on the host
+        try:
+            from sklearn.neighbors import KDTree
+            host = segs[:max(1, nseg // 100)].cpu().numpy().astype(np.float64)
+            tree = KDTree(table.cpu().numpy().astype(np.float64))
+            t0 = time.perf_counter()
+            tree.query(host, k=1, return_distance=True)
+            t_kd = (time.perf_counter() - t0) * 1e3 * nseg / len(host)
+            lines.append(f'(c) sklearn KDTree.query on the host, {len(host)} segments (f64) scaled to {nseg}: {t_kd / 1e3:10.1f} s = x {t_kd / t_assign:.0f} assign')
+        except ImportError:
+            lines.append('(c) sklearn is not installed here: no host row')
+        print(lines[-1], flush=True)
+        del ids, means, dist, segs, out
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as fh:
+        fh.write(text)
+
+
+if __name__ == '__main__':
+    main()
