@@ -1,0 +1,351 @@
+"""
+The reference's Zheng et al. denoiser (`ecg_transformer/preprocess/data_preprocessor.py:22-148`, MATLAB twin `preprocess_matlab/DataPreprocessor.m`
+and `nlm.m`) on the device: zero-phase Butterworth low-pass, the noise estimate and non-local means, the stage that writes the `*-denoised.hdf5`
+files every reference run trains on.  The three sweeps are HIP kernels (`csrc/denoise.hip`) over the record stores `fit_dynamic_normalize` and
+`EcgTokenizer` take: (n, 12, L) float32 records, a ragged (12, S_total) store with `offsets`, a subset `idxs` of either.  A device store is
+processed where it lies -- in place with `out=records`, into `out=`, or (default) into a new tensor that starts as a copy, so records outside
+`idxs` carry over; a host array / memmap streams through the device `chunk_records` records at a time and comes back as a float32 numpy array.
+There is no CPU fallback.
+
+Not built: the robust LOESS baseline the reference subtracts between the low-pass and the non-local means (`rloess`, from the `loess` package):
+`EcgDenoiser.__call__(records, baseline=...)` takes that baseline from the caller instead.  Records longer than
+`MAX_LEN` = 32768 samples and NaN samples are refused / unsupported.
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from .transform import _record_tables
+
+MAX_LEN = 32768            # samples per record: the non-local means keeps a lead in LDS
+MAX_TAPS = 9
+C = 12                     # leads per record: what `_record_tables` admits
+_WS_BYTES = 256 * 2 ** 20  # f64 intermediates of the low-pass / noise estimate per launch: more records go in several launches
+
+
+# ---- filter design (scipy.signal.buttord / butter / lfilter_zi restated in numpy f64; the product imports no scipy) -----------------
+def design_lowpass(fqs=500, passband=50, stopband=60, passband_ripple=1, stopband_attenuation=2.5):
+    """-> (b, a, zi): the digital Butterworth low-pass of minimal order that loses at most `passband_ripple` dB up to `passband` Hz and at least
+    `stopband_attenuation` dB from `stopband` Hz (`signal.buttord`, `signal.butter(ord, wn, 'low')`), and its `signal.lfilter_zi`.  The defaults
+    are the reference's `util/config.py:88-100`; at 500 and 250 Hz the order is 3."""
+    nyq = 0.5 * fqs
+    wp, ws = passband / nyq, stopband / nyq
+    if not (0 < wp < ws < 1):
+        raise ValueError(f'a low-pass needs 0 < passband < stopband < fqs / 2, got {passband}, {stopband} at fqs = {fqs}')
+    if not (0 < passband_ripple < stopband_attenuation):
+        raise ValueError('a low-pass needs 0 < passband_ripple < stopband_attenuation (dB)')
+    passb, stopb = math.tan(math.pi * wp / 2.0), math.tan(math.pi * ws / 2.0)       # buttord: pre-warped band edges
+    g_stop, g_pass = 10 ** (0.1 * abs(stopband_attenuation)), 10 ** (0.1 * abs(passband_ripple))
+    order = int(math.ceil(math.log10((g_stop - 1.0) / (g_pass - 1.0)) / (2 * math.log10(stopb / passb))))
+    if not 1 <= order <= MAX_TAPS - 1:
+        raise ValueError(f'the design needs order {order}: 1 to {MAX_TAPS - 1} are supported')
+    w0 = (g_pass - 1.0) ** (-1.0 / (2.0 * order))
+    wn = (2.0 / math.pi) * math.atan(w0 * passb)
+    # butter: analogue prototype poles, low-pass to the warped frequency, bilinear transform at fs = 2
+    p = -np.exp(1j * math.pi * np.arange(-order + 1, order, 2) / (2 * order))
+    warped = 4.0 * math.tan(math.pi * wn / 2.0)
+    p = warped * p
+    k = warped ** order
+    pz = (4.0 + p) / (4.0 - p)
+    kz = k * np.real(1.0 / np.prod(4.0 - p))
+    b = kz * np.poly(-np.ones(order))
+    a = np.real(np.poly(pz))
+    b, a = np.ascontiguousarray(b, np.float64), np.ascontiguousarray(a, np.float64)
+    return b, a, lfilter_zi(b, a)
+
+
+def lfilter_zi(b, a):
+    """the initial state of the direct-form-II-transposed filter whose step response starts at its final value (`signal.lfilter_zi`)"""
+    b, a = np.atleast_1d(np.asarray(b, np.float64)), np.atleast_1d(np.asarray(a, np.float64))
+    if a[0] != 1.0:
+        b, a = b / a[0], a / a[0]
+    n = max(len(a), len(b))
+    a, b = np.r_[a, np.zeros(n - len(a))], np.r_[b, np.zeros(n - len(b))]
+    comp = np.zeros((n - 1, n - 1))
+    comp[0] = -a[1:]
+    comp[np.arange(1, n - 1), np.arange(0, n - 2)] = 1.0
+    return np.linalg.solve(np.eye(n - 1) - comp.T, b[1:] - a[1:] * b[0])
+
+
+def _taps(b, a, zi):
+    b, a = np.atleast_1d(np.asarray(b, np.float64)), np.atleast_1d(np.asarray(a, np.float64))
+    nt = max(len(a), len(b))
+    if b.ndim != 1 or a.ndim != 1 or not 2 <= nt <= MAX_TAPS:
+        raise ValueError(f'b and a must be 1-D with 2 to {MAX_TAPS} taps')
+    if a[0] != 1.0:
+        raise ValueError('a[0] must be 1 (normalise the filter)')
+    b, a = np.r_[b, np.zeros(nt - len(b))], np.r_[a, np.zeros(nt - len(a))]
+    zi = lfilter_zi(b, a) if zi is None else np.asarray(zi, np.float64)
+    if zi.shape != (nt - 1,):
+        raise ValueError(f'zi must hold {nt - 1} values')
+    if not (np.isfinite(b).all() and np.isfinite(a).all() and np.isfinite(zi).all()):
+        raise ValueError('b, a and zi must be finite')
+    return np.ascontiguousarray(b), np.ascontiguousarray(a), np.ascontiguousarray(zi), nt
+
+
+def _dp(arr):
+    return arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+# ---- stores ---------------------------------------------------------------------------------------------------------------------------
+class _Tables:
+    """the device tables of the selected records of one device store"""
+
+    def __init__(self, x, src_off, raw_len, stride):
+        self.x, self.R, self.stride = x, len(raw_len), int(stride)
+        self.src_off_h, self.raw_len_h = np.ascontiguousarray(src_off, np.int64), np.ascontiguousarray(raw_len, np.int64)
+        self.src_off = torch.from_numpy(self.src_off_h.copy()).to(x.device)
+        self.raw_len = torch.from_numpy(self.raw_len_h.astype(np.int32)).to(x.device)
+        self.min_len, self.max_len = int(self.raw_len_h.min()), int(self.raw_len_h.max())
+
+    def launches(self):
+        """(first record, records) per launch, so that the f64 workspace of a launch stays within _WS_BYTES"""
+        from .hip import lib
+        step = max(1, _WS_BYTES // lib().ecgvit_denoise_workspace(1, C, self.max_len))
+        return [(lo, min(step, self.R - lo)) for lo in range(0, self.R, step)]
+
+
+def _check_device_store(records, what='records'):
+    if records.dtype != torch.float32:
+        raise ValueError(f'{what} must be float32, got {records.dtype}')
+    if not records.is_cuda:
+        raise ValueError(f'{what} must be a device tensor or a host array (a host TENSOR is taken as a host array only as `records`)')
+    if not records.is_contiguous():
+        raise ValueError(f'{what} must be contiguous')
+
+
+def _check_lengths(raw_len, min_len=1):
+    if int(raw_len.max()) > MAX_LEN:
+        raise ValueError(f'a record of {int(raw_len.max())} samples: at most {MAX_LEN} are supported (a tiled form for longer records is not built)')
+    if int(raw_len.min()) < min_len:
+        raise ValueError(f'a record of {int(raw_len.min())} samples: this stage needs at least {min_len}')
+
+
+def _resolve_out(records, out):
+    """out=None: a new tensor that starts as a copy; out is records: in place; else a tensor of the same layout that does not overlap records"""
+    if out is None:
+        return records.clone()
+    if not isinstance(out, torch.Tensor):
+        raise ValueError('out must be a device tensor')
+    if out is records:
+        return out
+    _check_device_store(out, 'out')
+    if out.shape != records.shape or out.device != records.device:
+        raise ValueError(f'out must have the shape and device of records, got {tuple(out.shape)} on {out.device}')
+    if out.data_ptr() == records.data_ptr():
+        return out
+    lo, hi = records.data_ptr(), records.data_ptr() + records.numel() * 4
+    if out.data_ptr() < hi and lo < out.data_ptr() + out.numel() * 4:
+        raise ValueError('out overlaps records without being records: pass out=records to run in place')
+    return out
+
+
+def _host_chunks(records, rect, src_off, raw_len, sel, chunk_records, device):
+    """-> per chunk (device buffer, _Tables, scatter): the selected records, `chunk_records` at a time, as a compact device store of the same form;
+    scatter(host_out, buffer) writes the chunk's records back where they came from"""
+    if chunk_records is None:   # about 256 MB of f32 per chunk
+        chunk_records = max(1, int(64 * 2 ** 20 // (C * max(1, int(raw_len.max())))))
+    step = int(chunk_records)
+    for lo in range(0, len(sel), step):
+        ids, lens, srcs = sel[lo:lo + step], raw_len[lo:lo + step], src_off[lo:lo + step]
+        if rect:
+            L = int(lens[0])
+            buf = np.ascontiguousarray(records[ids], dtype=np.float32)
+            off, stride = np.arange(len(ids), dtype=np.int64) * (C * L), L
+
+            def scatter(host_out, dev, ids=ids):
+                host_out[ids] = dev.cpu().numpy()
+        else:
+            S = int(lens.sum())
+            buf = np.empty((C, S), np.float32)
+            off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+            for o, s, l in zip(off.tolist(), srcs.tolist(), lens.tolist()):
+                buf[:, o:o + l] = records[:, s:s + l]
+            stride = S
+
+            def scatter(host_out, dev, off=off, srcs=srcs, lens=lens):
+                h = dev.cpu().numpy()
+                for o, s, l in zip(off.tolist(), srcs.tolist(), lens.tolist()):
+                    host_out[:, s:s + l] = h[:, o:o + l]
+        x = torch.from_numpy(buf).to(device)
+        yield x, _Tables(x, off, lens, stride), scatter
+
+
+def _sweep(records, offsets, idxs, out, chunk_records, min_len, stage):
+    """Run `stage(x, out, tables, first selected record)` over the selected records.  Device store: one call, returns the output tensor.  Host
+    store: chunk by chunk in place on a staging buffer, returns a float32 numpy array (a copy of the input with the selected records replaced;
+    `out`, a float32 array of the same shape, is filled instead when given)."""
+    if isinstance(records, torch.Tensor) and records.is_cuda:
+        _check_device_store(records)
+        rect, n, _, src_off, raw_len, stride, sel = _record_tables(records, offsets, idxs)
+        _check_lengths(raw_len, min_len)
+        if len(np.unique(sel)) != len(sel):
+            raise ValueError('idxs repeats a record: two workgroups would write the same samples')
+        out = _resolve_out(records, out)
+        with torch.cuda.device(records.device):
+            stage(records, out, _Tables(records, src_off, raw_len, stride), 0)
+        return out
+    host = records.numpy() if isinstance(records, torch.Tensor) else records
+    if not hasattr(host, 'shape') or not hasattr(host, 'dtype') or not np.issubdtype(host.dtype, np.floating):
+        raise ValueError('records must be a float32 device tensor or a host array / memmap / tensor of a float type')
+    rect, n, _, src_off, raw_len, stride, sel = _record_tables(host, offsets, idxs)
+    _check_lengths(raw_len, min_len)
+    if out is not None and out is not False:
+        if not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.shape != host.shape:
+            raise ValueError('for a host store, out must be a float32 numpy array of the same shape')
+    if chunk_records is not None and int(chunk_records) < 1:
+        raise ValueError('chunk_records must be at least 1')
+    if not torch.cuda.is_available():
+        raise RuntimeError('the denoiser runs on the device (no CPU fallback exists)')
+    if out is None:
+        out = np.array(host, dtype=np.float32)
+    device = torch.device('cuda')
+    first = 0
+    with torch.cuda.device(device):
+        for x, tab, scatter in _host_chunks(host, rect, src_off, raw_len, sel, chunk_records, device):
+            stage(x, x, tab, first)
+            if out is not False:
+                scatter(out, x)
+            first += tab.R
+    return out
+
+
+# ---- the three stages -----------------------------------------------------------------------------------------------------------------
+def _workspace(tab, device):
+    from .hip import lib
+    R = max(cnt for _, cnt in tab.launches())
+    return torch.empty(lib().ecgvit_denoise_workspace(R, C, tab.max_len) // 8, dtype=torch.float64, device=device)
+
+
+def lowpass_taps(records, b, a, zi=None, offsets=None, idxs=None, out=None, chunk_records=None):
+    """`scipy.signal.filtfilt(b, a, lead)` with its defaults for every lead of the selected records (f64 arithmetic; odd extension by
+    3 * max(len(a), len(b)) samples, which every record must exceed).  zi: `lfilter_zi(b, a)` when None."""
+    from .hip import lib, check, ptr, stream
+    b, a, zi, nt = _taps(b, a, zi)
+
+    def stage(x, o, tab, first):
+        ws = _workspace(tab, x.device)
+        for lo, cnt in tab.launches():
+            check(lib().ecgvit_filtfilt(ptr(x), ptr(o), ptr(tab.src_off[lo:]), tab.stride, ptr(tab.raw_len[lo:]), cnt, C, tab.min_len, tab.max_len,
+                                        _dp(b), _dp(a), _dp(zi), nt, ptr(ws), stream()), 'ecgvit_filtfilt')
+    return _sweep(records, offsets, idxs, out, chunk_records, 3 * nt + 1, stage)
+
+
+def lowpass(records, fqs=500, passband=50, stopband=60, passband_ripple=1, stopband_attenuation=2.5, offsets=None, idxs=None, out=None,
+            chunk_records=None):
+    """The reference's `butterworth_low_pass` (:48-58): `design_lowpass` then the zero-phase filter.  The reference's `zheng` never passes its
+    `fqs` on, so it always filters with the 500 Hz design; the MATLAB twin passes it.  Here `fqs` is explicit."""
+    b, a, zi = design_lowpass(fqs, passband, stopband, passband_ripple, stopband_attenuation)
+    return lowpass_taps(records, b, a, zi, offsets=offsets, idxs=idxs, out=out, chunk_records=chunk_records)
+
+
+def estimate_noise_std(records, offsets=None, idxs=None, chunk_records=None):
+    """The reference's `est_noise_std` (:76-80) for every lead of the selected records -> (R, 12) float64 device tensor, rows in `idxs` order."""
+    tables = []
+
+    def stage(x, o, tab, first):
+        sig = _sigma_of(x, tab)
+        tables.append(sig)
+    if isinstance(records, torch.Tensor) and records.is_cuda:
+        _check_device_store(records)
+        rect, n, _, src_off, raw_len, stride, sel = _record_tables(records, offsets, idxs)
+        _check_lengths(raw_len)
+        with torch.cuda.device(records.device):
+            stage(records, None, _Tables(records, src_off, raw_len, stride), 0)
+    else:
+        _sweep(records, offsets, idxs, False, chunk_records, 1, stage)
+    return tables[0] if len(tables) == 1 else torch.cat(tables)
+
+
+def _check_nlm(scale, search_width, patch_width):
+    if not (isinstance(patch_width, (int, np.integer)) and patch_width >= 1):
+        raise ValueError(f'patch_width = {patch_width!r}: an int, at least 1')
+    if search_width is not None and not (isinstance(search_width, (int, np.integer)) and search_width >= 1):
+        raise ValueError(f'search_width = {search_width!r}: None (the whole record) or an int, at least 1')
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError(f'scale = {scale!r}: a positive number')
+
+
+def nlm(records, scale=1.5, search_width=None, patch_width=10, sigma=None, offsets=None, idxs=None, out=None, chunk_records=None):
+    """The reference's `DataPreprocessor.nlm` (:83-148) for every lead of the selected records, quirks included (include/ecgvit_hip.h spells
+    them out): f32 arithmetic.  sigma: the (R, 12) float64 table of `estimate_noise_std` over the same selection; None estimates it from
+    `records`, as the reference does.  A lead with sigma == 0 (a constant lead) is copied through; the reference returns NaN there.
+    The defaults are the reference's (`util/config.py`: smooth_factor 1.5, window_size 10)."""
+    from .hip import lib, check, ptr, stream
+    _check_nlm(scale, search_width, patch_width)
+    if sigma is not None:
+        if isinstance(sigma, np.ndarray):
+            sigma = torch.from_numpy(np.ascontiguousarray(sigma, np.float64))
+        if not isinstance(sigma, torch.Tensor) or sigma.dtype != torch.float64 or sigma.dim() != 2 or sigma.shape[1] != 12:
+            raise ValueError('sigma must be an (R, 12) float64 table, one row per selected record')
+
+    def stage(x, o, tab, first):
+        if sigma is None:
+            sig = _sigma_of(x, tab)
+        else:
+            sig = sigma[first:first + tab.R].to(x.device).contiguous()
+        check(lib().ecgvit_nlm_denoise(ptr(x), ptr(o), ptr(tab.src_off), tab.stride, ptr(tab.raw_len), tab.R, C, tab.max_len, ptr(sig), float(scale),
+                                       int(patch_width), 0 if search_width is None else int(search_width), stream()), 'ecgvit_nlm_denoise')
+    if sigma is not None:
+        n_sel = _selected(records, offsets, idxs)
+        if sigma.shape[0] != n_sel:
+            raise ValueError(f'sigma holds {sigma.shape[0]} rows for {n_sel} selected records')
+    return _sweep(records, offsets, idxs, out, chunk_records, 1, stage)
+
+
+def _sigma_of(x, tab):
+    """the noise estimate over exactly the records of `tab` (a device store)"""
+    from .hip import lib, check, ptr, stream
+    sig = torch.zeros((tab.R, C), dtype=torch.float64, device=x.device)
+    ws = _workspace(tab, x.device)
+    for lo, cnt in tab.launches():
+        check(lib().ecgvit_nlm_sigma(ptr(x), ptr(tab.src_off[lo:]), tab.stride, ptr(tab.raw_len[lo:]), cnt, C, tab.max_len, ptr(sig[lo:]), ptr(ws),
+                                     stream()), 'ecgvit_nlm_sigma')
+    return sig
+
+
+def _selected(records, offsets, idxs):
+    host = records.numpy() if isinstance(records, torch.Tensor) and not records.is_cuda else records
+    return len(_record_tables(host, offsets, idxs)[6])
+
+
+class EcgDenoiser:
+    """`DataPreprocessor.zheng` as one call over a record store: low-pass, minus `baseline`, non-local means.
+
+    `EcgDenoiser(fqs=500)(records)` reproduces the reference's Python `zheng(sig, fqs)` for ANY fqs (its low-pass is always designed for
+    500 Hz: `zheng` does not pass `fqs` on); `EcgDenoiser(fqs=f)(records)` with the record's own rate reproduces the MATLAB twin, which does.
+    The robust LOESS fit the reference subtracts between the two stages is not built: `baseline`, a tensor in the store's own layout, is
+    subtracted at that place instead (None: nothing is)."""
+
+    def __init__(self, fqs=500, scale=1.5, search_width=None, patch_width=10):
+        _check_nlm(scale, search_width, patch_width)
+        self.fqs, self.scale, self.search_width, self.patch_width = fqs, scale, search_width, patch_width
+        self.b, self.a, self.zi = design_lowpass(fqs)
+
+    def __repr__(self):
+        return f'<{self.__class__.__qualname__} fqs={self.fqs} scale={self.scale} search_width={self.search_width} patch_width={self.patch_width}>'
+
+    def __call__(self, records, baseline=None, offsets=None, idxs=None, out=None, chunk_records=None):
+        """records: a float32 device store (-> device tensor), or a host array / memmap, streamed `chunk_records` records at a time through each
+        stage (-> float32 numpy array; `baseline` is then a host array of the same shape)."""
+        device = isinstance(records, torch.Tensor) and records.is_cuda
+        rect, n, _, src_off, raw_len, stride, sel = _record_tables(records.numpy() if isinstance(records, torch.Tensor) and not device else records, offsets, idxs)
+        if baseline is not None:
+            ok = (isinstance(baseline, torch.Tensor) and baseline.dtype == torch.float32 and baseline.device == records.device) if device else \
+                isinstance(baseline, (np.ndarray, torch.Tensor))
+            if not ok or tuple(baseline.shape) != tuple(records.shape):
+                raise ValueError("baseline must be in the store's layout: a float32 device tensor for a device store, a host array for a host store")
+        out = lowpass_taps(records, self.b, self.a, self.zi, offsets=offsets, idxs=idxs, out=out, chunk_records=chunk_records)
+        if baseline is not None:
+            base = baseline if device else np.asarray(baseline, np.float32)
+            if idxs is None:
+                out -= base
+            elif rect:
+                ids = torch.from_numpy(sel).to(out.device) if device else sel
+                out[ids] = out[ids] - base[ids]
+            else:
+                for s, l in zip(src_off.tolist(), raw_len.tolist()):
+                    out[:, s:s + l] -= base[:, s:s + l]
+        return nlm(out, self.scale, self.search_width, self.patch_width, offsets=offsets, idxs=idxs, out=out, chunk_records=chunk_records)

@@ -7,7 +7,7 @@ missing or a call returns non-zero this module raises -- the product path never 
 """
 import ctypes
 import os
-from ctypes import c_int, c_int32, c_int64, c_uint64, c_float, c_void_p, c_char_p, POINTER, Structure, byref
+from ctypes import c_int, c_int32, c_int64, c_uint64, c_float, c_double, c_void_p, c_char_p, POINTER, Structure, byref
 
 import torch
 
@@ -24,6 +24,7 @@ ACC_INIT, ACC_ADD, ACC_FOLD = 0, 1, 2   # ecgvit_grad_accumulate modes
 KERNEL_NONE, KERNEL_GEMM_F32, KERNEL_GEMM_BF16, KERNEL_GEMM_NT, KERNEL_GEMM_WGRAD = 0, 1, 2, 3, 4
 POOL_CLS, POOL_MEAN = 0, 1   # ecgvit_pool_records modes
 FIT_TARGETS, FIT_BINS = 16, 256   # ecgvit_fit_histogram / ecgvit_fit_select: targets per lead, bins per pass
+DENOISE_MAX_LEN, DENOISE_MAX_TAPS = 32768, 9   # ecgvit_filtfilt / ecgvit_nlm_*: samples per record, filter taps
 
 _ERR = {1: 'ECGVIT_EINVAL (unsupported shape / argument)', 2: 'ECGVIT_ELAUNCH (HIP launch failure)'}
 
@@ -48,7 +49,7 @@ class GemmDesc(Structure):
 
 
 # name -> (restype, argtypes); mirrors include/ecgvit_hip.h one to one
-_P, _I, _L, _F, _U = c_void_p, c_int, c_int64, c_float, c_uint64
+_P, _I, _L, _F, _U, _D = c_void_p, c_int, c_int64, c_float, c_uint64, c_double
 SIGNATURES = {
     'ecgvit_version': (c_char_p, []),
     'ecgvit_abi_version': (c_int, []),
@@ -132,6 +133,10 @@ SIGNATURES = {
     'ecgvit_tok_workspace': (c_int64, [_I, _I]),
     'ecgvit_tok_update': (c_int, [_P, _P, _L, _P, _P, _P, _L, _I, _I, _L, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     'ecgvit_tok_decode': (c_int, [_P, _P, _L, _P, _P, _P, _L, _I, _I, _L, _I, _P, _P, _P, _I, _P]),
+    'ecgvit_denoise_workspace': (c_int64, [_I, _I, _I]),
+    'ecgvit_filtfilt': (c_int, [_P, _P, _P, _L, _P, _I, _I, _I, _I, POINTER(c_double), POINTER(c_double), POINTER(c_double), _I, _P, _P]),
+    'ecgvit_nlm_sigma': (c_int, [_P, _P, _L, _P, _I, _I, _I, _P, _P, _P]),
+    'ecgvit_nlm_denoise': (c_int, [_P, _P, _P, _L, _P, _I, _I, _I, _P, _D, _I, _I, _P]),
 }
 
 _lib = None

@@ -549,6 +549,43 @@ int ecgvit_tok_decode(float *out, const int64_t *src_off, int64_t lead_stride, c
                       const int64_t *dst_off, int64_t dst_stride, int R, int C, int64_t n_seg, int k, const int32_t *ids, const float *means,
                       const float *centers, int V, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * the Zheng et al. denoiser (denoise.py; the reference's preprocess/data_preprocessor.py:22-148 and its MATLAB twin): zero-phase low-pass, noise
+ * estimate, non-local means.  Additive entry points: the ABI version stays 6.
+ * The store is addressed as ecgvit_fit_moments addresses it (x, src_off, lead_stride, raw_len; raw_len[r] <= 0 skips a record; a record starts
+ * at any 4-byte address).  max_len: the caller's upper bound of raw_len, at most 32768 (the non-local means keeps a lead in LDS); a record longer
+ * than max_len is left untouched.  out: the store's own layout (lead c of record r at out + src_off[r] + c * lead_stride); out == x runs in
+ * place, any other overlap is the caller's error.  Only the selected records' raw_len samples are written.  One workgroup per (record, lead);
+ * every sum runs in an order that is a function of the record's own length and of the parameters alone, without floating-point atomics: a
+ * record's output has the same bits in a rectangle, a ragged store or a subset, alone or in a batch.  NaN input is not supported.
+ * ------------------------------------------------------------------------------------------------ */
+/* bytes of `workspace` ecgvit_filtfilt and ecgvit_nlm_sigma need (f64 intermediates, [R][C][max_len + 64]); 0 for unsupported arguments */
+int64_t ecgvit_denoise_workspace(int R, int C, int max_len);
+/* scipy.signal.filtfilt(b, a, x) with its defaults, per lead: odd extension by padlen = 3 * ntaps samples at each end, a direct-form-II-transposed
+ * pass started from zi * x_ext[0], the same pass over the reversed result started from zi * y[-1], reversed again and stripped.  b, a (ntaps each,
+ * the shorter padded with zeros; 1 <= ntaps <= 9; a[0] == 1) and zi (ntaps - 1; scipy.signal.lfilter_zi) are HOST arrays of finite doubles.
+ * f64 arithmetic, f32 loads and stores.  min_len: the caller's lower bound of the positive raw_len; min_len <= padlen is refused, where scipy
+ * raises (a shorter record that reaches the kernel all the same is left untouched). */
+int ecgvit_filtfilt(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
+                    int max_len, const double *b, const double *a, const double *zi, int ntaps, void *workspace, void *stream);
+/* sigma[r * C + c] (f64) = the reference's est_noise_std of the lead: res = x; res[i] = (2 res[i] - res[i-1] - res[i+1]) / sqrt(6) for i = 1 .. n-2
+ * in place (res[i-1] updated, res[i+1] original); m = median(res); sigma = median |1.4826 (res - m)|.  f64 in the reference's order; both medians
+ * are exact order statistics (radix select on the f64 bit pattern; the mean of the two middle values for even n).  scipy's
+ * median_abs_deviation subtracts the median of 1.4826 (res - m) once more: exactly 0 for odd n, a rounding of m (1e-16 relative) for even n.
+ * Entries of skipped records are not written. */
+int ecgvit_nlm_sigma(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len, double *sigma,
+                     void *workspace, void *stream);
+/* DataPreprocessor.nlm per lead, quirks included (n = 2p + 2 denoises its one middle sample, as the reference's range(p + 1, n - p) does).  p = patch_wd >= 1, W = sch_wd (0 or more than n: n), h = 2 (2p + 1) (scale * sigma[r * C + c])^2.
+ * For ii = p + 1 .. n - p - 1:  out[ii] = sum_idx w x[ii + idx] / (sum_idx w + 2.220446049250313e-16) over idx = -(W - 1) .. W - 1 with
+ * 0 < ii + idx < n (sample 0 is never a neighbour), w = exp(-d / h), d = sum_{j = -p .. p} (x[ii + j] - x[ii + j + idx])^2 where a pair whose
+ * second index lies outside [0, n) contributes 0.  The first p + 1 and the last p samples are copied; a record with n <= 2p + 1 is copied
+ * through, and so is a lead with sigma == 0 (or with 1 / h past f32) -- the reference divides 0 by 0 there and returns NaN.
+ * f32 arithmetic (1 / h once per lead from the f64 sigma, v_exp_f32).  A lane owns runs of 15 consecutive output samples (the last run of a
+ * record ends on sample n - p - 1) and adds the shifts in ascending order; d is summed from its 2p + 1 terms at the start of each run and shift
+ * and slides within the run (d += new^2 - old^2). */
+int ecgvit_nlm_denoise(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len,
+                       const double *sigma, double scale, int patch_wd, int sch_wd, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

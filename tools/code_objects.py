@@ -55,6 +55,37 @@ def kernels(path):
     return res
 
 
+OBJDUMP = '/opt/rocm/lib/llvm/bin/llvm-objdump'
+
+
+def hot_blocks(path, kernel, marker='v_exp_f32', at_least=8):
+    """[(vector instructions, `marker` instructions)] of every basic block of the kernel whose mangled name contains `kernel` that holds at
+    least `at_least` `marker` instructions, from the disassembly: the issue cost per marker of a loop body (tools/denoise_rate.py)"""
+    out = []
+    for co in code_objects(path):
+        with tempfile.NamedTemporaryFile(suffix='.co', delete=False) as f:
+            f.write(co)
+            name = f.name
+        try:
+            txt = subprocess.run([OBJDUMP, '-d', name], capture_output=True, text=True, check=True).stdout
+        finally:
+            os.unlink(name)
+        inside, valu, mark = False, 0, 0
+        for line in txt.splitlines():
+            m = re.match(r'^[0-9a-f]+ <(\S+)>:', line)
+            t = line.strip()
+            if m or t.startswith('s_cbranch') or t.startswith('s_branch'):      # a block ends at a function head or a branch
+                if inside and mark >= at_least:
+                    out.append((valu, mark))
+                valu = mark = 0
+                if m:
+                    inside = kernel in m.group(1)
+            elif inside and t.startswith('v_'):
+                valu += 1
+                mark += t.startswith(marker)
+    return out
+
+
 if __name__ == '__main__':
     args = [a for a in sys.argv[1:] if not a.startswith('--')]
     lib = args[0] if args else os.path.join(ROOT, 'ecg-representation-learning_amd', 'libecgvit_hip.so')
