@@ -66,7 +66,10 @@ __global__ __launch_bounds__(256) void bce_bwd_kernel(const float *__restrict__ 
     const int64_t i = blockIdx.x * 256ll + threadIdx.x;
     if (i >= count) return;
     const float up = (gelem ? gelem[i] : (gscalar ? gscalar[0] : 1.0f)) * gscale;
-    const float sg = 1.0f / (1.0f + expf(-z[i]));
+    // below -87 expf(-z) nears and then passes FLT_MAX (1 / (1 + inf) = 0) while sigmoid(z) = e^z (1 - e^z + ...) is still a representable
+    // (from -87.4 on denormal) f32: take e^z there, which is sigmoid(z) to 1e-38 relative
+    const float zi = z[i];
+    const float sg = zi < -87.0f ? expf(zi) : 1.0f / (1.0f + expf(-zi));
     float g = (sg - y[i]) * up;
     if (w) g *= w[i];
     dz[i] = g;
@@ -284,8 +287,8 @@ __global__ __launch_bounds__(256) void adamw_spans_kernel(float *__restrict__ p,
 
 // ---- micro-batch gradient accumulation over a span table (same format as above): MODE INIT acc = s*g, ADD acc += s*g, FOLD g = s*g + acc.
 //      Every element of a span is read and written by exactly one thread (no reduction, no atomics), so the result does not depend on the
-//      grid.  Spans whose offset is a multiple of 4 take 16-B accesses; the layout's offsets are multiples of 16 (the host checks it), the
-//      element path only covers a count's tail.
+//      grid.  Spans whose offset is a multiple of 4 elements take 16-B accesses with an element tail; any other offset takes the element path
+//      for the whole span (the engine's layout keeps its offsets at multiples of 16, so it only meets the tail).
 template <int MODE>
 __global__ __launch_bounds__(256) void grad_accumulate_kernel(float *__restrict__ acc, float *__restrict__ g, const int64_t *__restrict__ spans,
                                                               int nspan, float scale) {

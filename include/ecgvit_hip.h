@@ -373,7 +373,7 @@ int ecgvit_adamw_step_spans(float *p, const float *g, float *m, float *v, void *
  *   ECGVIT_ACC_ADD   acc += scale * g         (after each middle micro-batch)
  *   ECGVIT_ACC_FOLD  g = scale * g + acc      (the last micro-batch: g then holds the whole batch's gradient for the norm, the exchange and AdamW)
  * scale = 1 for gradients (exact); total = the sum of the counts (sizes the grid).  acc and g 16-B aligned; span offsets should be multiples
- * of 8 elements (16-B accesses; others take the element path).  Elements outside the spans are neither read nor written. */
+ * of 4 elements (16-B accesses; others take the element path).  Elements outside the spans are neither read nor written. */
 #define ECGVIT_ACC_INIT 0
 #define ECGVIT_ACC_ADD 1
 #define ECGVIT_ACC_FOLD 2
