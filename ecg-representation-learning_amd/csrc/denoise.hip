@@ -1,7 +1,7 @@
 // The Zheng et al. denoiser (denoise.py; the reference's preprocess/data_preprocessor.py): zero-phase low-pass, the noise estimate and non-local
 // means, per (record, lead), over a record store addressed as fit_stats.hip addresses it.  Contracts and the order of every sum: include/ecgvit_hip.h.
 //
-// One workgroup per (record, lead) in all three kernels.  The low-pass and the noise estimate are sequential recurrences in f64: lane 0 walks
+// One workgroup per (record, lead) in every kernel.  The robust LOESS baseline (rloess_kernel) is described at the end of the file.  Of the other three:  The low-pass and the noise estimate are sequential recurrences in f64: lane 0 walks
 // them chunk by chunk through LDS while the whole workgroup moves the chunks (coalesced), and their f64 intermediates live in a caller's
 // workspace.  Non-local means is the hot path: the lead sits in LDS as f32, a lane owns runs of NLM_RUN consecutive output samples.
 #include "common.h"
@@ -381,6 +381,236 @@ int ecgvit_nlm_denoise(const float *x, float *out, const int64_t *src_off, int64
     if (max_len <= 4096) hipLaunchKernelGGL(nlm_kernel<4096>, dim3(R, C), dim3(threads), 0, as_stream(stream), g);
     else if (max_len <= 8192) hipLaunchKernelGGL(nlm_kernel<8192>, dim3(R, C), dim3(threads), 0, as_stream(stream), g);
     else hipLaunchKernelGGL(nlm_kernel<DN_MAX_LEN>, dim3(R, C), dim3(threads), 0, as_stream(stream), g);
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
+}
+
+// =====================================================================================================
+// robust LOESS baseline (the reference's rloess: loess_1d(x, sig, degree=2, npoints=n)[1] of the `loess` package, which is not available: the
+// algorithm is the one include/ecgvit_hip.h states in full, and parity with the package is UNPINNED).  Two choices are made here where the
+// reference leaves the result open: for an even window the two samples at distance m / 2 tie and the LOWER index enters the window (the
+// reference's unstable argsort takes either, by numpy version and CPU); a window whose median absolute residual is 0 (below the smallest normal
+// f64) ends its robust loop and keeps the fit it has (the reference divides by zero).
+//
+// One workgroup per (record, lead), the lead in LDS as f32; one wave per output sample j, window sample lo + lane + 64 v in slot v of the lane
+// (NV = ceil(m / 64) slots: distance weight, residual and the f32 sample in registers).  f64 throughout, without contraction into fma: every
+// operation is the IEEE one in the order written, which tests/loess_ref.py restates operation for operation.
+//   fit      eight moment sums (S_k = sum w s^k, k = 0 .. 4; T_k = sum w s^k y, k = 0 .. 2; s = (i - j) (1 / d)): a lane adds its slots in
+//            ascending order from +0, the wave adds lanes by the xor butterfly 32, 16, .. 1; a slot past the window adds +0, so the sums do not
+//            depend on NV.  The (g + 1) x (g + 1) normal equations are solved by elimination without pivoting (symmetric positive definite in
+//            the scaled abscissa); the value at j is the constant coefficient.
+//   median   exact: the non-negative f64 patterns order as integers; the k-th smallest is found bit by bit from bit 62, counting the samples
+//            below the trial value with one wave ballot per slot (scalar population counts: no cross-lane sums), until one candidate is left.
+// =====================================================================================================
+#pragma clang fp contract(off)
+#define RL_THREADS 512
+#define RL_MAX_POINTS 1024
+#define RL_MAX_ITERS 10
+#define RL_CUT 0.34
+#define RL_MIN_MAD 2.2250738585072014e-308
+
+struct RloessArgs {
+    const float *x;
+    float *out;
+    const int64_t *src_off;
+    int64_t lead_stride;
+    const int32_t *raw_len;
+    int8_t *iters;
+    double frac;
+    int C, max_len, npoints, degree, robust_iters, subtract;
+};
+
+// the reference's force_odd(int(n * frac) - 1), as Python computes it: truncation of the f64 product, floor division by 2
+__host__ __device__ __forceinline__ int rl_frac_points(int n, double frac) {
+    const int k = (int)((double)n * frac) - 1;
+    return 2 * (k >= 0 ? k / 2 : -((1 - k) / 2)) + 1;
+}
+
+__device__ __forceinline__ double rl_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned long long rl_wave_max(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long u = __shfl_xor(v, o, 64);
+        v = u > v ? u : v;
+    }
+    return v;
+}
+
+template <int NV> struct RlWindow {
+    double dw[NV], aerr[NV];     // distance weight (0 past the window), |fit - y| of the last fit (+inf past the window)
+    float y[NV];
+    int t0;                      // (lo + lane) - j: slot v holds the window sample at signed distance t0 + 64 v
+    double inv_d;
+};
+
+// weighted fit with weights dw * bw, bw = (1 - min((aerr inv6)^2, 1))^2 (inv6 == 0: bw = 1, the distance-weighted fit).  -> the coefficients
+// (every lane holds them) and the lane's outlier bits (bw < 0.34, one per slot); a slot past the window has bw = 0 in every robust fit
+template <int NV> __device__ __forceinline__ unsigned rl_fit(const RlWindow<NV> &w, double inv6, int degree, double &a0, double &a1, double &a2) {
+    double S0 = 0.0, S1 = 0.0, S2 = 0.0, S3 = 0.0, S4 = 0.0, T0 = 0.0, T1 = 0.0, T2 = 0.0;
+    unsigned bad = 0u;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const double s = (double)(w.t0 + 64 * v) * w.inv_d;
+        const double q = w.aerr[v] * inv6;
+        const double u = 1.0 - fmin(q * q, 1.0);
+        const double bw = u * u;
+        bad |= (bw < RL_CUT ? 1u : 0u) << v;
+        const double wt = w.dw[v] * bw, y = (double)w.y[v];
+        const double w1 = wt * s, w2 = w1 * s, w3 = w2 * s, w4 = w3 * s;
+        S0 += wt; S1 += w1; S2 += w2; S3 += w3; S4 += w4;
+        T0 += wt * y; T1 += w1 * y; T2 += w2 * y;
+    }
+    S0 = rl_wave_sum(S0); S1 = rl_wave_sum(S1); S2 = rl_wave_sum(S2); T0 = rl_wave_sum(T0); T1 = rl_wave_sum(T1);
+    const double r0 = 1.0 / S0;
+    const double l1 = S1 * r0;
+    const double A11 = S2 - l1 * S1, B1 = T1 - l1 * T0;
+    if (degree == 2) {
+        S3 = rl_wave_sum(S3); S4 = rl_wave_sum(S4); T2 = rl_wave_sum(T2);
+        const double l2 = S2 * r0;
+        const double A12 = S3 - l1 * S2, A22 = S4 - l2 * S2, B2 = T2 - l2 * T0;
+        const double r1 = 1.0 / A11;
+        const double l21 = A12 * r1;
+        const double D22 = A22 - l21 * A12, E2 = B2 - l21 * B1;
+        a2 = E2 / D22;
+        a1 = (B1 - A12 * a2) * r1;
+        a0 = ((T0 - S1 * a1) - S2 * a2) * r0;
+    } else {
+        a2 = 0.0;
+        a1 = B1 / A11;
+        a0 = (T0 - S1 * a1) * r0;
+    }
+    return bad;
+}
+
+template <int NV> __device__ __forceinline__ void rl_residuals(RlWindow<NV> &w, int m, int lane, double a0, double a1, double a2) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const double s = (double)(w.t0 + 64 * v) * w.inv_d;
+        const double f = a0 + s * (a1 + s * a2);
+        w.aerr[v] = lane + 64 * v < m ? fabs(f - (double)w.y[v]) : __builtin_huge_val();
+    }
+}
+
+// np.median of the window's residuals: the (m - 1) / 2-th smallest, for even m its mean with the next one.  Wave-uniform control flow.
+template <int NV> __device__ __forceinline__ double rl_median(const RlWindow<NV> &w, int m) {
+    unsigned long long key[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) key[v] = (unsigned long long)__double_as_longlong(w.aerr[v]);     // +inf past the window: above every sample
+    const int k = (m - 1) / 2;
+    unsigned long long prefix = 0ull;
+    int below = 0, cand = m, b = 62;
+    for (; b >= 0 && cand > 1; --b) {
+        const unsigned long long mid = prefix | (1ull << b);
+        int cnt = 0;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) cnt += __popcll(__ballot(key[v] < mid));
+        if (k < cnt) {
+            cand = cnt - below;
+        } else {
+            prefix = mid;
+            cand = below + cand - cnt;
+            below = cnt;
+        }
+    }
+    // the candidates are the keys in [prefix, prefix + 2^(b + 1)): one key, or equal ones
+    const unsigned long long span = b >= 0 ? (2ull << b) - 1ull : 0ull;
+    unsigned long long best = 0ull;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) best = (key[v] >= prefix && key[v] - prefix <= span && key[v] > best) ? key[v] : best;
+    const unsigned long long k1 = rl_wave_max(best);
+    if (m & 1) return __longlong_as_double((long long)k1);
+    int le = 0;
+    unsigned long long next = ~0ull;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        le += __popcll(__ballot(key[v] <= k1));
+        next = (key[v] > k1 && key[v] < next) ? key[v] : next;
+    }
+    unsigned long long k2 = k1;
+    if (le <= k + 1) k2 = ~rl_wave_max(~next);
+    return (__longlong_as_double((long long)k1) + __longlong_as_double((long long)k2)) / 2.0;
+}
+
+template <int NV, int CAP> __global__ __launch_bounds__(RL_THREADS) void rloess_kernel(RloessArgs g) {
+    __shared__ float s[CAP];
+    const int rec = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+    const int n = g.raw_len[rec];
+    if (n <= 0 || n > CAP || n > g.max_len) return;
+    int m = g.frac > 0.0 ? rl_frac_points(n, g.frac) : g.npoints;
+    if (m > n) m = n;
+    if (m < g.degree + 2 || m > 64 * NV) return;         // (the launcher refused both for the lengths the caller promised)
+    const int64_t base = g.src_off[rec] + (int64_t)c * g.lead_stride;
+    const float *x = g.x + base;       // (no __restrict__: out may be x)
+    float *out = g.out + base;
+    for (int i = tid; i < n; i += RL_THREADS) s[i] = x[i];
+    __syncthreads();           // from here on the lead is read from LDS alone: out may be x
+    int8_t *iters = g.iters ? g.iters + ((int64_t)rec * g.C + c) * g.max_len : nullptr;
+    const int lane = tid & 63, half = (m & 1) ? (m - 1) / 2 : m / 2;
+    for (int j = tid >> 6; j < n; j += RL_THREADS / 64) {
+        const int lo = min(max(j - half, 0), n - m);
+        const int d = max(j - lo, lo + m - 1 - j);
+        RlWindow<NV> w;
+        w.t0 = lo + lane - j;
+        w.inv_d = 1.0 / (double)d;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const bool in = lane + 64 * v < m;
+            const double a = fabs((double)(w.t0 + 64 * v) * w.inv_d);
+            const double u = 1.0 - a * a * a;
+            w.dw[v] = in ? u * u * u : 0.0;
+            w.y[v] = in ? s[lo + lane + 64 * v] : 0.f;
+            w.aerr[v] = 0.0;
+        }
+        double a0, a1, a2;
+        rl_fit<NV>(w, 0.0, g.degree, a0, a1, a2);
+        unsigned bad = 0u;
+        int it = 0;
+        while (it < g.robust_iters) {
+            rl_residuals<NV>(w, m, lane, a0, a1, a2);
+            const double mad = rl_median<NV>(w, m);
+            if (!(mad >= RL_MIN_MAD)) break;
+            const unsigned now = rl_fit<NV>(w, 1.0 / (6.0 * mad), g.degree, a0, a1, a2);
+            const bool same = it > 0 && __ballot(now != bad) == 0ull;
+            bad = now;
+            ++it;
+            if (same) break;
+        }
+        if (lane == 0) {
+            out[j] = g.subtract ? (float)((double)s[j] - a0) : (float)a0;
+            if (iters) iters[j] = (int8_t)it;
+        }
+    }
+}
+
+template <int CAP> static void rl_launch(int nv, dim3 grid, hipStream_t st, const RloessArgs &g) {
+    if (nv <= 1) hipLaunchKernelGGL((rloess_kernel<1, CAP>), grid, dim3(RL_THREADS), 0, st, g);
+    else if (nv <= 2) hipLaunchKernelGGL((rloess_kernel<2, CAP>), grid, dim3(RL_THREADS), 0, st, g);
+    else if (nv <= 4) hipLaunchKernelGGL((rloess_kernel<4, CAP>), grid, dim3(RL_THREADS), 0, st, g);
+    else if (nv <= 8) hipLaunchKernelGGL((rloess_kernel<8, CAP>), grid, dim3(RL_THREADS), 0, st, g);
+    else hipLaunchKernelGGL((rloess_kernel<16, CAP>), grid, dim3(RL_THREADS), 0, st, g);
+}
+
+int ecgvit_rloess(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
+                  int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters, void *stream) {
+    if (!dn_store_ok(x, src_off, raw_len, R, C, max_len) || !out || (reinterpret_cast<uintptr_t>(out) & 3u) || lead_stride <= 0) return ECGVIT_EINVAL;
+    if (degree < 1 || degree > 2 || robust_iters < 0 || robust_iters > RL_MAX_ITERS || (subtract != 0 && subtract != 1)) return ECGVIT_EINVAL;
+    if (!(frac >= 0.0 && frac <= 1.0) || min_len < degree + 2 || min_len > max_len) return ECGVIT_EINVAL;
+    int widest = npoints;
+    if (frac > 0.0) {          // the window of the shortest and of the longest record: a fraction's width grows with the length
+        widest = rl_frac_points(max_len, frac);
+        if (rl_frac_points(min_len, frac) < degree + 2) return ECGVIT_EINVAL;
+    }
+    if (widest < degree + 2 || widest > RL_MAX_POINTS) return ECGVIT_EINVAL;
+    RloessArgs g;
+    g.x = x; g.out = out; g.src_off = src_off; g.lead_stride = lead_stride; g.raw_len = raw_len; g.iters = iters; g.frac = frac;
+    g.C = C; g.max_len = max_len; g.npoints = npoints; g.degree = degree; g.robust_iters = robust_iters; g.subtract = subtract;
+    const int nv = (min(widest, max_len) + 63) / 64;
+    if (max_len <= 8192) rl_launch<8192>(nv, dim3(R, C), as_stream(stream), g);
+    else rl_launch<DN_MAX_LEN>(nv, dim3(R, C), as_stream(stream), g);
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
 }

@@ -550,8 +550,8 @@ int ecgvit_tok_decode(float *out, const int64_t *src_off, int64_t lead_stride, c
                       const float *centers, int V, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
- * the Zheng et al. denoiser (denoise.py; the reference's preprocess/data_preprocessor.py:22-148 and its MATLAB twin): zero-phase low-pass, noise
- * estimate, non-local means.  Additive entry points: the ABI version stays 6.
+ * the Zheng et al. denoiser (denoise.py; the reference's preprocess/data_preprocessor.py:22-148 and its MATLAB twin): zero-phase low-pass, robust
+ * LOESS baseline, noise estimate, non-local means.  Additive entry points: the ABI version stays 6.
  * The store is addressed as ecgvit_fit_moments addresses it (x, src_off, lead_stride, raw_len; raw_len[r] <= 0 skips a record; a record starts
  * at any 4-byte address).  max_len: the caller's upper bound of raw_len, at most 32768 (the non-local means keeps a lead in LDS); a record longer
  * than max_len is left untouched.  out: the store's own layout (lead c of record r at out + src_off[r] + c * lead_stride); out == x runs in
@@ -585,6 +585,34 @@ int ecgvit_nlm_sigma(const float *x, const int64_t *src_off, int64_t lead_stride
  * and slides within the run (d += new^2 - old^2). */
 int ecgvit_nlm_denoise(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len,
                        const double *sigma, double scale, int patch_wd, int sch_wd, void *stream);
+/* The robust LOESS baseline the reference subtracts between the low-pass and the non-local means (rloess: loess_1d(x, sig, degree=2,
+ * npoints=n)[1] of the `loess` package).  The package is not available, so no fixture could be written by running it: parity with the reference
+ * is UNPINNED, and what the tests hold the kernel to is a numpy f64 restatement of the algorithm below (tests/loess_ref.py).
+ * Per lead y[0 .. n) at x = 0 .. n - 1, m = min(npoints, n), degree g, for every sample j:
+ *   window    the m samples nearest to j, [lo, lo + m): lo = clamp(j - (m - 1) / 2, 0, n - m) for odd m, clamp(j - m / 2, 0, n - m) for even m
+ *   weights   d = max(j - lo, lo + m - 1 - j), dw_i = (1 - (|i - j| / d)^3)^3 (the farthest sample has weight 0)
+ *   fit       the weighted least-squares polynomial of degree g through the window, weights dw
+ *   robust    at most robust_iters times: aerr = |fit - y| over the window, mad = median(aerr) (the mean of the two middle values for even m),
+ *             bw = (1 - min((aerr / (6 mad))^2, 1))^2, refit with weights dw bw, bad = bw < 0.34; stop when bad equals the previous
+ *             iteration's bad (the first iteration never stops)
+ *   result    the last fit's value at j
+ * DEFINED HERE, where the reference leaves the result open: (1) for even m the two samples at distance m / 2 tie and the LOWER index enters the
+ * window, what a stable sort of the distances gives (the reference's default argsort takes either, by numpy version and CPU; the sample has
+ * regression weight 0 but enters the median and `bad`, which moves the result by up to 5e-3 of the amplitude; zheng passes n = fqs = 500, even);
+ * (2) mad == 0 (an all-zero lead; below the smallest normal f64 counts as 0) ends the robust loop and the fit it has stands (the reference
+ * divides by zero), as the sigma == 0 lead of ecgvit_nlm_denoise is copied through.
+ * frac > 0 replaces npoints per record by the reference's force_odd(int(n * frac) - 1) = 2 floor((int(n frac) - 1) / 2) + 1, computed in f64 as
+ * Python computes it.  degree: 1 or 2; robust_iters: 0 (the plain LOESS) .. 10; npoints (frac == 0), or the fraction's width of a record of
+ * max_len samples: at most 1024; npoints, and the fraction's width of a record of min_len samples: at least degree + 2.  min_len: the caller's
+ * lower bound of the positive raw_len, at least degree + 2 (a record whose window is narrower or wider all the same is left untouched).
+ * subtract == 0 writes the baseline, 1 writes x - baseline (the difference in f64, rounded once); out == x works in both.
+ * iters (nullable): bytes [R][C][max_len], the robust iterations run at sample j of lead c of the launch's r-th record at
+ * iters[(r * C + c) * max_len + j]; other bytes are not written.
+ * f64 arithmetic without contraction: s = (i - j) (1 / d); eight moment sums (sum w s^k, k = 0 .. 4; sum w s^k y, k = 0 .. 2), window sample
+ * lo + l + 64 v in slot v of lane l, a lane adds its slots in ascending order, the wave adds lanes by the butterfly 32, 16, .. 1; the normal
+ * equations by elimination without pivoting; the value at j is the constant coefficient.  The median is an exact order statistic. */
+int ecgvit_rloess(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
+                  int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters, void *stream);
 
 #ifdef __cplusplus
 }
