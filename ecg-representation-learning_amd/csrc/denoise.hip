@@ -1,24 +1,29 @@
 // The Zheng et al. denoiser (denoise.py; the reference's preprocess/data_preprocessor.py): zero-phase low-pass, the noise estimate and non-local
 // means, per (record, lead), over a record store addressed as fit_stats.hip addresses it.  Contracts and the order of every sum: include/ecgvit_hip.h.
 //
-// One workgroup per (record, lead) in every kernel.  The robust LOESS baseline (rloess_kernel) is described at the end of the file.  Of the other three:  The low-pass and the noise estimate are sequential recurrences in f64: lane 0 walks
+// One workgroup per (record, lead) in every kernel but the two tiled along time for records past DN_MAX_LEN (nlm_tiled_kernel, rloess_tiled_kernel:
+// grid (record, lead, tile), each described where it stands).  The robust LOESS baseline (rloess_kernel) is described at the end of the file.
+// Of the other three:  The low-pass and the noise estimate are sequential recurrences in f64: lane 0 walks
 // them chunk by chunk through LDS while the whole workgroup moves the chunks (coalesced), and their f64 intermediates live in a caller's
 // workspace.  Non-local means is the hot path: the lead sits in LDS as f32, a lane owns runs of NLM_RUN consecutive output samples.
 #include "common.h"
 
 #define DN_MAX_LEN 32768            // samples per record: 128 KiB of f32 in LDS for the non-local means
+#define DN_MAX_LEN_TILED (1 << 25)  // samples per record of the _long / _tiled entry points (24 hours at 360 Hz): nothing keeps a whole lead in LDS
 #define DN_WS_PAD 64                // workspace doubles per lead beyond max_len (the low-pass's two extensions: 2 * 3 * 9 = 54)
 #define DN_MAX_TAPS 9
 
-static bool dn_store_ok(const float *x, const int64_t *src_off, const int32_t *raw_len, int R, int C, int max_len) {
-    return x && src_off && raw_len && R > 0 && C > 0 && C <= 65535 && max_len > 0 && max_len <= DN_MAX_LEN && (reinterpret_cast<uintptr_t>(x) & 3u) == 0 &&
+static bool dn_store_ok(const float *x, const int64_t *src_off, const int32_t *raw_len, int R, int C, int max_len, int cap = DN_MAX_LEN) {
+    return x && src_off && raw_len && R > 0 && C > 0 && C <= 65535 && max_len > 0 && max_len <= cap && (reinterpret_cast<uintptr_t>(x) & 3u) == 0 &&
            (reinterpret_cast<uintptr_t>(src_off) & 7u) == 0 && (reinterpret_cast<uintptr_t>(raw_len) & 3u) == 0;
 }
 
-int64_t ecgvit_denoise_workspace(int R, int C, int max_len) {
-    if (R <= 0 || C <= 0 || max_len <= 0 || max_len > DN_MAX_LEN) return 0;
+static int64_t dn_workspace(int R, int C, int max_len, int cap) {
+    if (R <= 0 || C <= 0 || max_len <= 0 || max_len > cap) return 0;
     return (int64_t)R * C * (max_len + DN_WS_PAD) * 8;
 }
+int64_t ecgvit_denoise_workspace(int R, int C, int max_len) { return dn_workspace(R, C, max_len, DN_MAX_LEN); }
+int64_t ecgvit_denoise_workspace_long(int R, int C, int max_len) { return dn_workspace(R, C, max_len, DN_MAX_LEN_TILED); }
 
 // =====================================================================================================
 // zero-phase IIR filter (scipy.signal.filtfilt with its defaults)
@@ -102,9 +107,10 @@ __global__ __launch_bounds__(FF_THREADS) void filtfilt_kernel(FiltArgs g) {
     }
 }
 
-int ecgvit_filtfilt(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
-                    int max_len, const double *b, const double *a, const double *zi, int ntaps, void *workspace, void *stream) {
-    if (!dn_store_ok(x, src_off, raw_len, R, C, max_len) || !out || (reinterpret_cast<uintptr_t>(out) & 3u) || !workspace ||
+// both entry points: the same kernel, so a record's bits are the same from either; only the cap of max_len differs
+static int ff_launch(int cap, const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
+                     int max_len, const double *b, const double *a, const double *zi, int ntaps, void *workspace, void *stream) {
+    if (!dn_store_ok(x, src_off, raw_len, R, C, max_len, cap) || !out || (reinterpret_cast<uintptr_t>(out) & 3u) || !workspace ||
         (reinterpret_cast<uintptr_t>(workspace) & 7u) || !b || !a || ntaps < 1 || ntaps > DN_MAX_TAPS || (ntaps > 1 && !zi))
         return ECGVIT_EINVAL;
     if (min_len <= 3 * ntaps || min_len > max_len) return ECGVIT_EINVAL;      // where scipy raises: the run must be longer than padlen
@@ -121,6 +127,15 @@ int ecgvit_filtfilt(const float *x, float *out, const int64_t *src_off, int64_t 
     hipLaunchKernelGGL(filtfilt_kernel, dim3(R, C), dim3(FF_THREADS), 0, as_stream(stream), g);
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
+}
+
+int ecgvit_filtfilt(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
+                    int max_len, const double *b, const double *a, const double *zi, int ntaps, void *workspace, void *stream) {
+    return ff_launch(DN_MAX_LEN, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, b, a, zi, ntaps, workspace, stream);
+}
+int ecgvit_filtfilt_long(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
+                         int max_len, const double *b, const double *a, const double *zi, int ntaps, void *workspace, void *stream) {
+    return ff_launch(DN_MAX_LEN_TILED, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, b, a, zi, ntaps, workspace, stream);
 }
 
 // =====================================================================================================
@@ -210,15 +225,24 @@ __global__ __launch_bounds__(SG_THREADS) void nlm_sigma_kernel(const float *__re
     if (tid == 0) sigma[(int64_t)r * C + c] = s;
 }
 
-int ecgvit_nlm_sigma(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len, double *sigma,
+static int sg_launch(int cap, const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len, double *sigma,
                      void *workspace, void *stream) {
-    if (!dn_store_ok(x, src_off, raw_len, R, C, max_len) || !sigma || (reinterpret_cast<uintptr_t>(sigma) & 7u) || !workspace ||
+    if (!dn_store_ok(x, src_off, raw_len, R, C, max_len, cap) || !sigma || (reinterpret_cast<uintptr_t>(sigma) & 7u) || !workspace ||
         (reinterpret_cast<uintptr_t>(workspace) & 7u))
         return ECGVIT_EINVAL;
     hipLaunchKernelGGL(nlm_sigma_kernel, dim3(R, C), dim3(SG_THREADS), 0, as_stream(stream), x, src_off, lead_stride, raw_len, C, max_len, sigma,
                        reinterpret_cast<double *>(workspace));
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
+}
+
+int ecgvit_nlm_sigma(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len, double *sigma,
+                     void *workspace, void *stream) {
+    return sg_launch(DN_MAX_LEN, x, src_off, lead_stride, raw_len, R, C, max_len, sigma, workspace, stream);
+}
+int ecgvit_nlm_sigma_long(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len, double *sigma,
+                          void *workspace, void *stream) {
+    return sg_launch(DN_MAX_LEN_TILED, x, src_off, lead_stride, raw_len, R, C, max_len, sigma, workspace, stream);
 }
 
 // =====================================================================================================
@@ -246,6 +270,7 @@ struct NlmArgs {
     const double *sigma;
     double scale;
     int C, p, W, max_len;
+    int tile_runs;              // nlm_tiled_kernel alone: runs per workgroup
 };
 
 // one t0 for the run that starts at output sample a and holds len samples; pairs whose neighbour index falls outside [0, n) contribute 0
@@ -279,11 +304,11 @@ __device__ __forceinline__ void nlm_general(const float *s, int n, int p, int a,
 }
 
 // NLM_U consecutive t0 (t0 >= NLM_P, t0 + NLM_U - 1 + NLM_RUN - 1 + NLM_P < n): every pair in bounds, every neighbour in (0, n)
-__device__ __forceinline__ void nlm_fast(const float *s, int a, int t0, float cexp, const float (&xo)[NLM_WN], float (&acc)[NLM_RUN],
-                                         float (&z)[NLM_RUN]) {
+// win: the neighbour window's first sample, s + t0 - NLM_P
+__device__ __forceinline__ void nlm_fast(const float *win, float cexp, const float (&xo)[NLM_WN], float (&acc)[NLM_RUN], float (&z)[NLM_RUN]) {
     float xs[NLM_WN + NLM_U - 1];
 #pragma unroll
-    for (int j = 0; j < NLM_WN + NLM_U - 1; ++j) xs[j] = s[t0 - NLM_P + j];
+    for (int j = 0; j < NLM_WN + NLM_U - 1; ++j) xs[j] = win[j];
 #pragma unroll
     for (int u = 0; u < NLM_U; ++u) {
         {
@@ -352,7 +377,7 @@ template <int CAP> __global__ __launch_bounds__(NLM_MAX_THREADS) void nlm_kernel
         const int t_end = min(n - 1, a + W1);
         while (t0 <= t_end) {
             if (fast && t0 >= f_lo && t0 + NLM_U - 1 <= f_hi && t0 + NLM_U - 1 <= t_end) {
-                nlm_fast(s, a, t0, cexp, xo, acc, z);
+                nlm_fast(s + (t0 - NLM_P), cexp, xo, acc, z);
                 t0 += NLM_U;
             } else {
                 nlm_general(s, n, p, a, len, t0, cexp, acc, z);
@@ -372,7 +397,7 @@ int ecgvit_nlm_denoise(const float *x, float *out, const int64_t *src_off, int64
         return ECGVIT_EINVAL;
     NlmArgs g;
     g.x = x; g.out = out; g.src_off = src_off; g.lead_stride = lead_stride; g.raw_len = raw_len; g.sigma = sigma; g.scale = scale;
-    g.C = C; g.p = patch_wd; g.W = sch_wd; g.max_len = max_len;
+    g.C = C; g.p = patch_wd; g.W = sch_wd; g.max_len = max_len; g.tile_runs = 0;
     // one lane per run of the longest record, whole waves, at most NLM_MAX_THREADS (a lane then takes several runs)
     const int M = max_len - 2 * patch_wd - 1;
     int runs = M > 0 ? (M + NLM_RUN - 1) / NLM_RUN : 1;
@@ -381,6 +406,114 @@ int ecgvit_nlm_denoise(const float *x, float *out, const int64_t *src_off, int64
     if (max_len <= 4096) hipLaunchKernelGGL(nlm_kernel<4096>, dim3(R, C), dim3(threads), 0, as_stream(stream), g);
     else if (max_len <= 8192) hipLaunchKernelGGL(nlm_kernel<8192>, dim3(R, C), dim3(threads), 0, as_stream(stream), g);
     else hipLaunchKernelGGL(nlm_kernel<DN_MAX_LEN>, dim3(R, C), dim3(threads), 0, as_stream(stream), g);
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
+}
+
+// -----------------------------------------------------------------------------------------------------
+// non-local means, tiled along time: grid (record, lead, tile), a workgroup owns tile_runs consecutive runs of one lead and nothing keeps the
+// whole lead on the CU.  The run decomposition and the order of every sum are nlm_kernel's (the same two bodies), so the bits are its bits.
+// A lane's own window comes from global memory into registers; the neighbour side of the fast body is streamed: the workgroup walks the hull of
+// its lanes' t0 ranges in ascending chunks of NLT_CHUNK, stages x[t0c - P .. t0c + NLT_CHUNK + RUN - 1 + P) into one of two LDS buffers while it
+// computes on the other, and a lane takes the t0 of the chunk that lie in its own range (the full search: the same for every lane, so the
+// window stays one LDS broadcast).  The general body (any patch_wd, t0 near either end) reads global memory: x is not written by this launch
+// (the launcher refuses out == x); it walks the same chunks, so that both bodies keep one call site as in nlm_kernel, and stages nothing where
+// no lane takes the fast body.  Every barrier sits in loops whose bounds are uniform across the workgroup.
+// -----------------------------------------------------------------------------------------------------
+#define NLT_CHUNK 256
+#define NLT_SPAN (NLT_CHUNK + NLM_RUN - 1 + 2 * NLM_P)
+#define NLT_MAX_TILES 65535
+
+__global__ __launch_bounds__(NLM_MAX_THREADS) void nlm_tiled_kernel(NlmArgs g) {
+    __shared__ float sb[2][NLT_SPAN];
+    const int rec = blockIdx.x, c = blockIdx.y, tile = blockIdx.z, tid = threadIdx.x, nthr = blockDim.x;
+    const int n = g.raw_len[rec];
+    if (n <= 0 || n > g.max_len) return;
+    const int64_t base = g.src_off[rec] + (int64_t)c * g.lead_stride;
+    const float *__restrict__ x = g.x + base;
+    float *__restrict__ out = g.out + base;
+    const int p = g.p, M = n - 2 * p - 1;      // output samples p + 1 .. n - p - 1
+    const double sg = g.scale * g.sigma[(int64_t)rec * g.C + c];
+    const double h = 2.0 * (double)(2 * p + 1) * sg * sg;
+    const float cexp = (float)(-1.4426950408889634 / h);
+    if (M <= 0 || !(h > 0.0) || !(cexp - cexp == 0.f)) {          // copied through: every tile of the launch takes a share
+        for (int i = tile * nthr + tid; i < n; i += (int)gridDim.z * nthr) out[i] = x[i];
+        return;
+    }
+    if (tile == 0) {
+        for (int i = tid; i < p + 1; i += nthr) out[i] = x[i];
+        for (int i = n - p + tid; i < n; i += nthr) out[i] = x[i];
+    }
+    const int W = g.W <= 0 || g.W > n ? n : g.W, W1 = W - 1;
+    const int K = (M + NLM_RUN - 1) / NLM_RUN;
+    const int len = M < NLM_RUN ? M : NLM_RUN;
+    const int f_hi = p == NLM_P && M >= NLM_RUN ? n - NLM_RUN - NLM_P : -1;    // the fast body's t0 are NLM_P .. f_hi; -1: none (nlm_kernel's !fast)
+    const int k0 = tile * g.tile_runs;
+    if (k0 >= K) return;                       // a tile past this record's last run: before the first barrier
+    const int k1 = min(K, k0 + g.tile_runs);
+    for (int kp = k0; kp < k1; kp += nthr) {   // uniform: lane tid takes run kp + tid of each pass
+        const int k = kp + tid;
+        const bool live = k < k1;
+        const int first = p + 1 + k * NLM_RUN;
+        const int a = k == K - 1 ? n - p - len : first;
+        float acc[NLM_RUN], z[NLM_RUN], xo[NLM_WN];
+#pragma unroll
+        for (int r = 0; r < NLM_RUN; ++r) { acc[r] = 0.f; z[r] = 0.f; }
+        if (f_hi >= 0) {
+#pragma unroll
+            for (int j = 0; j < NLM_WN; ++j) xo[j] = live ? x[a - NLM_P + j] : 0.f;
+        }
+        const int lo = live ? max(2 - len, a - W1) : 1, hi = live ? min(n - 1, a + W1) : 0;      // the lane's own t0, as in nlm_kernel
+        // the hull of the pass's ranges: a grows with the run, so the first lane has the lowest and the last live lane the highest t0
+        const int kl = min(k1, kp + nthr) - 1;
+        const int a_f = kp == K - 1 ? n - p - len : p + 1 + kp * NLM_RUN, a_l = kl == K - 1 ? n - p - len : p + 1 + kl * NLM_RUN;
+        const int h_lo = max(2 - len, a_f - W1), h_hi = min(n - 1, a_l + W1);
+        const int nch = (h_hi - h_lo) / NLT_CHUNK + 1;              // (h_hi >= h_lo: a_f is an output sample)
+        if (f_hi >= 0)
+            for (int i = tid; i < NLT_SPAN; i += nthr) { const int gi = h_lo - NLM_P + i; sb[0][i] = (unsigned)gi < (unsigned)n ? x[gi] : 0.f; }
+        __syncthreads();
+        for (int ci = 0; ci < nch; ++ci) {
+            const int t0c = h_lo + ci * NLT_CHUNK;
+            if (f_hi >= 0 && ci + 1 < nch)          // the next chunk into the other buffer: its last readers passed the barrier below
+                for (int i = tid; i < NLT_SPAN; i += nthr) {
+                    const int gi = t0c + NLT_CHUNK - NLM_P + i;
+                    sb[(ci + 1) & 1][i] = (unsigned)gi < (unsigned)n ? x[gi] : 0.f;
+                }
+            const float *w = sb[ci & 1];
+            const int u_hi = min(hi, t0c + NLT_CHUNK - 1);
+            for (int t0 = max(lo, t0c); t0 <= u_hi; ++t0) {
+                if (t0 >= NLM_P && t0 <= f_hi) nlm_fast(w + (t0 - t0c), cexp, xo, acc, z);
+                else nlm_general(x, n, p, a, len, t0, cexp, acc, z);
+            }
+            __syncthreads();
+        }
+        if (live) {
+#pragma unroll
+            for (int r = 0; r < NLM_RUN; ++r)
+                if (r < len && a + r >= first) out[a + r] = acc[r] / (z[r] + 2.220446049250313e-16f);
+        }
+    }
+}
+
+int ecgvit_nlm_denoise_tiled(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len,
+                             const double *sigma, double scale, int patch_wd, int sch_wd, int tile_runs, void *stream) {
+    if (!dn_store_ok(x, src_off, raw_len, R, C, max_len, DN_MAX_LEN_TILED) || !out || (reinterpret_cast<uintptr_t>(out) & 3u) || !sigma ||
+        (reinterpret_cast<uintptr_t>(sigma) & 7u) || patch_wd < 1 || patch_wd > DN_MAX_LEN_TILED || sch_wd < 0 || !(scale > 0.0) ||
+        !(scale - scale == 0.0) || tile_runs < 0)
+        return ECGVIT_EINVAL;
+    if (out == x) return ECGVIT_EINVAL;        // a workgroup reads samples that another one writes
+    const int64_t M = (int64_t)max_len - 2 * (int64_t)patch_wd - 1;
+    const int runs = M > 0 ? (int)((M + NLM_RUN - 1) / NLM_RUN) : 1;
+    int tr = tile_runs == 0 ? NLM_MAX_THREADS : tile_runs;
+    if (tr > runs) tr = runs;
+    const int tiles = (runs + tr - 1) / tr;
+    if (tiles > NLT_MAX_TILES) return ECGVIT_EINVAL;
+    NlmArgs g;
+    g.x = x; g.out = out; g.src_off = src_off; g.lead_stride = lead_stride; g.raw_len = raw_len; g.sigma = sigma; g.scale = scale;
+    g.C = C; g.p = patch_wd; g.W = sch_wd; g.max_len = max_len; g.tile_runs = tr;
+    int threads = (tr + WAVE - 1) / WAVE * WAVE;
+    if (threads > NLM_MAX_THREADS) threads = NLM_MAX_THREADS;
+    hipLaunchKernelGGL(nlm_tiled_kernel, dim3(R, C, tiles), dim3(threads), 0, as_stream(stream), g);
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
 }
@@ -418,6 +551,7 @@ struct RloessArgs {
     int8_t *iters;
     double frac;
     int C, max_len, npoints, degree, robust_iters, subtract;
+    int tile_samples;           // rloess_tiled_kernel alone: output samples per workgroup
 };
 
 // the reference's force_odd(int(n * frac) - 1), as Python computes it: truncation of the f64 product, floor division by 2
@@ -535,6 +669,41 @@ template <int NV> __device__ __forceinline__ double rl_median(const RlWindow<NV>
     return (__longlong_as_double((long long)k1) + __longlong_as_double((long long)k2)) / 2.0;
 }
 
+// one output sample by one wave: window placement, the distance-weighted fit, the robust loop.  s[i - sb] holds sample i of the lead for every i
+// of the window.  -> the fit's value at j (every lane holds it); it: the robust iterations run
+template <int NV> __device__ __forceinline__ double rl_sample(const float *s, int sb, int n, int m, int half, int j, int lane, int degree, int robust_iters,
+                                                              int &it) {
+    const int lo = min(max(j - half, 0), n - m);
+    const int d = max(j - lo, lo + m - 1 - j);
+    RlWindow<NV> w;
+    w.t0 = lo + lane - j;
+    w.inv_d = 1.0 / (double)d;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const bool in = lane + 64 * v < m;
+        const double a = fabs((double)(w.t0 + 64 * v) * w.inv_d);
+        const double u = 1.0 - a * a * a;
+        w.dw[v] = in ? u * u * u : 0.0;
+        w.y[v] = in ? s[lo + lane + 64 * v - sb] : 0.f;
+        w.aerr[v] = 0.0;
+    }
+    double a0, a1, a2;
+    rl_fit<NV>(w, 0.0, degree, a0, a1, a2);
+    unsigned bad = 0u;
+    it = 0;
+    while (it < robust_iters) {
+        rl_residuals<NV>(w, m, lane, a0, a1, a2);
+        const double mad = rl_median<NV>(w, m);
+        if (!(mad >= RL_MIN_MAD)) break;
+        const unsigned now = rl_fit<NV>(w, 1.0 / (6.0 * mad), degree, a0, a1, a2);
+        const bool same = it > 0 && __ballot(now != bad) == 0ull;
+        bad = now;
+        ++it;
+        if (same) break;
+    }
+    return a0;
+}
+
 template <int NV, int CAP> __global__ __launch_bounds__(RL_THREADS) void rloess_kernel(RloessArgs g) {
     __shared__ float s[CAP];
     const int rec = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
@@ -551,36 +720,47 @@ template <int NV, int CAP> __global__ __launch_bounds__(RL_THREADS) void rloess_
     int8_t *iters = g.iters ? g.iters + ((int64_t)rec * g.C + c) * g.max_len : nullptr;
     const int lane = tid & 63, half = (m & 1) ? (m - 1) / 2 : m / 2;
     for (int j = tid >> 6; j < n; j += RL_THREADS / 64) {
-        const int lo = min(max(j - half, 0), n - m);
-        const int d = max(j - lo, lo + m - 1 - j);
-        RlWindow<NV> w;
-        w.t0 = lo + lane - j;
-        w.inv_d = 1.0 / (double)d;
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            const bool in = lane + 64 * v < m;
-            const double a = fabs((double)(w.t0 + 64 * v) * w.inv_d);
-            const double u = 1.0 - a * a * a;
-            w.dw[v] = in ? u * u * u : 0.0;
-            w.y[v] = in ? s[lo + lane + 64 * v] : 0.f;
-            w.aerr[v] = 0.0;
-        }
-        double a0, a1, a2;
-        rl_fit<NV>(w, 0.0, g.degree, a0, a1, a2);
-        unsigned bad = 0u;
-        int it = 0;
-        while (it < g.robust_iters) {
-            rl_residuals<NV>(w, m, lane, a0, a1, a2);
-            const double mad = rl_median<NV>(w, m);
-            if (!(mad >= RL_MIN_MAD)) break;
-            const unsigned now = rl_fit<NV>(w, 1.0 / (6.0 * mad), g.degree, a0, a1, a2);
-            const bool same = it > 0 && __ballot(now != bad) == 0ull;
-            bad = now;
-            ++it;
-            if (same) break;
-        }
+        int it;
+        const double a0 = rl_sample<NV>(s, 0, n, m, half, j, lane, g.degree, g.robust_iters, it);
         if (lane == 0) {
             out[j] = g.subtract ? (float)((double)s[j] - a0) : (float)a0;
+            if (iters) iters[j] = (int8_t)it;
+        }
+    }
+}
+
+// tiled along time: grid (record, lead, tile), a workgroup owns tile_samples consecutive output samples and keeps them with one window of halo on
+// either side in LDS: x[max(0, j0 - m) .. min(n, j0 + tile_samples + m)).  A sample's arithmetic reads only its window and is rl_sample's, so the
+// output and the iteration counts are rloess_kernel's bit for bit.  Other workgroups write out while this one reads x: the launcher refuses out == x.
+#define RLT_LDS 4096                // samples: a tile and two windows
+#define RLT_TILE (RLT_LDS - 2 * RL_MAX_POINTS)
+#define RLT_MAX_TILES 65535
+
+template <int NV> __global__ __launch_bounds__(RL_THREADS) void rloess_tiled_kernel(RloessArgs g) {
+    __shared__ float s[RLT_LDS];
+    const int rec = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+    const int n = g.raw_len[rec];
+    if (n <= 0 || n > g.max_len) return;
+    int m = g.frac > 0.0 ? rl_frac_points(n, g.frac) : g.npoints;
+    if (m > n) m = n;
+    if (m < g.degree + 2 || m > 64 * NV) return;
+    const int j0 = (int)blockIdx.z * g.tile_samples;
+    if (j0 >= n) return;               // a tile past this record's end: before the barrier
+    const int j1 = min(n, j0 + g.tile_samples);
+    const int s0 = max(0, j0 - m), s1 = min(n, j0 + g.tile_samples + m);
+    if (s1 - s0 > RLT_LDS) return;     // (the launcher refused a tile that does not fit with the widest window)
+    const int64_t base = g.src_off[rec] + (int64_t)c * g.lead_stride;
+    const float *x = g.x + base;
+    float *out = g.out + base;
+    for (int i = s0 + tid; i < s1; i += RL_THREADS) s[i - s0] = x[i];
+    __syncthreads();
+    int8_t *iters = g.iters ? g.iters + ((int64_t)rec * g.C + c) * g.max_len : nullptr;
+    const int lane = tid & 63, half = (m & 1) ? (m - 1) / 2 : m / 2;
+    for (int j = j0 + (tid >> 6); j < j1; j += RL_THREADS / 64) {
+        int it;
+        const double a0 = rl_sample<NV>(s, s0, n, m, half, j, lane, g.degree, g.robust_iters, it);
+        if (lane == 0) {
+            out[j] = g.subtract ? (float)((double)s[j - s0] - a0) : (float)a0;
             if (iters) iters[j] = (int8_t)it;
         }
     }
@@ -594,23 +774,57 @@ template <int CAP> static void rl_launch(int nv, dim3 grid, hipStream_t st, cons
     else hipLaunchKernelGGL((rloess_kernel<16, CAP>), grid, dim3(RL_THREADS), 0, st, g);
 }
 
-int ecgvit_rloess(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
-                  int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters, void *stream) {
-    if (!dn_store_ok(x, src_off, raw_len, R, C, max_len) || !out || (reinterpret_cast<uintptr_t>(out) & 3u) || lead_stride <= 0) return ECGVIT_EINVAL;
-    if (degree < 1 || degree > 2 || robust_iters < 0 || robust_iters > RL_MAX_ITERS || (subtract != 0 && subtract != 1)) return ECGVIT_EINVAL;
-    if (!(frac >= 0.0 && frac <= 1.0) || min_len < degree + 2 || min_len > max_len) return ECGVIT_EINVAL;
+// the checks both launchers share -> the widest window of the launch, or 0 when the call is refused
+static int rl_check(int cap, const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
+                    int max_len, int npoints, double frac, int degree, int robust_iters, int subtract) {
+    if (!dn_store_ok(x, src_off, raw_len, R, C, max_len, cap) || !out || (reinterpret_cast<uintptr_t>(out) & 3u) || lead_stride <= 0) return 0;
+    if (degree < 1 || degree > 2 || robust_iters < 0 || robust_iters > RL_MAX_ITERS || (subtract != 0 && subtract != 1)) return 0;
+    if (!(frac >= 0.0 && frac <= 1.0) || min_len < degree + 2 || min_len > max_len) return 0;
     int widest = npoints;
     if (frac > 0.0) {          // the window of the shortest and of the longest record: a fraction's width grows with the length
         widest = rl_frac_points(max_len, frac);
-        if (rl_frac_points(min_len, frac) < degree + 2) return ECGVIT_EINVAL;
+        if (rl_frac_points(min_len, frac) < degree + 2) return 0;
     }
-    if (widest < degree + 2 || widest > RL_MAX_POINTS) return ECGVIT_EINVAL;
+    if (widest < degree + 2 || widest > RL_MAX_POINTS) return 0;
+    return min(widest, max_len);
+}
+
+int ecgvit_rloess(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
+                  int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters, void *stream) {
+    const int widest = rl_check(DN_MAX_LEN, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, npoints, frac, degree, robust_iters, subtract);
+    if (widest <= 0) return ECGVIT_EINVAL;
     RloessArgs g;
     g.x = x; g.out = out; g.src_off = src_off; g.lead_stride = lead_stride; g.raw_len = raw_len; g.iters = iters; g.frac = frac;
-    g.C = C; g.max_len = max_len; g.npoints = npoints; g.degree = degree; g.robust_iters = robust_iters; g.subtract = subtract;
-    const int nv = (min(widest, max_len) + 63) / 64;
+    g.C = C; g.max_len = max_len; g.npoints = npoints; g.degree = degree; g.robust_iters = robust_iters; g.subtract = subtract; g.tile_samples = 0;
+    const int nv = (widest + 63) / 64;
     if (max_len <= 8192) rl_launch<8192>(nv, dim3(R, C), as_stream(stream), g);
     else rl_launch<DN_MAX_LEN>(nv, dim3(R, C), as_stream(stream), g);
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
+}
+
+int ecgvit_rloess_tiled(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
+                        int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters, int tile_samples,
+                        void *stream) {
+    const int widest = rl_check(DN_MAX_LEN_TILED, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, npoints, frac, degree, robust_iters,
+                                subtract);
+    if (widest <= 0 || tile_samples < 0) return ECGVIT_EINVAL;
+    if (out == x) return ECGVIT_EINVAL;        // a workgroup reads samples that another one writes
+    const int T = tile_samples == 0 ? RLT_TILE : tile_samples;
+    if (T > RLT_LDS || T + 2 * widest > RLT_LDS) return ECGVIT_EINVAL;
+    const int tiles = (max_len + T - 1) / T;
+    if (tiles > RLT_MAX_TILES) return ECGVIT_EINVAL;
+    RloessArgs g;
+    g.x = x; g.out = out; g.src_off = src_off; g.lead_stride = lead_stride; g.raw_len = raw_len; g.iters = iters; g.frac = frac;
+    g.C = C; g.max_len = max_len; g.npoints = npoints; g.degree = degree; g.robust_iters = robust_iters; g.subtract = subtract; g.tile_samples = T;
+    const int nv = (widest + 63) / 64;
+    const dim3 grid(R, C, tiles);
+    hipStream_t st = as_stream(stream);
+    if (nv <= 1) hipLaunchKernelGGL(rloess_tiled_kernel<1>, grid, dim3(RL_THREADS), 0, st, g);
+    else if (nv <= 2) hipLaunchKernelGGL(rloess_tiled_kernel<2>, grid, dim3(RL_THREADS), 0, st, g);
+    else if (nv <= 4) hipLaunchKernelGGL(rloess_tiled_kernel<4>, grid, dim3(RL_THREADS), 0, st, g);
+    else if (nv <= 8) hipLaunchKernelGGL(rloess_tiled_kernel<8>, grid, dim3(RL_THREADS), 0, st, g);
+    else hipLaunchKernelGGL(rloess_tiled_kernel<16>, grid, dim3(RL_THREADS), 0, st, g);
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
 }

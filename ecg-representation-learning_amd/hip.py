@@ -25,6 +25,7 @@ KERNEL_NONE, KERNEL_GEMM_F32, KERNEL_GEMM_BF16, KERNEL_GEMM_NT, KERNEL_GEMM_WGRA
 POOL_CLS, POOL_MEAN = 0, 1   # ecgvit_pool_records modes
 FIT_TARGETS, FIT_BINS = 16, 256   # ecgvit_fit_histogram / ecgvit_fit_select: targets per lead, bins per pass
 DENOISE_MAX_LEN, DENOISE_MAX_TAPS = 32768, 9   # ecgvit_filtfilt / ecgvit_nlm_*: samples per record, filter taps
+DENOISE_MAX_LEN_TILED = 1 << 25   # ecgvit_*_long / ecgvit_*_tiled: samples per record
 DENOISE_MAX_POINTS = 1024   # ecgvit_rloess: samples per regression window
 
 _ERR = {1: 'ECGVIT_EINVAL (unsupported shape / argument)', 2: 'ECGVIT_ELAUNCH (HIP launch failure)'}
@@ -139,6 +140,11 @@ SIGNATURES = {
     'ecgvit_nlm_sigma': (c_int, [_P, _P, _L, _P, _I, _I, _I, _P, _P, _P]),
     'ecgvit_nlm_denoise': (c_int, [_P, _P, _P, _L, _P, _I, _I, _I, _P, _D, _I, _I, _P]),
     'ecgvit_rloess': (c_int, [_P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _P]),
+    'ecgvit_denoise_workspace_long': (c_int64, [_I, _I, _I]),
+    'ecgvit_filtfilt_long': (c_int, [_P, _P, _P, _L, _P, _I, _I, _I, _I, POINTER(c_double), POINTER(c_double), POINTER(c_double), _I, _P, _P]),
+    'ecgvit_nlm_sigma_long': (c_int, [_P, _P, _L, _P, _I, _I, _I, _P, _P, _P]),
+    'ecgvit_nlm_denoise_tiled': (c_int, [_P, _P, _P, _L, _P, _I, _I, _I, _P, _D, _I, _I, _I, _P]),
+    'ecgvit_rloess_tiled': (c_int, [_P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _I, _P]),
 }
 
 _lib = None

@@ -553,8 +553,8 @@ int ecgvit_tok_decode(float *out, const int64_t *src_off, int64_t lead_stride, c
  * the Zheng et al. denoiser (denoise.py; the reference's preprocess/data_preprocessor.py:22-148 and its MATLAB twin): zero-phase low-pass, robust
  * LOESS baseline, noise estimate, non-local means.  Additive entry points: the ABI version stays 6.
  * The store is addressed as ecgvit_fit_moments addresses it (x, src_off, lead_stride, raw_len; raw_len[r] <= 0 skips a record; a record starts
- * at any 4-byte address).  max_len: the caller's upper bound of raw_len, at most 32768 (the non-local means keeps a lead in LDS); a record longer
- * than max_len is left untouched.  out: the store's own layout (lead c of record r at out + src_off[r] + c * lead_stride); out == x runs in
+ * at any 4-byte address).  max_len: the caller's upper bound of raw_len, at most 32768 (the non-local means and the robust LOESS keep a lead in
+ * LDS; the _long / _tiled entry points at the end of this section take up to 1 << 25); a record longer than max_len is left untouched.  out: the store's own layout (lead c of record r at out + src_off[r] + c * lead_stride); out == x runs in
  * place, any other overlap is the caller's error.  Only the selected records' raw_len samples are written.  One workgroup per (record, lead);
  * every sum runs in an order that is a function of the record's own length and of the parameters alone, without floating-point atomics: a
  * record's output has the same bits in a rectangle, a ragged store or a subset, alone or in a batch.  NaN input is not supported.
@@ -613,6 +613,40 @@ int ecgvit_nlm_denoise(const float *x, float *out, const int64_t *src_off, int64
  * equations by elimination without pivoting; the value at j is the constant coefficient.  The median is an exact order statistic. */
 int ecgvit_rloess(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
                   int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters, void *stream);
+
+/* ---- records longer than 32768 samples (Holter length): the same stages with max_len up to 1 << 25 = 33554432 samples (24 hours at 360 Hz).
+ * Additive entry points: the ABI version stays 6.  The store is addressed as above; every per-record index that multiplies by max_len is 64-bit.
+ * The entry points above keep their cap of 32768 and their behaviour; these are opt-in and run short records too.
+ * ecgvit_denoise_workspace_long, ecgvit_filtfilt_long, ecgvit_nlm_sigma_long: the formula, the arguments and THE KERNELS of
+ * ecgvit_denoise_workspace, ecgvit_filtfilt and ecgvit_nlm_sigma (one launcher each, two caps): a record's bits are the same from either entry
+ * point.  Both kernels stage the lead through LDS in chunks and keep their f64 intermediates in `workspace`; the recurrence is walked by one
+ * lane (a block-parallel IIR would change the bits). */
+int64_t ecgvit_denoise_workspace_long(int R, int C, int max_len);
+int ecgvit_filtfilt_long(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
+                         int max_len, const double *b, const double *a, const double *zi, int ntaps, void *workspace, void *stream);
+int ecgvit_nlm_sigma_long(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len, double *sigma,
+                          void *workspace, void *stream);
+/* ecgvit_nlm_denoise tiled along time: grid (R, C, tiles), a workgroup owns tile_runs consecutive runs of 15 output samples of one lead
+ * (tile_runs == 0: 512, one run per lane of a 512-lane workgroup; more runs than the longest record holds are clamped to that).  The run
+ * decomposition is ecgvit_nlm_denoise's: run k starts at p + 1 + 15 k, the last run is moved back to end on n - p - 1, a lane owns whole runs and
+ * adds the shifts in ascending order, d is summed afresh at the start of each (run, shift) and slides within the run.  A lane's own window is
+ * loaded from global memory; the neighbour side is streamed through LDS in ascending chunks of 256 shifts, double-buffered.
+ * CONTRACT: the order of every sum is a function of n, p and W alone, so the output is bit-identical to ecgvit_nlm_denoise for every
+ * n <= 32768 and every tile_runs.
+ * out == x is REFUSED (ECGVIT_EINVAL): a workgroup reads samples that another workgroup writes, where ecgvit_nlm_denoise loads the lead before
+ * its first store.  Also refused: tile_runs < 0, patch_wd > 1 << 25, and a tile_runs so small that max_len needs more than 65535 tiles. */
+int ecgvit_nlm_denoise_tiled(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len,
+                             const double *sigma, double scale, int patch_wd, int sch_wd, int tile_runs, void *stream);
+/* ecgvit_rloess tiled along time: grid (R, C, tiles), a workgroup owns tile_samples consecutive output samples [j0, j0 + tile_samples) and
+ * loads x[max(0, j0 - m) .. min(n, j0 + tile_samples + m)) into an LDS array of 4096 f32 (tile_samples == 0: 2048, which fits with two windows
+ * of the widest width, 1024).  The per-sample wave code is ecgvit_rloess's, unchanged (window placement, even-tie rule, moment sums,
+ * elimination, bit-by-bit median, `iters` bytes), and a sample's arithmetic reads only its window.
+ * CONTRACT: the output and `iters` are bit-identical to ecgvit_rloess for every n <= 32768 and every tile_samples.
+ * Refused: tile_samples < 0; tile_samples + 2 * (the launch's widest window, at most max_len) > 4096; more than 65535 tiles for max_len;
+ * out == x (as above). */
+int ecgvit_rloess_tiled(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
+                        int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters, int tile_samples,
+                        void *stream);
 
 #ifdef __cplusplus
 }

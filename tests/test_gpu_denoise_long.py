@@ -1,0 +1,252 @@
+"""GPU: the denoiser on Holter-length records (`tiled=True`: `ecgvit_filtfilt_long`, `ecgvit_nlm_sigma_long`, `ecgvit_nlm_denoise_tiled`,
+`ecgvit_rloess_tiled` of csrc/denoise.hip).
+
+Up to 32768 samples the tiled kernels are held to the resident ones bit for bit (the header's contract), for every tile: at the run counts around
+a tile's runs, at record lengths around the stream chunk of the non-local means (256 shifts: the full search of a record of n samples walks
+n + 13 of them, so n = 755, 756, 757 end a chunk, start one with a single shift, and one with two), at LOESS tiles whose halo is cut at sample 0
+and at n, in a rectangle, a ragged store and a subset.  Above 32768 samples there is no resident kernel: the stages are held to the numpy
+restatements (tests/denoise_ref.py, tests/loess_ref.py) within the bounds tests/test_gpu_denoise.py and tests/test_gpu_loess.py use at 32768.
+
+Measured on the MI355X: every tiled-against-resident comparison bit-equal.  Above the cap, non-local means against the f32 restatement over
+max |x| (bound min(1e-4, max(2^-20, 8 E32)) = 1e-4, the gate, in all four): n = 32769 1.6e-7 and 1.1e-7 (leads 0 and 11; E32 3.6e-5),
+n = 40000 8.7e-8 and 1.2e-7 (E32 4.6e-5).  Low-pass at 40000 samples: 3.0e-8 and 6.0e-8 on leads 5 and 11 against bounds of 1.0e-7 and 1.7e-7.
+Robust LOESS at 40000 samples: at most 1.2e-7 from the restatement, the f32 store's rounding included (npoints 5 and 7), every iteration count
+equal, the restatement's outlier decisions at least 4.6e-7 from the cut."""
+import numpy as np
+import pytest
+import torch
+
+import ecg_representation_learning_amd as E
+from ecg_representation_learning_amd import denoise
+import denoise_ref as R
+import loess_ref as LR
+from test_gpu_denoise import leads, guarded, bound, dev, L, RAGGED_LENGTHS, SHARED
+
+pytestmark = pytest.mark.gpu
+P = 10
+NLM_TILES = [15, 30, 960, None]
+LOESS_TILES = [64, 65, 1000, None]
+
+
+@pytest.fixture(scope='module')
+def stores():
+    rng = np.random.default_rng(11)
+    recs = [leads(rng, l) for l in RAGGED_LENGTHS]
+    rect = np.stack([recs[i] for i in SHARED])
+    off = np.concatenate([[0], np.cumsum(RAGGED_LENGTHS)])
+    return rect, np.concatenate(recs, axis=1), off
+
+
+# ---- 1. non-local means, tiled against resident -----------------------------------------------------------------
+# the issue's lengths; K = 63, 64, 65 runs (a tile of 960 samples is 64 runs; 30 samples, 2 runs: K = 1 at n = 36, 2 at 37); the chunk edges
+@pytest.mark.parametrize('n', [22, 23, 36, 37, 161, 997, 2000, 7700, 966, 981, 982, 755, 756, 757])
+def test_nlm_tiled_is_the_resident_kernel_bit_for_bit(n):
+    x = dev(np.stack([leads(np.random.default_rng(n + i), n) for i in range(2)]))
+    for pw in (10, 3):
+        for sw in (None, 40, 1):
+            want = E.nlm(x, search_width=sw, patch_width=pw)
+            if n > 2 * pw + 1 and sw is None:
+                assert not torch.equal(want, x)
+            for tile in NLM_TILES:
+                got = E.nlm(x, search_width=sw, patch_width=pw, tiled=True, tile=tile)
+                assert torch.equal(got, want), (n, pw, sw, tile, int((got != want).sum()))
+
+
+def test_nlm_tiled_layouts(stores):
+    rect_h, rag_h, off = stores
+    rect, rag = dev(rect_h), dev(rag_h)
+    for pw, sw in ((10, None), (10, 40), (3, None), (3, 1)):
+        base = E.nlm(rect, search_width=sw, patch_width=pw)
+        r_all = E.nlm(rag, offsets=off, search_width=sw, patch_width=pw)
+        for tile in NLM_TILES:
+            kw = dict(search_width=sw, patch_width=pw, tiled=True, tile=tile)
+            assert torch.equal(E.nlm(rect, **kw), base)
+            assert torch.equal(E.nlm(rect, idxs=[2, 0], **kw), E.nlm(rect, idxs=[2, 0], search_width=sw, patch_width=pw))
+            assert torch.equal(E.nlm(rag, offsets=off, **kw), r_all)             # odd 4-byte offsets, a 23-sample record beside long ones
+            assert torch.equal(E.nlm(rag, offsets=off, idxs=[4, 1], **kw), E.nlm(rag, offsets=off, idxs=[4, 1], search_width=sw, patch_width=pw))
+    sg = E.estimate_noise_std(rect)
+    assert torch.equal(E.nlm(rect, sigma=sg, tiled=True), E.nlm(rect)) and torch.equal(E.estimate_noise_std(rect, tiled=True), sg)
+    h = E.nlm(rect_h, chunk_records=2, tiled=True, tile=30)                      # a host store streams through in chunks (in place on its staging buffer)
+    assert isinstance(h, np.ndarray) and np.array_equal(h, E.nlm(rect).cpu().numpy())
+
+
+# ---- 2. robust LOESS, tiled against resident ----------------------------------------------------------------------
+@pytest.mark.parametrize('n', [5, 64, 300, 700, 3000])
+def test_rloess_tiled_is_the_resident_kernel_bit_for_bit(n):
+    x = dev(LR.signal(300 + n, n)[None])
+    for npoints in (5, 32, 500, 501, 1024):               # a record shorter than one window takes all its samples; 64-sample tiles of 700 samples:
+        for degree in (1, 2):                             # the first tile's halo is cut at sample 0, the last one's at n
+            for ri in (0, 10):
+                want, it_want = E.rloess(x, npoints, degree, ri, return_iters=True)
+                sub = E.rloess(x, npoints, degree, ri, subtract=True)
+                for tile in LOESS_TILES:
+                    got, it = E.rloess(x, npoints, degree, ri, return_iters=True, tiled=True, tile=tile)
+                    assert torch.equal(got, want) and torch.equal(it, it_want), (n, npoints, degree, ri, tile, int((got != want).sum()), int((it != it_want).sum()))
+                    assert torch.equal(E.rloess(x, npoints, degree, ri, subtract=True, tiled=True, tile=tile), sub), (n, npoints, degree, ri, tile)
+                if ri and n >= 64:
+                    assert int(it_want.max()) >= 1
+
+
+def test_rloess_tiled_layouts_and_the_fraction_form(stores):
+    lengths = (700, 333, 64)                               # the fraction form on a ragged store: windows of 209, 99 and 19 points
+    off = np.concatenate([[0], np.cumsum(lengths)])
+    rag = dev(np.concatenate([LR.signal(23 + 1000 * i, n) for i, n in enumerate(lengths)], axis=1))
+    for degree in (1, 2):
+        want, it_want = E.rloess(rag, 0.3, degree, offsets=off, return_iters=True)
+        for tile in LOESS_TILES:
+            got, it = E.rloess(rag, 0.3, degree, offsets=off, return_iters=True, tiled=True, tile=tile)
+            assert torch.equal(got, want) and torch.equal(it, it_want), (degree, tile)
+            got, it = E.rloess(rag, 0.3, degree, offsets=off, idxs=[2, 0], return_iters=True, tiled=True, tile=tile)
+            assert torch.equal(it, it_want[[2, 0]]) and torch.equal(got[:, off[2]:], want[:, off[2]:]) and torch.equal(got[:, off[1]:off[2]], rag[:, off[1]:off[2]])
+    rect_h, rag_h, roff = stores
+    rect, rg = dev(rect_h), dev(rag_h)
+    for tile in LOESS_TILES:
+        assert torch.equal(E.rloess(rect, 31, tiled=True, tile=tile), E.rloess(rect, 31))
+        assert torch.equal(E.rloess(rg, 31, offsets=roff, subtract=True, tiled=True, tile=tile), E.rloess(rg, 31, offsets=roff, subtract=True))
+    want, it_want = E.rloess(rect, 31, return_iters=True)
+    h, it_h = E.rloess(rect_h, 31, chunk_records=2, return_iters=True, tiled=True, tile=65)       # a host store, chunk by chunk
+    assert isinstance(h, np.ndarray) and np.array_equal(h, want.cpu().numpy()) and np.array_equal(it_h, it_want.cpu().numpy())
+
+
+# ---- 3. above the old cap, against the restatements -----------------------------------------------------------------
+def long_lead(seed, n):
+    x = leads(np.random.default_rng(seed), n, 1).repeat(12, axis=0)
+    x[1:] *= np.linspace(0.5, 1.5, 11, dtype=np.float32)[:, None]
+    return x
+
+
+@pytest.mark.parametrize('n', [32769, 40000])
+def test_nlm_above_the_cap(n):
+    x = long_lead(7 + n, n)
+    sg = np.array([R.est_noise_std(l.astype(np.float64)) for l in x])
+    sg_dev = E.estimate_noise_std(dev(x[None]), tiled=True)[0].cpu().numpy()
+    rel = np.abs(sg_dev - sg) / sg
+    print(f'sigma n={n}: max rel {rel.max():.3e}')
+    assert np.all(rel <= 1e-12), rel                                  # the noise estimate against est_noise_std
+    got = E.nlm(dev(x[None]), sigma=sg[None], tiled=True)[0].cpu().numpy()
+    assert np.array_equal(got[:, :P + 1], x[:, :P + 1]) and np.array_equal(got[:, n - P:], x[:, n - P:])      # the copied edge samples: bit-equal
+    K = R.n_runs(n, P)
+    # a strided sample of the runs: both ends, around a wave's span (64 runs), a workgroup's and a tile's (512 runs each by default) and the next tile's
+    runs = [0, 1, 63, 64, 511, 512, 513, 1023, 1024, 1025, 1301, K - 2, K - 1]
+    keep = R.run_samples(n, P, runs)
+    for c in (0, 11):
+        ref, f32 = R.nlm(x[c].astype(np.float64), sg[c], runs=runs), R.nlm(x[c], sg[c], dtype=np.float32, runs=runs)
+        amax = float(np.abs(x[c]).max())
+        e32 = float(np.abs(f32[keep] - ref[keep]).max()) / amax
+        err = float(np.abs(got[c][keep] - f32[keep]).max()) / amax
+        print(f'nlm n={n} lead {c}: E32 {e32:.3e}  bound {bound(e32):.3e}  kernel vs f32 restatement {err:.3e}')
+        assert err <= bound(e32), (c, err, bound(e32))
+    assert np.isfinite(got).all() and (got[:, P + 1:n - P] != x[:, P + 1:n - P]).mean() > 0.99
+    got960 = E.nlm(dev(x[None]), sigma=sg[None], tiled=True, tile=960)[0].cpu().numpy()        # another tile: the same bits above the cap too
+    assert np.array_equal(got960, got)
+
+
+def test_lowpass_above_the_cap():
+    n = 40000
+    x = long_lead(3, n)
+    b, a, zi = E.design_lowpass(500)
+    got = E.lowpass(dev(x[None]), tiled=True)[0].cpu().numpy().astype(np.float64)
+    for c in (0, 5, 11):
+        want = R.filtfilt(b, a, zi, x[c].astype(np.float64))
+        err = np.abs(got[c] - want).max()
+        print(f'lowpass n={n} lead {c}: max err {err:.3e}, bound {2.0 ** -23 * np.abs(want).max():.3e}')
+        assert np.all(np.abs(got[c] - want) <= 2.0 ** -23 * np.abs(want).max()), c
+    for fn in (E.lowpass, E.estimate_noise_std, E.nlm, E.rloess):
+        with pytest.raises(ValueError, match='32768'):                # without tiled the cap stands
+            fn(dev(x[None]))
+
+
+@pytest.mark.parametrize('npoints,degree,seed', [(5, 1, 122), (7, 2, 124)])
+def test_rloess_above_the_cap(npoints, degree, seed):
+    n = 40000
+    x = LR.signal(seed, n)
+    base, iters = E.rloess(dev(x[None]), npoints, degree, return_iters=True, tiled=True)
+    sub = E.rloess(dev(x[None]), npoints, degree, subtract=True, tiled=True)
+    base, iters, sub = base[0].cpu().numpy(), iters[0].cpu().numpy(), sub[0].cpu().numpy()
+    assert iters.shape == (12, n) and iters.dtype == np.int8
+    for c in (0, 5, 11):
+        y = x[c].astype(np.float64)
+        fit, it, margin = LR.loess_fast(y, npoints, degree, 10)
+        assert margin >= 1e-8, margin              # the restatement takes every outlier decision away from the cut (tests/test_loess.py)
+        slack = 1e-8 * float(np.abs(y).max())
+        diff = y - fit
+        print(f'rloess n={n} npoints {npoints} lead {c}: max |device - restatement| {np.abs(base[c] - fit).max():.3e}, decision margin {margin:.2e}')
+        assert np.all(np.abs(base[c] - fit) <= 2.0 ** -24 * np.abs(fit) + slack), (c, np.abs(base[c] - fit).max())
+        assert np.all(np.abs(sub[c] - diff) <= 2.0 ** -24 * np.abs(diff) + slack), (c, np.abs(sub[c] - diff).max())
+        assert np.array_equal(iters[c], it), (c, np.flatnonzero(iters[c] != it)[:8])
+
+
+# ---- 4. the _long entry points against the present ones ---------------------------------------------------------
+def test_long_entry_points_give_the_present_bits():
+    x = dev(np.stack([leads(np.random.default_rng(40 + i), 5000) for i in range(2)]))
+    assert torch.equal(E.lowpass(x, tiled=True), E.lowpass(x)) and torch.equal(E.lowpass(x, fqs=250, tiled=True), E.lowpass(x, fqs=250))
+    assert torch.equal(E.estimate_noise_std(x, tiled=True), E.estimate_noise_std(x))
+    inpl = x.clone()
+    assert E.lowpass(inpl, out=inpl, tiled=True) is inpl and torch.equal(inpl, E.lowpass(x))
+
+
+# ---- 5, 6. guards and in-place ---------------------------------------------------------------------------------
+STAGES = {'lowpass': (lambda x, **kw: E.lowpass(x, **kw), 960), 'nlm': (lambda x, **kw: E.nlm(x, **kw), 960),
+          'rloess': (lambda x, **kw: E.rloess(x, 31, **kw), 100), 'rloess_sub': (lambda x, **kw: E.rloess(x, 31, subtract=True, **kw), 100),
+          'chain': (lambda x, **kw: E.EcgDenoiser(loess_points=31)(x, baseline='rloess', **kw), 120)}
+
+
+@pytest.mark.parametrize('stage', list(STAGES))
+def test_guards_and_in_place(stores, stage):
+    """the tiles overhang every record's end (960 and 100 samples a tile, records of 161 and fewer)"""
+    rect_h, rag_h, off = stores
+    fn, tile = STAGES[stage]
+    rect, rag = dev(rect_h), dev(rag_h)
+    base = fn(rect)                                                           # the resident kernels
+    for t in (tile, None):
+        kw = dict(tiled=True, tile=t)
+        assert torch.equal(fn(rect, **kw), base) and np.array_equal(rect.cpu().numpy(), rect_h)       # the input is not modified
+        inpl = rect.clone()                                                   # in place equals out of place
+        assert fn(inpl, out=inpl, **kw) is inpl and torch.equal(inpl, base)
+        flat, out = guarded(rect.shape)                                       # a subset into a guarded out
+        fn(rect, idxs=[2, 0], out=out, **kw)
+        assert torch.equal(out[2], base[2]) and torch.equal(out[0], base[0]) and (out[1] == -7.25).all()
+        assert (flat[:256] == -7.25).all() and (flat[-256:] == -7.25).all()
+        flat, out = guarded(rag.shape)                                        # the ragged store: the records between the selected ones are its gaps
+        fn(rag, offsets=off, idxs=[4, 1], out=out, **kw)
+        o = out.cpu().numpy()
+        assert np.array_equal(o[:, off[4]:off[5]], base[2].cpu().numpy()) and np.array_equal(o[:, off[1]:off[2]], base[0].cpu().numpy())
+        mask = np.ones(rag.shape[1], bool)
+        mask[off[4]:off[5]] = mask[off[1]:off[2]] = False
+        assert (o[:, mask] == -7.25).all() and (flat[:256] == -7.25).all() and (flat[-256:] == -7.25).all()
+        flat, inpl = guarded(rag.shape)                                       # the same in place, inside guard bands
+        inpl.copy_(rag)
+        fn(inpl, offsets=off, idxs=[4, 1], out=inpl, **kw)
+        o = inpl.cpu().numpy()
+        assert np.array_equal(o[:, off[4]:off[5]], base[2].cpu().numpy()) and np.array_equal(o[:, off[1]:off[2]], base[0].cpu().numpy())
+        assert np.array_equal(o[:, mask], rag_h[:, mask]) and (flat[:256] == -7.25).all() and (flat[-256:] == -7.25).all()
+
+
+def test_in_place_launch_groups(stores, monkeypatch):
+    """more than one launch group in place: a group is the records that fit `_WS_BYTES` of f32"""
+    rect_h, rag_h, off = stores
+    rag = dev(rag_h)
+    want_n, want_l = E.nlm(rag, offsets=off), E.rloess(rag, 31, offsets=off, return_iters=True)
+    monkeypatch.setattr(denoise, '_WS_BYTES', 2 * 12 * L * 4)                 # two records a group
+    assert len(denoise._Tables(rag, off[:-1], np.diff(off), rag.shape[1]).groups()) == 3
+    a = rag.clone()
+    assert torch.equal(E.nlm(a, offsets=off, out=a, tiled=True), want_n)
+    a = rag.clone()
+    got, it = E.rloess(a, 31, offsets=off, out=a, return_iters=True, tiled=True)
+    assert got is a and torch.equal(got, want_l[0]) and torch.equal(it, want_l[1])
+
+
+# ---- 7. the chain ---------------------------------------------------------------------------------------------------
+def test_the_chain_tiled():
+    d = E.EcgDenoiser()
+    x = dev(np.stack([leads(np.random.default_rng(70 + i), 2500) for i in range(2)]))
+    want = d(x, baseline='rloess')
+    assert torch.equal(d(x, baseline='rloess', tiled=True), want) and torch.equal(d(x, baseline='rloess', tiled=True, tile=1500), want)
+    assert torch.equal(d(x, tiled=True), d(x))
+    xl = dev(long_lead(77, 40000)[None])
+    got = d(xl, baseline='rloess', tiled=True)
+    lp = E.lowpass(xl, tiled=True)
+    stages = E.nlm(E.rloess(lp, 500, subtract=True, tiled=True), tiled=True)
+    assert torch.equal(got, stages) and torch.isfinite(got).all() and not torch.equal(got, lp)
+    with pytest.raises(ValueError, match='32768'):
+        d(xl, baseline='rloess')
