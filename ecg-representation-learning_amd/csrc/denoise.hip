@@ -390,14 +390,21 @@ template <int CAP> __global__ __launch_bounds__(NLM_MAX_THREADS) void nlm_kernel
     }
 }
 
-int ecgvit_nlm_denoise(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len,
-                       const double *sigma, double scale, int patch_wd, int sch_wd, void *stream) {
-    if (!dn_store_ok(x, src_off, raw_len, R, C, max_len) || !out || (reinterpret_cast<uintptr_t>(out) & 3u) || !sigma ||
-        (reinterpret_cast<uintptr_t>(sigma) & 7u) || patch_wd < 1 || patch_wd > DN_MAX_LEN || sch_wd < 0 || !(scale > 0.0) || !(scale - scale == 0.0))
-        return ECGVIT_EINVAL;
-    NlmArgs g;
+// the checks and the arguments both launchers share -> false when the call is refused
+static bool nlm_args(NlmArgs &g, int cap, const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C,
+                     int max_len, const double *sigma, double scale, int patch_wd, int sch_wd) {
+    if (!dn_store_ok(x, src_off, raw_len, R, C, max_len, cap) || !out || (reinterpret_cast<uintptr_t>(out) & 3u) || !sigma ||
+        (reinterpret_cast<uintptr_t>(sigma) & 7u) || patch_wd < 1 || patch_wd > cap || sch_wd < 0 || !(scale > 0.0) || !(scale - scale == 0.0))
+        return false;
     g.x = x; g.out = out; g.src_off = src_off; g.lead_stride = lead_stride; g.raw_len = raw_len; g.sigma = sigma; g.scale = scale;
     g.C = C; g.p = patch_wd; g.W = sch_wd; g.max_len = max_len; g.tile_runs = 0;
+    return true;
+}
+
+int ecgvit_nlm_denoise(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len,
+                       const double *sigma, double scale, int patch_wd, int sch_wd, void *stream) {
+    NlmArgs g;
+    if (!nlm_args(g, DN_MAX_LEN, x, out, src_off, lead_stride, raw_len, R, C, max_len, sigma, scale, patch_wd, sch_wd)) return ECGVIT_EINVAL;
     // one lane per run of the longest record, whole waves, at most NLM_MAX_THREADS (a lane then takes several runs)
     const int M = max_len - 2 * patch_wd - 1;
     int runs = M > 0 ? (M + NLM_RUN - 1) / NLM_RUN : 1;
@@ -497,21 +504,16 @@ __global__ __launch_bounds__(NLM_MAX_THREADS) void nlm_tiled_kernel(NlmArgs g) {
 
 int ecgvit_nlm_denoise_tiled(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len,
                              const double *sigma, double scale, int patch_wd, int sch_wd, int tile_runs, void *stream) {
-    if (!dn_store_ok(x, src_off, raw_len, R, C, max_len, DN_MAX_LEN_TILED) || !out || (reinterpret_cast<uintptr_t>(out) & 3u) || !sigma ||
-        (reinterpret_cast<uintptr_t>(sigma) & 7u) || patch_wd < 1 || patch_wd > DN_MAX_LEN_TILED || sch_wd < 0 || !(scale > 0.0) ||
-        !(scale - scale == 0.0) || tile_runs < 0)
+    NlmArgs g;
+    if (tile_runs < 0 || !nlm_args(g, DN_MAX_LEN_TILED, x, out, src_off, lead_stride, raw_len, R, C, max_len, sigma, scale, patch_wd, sch_wd))
         return ECGVIT_EINVAL;
     if (out == x) return ECGVIT_EINVAL;        // a workgroup reads samples that another one writes
     const int64_t M = (int64_t)max_len - 2 * (int64_t)patch_wd - 1;
     const int runs = M > 0 ? (int)((M + NLM_RUN - 1) / NLM_RUN) : 1;
-    int tr = tile_runs == 0 ? NLM_MAX_THREADS : tile_runs;
-    if (tr > runs) tr = runs;
-    const int tiles = (runs + tr - 1) / tr;
+    g.tile_runs = min(tile_runs == 0 ? NLM_MAX_THREADS : tile_runs, runs);
+    const int tiles = (runs + g.tile_runs - 1) / g.tile_runs;
     if (tiles > NLT_MAX_TILES) return ECGVIT_EINVAL;
-    NlmArgs g;
-    g.x = x; g.out = out; g.src_off = src_off; g.lead_stride = lead_stride; g.raw_len = raw_len; g.sigma = sigma; g.scale = scale;
-    g.C = C; g.p = patch_wd; g.W = sch_wd; g.max_len = max_len; g.tile_runs = tr;
-    int threads = (tr + WAVE - 1) / WAVE * WAVE;
+    int threads = (g.tile_runs + WAVE - 1) / WAVE * WAVE;
     if (threads > NLM_MAX_THREADS) threads = NLM_MAX_THREADS;
     hipLaunchKernelGGL(nlm_tiled_kernel, dim3(R, C, tiles), dim3(threads), 0, as_stream(stream), g);
     ECGVIT_CHECK_LAUNCH();
@@ -766,17 +768,18 @@ template <int NV> __global__ __launch_bounds__(RL_THREADS) void rloess_tiled_ker
     }
 }
 
-template <int CAP> static void rl_launch(int nv, dim3 grid, hipStream_t st, const RloessArgs &g) {
-    if (nv <= 1) hipLaunchKernelGGL((rloess_kernel<1, CAP>), grid, dim3(RL_THREADS), 0, st, g);
-    else if (nv <= 2) hipLaunchKernelGGL((rloess_kernel<2, CAP>), grid, dim3(RL_THREADS), 0, st, g);
-    else if (nv <= 4) hipLaunchKernelGGL((rloess_kernel<4, CAP>), grid, dim3(RL_THREADS), 0, st, g);
-    else if (nv <= 8) hipLaunchKernelGGL((rloess_kernel<8, CAP>), grid, dim3(RL_THREADS), 0, st, g);
-    else hipLaunchKernelGGL((rloess_kernel<16, CAP>), grid, dim3(RL_THREADS), 0, st, g);
+// the one NV dispatch: launch(NV) with the slots a lane needs for the widest window, as a compile-time constant: 1, 2, 4, 8 or 16
+template <class F> static void rl_dispatch(int nv, F launch) {
+    if (nv <= 1) launch(std::integral_constant<int, 1>());
+    else if (nv <= 2) launch(std::integral_constant<int, 2>());
+    else if (nv <= 4) launch(std::integral_constant<int, 4>());
+    else if (nv <= 8) launch(std::integral_constant<int, 8>());
+    else launch(std::integral_constant<int, 16>());
 }
 
-// the checks both launchers share -> the widest window of the launch, or 0 when the call is refused
-static int rl_check(int cap, const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
-                    int max_len, int npoints, double frac, int degree, int robust_iters, int subtract) {
+// the checks and the arguments both launchers share -> the widest window of the launch, or 0 when the call is refused
+static int rl_args(RloessArgs &g, int cap, const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C,
+                   int min_len, int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters) {
     if (!dn_store_ok(x, src_off, raw_len, R, C, max_len, cap) || !out || (reinterpret_cast<uintptr_t>(out) & 3u) || lead_stride <= 0) return 0;
     if (degree < 1 || degree > 2 || robust_iters < 0 || robust_iters > RL_MAX_ITERS || (subtract != 0 && subtract != 1)) return 0;
     if (!(frac >= 0.0 && frac <= 1.0) || min_len < degree + 2 || min_len > max_len) return 0;
@@ -786,19 +789,22 @@ static int rl_check(int cap, const float *x, float *out, const int64_t *src_off,
         if (rl_frac_points(min_len, frac) < degree + 2) return 0;
     }
     if (widest < degree + 2 || widest > RL_MAX_POINTS) return 0;
+    g.x = x; g.out = out; g.src_off = src_off; g.lead_stride = lead_stride; g.raw_len = raw_len; g.iters = iters; g.frac = frac;
+    g.C = C; g.max_len = max_len; g.npoints = npoints; g.degree = degree; g.robust_iters = robust_iters; g.subtract = subtract; g.tile_samples = 0;
     return min(widest, max_len);
 }
 
 int ecgvit_rloess(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
                   int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters, void *stream) {
-    const int widest = rl_check(DN_MAX_LEN, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, npoints, frac, degree, robust_iters, subtract);
-    if (widest <= 0) return ECGVIT_EINVAL;
     RloessArgs g;
-    g.x = x; g.out = out; g.src_off = src_off; g.lead_stride = lead_stride; g.raw_len = raw_len; g.iters = iters; g.frac = frac;
-    g.C = C; g.max_len = max_len; g.npoints = npoints; g.degree = degree; g.robust_iters = robust_iters; g.subtract = subtract; g.tile_samples = 0;
+    const int widest = rl_args(g, DN_MAX_LEN, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, npoints, frac, degree, robust_iters, subtract,
+                               iters);
+    if (widest <= 0) return ECGVIT_EINVAL;
     const int nv = (widest + 63) / 64;
-    if (max_len <= 8192) rl_launch<8192>(nv, dim3(R, C), as_stream(stream), g);
-    else rl_launch<DN_MAX_LEN>(nv, dim3(R, C), as_stream(stream), g);
+    const dim3 grid(R, C), block(RL_THREADS);
+    hipStream_t st = as_stream(stream);
+    if (max_len <= 8192) rl_dispatch(nv, [&](auto v) { hipLaunchKernelGGL((rloess_kernel<decltype(v)::value, 8192>), grid, block, 0, st, g); });
+    else rl_dispatch(nv, [&](auto v) { hipLaunchKernelGGL((rloess_kernel<decltype(v)::value, DN_MAX_LEN>), grid, block, 0, st, g); });
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
 }
@@ -806,25 +812,18 @@ int ecgvit_rloess(const float *x, float *out, const int64_t *src_off, int64_t le
 int ecgvit_rloess_tiled(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
                         int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters, int tile_samples,
                         void *stream) {
-    const int widest = rl_check(DN_MAX_LEN_TILED, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, npoints, frac, degree, robust_iters,
-                                subtract);
+    RloessArgs g;
+    const int widest = rl_args(g, DN_MAX_LEN_TILED, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, npoints, frac, degree, robust_iters,
+                               subtract, iters);
     if (widest <= 0 || tile_samples < 0) return ECGVIT_EINVAL;
     if (out == x) return ECGVIT_EINVAL;        // a workgroup reads samples that another one writes
-    const int T = tile_samples == 0 ? RLT_TILE : tile_samples;
-    if (T > RLT_LDS || T + 2 * widest > RLT_LDS) return ECGVIT_EINVAL;
-    const int tiles = (max_len + T - 1) / T;
+    g.tile_samples = tile_samples == 0 ? RLT_TILE : tile_samples;
+    if (g.tile_samples > RLT_LDS || g.tile_samples + 2 * widest > RLT_LDS) return ECGVIT_EINVAL;
+    const int tiles = (max_len + g.tile_samples - 1) / g.tile_samples;
     if (tiles > RLT_MAX_TILES) return ECGVIT_EINVAL;
-    RloessArgs g;
-    g.x = x; g.out = out; g.src_off = src_off; g.lead_stride = lead_stride; g.raw_len = raw_len; g.iters = iters; g.frac = frac;
-    g.C = C; g.max_len = max_len; g.npoints = npoints; g.degree = degree; g.robust_iters = robust_iters; g.subtract = subtract; g.tile_samples = T;
-    const int nv = (widest + 63) / 64;
-    const dim3 grid(R, C, tiles);
+    const dim3 grid(R, C, tiles), block(RL_THREADS);
     hipStream_t st = as_stream(stream);
-    if (nv <= 1) hipLaunchKernelGGL(rloess_tiled_kernel<1>, grid, dim3(RL_THREADS), 0, st, g);
-    else if (nv <= 2) hipLaunchKernelGGL(rloess_tiled_kernel<2>, grid, dim3(RL_THREADS), 0, st, g);
-    else if (nv <= 4) hipLaunchKernelGGL(rloess_tiled_kernel<4>, grid, dim3(RL_THREADS), 0, st, g);
-    else if (nv <= 8) hipLaunchKernelGGL(rloess_tiled_kernel<8>, grid, dim3(RL_THREADS), 0, st, g);
-    else hipLaunchKernelGGL(rloess_tiled_kernel<16>, grid, dim3(RL_THREADS), 0, st, g);
+    rl_dispatch((widest + 63) / 64, [&](auto v) { hipLaunchKernelGGL(rloess_tiled_kernel<decltype(v)::value>, grid, block, 0, st, g); });
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
 }

@@ -1,8 +1,8 @@
 """
 The reference's Zheng et al. denoiser (`ecg_transformer/preprocess/data_preprocessor.py:22-148`, MATLAB twin `preprocess_matlab/DataPreprocessor.m`
 and `nlm.m`) on the device: zero-phase Butterworth low-pass, the robust LOESS baseline it subtracts, the noise estimate and non-local means,
-the stage that writes the `*-denoised.hdf5` files every reference run trains on.  The sweeps are HIP kernels (`csrc/denoise.hip`) over the record stores `fit_dynamic_normalize` and
-`EcgTokenizer` take: (n, 12, L) float32 records, a ragged (12, S_total) store with `offsets`, a subset `idxs` of either.  A device store is
+the stage that writes the `*-denoised.hdf5` files every reference run trains on.  The sweeps are HIP kernels (`csrc/denoise.hip`) over the record stores of `records.py`, which
+`fit_dynamic_normalize` and `EcgTokenizer` take too: (n, 12, L) float32 records, a ragged (12, S_total) store with `offsets`, a subset `idxs` of either.  A device store is
 processed where it lies -- in place with `out=records`, into `out=`, or (default) into a new tensor that starts as a copy, so records outside
 `idxs` carry over; a host array / memmap streams through the device `chunk_records` records at a time and comes back as a float32 numpy array.
 There is no CPU fallback.
@@ -32,7 +32,7 @@ import math
 import numpy as np
 import torch
 
-from .transform import _record_tables
+from .records import DeviceTables, RecordSelection, check_device_store, host_chunks, select_records
 
 MAX_LEN = 32768            # samples per record: the resident non-local means and LOESS keep a lead in LDS
 MAX_LEN_TILED = 1 << 25    # samples per record with tiled=True (24 hours at 360 Hz)
@@ -44,7 +44,7 @@ _MAX_TILES = 65535         # tiles per lead (the grid's third dimension)
 MAX_TAPS = 9
 MAX_POINTS = 1024          # samples per LOESS window: covers every sampling rate of the reference's config (250, 257, 500, 1000)
 MAX_ROBUST_ITERS = 10
-C = 12                     # leads per record: what `_record_tables` admits
+C = 12                     # leads per record: what `select_records` admits
 _WS_BYTES = 256 * 2 ** 20  # f64 intermediates of the low-pass / noise estimate per launch: more records go in several launches
 
 
@@ -113,36 +113,32 @@ def _dp(arr):
 
 
 # ---- stores ---------------------------------------------------------------------------------------------------------------------------
-class _Tables:
-    """the device tables of the selected records of one device store"""
+_ENTRY = {   # by `tiled`: the entry points that differ only in their cap, under the names `check` reports
+    False: dict(workspace='ecgvit_denoise_workspace', filtfilt='ecgvit_filtfilt', sigma='ecgvit_nlm_sigma'),
+    True: dict(workspace='ecgvit_denoise_workspace_long', filtfilt='ecgvit_filtfilt_long', sigma='ecgvit_nlm_sigma_long')}
 
-    def __init__(self, x, src_off, raw_len, stride):
-        self.x, self.R, self.stride = x, len(raw_len), int(stride)
-        self.src_off_h, self.raw_len_h = np.ascontiguousarray(src_off, np.int64), np.ascontiguousarray(raw_len, np.int64)
-        self.src_off = torch.from_numpy(self.src_off_h.copy()).to(x.device)
-        self.raw_len = torch.from_numpy(self.raw_len_h.astype(np.int32)).to(x.device)
-        self.min_len, self.max_len = int(self.raw_len_h.min()), int(self.raw_len_h.max())
 
-    def launches(self, tiled=False):
-        """(first record, records) per launch, so that the f64 workspace of a launch stays within _WS_BYTES"""
-        from .hip import lib
-        size = lib().ecgvit_denoise_workspace_long if tiled else lib().ecgvit_denoise_workspace
-        step = max(1, _WS_BYTES // size(1, C, self.max_len))
-        return [(lo, min(step, self.R - lo)) for lo in range(0, self.R, step)]
+def launches(tab, entry):
+    """(first record, records) per launch over the `DeviceTables` tab, so that the f64 workspace of a launch stays within _WS_BYTES"""
+    from .hip import lib
+    step = max(1, _WS_BYTES // getattr(lib(), entry['workspace'])(1, C, tab.max_len))
+    return [(lo, min(step, tab.R - lo)) for lo in range(0, tab.R, step)]
 
-    def groups(self):
-        """(first record, records) per launch group of a tiled stage that runs in place: each of the group's two f32 scratch stores stays within
-        _WS_BYTES (at 462 600 samples: 12 records)"""
-        step = max(1, _WS_BYTES // (4 * C * self.max_len))
-        return [(lo, min(step, self.R - lo)) for lo in range(0, self.R, step)]
 
-    def compact(self, lo, cnt):
-        """the records lo .. lo + cnt as a compact (12, S) store -> (its offsets as a device table, S, the store column of every compact column)"""
-        lens, src = self.raw_len_h[lo:lo + cnt], self.src_off_h[lo:lo + cnt]
-        off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
-        S = int(lens.sum())
-        cols = np.repeat(src - off, lens) + np.arange(S, dtype=np.int64)
-        return torch.from_numpy(off).to(self.x.device), S, torch.from_numpy(cols).to(self.x.device)
+def groups(tab):
+    """(first record, records) per launch group of a tiled stage that runs in place: each of the group's two f32 scratch stores stays within
+    _WS_BYTES (at 462 600 samples: 12 records)"""
+    step = max(1, _WS_BYTES // (4 * C * tab.max_len))
+    return [(lo, min(step, tab.R - lo)) for lo in range(0, tab.R, step)]
+
+
+def compact(tab, lo, cnt):
+    """the records lo .. lo + cnt as a compact (12, S) store -> (its offsets as a device table, S, the store column of every compact column)"""
+    lens, src = tab.raw_len_h[lo:lo + cnt], tab.src_off_h[lo:lo + cnt]
+    off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    S = int(lens.sum())
+    cols = np.repeat(src - off, lens) + np.arange(S, dtype=np.int64)
+    return torch.from_numpy(off).to(tab.x.device), S, torch.from_numpy(cols).to(tab.x.device)
 
 
 def _tiled_groups(x, o, tab, launch):
@@ -152,31 +148,13 @@ def _tiled_groups(x, o, tab, launch):
         launch(x, o, tab.src_off, tab.stride, 0, tab.R)
         return
     flat_x, flat_o = x.view(-1), o.view(-1)
-    for lo, cnt in tab.groups():
-        off, S, cols = tab.compact(lo, cnt)
+    for lo, cnt in groups(tab):
+        off, S, cols = compact(tab, lo, cnt)
         a = torch.stack([flat_x[cols + c * tab.stride] for c in range(C)])
         b = a.clone()           # (a lead the kernel leaves alone keeps its samples)
         launch(a, b, off, S, lo, cnt)
         for c in range(C):
             flat_o[cols + c * tab.stride] = b[c]
-
-
-def _check_device_store(records, what='records'):
-    if records.dtype != torch.float32:
-        raise ValueError(f'{what} must be float32, got {records.dtype}')
-    if not records.is_cuda:
-        raise ValueError(f'{what} must be a device tensor or a host array (a host TENSOR is taken as a host array only as `records`)')
-    if not records.is_contiguous():
-        raise ValueError(f'{what} must be contiguous')
-
-
-def _check_lengths(raw_len, min_len=1, tiled=False):
-    if tiled and int(raw_len.max()) > MAX_LEN_TILED:
-        raise ValueError(f'a record of {int(raw_len.max())} samples: at most {MAX_LEN_TILED} are supported with tiled=True')
-    if not tiled and int(raw_len.max()) > MAX_LEN:
-        raise ValueError(f'a record of {int(raw_len.max())} samples: at most {MAX_LEN} are supported (tiled=True takes up to {MAX_LEN_TILED})')
-    if int(raw_len.min()) < min_len:
-        raise ValueError(f'a record of {int(raw_len.min())} samples: this stage needs at least {min_len}')
 
 
 def _check_tile(tiled, tile, multiple=1):
@@ -200,7 +178,7 @@ def _resolve_out(records, out):
         raise ValueError('out must be a device tensor')
     if out is records:
         return out
-    _check_device_store(out, 'out')
+    check_device_store(out, 'out')
     if out.shape != records.shape or out.device != records.device:
         raise ValueError(f'out must have the shape and device of records, got {tuple(out.shape)} on {out.device}')
     if out.data_ptr() == records.data_ptr():
@@ -211,85 +189,62 @@ def _resolve_out(records, out):
     return out
 
 
-def _host_chunks(records, rect, src_off, raw_len, sel, chunk_records, device):
-    """-> per chunk (device buffer, _Tables, scatter): the selected records, `chunk_records` at a time, as a compact device store of the same form;
-    scatter(host_out, buffer) writes the chunk's records back where they came from"""
-    if chunk_records is None:   # about 256 MB of f32 per chunk
-        chunk_records = max(1, int(64 * 2 ** 20 // (C * max(1, int(raw_len.max())))))
-    step = int(chunk_records)
-    for lo in range(0, len(sel), step):
-        ids, lens, srcs = sel[lo:lo + step], raw_len[lo:lo + step], src_off[lo:lo + step]
-        if rect:
-            L = int(lens[0])
-            buf = np.ascontiguousarray(records[ids], dtype=np.float32)
-            off, stride = np.arange(len(ids), dtype=np.int64) * (C * L), L
-
-            def scatter(host_out, dev, ids=ids):
-                host_out[ids] = dev.cpu().numpy()
-        else:
-            S = int(lens.sum())
-            buf = np.empty((C, S), np.float32)
-            off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
-            for o, s, l in zip(off.tolist(), srcs.tolist(), lens.tolist()):
-                buf[:, o:o + l] = records[:, s:s + l]
-            stride = S
-
-            def scatter(host_out, dev, off=off, srcs=srcs, lens=lens):
-                h = dev.cpu().numpy()
-                for o, s, l in zip(off.tolist(), srcs.tolist(), lens.tolist()):
-                    host_out[:, s:s + l] = h[:, o:o + l]
-        x = torch.from_numpy(buf).to(device)
-        yield x, _Tables(x, off, lens, stride), scatter
+def _resolve(records, offsets, idxs, min_len=1, tiled=False, unique=(True, False)):
+    """The one resolution of a public call -> (the store: a device tensor or a host array, its `RecordSelection`), the store and the lengths
+    checked.  unique: whether an `idxs` that repeats a record is refused, for (a device store, a host store).  idxs: a `RecordSelection` is
+    taken as it is: what `EcgDenoiser` resolved for a store of this layout, `offsets` and repeats included."""
+    on_device = isinstance(records, torch.Tensor) and records.is_cuda
+    if on_device:
+        check_device_store(records)
+    else:
+        records = records.numpy() if isinstance(records, torch.Tensor) else records
+        if not hasattr(records, 'shape') or not hasattr(records, 'dtype') or not np.issubdtype(records.dtype, np.floating):
+            raise ValueError('records must be a float32 device tensor or a host array / memmap / tensor of a float type')
+    s = idxs if isinstance(idxs, RecordSelection) else select_records(records, offsets, idxs, unique=unique[not on_device])
+    if tiled and s.max_len > MAX_LEN_TILED:
+        raise ValueError(f'a record of {s.max_len} samples: at most {MAX_LEN_TILED} are supported with tiled=True')
+    if not tiled and s.max_len > MAX_LEN:
+        raise ValueError(f'a record of {s.max_len} samples: at most {MAX_LEN} are supported (tiled=True takes up to {MAX_LEN_TILED})')
+    if s.min_len < min_len:
+        raise ValueError(f'a record of {s.min_len} samples: this stage needs at least {min_len}')
+    return records, s
 
 
-def _sweep(records, offsets, idxs, out, chunk_records, min_len, stage, tables=None, tiled=False):
-    """Run `stage(x, out, tables, first selected record)` over the selected records.  Device store: one call, returns the output tensor.  Host
-    store: chunk by chunk in place on a staging buffer, returns a float32 numpy array (a copy of the input with the selected records replaced;
-    `out`, a float32 array of the same shape, is filled instead when given).  tables: what `_record_tables` gave a caller that had to check the
-    selection before (the lengths are then the caller's to check)."""
-    if isinstance(records, torch.Tensor) and records.is_cuda:
-        _check_device_store(records)
-        rect, n, _, src_off, raw_len, stride, sel = tables or _record_tables(records, offsets, idxs)
-        if tables is None:
-            _check_lengths(raw_len, min_len, tiled)
-        if len(np.unique(sel)) != len(sel):
-            raise ValueError('idxs repeats a record: two workgroups would write the same samples')
-        out = _resolve_out(records, out)
+def _sweep(records, s, out, chunk_records, stage):
+    """Run `stage(x, out, tables, first selected record)` over the records `_resolve` selected.  Device store: one call, returns the output
+    tensor.  Host store: chunk by chunk in place on a staging buffer, returns a float32 numpy array (a copy of the input with the selected
+    records replaced; `out`, a float32 array of the same shape, is filled instead when given).  out=False: a stage that only reads; it gets
+    None for a device store, and nothing comes back from the device for a host one."""
+    if isinstance(records, torch.Tensor):
+        out = None if out is False else _resolve_out(records, out)
         with torch.cuda.device(records.device):
-            stage(records, out, _Tables(records, src_off, raw_len, stride), 0)
+            stage(records, out, DeviceTables.of(records, s), 0)
         return out
-    host = records.numpy() if isinstance(records, torch.Tensor) else records
-    if not hasattr(host, 'shape') or not hasattr(host, 'dtype') or not np.issubdtype(host.dtype, np.floating):
-        raise ValueError('records must be a float32 device tensor or a host array / memmap / tensor of a float type')
-    rect, n, _, src_off, raw_len, stride, sel = tables or _record_tables(host, offsets, idxs)
-    if tables is None:
-        _check_lengths(raw_len, min_len, tiled)
     if out is not None and out is not False:
-        if not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.shape != host.shape:
+        if not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.shape != records.shape:
             raise ValueError('for a host store, out must be a float32 numpy array of the same shape')
-    if chunk_records is not None and int(chunk_records) < 1:
-        raise ValueError('chunk_records must be at least 1')
+    chunks = host_chunks(records, s, chunk_records)
     if not torch.cuda.is_available():
         raise RuntimeError('the denoiser runs on the device (no CPU fallback exists)')
     if out is None:
-        out = np.array(host, dtype=np.float32)
+        out = np.array(records, dtype=np.float32)
     device = torch.device('cuda')
     first = 0
     with torch.cuda.device(device):
-        for x, tab, scatter in _host_chunks(host, rect, src_off, raw_len, sel, chunk_records, device):
-            stage(x, x, tab, first)
+        for buf, off, lens, stride, scatter in chunks:
+            x = torch.from_numpy(buf).to(device)
+            stage(x, x, DeviceTables(x, off, lens, stride), first)
             if out is not False:
-                scatter(out, x)
-            first += tab.R
+                scatter(out, x.cpu().numpy())
+            first += len(lens)
     return out
 
 
-# ---- the three stages -----------------------------------------------------------------------------------------------------------------
-def _workspace(tab, device, tiled=False):
+# ---- the stages -----------------------------------------------------------------------------------------------------------------------
+def _workspace(tab, device, entry):
     from .hip import lib
-    R = max(cnt for _, cnt in tab.launches(tiled))
-    size = lib().ecgvit_denoise_workspace_long if tiled else lib().ecgvit_denoise_workspace
-    return torch.empty(size(R, C, tab.max_len) // 8, dtype=torch.float64, device=device)
+    R = max(cnt for _, cnt in launches(tab, entry))
+    return torch.empty(getattr(lib(), entry['workspace'])(R, C, tab.max_len) // 8, dtype=torch.float64, device=device)
 
 
 def lowpass_taps(records, b, a, zi=None, offsets=None, idxs=None, out=None, chunk_records=None, tiled=False, tile=None):
@@ -300,14 +255,14 @@ def lowpass_taps(records, b, a, zi=None, offsets=None, idxs=None, out=None, chun
     from .hip import lib, check, ptr, stream
     b, a, zi, nt = _taps(b, a, zi)
     _check_tile(tiled, tile)
+    entry = _ENTRY[tiled]
 
     def stage(x, o, tab, first):
-        ws = _workspace(tab, x.device, tiled)
-        fn, name = (lib().ecgvit_filtfilt_long, 'ecgvit_filtfilt_long') if tiled else (lib().ecgvit_filtfilt, 'ecgvit_filtfilt')
-        for lo, cnt in tab.launches(tiled):
-            check(fn(ptr(x), ptr(o), ptr(tab.src_off[lo:]), tab.stride, ptr(tab.raw_len[lo:]), cnt, C, tab.min_len, tab.max_len,
-                     _dp(b), _dp(a), _dp(zi), nt, ptr(ws), stream()), name)
-    return _sweep(records, offsets, idxs, out, chunk_records, 3 * nt + 1, stage, tiled=tiled)
+        ws = _workspace(tab, x.device, entry)
+        for lo, cnt in launches(tab, entry):
+            check(getattr(lib(), entry['filtfilt'])(ptr(x), ptr(o), ptr(tab.src_off[lo:]), tab.stride, ptr(tab.raw_len[lo:]), cnt, C, tab.min_len,
+                                                    tab.max_len, _dp(b), _dp(a), _dp(zi), nt, ptr(ws), stream()), entry['filtfilt'])
+    return _sweep(*_resolve(records, offsets, idxs, 3 * nt + 1, tiled), out, chunk_records, stage)
 
 
 def lowpass(records, fqs=500, passband=50, stopband=60, passband_ripple=1, stopband_attenuation=2.5, offsets=None, idxs=None, out=None,
@@ -318,23 +273,25 @@ def lowpass(records, fqs=500, passband=50, stopband=60, passband_ripple=1, stopb
     return lowpass_taps(records, b, a, zi, offsets=offsets, idxs=idxs, out=out, chunk_records=chunk_records, tiled=tiled, tile=tile)
 
 
+def _sigma_of(x, tab, tiled=False):
+    """the noise estimate over exactly the records of `tab` (a device store)"""
+    from .hip import lib, check, ptr, stream
+    entry = _ENTRY[tiled]
+    sig = torch.zeros((tab.R, C), dtype=torch.float64, device=x.device)
+    ws = _workspace(tab, x.device, entry)
+    for lo, cnt in launches(tab, entry):
+        check(getattr(lib(), entry['sigma'])(ptr(x), ptr(tab.src_off[lo:]), tab.stride, ptr(tab.raw_len[lo:]), cnt, C, tab.max_len, ptr(sig[lo:]),
+                                             ptr(ws), stream()), entry['sigma'])
+    return sig
+
+
 def estimate_noise_std(records, offsets=None, idxs=None, chunk_records=None, tiled=False, tile=None):
     """The reference's `est_noise_std` (:76-80) for every lead of the selected records -> (R, 12) float64 device tensor, rows in `idxs` order.
     tiled: run `ecgvit_nlm_sigma_long` (the same kernel, records up to `MAX_LEN_TILED` samples, the same bits); `tile` is checked and ignored."""
     tables = []
     _check_tile(tiled, tile)
-
-    def stage(x, o, tab, first):
-        sig = _sigma_of(x, tab, tiled)
-        tables.append(sig)
-    if isinstance(records, torch.Tensor) and records.is_cuda:
-        _check_device_store(records)
-        rect, n, _, src_off, raw_len, stride, sel = _record_tables(records, offsets, idxs)
-        _check_lengths(raw_len, 1, tiled)
-        with torch.cuda.device(records.device):
-            stage(records, None, _Tables(records, src_off, raw_len, stride), 0)
-    else:
-        _sweep(records, offsets, idxs, False, chunk_records, 1, stage, tiled=tiled)
+    records, s = _resolve(records, offsets, idxs, 1, tiled, unique=(False, False))
+    _sweep(records, s, False, chunk_records, lambda x, o, tab, first: tables.append(_sigma_of(x, tab, tiled)))
     return tables[0] if len(tables) == 1 else torch.cat(tables)
 
 
@@ -359,6 +316,7 @@ def nlm(records, scale=1.5, search_width=None, patch_width=10, sigma=None, offse
     from .hip import lib, check, ptr, stream
     _check_nlm(scale, search_width, patch_width)
     tile_runs = _check_tile(tiled, tile, NLM_RUN) // NLM_RUN
+    tail = (float(scale), int(patch_width), 0 if search_width is None else int(search_width))
     if sigma is not None:
         if isinstance(sigma, np.ndarray):
             sigma = torch.from_numpy(np.ascontiguousarray(sigma, np.float64))
@@ -366,27 +324,22 @@ def nlm(records, scale=1.5, search_width=None, patch_width=10, sigma=None, offse
             raise ValueError('sigma must be an (R, 12) float64 table, one row per selected record')
 
     def stage(x, o, tab, first):
-        if sigma is None:
-            sig = _sigma_of(x, tab, tiled)
-        else:
-            sig = sigma[first:first + tab.R].to(x.device).contiguous()
-        if tiled:
-            runs = max(1, -(-(tab.max_len - 2 * int(patch_width) - 1) // NLM_RUN))
-            if -(-runs // min(tile_runs or NLM_TILE // NLM_RUN, runs)) > _MAX_TILES:
-                raise ValueError(f'tile = {tile}: a record of {tab.max_len} samples would need more than {_MAX_TILES} tiles')
+        sig = _sigma_of(x, tab, tiled) if sigma is None else sigma[first:first + tab.R].to(x.device).contiguous()
+        if not tiled:
+            return check(lib().ecgvit_nlm_denoise(ptr(x), ptr(o), ptr(tab.src_off), tab.stride, ptr(tab.raw_len), tab.R, C, tab.max_len, ptr(sig), *tail,
+                                                  stream()), 'ecgvit_nlm_denoise')
+        runs = max(1, -(-(tab.max_len - 2 * int(patch_width) - 1) // NLM_RUN))
+        if -(-runs // min(tile_runs or NLM_TILE // NLM_RUN, runs)) > _MAX_TILES:
+            raise ValueError(f'tile = {tile}: a record of {tab.max_len} samples would need more than {_MAX_TILES} tiles')
 
-            def launch(xs, os_, off, stride, lo, cnt):
-                check(lib().ecgvit_nlm_denoise_tiled(ptr(xs), ptr(os_), ptr(off), stride, ptr(tab.raw_len[lo:]), cnt, C,
-                                                     tab.max_len, ptr(sig[lo:]), float(scale), int(patch_width),
-                                                     0 if search_width is None else int(search_width), tile_runs, stream()), 'ecgvit_nlm_denoise_tiled')
-            return _tiled_groups(x, o, tab, launch)
-        check(lib().ecgvit_nlm_denoise(ptr(x), ptr(o), ptr(tab.src_off), tab.stride, ptr(tab.raw_len), tab.R, C, tab.max_len, ptr(sig), float(scale),
-                                       int(patch_width), 0 if search_width is None else int(search_width), stream()), 'ecgvit_nlm_denoise')
-    if sigma is not None:
-        n_sel = _selected(records, offsets, idxs)
-        if sigma.shape[0] != n_sel:
-            raise ValueError(f'sigma holds {sigma.shape[0]} rows for {n_sel} selected records')
-    return _sweep(records, offsets, idxs, out, chunk_records, 1, stage, tiled=tiled)
+        def launch(xs, os_, off, stride, lo, cnt):
+            check(lib().ecgvit_nlm_denoise_tiled(ptr(xs), ptr(os_), ptr(off), stride, ptr(tab.raw_len[lo:]), cnt, C, tab.max_len, ptr(sig[lo:]), *tail,
+                                                 tile_runs, stream()), 'ecgvit_nlm_denoise_tiled')
+        _tiled_groups(x, o, tab, launch)
+    records, s = _resolve(records, offsets, idxs, 1, tiled)
+    if sigma is not None and sigma.shape[0] != s.R:
+        raise ValueError(f'sigma holds {sigma.shape[0]} rows for {s.R} selected records')
+    return _sweep(records, s, out, chunk_records, stage)
 
 
 def frac_points(n, frac):
@@ -394,44 +347,37 @@ def frac_points(n, frac):
     return 2 * math.floor((int(n * frac) - 1) / 2) + 1
 
 
-def _check_rloess(records, npoints, degree, robust_iters, offsets, idxs, tiled=False, tile=None):
-    """every check of `rloess` that needs no device -> (npoints as the kernel takes it, the fraction or 0.0, the `_record_tables` of the selection)"""
+def _check_rloess_args(npoints, degree, robust_iters):
+    """-> (npoints as the kernel takes it, the fraction or 0.0)"""
     if isinstance(degree, bool) or not isinstance(degree, (int, np.integer)) or degree not in (1, 2):
         raise ValueError(f'degree = {degree!r}: 1 or 2')
     if isinstance(robust_iters, bool) or not isinstance(robust_iters, (int, np.integer)) or not 0 <= robust_iters <= MAX_ROBUST_ITERS:
         raise ValueError(f'robust_iters = {robust_iters!r}: an int, 0 to {MAX_ROBUST_ITERS}')
-    frac = 0.0
     if isinstance(npoints, (float, np.floating)):
         if not 0.0 < npoints < 1.0:
             raise ValueError(f'npoints = {npoints!r}: a fraction lies in (0, 1)')
-        frac, npoints = float(npoints), 0
-    elif isinstance(npoints, bool) or not isinstance(npoints, (int, np.integer)) or not degree + 2 <= npoints <= MAX_POINTS:
+        return 0, float(npoints)
+    if isinstance(npoints, bool) or not isinstance(npoints, (int, np.integer)) or not degree + 2 <= npoints <= MAX_POINTS:
         raise ValueError(f'npoints = {npoints!r}: an int, {degree + 2} (degree + 2) to {MAX_POINTS}, or a fraction in (0, 1)')
-    host = records.numpy() if isinstance(records, torch.Tensor) and not records.is_cuda else records
-    if isinstance(host, torch.Tensor):
-        _check_device_store(host)
-    elif not hasattr(host, 'shape') or not hasattr(host, 'dtype') or not np.issubdtype(host.dtype, np.floating):
-        raise ValueError('records must be a float32 device tensor or a host array / memmap / tensor of a float type')
-    tabs = _record_tables(host, offsets, idxs)
-    raw_len, sel = tabs[4], tabs[6]
-    if len(np.unique(sel)) != len(sel):
-        raise ValueError('idxs repeats a record: two workgroups would write the same samples')
-    _check_lengths(raw_len, degree + 2, tiled)
+    return int(npoints), 0.0
+
+
+def _check_rloess_windows(s, npoints, frac, degree, tiled, tile):
+    """the checks of `rloess` that need the lengths of the selection `s` and no device -> the tile as the kernel takes it"""
     if frac:
-        lo, hi = frac_points(int(raw_len.min()), frac), frac_points(int(raw_len.max()), frac)
+        lo, hi = frac_points(s.min_len, frac), frac_points(s.max_len, frac)
         if lo < degree + 2:
-            raise ValueError(f'npoints = {frac!r} gives a record of {int(raw_len.min())} samples a window of {lo}: degree {degree} needs {degree + 2} points')
+            raise ValueError(f'npoints = {frac!r} gives a record of {s.min_len} samples a window of {lo}: degree {degree} needs {degree + 2} points')
         if hi > MAX_POINTS:
-            raise ValueError(f'npoints = {frac!r} gives a record of {int(raw_len.max())} samples a window of {hi}: at most {MAX_POINTS} are supported')
-    t = _check_tile(tiled, tile) or LOESS_TILE
+            raise ValueError(f'npoints = {frac!r} gives a record of {s.max_len} samples a window of {hi}: at most {MAX_POINTS} are supported')
+    t = _check_tile(tiled, tile)
     if tiled:
-        longest = int(raw_len.max())
-        widest = min(frac_points(longest, frac) if frac else int(npoints), longest)
-        if t + 2 * widest > LOESS_LDS:
+        widest = min(frac_points(s.max_len, frac) if frac else npoints, s.max_len)
+        if (t or LOESS_TILE) + 2 * widest > LOESS_LDS:
             raise ValueError(f'tile = {tile}: the tile and two windows of {widest} samples must fit {LOESS_LDS} samples of LDS (at most {LOESS_LDS - 2 * widest})')
-        if -(-longest // t) > _MAX_TILES:
-            raise ValueError(f'tile = {tile}: a record of {longest} samples would need more than {_MAX_TILES} tiles')
-    return int(npoints), frac, tabs
+        if -(-s.max_len // (t or LOESS_TILE)) > _MAX_TILES:
+            raise ValueError(f'tile = {tile}: a record of {s.max_len} samples would need more than {_MAX_TILES} tiles')
+    return t
 
 
 def rloess(records, npoints=500, degree=2, robust_iters=10, subtract=False, offsets=None, idxs=None, out=None, chunk_records=None,
@@ -448,48 +394,31 @@ def rloess(records, npoints=500, degree=2, robust_iters=10, subtract=False, offs
     LDS.  In place the tiled kernel runs through a scratch (the module's docstring says what it costs).  The iteration table is one byte per
     sample and lead of the selection (5.6 MB per record of 462 600 samples); a host store moves it to the host chunk by chunk."""
     from .hip import lib, check, ptr, stream
-    npoints, frac, tabs = _check_rloess(records, npoints, degree, robust_iters, offsets, idxs, tiled, tile)
-    tile = 0 if tile is None else int(tile)
-    on_device = isinstance(records, torch.Tensor) and records.is_cuda
-    raw_len = tabs[4]
-    width = int(raw_len.max())
+    npoints, frac = _check_rloess_args(npoints, degree, robust_iters)
+    records, s = _resolve(records, offsets, idxs, degree + 2, tiled, unique=(True, True))
+    tile = _check_rloess_windows(s, npoints, frac, degree, tiled, tile)
+    on_device = isinstance(records, torch.Tensor)
+    tail = (npoints, frac, int(degree), int(robust_iters), int(bool(subtract)))
     tables = []
 
     def stage(x, o, tab, first):
         it = torch.zeros((tab.R, C, tab.max_len), dtype=torch.int8, device=x.device) if return_iters else None
         if tiled:
             def launch(xs, os_, off, stride, lo, cnt):
-                check(lib().ecgvit_rloess_tiled(ptr(xs), ptr(os_), ptr(off), stride, ptr(tab.raw_len[lo:]), cnt, C,
-                                                tab.min_len, tab.max_len, int(npoints), frac, int(degree), int(robust_iters), int(bool(subtract)),
+                check(lib().ecgvit_rloess_tiled(ptr(xs), ptr(os_), ptr(off), stride, ptr(tab.raw_len[lo:]), cnt, C, tab.min_len, tab.max_len, *tail,
                                                 ptr(it[lo:]) if it is not None else None, tile, stream()), 'ecgvit_rloess_tiled')
             _tiled_groups(x, o, tab, launch)
         else:
-            check(lib().ecgvit_rloess(ptr(x), ptr(o), ptr(tab.src_off), tab.stride, ptr(tab.raw_len), tab.R, C, tab.min_len, tab.max_len, int(npoints),
-                                      frac, int(degree), int(robust_iters), int(bool(subtract)), ptr(it), stream()), 'ecgvit_rloess')
+            check(lib().ecgvit_rloess(ptr(x), ptr(o), ptr(tab.src_off), tab.stride, ptr(tab.raw_len), tab.R, C, tab.min_len, tab.max_len, *tail,
+                                      ptr(it), stream()), 'ecgvit_rloess')
         if it is not None:
-            it = it if tab.max_len == width else torch.nn.functional.pad(it, (0, width - tab.max_len))
+            it = it if tab.max_len == s.max_len else torch.nn.functional.pad(it, (0, s.max_len - tab.max_len))
             tables.append(it if on_device or not tiled else it.cpu())
-    res = _sweep(records, offsets, idxs, out, chunk_records, degree + 2, stage, tables=tabs)
+    res = _sweep(records, s, out, chunk_records, stage)
     if not return_iters:
         return res
     iters = tables[0] if len(tables) == 1 else torch.cat(tables)
     return res, (iters if isinstance(res, torch.Tensor) else iters.cpu().numpy())
-
-
-def _sigma_of(x, tab, tiled=False):
-    """the noise estimate over exactly the records of `tab` (a device store)"""
-    from .hip import lib, check, ptr, stream
-    sig = torch.zeros((tab.R, C), dtype=torch.float64, device=x.device)
-    ws = _workspace(tab, x.device, tiled)
-    fn, name = (lib().ecgvit_nlm_sigma_long, 'ecgvit_nlm_sigma_long') if tiled else (lib().ecgvit_nlm_sigma, 'ecgvit_nlm_sigma')
-    for lo, cnt in tab.launches(tiled):
-        check(fn(ptr(x), ptr(tab.src_off[lo:]), tab.stride, ptr(tab.raw_len[lo:]), cnt, C, tab.max_len, ptr(sig[lo:]), ptr(ws), stream()), name)
-    return sig
-
-
-def _selected(records, offsets, idxs):
-    host = records.numpy() if isinstance(records, torch.Tensor) and not records.is_cuda else records
-    return len(_record_tables(host, offsets, idxs)[6])
 
 
 class EcgDenoiser:
@@ -525,31 +454,31 @@ class EcgDenoiser:
         tiled, tile: every stage with `tiled=True` (records up to `MAX_LEN_TILED` samples); `tile` goes to the non-local means and the robust
         LOESS alike, so it is a multiple of 15 that fits the LOESS (the stages after the low-pass work in place: through a scratch)."""
         _check_tile(tiled, tile, NLM_RUN)
-        device = isinstance(records, torch.Tensor) and records.is_cuda
-        rect, n, _, src_off, raw_len, stride, sel = _record_tables(records.numpy() if isinstance(records, torch.Tensor) and not device else records, offsets, idxs)
         loess = isinstance(baseline, str)
         if loess and baseline != 'rloess':
             raise ValueError(f"baseline = {baseline!r}: 'rloess' (the robust LOESS fit), a tensor in the store's layout, or None")
+        # the one resolution, which every stage takes as its `idxs`; the low-pass needs the longest records of the three (13 samples at least)
+        records, s = _resolve(records, offsets, idxs, 3 * max(len(self.a), len(self.b)) + 1, tiled, unique=(True, loess))
+        device = isinstance(records, torch.Tensor)
         if loess:               # every check of the LOESS stage before the first stage touches the device
             self._check_loess_points(self.loess_points)
-            _check_rloess(records, self.loess_points, 2, MAX_ROBUST_ITERS, offsets, idxs, tiled, tile)
+            _check_rloess_windows(s, self.loess_points, 0.0, 2, tiled, tile)
         if baseline is not None and not loess:
             ok = (isinstance(baseline, torch.Tensor) and baseline.dtype == torch.float32 and baseline.device == records.device) if device else \
                 isinstance(baseline, (np.ndarray, torch.Tensor))
             if not ok or tuple(baseline.shape) != tuple(records.shape):
                 raise ValueError("baseline must be in the store's layout: a float32 device tensor for a device store, a host array for a host store")
-        out = lowpass_taps(records, self.b, self.a, self.zi, offsets=offsets, idxs=idxs, out=out, chunk_records=chunk_records, tiled=tiled, tile=tile)
+        out = lowpass_taps(records, self.b, self.a, self.zi, idxs=s, out=out, chunk_records=chunk_records, tiled=tiled, tile=tile)
         if loess:
-            out = rloess(out, self.loess_points, subtract=True, offsets=offsets, idxs=idxs, out=out, chunk_records=chunk_records, tiled=tiled, tile=tile)
+            out = rloess(out, self.loess_points, subtract=True, idxs=s, out=out, chunk_records=chunk_records, tiled=tiled, tile=tile)
         elif baseline is not None:
             base = baseline if device else np.asarray(baseline, np.float32)
             if idxs is None:
                 out -= base
-            elif rect:
-                ids = torch.from_numpy(sel).to(out.device) if device else sel
+            elif s.rect:
+                ids = torch.from_numpy(s.sel).to(out.device) if device else s.sel
                 out[ids] = out[ids] - base[ids]
             else:
-                for s, l in zip(src_off.tolist(), raw_len.tolist()):
-                    out[:, s:s + l] -= base[:, s:s + l]
-        return nlm(out, self.scale, self.search_width, self.patch_width, offsets=offsets, idxs=idxs, out=out, chunk_records=chunk_records, tiled=tiled,
-                   tile=tile)
+                for src, l in zip(s.src_off.tolist(), s.raw_len.tolist()):
+                    out[:, src:src + l] -= base[:, src:src + l]
+        return nlm(out, self.scale, self.search_width, self.patch_width, idxs=s, out=out, chunk_records=chunk_records, tiled=tiled, tile=tile)

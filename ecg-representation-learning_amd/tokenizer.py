@@ -10,7 +10,7 @@ Not built: `save` / pickling, the plots, the four non-k-means clusterings and k-
 import numpy as np
 import torch
 
-from .transform import _record_tables
+from .records import DeviceTables, check_device_store, select_records
 
 SEGMENT_SIZES = (8, 16, 32)
 PADS = {'zero': 0, 'shift': 1}
@@ -18,35 +18,27 @@ MAX_CLUSTERS = 65536
 D_CLS_TH = dict(hierarchical='distance_threshold', dbscan='eps', optics='max_eps', birch='threshold', kmeans='n_clusters')   # ecg_tokenizer.py:72-78
 
 
-class _Store:
-    """the device tables of one sweep: where every (record, lead) run starts, how long it is, where its segments' outputs go"""
+class _Store(DeviceTables):
+    """the device tables of one sweep: where every (record, lead) run starts, how long it is (`DeviceTables`), where its segments' outputs go"""
 
-    def __init__(self, x, src_off, raw_len, lead_stride, C, ragged, k, pad):
-        if not (isinstance(x, torch.Tensor) and x.is_cuda):
-            raise ValueError('the tokenizer runs on the device: pass a float32 device tensor (no CPU fallback exists)')
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            raise ValueError(f'signals must be a contiguous float32 tensor, got {x.dtype}, contiguous={x.is_contiguous()}')
-        raw_len = np.asarray(raw_len, np.int64)
-        nseg = raw_len // k + 1                       # a whole extra segment when k divides the length (EcgPadder never takes its n_pad == 0 branch)
+    def __init__(self, x, src_off, raw_len, stride, C, ragged, k, pad):
+        check_device_store(x, 'signals')
+        super().__init__(x, src_off, raw_len, stride)
+        nseg = self.raw_len_h // k + 1                # a whole extra segment when k divides the length (EcgPadder never takes its n_pad == 0 branch)
         self.seg_cum = np.concatenate([[0], np.cumsum(nseg)]).astype(np.int64)
-        self.x, self.k, self.pad, self.C, self.R, self.ragged = x, k, PADS[pad], int(C), len(raw_len), ragged
+        self.k, self.pad, self.C, self.ragged = k, PADS[pad], int(C), ragged
         self.n_seg = int(self.seg_cum[-1])
-        self.lead_stride = int(lead_stride)
         if ragged:
             dst_off, self.dst_stride, self.out_shape = self.seg_cum[:-1], self.n_seg, (self.C, self.n_seg)
         else:
             T = int(nseg[0])
             dst_off, self.dst_stride, self.out_shape = np.arange(self.R, dtype=np.int64) * (self.C * T), T, (self.R, self.C, T)
-        dev = x.device
-        self.src_off_h, self.raw_len_h = np.asarray(src_off, np.int64), raw_len
-        self.src_off = torch.from_numpy(self.src_off_h.copy()).to(dev)
-        self.raw_len_d = torch.from_numpy(raw_len.astype(np.int32)).to(dev)
-        self.seg_cum_d = torch.from_numpy(self.seg_cum).to(dev)
-        self.dst_off = torch.from_numpy(np.ascontiguousarray(dst_off, np.int64)).to(dev)
+        self.seg_cum_d = torch.from_numpy(self.seg_cum).to(x.device)
+        self.dst_off = torch.from_numpy(np.ascontiguousarray(dst_off, np.int64)).to(x.device)
 
     def args(self, x=None):
         from .hip import ptr
-        return (ptr(self.x if x is None else x), ptr(self.src_off), self.lead_stride, ptr(self.raw_len_d), ptr(self.seg_cum_d), ptr(self.dst_off),
+        return (ptr(self.x if x is None else x), ptr(self.src_off), self.stride, ptr(self.raw_len), ptr(self.seg_cum_d), ptr(self.dst_off),
                 self.dst_stride, self.R, self.C, self.n_seg, self.k)
 
     def new(self, dtype):
@@ -160,12 +152,12 @@ class EcgTokenizer:
         return _Store(sig, np.arange(rows, dtype=np.int64) * L, np.full(rows, L, np.int64), L, 1, False, self.k, self.pad)
 
     def _record_store(self, sigs, offsets, idxs):
-        """(n, 12, L) records or a ragged (12, S_total) store with offsets, and a subset of either: `fit_dynamic_normalize`'s convention and validator"""
+        """(n, 12, L) records or a ragged (12, S_total) store with offsets, and a subset of either: the convention and validator of `records.py`"""
         if not isinstance(sigs, torch.Tensor):
             raise ValueError('signals must be a float32 device tensor (no CPU fallback exists)')
-        rect, n, C, src_off, raw_len, stride, sel = _record_tables(sigs, offsets, idxs)
-        check_lengths(raw_len, self.k, self.pad)
-        return _Store(sigs, src_off, raw_len, stride, C, not rect, self.k, self.pad)
+        s = select_records(sigs, offsets, idxs)
+        check_lengths(s.raw_len, self.k, self.pad)
+        return _Store(sigs, s.src_off, s.raw_len, s.stride, s.C, not s.rect, self.k, self.pad)
 
     # ---- kernels ------------------------------------------------------------------------------------
     def _assign(self, st, table, ids, means, dist=None, prev_ids=None, changed=None):
@@ -249,7 +241,7 @@ class EcgTokenizer:
         n_pad = self.k - l % self.k
         keep = (i < l) | (st.pad == 1)
         i = np.where(i < l, i, np.clip(i - n_pad, 0, l - 1))
-        flat = st.src_off_h[r][:, None] + c[:, None] * st.lead_stride + i
+        flat = st.src_off_h[r][:, None] + c[:, None] * st.stride + i
         dev = st.x.device
         seg = st.x.reshape(-1)[torch.from_numpy(flat).to(dev)]
         seg = torch.where(torch.from_numpy(keep).to(dev), seg, torch.zeros_like(seg))      # (a select: a NaN at the clamped index stays out)
@@ -276,7 +268,7 @@ class EcgTokenizer:
 
     def fit(self, sigs, method='kmeans', cls_kwargs=None, offsets=None, idxs=None):
         """k-means over the mean-removed segments of `sigs`: (n, 12, L) float32 device records, or a ragged (12, S_total) store with `offsets`;
-        `idxs` selects records without a copy (the calling convention of `fit_dynamic_normalize`).
+        `idxs` selects records without a copy (the record-store convention of `records.py`).
         cls_kwargs: n_clusters (required), max_iter=256, n_init=1, random_state=None, init='random' (n_clusters distinct segments drawn by a
         seeded host generator) or a (n_clusters, k) array (Lloyd from a given start is deterministic).  Lloyd iterations are assign then update;
         they stop when an iteration changes no id, or at max_iter; n_init > 1 keeps the run of lowest inertia.  A centre that loses every

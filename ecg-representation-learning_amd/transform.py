@@ -20,6 +20,8 @@ import math
 import numpy as np
 import torch
 
+from .records import DeviceTables, check_device_store, chunk_step, host_chunks, select_records
+
 
 class FusedInputTransform:
     def __init__(self, mean, std, patch_size, timeout=False, timeout_scale=(0.0, 0.5), per_record=False):
@@ -215,94 +217,27 @@ def _key_to_f32(keys):
     return bits.astype(np.uint32).view(np.float32)
 
 
-def _record_tables(records, offsets, idxs):
-    """-> (rectangular?, n records, C, src_off int64 (R,), raw_len int64 (R,), lead_stride) for the selected records"""
-    shape = tuple(records.shape)
-    if len(shape) == 3:
-        if offsets is not None:
-            raise ValueError('offsets come with a ragged (12, S_total) store, not with (n, 12, L) records')
-        n, C, L = shape
-        if L < 1 or L > 2 ** 31 - 1:
-            raise ValueError(f'records of {L} samples')
-        off_all, len_all, stride = np.arange(n, dtype=np.int64) * (C * L), np.full(n, L, np.int64), L
-    elif len(shape) == 2:
-        if offsets is None:
-            raise ValueError('a ragged (12, S_total) store needs offsets, an (n + 1,) table')
-        C, S = shape
-        off = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets).astype(np.int64)
-        if off.ndim != 1 or len(off) < 2 or off[0] != 0 or off[-1] != S or (np.diff(off) <= 0).any():
-            raise ValueError('offsets must be (n + 1,) strictly increasing from 0 to S_total')
-        if int(np.diff(off).max()) > 2 ** 31 - 1:
-            raise ValueError('a record is longer than 2^31 - 1 samples')
-        n, off_all, len_all, stride = len(off) - 1, off[:-1], np.diff(off), S
-    else:
-        raise ValueError(f'records must be (n, 12, L) or a ragged (12, S_total) store with offsets, got shape {shape}')
-    if C != 12:
-        raise ValueError(f'records must hold 12 leads, got {C}')   # transform.py:26
-    if idxs is None:
-        sel = np.arange(n, dtype=np.int64)
-    else:
-        sel = np.asarray(idxs.cpu() if isinstance(idxs, torch.Tensor) else idxs)
-        if sel.dtype == bool or sel.ndim != 1 or not np.issubdtype(sel.dtype, np.integer):
-            raise ValueError('idxs must be a 1-D integer array of record indices')
-        sel = sel.astype(np.int64)
-        if len(sel) and (sel.min() < 0 or sel.max() >= n):
-            raise ValueError(f'idxs out of range for {n} records')
-    if len(sel) == 0:
-        raise ValueError('no record selected')
-    return len(shape) == 3, n, C, off_all[sel], len_all[sel], stride, sel
-
-
 class _DeviceSweep:
     """the launches of one pass over the selected records: in place on a device store, or chunk by chunk through a staging buffer for a host one"""
 
-    def __init__(self, records, rect, src_off, raw_len, stride, sel, chunk_records, device):
+    def __init__(self, records, s, chunk_records, device):
         from . import hip
-        self.hip, self.C, self.device = hip, 12, device
-        self.on_device = isinstance(records, torch.Tensor) and records.is_cuda
-        if self.on_device:
-            if records.dtype != torch.float32:
-                raise ValueError(f'a device store must be float32, got {records.dtype} (fitting on other sample types is not supported)')
-            if not records.is_contiguous():
-                raise ValueError('a device store must be contiguous')
-            R = len(sel)
-            self.chunks = [(records, torch.from_numpy(src_off).to(device), torch.from_numpy(raw_len.astype(np.int32)).to(device), stride, R)]
-            self.ws = torch.empty(max(8, hip.lib().ecgvit_fit_workspace(R, self.C) // 8), dtype=torch.float64, device=device)
-            return
-        self.records = records.numpy() if isinstance(records, torch.Tensor) else records
-        self.rect, self.sel, self.host_off, self.host_len = rect, sel, src_off, raw_len
-        if chunk_records is None:   # about 256 MB of f32 per chunk
-            chunk_records = max(1, int(64 * 2 ** 20 // (self.C * max(1, int(raw_len.max())))))
-        if int(chunk_records) < 1:
-            raise ValueError('chunk_records must be at least 1')
-        self.step = int(chunk_records)
-        self.ws = torch.empty(max(8, hip.lib().ecgvit_fit_workspace(min(self.step, len(sel)), self.C) // 8), dtype=torch.float64, device=device)
-        self.chunks = None
-
-    def _host_chunks(self):
-        C = self.C
-        for lo in range(0, len(self.sel), self.step):
-            ids, lens = self.sel[lo:lo + self.step], self.host_len[lo:lo + self.step]
-            if self.rect:
-                L = int(lens[0])
-                buf = np.ascontiguousarray(self.records[ids], dtype=np.float32)   # (k, C, L)
-                off = np.arange(len(ids), dtype=np.int64) * (C * L)
-                stride = L
-            else:
-                S = int(lens.sum())
-                buf = np.empty((C, S), np.float32)
-                off = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
-                for o, s, l in zip(off.tolist(), self.host_off[lo:lo + self.step].tolist(), lens.tolist()):
-                    buf[:, o:o + l] = self.records[:, s:s + l]      # (float64 -> float32 happens in this assignment, as in the feeders)
-                stride = S
-            yield (torch.from_numpy(buf).to(self.device), torch.from_numpy(off).to(self.device),
-                   torch.from_numpy(lens.astype(np.int32)).to(self.device), stride, len(ids))
+        if isinstance(records, torch.Tensor) and records.is_cuda:
+            check_device_store(records, 'a device store')
+            tab, R = DeviceTables.of(records, s), s.R
+            self.chunks = lambda: [tab]
+        else:
+            host = records.numpy() if isinstance(records, torch.Tensor) else records
+            R = min(chunk_step(s, chunk_records), s.R)
+            self.chunks = lambda: (DeviceTables(torch.from_numpy(buf).to(device), off, lens, stride)
+                                   for buf, off, lens, stride, _ in host_chunks(host, s, chunk_records))
+        self.ws = torch.empty(max(8, hip.lib().ecgvit_fit_workspace(R, s.C) // 8), dtype=torch.float64, device=device)
 
     def run(self, *launches):
-        """every launch of `launches` (callables of (x, src_off, raw_len, stride, R)) over every chunk, the chunks uploaded once per call"""
-        for chunk in (self.chunks if self.on_device else self._host_chunks()):
+        """every launch of `launches` (callables of a chunk's DeviceTables) over every chunk, the chunks uploaded once per call"""
+        for tab in self.chunks():
             for fn in launches:
-                fn(*chunk)
+                fn(tab)
 
 
 def device_raw_stats(records, specs, want_std, offsets=None, idxs=None, chunk_records=None, device=None):
@@ -311,7 +246,8 @@ def device_raw_stats(records, specs, want_std, offsets=None, idxs=None, chunk_re
     digits -- a host store is uploaded four times (twice without order statistics), a device store is read in place."""
     from . import hip
     from .hip import lib, check, ptr, stream
-    rect, n, C, src_off, raw_len, stride, sel = _record_tables(records, offsets, idxs)
+    s = select_records(records, offsets, idxs)
+    C = s.C
     if len(specs) and 2 * len(specs) > MAX_TARGETS + (2 if 'min' in specs else 0):
         raise ValueError(f'{len(specs)} order statistics per lead need more than {MAX_TARGETS} ranks: fit fewer distinct percentiles at once')
     if isinstance(records, torch.Tensor) and records.is_cuda:
@@ -321,17 +257,17 @@ def device_raw_stats(records, specs, want_std, offsets=None, idxs=None, chunk_re
         if device.type != 'cuda' or not torch.cuda.is_available():
             raise RuntimeError('fit_dynamic_normalize runs on the device (no CPU fallback exists)')
     with torch.cuda.device(device):
-        sweep = _DeviceSweep(records, rect, src_off, raw_len, stride, sel, chunk_records, device)
+        sweep = _DeviceSweep(records, s, chunk_records, device)
         state = torch.zeros(C, 4, dtype=torch.int64, device=device)
         hist = torch.zeros(4, C, hip.FIT_TARGETS, hip.FIT_BINS, dtype=torch.int64, device=device)
         selt = torch.zeros(C, hip.FIT_TARGETS, 4, dtype=torch.int64, device=device)
         ws = sweep.ws
 
         def moments(mean):
-            return lambda x, so, rl, st, R: check(lib().ecgvit_fit_moments(ptr(x), ptr(so), st, ptr(rl), R, C, ptr(mean), ptr(ws), ptr(state), stream()), 'fit_moments')
+            return lambda t: check(lib().ecgvit_fit_moments(ptr(t.x), ptr(t.src_off), t.stride, ptr(t.raw_len), t.R, C, ptr(mean), ptr(ws), ptr(state), stream()), 'fit_moments')
 
         def histogram(p, T):
-            return lambda x, so, rl, st, R: check(lib().ecgvit_fit_histogram(ptr(x), ptr(so), st, ptr(rl), R, C, ptr(selt), T, p, ptr(hist[p]), stream()), 'fit_histogram')
+            return lambda t: check(lib().ecgvit_fit_histogram(ptr(t.x), ptr(t.src_off), t.stride, ptr(t.raw_len), t.R, C, ptr(selt), T, p, ptr(hist[p]), stream()), 'fit_histogram')
 
         sweep.run(moments(None), *([histogram(0, 0)] if specs else []))
         st = state.cpu().numpy()

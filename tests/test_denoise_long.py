@@ -13,6 +13,7 @@ import torch
 from conftest import ROOT
 import ecg_representation_learning_amd as E
 from ecg_representation_learning_amd import hip, denoise
+from ecg_representation_learning_amd.records import DeviceTables
 
 HEADER = os.path.join(ROOT, 'include', 'ecgvit_hip.h')
 CAP = 1 << 25
@@ -179,10 +180,10 @@ def test_host_refusals():
 
 
 def test_launch_groups_at_the_incart_length():
-    tab = denoise._Tables.__new__(denoise._Tables)
+    tab = DeviceTables.__new__(DeviceTables)
     tab.R, tab.max_len = 75, INCART
-    ws = [cnt * hip.lib().ecgvit_denoise_workspace_long(1, 12, INCART) for _, cnt in tab.launches(tiled=True)]
-    assert max(ws) <= denoise._WS_BYTES and sum(cnt for _, cnt in tab.launches(tiled=True)) == 75
-    groups = tab.groups()
+    ws = [cnt * hip.lib().ecgvit_denoise_workspace_long(1, 12, INCART) for _, cnt in denoise.launches(tab, denoise._ENTRY[True])]
+    assert max(ws) <= denoise._WS_BYTES and sum(cnt for _, cnt in denoise.launches(tab, denoise._ENTRY[True])) == 75
+    groups = denoise.groups(tab)
     assert max(cnt for _, cnt in groups) * 12 * INCART * 4 <= denoise._WS_BYTES and sum(cnt for _, cnt in groups) == 75
     assert [lo for lo, _ in groups] == list(np.cumsum([0] + [cnt for _, cnt in groups])[:-1])

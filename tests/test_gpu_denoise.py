@@ -230,6 +230,17 @@ def test_sigma_layouts_give_the_same_bits(stores):
     assert torch.equal(E.nlm(rect, sigma=torch.from_numpy(base)), E.nlm(rect))
 
 
+def test_a_passed_sigma_table_follows_the_host_chunks(stores):
+    """row `first` of a passed table belongs to the first record of a chunk: the second chunk of a host store reads its own rows"""
+    rect_h = stores[0]
+    rect = dev(rect_h)
+    table = E.estimate_noise_std(rect)
+    assert np.array_equal(E.nlm(rect_h, sigma=table, chunk_records=2), E.nlm(rect).cpu().numpy())
+    want = E.nlm(rect, idxs=[2, 0]).cpu().numpy()
+    for chunk in (2, 1):
+        assert np.array_equal(E.nlm(rect_h, sigma=table[[2, 0]], idxs=[2, 0], chunk_records=chunk), want)
+
+
 @pytest.mark.parametrize('long', [4300, 8300])
 def test_a_record_beside_a_long_one_keeps_its_bits(stores, long):
     """the longest record of a launch picks the LDS size of the non-local means (4096 / 8192 / 32768 samples), its workgroup size (64 lanes for

@@ -18,6 +18,7 @@ import torch
 
 import ecg_representation_learning_amd as E
 from ecg_representation_learning_amd import denoise
+from ecg_representation_learning_amd.records import DeviceTables
 import denoise_ref as R
 import loess_ref as LR
 from test_gpu_denoise import leads, guarded, bound, dev, L, RAGGED_LENGTHS, SHARED
@@ -228,7 +229,7 @@ def test_in_place_launch_groups(stores, monkeypatch):
     rag = dev(rag_h)
     want_n, want_l = E.nlm(rag, offsets=off), E.rloess(rag, 31, offsets=off, return_iters=True)
     monkeypatch.setattr(denoise, '_WS_BYTES', 2 * 12 * L * 4)                 # two records a group
-    assert len(denoise._Tables(rag, off[:-1], np.diff(off), rag.shape[1]).groups()) == 3
+    assert len(denoise.groups(DeviceTables(rag, off[:-1], np.diff(off), rag.shape[1]))) == 3
     a = rag.clone()
     assert torch.equal(E.nlm(a, offsets=off, out=a, tiled=True), want_n)
     a = rag.clone()

@@ -129,10 +129,6 @@ def test_record_table_refusals():
                dict(records=rag, offsets=off, idxs=np.array([2]))):
         with pytest.raises(ValueError):
             T.fit_dynamic_normalize(normalize='std', **kw)
-    tables = T._record_tables(rag, off, np.array([1, 0]))
-    assert tables[3].tolist() == [20, 0] and tables[4].tolist() == [30, 20] and tables[5] == 50
-    tables = T._record_tables(x, None, np.array([3, 1]))
-    assert tables[3].tolist() == [3 * 360, 360] and tables[4].tolist() == [30, 30] and tables[5] == 30
 
 
 def test_more_than_sixteen_ranks_are_refused():

@@ -27,6 +27,7 @@ sys.path.insert(0, ROOT)
 import ecg_representation_learning_amd as E  # noqa: E402
 from ecg_representation_learning_amd import hip, transform as T  # noqa: E402
 from ecg_representation_learning_amd.hip import lib, check, ptr, stream  # noqa: E402
+from ecg_representation_learning_amd.records import DeviceTables, select_records  # noqa: E402
 
 C, L = 12, 2500
 
@@ -63,9 +64,8 @@ def make(n, kind, ragged, seed):
 
 def passes(x, off, reps):
     """{pass name: us}, the launches exactly as `device_raw_stats` queues them for the default fit"""
-    rect, n, _, so, rl, stride, sel = T._record_tables(x, off, None)
-    R = len(sel)
-    so, rl = torch.from_numpy(so).cuda(), torch.from_numpy(rl.astype(np.int32)).cuda()
+    tab = DeviceTables.of(x, select_records(x, off, None))
+    R, so, rl, stride = tab.R, tab.src_off, tab.raw_len, tab.stride
     ws = torch.empty(lib().ecgvit_fit_workspace(R, C) // 8, dtype=torch.float64, device='cuda')
     state = torch.zeros(C, 4, dtype=torch.int64, device='cuda')
     hist = torch.zeros(4, C, 16, 256, dtype=torch.int64, device='cuda')
