@@ -27,6 +27,7 @@ FIT_TARGETS, FIT_BINS = 16, 256   # ecgvit_fit_histogram / ecgvit_fit_select: ta
 DENOISE_MAX_LEN, DENOISE_MAX_TAPS = 32768, 9   # ecgvit_filtfilt / ecgvit_nlm_*: samples per record, filter taps
 DENOISE_MAX_LEN_TILED = 1 << 25   # ecgvit_*_long / ecgvit_*_tiled: samples per record
 DENOISE_MAX_POINTS = 1024   # ecgvit_rloess: samples per regression window
+RESAMPLE_MAX_LEN, RESAMPLE_MAX_GENERIC = 1 << 25, 65536   # ecgvit_resample: samples per record, the widest generic-radix pass
 
 _ERR = {1: 'ECGVIT_EINVAL (unsupported shape / argument)', 2: 'ECGVIT_ELAUNCH (HIP launch failure)'}
 
@@ -145,6 +146,9 @@ SIGNATURES = {
     'ecgvit_nlm_sigma_long': (c_int, [_P, _P, _L, _P, _I, _I, _I, _P, _P, _P]),
     'ecgvit_nlm_denoise_tiled': (c_int, [_P, _P, _P, _L, _P, _I, _I, _I, _P, _D, _I, _I, _I, _P]),
     'ecgvit_rloess_tiled': (c_int, [_P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _D, _I, _I, _I, _P, _I, _P]),
+    'ecgvit_resample_plan': (c_int, [_I, POINTER(c_int), _I]),
+    'ecgvit_resample_workspace': (c_int64, [_I, _I, _I, _I]),
+    'ecgvit_resample': (c_int, [_P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P]),
 }
 
 _lib = None

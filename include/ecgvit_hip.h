@@ -648,6 +648,54 @@ int ecgvit_rloess_tiled(const float *x, float *out, const int64_t *src_off, int6
                         int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters, int tile_samples,
                         void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Fourier resampling of a record store to another length (resample.py; the reference's export stage, preprocess/data_export.py:202-215:
+ * wfdb.processing.resample_sig(sig, fqs, 250) per lead, which reduces to scipy.signal.resample(x, num = int(n * fs_target / fs))).  Parity is
+ * pinned at the scipy call; the wfdb wrapper and its length rule are restated (resample.resampled_length), not executed.  Additive entry points:
+ * the ABI version stays 6.
+ * The one stage whose output has another shape than its input: the source is addressed as ecgvit_fit_moments addresses it (lead c of record r =
+ * n_in f32 samples at x + src_off[r] + c * src_stride), the destination by a table of its own (n_out f32 samples at out + dst_off[r] +
+ * c * dst_stride; src_off, dst_off int64 [R], device arrays); every record of a call has the same n_in and the same n_out: the caller groups a
+ * ragged store by length.  A record starts at any 4-byte address; out must not overlap x.  1 <= n_in, n_out <= 1 << 25; all per-record indexing
+ * is 64-bit.  NaN input is not supported (wfdb interpolates NaN before it resamples).
+ * ALGORITHM, per record:
+ *   pairing   C is even; leads 2p and 2p + 1 are the real and the imaginary part of one complex f64 sequence z of n_in samples.  The resample is
+ *             linear and the spectrum rule below is scipy's rule for complex input, so resample(x_a + i x_b) = resample(x_a) + i resample(x_b):
+ *             one transform serves two leads and no spectrum separation is needed.  The two leads meet only in rounding (tests: 1e-12 of the
+ *             record's largest sample).
+ *   forward   X = DFT(z), X[k] = sum_j z[j] exp(-2 pi i j k / n_in)
+ *   spectrum  N = min(n_in, n_out); Y has n_out bins, zero but for Y[m] = X[m], m = 0 .. N/2, and Y[n_out - m] = X[n_in - m],
+ *             m = 1 .. N - N/2 - 1 (integer halves).  For even N: downsampling (n_out < n_in) Y[N/2] += X[n_in - N/2]; upsampling (n_in < n_out)
+ *             Y[N/2] is halved and Y[n_out - N/2] set to the same value.  Every bin is multiplied by 1 / n_in (the inverse transform's
+ *             1 / n_out times scipy's n_out / n_in).
+ *   inverse   y[j] = sum_m Y[m] exp(+2 pi i j m / n_out); re y -> lead 2p, im y -> lead 2p + 1, each rounded once to f32.
+ *   twiddles  tw_in[k] = exp(-2 pi i k / n_in), k < n_in, and tw_out[k] = exp(+2 pi i k / n_out), k < n_out: (re, im) f64 pairs in DEVICE memory,
+ *             16-byte aligned, made by the caller (resample.py: numpy on the host).  The kernels compute no sine or cosine: every root of unity,
+ *             those of the small transforms included, is a table entry, so the bits do not depend on a device math library.
+ *   plan      a transform of length n is a sequence of mixed-radix Stockham (autosort, out-of-place) passes, one launch each over all records and
+ *             lead pairs of the call, ping-pong between the two halves of `workspace`.  The radices are a pure function of n: the built radices
+ *             25, 16, 8, 5, 4, 3, 2 in this order, each for as long as it divides what is left, then every remaining prime factor in ascending
+ *             order, with multiplicity.  The built radices run in registers (16 and 8 as 4 x 4 and 4 x 2, 25 as 5 x 5); any other radix r runs
+ *             one generic pass: a thread per output, a loop over its r inputs.  With r = n that pass is the dense DFT, so a prime length works,
+ *             at n^2 complex multiply-adds per lead pair and direction instead of n log n (n = 32 771, prime: 1.1e9; Bluestein's algorithm is not
+ *             built).  A generic radix above 65 536 is refused: its pass would hold the device for minutes.
+ *             Pass with radix r after passes of product Ns, butterfly j < n / r, k = j mod Ns: v[q] = in[j + q n / r] tw[q k n / (Ns r)],
+ *             u = DFT_r(v), out[(j - k) r + k + p Ns] = u[p].
+ * Each pass reads and writes 16 bytes per complex element: an HBM stream of 32 bytes per element, pack and unpack 8 + 16 each.
+ * No atomics; every sum runs in an order fixed by (n_in, n_out): a record's output has the same bits in a rectangle, a ragged store, a subset or
+ * a chunk, alone or in a batch.
+ * ------------------------------------------------------------------------------------------------ */
+/* radices[0 .. count) = the plan of a length n, 1 <= n <= 1 << 25 -> count (their product is n; n == 1 has the empty plan, count 0; a prime
+ * has the plan { n }); -1 for n out of range or more radices than `cap`.  Host only: nothing is launched. */
+int ecgvit_resample_plan(int n, int *radices, int cap);
+/* bytes of `workspace` ecgvit_resample needs: two buffers of R * (C / 2) * max(n_in, n_out) complex f64; 0 for unsupported arguments (C odd,
+ * R * C / 2 > 65535, a length out of range or with a generic radix above 65 536) */
+int64_t ecgvit_resample_workspace(int R, int C, int n_in, int n_out);
+/* launches: pack, the passes of n_in, the spectrum map, the passes of n_out, unpack.  n_in == n_out runs the round trip (resample.py copies
+ * instead, as wfdb does).  Unsupported arguments (as above, a null or misaligned pointer) return ECGVIT_EINVAL and launch nothing. */
+int ecgvit_resample(const float *x, float *out, const int64_t *src_off, int64_t src_stride, const int64_t *dst_off, int64_t dst_stride, int R, int C,
+                    int n_in, int n_out, const double *tw_in, const double *tw_out, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,11 @@ int ecgvit_tools_attn_fwd_variant(int v);
  * anything else = ecgvit_gemm (tools/gemm_ab.py) */
 int ecgvit_tools_gemm(const ecgvit_gemm_desc *d, void *stream, int kernel, int raster_g);
 
+/* one Stockham pass of ecgvit_resample alone: radix r after passes of product Ns, over T transforms of length n (complex f64, transform t at
+ * element t * n), in -> out (in != out), tw the table of n roots the passes of that length read; r divides n and Ns divides n / r
+ * (tools/resample_rate.py: the time per pass kind) */
+int ecgvit_tools_resample_pass(const void *in, void *out, const double *tw, int n, int T, int Ns, int r, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
