@@ -94,10 +94,13 @@ class HipTrainStep:
     args: dict as produced by `get_train_args` (uses optimizer, learning_rate, weight_decay, warmup_ratio, schedule, n_step, and
     micro_batch_size: the default of `step` / `step_masked`).
 
-    Gradient accumulation (micro_batch_size=m < B): the batch of one optimiser step runs as ceil(B/m) forward + backward passes over the
-    consecutive slices [s, s+m) (the last may be shorter), the activation memory of m records, then ONE clip + AdamW update.  Each backward
-    pass overwrites the flat gradient buffer as usual; `ecgvit_grad_accumulate` sums it into a second flat buffer (`gacc`, allocated on the
-    first split batch) and folds the sum back before the norm, the data-parallel exchange (last pass only) and the optimiser.  Up to f32
+    Every step, `step` and `step_masked` alike, is ONE loop over passes (`_run`): the record ranges [s, e) of `_cuts` -- the whole batch, or
+    with micro_batch_size=m < B (gradient accumulation) the ceil(B/m) consecutive slices [s, s+m), the last maybe shorter, at the activation
+    memory of m records -- then ONE clip + AdamW update (`_update`).  A pass draws its dropout seed, runs the objective's forward and then its
+    backward; the objective (`_Supervised`, `_Masked`) says how a pass's inputs are cut, where its output rows land, what it weighs and how the
+    whole batch's loss comes about, nothing else.  The one-pass step touches no accumulator.  In a split step each backward pass overwrites
+    the flat gradient buffer as usual; `ecgvit_grad_accumulate` sums it into a second flat buffer (`gacc`, allocated on the first split
+    batch) and folds the sum back before the norm, the data-parallel exchange (armed in the last pass only) and the optimiser.  Up to f32
     summation order this is the full batch's step when dropout is 0.  With dropout every pass draws its own seed, so the masks are not those
     of the unsplit batch.
     """
@@ -147,19 +150,25 @@ class HipTrainStep:
     def get_last_lr(self):
         return self.lr0 * self.mult(self.step_count)
 
+    def _alloc_state(self, numel, device):
+        """the optimiser moments over `numel` elements and what the norm and its readbacks need; True when they were (re)allocated"""
+        if self.m is not None and self.m.device == device and self.m.numel() == numel:
+            return False
+        self.m = torch.zeros(numel, device=device, dtype=torch.float32)
+        self.v = torch.zeros_like(self.m)
+        self.norm_out = torch.zeros(2, device=device, dtype=torch.float32)
+        self.norm_host = torch.ones(2, dtype=torch.float32).pin_memory()
+        self.sumsq_host = torch.zeros(1, dtype=torch.float32).pin_memory()
+        self._flag_event = torch.cuda.Event()
+        self._norm_event = torch.cuda.Event()
+        self.sumsq = torch.zeros(1, device=device, dtype=torch.float32)
+        self.ws = torch.empty(hip.lib().ecgvit_sumsq_workspace(numel), device=device, dtype=torch.uint8)
+        return True
+
     def _state(self):
         m = self.model.encoder if hasattr(self.model, 'encoder') else self.model
         m._engine()
-        if self.m is None or self.m.device != m._pflat.device or self.m.numel() != m._pflat.numel():
-            self.m = torch.zeros_like(m._pflat)
-            self.v = torch.zeros_like(m._pflat)
-            self.norm_out = torch.zeros(2, device=m._pflat.device, dtype=torch.float32)
-            self.norm_host = torch.ones(2, dtype=torch.float32).pin_memory()
-            self.sumsq_host = torch.zeros(1, dtype=torch.float32).pin_memory()
-            self._flag_event = torch.cuda.Event()
-            self._norm_event = torch.cuda.Event()
-            self.sumsq = torch.zeros(1, device=m._pflat.device, dtype=torch.float32)
-            self.ws = torch.empty(hip.lib().ecgvit_sumsq_workspace(m._pflat.numel()), device=m._pflat.device, dtype=torch.uint8)
+        if self._alloc_state(m._pflat.numel(), m._pflat.device):
             self._replicas_synced = False
             self._flags_dirty = True
         if self.collectives and not self._replicas_synced:
@@ -238,42 +247,15 @@ class HipTrainStep:
         flat; micro-batches are then record ranges (a ragged one a ragged batch of its own), pass j weighted by its share of the masked
         patches.  Under a per-record input transform lengths are RAW sample counts and record b has padded_length(l_b) / P patches; the
         targets are the transformed patches.  Returns (loss, reconstruction (sum m_b, C*P))."""
-        mb = self._micro_batch_size(micro_batch_size)
         wrapper, model = self.model, self.model.encoder
-        geo = wrapper.check_varlen_input(sample_values, mask_idx, lengths, mask_counts)   # host work only, before anything launches
+        # (host work only, before anything launches)
+        mb, eng, geo = self._begin(model, micro_batch_size, lambda: wrapper.check_varlen_input(sample_values, mask_idx, lengths, mask_counts))
         if geo is not None:
             rect = geo.as_rectangular(model.config.max_signal_length)
             if rect is not None:   # every record full-width with one mask count: the rectangular step itself
                 mask_idx, geo = rect, None
-        if not model.training:
-            raise RuntimeError('train step on a model in eval mode')
-        self._read_flags(model)
-        self._state()
-        self._apply_flags(model)
-        self._raise_if_flagged()
-        eng = model._engine()
-        if geo is not None and mb is not None and mb < geo.B:
-            return self._step_masked_varlen_micro(model, eng, sample_values.contiguous().float(), geo, mb)
-        if geo is None and mb is not None and mb < sample_values.shape[0]:
-            return self._step_masked_micro(wrapper, model, eng, sample_values, mask_idx, mb)
-        seed = self._dropout_seed(model)
-        x = sample_values.contiguous().float()
-        if geo is not None:
-            pred, loss = eng.forward_masked_varlen(x, geo, training=True, seed=seed)
-        else:
-            wrapper.check_mask_indices(mask_idx, x.shape[0])
-            idx = self._device_mask_idx(mask_idx, x.device)
-            pred, loss = eng.forward_masked(x, idx, training=True, seed=seed)
-        model._fwd_id += 1
-        tpw = self._arm_overlap(model)
-        try:
-            eng.backward_masked(tiles_per_workgroup=tpw, trainable=self._trainable)
-        finally:
-            eng.on_grads_ready = None
-        loss, pred = loss.clone(), pred.clone()   # the engine reuses its buffers next step: hand out copies
-        self._update(model)
-        self.last_loss = loss
-        return loss, pred
+        cuts = _cuts(sample_values.shape[0] if geo is None else geo.B, mb)
+        return self._run(model, eng, _Masked(self, wrapper, eng, sample_values, mask_idx, geo, cuts))
 
     def _device_mask_idx(self, mask_idx, device):
         """the (B, m) mask indices as a contiguous int32 device tensor"""
@@ -294,18 +276,17 @@ class HipTrainStep:
         st[2].record()
         return st[1]
 
-    def _update(self, model):
-        gflat = model._gflat
+    def _update(self, model, lo=0, hi=None):
+        """the optimiser update over the whole flat buffers, or over their range [lo, hi) (the moments are then sized to it)"""
+        gflat, pflat, wlow = model._gflat, model._pflat, model._wlow
+        if hi is not None:
+            gflat, pflat, wlow = gflat[lo:hi], pflat[lo:hi], None if wlow is None else wlow[lo:hi]
         if self.collectives:
             self._xchg.finish()
         l = hip.lib()
         st = hip.stream()
-        spans = self._spans
-        if spans is None:
-            hip.check(l.ecgvit_sumsq(gflat.data_ptr(), gflat.numel(), self.sumsq.data_ptr(), self.ws.data_ptr(), st), 'sumsq')
-        else:   # frozen parameters: the norm of the trainable gradients only
-            hip.check(l.ecgvit_sumsq_spans(gflat.data_ptr(), spans[0].data_ptr(), spans[1], spans[2], self.sumsq.data_ptr(), self.ws.data_ptr(), st),
-                      'sumsq_spans')
+        spans = self._spans   # frozen parameters: the norm of the trainable gradients only
+        _sumsq(gflat, spans, self.sumsq, self.ws)
         # The non-finite decision needs only the sum of squares (the optimiser kernel's test is isfinite(sqrt(sumsq) * |1/world|)): its
         # readback goes out HERE, ahead of the optimiser and the weight-shadow transposes, so that the same-step check below lets the host
         # go on ~0.8 ms before the device has finished the step -- the Python prelude of the next step then runs under those kernels instead
@@ -315,16 +296,16 @@ class HipTrainStep:
         self._flag_event.record()
         self.step_count += 1
         lr = self.lr0 * self.mult(self.step_count - 1)  # lr in effect for this optimiser step
-        wlow = model._wlow.data_ptr() if model._wlow is not None else None
+        wlow = hip.ptr(wlow)
         if spans is None:
             hip.check(l.ecgvit_adamw_step(
-                model._pflat.data_ptr(), gflat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), wlow, gflat.numel(), self.sumsq.data_ptr(),
+                pflat.data_ptr(), gflat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), wlow, gflat.numel(), self.sumsq.data_ptr(),
                 1.0 / self.world, self.max_grad_norm, lr, 0.9, 0.999, 1e-8, self.wd, self.step_count, 1 if self.decoupled else 0,
                 self.norm_out.data_ptr(), st), 'adamw_step')
         else:
             # frozen parameters: no update, no decay, no moment update; each span at its own step (the lr follows the global one)
             hip.check(l.ecgvit_adamw_step_spans(
-                model._pflat.data_ptr(), gflat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), wlow, spans[0].data_ptr(), spans[1], spans[2],
+                pflat.data_ptr(), gflat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), wlow, spans[0].data_ptr(), spans[1], spans[2],
                 self.sumsq.data_ptr(), 1.0 / self.world, self.max_grad_norm, lr, 0.9, 0.999, 1e-8, self.wd, self.step_count,
                 1 if self.decoupled else 0, self.norm_out.data_ptr(), st), 'adamw_step_spans')
             for i, f in enumerate(self._flags):
@@ -348,15 +329,8 @@ class HipTrainStep:
         Under a per-record input transform (`FusedInputTransform(per_record=True)`) sample_values holds RAW records -- (B, C, W) or a ragged
         (C, S_raw) batch -- and lengths their raw sample counts; TimeOut spans are drawn per record in batch order, micro-batch by
         micro-batch, so the draws of a split step are those of the unsplit one."""
-        mb = self._micro_batch_size(micro_batch_size)
         model = self.model
-        if not model.training:
-            raise RuntimeError('train step on a model in eval mode')
-        self._read_flags(model)
-        self._state()
-        self._apply_flags(model)
-        self._raise_if_flagged()
-        eng = model._engine()
+        mb, eng, _ = self._begin(model, micro_batch_size)
         # the classifier reads the CLS rows only: the last block skips the other rows past its K / V (bf16 engine; the fp8 step keeps the
         # full block -- its 512-row products would fall below the 8-bit kernels' gates and change the delayed-scaling sites)
         cls_only = eng.dtype == torch.bfloat16 and not eng.fp8
@@ -367,134 +341,51 @@ class HipTrainStep:
         elif eng.input_transform is not None and eng.input_transform.per_record:
             # RAW records (B, C, W): validated once (the RawPaddedBatch travels on, micro-batches keep the whole batch's pass width)
             lengths = eng.check_raw_input(sample_values, lengths)
-        if mb is not None and mb < (labels.shape[0] if ragged else sample_values.shape[0]):
-            return self._step_micro(model, eng, sample_values, labels, lengths, mb, cls_only)
-        seed = self._dropout_seed(model)
-        x = sample_values.contiguous().float()
-        y = labels.contiguous().float()
-        w = None
-        if model.loss_weight:
-            w = torch.tensor(model.loss_weight, device=y.device, dtype=torch.float32)[y.long()].contiguous()
-        logits, _, loss_mean = eng.forward(x, y, w, training=True, seed=seed, want_mean=True, cls_only_last=cls_only, lengths=lengths)
-        model._fwd_id += 1
-        B, K = y.shape[0], eng.K
-        tpw = self._arm_overlap(model)
-        try:
-            eng.backward(gscalar=self._one(x.device), gscale=1.0 / (B * K), tiles_per_workgroup=tpw, trainable=self._trainable)
-        finally:
-            eng.on_grads_ready = None
-        loss_mean, logits = loss_mean.clone(), logits.clone()   # the engine reuses its buffers next step: hand out copies
-        self._update(model)
-        self.last_loss = loss_mean
-        return loss_mean, logits
+        cuts = _cuts(labels.shape[0] if ragged else sample_values.shape[0], mb)
+        return self._run(model, eng, _Supervised(self, model, eng, sample_values, labels, lengths, cuts, cls_only))
 
-    # -- gradient accumulation over micro-batches
-    def _micro_batch_size(self, value):
-        return self.micro_batch_size if value is None else check_micro_batch_size(value)
+    def _begin(self, model, micro_batch_size, validate=None):
+        """the prelude of every step: the host-only validation (micro_batch_size, then `validate()`) before anything touches the device, the
+        eval-mode refusal, the frozen set, the optimiser state, the pending non-finite check -> (micro_batch_size, engine, validate())"""
+        mb = self.micro_batch_size if micro_batch_size is None else check_micro_batch_size(micro_batch_size)
+        checked = None if validate is None else validate()
+        if not model.training:
+            raise RuntimeError('train step on a model in eval mode')
+        self._read_flags(model)
+        self._state()
+        self._apply_flags(model)
+        self._raise_if_flagged()
+        return mb, model._engine(), checked
 
-    def _step_micro(self, model, eng, sample_values, labels, lengths, mb, cls_only):
-        """`step` over consecutive slices of mb records: per slice a forward (its own dropout seed) and a backward with the WHOLE batch's
-        1/(B*K); the slices' logits are gathered and the loss is one BCE pass over all of them (equal logits -> the unsplit step's loss bit for
-        bit).  The labels, the loss_weight element weights and the lengths travel with their records."""
-        x = sample_values.contiguous().float()
-        y = labels.contiguous().float()
-        B, K = y.shape[0], eng.K
-        ragged = x.dim() == 2   # (validated by `step`)
-        w = None
-        if model.loss_weight:
-            w = torch.tensor(model.loss_weight, device=y.device, dtype=torch.float32)[y.long()].contiguous()
-        if lengths is not None and eng.input_transform is None and not ragged:
-            check_lengths(lengths, B, eng.P, x.shape[2])   # the whole batch's lengths are valid before the first pass
-        logits_all = torch.empty((B, K), device=x.device, dtype=torch.float32)
-        one = self._one(x.device)
-        starts = list(range(0, B, mb))
-        for j, s in enumerate(starts):
-            e = min(s + mb, B)
+    def _run(self, model, eng, obj):
+        """THE pass loop: one optimiser step as the passes `obj.cuts` of the objective `obj`.  Per pass: a fresh dropout seed,
+        `obj.forward(j, s, e, seed)` -> that pass's backward, `backward(tiles_per_workgroup)`.  Only the last pass is armed for the exchange.
+        A split step sums the passes' gradients: acc = g (pass 0) or acc += g, and in the last pass g += acc -- over each bucket as the
+        backward reports it final, right before its all-reduce goes out (overlapped exchange), else over every span after the pass.  The
+        number of collectives per optimiser step does not change, and the one-pass step never touches the accumulator."""
+        split, overlapped = len(obj.cuts) > 1, self.collectives and self.overlap
+        for j, (s, e) in enumerate(obj.cuts):
+            last = j == len(obj.cuts) - 1
             seed = self._dropout_seed(model)
-            if ragged:   # records s .. e - 1: a ragged batch of their own (host offsets, no device read)
-                xs, ls = ragged_slice(x, lengths, s, e)
-            elif isinstance(lengths, RawPaddedBatch):
-                xs, ls = x[s:e], lengths.records(s, e)
-            else:
-                xs, ls = x[s:e], None if lengths is None else lengths[s:e]
-            logits, _, _ = eng.forward(xs, y[s:e], None if w is None else w[s:e], training=True, seed=seed, want_mean=False,
-                                       cls_only_last=cls_only, lengths=ls)
+            backward = obj.forward(j, s, e, seed)
             model._fwd_id += 1
-            logits_all[s:e].copy_(logits)
-            self._micro_backward(model, eng, j, j == len(starts) - 1,
-                                 lambda tpw: eng.backward(gscalar=one, gscale=1.0 / (B * K), tiles_per_workgroup=tpw, trainable=self._trainable))
-        if getattr(self, '_bce_elem', None) is None or self._bce_elem.shape != (B, K) or self._bce_elem.device != x.device:
-            self._bce_elem = torch.empty((B, K), device=x.device, dtype=torch.float32)
-        loss_mean = torch.empty(1, device=x.device, dtype=torch.float32)
-        hip.check(hip.lib().ecgvit_bce_fwd(logits_all.data_ptr(), y.data_ptr(), hip.ptr(w), self._bce_elem.data_ptr(), loss_mean.data_ptr(),
-                                           B * K, hip.stream()), 'bce_fwd')
-        self._update(model)
-        self.last_loss = loss_mean
-        return loss_mean, logits_all
-
-    def _step_masked_micro(self, wrapper, model, eng, sample_values, mask_idx, mb):
-        """`step_masked` over consecutive slices of mb records (records and mask indices together): slice j's L1 mean enters the loss and
-        the upstream gradient with weight B_j / B, so the sum is the whole batch's mean"""
-        x = sample_values.contiguous().float()
-        B = x.shape[0]
-        wrapper.check_mask_indices(mask_idx, B)
-        idx = self._device_mask_idx(mask_idx, x.device)   # staged once, sliced on the device
-        m = idx.shape[1]
-        l, st = hip.lib(), hip.stream()
-        loss = torch.empty(1, device=x.device, dtype=torch.float32)
-        one_span = self._const(x.device, 'one span', [[0, 1, 0]], torch.int64)   # the loss: a one-element span
-        pred_all = None
-        starts = list(range(0, B, mb))
-        for j, s in enumerate(starts):
-            e = min(s + mb, B)
-            seed = self._dropout_seed(model)
-            pred, mloss = eng.forward_masked(x[s:e], idx[s:e], training=True, seed=seed)
-            model._fwd_id += 1
-            if pred_all is None:
-                pred_all = torch.empty((B * m,) + tuple(pred.shape[1:]), device=x.device, dtype=pred.dtype)
-            pred_all[s * m:e * m].copy_(pred)
-            wj = (e - s) / B
-            hip.check(l.ecgvit_grad_accumulate(loss.data_ptr(), mloss.data_ptr(), one_span.data_ptr(), 1, 1,
-                                               hip.ACC_INIT if j == 0 else hip.ACC_ADD, wj, st), 'grad_accumulate')
-            gs = self._const(x.device, ('upstream', wj), [wj], torch.float32)
-            self._micro_backward(model, eng, j, j == len(starts) - 1,
-                                 lambda tpw: eng.backward_masked(gscalar=gs, tiles_per_workgroup=tpw, trainable=self._trainable))
+            eng.on_grads_ready, tpw = None, 0
+            if last:
+                tpw = self._arm_overlap(model)
+                if split and overlapped:
+                    eng.on_grads_ready = self._fold_then_send(model)
+            try:
+                backward(tpw)
+            finally:
+                eng.on_grads_ready = None
+            if split and not (last and overlapped):
+                self._accumulate(model, hip.ACC_FOLD if last else hip.ACC_INIT if j == 0 else hip.ACC_ADD, self._acc_state(model)[0])
+        loss, out = obj.result()
         self._update(model)
         self.last_loss = loss
-        return loss, pred_all
+        return loss, out
 
-    def _step_masked_varlen_micro(self, model, eng, x, geo, mb):
-        """`step_masked` of records of unequal length over consecutive ranges of mb records, each with its own mask indices (cut by the
-        counts' prefix sums; a ragged batch by `MaskedVarlenBatch.records`, host offsets only): pass j's L1 mean enters the loss and the
-        upstream gradient with weight (its masked patches) / (the batch's), so the sum is the whole batch's mean"""
-        B = geo.B
-        l, st = hip.lib(), hip.stream()
-        loss = torch.empty(1, device=x.device, dtype=torch.float32)
-        one_span = self._const(x.device, 'one span', [[0, 1, 0]], torch.int64)
-        starts = list(range(0, B, mb))
-        parts = [geo.records(s, min(s + mb, B)) for s in starts]
-        weights = [g.m / geo.m for _, g in parts]
-        up = torch.tensor(weights, dtype=torch.float32).pin_memory().to(x.device, non_blocking=True)   # the upstream gradients, one copy
-        pred_all, k0 = None, 0
-        for j, (s, ((s0, s1), g)) in enumerate(zip(starts, parts)):
-            seed = self._dropout_seed(model)
-            xs = x[:, s0:s1].contiguous() if x.dim() == 2 else x[s:s + g.B]
-            pred, mloss = eng.forward_masked_varlen(xs, g, training=True, seed=seed)
-            model._fwd_id += 1
-            if pred_all is None:
-                pred_all = torch.empty((geo.m,) + tuple(pred.shape[1:]), device=x.device, dtype=pred.dtype)
-            pred_all[k0:k0 + g.m].copy_(pred)
-            k0 += g.m
-            hip.check(l.ecgvit_grad_accumulate(loss.data_ptr(), mloss.data_ptr(), one_span.data_ptr(), 1, 1,
-                                               hip.ACC_INIT if j == 0 else hip.ACC_ADD, weights[j], st), 'grad_accumulate')
-            gs = up[j:j + 1]
-            self._micro_backward(model, eng, j, j == len(starts) - 1,
-                                 lambda tpw: eng.backward_masked(gscalar=gs, tiles_per_workgroup=tpw, trainable=self._trainable))
-        self._update(model)
-        self.last_loss = loss
-        return loss, pred_all
-
-    def _const(self, device, key, values, dtype):
+    def _const(self, device, key, values, dtype=torch.float32):
         """a small constant device tensor, made once per key"""
         cache = self.__dict__.setdefault('_consts', {})
         if (key, device) not in cache:
@@ -533,38 +424,16 @@ class HipTrainStep:
         hip.check(hip.lib().ecgvit_grad_accumulate(self.gacc.data_ptr(), model._gflat.data_ptr(), table[0].data_ptr(), table[1], table[2], mode,
                                                    1.0, hip.stream()), 'grad_accumulate')
 
-    def _micro_backward(self, model, eng, j, last, run):
-        """backward pass j of a split batch (`run(tiles_per_workgroup)`).  Before the last one: no exchange, then acc = g (j = 0) or acc += g.
-        The last one: armed for the exchange; g += acc over each bucket as the backward reports it final, right before its all-reduce goes out
-        (overlapped exchange), else over every span after the pass.  The number of collectives per optimiser step does not change."""
-        if not last:
-            eng.on_grads_ready = None
-            run(0)
-            whole, _ = self._acc_state(model)
-            self._accumulate(model, hip.ACC_INIT if j == 0 else hip.ACC_ADD, whole)
-            return
-        tpw = self._arm_overlap(model)
-        whole, per = self._acc_state(model)
-        if self.collectives and self.overlap:
-            folded = set()
+    def _fold_then_send(self, model):
+        """the last pass's `on_grads_ready` under an overlapped exchange: g += acc over a bucket, then its all-reduce"""
+        per, folded = self._acc_state(model)[1], set()
 
-            def fold_then_send(tag):
-                if tag in per and tag not in folded:
-                    folded.add(tag)
-                    self._accumulate(model, hip.ACC_FOLD, per[tag])
-                self._xchg.bucket_ready(tag)
-            eng.on_grads_ready = fold_then_send
-        try:
-            run(tpw)
-        finally:
-            eng.on_grads_ready = None
-        if not (self.collectives and self.overlap):
-            self._accumulate(model, hip.ACC_FOLD, whole)
-
-    def _one(self, device):
-        if getattr(self, '_one_t', None) is None or self._one_t.device != device:
-            self._one_t = torch.ones(1, device=device, dtype=torch.float32)
-        return self._one_t
+        def fold_then_send(tag):
+            if tag in per and tag not in folded:
+                folded.add(tag)
+                self._accumulate(model, hip.ACC_FOLD, per[tag])
+            self._xchg.bucket_ready(tag)
+        return fold_then_send
 
     _flag_pending = False
 
@@ -617,17 +486,9 @@ class HipProbeStep(HipTrainStep):
         model = self.model
         model._engine()
         lo, hi = model._layout.span(lambda n: n.startswith('vit.mlp_head.'))
-        dev = model._pflat.device
-        if self.m is None or self.m.device != dev or self.m.numel() != hi - lo:
-            self.m = torch.zeros(hi - lo, device=dev, dtype=torch.float32)
-            self.v = torch.zeros_like(self.m)
-            self.norm_out = torch.zeros(2, device=dev, dtype=torch.float32)
-            self.norm_host = torch.ones(2, dtype=torch.float32).pin_memory()
-            self.sumsq_host = torch.zeros(1, dtype=torch.float32).pin_memory()
-            self._flag_event = torch.cuda.Event()
-            self._norm_event = torch.cuda.Event()
-            self.sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
-            self.ws = torch.empty(hip.lib().ecgvit_sumsq_workspace(hi - lo), device=dev, dtype=torch.uint8)
+        self._alloc_state(hi - lo, model._pflat.device)
+        if self._trainable is None:   # (`_update` refreshes the shadows of these only)
+            self._trainable = [n for n in model._param_names if n.startswith('vit.mlp_head.')]
         return lo, hi
 
     def step(self, features, labels):
@@ -646,9 +507,7 @@ class HipProbeStep(HipTrainStep):
         x = features.detach().contiguous().float()
         y = labels.contiguous().float()
         B = x.shape[0]
-        w = None
-        if model.loss_weight:
-            w = torch.tensor(model.loss_weight, device=y.device, dtype=torch.float32)[y.long()].contiguous()
+        w = _elem_weights(model, y)
         if self._buf is None or self._buf['xhat'].shape[0] != B or self._buf['xhat'].device != x.device:
             f32 = dict(device=x.device, dtype=torch.float32)
             self._buf = dict(xhat=torch.empty((B, d), **f32), hrstd=torch.empty(B, **f32), loss_elem=torch.empty((B, K), **f32),
@@ -661,35 +520,140 @@ class HipProbeStep(HipTrainStep):
         hip.check(l.ecgvit_head_fwd(ptr(x), 1, ptr(P[pre + '0.weight']), ptr(P[pre + '0.bias']), ptr(P[pre + '1.weight']), ptr(P[pre + '1.bias']),
                                     ptr(logits), ptr(a['xhat']), ptr(a['hrstd']), B, d, K, LN_EPS, hip.F32, st), 'head_fwd')
         hip.check(l.ecgvit_bce_fwd(ptr(logits), ptr(y), ptr(w), ptr(a['loss_elem']), ptr(loss), B * K, st), 'bce_fwd')
-        hip.check(l.ecgvit_bce_bwd(ptr(logits), ptr(y), ptr(w), ptr(self._one(x.device)), None, 1.0 / (B * K), ptr(a['dlogits']), B * K, st),
-                  'bce_bwd')
+        one = self._const(x.device, 'one', [1.0])
+        hip.check(l.ecgvit_bce_bwd(ptr(logits), ptr(y), ptr(w), ptr(one), None, 1.0 / (B * K), ptr(a['dlogits']), B * K, st), 'bce_bwd')
         hip.check(l.ecgvit_head_bwd(ptr(a['dlogits']), ptr(a['xhat']), ptr(a['hrstd']), ptr(P[pre + '0.weight']), ptr(P[pre + '0.bias']),
                                     ptr(P[pre + '1.weight']), ptr(G[pre + '1.weight']), ptr(G[pre + '1.bias']), ptr(G[pre + '0.weight']),
                                     ptr(G[pre + '0.bias']), ptr(a['dx']), 1, B, d, K, hip.F32, st), 'head_bwd')
         self._keep = (x, y, w)   # alive until the kernels that read them have run
-        self._update_head(model, lo, hi)
+        # (the alignment padding inside the head's range holds zeros and stays zero)
+        self._update(model, lo, hi)
         self.last_loss = loss
         return loss, logits
 
-    def _update_head(self, model, lo, hi):
-        """`HipTrainStep._update` over the head's range [lo, hi) of the flat buffers (the alignment padding inside it holds zeros and stays
-        zero): the norm of the head's gradient, the early read of it, clip + AdamW at the head's own step count, the bf16 shadow of the head"""
-        l, st = hip.lib(), hip.stream()
-        g, p = model._gflat[lo:hi], model._pflat[lo:hi]
-        hip.check(l.ecgvit_sumsq(g.data_ptr(), hi - lo, self.sumsq.data_ptr(), self.ws.data_ptr(), st), 'sumsq')
-        self.sumsq_host.copy_(self.sumsq, non_blocking=True)
-        self._flag_event.record()
-        self.step_count += 1
-        lr = self.lr0 * self.mult(self.step_count - 1)  # lr in effect for this optimiser step
-        wlow = model._wlow[lo:hi].data_ptr() if model._wlow is not None else None
-        hip.check(l.ecgvit_adamw_step(p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), wlow, hi - lo, self.sumsq.data_ptr(),
-                                      1.0, self.max_grad_norm, lr, 0.9, 0.999, 1e-8, self.wd, self.step_count, 1 if self.decoupled else 0,
-                                      self.norm_out.data_ptr(), st), 'adamw_step')
-        self.norm_host.copy_(self.norm_out, non_blocking=True)
-        self._norm_event.record()
-        self._flag_pending = True
-        if self.sync_nonfinite:
-            self._raise_if_flagged(wait=True)
+
+def _elem_weights(model, y):
+    """the BCE element weights of labels y under the model's `loss_weight` (None without one)"""
+    if not model.loss_weight:
+        return None
+    return torch.tensor(model.loss_weight, device=y.device, dtype=torch.float32)[y.long()].contiguous()
+
+
+def _sumsq(g, spans, out, ws):
+    """out = the sum of squares of the flat gradient buffer g (or a range of it), or of its spans (device table, rows, elements) only"""
+    l, st = hip.lib(), hip.stream()
+    if spans is None:
+        hip.check(l.ecgvit_sumsq(g.data_ptr(), g.numel(), out.data_ptr(), ws.data_ptr(), st), 'sumsq')
+    else:
+        hip.check(l.ecgvit_sumsq_spans(g.data_ptr(), spans[0].data_ptr(), spans[1], spans[2], out.data_ptr(), ws.data_ptr(), st), 'sumsq_spans')
+
+
+def _cuts(B, mb):
+    """the record ranges [s, e) of a step's passes: the whole batch, or consecutive slices of mb < B records (the last may be shorter)"""
+    if mb is None or mb >= B:
+        return [(0, B)]
+    return [(s, min(s + mb, B)) for s in range(0, B, mb)]
+
+
+class _Supervised:
+    """`step` to the pass loop.  One pass keeps the loss fused in the forward and hands out copies of the engine's loss and logits.  A split
+    step runs every pass's backward with the WHOLE batch's 1/(B*K), gathers the passes' logits and takes the loss in one BCE pass over all
+    of them (equal logits -> the unsplit step's loss bit for bit); the labels, the `loss_weight` element weights and the lengths travel with
+    their records."""
+
+    def __init__(self, st, model, eng, x, y, lengths, cuts, cls_only):
+        self.st, self.eng, self.lengths, self.cuts, self.cls_only, self.split = st, eng, lengths, cuts, cls_only, len(cuts) > 1
+        self.x, self.y = x.contiguous().float(), y.contiguous().float()
+        self.w = _elem_weights(model, self.y)
+        self.B, self.K = self.y.shape[0], eng.K
+        if self.split:
+            if lengths is not None and eng.input_transform is None and self.x.dim() == 3:
+                check_lengths(lengths, self.B, eng.P, self.x.shape[2])   # the whole batch's lengths are valid before the first pass
+            self.logits = torch.empty((self.B, self.K), device=self.x.device, dtype=torch.float32)
+
+    def forward(self, j, s, e, seed):
+        x, y, w, ls = self.x, self.y, self.w, self.lengths
+        if self.split:
+            y, w = y[s:e], None if w is None else w[s:e]
+            if x.dim() == 2:   # records s .. e - 1: a ragged batch of their own (host offsets, no device read)
+                x, ls = ragged_slice(x, ls, s, e)
+            elif isinstance(ls, RawPaddedBatch):
+                x, ls = x[s:e], ls.records(s, e)
+            else:
+                x, ls = x[s:e], None if ls is None else ls[s:e]
+        logits, _, loss = self.eng.forward(x, y, w, training=True, seed=seed, want_mean=not self.split, cls_only_last=self.cls_only, lengths=ls)
+        if self.split:
+            self.logits[s:e].copy_(logits)
+        else:
+            self.loss, self.logits = loss, logits
+        one = self.st._const(self.x.device, 'one', [1.0])
+        return lambda tpw: self.eng.backward(gscalar=one, gscale=1.0 / (self.B * self.K), tiles_per_workgroup=tpw, trainable=self.st._trainable)
+
+    def result(self):
+        if not self.split:
+            return self.loss.clone(), self.logits.clone()   # the engine reuses its buffers next step: hand out copies
+        st, y, (B, K) = self.st, self.y, self.logits.shape
+        if getattr(st, '_bce_elem', None) is None or st._bce_elem.shape != (B, K) or st._bce_elem.device != y.device:
+            st._bce_elem = torch.empty((B, K), device=y.device, dtype=torch.float32)
+        loss = torch.empty(1, device=y.device, dtype=torch.float32)
+        hip.check(hip.lib().ecgvit_bce_fwd(self.logits.data_ptr(), y.data_ptr(), hip.ptr(self.w), st._bce_elem.data_ptr(), loss.data_ptr(), B * K,
+                                           hip.stream()), 'bce_fwd')
+        return loss, self.logits
+
+
+class _Masked:
+    """`step_masked` to the pass loop, rectangular (geo None: (B, m) mask indices, staged once and sliced on the device) or over records of
+    unequal length (geo: a MaskedVarlenBatch, cut by `records` -- the counts' prefix sums, host offsets only).  One pass hands out copies of
+    the engine's loss and reconstruction.  In a split step pass j's L1 mean enters the loss and the upstream gradient with weight B_j / B
+    (rectangular) or (its masked patches) / (the batch's), so the sum is the whole batch's mean."""
+
+    def __init__(self, st, wrapper, eng, x, mask_idx, geo, cuts):
+        self.st, self.eng, self.geo, self.cuts, self.split = st, eng, geo, cuts, len(cuts) > 1
+        self.x = x = x.contiguous().float()
+        if geo is None:
+            wrapper.check_mask_indices(mask_idx, x.shape[0])
+            self.idx = st._device_mask_idx(mask_idx, x.device)
+        if self.split:
+            self.loss = torch.empty(1, device=x.device, dtype=torch.float32)
+            self.one_span = st._const(x.device, 'one span', [[0, 1, 0]], torch.int64)   # the loss: a one-element span
+            self.pred, self.k0 = None, 0
+            if geo is not None:
+                self.parts = [geo.records(s, e) for s, e in cuts]
+                self.weights = [g.m / geo.m for _, g in self.parts]
+                # the upstream gradients, one copy
+                self.up = torch.tensor(self.weights, dtype=torch.float32).pin_memory().to(x.device, non_blocking=True)
+
+    def forward(self, j, s, e, seed):
+        st, eng, x, geo = self.st, self.eng, self.x, self.geo
+        if geo is None:
+            xs, idx = (x[s:e], self.idx[s:e]) if self.split else (x, self.idx)
+            pred, mloss = eng.forward_masked(xs, idx, training=True, seed=seed)
+        else:
+            xs, g = x, geo
+            if self.split:
+                (s0, s1), g = self.parts[j]
+                xs = x[:, s0:s1].contiguous() if x.dim() == 2 else x[s:s + g.B]
+            pred, mloss = eng.forward_masked_varlen(xs, g, training=True, seed=seed)
+        if not self.split:
+            self.loss, self.pred = mloss, pred
+            return lambda tpw: eng.backward_masked(tiles_per_workgroup=tpw, trainable=st._trainable)
+        if geo is None:
+            m, wj = self.idx.shape[1], (e - s) / x.shape[0]
+            rows, total, gs = (e - s) * m, x.shape[0] * m, st._const(x.device, ('upstream', wj), [wj])
+        else:
+            rows, total, wj, gs = g.m, geo.m, self.weights[j], self.up[j:j + 1]
+        if self.pred is None:
+            self.pred = torch.empty((total,) + tuple(pred.shape[1:]), device=x.device, dtype=pred.dtype)
+        self.pred[self.k0:self.k0 + rows].copy_(pred)
+        self.k0 += rows
+        hip.check(hip.lib().ecgvit_grad_accumulate(self.loss.data_ptr(), mloss.data_ptr(), self.one_span.data_ptr(), 1, 1,
+                                                   hip.ACC_INIT if j == 0 else hip.ACC_ADD, wj, hip.stream()), 'grad_accumulate')
+        return lambda tpw: eng.backward_masked(gscalar=gs, tiles_per_workgroup=tpw, trainable=st._trainable)
+
+    def result(self):
+        if not self.split:
+            return self.loss.clone(), self.pred.clone()   # the engine reuses its buffers next step: hand out copies
+        return self.loss, self.pred
 
 
 def span_table(layout, names, flags, lag):
@@ -739,13 +703,11 @@ def clip_grad_norm_(model, max_norm=1.0, error_if_nonfinite=True):
     sumsq = torch.empty(1, device=g.device, dtype=torch.float32)
     out = torch.empty(2, device=g.device, dtype=torch.float32)
     has = [p.grad is not None for p in model._param_list]
-    if all(has):
-        hip.check(l.ecgvit_sumsq(g.data_ptr(), g.numel(), sumsq.data_ptr(), ws.data_ptr(), hip.stream()), 'sumsq')
-    else:   # as torch: parameters without a gradient (frozen ones) are not counted; their part of the buffer is not a gradient
+    spans = None
+    if not all(has):   # as torch: parameters without a gradient (frozen ones) are not counted; their part of the buffer is not a gradient
         rows = span_table(model._layout, model._param_names, has, [0] * len(has))
-        spans = torch.tensor(rows, dtype=torch.int64, device=g.device)
-        hip.check(l.ecgvit_sumsq_spans(g.data_ptr(), spans.data_ptr(), len(rows), sum(r[1] for r in rows), sumsq.data_ptr(), ws.data_ptr(),
-                                       hip.stream()), 'sumsq_spans')
+        spans = (torch.tensor(rows, dtype=torch.int64, device=g.device), len(rows), sum(r[1] for r in rows))
+    _sumsq(g, spans, sumsq, ws)
     hip.check(l.ecgvit_clip_scale(g.data_ptr(), g.numel(), sumsq.data_ptr(), float(max_norm), out.data_ptr(), hip.stream()),
               'clip_scale')
     norm, finite = out.tolist()

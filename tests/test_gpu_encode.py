@@ -317,3 +317,19 @@ def test_probe_step_is_the_frozen_encoder_step(dtype):
             assert torch.equal(lay.view(probe._pflat, n), lay.view(before, n)), n
     with torch.no_grad():                                          # and the model serves the trained head
         assert rel_err(probe(x).logits, full(x).logits) <= TOL[dtype]
+
+
+@pytest.mark.parametrize('dtype', [F32, BF16])
+def test_probe_step_keeps_its_own_count_and_lr(dtype):
+    """two consecutive probe steps: the optimiser update it shares with `HipTrainStep` counts the probe's steps and follows its schedule"""
+    args = dict(n_step=10, warmup_ratio=0.2, learning_rate=1e-2)
+    probe = _model(dtype)
+    y = (torch.rand(6, K, generator=torch.Generator().manual_seed(8)) < 0.3).float().cuda()
+    feats = probe.encode(_batch(), norm=False)
+    st = E.HipProbeStep(probe, args)
+    assert st.step_count == 0
+    for _ in range(2):
+        st.step(feats, y)
+    st.finish()
+    assert st.step_count == 2
+    assert st.get_last_lr() == st.lr0 * st.mult(2) == 1e-2 * E.lr_multiplier('cosine', 2, 10)(2)

@@ -351,6 +351,30 @@ def test_step_masked_micro_batches(dtype, form, mb):
     assert p1.shape == p0.shape and el < tl and eg < tg and en < tn and eo < to
 
 
+@pytest.mark.parametrize('form', ['padded', 'ragged'])
+def test_step_masked_micro_batch_at_least_the_batch_is_the_plain_path(form):
+    """micro_batch_size = B and > B against None over 3 steps: bit-identical loss, reconstruction, gradients, grad norm and parameters, and
+    no accumulator (the shapes of test_step_masked_micro_batches, bf16: the one dtype both forms run in)"""
+    L, B = 1000, 6
+    lengths = torch.tensor([1000, 200, 604, 4, 1000, 52])
+    ms = _step_models(_conf(128, 2, L), BF16, 3)
+    x, _ = O.synthetic_batch(B, length=L, num_class=7, seed=12)
+    idx, counts = ms[0].random_mask_indices_varlen(lengths, generator=torch.Generator().manual_seed(8))
+    xx = x.cuda() if form == 'padded' else _ragged(x, lengths).cuda()
+    res = []
+    for m, size in zip(ms, (None, B, B + 1)):
+        step = E.HipTrainStep(m, dict(ARGS))
+        out = []
+        for _ in range(3):
+            loss, pred = step.step_masked(xx, idx, micro_batch_size=size, lengths=lengths, mask_counts=counts)
+            out += [loss.clone(), pred.clone(), _flat_grad(m), step.norm_out.clone()]
+        step.finish()
+        assert step.gacc is None   # no accumulator: the one-pass step ran
+        res.append(out + [m.encoder._pflat.clone()])
+    for got in res[1:]:
+        assert len(got) == len(res[0]) and all(torch.equal(a, b) for a, b in zip(res[0], got))
+
+
 def test_step_masked_frozen_encoder_and_dropout_reproducible():
     L = 1000
     conf = _conf(128, 2, L, drop=0.1)

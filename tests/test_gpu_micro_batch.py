@@ -147,16 +147,27 @@ def test_bf16_micro_batches_equal_the_plain_step(h):
         assert cos >= 0.9998 and w['loss'] <= 2e-3
 
 
-@pytest.mark.parametrize('dtype', [F32, BF16])
-def test_micro_batch_at_least_the_batch_is_the_plain_path(dtype):
+def _plain_path(dtype, masked):
     conf = _conf(**F32_CONF) if dtype == F32 else _conf()
-    ref, p_ref, _, st0 = _run(conf, dtype, None)
+    ref, p_ref, _, st0 = _run(conf, dtype, None, masked=masked)
+    assert st0.gacc is None
     for mb in (24, 100):
-        got, p, _, st = _run(conf, dtype, mb)
+        got, p, _, st = _run(conf, dtype, mb, masked=masked)
         assert st.gacc is None   # no accumulator: the unsplit path ran
         assert all(a[0] == b[0] and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2]) and a[3] == b[3] for a, b in zip(ref, got)), mb
         assert torch.equal(p, p_ref), mb
-    print(f'{dtype}: micro_batch_size 24 and 100 bit-identical to None over 3 steps')
+    print(f'{dtype}{" masked" if masked else ""}: micro_batch_size 24 and 100 bit-identical to None over 3 steps')
+
+
+@pytest.mark.parametrize('dtype', [F32, BF16])
+def test_micro_batch_at_least_the_batch_is_the_plain_path(dtype):
+    _plain_path(dtype, masked=False)
+
+
+@pytest.mark.parametrize('dtype', [F32, BF16])
+def test_masked_micro_batch_at_least_the_batch_is_the_plain_path(dtype):
+    """the same for `step_masked`: loss, reconstruction, gradients, grad norm and parameters"""
+    _plain_path(dtype, masked=True)
 
 
 @pytest.mark.parametrize('setup', ['linear_probe', 'top2'])

@@ -11,9 +11,15 @@ gradient buffer.  Two runs of this file, one per build, show that a change of th
 Every function of the loaded library object (`hip.lib()`) is wrapped; a pointer argument is recorded as `*` (`0` when NULL), every other
 argument by value; for `ecgvit_gemm*` the scalar fields of the descriptor are written out.  One training forward + backward per form, the host
 RNG seeded per form (so the dropout seeds are arguments like any other).  Shapes: C = 12, P = 4, d = 128, h = 2, f = 256, 2 layers, K = 5,
-max_signal_length = 1000 (251 tokens), 4 records, hidden / embedding dropout 0.1; the fp8_linear form d = 256, h = 4, f = 512, 16 records
-(4 016 token rows: the 8-bit routes switch on at 2 048), two steps (the second runs on delayed scales and the 8-bit emitting kernels).
-Before anything is wrapped the file also times the host: forward + backward of the bf16 uniform form, no synchronisation inside the loop.
+max_signal_length = 1000 (251 tokens), 4 records, hidden / embedding dropout 0.1; the fp8_linear form d = 512, h = 8, f = 1024, 16 records
+(4 016 token rows: the 8-bit routes switch on at 2 048 rows and take products of K >= 384 only), two steps (the second runs on delayed
+scales and the 8-bit emitting kernels).
+The fused steps (`HipTrainStep.step` / `step_masked` unsplit and at micro_batch_size = 3 -- passes of 3 and 1 records, the short one last --, the
+frozen linear probe, `HipProbeStep.step`) run two optimiser steps each, so the second step's count and lr are arguments in the trace, and hash
+the loss, the outputs, the gradient buffer and the parameter buffer after each step.  The f32 supervised step at micro_batch_size = 3 runs at
+dropout 0: the f32 attention dropout kernel takes B h N^2 in multiples of 8 only, which 251 tokens and 2 heads meet at B = 4 but not at 3 or 1.
+Before anything is wrapped the file also times the host: forward + backward of the bf16 uniform form and the unsplit `HipTrainStep.step` on it
+(sync_nonfinite=False), no synchronisation inside the loop.
 usage: python tools/launch_trace.py [--out FILE] [--host-iters 300] | --compare A B [A2]"""
 import argparse
 import ctypes
@@ -84,14 +90,14 @@ def digest(*tensors):
 
 
 # ------------------------------------------------------------------------------------------------ the forms
-def config(E, d=128, h=2, f=256):
+def config(E, d=128, h=2, f=256, drop=0.1):
     return E.EcgVitConfig(max_signal_length=1000, patch_size=4, hidden_size=d, num_hidden_layers=2, num_attention_heads=h,
-                          intermediate_size=f, hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1)
+                          intermediate_size=f, hidden_dropout_prob=drop, attention_probs_dropout_prob=drop)
 
 
-def model_of(E, dtype, xf=None, masked=False, fp8=False):
+def model_of(E, dtype, xf=None, masked=False, fp8=False, drop=0.1):
     torch.manual_seed(1234)
-    m = E.EcgVit(num_class=5, config=config(E, 256, 4, 512) if fp8 else config(E), compute_dtype=dtype, fp8_linear=fp8)
+    m = E.EcgVit(num_class=5, config=config(E, 512, 8, 1024) if fp8 else config(E, drop=drop), compute_dtype=dtype, fp8_linear=fp8)
     if xf is not None:
         m.set_input_transform(xf)
     w = E.MaskedEcgVit(m, mask_ratio=0.5) if masked else m
@@ -147,6 +153,58 @@ def masked(E, dtype, x, lengths=None, xf=None):
     return [o.loss, o.logits] + grads(w.encoder)
 
 
+def state(m):
+    """copies of every gradient and every parameter as the engine holds them"""
+    return [t.clone() for t in grads(m) + list(m._engine().P32.values())]
+
+
+def fused(E, dtype, x, lengths=None, xf=None, mb=None, loss_weight=None, head_only=False, drop=0.1):
+    """two `HipTrainStep.step` calls on 4 records; head_only: every parameter but vit.mlp_head.* frozen (span kernels, truncated backward)"""
+    m = model_of(E, dtype, xf, drop=drop)
+    m.loss_weight = loss_weight
+    if head_only:
+        for n, p in m.named_parameters():
+            p.requires_grad_(n.startswith('vit.mlp_head.'))
+    x, y = x.cuda(), records(4, 4)[1].cuda()
+    lt = None if lengths is None else torch.tensor(lengths, dtype=torch.int64)
+    step = E.HipTrainStep(m, dict(n_step=10), sync_nonfinite=True)
+    out = []
+    for _ in range(2):
+        loss, logits = step.step(x, y, lengths=lt, micro_batch_size=mb)
+        out += [loss, logits] + state(m)
+    return out
+
+
+def fused_masked(E, dtype, x, lengths=None, xf=None, mb=None):
+    """two `HipTrainStep.step_masked` calls on 4 records, the mask of `masked`"""
+    w = model_of(E, dtype, xf, masked=True)
+    g = torch.Generator().manual_seed(9)
+    kw = {}
+    if lengths is None:
+        idx = w.random_mask_indices(x.shape[0], generator=g)
+    else:
+        idx, counts = w.random_mask_indices_varlen(torch.tensor(lengths), generator=g)
+        kw = dict(lengths=torch.tensor(lengths, dtype=torch.int64), mask_counts=counts)
+    step = E.HipTrainStep(w, dict(n_step=10), sync_nonfinite=True)
+    out = []
+    for _ in range(2):
+        loss, pred = step.step_masked(x.cuda(), idx, micro_batch_size=mb, **kw)
+        out += [loss, pred] + state(w.encoder)
+    return out
+
+
+def probe(E, dtype, x):
+    """two `HipProbeStep.step` calls on the cached features of 4 records"""
+    m = model_of(E, dtype)
+    feats, y = m.encode(x.cuda(), norm=False), records(4, 4)[1].cuda()
+    step = E.HipProbeStep(m, dict(n_step=10), sync_nonfinite=True)
+    out = [feats]
+    for _ in range(2):
+        loss, logits = step.step(feats, y)
+        out += [loss, logits] + state(m)
+    return out
+
+
 def encode(E, x, lengths):
     m = model_of(E, torch.bfloat16)
     lt = torch.tensor(lengths, dtype=torch.int64)
@@ -185,16 +243,42 @@ def forms(E):
         ('bf16 encode cls + mean, ragged', lambda: encode(E, xr, LENGTHS)),
         ('bf16 attention_rollout_batch, ragged', lambda: rollout(E, xr, LENGTHS)),
         ('fp8_linear uniform, 16 records, two fused steps', lambda: supervised(E, bf16, records(16, 1000)[0], fused_step=True, fp8=True, steps=2)),
+        ('step bf16 uniform, mb=3', lambda: fused(E, bf16, x, mb=3)),
+        ('step bf16 lengths, padded, mb=3', lambda: fused(E, bf16, x, LENGTHS, mb=3)),
+        ('step bf16 ragged, mb=3', lambda: fused(E, bf16, xr, LENGTHS, mb=3)),
+        ('step bf16 raw records, padded, mb=3', lambda: fused(E, bf16, x, RAW, xf=transform(E, True), mb=3)),
+        ('step bf16 uniform, loss_weight', lambda: fused(E, bf16, x, loss_weight=[0.3, 2.0])),
+        ('step bf16 uniform, loss_weight, mb=3', lambda: fused(E, bf16, x, loss_weight=[0.3, 2.0], mb=3)),
+        ('step bf16 uniform, mb=4 (one pass)', lambda: fused(E, bf16, x, mb=4)),
+        ('step f32 uniform, mb=3, dropout 0', lambda: fused(E, f32, x, mb=3, drop=0.0)),
+        ('step_masked bf16 rectangular', lambda: fused_masked(E, bf16, x)),
+        ('step_masked bf16 rectangular, mb=3', lambda: fused_masked(E, bf16, x, mb=3)),
+        ('step_masked bf16 lengths, padded', lambda: fused_masked(E, bf16, x, LENGTHS)),
+        ('step_masked bf16 lengths, padded, mb=3', lambda: fused_masked(E, bf16, x, LENGTHS, mb=3)),
+        ('step_masked bf16 ragged', lambda: fused_masked(E, bf16, xr, LENGTHS)),
+        ('step_masked bf16 ragged, mb=3', lambda: fused_masked(E, bf16, xr, LENGTHS, mb=3)),
+        ('step_masked bf16 raw records, ragged, mb=3', lambda: fused_masked(E, bf16, xraw, RAW, xf=transform(E, True), mb=3)),
+        ('step_masked bf16 lengths all full width, equal counts (as_rectangular)', lambda: fused_masked(E, bf16, x, (1000,) * 4)),
+        ('step_masked f32 rectangular, mb=3', lambda: fused_masked(E, f32, x, mb=3)),
+        ('step bf16 frozen linear probe', lambda: fused(E, bf16, x, head_only=True)),
+        ('step bf16 frozen linear probe, mb=3', lambda: fused(E, bf16, x, head_only=True, mb=3)),
+        ('HipProbeStep bf16', lambda: probe(E, bf16, x)),
+        ('HipProbeStep f32', lambda: probe(E, f32, x)),
     ]
 
 
-def host_time(E, iters):
-    """host microseconds per forward + backward of the bf16 uniform form: the loop only enqueues (nothing inside it waits for the device)"""
+def host_time(E, iters, fused_step=False):
+    """host microseconds per forward + backward of the bf16 uniform form, or (fused_step) per unsplit `HipTrainStep.step` on it with
+    sync_nonfinite=False: the loop only enqueues (nothing inside it waits for the device)"""
     m = model_of(E, torch.bfloat16)
     x, y = (t.cuda() for t in records(4, 1000))
+    step = E.HipTrainStep(m, dict(n_step=iters + 20), sync_nonfinite=False)
 
     def one():
-        m(sample_values=x, labels=y).loss.backward()
+        if fused_step:
+            step.step(x, y)
+        else:
+            m(sample_values=x, labels=y).loss.backward()
     for _ in range(20):
         one()
     torch.cuda.synchronize()
@@ -269,6 +353,9 @@ def main():
         enq, tot = host_time(E, a.host_iters)
         lines.append(f'host: {enq:.1f} us per forward + backward to enqueue, {tot:.1f} us with the final synchronisation '
                      f'(bf16 uniform form, {a.host_iters} iterations)')
+        enq, tot = host_time(E, a.host_iters, fused_step=True)
+        lines.append(f'host: {enq:.1f} us per fused step (HipTrainStep.step, unsplit, sync_nonfinite=False) to enqueue, {tot:.1f} us with the '
+                     f'final synchronisation (bf16 uniform form, {a.host_iters} iterations)')
     l = hip.lib()
     for name, run in forms(E):
         torch.manual_seed(4321)
