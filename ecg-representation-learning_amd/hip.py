@@ -28,6 +28,7 @@ DENOISE_MAX_LEN, DENOISE_MAX_TAPS = 32768, 9   # ecgvit_filtfilt / ecgvit_nlm_*:
 DENOISE_MAX_LEN_TILED = 1 << 25   # ecgvit_*_long / ecgvit_*_tiled: samples per record
 DENOISE_MAX_POINTS = 1024   # ecgvit_rloess: samples per regression window
 RESAMPLE_MAX_LEN, RESAMPLE_MAX_GENERIC = 1 << 25, 65536   # ecgvit_resample: samples per record, the widest generic-radix pass
+RESAMPLE_MAX_CHIRP = 1 << 24   # ecgvit_resample_chirp: samples of a length on the chirp route (its M stays within RESAMPLE_MAX_LEN)
 
 _ERR = {1: 'ECGVIT_EINVAL (unsupported shape / argument)', 2: 'ECGVIT_ELAUNCH (HIP launch failure)'}
 
@@ -149,6 +150,10 @@ SIGNATURES = {
     'ecgvit_resample_plan': (c_int, [_I, POINTER(c_int), _I]),
     'ecgvit_resample_workspace': (c_int64, [_I, _I, _I, _I]),
     'ecgvit_resample': (c_int, [_P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P]),
+    'ecgvit_resample_chirp_length': (c_int, [_I]),
+    'ecgvit_resample_chirp_workspace': (c_int64, [_I, _I, _I, _I, _I, _I]),
+    'ecgvit_resample_chirp_filter': (c_int, [_P, _I, _I, _P, _P, _P, _P]),
+    'ecgvit_resample_chirp': (c_int, [_P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

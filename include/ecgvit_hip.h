@@ -677,8 +677,9 @@ int ecgvit_rloess_tiled(const float *x, float *out, const int64_t *src_off, int6
  *             25, 16, 8, 5, 4, 3, 2 in this order, each for as long as it divides what is left, then every remaining prime factor in ascending
  *             order, with multiplicity.  The built radices run in registers (16 and 8 as 4 x 4 and 4 x 2, 25 as 5 x 5); any other radix r runs
  *             one generic pass: a thread per output, a loop over its r inputs.  With r = n that pass is the dense DFT, so a prime length works,
- *             at n^2 complex multiply-adds per lead pair and direction instead of n log n (n = 32 771, prime: 1.1e9; Bluestein's algorithm is not
- *             built).  A generic radix above 65 536 is refused: its pass would hold the device for minutes.
+ *             at n^2 complex multiply-adds per lead pair and direction instead of n log n (n = 32 771, prime: 1.1e9; the chirp route below is
+ *             the n log n form, through ecgvit_resample_chirp).  A generic radix above 65 536 is refused: its pass would hold the device for
+ *             minutes.
  *             Pass with radix r after passes of product Ns, butterfly j < n / r, k = j mod Ns: v[q] = in[j + q n / r] tw[q k n / (Ns r)],
  *             u = DFT_r(v), out[(j - k) r + k + p Ns] = u[p].
  * Each pass reads and writes 16 bytes per complex element: an HBM stream of 32 bytes per element, pack and unpack 8 + 16 each.
@@ -695,6 +696,53 @@ int64_t ecgvit_resample_workspace(int R, int C, int n_in, int n_out);
  * instead, as wfdb does).  Unsupported arguments (as above, a null or misaligned pointer) return ECGVIT_EINVAL and launch nothing. */
 int ecgvit_resample(const float *x, float *out, const int64_t *src_off, int64_t src_stride, const int64_t *dst_off, int64_t dst_stride, int R, int C,
                     int n_in, int n_out, const double *tw_in, const double *tw_out, void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The chirp route (Bluestein's algorithm, the chirp-z transform): the exact DFT of ANY length n <= 1 << 24 at O(n log n), as one circular
+ * convolution of a smooth length M run by the passes above.  Additive and opt-in (resample.py: `chirp=`): ecgvit_resample, its plan and its
+ * workspace query are unchanged, and the ABI version stays 6.  A side of a resample (the forward transform of n_in, the inverse transform of
+ * n_out) either runs its plan as above ("plain") or is transformed AS A WHOLE by the chirp route; the two sides choose independently.
+ * ALGORITHM, for a transform of length n and sign s (-1: the forward side, +1: the inverse side), X[k] = sum_j z[j] exp(s 2 pi i j k / n):
+ *   chirp     w[j] = exp(s i pi j^2 / n), j < n: (re, im) f64 pairs in DEVICE memory, 16-byte aligned, made by the caller as
+ *             cos / sin(pi ((j j) mod 2 n) / n) with the square and the reduction in 64-bit integers (resample.py: numpy on the host).  No
+ *             device trigonometry, as above.  j k = (j^2 + k^2 - (k - j)^2) / 2 gives X[k] = w[k] sum_j (z[j] w[j]) conj(w[k - j]).
+ *   length    M = the smallest integer >= 2 n - 1 of the form 2^a 3^b 5^c (ecgvit_resample_chirp_length), so the plan of M holds built radices
+ *             only; n <= 1 << 24 keeps M <= 1 << 25, the cap of the passes.
+ *   operand   a[j] = z[j] w[j], j < n; a[j] = 0, n <= j < M.
+ *   filter    b[j] = conj(w[j]), j < n; b[M - j] = conj(w[j]), 1 <= j < n; b = 0 elsewhere.  filter = DFT_M(b) / M, computed on the device
+ *             once per (n, s) by the same passes (ecgvit_resample_chirp_filter) and passed to every launch of that length.
+ *   result    c = conj(DFT_M(conj(DFT_M(a) filter))) (the circular convolution of a and b), X[k] = w[k] c[k], k < n.
+ *   tables    the inverse M-transform is the forward one between two conjugations, so a length M needs ONE twiddle table,
+ *             tw_M[k] = exp(-2 pi i k / M), k < M, whatever s is, shared by every n that maps to that M.
+ * KERNELS (complex f64, no atomics; transforms of a chirp side live at stride M in the workspace), and what is fused:
+ *   pack      forward side: the f32 lead pair -> a, the chirp multiply and the zero fill up to M folded into the pack (one launch over M).
+ *   product   A[j] <- conj(A[j] filter[j]), j < M, in place: the one sweep of its own (32 bytes per element) between the two runs of passes.
+ *   post      X[k] = w[k] conj(D[k]), D = DFT_M(conj(A filter)): no launch of its own.  Forward side: folded into the spectrum map's loads
+ *             (the map reads bin k as w_in[k] conj(D[k])).  Inverse side: folded into the unpack, rounded once to f32.
+ *   pre       inverse side: the spectrum map's output Y[m] / n_in, times w_out[m], with the zero fill n_out <= m < M: folded into the spectrum
+ *             map's stores (one launch over M).
+ * Every element of an operand up to M is WRITTEN by the pack or the map before a pass reads it: the content of `workspace` is never assumed.
+ * Launches of a chirp side: 2 passes(M) + 1 beside pack / map / unpack.  Every sum's order is fixed by (n_in, n_out, route of each side): a
+ * record keeps the same bits in every store form.  The two routes of one length agree within rounding, not bit for bit.
+ * ------------------------------------------------------------------------------------------------ */
+/* M of a length n: the smallest 2^a 3^b 5^c >= 2 n - 1; -1 for n < 1 or n > 1 << 24.  Host only. */
+int ecgvit_resample_chirp_length(int n);
+/* bytes of `workspace` ecgvit_resample_chirp needs: two buffers of R * (C / 2) * max(side lengths) complex f64, where a chirp side (flag != 0)
+ * counts its M and a plain side its n; 0 for anything refused (as ecgvit_resample_workspace for a plain side; n > 1 << 24 on a chirp side) */
+int64_t ecgvit_resample_chirp_workspace(int R, int C, int n_in, int n_out, int chirp_in, int chirp_out);
+/* filter[0 .. M) = DFT_M(b) / M for the chirp table `chirp` of n entries (either sign), M == ecgvit_resample_chirp_length(n), tw_M the table of
+ * M above; `workspace`: 2 M complex f64 (32 M bytes), every element written before it is read.  All pointers device memory, 16-byte aligned.
+ * Launches: the fill of b, the passes of M, the scaling.  Null or misaligned pointers, n out of range, another M: ECGVIT_EINVAL, no launch. */
+int ecgvit_resample_chirp_filter(const double *chirp, int n, int M, const double *tw_M, double *filter, void *workspace, void *stream);
+/* ecgvit_resample with a route per side.  chirp_in / filter_in both null: the input side is plain and tw_in is the table of n_in, as in
+ * ecgvit_resample; both non-null: the input side takes the chirp route, chirp_in = w of (n_in, -1), filter_in its filter, and tw_in is the table
+ * of M_in, exp(-2 pi i k / M_in).  chirp_out / filter_out likewise with (n_out, +1): plain takes tw_out = exp(+2 pi i k / n_out), chirp takes
+ * tw_out = exp(-2 pi i k / M_out).  Both sides plain runs ecgvit_resample's launches and gives its bits.  `workspace`:
+ * ecgvit_resample_chirp_workspace bytes.  Everything is checked on the host; a null or misaligned pointer, half of a chirp / filter pair, a
+ * chirp side above 1 << 24 samples, a plain side ecgvit_resample refuses: ECGVIT_EINVAL, and nothing is launched. */
+int ecgvit_resample_chirp(const float *x, float *out, const int64_t *src_off, int64_t src_stride, const int64_t *dst_off, int64_t dst_stride, int R,
+                          int C, int n_in, int n_out, const double *tw_in, const double *tw_out, const double *chirp_in, const double *filter_in,
+                          const double *chirp_out, const double *filter_out, void *workspace, void *stream);
 
 #ifdef __cplusplus
 }

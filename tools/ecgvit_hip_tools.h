@@ -31,6 +31,13 @@ int ecgvit_tools_gemm(const ecgvit_gemm_desc *d, void *stream, int kernel, int r
  * (tools/resample_rate.py: the time per pass kind) */
 int ecgvit_tools_resample_pass(const void *in, void *out, const double *tw, int n, int T, int Ns, int r, void *stream);
 
+/* the chirp route of ecgvit_resample_chirp as a transform of its own, before the f32 store hides its f64 arithmetic: T complex f64 sequences of
+ * length n (sequence t at element t * n of `in`) -> their DFT of the chirp table's sign, complex f64, in `out` (same layout).  chirp, filter,
+ * tw_M, M as ecgvit_resample_chirp_filter states them; `workspace`: 2 T M complex f64.  The passes, the pointwise product and the post multiply
+ * are the product's; the chirp multiply and zero fill of the operand is a kernel of its own here (tests/test_gpu_resample_chirp.py) */
+int ecgvit_tools_resample_chirp(const void *in, void *out, const double *chirp, const double *filter, const double *tw_M, int n, int M, int T,
+                                void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

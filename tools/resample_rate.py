@@ -10,7 +10,10 @@
   per pass          every pass of both plans alone over the store's transforms (`ecgvit_tools_resample_pass` of the tools library), device
                     events: ms, bytes / time, specialised (registers) or generic (a thread per output, r inputs each)
 Stores: beats + sway + Gaussian noise 0.05 (tools/denoise_long_rate.py `store`).  Warm-up, device events.  Writes profiles/r23_resample.txt (--out).
-usage: python tools/resample_rate.py [--reps 5]"""
+--chirp: the table behind `resample.CHIRP_DEFAULT` instead (`chirp_main`): per prime r of 7 .. 65 521 and two shapes, the launch sequence with the
+input side on the dense route and on the chirp route (Bluestein), alternating in this one process, and the headline shapes 512 x 4999 -> 2499,
+1 x 131 101 -> 65 550 beside 512 x 5000 -> 2500.  Writes profiles/r24_resample_chirp.txt (--out).
+usage: python tools/resample_rate.py [--reps 5] [--chirp]"""
 import argparse
 import os
 import sys
@@ -60,11 +63,107 @@ def stream_rate(nbytes, reps):
     return 4 * d * b * n / (ms * 1e-3), 4 * d * b * n
 
 
+CHIRP_PRIMES = (7, 13, 31, 61, 127, 257, 509, 1021, 4099, 16411, 65521)
+CHIRP_SHAPES = ((512, 5000, 2500), (1, 460000, 225000))     # records, the length the input side is near, the output length (built radices only)
+
+
+def chirp_main(a):
+    """--chirp: where the chirp route (Bluestein) overtakes the generic pass.  Per tabled prime r and shape: the input length is r k, k of built radices
+    only, nearest the shape's length, so r is the plan's one generic radix; the output length has built radices only and runs the same plain passes on both routes,
+    so the two launch sequences differ in the input side alone.  Both are timed in this one process, in alternating order, each window at
+    least ~20 ms of calls between two device events; the table gives the median and the minimum over the rounds."""
+    import importlib
+    import bench
+    import code_objects
+    RS = importlib.import_module('ecg_representation_learning_amd.resample')
+    L = lib()
+    lines = []
+
+    def note(s):
+        lines.append(s)
+        print(s, flush=True)
+
+    def side(n, sign, chirp):
+        tables = {}
+        return RS._side_tables(n, sign, chirp, tables, torch.device('cuda'))
+
+    def compare(R, n_in, n_out, routes):
+        """routes: [(chirp_in, chirp_out)] -> {route: (median ms, min ms)}, max |route - first route| / max |x|"""
+        x = torch.randn((R, C, n_in), device='cuda', generator=torch.Generator('cuda').manual_seed(24))
+        src = torch.arange(R, device='cuda', dtype=torch.int64) * (C * n_in)
+        dst = torch.arange(R, device='cuda', dtype=torch.int64) * (C * n_out)
+        fns, outs = {}, {}
+        for ci, co in routes:
+            ti, to = side(n_in, -1, ci), side(n_out, 1, co)
+            ws = torch.empty(L.ecgvit_resample_chirp_workspace(R, C, n_in, n_out, ci, co) // 8, dtype=torch.float64, device='cuda')
+            out = torch.empty((R, C, n_out), device='cuda')
+            outs[(ci, co)] = out
+
+            def fn(ti=ti, to=to, ws=ws, out=out):
+                check(L.ecgvit_resample_chirp(ptr(x), ptr(out), ptr(src), n_in, ptr(dst), n_out, R, C, n_in, n_out, ptr(ti[0]), ptr(to[0]),
+                                              ptr(ti[1]), ptr(ti[2]), ptr(to[1]), ptr(to[2]), ptr(ws), stream()), 'ecgvit_resample_chirp')
+            fns[(ci, co)] = fn
+        inner = {k: max(1, min(64, int(20.0 / max(timed(f, 1), 1e-3)))) for k, f in fns.items()}       # (timed() warms each route up once)
+        ms = {k: [] for k in fns}
+        for rnd in range(a.reps):
+            for k in (routes if rnd % 2 == 0 else routes[::-1]):
+                ms[k].append(timed(fns[k], inner[k], warmup=0))
+        first = outs[routes[0]]
+        dev = max(float((outs[k] - first).abs().max()) for k in routes) / float(x.abs().max())
+        return {k: (float(np.median(v)), min(v)) for k, v in ms.items()}, dev
+
+    note(f'sources: bench.kernel_source_hash() = {bench.kernel_source_hash()}; {torch.cuda.get_device_name(0)}, '
+         f'{torch.cuda.get_device_properties(0).multi_processor_count} CUs')
+    note(f'ecgvit_resample_chirp, the launch sequence alone on prepared tables (device events); {a.reps} rounds per row, the routes in alternating order, '
+         f'a window of ~20 ms of calls (at least one); ms per call: median (minimum); stores: Gaussian noise')
+    for name, k in sorted(code_objects.kernels(hip.LIB_PATH).items()):
+        if 'rs_' in name and ('chirp' in name or 'rs_scale' in name):
+            note(f'    {name}: {k["vgpr_count"]} VGPRs, VGPR spills {k["vgpr_spill_count"]}, scratch {k["private_segment_fixed_size"]} B')
+    wins = {r: [] for r in CHIRP_PRIMES}
+    smooth = sorted(2 ** i * 3 ** j * 5 ** k for i in range(20) for j in range(13) for k in range(9) if 2 ** i * 3 ** j * 5 ** k <= 1 << 19)
+    for R, near, n_out in CHIRP_SHAPES:
+        note(f'shape {R} x {C} x ~{near} -> {n_out} (plan {RS.plan(n_out)}): the input side on the dense route (its plan, a generic pass of radix r) and on the chirp route')
+        for r in CHIRP_PRIMES:
+            n_in = r * min(smooth, key=lambda k: abs(r * k - near))
+            if abs(n_in - near) > near // 5:
+                note(f'    r = {r:6d}: no length within 20% of {near} has this factor: not measured at this shape')
+                continue
+            res, dev = compare(R, n_in, n_out, [(0, 0), (1, 0)])
+            (d_med, d_min), (c_med, c_min) = res[(0, 0)], res[(1, 0)]
+            wins[r].append(c_med < d_med)
+            note(f'    r = {r:6d}: n_in = {n_in:7d} plan {RS.plan(n_in)}, M = {RS.chirp_length(n_in)} plan {RS.plan(RS.chirp_length(n_in))}: dense {d_med:9.3f} ({d_min:9.3f}) ms, '
+                 f'chirp {c_med:9.3f} ({c_min:9.3f}) ms, dense / chirp {d_med / c_med:8.2f}; max |chirp - dense| / max |x| = {dev:.1e}')
+            torch.cuda.empty_cache()
+    crossover = None
+    for r in reversed(CHIRP_PRIMES):
+        if not (wins[r] and all(wins[r])):
+            break
+        crossover = r
+    note(f'the chirp route wins at every measured shape for the tabled primes {[r for r in CHIRP_PRIMES if wins[r] and all(wins[r])]}; '
+         f'the smallest tabled prime from which it wins at every measured shape, and at every larger tabled prime: {crossover} (CHIRP_DEFAULT)')
+    note('headline shapes, same run (routes as (input side, output side)):')
+    for R, n_in, n_out, routes in ((512, 5000, 2500, [(0, 0)]), (512, 4999, 2499, [(0, 0), (1, 0), (1, 1)]), (1, 131101, 65550, [(1, 0), (1, 1)])):
+        res, dev = compare(R, n_in, n_out, routes)
+        word = {0: 'plain / dense', 1: 'chirp'}
+        for (ci, co), (med, mn) in res.items():
+            note(f'    {R} x {C} x {n_in} -> {n_out} ({word[ci]}, {word[co]}): {med:9.3f} ({mn:9.3f}) ms')
+        if len(routes) > 1:
+            note(f'        max |route - first route| / max |x| = {dev:.1e}' + ('; the dense input side of 131 101 is refused (a prime above 65 536)' if n_in == 131101 else ''))
+        torch.cuda.empty_cache()
+    with open(a.out, 'w') as fh:
+        fh.write('\n'.join(lines) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r23_resample.txt'))
+    ap.add_argument('--chirp', action='store_true', help='the dense / chirp crossover table (profiles/r24_resample_chirp.txt)')
+    ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, 'profiles', 'r24_resample_chirp.txt' if a.chirp else 'r23_resample.txt')
+    if a.chirp:
+        return chirp_main(a)
     import importlib
     import bench
     import code_objects

@@ -27,5 +27,6 @@ def tools_lib():
         l.ecgvit_attention_bwd_oneitem.restype, l.ecgvit_attention_bwd_oneitem.argtypes = I, [P, P, P, P, P, I, I, I, I, F, F, U, I, P]
         l.ecgvit_tools_attn_fwd_variant.restype, l.ecgvit_tools_attn_fwd_variant.argtypes = I, [I]
         l.ecgvit_tools_resample_pass.restype, l.ecgvit_tools_resample_pass.argtypes = I, [P, P, P, I, I, I, I, P]
+        l.ecgvit_tools_resample_chirp.restype, l.ecgvit_tools_resample_chirp.argtypes = I, [P, P, P, P, P, I, I, I, P, P]
         _tools = l
     return _tools
