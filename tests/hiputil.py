@@ -34,6 +34,30 @@ def release():
     _keepalive.clear()
 
 
+PAD = 64            # guard band, elements (keeps the interior 16-B aligned)
+SENTINEL = -777.25  # exactly representable in f32 and bf16
+_BITS = {torch.float32: torch.int32, torch.bfloat16: torch.int16}
+
+
+def bits(t):
+    return t.view(_BITS[t.dtype])
+
+
+class Guarded:
+    """n elements, NaN, inside a sentinel-filled device buffer"""
+
+    def __init__(self, n, dtype):
+        self.n = n
+        self.buf = torch.full((n + 2 * PAD,), SENTINEL, dtype=dtype, device='cuda')
+        self.t = self.buf[PAD:PAD + n]
+        self.t.fill_(float('nan'))
+        self.before = self.buf.clone()
+
+    def bands_ok(self):
+        b, a = bits(self.buf), bits(self.before)
+        return torch.equal(b[:PAD], a[:PAD]) and torch.equal(b[PAD + self.n:], a[PAD + self.n:])
+
+
 def rel_err(a, b):
     a, b = a.detach().double().cpu(), b.detach().double().cpu()
     return float((a - b).norm() / (b.norm() + 1e-30))

@@ -11,35 +11,13 @@ import torch
 
 import attention_ref as R
 from attention_ref import C, F32, F64, BF16, judge
-from hiputil import ptr, check, stream, _attn_prob_mult_bf16
+from hiputil import ptr, check, stream, _attn_prob_mult_bf16, Guarded
 from ecg_representation_learning_amd import hip
 from ecg_representation_learning_amd.hip import lib
 
 pytestmark = pytest.mark.gpu
 
-PAD = 64            # guard band, elements (keeps the interior 16-B aligned)
-SENTINEL = -777.25  # exactly representable in f32 and bf16
 SEED = 1234
-_BITS = {F32: torch.int32, BF16: torch.int16}
-
-
-def bits(t):
-    return t.view(_BITS[t.dtype])
-
-
-class Guarded:
-    """n elements, NaN, inside a sentinel-filled device buffer"""
-
-    def __init__(self, n, dtype):
-        self.n = n
-        self.buf = torch.full((n + 2 * PAD,), SENTINEL, dtype=dtype, device='cuda')
-        self.t = self.buf[PAD:PAD + n]
-        self.t.fill_(float('nan'))
-        self.before = self.buf.clone()
-
-    def bands_ok(self):
-        b, a = bits(self.buf), bits(self.before)
-        return torch.equal(b[:PAD], a[:PAD]) and torch.equal(b[PAD + self.n:], a[PAD + self.n:])
 
 
 class Figures:
