@@ -1,5 +1,5 @@
-// The segment tokenizer (tokenizer.EcgTokenizer; the reference's models/ecg_tokenizer.py): nearest-centre assignment, the Lloyd update and the
-// decode, over a record store addressed as fit_stats.hip addresses it.  Contract, padding rule and the order of every sum: include/ecgvit_hip.h.
+// The segment tokenizer (tokenizer.EcgTokenizer; the reference's models/ecg_tokenizer.py): nearest-centre assignment, the Lloyd update, the
+// k-means++ seeding and the decode, over a record store addressed as fit_stats.hip addresses it.  Contract, padding rule and the order of every sum: include/ecgvit_hip.h.
 //
 // Work is laid out per lead: workgroup (b, c) takes positions [b * span, (b + 1) * span) of lead c's segments, a position finds its record by
 // a binary search in seg_cum.  The padding is applied in the segment load; no padded copy of the store exists.
@@ -251,6 +251,238 @@ __global__ __launch_bounds__(TOK_THREADS) void tok_finish_kernel(const u64 *__re
 }
 
 // =====================================================================================================
+// k-means++ seeding (sklearn's greedy _kmeans_plusplus, every sum an integer; the contract: include/ecgvit_hip.h).  Two launches per centre:
+//   sweep s  reads every segment once: applies centre s - 1 to closest[g] (a flat f32 array over g = c * n_seg + p), then weighs the segment
+//            under each of the step's candidates, q_t = quant(min(closest, d2_t)), and leaves ONE u64 per (candidate, workgroup) in
+//            block_sums[t][c * blocks + b] -- workgroups ascend with g; no atomics, integer addition has no order.
+//   pick s   (one workgroup) sums each candidate's row to its potential, accepts the argmin as centre s, then draws the next step's candidates:
+//            a chunked scan of the winner's row finds each target's workgroup, the weights of that one span are recomputed by the sweep's own
+//            expression and scanned to the segment.
+// Step 0 is the same pipeline with one candidate, the given first segment, from closest = +inf (which is never quantised, nor stored: the
+// array is first written by sweep 1 and first read by pick 1).
+// =====================================================================================================
+#define SEED_SPAN 1024                                   // segments per workgroup of the sweep: four per thread
+#define SEED_PER (SEED_SPAN / TOK_THREADS)
+#define SEED_TMAX 16                                     // candidates per step
+#define SEED_PICK_THREADS SEED_SPAN                      // the pick scans a sweep span with one segment per thread
+#define SEED_WS_CAND_G 16                                // workspace: the maximum's bits at 0, the candidates' g (int64 [16]),
+#define SEED_WS_CAND_C (SEED_WS_CAND_G + SEED_TMAX * 8)  //   the candidates' segments (f32 [16][32]),
+#define SEED_WS_SUMS (SEED_WS_CAND_C + SEED_TMAX * 32 * 4)   // block_sums (u64 [T][C * blocks]), then closest (f32 [C * n_seg])
+
+// sum_e (s_e - c_e)^2: f32, UNFUSED (every difference, product and addition rounds on its own), in sample order
+template <int K> __device__ __forceinline__ float tok_d2(const float (&v)[K], const float *c) {
+#pragma clang fp contract(off)
+    float acc = 0.f;
+#pragma unroll
+    for (int e = 0; e < K; ++e) {
+        const float d = v[e] - c[e];
+        const float sq = d * d;
+        acc = e ? acc + sq : sq;
+    }
+    return acc;
+}
+
+// rint(d 2^F) in f64, where the product is exact; a non-finite distance (a segment with a non-finite sample, the untouched +inf) weighs nothing
+__device__ __forceinline__ u64 tok_quant(float d, int F) {
+    return (__float_as_uint(d) & 0x7F800000u) == 0x7F800000u ? 0ull : __double2ull_rn(ldexp((double)d, F));
+}
+
+// F = 63 - H - (2 E + 2 + log2 k) from fbase = 63 - H - 2 - log2 k and the maximum's bits
+__device__ __forceinline__ int tok_seed_f(int fbase, uint32_t amax_bits) { return fbase - 2 * (31 - tok_shift(amax_bits)); }
+
+__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// inclusive scan over the workgroup's threads in thread order; sh: one u64 per wave
+__device__ __forceinline__ u64 block_scan_u64(u64 v, u64 *sh) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const u64 up = __shfl_up(v, o, 64);
+        if (lane >= o) v += up;
+    }
+    if (lane == 63) sh[wave] = v;
+    __syncthreads();
+    u64 before = 0;
+    for (int w = 0; w < nw; ++w) before += w < wave ? sh[w] : 0ull;
+    __syncthreads();
+    return v + before;
+}
+
+template <int K>
+__global__ __launch_bounds__(TOK_THREADS) void tok_seed_sweep_kernel(TokStore st, int64_t n_seg, int step, int T, int64_t first,
+                                                                      const float *__restrict__ centers, float *__restrict__ cand_c,
+                                                                      int64_t *__restrict__ cand_g, float *__restrict__ closest,
+                                                                      u64 *__restrict__ block_sums, int64_t NB, const uint32_t *__restrict__ amax,
+                                                                      int fbase) {
+    __shared__ float cc[(SEED_TMAX + 1) * K];            // row 0: the centre accepted by the previous pick; rows 1 .. T: the candidates
+    __shared__ u64 red[TOK_THREADS / WAVE][SEED_TMAX];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = blockIdx.y;
+    if (step == 0) {                                     // the one candidate is the given segment; workgroup (0, 0) also leaves it for the pick
+        if (tid == 0) {
+            const int fc = (int)(first / n_seg);
+            const TokSeg g = tok_locate(st, fc, first % n_seg);
+            float v[K];
+            tok_load<K>(st, fc, g, v);
+#pragma unroll
+            for (int e = 0; e < K; ++e) cc[K + e] = v[e];
+            if (blockIdx.x == 0 && c == 0) {
+#pragma unroll
+                for (int e = 0; e < K; ++e) cand_c[e] = v[e];
+                cand_g[0] = first;
+            }
+        }
+    } else {
+        for (int i = tid; i < (T + 1) * K; i += TOK_THREADS) cc[i] = i < K ? centers[(int64_t)(step - 1) * K + i] : cand_c[i - K];
+    }
+    __syncthreads();
+    const int F = tok_seed_f(fbase, *amax);
+    // the span's four segments per thread stay in registers; the centre of the previous pick is applied once, then each candidate is one pass
+    float v[SEED_PER][K], cl[SEED_PER];
+    bool live[SEED_PER];
+#pragma unroll
+    for (int j = 0; j < SEED_PER; ++j) {
+        const int64_t p = (int64_t)blockIdx.x * SEED_SPAN + j * TOK_THREADS + tid;
+        live[j] = p < n_seg;
+        cl[j] = __builtin_inff();
+#pragma unroll
+        for (int e = 0; e < K; ++e) v[j][e] = 0.f;
+        if (live[j]) {
+            const TokSeg g = tok_locate(st, c, p);
+            tok_load<K>(st, c, g, v[j]);
+            if (step >= 1) {
+                const float d = tok_d2<K>(v[j], cc);
+                if (step >= 2) cl[j] = closest[(int64_t)c * n_seg + p];
+                cl[j] = d < cl[j] ? d : cl[j];           // (a NaN distance leaves what is there)
+                closest[(int64_t)c * n_seg + p] = cl[j];
+            }
+        }
+    }
+#pragma unroll 1
+    for (int t = 0; t < T; ++t) {
+        float row[K];
+#pragma unroll
+        for (int e = 0; e < K; ++e) row[e] = cc[(t + 1) * K + e];
+        u64 a = 0;
+#pragma unroll
+        for (int j = 0; j < SEED_PER; ++j) {
+            const float d = tok_d2<K>(v[j], row);
+            if (live[j]) a += tok_quant(d < cl[j] ? d : cl[j], F);
+        }
+        a = wave_sum_u64(a);
+        if (lane == 0) red[wave][t] = a;
+    }
+    __syncthreads();
+    if (tid < T) {
+        u64 s = 0;
+#pragma unroll
+        for (int w = 0; w < TOK_THREADS / WAVE; ++w) s += red[w][tid];
+        block_sums[(int64_t)tid * NB + (int64_t)c * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(SEED_PICK_THREADS) void tok_seed_pick_kernel(TokStore st, int64_t n_seg, int64_t B, int64_t NB, int step, int T, int T_next,
+                                                                           int n_trials, const u64 *__restrict__ u53, const float *__restrict__ closest,
+                                                                           const u64 *__restrict__ block_sums, float *cand_c, int64_t *cand_g,
+                                                                           float *__restrict__ centers, int64_t *__restrict__ indices,
+                                                                           u64 *__restrict__ trace, const uint32_t *__restrict__ amax, int fbase) {
+    __shared__ u64 wsum[SEED_PICK_THREADS / WAVE], pots[SEED_TMAX], tgt[SEED_TMAX], res[SEED_TMAX];
+    __shared__ int64_t blk[SEED_TMAX];
+    __shared__ float acc_c[K];
+    __shared__ int s_win;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the potentials of the step's candidates
+    for (int t = 0; t < T; ++t) {
+        u64 a = 0;
+        for (int64_t i = tid; i < NB; i += SEED_PICK_THREADS) a += block_sums[(int64_t)t * NB + i];
+        a = wave_sum_u64(a);
+        if (lane == 0) wsum[wave] = a;
+        __syncthreads();
+        if (tid == 0) {
+            u64 s = 0;
+            for (int w = 0; w < SEED_PICK_THREADS / WAVE; ++w) s += wsum[w];
+            pots[t] = s;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {                                      // the smallest potential; equal potentials go to the smaller trial index
+        int win = 0;
+        for (int t = 1; t < T; ++t) win = pots[t] < pots[win] ? t : win;
+        s_win = win;
+        indices[step] = cand_g[win];
+        if (trace && step >= 1) {
+            for (int t = 0; t < T; ++t) {
+                trace[((int64_t)(step - 1) * n_trials + t) * 2] = (u64)cand_g[t];
+                trace[((int64_t)(step - 1) * n_trials + t) * 2 + 1] = pots[t];
+            }
+        }
+    }
+    __syncthreads();
+    const int win = s_win;
+    const u64 potw = pots[win];
+    if (tid < K) {
+        const float w = cand_c[win * K + tid];
+        centers[(int64_t)step * K + tid] = w;
+        acc_c[tid] = w;
+    }
+    if (T_next == 0) return;
+    // the next step's targets, (U pot) >> 53 of the 117-bit product, and the workgroup of the sweep each falls into
+    if (tid < T_next) {
+        const u64 U = u53[tid];
+        tgt[tid] = (__umul64hi(U, potw) << 11) | ((U * potw) >> 53);
+        blk[tid] = 0;
+        res[tid] = 0;
+    }
+    const u64 *__restrict__ bs = block_sums + (int64_t)win * NB;
+    const int64_t chunk = (NB + SEED_PICK_THREADS - 1) / SEED_PICK_THREADS;
+    const int64_t lo = tid * chunk < NB ? tid * chunk : NB, hi = lo + chunk < NB ? lo + chunk : NB;
+    u64 cs = 0;
+    for (int64_t i = lo; i < hi; ++i) cs += bs[i];
+    const u64 incl = block_scan_u64(cs, wsum), excl = incl - cs;       // (its barriers also publish tgt and acc_c)
+    for (int t = 0; t < T_next; ++t) {
+        const u64 tg = tgt[t];
+        if (tg >= excl && tg < incl) {                   // one thread: the chunks partition [0, pot) and tg < pot
+            u64 run = excl;
+            for (int64_t i = lo; i < hi; ++i) {
+                const u64 b = bs[i];
+                if (tg < run + b) { blk[t] = i; res[t] = tg - run; break; }
+                run += b;
+            }
+        }
+    }
+    __syncthreads();
+    // inside that span: the winner's weights again, by the sweep's expression, scanned to the first segment whose running sum exceeds the target
+    const int F = tok_seed_f(fbase, *amax);
+    for (int t = 0; t < T_next; ++t) {
+        const int c = (int)(blk[t] / B);
+        const int64_t p = (blk[t] % B) * SEED_SPAN + tid;
+        float v[K];
+#pragma unroll
+        for (int e = 0; e < K; ++e) v[e] = 0.f;
+        u64 qv = 0;
+        if (p < n_seg) {
+            const TokSeg g = tok_locate(st, c, p);
+            tok_load<K>(st, c, g, v);
+            const float d = tok_d2<K>(v, acc_c);
+            const float cl = step >= 1 ? closest[(int64_t)c * n_seg + p] : __builtin_inff();
+            qv = tok_quant(d < cl ? d : cl, F);
+        }
+        const u64 run = block_scan_u64(qv, wsum);
+        const u64 r = res[t];
+        const bool hit = potw ? (qv != 0 && run > r && run - qv <= r) : tid == 0;      // pot == 0: g = 0, what searchsorted returns there
+        if (hit) {
+            cand_g[t] = (int64_t)c * n_seg + p;
+#pragma unroll
+            for (int e = 0; e < K; ++e) cand_c[t * K + e] = v[e];
+        }
+    }
+}
+
+// =====================================================================================================
 // decode: one thread per segment, written back in the store's layout and cut at the run's length
 // =====================================================================================================
 template <int K>
@@ -355,7 +587,64 @@ int ecgvit_tok_update(const float *x, const int64_t *src_off, int64_t lead_strid
     return ECGVIT_OK;
 }
 
-int ecgvit_tok_decode(float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
+static inline bool tok_seed_shape_ok(int C, int64_t n_seg, int V, int k, int n_trials) {
+    return tok_table_ok(V) && (k == 8 || k == 16 || k == 32) && C >= 1 && C <= 65535 && n_seg >= 1 && n_trials >= 1 && n_trials <= SEED_TMAX &&
+           n_seg <= 0xFFFFFFFFll / C && (int64_t)V <= (int64_t)C * n_seg;      // C * n_seg >= 2^32: past what the integer potentials admit
+}
+
+int64_t ecgvit_tok_seed_workspace(int C, int64_t n_seg, int V, int k, int n_trials) {
+    if (!tok_seed_shape_ok(C, n_seg, V, k, n_trials)) return 0;
+    const int64_t NB = (n_seg + SEED_SPAN - 1) / SEED_SPAN * C;
+    return SEED_WS_SUMS + (int64_t)n_trials * NB * 8 + (((int64_t)C * n_seg * 4 + 7) & ~7ll);
+}
+
+int ecgvit_tok_seed(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
+                    const int64_t *dst_off, int64_t dst_stride, int R, int C, int64_t n_seg, int k, int pad, int V, int n_trials, int64_t first,
+                    const uint64_t *u53, float *centers, int64_t *indices, uint64_t *trace, void *workspace, int keep_amax, void *stream) {
+    if (!tok_store_ok(x, src_off, raw_len, seg_cum, dst_off, R, C, n_seg, k, pad) || !tok_seed_shape_ok(C, n_seg, V, k, n_trials) ||
+        first < 0 || first >= (int64_t)C * n_seg || (V > 1 && !tok_al(u53, 8)) || !tok_al(centers, 4) || !tok_al(indices, 8) ||
+        (trace && !tok_al(trace, 8)) || !tok_al(workspace, 8) || (keep_amax != 0 && keep_amax != 1))
+        return ECGVIT_EINVAL;
+    const int64_t B = (n_seg + SEED_SPAN - 1) / SEED_SPAN, NB = B * C, ablocks = (n_seg + TOK_THREADS - 1) / TOK_THREADS;
+    if (ablocks > 0x7FFFFFFFll) return ECGVIT_EINVAL;
+    char *ws = reinterpret_cast<char *>(workspace);
+    uint32_t *amax = reinterpret_cast<uint32_t *>(ws);
+    int64_t *cand_g = reinterpret_cast<int64_t *>(ws + SEED_WS_CAND_G);
+    float *cand_c = reinterpret_cast<float *>(ws + SEED_WS_CAND_C);
+    u64 *block_sums = reinterpret_cast<u64 *>(ws + SEED_WS_SUMS);
+    float *closest = reinterpret_cast<float *>(block_sums + (int64_t)n_trials * NB);
+    int H = 0, log2k = 0;
+    while (((int64_t)C * n_seg) >> H) ++H;               // bit_length(C * n_seg)
+    while ((1 << log2k) < k) ++log2k;
+    const int fbase = 63 - H - 2 - log2k;
+    const TokStore st = tok_store(x, src_off, lead_stride, raw_len, seg_cum, dst_off, dst_stride, R, pad);
+    if (!keep_amax) {
+        if (hipMemsetAsync(amax, 0, 16, as_stream(stream)) != hipSuccess) return ECGVIT_ELAUNCH;
+#define TOK_LAUNCH(KK) hipLaunchKernelGGL(tok_amax_kernel<KK>, dim3((unsigned)ablocks, C), dim3(TOK_THREADS), 0, as_stream(stream), st, n_seg, amax)
+        TOK_BY_K(k, TOK_LAUNCH);
+#undef TOK_LAUNCH
+        ECGVIT_CHECK_LAUNCH();
+    }
+    for (int s = 0; s < V; ++s) {
+        const int T = s ? n_trials : 1, T_next = s + 1 < V ? n_trials : 0;
+        const u64 *u = T_next ? reinterpret_cast<const u64 *>(u53) + (int64_t)s * n_trials : nullptr;
+#define TOK_LAUNCH(KK)                                                                                                                          \
+    hipLaunchKernelGGL(tok_seed_sweep_kernel<KK>, dim3((unsigned)B, C), dim3(TOK_THREADS), 0, as_stream(stream), st, n_seg, s, T, first, centers, \
+                       cand_c, cand_g, closest, block_sums, NB, amax, fbase)
+        TOK_BY_K(k, TOK_LAUNCH);
+#undef TOK_LAUNCH
+        ECGVIT_CHECK_LAUNCH();
+#define TOK_LAUNCH(KK)                                                                                                                      \
+    hipLaunchKernelGGL(tok_seed_pick_kernel<KK>, dim3(1), dim3(SEED_PICK_THREADS), 0, as_stream(stream), st, n_seg, B, NB, s, T, T_next, n_trials, \
+                       u, closest, block_sums, cand_c, cand_g, centers, indices, reinterpret_cast<u64 *>(trace), amax, fbase)
+        TOK_BY_K(k, TOK_LAUNCH);
+#undef TOK_LAUNCH
+        ECGVIT_CHECK_LAUNCH();
+    }
+    return ECGVIT_OK;
+}
+
+int ecgvit_tok_decode(float *out,const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
                       const int64_t *dst_off, int64_t dst_stride, int R, int C, int64_t n_seg, int k, const int32_t *ids, const float *means,
                       const float *centers, int V, void *stream) {
     if (!tok_store_ok(out, src_off, raw_len, seg_cum, dst_off, R, C, n_seg, k, 0) || !tok_table_ok(V) || !tok_al(ids, 4) || !tok_al(means, 4) ||

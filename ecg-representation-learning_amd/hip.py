@@ -136,6 +136,8 @@ SIGNATURES = {
     'ecgvit_tok_assign': (c_int, [_P, _P, _L, _P, _P, _P, _L, _I, _I, _L, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     'ecgvit_tok_workspace': (c_int64, [_I, _I]),
     'ecgvit_tok_update': (c_int, [_P, _P, _L, _P, _P, _P, _L, _I, _I, _L, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
+    'ecgvit_tok_seed_workspace': (c_int64, [_I, _L, _I, _I, _I]),
+    'ecgvit_tok_seed': (c_int, [_P, _P, _L, _P, _P, _P, _L, _I, _I, _L, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P, _I, _P]),
     'ecgvit_tok_decode': (c_int, [_P, _P, _L, _P, _P, _P, _L, _I, _I, _L, _I, _P, _P, _P, _I, _P]),
     'ecgvit_denoise_workspace': (c_int64, [_I, _I, _I]),
     'ecgvit_filtfilt': (c_int, [_P, _P, _P, _L, _P, _I, _I, _I, _I, POINTER(c_double), POINTER(c_double), POINTER(c_double), _I, _P, _P]),

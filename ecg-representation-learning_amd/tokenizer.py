@@ -5,7 +5,9 @@ every lead is cut into k-sample segments, each segment loses its mean, the segme
 (`csrc/tokenize.hip`) that read a resident record store in place; the host side here builds address tables, runs the Lloyd loop and keeps the
 vocabulary.  There is no CPU fallback: host tensors raise.
 
-Not built: `save` / pickling, the plots, the four non-k-means clusterings and k-means++ seeding (DESIGN.md says why).
+k-means++ seeding (the reference's default `init`) is a kernel pair too: `EcgTokenizer.kmeans_plusplus`, and `init=KMeansPlusPlus()` in `fit`.
+
+Not built: `save` / pickling, the plots and the four non-k-means clusterings (DESIGN.md says why).
 """
 import numpy as np
 import torch
@@ -15,6 +17,8 @@ from .records import DeviceTables, check_device_store, select_records
 SEGMENT_SIZES = (8, 16, 32)
 PADS = {'zero': 0, 'shift': 1}
 MAX_CLUSTERS = 65536
+MAX_LOCAL_TRIALS = 16
+SEED_SPAN = 1024            # consecutive positions of one lead per workgroup of the seeding's sweep (csrc/tokenize.hip)
 D_CLS_TH = dict(hierarchical='distance_threshold', dbscan='eps', optics='max_eps', birch='threshold', kmeans='n_clusters')   # ecg_tokenizer.py:72-78
 
 
@@ -43,6 +47,29 @@ class _Store(DeviceTables):
 
     def new(self, dtype):
         return torch.empty(self.out_shape, dtype=dtype, device=self.x.device)
+
+
+def check_local_trials(n_local_trials):
+    if n_local_trials is not None and not (isinstance(n_local_trials, (int, np.integer)) and 1 <= n_local_trials <= MAX_LOCAL_TRIALS):
+        raise ValueError(f'n_local_trials = {n_local_trials!r}: None (2 + int(log(n_clusters))) or an int from 1 to {MAX_LOCAL_TRIALS}')
+    return n_local_trials
+
+
+class KMeansPlusPlus:
+    """`fit(..., cls_kwargs=dict(init=KMeansPlusPlus(), ...))`: every restart is seeded on the device by `EcgTokenizer.kmeans_plusplus`'s kernels
+    (sklearn's greedy k-means++; n_local_trials as there, None = 2 + int(log(n_clusters)), at most 16).  An object, not the string: the string
+    `'k-means++'` promises sklearn's random stream as well, which the device does not reproduce, and stays refused."""
+
+    def __init__(self, n_local_trials=None):
+        self.n_local_trials = check_local_trials(n_local_trials)
+
+    def __repr__(self):
+        return f'{self.__class__.__qualname__}(n_local_trials={self.n_local_trials})'
+
+    def trials(self, V):
+        """the trials per centre for a table of V rows: sklearn's default rule, held to what the kernels take"""
+        T = 2 + int(np.log(V)) if self.n_local_trials is None else int(self.n_local_trials)
+        return min(T, MAX_LOCAL_TRIALS)
 
 
 def check_lengths(lengths, k, pad):
@@ -151,12 +178,15 @@ class EcgTokenizer:
             raise ValueError('no signal given')
         return _Store(sig, np.arange(rows, dtype=np.int64) * L, np.full(rows, L, np.int64), L, 1, False, self.k, self.pad)
 
-    def _record_store(self, sigs, offsets, idxs):
-        """(n, 12, L) records or a ragged (12, S_total) store with offsets, and a subset of either: the convention and validator of `records.py`"""
+    def _record_store(self, sigs, offsets, idxs, n_clusters=None):
+        """(n, 12, L) records or a ragged (12, S_total) store with offsets, and a subset of either: the convention and validator of `records.py`.
+        n_clusters: held against the segment count (a seeding chooses that many segments), before a device is asked for"""
         if not isinstance(sigs, torch.Tensor):
             raise ValueError('signals must be a float32 device tensor (no CPU fallback exists)')
         s = select_records(sigs, offsets, idxs)
         check_lengths(s.raw_len, self.k, self.pad)
+        if n_clusters is not None and n_clusters > s.C * int((s.raw_len // self.k + 1).sum()):
+            raise ValueError(f'n_clusters = {n_clusters} exceeds the {s.C * int((s.raw_len // self.k + 1).sum())} segments of the store')
         return _Store(sigs, s.src_off, s.raw_len, s.stride, s.C, not s.rect, self.k, self.pad)
 
     # ---- kernels ------------------------------------------------------------------------------------
@@ -170,6 +200,52 @@ class EcgTokenizer:
         from .hip import lib, check, ptr, stream
         check(lib().ecgvit_tok_update(*st.args(), st.pad, ptr(ids), ptr(table), table.shape[0], ptr(lens), ptr(ws), int(keep_amax), stream()),
               'ecgvit_tok_update')
+
+    def _seed(self, st, V, T, first, u53, trace=False, ws=None, keep_amax=False):
+        """one k-means++ seeding, enqueued whole: -> (centres (V, k) f32, indices (V,) int64 [g = c * n_seg + p], trace (V - 1, T, 2) int64 or
+        None, the workspace), device tensors.  u53: (V - 1, T) uint64 host array, floor(u 2^53).  keep_amax: `ws` comes from a seeding over this
+        very store, whose absolute maximum it still holds"""
+        from .hip import lib, check, ptr, stream
+        dev = st.x.device
+        nbytes = lib().ecgvit_tok_seed_workspace(st.C, st.n_seg, V, st.k, T)
+        if nbytes == 0:
+            raise ValueError(f'a seeding of {V} centres with {T} trials over {st.C} x {st.n_seg} segments is not supported (1 to {MAX_LOCAL_TRIALS} '
+                             f'trials, n_clusters at most the segment count, fewer than 2^32 segments)')
+        if ws is None:
+            ws, keep_amax = torch.empty(nbytes // 8, dtype=torch.int64, device=dev), False
+        u53 = np.ascontiguousarray(u53, np.uint64).reshape(V - 1, T)
+        if u53.size and int(u53.max()) >= 2 ** 53:
+            raise ValueError('u53 holds floor(u 2^53) of uniform draws u in [0, 1)')
+        u_d = torch.from_numpy(u53.view(np.int64).reshape(-1).copy()).to(dev) if u53.size else None
+        centers = torch.empty((V, st.k), dtype=torch.float32, device=dev)
+        indices = torch.empty(V, dtype=torch.int64, device=dev)
+        tr = torch.zeros((V - 1, T, 2), dtype=torch.int64, device=dev) if trace else None
+        check(lib().ecgvit_tok_seed(*st.args(), st.pad, V, T, int(first), ptr(u_d), ptr(centers), ptr(indices), ptr(tr), ptr(ws), int(keep_amax),
+                                    stream()), 'ecgvit_tok_seed')
+        return centers, indices, tr, ws
+
+    @staticmethod
+    def _seed_draws(rng, total, V, T):
+        """what one seeding takes from the generator, in this order: the first centre, then a (V - 1, T) block of uniforms"""
+        first = int(rng.integers(total))
+        return first, np.floor(rng.random((V - 1, T)) * 2.0 ** 53).astype(np.uint64)
+
+    def kmeans_plusplus(self, sigs, n_clusters, random_state=None, n_local_trials=None, offsets=None, idxs=None):
+        """`sklearn.cluster.kmeans_plusplus` over the mean-removed segments of a store `fit` takes -> (centers (V, k) f32, indices (V,) int64),
+        numpy arrays; index g = c * n_seg + p is segment p of lead c, counted over the selected records in order.  sklearn's greedy algorithm
+        (n_local_trials candidates per centre, drawn in proportion to the squared distance to the nearest chosen centre; the one that leaves
+        the smallest potential is kept) with integer sums (include/ecgvit_hip.h), not sklearn's random stream: `random_state` seeds
+        `np.random.default_rng` (a Generator is used as it is), which gives the first centre and then (V - 1, n_local_trials) uniforms."""
+        V = int(n_clusters)
+        if not 1 <= V <= MAX_CLUSTERS:
+            raise ValueError(f'n_clusters = {V}: 1 to {MAX_CLUSTERS} are supported')
+        T = KMeansPlusPlus(n_local_trials).trials(V)
+        st = self._record_store(sigs, offsets, idxs, n_clusters=V)
+        rng = np.random.default_rng(random_state)
+        with torch.cuda.device(sigs.device):
+            first, u53 = self._seed_draws(rng, st.C * st.n_seg, V, T)
+            centers, indices, _, _ = self._seed(st, V, T, first, u53)
+            return centers.cpu().numpy(), indices.cpu().numpy()
 
     # ---- encode / decode ----------------------------------------------------------------------------
     def __call__(self, sig, th=None, offsets=None):
@@ -270,7 +346,8 @@ class EcgTokenizer:
         """k-means over the mean-removed segments of `sigs`: (n, 12, L) float32 device records, or a ragged (12, S_total) store with `offsets`;
         `idxs` selects records without a copy (the record-store convention of `records.py`).
         cls_kwargs: n_clusters (required), max_iter=256, n_init=1, random_state=None, init='random' (n_clusters distinct segments drawn by a
-        seeded host generator) or a (n_clusters, k) array (Lloyd from a given start is deterministic).  Lloyd iterations are assign then update;
+        seeded host generator), a `KMeansPlusPlus()` object (every restart seeded on the device, `kmeans_plusplus`; with n_init=8 the
+        reference's default configuration) or a (n_clusters, k) array (Lloyd from a given start is deterministic).  Lloyd iterations are assign then update;
         they stop when an iteration changes no id, or at max_iter; n_init > 1 keeps the run of lowest inertia.  A centre that loses every
         segment keeps its value with size 0.  Label order is the clustering's own, as in the reference; nothing is reordered."""
         if method != 'kmeans':
@@ -289,23 +366,33 @@ class EcgTokenizer:
             raise ValueError(f'n_clusters = {V}: 1 to {MAX_CLUSTERS} are supported')
         if max_iter < 1 or n_init < 1:
             raise ValueError('max_iter and n_init must be at least 1')
-        fixed = None
+        fixed = plus = None
         if isinstance(init, str):
             if init != 'random':
-                raise NotImplementedError(f"init = {init!r}: 'random' or a (n_clusters, k) array are supported (exact k-means++ seeding is n_clusters dependent passes over the store)")
+                raise NotImplementedError(f"init = {init!r}: 'random', a KMeansPlusPlus() object (k-means++ seeding on the device: sklearn's algorithm, "
+                                          f"not the random stream the string promises) or a (n_clusters, k) array are supported")
+        elif isinstance(init, KMeansPlusPlus):
+            plus = init.trials(V)
         else:
             fixed = np.ascontiguousarray(init.detach().cpu().numpy() if isinstance(init, torch.Tensor) else init, dtype=np.float32)
             if fixed.shape != (V, self.k):
                 raise ValueError(f'init must be ({V}, {self.k}), got {fixed.shape}')
-        st = self._record_store(sigs, offsets, idxs)
+        st = self._record_store(sigs, offsets, idxs, n_clusters=V if plus else None)
         rng = np.random.default_rng(kw['random_state'])
-        best = None
+        best = seed_ws = None
         with torch.cuda.device(sigs.device):
             from .hip import lib
             ws = torch.empty(lib().ecgvit_tok_workspace(V, self.k) // 8, dtype=torch.int64, device=sigs.device)
             ws_state = dict(amax=False)
             for _ in range(1 if fixed is not None else n_init):
-                table = torch.from_numpy(fixed.copy()).to(sigs.device) if fixed is not None else self._random_init(st, V, rng)
+                if plus:                # the table stays on the device; the seeding's sweep for the absolute maximum serves every update too
+                    first, u53 = self._seed_draws(rng, st.C * st.n_seg, V, plus)
+                    table, _, _, seed_ws = self._seed(st, V, plus, first, u53, ws=seed_ws, keep_amax=seed_ws is not None)
+                    if not ws_state['amax']:
+                        ws[-2:].copy_(seed_ws[:2])
+                        ws_state['amax'] = True
+                else:
+                    table = torch.from_numpy(fixed.copy()).to(sigs.device) if fixed is not None else self._random_init(st, V, rng)
                 run = self._lloyd(st, table, max_iter, ws, ws_state)
                 if best is None or run[2] < best[2]:
                     best = run

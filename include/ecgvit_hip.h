@@ -543,6 +543,37 @@ int64_t ecgvit_tok_workspace(int V, int k);
 int ecgvit_tok_update(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
                       const int64_t *dst_off, int64_t dst_stride, int R, int C, int64_t n_seg, int k, int pad, const int32_t *ids,
                       float *centers, int V, int64_t *lens, void *workspace, int keep_amax, void *stream);
+/* k-means++ seeding: sklearn.cluster.kmeans_plusplus (the greedy `_kmeans_plusplus`) over the mean-removed segments of the store, with the
+ * generator's draws handed in and every sum an integer.  It is sklearn's algorithm, not its random stream.
+ *   segment index   g = c * n_seg + p: lead c, position p among that lead's segments in record order -- the same for a rectangle, a ragged
+ *                   store, an idxs subset and its compact copy.
+ *   distance        d2 = sum_e (s_e - c_e)^2 in f32, UNFUSED: every difference, product and addition rounds on its own, in sample order from
+ *                   the first product; s as every tokenizer kernel loads it (the f32 mean rule above).  closest(g) = the smallest d2 to the
+ *                   centres chosen so far, taken with a strict < from +inf (a NaN distance changes nothing).
+ *   weight          q = rint(d2 * 2^F) as uint64, computed in f64 where the product is exact (ties to even: a distance of half a unit or less
+ *                   weighs 0 and cannot be drawn); F = 63 - H - (2 E + 2 + log2 k) with 2^(E - 1) <= A < 2^E for the absolute maximum A of the
+ *                   mean-removed samples (the sweep of ecgvit_tok_update, its exponent rule) and H = bit_length(C * n_seg).  d2 <= k (2 A)^2
+ *                   < 2^(2 E + 2 + log2 k), so q <= 2^(63 - H) and every potential (the sum of q over all segments) is below 2^63: no overflow
+ *                   check exists.  C * n_seg >= 2^32 is refused.  The unit 2^-F is 2^-(61 - H) of k (2 A)^2: at 2^28 segments and k = 8,
+ *                   2^-30 of 32 A^2.  A segment whose distance is not finite (it holds a non-finite sample) weighs 0.
+ *   step 0          centre 0 is segment `first` (0 <= first < C * n_seg).
+ *   step c >= 1     with pot = the potential under centres 0 .. c - 1, trial t (0 <= t < n_trials, 1 .. 16) draws target =
+ *                   (u53[(c - 1) * n_trials + t] * pot) >> 53 from the 117-bit product (u53: device uint64, each below 2^53 -- floor(u 2^53) of
+ *                   a uniform u in [0, 1)); its candidate is the smallest g whose inclusive running sum of q exceeds the target (a segment of
+ *                   weight 0 is never drawn), and g = 0 when pot == 0 (every segment coincides with a chosen centre: what sklearn's searchsorted
+ *                   returns there).  The candidate that leaves the smallest potential becomes centre c; equal potentials go to the smaller t.
+ * centers (f32 [V][k]) receives the chosen segments (mean removed, bit for bit what the kernels load), indices (int64 [V]) their g; trace (NULL,
+ * or uint64 [V - 1][n_trials][2]) every trial's candidate g and the potential it leaves.  V <= C * n_seg.  u53 may be NULL when V == 1.
+ * keep_amax == 1: the sweep for A is skipped and the maximum a previous seeding left at the start of this workspace is used again (the first
+ * 16 bytes of the workspace hold what the last 16 bytes of ecgvit_tok_update's hold: the bits of A, then zeros).
+ * 2 V launches after that sweep, all on `stream`: no host read, allocation or synchronisation.  Per centre a sweep reads the store once, updates
+ * closest (4 bytes read and written per segment) and leaves one uint64 per (trial, workgroup of 1024 consecutive positions of one lead); a
+ * one-workgroup pick sums them, takes the argmin and finds the next candidates by a scan of the winner's sums and of one span.  No atomics:
+ * integer addition has no order, so the same arguments give the same bits, and a record gives the same weights in every store form. */
+int64_t ecgvit_tok_seed_workspace(int C, int64_t n_seg, int V, int k, int n_trials);   /* bytes; 0 when unsupported */
+int ecgvit_tok_seed(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
+                    const int64_t *dst_off, int64_t dst_stride, int R, int C, int64_t n_seg, int k, int pad, int V, int n_trials, int64_t first,
+                    const uint64_t *u53, float *centers, int64_t *indices, uint64_t *trace, void *workspace, int keep_amax, void *stream);
 /* out (the store's own layout: lead c of record r at out + src_off[r] + c * lead_stride) = centers[ids] + means, truncated to raw_len[r]
  * samples: the reference's decode plus the mean it adds back (:292).  A segment whose id lies outside [0, V) is written as NaN. */
 int ecgvit_tok_decode(float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,

@@ -9,7 +9,14 @@
       torch beforehand and not timed), and the share of those segments on which it agrees with assign's ids;
   (c) sklearn's `KDTree.query` on the host over a 1 % sample of the segments, scaled by 100 (stated in the row; skipped when sklearn is absent).
 Writes profiles/r19_tokenizer.txt (--out).
-usage: python tools/tokenizer_rate.py [--reps 3] [--records 21837]"""
+--seed: the k-means++ seeding (ecgvit_tok_seed) instead, on the same store at the same two shapes with sklearn's default number of trials T:
+  (d) a whole seeding; a sweep + pick pair, as the difference of a 9-centre and a 1-centre seeding over 8; the sweep and the pick apart, from
+      the kernel durations torch.profiler records for one 9-centre seeding (left out where the profiler reports no kernels);
+  (e) beside it `ecgvit_tok_assign` with a (T + 1)-row table on the same store, which reads the same bytes;
+  (f) `sklearn.cluster.kmeans_plusplus` on the host at a size the host finishes (2 M segments, V = 256, f64) against the device on the same
+      segments (skipped when sklearn is absent).
+Writes profiles/r25_tokenizer_seed.txt (--out).
+usage: python tools/tokenizer_rate.py [--reps 3] [--records 21837] [--seed]"""
 import argparse
 import os
 import sys
@@ -41,19 +48,97 @@ def timed(fn, reps, warmup=1):
     return t0.elapsed_time(t1) / reps
 
 
+def kernel_split(fn):
+    """us per launch of the seeding's two kernels over one call of fn, from torch.profiler's device events; {} where it records none"""
+    from torch.profiler import profile, ProfilerActivity
+    try:
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        out = {}
+        for ev in prof.key_averages():
+            for name in ('tok_seed_sweep_kernel', 'tok_seed_pick_kernel'):
+                total = getattr(ev, 'device_time_total', 0) or getattr(ev, 'cuda_time_total', 0)
+                if name in ev.key and ev.count and total:
+                    n, t = out.get(name, (0, 0.0))
+                    out[name] = (n + ev.count, t + total)
+        return {k: t / n for k, (n, t) in out.items()}
+    except Exception as e:          # a profiler that cannot attach is no reason to lose the table
+        print(f'torch.profiler: {e!r}', flush=True)
+        return {}
+
+
+def seed_table(a, x, lines):
+    for k, V in ((8, 4096), (16, 1024)):
+        tok = E.EcgTokenizer(k=k, pad='shift')
+        st = tok._record_store(x, None, None)
+        nseg = st.C * st.n_seg
+        T = E.KMeansPlusPlus().trials(V)
+        rng = np.random.default_rng(25)
+
+        def seeding(v):
+            first, u53 = tok._seed_draws(rng, nseg, v, T)
+            tok._seed(st, v, T, first, u53)
+        t_whole = timed(lambda: seeding(V), 1, warmup=0)
+        t1, t9 = timed(lambda: seeding(1), a.reps), timed(lambda: seeding(9), a.reps)
+        pair = (t9 - t1) / 8
+        split = kernel_split(lambda: seeding(9))
+        table = tok._random_init(st, T + 1, np.random.default_rng(25))
+        ids, means = st.new(torch.int32), st.new(torch.float32)
+        t_assign = timed(lambda: tok._assign(st, table, ids, means), a.reps)
+        lines.append(f'(d) k = {k}, V = {V}, T = {T}: {nseg} segments')
+        lines.append(f'    whole seeding            {t_whole / 1e3:10.2f} s   = {t_whole / V:8.3f} ms per centre (one run, the sweep for the maximum included)')
+        lines.append(f'    sweep + pick             {pair:10.3f} ms  {nseg / pair / 1e3:9.1f} M segments/s  ({(x.numel() * 4 + 8 * nseg) / 1e9 / (pair * 1e-3):7.0f} GB/s over the store and closest)')
+        if split:
+            lines.append('    apart (torch.profiler)   ' + ', '.join(f'{name} {us / 1e3:.3f} ms' for name, us in sorted(split.items())))
+        else:
+            lines.append('    apart                    not taken: torch.profiler recorded no kernel of the seeding')
+        lines.append(f'(e) ecgvit_tok_assign, a {T + 1}-row table, the same store: {t_assign:10.3f} ms; sweep + pick = x {pair / t_assign:.2f} of it')
+        print('\n'.join(lines[-5:]), flush=True)
+        del ids, means
+    # (f) the host's route, at a size the host finishes
+    k, V, rec = 8, 256, 267                      # 267 x 12 x 626 = 2 005 704 segments
+    tok = E.EcgTokenizer(k=k, pad='shift')
+    sub = x[:rec].contiguous()
+    st = tok._record_store(sub, None, None)
+    T = E.KMeansPlusPlus().trials(V)
+
+    def small():
+        first, u53 = tok._seed_draws(np.random.default_rng(25), st.C * st.n_seg, V, T)
+        tok._seed(st, V, T, first, u53)
+    t_dev = timed(small, a.reps)
+    try:
+        from sklearn.cluster import kmeans_plusplus
+        T_ = sub.shape[-1] // k
+        host = sub[..., :T_ * k].reshape(-1, k)
+        host = (host - host.mean(dim=1, keepdim=True)).cpu().numpy().astype(np.float64)
+        t0 = time.perf_counter()
+        kmeans_plusplus(host, V, random_state=25)
+        t_host = (time.perf_counter() - t0) * 1e3
+        lines.append(f'(f) k = {k}, V = {V}, T = {T}: sklearn.cluster.kmeans_plusplus on the host, {len(host)} whole segments (f64): {t_host / 1e3:8.2f} s; '
+                     f'the device, {st.C * st.n_seg} segments: {t_dev:8.2f} ms = x {t_host / t_dev:.0f}')
+    except ImportError:
+        lines.append(f'(f) sklearn is not installed here: no host row (the device, {st.C * st.n_seg} segments, V = {V}: {t_dev:8.2f} ms)')
+    print(lines[-1], flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--records', type=int, default=21837)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r19_tokenizer.txt'))
+    ap.add_argument('--seed', action='store_true', help='time the k-means++ seeding instead (profiles/r25_tokenizer_seed.txt)')
+    ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, 'profiles', 'r25_tokenizer_seed.txt' if a.seed else 'r19_tokenizer.txt')
     import bench
     n = a.records
     g = torch.Generator(device='cuda').manual_seed(19)
     x = torch.randn((n, C, L), device='cuda', generator=g).mul_(0.7).add_(0.3)
     lines = [f'sources: bench.kernel_source_hash() = {bench.kernel_source_hash()}; {torch.cuda.get_device_name(0)}',
              f'store: {n} x {C} x {L} f32 = {x.numel() * 4 / 1e9:.2f} GB, N(0.3, 0.7^2); {a.reps} launches after one warm-up']
-    for k, V in ((8, 4096), (16, 1024)):
+    if a.seed:
+        seed_table(a, x, lines)
+    for k, V in (() if a.seed else ((8, 4096), (16, 1024))):
         tok = E.EcgTokenizer(k=k, pad='shift')
         st = tok._record_store(x, None, None)
         nseg = st.C * st.n_seg
