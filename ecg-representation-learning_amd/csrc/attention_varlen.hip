@@ -351,13 +351,12 @@ int ecgvit_patch_gather_varlen(const float *x, void *patches, const int32_t *n_t
     const int n = L / P;
     const int64_t per = (int64_t)n * ld;
     const dim3 grid((unsigned)std::min<int64_t>((per + 255) / 256, 1024), (unsigned)B);
-    if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(patch_gather_varlen_kernel<float>, grid, dim3(256), 0, as_stream(stream), x, (float *)patches, n_tok, C, L, P, n, ld);
-    else if (dtype == ECGVIT_BF16)
-        hipLaunchKernelGGL(patch_gather_varlen_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), x, (bf16_t *)patches, n_tok, C, L, P, n, ld);
-    else return ECGVIT_EINVAL;
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        hipLaunchKernelGGL(patch_gather_varlen_kernel<T>, grid, dim3(256), 0, as_stream(stream), x, (T *)patches, n_tok, C, L, P, n, ld);
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
 }
 
 }  // extern "C"

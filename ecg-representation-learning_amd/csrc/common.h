@@ -55,6 +55,13 @@ template <typename T> __device__ __forceinline__ void st16(T *p, const Vec16<T> 
     *reinterpret_cast<decltype(r.v) *>(p) = r.v;
 }
 
+// ---- the launchers' one dtype dispatch: f(T()) with T = the element type of `dtype`; f holds the launch once, written on decltype of its argument
+template <typename F> static inline int dispatch_dtype(int dtype, F &&f) {
+    if (dtype == ECGVIT_F32) return f(float());
+    if (dtype == ECGVIT_BF16) return f(bf16_t());
+    return ECGVIT_EINVAL;
+}
+
 // ---- wave64 / block reductions ---------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -395,13 +395,12 @@ int ecgvit_head_fwd(const void *X, int N, const float *gamma, const float *beta,
                     float *xhat, float *rstd, int B, int d, int K, float eps, int dtype, void *stream) {
     if (B <= 0 || d <= 0 || K <= 0 || N <= 0 || d > 8192) return ECGVIT_EINVAL;
     const size_t lds = (size_t)(d + 4) * 4;
-    if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(head_fwd_kernel<float>, dim3(B), dim3(256), lds, as_stream(stream), (const float *)X, N, gamma, beta, W, bias, logits, xhat, rstd, d, K, eps);
-    else if (dtype == ECGVIT_BF16)
-        hipLaunchKernelGGL(head_fwd_kernel<bf16_t>, dim3(B), dim3(256), lds, as_stream(stream), (const bf16_t *)X, N, gamma, beta, W, bias, logits, xhat, rstd, d, K, eps);
-    else return ECGVIT_EINVAL;
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        hipLaunchKernelGGL(head_fwd_kernel<T>, dim3(B), dim3(256), lds, as_stream(stream), (const T *)X, N, gamma, beta, W, bias, logits, xhat, rstd, d, K, eps);
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
 }
 
 int ecgvit_bce_fwd(const float *logits, const float *labels, const float *weight, float *loss_elem, float *loss_mean, int64_t count,
@@ -433,12 +432,12 @@ int ecgvit_head_bwd(const float *dlogits, const float *xhat, const float *rstd, 
     hipLaunchKernelGGL(head_bwd_finish_kernel, dim3((d + 255) / 256), dim3(256), 0, s, W, gamma, beta, dbias, dW, dgamma, dbeta, d, K);
     ECGVIT_CHECK_LAUNCH();
     const size_t lds = (size_t)(K + d + 4) * 4;
-    if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(head_bwd_x_kernel<float>, dim3(B), dim3(256), lds, s, dlogits, xhat, rstd, gamma, W, (float *)dX, N, d, K);
-    else
-        hipLaunchKernelGGL(head_bwd_x_kernel<bf16_t>, dim3(B), dim3(256), lds, s, dlogits, xhat, rstd, gamma, W, (bf16_t *)dX, N, d, K);
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        hipLaunchKernelGGL(head_bwd_x_kernel<T>, dim3(B), dim3(256), lds, s, dlogits, xhat, rstd, gamma, W, (T *)dX, N, d, K);
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
 }
 
 int64_t ecgvit_sumsq_workspace(int64_t count) { (void)count; return (int64_t)SUMSQ_BLOCKS * 4; }

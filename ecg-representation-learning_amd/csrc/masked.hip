@@ -6,7 +6,28 @@
 
 namespace {
 
-// X[b*n + p] = (masked(b,p) ? mask_token : tok[b*n+p]) + pos[1 + p]; `flag` [B*n] bytes marks masked patches
+// one 16-B vector of X: X[row] = (flag[row] ? mask_token : tok[row]) + pos[1 + p], p = the row's patch index inside its record; `flag` marks
+// the masked rows, one byte each.  pad: a row past its record's patches (padded layout), written as exact zeros, nothing read
+template <typename T>
+__device__ __forceinline__ void mask_embed_vec(const T *__restrict__ tok, const float *__restrict__ mask_token, const float *__restrict__ pos,
+                                               const uint8_t *__restrict__ flag, T *__restrict__ X, int64_t row, int p, bool pad, int c0, int d) {
+    constexpr int VN = Vec16<T>::N;
+    Vec16<T> o;
+    if (pad) {
+#pragma unroll
+        for (int k = 0; k < VN; ++k) o.set(k, 0.f);
+    } else if (flag[row]) {
+#pragma unroll
+        for (int k = 0; k < VN; ++k) o.set(k, mask_token[c0 + k] + pos[(int64_t)(1 + p) * d + c0 + k]);
+    } else {
+        const Vec16<T> v = ld16(tok + row * d + c0);
+#pragma unroll
+        for (int k = 0; k < VN; ++k) o.set(k, v.get(k) + pos[(int64_t)(1 + p) * d + c0 + k]);
+    }
+    st16(X + row * d + c0, o);
+}
+
+// uniform form (n patches per record, row b * n + p): one flat grid-stride walk over the vectors of X
 template <typename T>
 __global__ __launch_bounds__(256) void mask_embed_kernel(const T *__restrict__ tok, const float *__restrict__ mask_token,
                                                          const float *__restrict__ pos, const uint8_t *__restrict__ flag,
@@ -16,89 +37,13 @@ __global__ __launch_bounds__(256) void mask_embed_kernel(const T *__restrict__ t
     const int64_t total = rows * dv;
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t row = i / dv;
-        const int c0 = (int)(i - row * dv) * VN;
-        const int p = (int)(row % n);
-        Vec16<T> o;
-        if (flag[row]) {
-#pragma unroll
-            for (int k = 0; k < VN; ++k) o.set(k, mask_token[c0 + k] + pos[(int64_t)(1 + p) * d + c0 + k]);
-        } else {
-            const Vec16<T> v = ld16(tok + row * d + c0);
-#pragma unroll
-            for (int k = 0; k < VN; ++k) o.set(k, v.get(k) + pos[(int64_t)(1 + p) * d + c0 + k]);
-        }
-        st16(X + row * d + c0, o);
+        mask_embed_vec(tok, mask_token, pos, flag, X, row, (int)(row % n), false, (int)(i - row * dv) * VN, d);
     }
 }
 
-// backward of mask_embed: dtok = dX where NOT masked (else 0); dmasked = dX where masked (else 0) -> its column sum is the
-// mask-token gradient; dpos[1 + p] = sum_b dX[b*n + p]   (dpos row 0 = CLS slot, untouched by the masked trunk: zeroed)
-// One workgroup per (patch p, group of 8 column vectors): its 256 threads are 8 column vectors x 32 batch lanes, so a wave instruction moves
-// 8 records' 128-B segments and n * d / 64 workgroups share the three streams (round 5; the first form -- one THREAD per (p, column vector)
-// walking all B records, 94 workgroups at base -- ran at a third of the HBM rate: 313 us for 0.6 GB).  The batch sum is folded over the 32
-// lanes through LDS in a fixed order: deterministic.
-template <typename T>
-__global__ __launch_bounds__(256) void mask_embed_bwd_kernel(const T *__restrict__ dX, const uint8_t *__restrict__ flag,
-                                                             T *__restrict__ dtok, T *__restrict__ dmasked,
-                                                             float *__restrict__ dpos, int B, int n, int d) {
-    constexpr int VN = Vec16<T>::N;
-    __shared__ float red[32][8][VN];
-    const int dv = d / VN, ngrp = (dv + 7) / 8;
-    const int p = blockIdx.x / ngrp, cg = blockIdx.x - p * ngrp;
-    const int cv = threadIdx.x & 7, bl = threadIdx.x >> 3;
-    const int c0 = (cg * 8 + cv) * VN;
-    const bool live = cg * 8 + cv < dv;
-    float acc[VN];
-#pragma unroll
-    for (int k = 0; k < VN; ++k) acc[k] = 0.f;
-    Vec16<T> zero;
-#pragma unroll
-    for (int k = 0; k < VN; ++k) zero.set(k, 0.f);
-    if (live) {
-        for (int b = bl; b < B; b += 32) {
-            const int64_t row = (int64_t)b * n + p;
-            const Vec16<T> v = ld16(dX + row * d + c0);
-#pragma unroll
-            for (int k = 0; k < VN; ++k) acc[k] += v.get(k);
-            const bool mk = flag[row] != 0;
-            st16(dtok + row * d + c0, mk ? zero : v);
-            st16(dmasked + row * d + c0, mk ? v : zero);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < VN; ++k) red[bl][cv][k] = acc[k];
-    __syncthreads();
-    if (bl == 0 && live) {
-#pragma unroll
-        for (int k = 0; k < VN; ++k) {
-            float s = 0.f;
-            for (int j = 0; j < 32; ++j) s += red[j][cv][k];
-            dpos[(int64_t)(1 + p) * d + c0 + k] = s;
-            if (p == 0) dpos[c0 + k] = 0.f;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void mark_mask_kernel(const int32_t *__restrict__ idx, uint8_t *__restrict__ flag, int B, int n, int m) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= B * m) return;
-    const int b = i / m;
-    const int p = idx[i];
-    if (p >= 0 && p < n) flag[(int64_t)b * n + p] = 1;
-}
-
-// ---- records of unequal length (no CLS row).  Record b holds n_tok[b] patches in the rows tok_off[b] .. tok_off[b] + n_tok[b] - 1 of tok / X / dX:
-// packed (n_pad == 0: tok_off = exclusive prefix sum of n_tok, no other row exists) or padded (n_pad > 0: tok_off[b] = b * n_pad, the rows
-// past n_tok[b] of a record are written as exact zeros and never read).  One kernel text serves both layouts.
-__global__ __launch_bounds__(256) void mark_rows_kernel(const int32_t *__restrict__ row_idx, uint8_t *__restrict__ flag, int count, int64_t M) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    const int64_t r = row_idx[i];
-    if (r >= 0 && r < M) flag[r] = 1;
-}
-
-// X[row] = (flag[row] ? mask_token : tok[row]) + pos[1 + j], j = the row's patch index inside its record.  One grid row per record, its
-// patches strided over the blocks (the shape of embed_finish_ragged_kernel).
+// ---- table form: records of unequal length (no CLS row).  Record b holds n_tok[b] patches in the rows tok_off[b] .. tok_off[b] + n_tok[b] - 1 of
+// tok / X / dX: packed (n_pad == 0: tok_off = exclusive prefix sum of n_tok, no other row exists) or padded (n_pad > 0: tok_off[b] = b * n_pad,
+// the rows past n_tok[b] of a record are written as exact zeros and never read).  One grid row per record, its patches strided over the blocks.
 template <typename T>
 __global__ __launch_bounds__(256) void mask_embed_varlen_kernel(const T *__restrict__ tok, const float *__restrict__ mask_token,
                                                                 const float *__restrict__ pos, const uint8_t *__restrict__ flag,
@@ -110,32 +55,25 @@ __global__ __launch_bounds__(256) void mask_embed_varlen_kernel(const T *__restr
     const int64_t r0 = tok_off[b], total = (int64_t)(n_pad ? n_pad : nb) * dv;
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int j = (int)(i / dv), c0 = (int)(i - (int64_t)j * dv) * VN;
-        const int64_t row = r0 + j;
-        Vec16<T> o;
-        if (j >= nb) {
-#pragma unroll
-            for (int k = 0; k < VN; ++k) o.set(k, 0.f);
-        } else if (flag[row]) {
-#pragma unroll
-            for (int k = 0; k < VN; ++k) o.set(k, mask_token[c0 + k] + pos[(int64_t)(1 + j) * d + c0 + k]);
-        } else {
-            const Vec16<T> v = ld16(tok + row * d + c0);
-#pragma unroll
-            for (int k = 0; k < VN; ++k) o.set(k, v.get(k) + pos[(int64_t)(1 + j) * d + c0 + k]);
-        }
-        st16(X + row * d + c0, o);
+        mask_embed_vec(tok, mask_token, pos, flag, X, r0 + j, j, j >= nb, c0, d);
     }
 }
 
-// its backward, in the shape of mask_embed_bwd_kernel (a workgroup per (patch p, 8 column vectors), 32 lanes across records, LDS fold in a
-// fixed order): dpos[1 + p] = the sum over the records that hold patch p.  `order` lists the records by falling n_tok (ties by record index:
-// a fixed order), so those records are order[0 .. cnt) with cnt found by bisection -- a workgroup of a tail position touches its few
-// contributors and never walks the B records to find them.  Padded layout: the rows (b, p) with p >= n_tok[b] get zeros in dtok / dmasked.
-template <typename T>
-__global__ __launch_bounds__(256) void mask_embed_varlen_bwd_kernel(const T *__restrict__ dX, const uint8_t *__restrict__ flag,
-                                                                    T *__restrict__ dtok, T *__restrict__ dmasked, float *__restrict__ dpos,
-                                                                    const int32_t *__restrict__ n_tok, const int32_t *__restrict__ tok_off,
-                                                                    const int32_t *__restrict__ order, int B, int n_pad, int d) {
+// backward of mask_embed: dtok = dX where NOT masked (else 0); dmasked = dX where masked (else 0) -> its column sum is the
+// mask-token gradient; dpos[1 + p] = sum_b dX[row of (b, p)]   (dpos row 0 = CLS slot, untouched by the masked trunk: zeroed)
+// One workgroup per (patch p, group of 8 column vectors): its 256 threads are 8 column vectors x 32 batch lanes, so a wave instruction moves
+// 8 records' 128-B segments and n * d / 64 workgroups share the three streams (round 5; the first form -- one THREAD per (p, column vector)
+// walking all B records, 94 workgroups at base -- ran at a third of the HBM rate: 313 us for 0.6 GB).  The batch sum is folded over the 32
+// lanes through LDS in a fixed order: deterministic.
+// One body, forms by template: the lanes walk contributor i = lane, lane + 32, ... of cnt.  The uniform form has cnt = B, contributor i =
+// record i, row i * n + p.  TABLES: `order` lists the records by falling n_tok (ties by record index: a fixed order), so the records that hold
+// patch p are order[0 .. cnt) with cnt found by bisection -- a workgroup of a tail position touches its few contributors and never walks the
+// B records to find them; padded layout (n_pad != 0): the rows (b, p) with p >= n_tok[b] get zeros in dtok / dmasked.
+template <typename T, bool TABLES>
+__device__ __forceinline__ void mask_embed_bwd_body(const T *__restrict__ dX, const uint8_t *__restrict__ flag, T *__restrict__ dtok,
+                                                    T *__restrict__ dmasked, float *__restrict__ dpos, const int32_t *__restrict__ n_tok,
+                                                    const int32_t *__restrict__ tok_off, const int32_t *__restrict__ order, int B, int n, int n_pad,
+                                                    int d) {
     constexpr int VN = Vec16<T>::N;
     __shared__ float red[32][8][VN];
     const int dv = d / VN, ngrp = (dv + 7) / 8;
@@ -143,11 +81,15 @@ __global__ __launch_bounds__(256) void mask_embed_varlen_bwd_kernel(const T *__r
     const int cv = threadIdx.x & 7, bl = threadIdx.x >> 3;
     const int c0 = (cg * 8 + cv) * VN;
     const bool live = cg * 8 + cv < dv;
-    int cnt = 0, hi = B;
-    while (cnt < hi) {   // first position of `order` whose record is too short for patch p
-        const int mid = (cnt + hi) >> 1;
-        if (n_tok[order[mid]] > p) cnt = mid + 1;
-        else hi = mid;
+    int cnt = B;
+    if (TABLES) {
+        int hi = B;
+        cnt = 0;
+        while (cnt < hi) {   // first position of `order` whose record is too short for patch p
+            const int mid = (cnt + hi) >> 1;
+            if (n_tok[order[mid]] > p) cnt = mid + 1;
+            else hi = mid;
+        }
     }
     float acc[VN];
 #pragma unroll
@@ -157,7 +99,7 @@ __global__ __launch_bounds__(256) void mask_embed_varlen_bwd_kernel(const T *__r
     for (int k = 0; k < VN; ++k) zero.set(k, 0.f);
     if (live) {
         for (int i = bl; i < cnt; i += 32) {
-            const int64_t row = (int64_t)tok_off[order[i]] + p;
+            const int64_t row = (TABLES ? (int64_t)tok_off[order[i]] : (int64_t)i * n) + p;
             const Vec16<T> v = ld16(dX + row * d + c0);
 #pragma unroll
             for (int k = 0; k < VN; ++k) acc[k] += v.get(k);
@@ -165,7 +107,7 @@ __global__ __launch_bounds__(256) void mask_embed_varlen_bwd_kernel(const T *__r
             st16(dtok + row * d + c0, mk ? zero : v);
             st16(dmasked + row * d + c0, mk ? v : zero);
         }
-        if (n_pad) {
+        if (TABLES && n_pad) {
             for (int i = cnt + bl; i < B; i += 32) {
                 const int64_t row = (int64_t)tok_off[order[i]] + p;
                 st16(dtok + row * d + c0, zero);
@@ -185,6 +127,30 @@ __global__ __launch_bounds__(256) void mask_embed_varlen_bwd_kernel(const T *__r
             if (p == 0) dpos[c0 + k] = 0.f;
         }
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void mask_embed_bwd_kernel(const T *__restrict__ dX, const uint8_t *__restrict__ flag,
+                                                             T *__restrict__ dtok, T *__restrict__ dmasked,
+                                                             float *__restrict__ dpos, int B, int n, int d) {
+    mask_embed_bwd_body<T, false>(dX, flag, dtok, dmasked, dpos, nullptr, nullptr, nullptr, B, n, 0, d);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void mask_embed_varlen_bwd_kernel(const T *__restrict__ dX, const uint8_t *__restrict__ flag,
+                                                                    T *__restrict__ dtok, T *__restrict__ dmasked, float *__restrict__ dpos,
+                                                                    const int32_t *__restrict__ n_tok, const int32_t *__restrict__ tok_off,
+                                                                    const int32_t *__restrict__ order, int B, int n_pad, int d) {
+    mask_embed_bwd_body<T, true>(dX, flag, dtok, dmasked, dpos, n_tok, tok_off, order, B, 0, n_pad, d);
+}
+
+// flag[b * nrow + idx[b * m + k]] = 1 for the m indices of each of nb batches (the indexing of rows_by_index_kernel); an index outside
+// [0, nrow) is ignored.  (B, n, m) marks the patches of a uniform batch, (1, M, m_total) rows of the whole buffer.
+__global__ __launch_bounds__(256) void mark_rows_kernel(const int32_t *__restrict__ idx, uint8_t *__restrict__ flag, int nb, int64_t nrow, int m) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nb * m) return;
+    const int64_t r = idx[i];
+    if (r >= 0 && r < nrow) flag[(i / m) * nrow + r] = 1;
 }
 
 // GATHER: out[b*m + k] = in[b*n + idx[b,k]] ; SCATTER: out[b*n + idx[b,k]] = in[b*m + k]
@@ -241,37 +207,43 @@ inline int grid_ew(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_
 
 extern "C" {
 
+// flag_ws = the 0 / 1 mask of `rows` rows: cleared, then (nb, nrow, m) marked as mark_rows_kernel reads them
+static int mark_flags(void *flag_ws, int64_t rows, const int32_t *idx, int nb, int64_t nrow, int m, hipStream_t s) {
+    if (hipMemsetAsync(flag_ws, 0, (size_t)rows, s) != hipSuccess) return ECGVIT_ELAUNCH;
+    if (m > 0) {
+        hipLaunchKernelGGL(mark_rows_kernel, dim3((nb * m + 255) / 256), dim3(256), 0, s, idx, (uint8_t *)flag_ws, nb, nrow, m);
+        ECGVIT_CHECK_LAUNCH();
+    }
+    return ECGVIT_OK;
+}
+
 int ecgvit_mask_embed_finish(const void *tok, const float *mask_token, const float *pos, const int32_t *idx, void *X,
                                 void *flag_ws, int B, int n, int m, int d, int dtype, void *stream) {
     if (B <= 0 || n <= 0 || m < 0 || m > n || d <= 0 || d % 8 != 0 || !flag_ws) return ECGVIT_EINVAL;
     hipStream_t s = as_stream(stream);
-    if (hipMemsetAsync(flag_ws, 0, (size_t)B * n, s) != hipSuccess) return ECGVIT_ELAUNCH;
-    if (m > 0) {
-        hipLaunchKernelGGL(mark_mask_kernel, dim3((B * m + 255) / 256), dim3(256), 0, s, idx, (uint8_t *)flag_ws, B, n, m);
-        ECGVIT_CHECK_LAUNCH();
-    }
     const int64_t rows = (int64_t)B * n;
-    if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(mask_embed_kernel<float>, dim3(grid_ew(rows * d / 4)), dim3(256), 0, s, (const float *)tok, mask_token, pos, (const uint8_t *)flag_ws, (float *)X, rows, n, d);
-    else if (dtype == ECGVIT_BF16)
-        hipLaunchKernelGGL(mask_embed_kernel<bf16_t>, dim3(grid_ew(rows * d / 8)), dim3(256), 0, s, (const bf16_t *)tok, mask_token, pos, (const uint8_t *)flag_ws, (bf16_t *)X, rows, n, d);
-    else return ECGVIT_EINVAL;
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    const int rc = mark_flags(flag_ws, rows, idx, B, n, m, s);
+    if (rc != ECGVIT_OK) return rc;
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        hipLaunchKernelGGL(mask_embed_kernel<T>, dim3(grid_ew(rows * d / Vec16<T>::N)), dim3(256), 0, s, (const T *)tok, mask_token, pos,
+                           (const uint8_t *)flag_ws, (T *)X, rows, n, d);
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
 }
 
 int ecgvit_mask_embed_bwd(const void *dX, const void *flag_ws, void *dtok, void *dmasked, float *dpos, int B, int n, int d,
                           int dtype, void *stream) {
     if (B <= 0 || n <= 0 || d <= 0 || d % 8 != 0 || !flag_ws) return ECGVIT_EINVAL;
-    const int dv = d / (dtype == ECGVIT_F32 ? 4 : 8);
-    const int grid = n * ((dv + 7) / 8);   // one workgroup per (patch, 8 column vectors)
-    if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(mask_embed_bwd_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), (const float *)dX, (const uint8_t *)flag_ws, (float *)dtok, (float *)dmasked, dpos, B, n, d);
-    else if (dtype == ECGVIT_BF16)
-        hipLaunchKernelGGL(mask_embed_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), (const bf16_t *)dX, (const uint8_t *)flag_ws, (bf16_t *)dtok, (bf16_t *)dmasked, dpos, B, n, d);
-    else return ECGVIT_EINVAL;
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        const int grid = n * ((d / Vec16<T>::N + 7) / 8);   // one workgroup per (patch, 8 column vectors)
+        hipLaunchKernelGGL(mask_embed_bwd_kernel<T>, dim3(grid), dim3(256), 0, as_stream(stream), (const T *)dX, (const uint8_t *)flag_ws, (T *)dtok,
+                           (T *)dmasked, dpos, B, n, d);
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
 }
 
 int ecgvit_mask_embed_varlen_fwd(const void *tok, const float *mask_token, const float *pos, const int32_t *row_idx, void *X, void *flag_ws,
@@ -281,52 +253,45 @@ int ecgvit_mask_embed_varlen_fwd(const void *tok, const float *mask_token, const
         !tok_off || (m_total > 0 && !row_idx) || (n_pad != 0 && M != (int64_t)B * n_pad))
         return ECGVIT_EINVAL;
     hipStream_t s = as_stream(stream);
-    if (hipMemsetAsync(flag_ws, 0, (size_t)M, s) != hipSuccess) return ECGVIT_ELAUNCH;
-    if (m_total > 0) {
-        hipLaunchKernelGGL(mark_rows_kernel, dim3((m_total + 255) / 256), dim3(256), 0, s, row_idx, (uint8_t *)flag_ws, m_total, M);
+    const int rc = mark_flags(flag_ws, M, row_idx, 1, M, m_total, s);
+    if (rc != ECGVIT_OK) return rc;
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        const int64_t per = (int64_t)(n_pad ? n_pad : N) * d / Vec16<T>::N;
+        const dim3 grid((unsigned)std::min<int64_t>((per + 255) / 256, 1024), (unsigned)B);
+        hipLaunchKernelGGL(mask_embed_varlen_kernel<T>, grid, dim3(256), 0, s, (const T *)tok, mask_token, pos, (const uint8_t *)flag_ws, (T *)X, n_tok,
+                           tok_off, n_pad, d);
         ECGVIT_CHECK_LAUNCH();
-    }
-    const int64_t per = (int64_t)(n_pad ? n_pad : N) * d / (dtype == ECGVIT_F32 ? 4 : 8);
-    const dim3 grid((unsigned)std::min<int64_t>((per + 255) / 256, 1024), (unsigned)B);
-    if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(mask_embed_varlen_kernel<float>, grid, dim3(256), 0, s, (const float *)tok, mask_token, pos, (const uint8_t *)flag_ws, (float *)X, n_tok, tok_off, n_pad, d);
-    else if (dtype == ECGVIT_BF16)
-        hipLaunchKernelGGL(mask_embed_varlen_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t *)tok, mask_token, pos, (const uint8_t *)flag_ws, (bf16_t *)X, n_tok, tok_off, n_pad, d);
-    else return ECGVIT_EINVAL;
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+        return ECGVIT_OK;
+    });
 }
 
 int ecgvit_mask_embed_varlen_bwd(const void *dX, const void *flag_ws, void *dtok, void *dmasked, float *dpos, const int32_t *n_tok,
                                  const int32_t *tok_off, const int32_t *order, int B, int N, int n_pad, int d, int dtype, void *stream) {
     if (B <= 0 || N <= 0 || (n_pad != 0 && n_pad < N) || d <= 0 || d % 8 != 0 || !flag_ws || !n_tok || !tok_off || !order) return ECGVIT_EINVAL;
-    const int dv = d / (dtype == ECGVIT_F32 ? 4 : 8);
-    const int64_t grid = (int64_t)(n_pad ? n_pad : N) * ((dv + 7) / 8);   // one workgroup per (patch, 8 column vectors)
-    if (grid >= (1ll << 31)) return ECGVIT_EINVAL;
-    if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(mask_embed_varlen_bwd_kernel<float>, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), (const float *)dX, (const uint8_t *)flag_ws, (float *)dtok, (float *)dmasked, dpos, n_tok, tok_off, order, B, n_pad, d);
-    else if (dtype == ECGVIT_BF16)
-        hipLaunchKernelGGL(mask_embed_varlen_bwd_kernel<bf16_t>, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), (const bf16_t *)dX, (const uint8_t *)flag_ws, (bf16_t *)dtok, (bf16_t *)dmasked, dpos, n_tok, tok_off, order, B, n_pad, d);
-    else return ECGVIT_EINVAL;
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        const int64_t grid = (int64_t)(n_pad ? n_pad : N) * ((d / Vec16<T>::N + 7) / 8);   // one workgroup per (patch, 8 column vectors)
+        if (grid >= (1ll << 31)) return ECGVIT_EINVAL;
+        hipLaunchKernelGGL(mask_embed_varlen_bwd_kernel<T>, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), (const T *)dX,
+                           (const uint8_t *)flag_ws, (T *)dtok, (T *)dmasked, dpos, n_tok, tok_off, order, B, n_pad, d);
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
 }
 
 static int rows_by_index(const void *in, const int32_t *idx, void *out, int B, int n, int m, int64_t width, int64_t ld_in,
                          int64_t ld_out, int dtype, void *stream, bool scatter) {
     if (B <= 0 || n <= 0 || m <= 0 || width <= 0 || width % 8 != 0 || ld_in % 8 != 0 || ld_out % 8 != 0) return ECGVIT_EINVAL;
-    hipStream_t s = as_stream(stream);
-    const int vn = dtype == ECGVIT_F32 ? 4 : 8;
-    const int g = grid_ew((int64_t)B * m * width / vn);
-    if (dtype == ECGVIT_F32) {
-        if (scatter) hipLaunchKernelGGL((rows_by_index_kernel<float, true>), dim3(g), dim3(256), 0, s, (const float *)in, idx, (float *)out, B, n, m, (int)width, ld_in, ld_out);
-        else hipLaunchKernelGGL((rows_by_index_kernel<float, false>), dim3(g), dim3(256), 0, s, (const float *)in, idx, (float *)out, B, n, m, (int)width, ld_in, ld_out);
-    } else if (dtype == ECGVIT_BF16) {
-        if (scatter) hipLaunchKernelGGL((rows_by_index_kernel<bf16_t, true>), dim3(g), dim3(256), 0, s, (const bf16_t *)in, idx, (bf16_t *)out, B, n, m, (int)width, ld_in, ld_out);
-        else hipLaunchKernelGGL((rows_by_index_kernel<bf16_t, false>), dim3(g), dim3(256), 0, s, (const bf16_t *)in, idx, (bf16_t *)out, B, n, m, (int)width, ld_in, ld_out);
-    } else return ECGVIT_EINVAL;
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        const int g = grid_ew((int64_t)B * m * width / Vec16<T>::N);
+#define ROWS(S) hipLaunchKernelGGL((rows_by_index_kernel<T, S>), dim3(g), dim3(256), 0, as_stream(stream), (const T *)in, idx, (T *)out, B, n, m, (int)width, ld_in, ld_out)
+        if (scatter) ROWS(true); else ROWS(false);
+#undef ROWS
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
 }
 
 int ecgvit_gather_rows(const void *in, const int32_t *idx, void *out, int B, int n, int m, int64_t width, int64_t ld_in,
@@ -344,12 +309,13 @@ int ecgvit_l1_loss_fwd_bwd(const void *pred, const void *target, float *loss, vo
     if (rows <= 0 || width <= 0 || ld < width || !partial) return ECGVIT_EINVAL;
     const int64_t total = rows * width;
     const int nb = (int)std::min<int64_t>(L1_BLOCKS, (total + 2047) / 2048);
-    if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(l1_loss_kernel<float>, dim3(nb), dim3(256), 0, as_stream(stream), (const float *)pred, (const float *)target, partial, (float *)dpred, gscalar, rows, width, ld);
-    else if (dtype == ECGVIT_BF16)
-        hipLaunchKernelGGL(l1_loss_kernel<bf16_t>, dim3(nb), dim3(256), 0, as_stream(stream), (const bf16_t *)pred, (const bf16_t *)target, partial, (bf16_t *)dpred, gscalar, rows, width, ld);
-    else return ECGVIT_EINVAL;
-    ECGVIT_CHECK_LAUNCH();
+    const int rc = dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        hipLaunchKernelGGL(l1_loss_kernel<T>, dim3(nb), dim3(256), 0, as_stream(stream), (const T *)pred, (const T *)target, partial, (T *)dpred, gscalar, rows, width, ld);
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
+    if (rc != ECGVIT_OK) return rc;
     hipLaunchKernelGGL(l1_finish_kernel, dim3(1), dim3(64), 0, as_stream(stream), partial, nb, loss, 1.0f / (float)total);
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;

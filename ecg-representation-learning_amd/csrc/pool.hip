@@ -89,16 +89,17 @@ int ecgvit_pool_records(const void *x, float *out, const int32_t *n_tok, const i
     if (!x || !out || B <= 0 || N <= 0 || d <= 0 || d % 8 != 0 || d > 2048) return ECGVIT_EINVAL;
     if (mode != 0 && mode != 1) return ECGVIT_EINVAL;
     if ((gamma == nullptr) != (beta == nullptr)) return ECGVIT_EINVAL;
-    if (dtype != ECGVIT_F32 && dtype != ECGVIT_BF16) return ECGVIT_EINVAL;
-    const int nchunk = dtype == ECGVIT_F32 ? (d + 31) / 32 : (d + 63) / 64;
-    if ((int64_t)B * nchunk > 0x7fffffffll) return ECGVIT_EINVAL;
-    if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(pool_records_kernel<float>, dim3(B * nchunk), dim3(POOL_THREADS), 0, as_stream(stream), (const float *)x, out, n_tok,
-                           tok_off, N, d, mode, nchunk);
-    else
-        hipLaunchKernelGGL(pool_records_kernel<bf16_t>, dim3(B * nchunk), dim3(POOL_THREADS), 0, as_stream(stream), (const bf16_t *)x, out, n_tok,
-                           tok_off, N, d, mode, nchunk);
-    ECGVIT_CHECK_LAUNCH();
+    const int rc = dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        constexpr int CW = 8 * Vec16<T>::N;   // the kernel's column chunk
+        const int nchunk = (d + CW - 1) / CW;
+        if ((int64_t)B * nchunk > 0x7fffffffll) return ECGVIT_EINVAL;
+        hipLaunchKernelGGL(pool_records_kernel<T>, dim3(B * nchunk), dim3(POOL_THREADS), 0, as_stream(stream), (const T *)x, out, n_tok, tok_off, N, d,
+                           mode, nchunk);
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
+    if (rc != ECGVIT_OK) return rc;
     if (gamma) {
         hipLaunchKernelGGL(pool_layernorm_kernel, dim3(B), dim3(256), 0, as_stream(stream), out, gamma, beta, d, eps);
         ECGVIT_CHECK_LAUNCH();

@@ -13,35 +13,43 @@ namespace {
 // XF = fused input transforms of the reference data pipeline (preprocess/transform.py, wired at ptb_dataset.py:132-149), applied
 // while the raw record streams through LDS -- no separate pass over the (B, 12, L) tensor:
 //   Normalize    (x - mean[c]) * inv_std[c]                       (transform.py:18-35)
-//   TimeEndPad   samples >= L_raw read as 0 (the record is zero-padded to L = n * P)   (:140-154)
+//   TimeEndPad   samples >= lb read as 0 (the record is zero-padded to n * P samples)   (:140-154)
 //   TimeOut      samples in [t0[b], t0[b] + tlen[b]) are zeroed   (:175-185; train-time augmentation, host-drawn span)
-template <typename T, bool XF>
-__global__ __launch_bounds__(256) void patch_gather_kernel(const float *__restrict__ x, T *__restrict__ out, int C, int L,
-                                                           int P, int n, int PB, int64_t ld, int L_raw,
-                                                           const float *__restrict__ mean, const float *__restrict__ inv_std,
-                                                           const int *__restrict__ t0, const int *__restrict__ tlen) {
-    extern __shared__ __attribute__((aligned(16))) float tile[];  // [C][W+1]
-    const int b = blockIdx.y, p0 = blockIdx.x * PB;
-    const int np = min(PB, n - p0), W = np * P, WS = PB * P + 1;
-    const int Lsrc = XF ? L_raw : L;
-    const float *xb = x + (int64_t)b * C * Lsrc + (int64_t)p0 * P;
+// One body, forms by template.  The form hands in what it knows of its record: xb / lead = the source base and the lead stride, lb = the valid
+// samples, nb = the valid patches, rows = the rows to write, row0 = the first output row.  TABLES (records of unequal length) keeps two early
+// exits: a block past `rows` returns (packed rows), a block past nb writes exact zeros and never reads x (padded rows).
+template <typename T, bool XF, bool TABLES>
+__device__ __forceinline__ void patch_gather_body(const float *__restrict__ xb, int64_t lead, int lb, int nb, int rows, T *__restrict__ out,
+                                                  int64_t row0, int C, int P, int PB, int64_t ld, const float *__restrict__ mean,
+                                                  const float *__restrict__ inv_std, const int *__restrict__ t0, const int *__restrict__ tlen) {
+    extern __shared__ __attribute__((aligned(16))) float tile[];  // [C][PB*P+1]
+    const int p0 = blockIdx.x * PB;
+    if (TABLES && p0 >= rows) return;
+    const int np = min(PB, rows - p0), W = np * P, WS = PB * P + 1;
+    const int CP = C * P;
+    T *ob = out + (row0 + p0) * ld;
+    if (TABLES && p0 >= nb) {
+        for (int idx = threadIdx.x; idx < np * (int)ld; idx += 256) ob[idx] = from_f32<T>(0.f);
+        return;
+    }
+    // the block's first sample: part of the 64-bit base in the uniform form, of the 32-bit offset inside the record in the table form
+    const int s0 = TABLES ? p0 * P : 0;
+    if (!TABLES) xb += (int64_t)p0 * P;
     int z0 = 0, z1 = 0;
-    if (XF && t0) { z0 = t0[b]; z1 = z0 + tlen[b]; }
+    if (XF && t0) { z0 = t0[blockIdx.y]; z1 = z0 + tlen[blockIdx.y]; }
     for (int idx = threadIdx.x; idx < C * W; idx += 256) {
         const int c = idx / W, s = idx - c * W;
         float v;
         if (XF) {
             const int pos = p0 * P + s;
             v = 0.f;
-            if (pos < L_raw && !(pos >= z0 && pos < z1)) v = (xb[(int64_t)c * Lsrc + s] - mean[c]) * inv_std[c];
+            if (pos < lb && !(pos >= z0 && pos < z1)) v = (xb[(int64_t)c * lead + (s0 + s)] - mean[c]) * inv_std[c];
         } else {
-            v = xb[(int64_t)c * L + s];
+            v = xb[(int64_t)c * lead + (s0 + s)];
         }
         tile[c * WS + s] = v;
     }
     __syncthreads();
-    const int CP = C * P;
-    T *ob = out + ((int64_t)b * n + p0) * ld;
     for (int idx = threadIdx.x; idx < np * (int)ld; idx += 256) {
         const int pp = idx / (int)ld, f = idx - pp * (int)ld;
         float v = 0.f;
@@ -53,13 +61,22 @@ __global__ __launch_bounds__(256) void patch_gather_kernel(const float *__restri
     }
 }
 
-// The same transforms PER RECORD, for records of unequal raw length (the reference applies them to one record at a time:
+// uniform form: every record holds L (XF: L_raw, zero-padded to L) samples per lead and writes its n = L / P rows
+template <typename T, bool XF>
+__global__ __launch_bounds__(256) void patch_gather_kernel(const float *__restrict__ x, T *__restrict__ out, int C, int L,
+                                                           int P, int n, int PB, int64_t ld, int L_raw,
+                                                           const float *__restrict__ mean, const float *__restrict__ inv_std,
+                                                           const int *__restrict__ t0, const int *__restrict__ tlen) {
+    const int b = blockIdx.y, Lsrc = XF ? L_raw : L;
+    patch_gather_body<T, XF, false>(x + (int64_t)b * C * Lsrc, Lsrc, L_raw, n, n, out, (int64_t)b * n, C, P, PB, ld, mean, inv_std, t0, tlen);
+}
+
+// table form, the transforms PER RECORD for records of unequal raw length (the reference applies them to one record at a time:
 // ptb_dataset.py:132-149): record b holds raw_len[b] samples per lead starting at x + src_off[b] (lead c at + c * lead_stride), is
 // zero-padded in normalised space to n_patch[b] * P samples, TimeOut zeroes [t0[b], t0[b] + tlen[b]) of the padded record, and its patch
-// rows go to out rows row_off[b] ...  One kernel text for both row layouts: nrows = 0 -- packed rows, record b writes its n_patch[b] rows;
-// nrows > 0 -- padded rows, record b writes nrows rows, exact zeros past n_patch[b].  A block whose patches all lie past n_patch[b] never
-// reads x.  Record starts fall on arbitrary sample offsets, so the loads are scalar (consecutive lanes, consecutive samples of one lead:
-// coalesced); the record base is 64-bit, offsets inside a record 32-bit.
+// rows go to out rows row_off[b] ...  Both row layouts: nrows = 0 -- packed rows, record b writes its n_patch[b] rows; nrows > 0 -- padded
+// rows, record b writes nrows rows, exact zeros past n_patch[b].  Record starts fall on arbitrary sample offsets, so the loads are scalar
+// (consecutive lanes, consecutive samples of one lead: coalesced); the record base is 64-bit, offsets inside a record 32-bit.
 template <typename T>
 __global__ __launch_bounds__(256) void patch_gather_transform_varlen_kernel(const float *__restrict__ x, T *__restrict__ out,
                                                                             const int64_t *__restrict__ src_off, int64_t lead_stride,
@@ -68,44 +85,41 @@ __global__ __launch_bounds__(256) void patch_gather_transform_varlen_kernel(cons
                                                                             int PB, int64_t ld, const float *__restrict__ mean,
                                                                             const float *__restrict__ inv_std, const int32_t *__restrict__ t0,
                                                                             const int32_t *__restrict__ tlen) {
-    extern __shared__ __attribute__((aligned(16))) float tile[];  // [C][PB*P+1]
-    const int b = blockIdx.y, p0 = blockIdx.x * PB;
+    const int b = blockIdx.y;
     const int nb = min(n_patch[b], nrows > 0 ? nrows : n_max);   // (a table entry past the rows the launch was sized for never writes there)
-    const int rows = nrows > 0 ? nrows : nb;
-    if (p0 >= rows) return;
-    const int np = min(PB, rows - p0), W = np * P, WS = PB * P + 1;
-    const int CP = C * P;
-    T *ob = out + ((int64_t)row_off[b] + p0) * ld;
-    if (p0 >= nb) {   // padded rows past the record: zeros, x is not read
-        for (int idx = threadIdx.x; idx < np * (int)ld; idx += 256) ob[idx] = from_f32<T>(0.f);
-        return;
-    }
-    const int lb = min(raw_len[b], nb * P);
-    const float *xb = x + src_off[b];
-    int z0 = 0, z1 = 0;
-    if (t0) { z0 = t0[b]; z1 = z0 + tlen[b]; }
-    for (int idx = threadIdx.x; idx < C * W; idx += 256) {
-        const int c = idx / W, s = idx - c * W;
-        const int pos = p0 * P + s;
-        float v = 0.f;
-        if (pos < lb && !(pos >= z0 && pos < z1)) v = (xb[(int64_t)c * lead_stride + pos] - mean[c]) * inv_std[c];
-        tile[c * WS + s] = v;
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < np * (int)ld; idx += 256) {
-        const int pp = idx / (int)ld, f = idx - pp * (int)ld;
-        float v = 0.f;
-        if (f < CP) {
-            const int j = f / C, c = f - j * C;
-            v = tile[c * WS + pp * P + j];
-        }
-        ob[(int64_t)pp * ld + f] = from_f32<T>(v);
-    }
+    patch_gather_body<T, true, true>(x + src_off[b], lead_stride, min(raw_len[b], nb * P), nb, nrows > 0 ? nrows : nb, out, row_off[b],
+                                     C, P, PB, ld, mean, inv_std, t0, tlen);
 }
 
 // =====================================================================================================
 // CLS concat + positional add (+ embedding dropout)
 // =====================================================================================================
+// one 16-B vector of X: row `row` = token t of its record, columns c0 ...: the CLS row (t == 0) or row tok_row of tok, + pos[t], then the
+// dropout multipliers, drawn at the element index row * d + c0 of X
+template <typename T>
+__device__ __forceinline__ void embed_finish_vec(const T *__restrict__ tok, const float *__restrict__ cls, const float *__restrict__ pos,
+                                                 T *__restrict__ X, int64_t tok_row, int t, int64_t row, int c0, int d, uint64_t seed,
+                                                 uint32_t thresh, float inv_keep) {
+    constexpr int VN = Vec16<T>::N;
+    Vec16<T> o;
+    if (t == 0) {
+#pragma unroll
+        for (int k = 0; k < VN; ++k) o.set(k, cls[c0 + k] + pos[c0 + k]);
+    } else {
+        const Vec16<T> v = ld16(tok + tok_row * (int64_t)d + c0);
+#pragma unroll
+        for (int k = 0; k < VN; ++k) o.set(k, v.get(k) + pos[(int64_t)t * d + c0 + k]);
+    }
+    if (thresh) {
+        float mk[VN];   // d and c0 are multiples of VN: the run starts on an even element
+        dropout_maskN<VN, sizeof(T) == 2>(seed, (uint32_t)row * (uint32_t)d + (uint32_t)c0, thresh, inv_keep, mk);
+#pragma unroll
+        for (int k = 0; k < VN; ++k) o.set(k, o.get(k) * mk[k]);
+    }
+    st16(X + row * d + c0, o);
+}
+
+// uniform form (n + 1 tokens per record): one flat grid-stride walk over the vectors of X
 template <typename T>
 __global__ __launch_bounds__(256) void embed_finish_kernel(const T *__restrict__ tok, const float *__restrict__ cls,
                                                            const float *__restrict__ pos, T *__restrict__ X, int B, int n,
@@ -118,80 +132,13 @@ __global__ __launch_bounds__(256) void embed_finish_kernel(const T *__restrict__
         const int64_t row = i / dv;
         const int t = (int)(row % N);
         const int64_t b = row / N;
-        const int c0 = cv * VN;
-        Vec16<T> o;
-        if (t == 0) {
-#pragma unroll
-            for (int k = 0; k < VN; ++k) o.set(k, cls[c0 + k] + pos[c0 + k]);
-        } else {
-            const Vec16<T> v = ld16(tok + (b * n + (t - 1)) * (int64_t)d + c0);
-#pragma unroll
-            for (int k = 0; k < VN; ++k) o.set(k, v.get(k) + pos[(int64_t)t * d + c0 + k]);
-        }
-        if (thresh) {
-            float mk[VN];   // d and c0 are multiples of VN: the run starts on an even element
-            dropout_maskN<VN, sizeof(T) == 2>(seed, (uint32_t)row * (uint32_t)d + (uint32_t)c0, thresh, inv_keep, mk);
-#pragma unroll
-            for (int k = 0; k < VN; ++k) o.set(k, o.get(k) * mk[k]);
-        }
-        st16(X + row * d + c0, o);
+        embed_finish_vec(tok, cls, pos, X, b * n + (t - 1), t, row, cv * VN, d, seed, thresh, inv_keep);
     }
 }
 
-// dtok copy + dpos/dcls reductions over the batch.  One block per (token t, group of 8 16-B column chunks): 8 chunk columns x 32 batch
-// lanes; every thread walks its batch residue class (b = lane, lane + 32, ...), then a fixed-order LDS tree over the 32 lanes --
-// deterministic, and N * d/(8 VN) blocks of 256 threads instead of one sequential 512-deep loop per thread.
-template <typename T>
-__global__ __launch_bounds__(256) void embed_bwd_kernel(const T *__restrict__ dX, T *__restrict__ dtok, float *__restrict__ dcls,
-                                                        float *__restrict__ dpos, int B, int n, int d, uint64_t seed,
-                                                        uint32_t thresh, float inv_keep) {
-    constexpr int VN = Vec16<T>::N;
-    __shared__ float red[32][8 * VN + 1];
-    const int N = n + 1, dv = d / VN, groups = (dv + 7) / 8;
-    const int t = blockIdx.x / groups, cg = blockIdx.x - t * groups;
-    const int cc = threadIdx.x & 7, bl = threadIdx.x >> 3;       // chunk column within the group, batch lane
-    const int chunk = cg * 8 + cc;
-    const bool live = chunk < dv;
-    const int c0 = chunk * VN;
-    float acc[VN];
-#pragma unroll
-    for (int k = 0; k < VN; ++k) acc[k] = 0.f;
-    if (live) {
-        for (int b = bl; b < B; b += 32) {
-            const int64_t row = (int64_t)b * N + t;
-            Vec16<T> v = ld16(dX + row * d + c0);
-            if (thresh) {
-                float mk[VN];
-                dropout_maskN<VN, sizeof(T) == 2>(seed, (uint32_t)row * (uint32_t)d + (uint32_t)c0, thresh, inv_keep, mk);
-#pragma unroll
-                for (int k = 0; k < VN; ++k) v.set(k, v.get(k) * mk[k]);
-            }
-#pragma unroll
-            for (int k = 0; k < VN; ++k) acc[k] += v.get(k);
-            if (t > 0) st16(dtok + ((int64_t)b * n + (t - 1)) * d + c0, v);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < VN; ++k) red[bl][cc * VN + k] = acc[k];
-    __syncthreads();
-    if (threadIdx.x < 8 * VN) {
-        const int col = cg * 8 * VN + threadIdx.x;
-        if (col < d) {
-            float s[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int r = 0; r < 32; r += 4) {
-                s[0] += red[r][threadIdx.x]; s[1] += red[r + 1][threadIdx.x]; s[2] += red[r + 2][threadIdx.x]; s[3] += red[r + 3][threadIdx.x];
-            }
-            const float tot = (s[0] + s[1]) + (s[2] + s[3]);
-            dpos[(int64_t)t * d + col] = tot;
-            if (t == 0) dcls[col] = tot;
-        }
-    }
-}
-
-// ragged batch (packed rows): record b's tokens are rows tok_off[b] .. tok_off[b] + n_tok[b] - 1 of X and its patch tokens rows
+// table form, a ragged batch (packed rows): record b's tokens are rows tok_off[b] .. tok_off[b] + n_tok[b] - 1 of X and its patch tokens rows
 // tok_off[b] - b .. tok_off[b] - b + n_tok[b] - 2 of tok (tok_off[b] = off_b / P + b); N = the widest record's token count.  Embedding
-// dropout draws its bits by packed element index.  Forward: one grid row per record, its tokens strided over the blocks.
+// dropout draws its bits by packed element index.  One grid row per record, its tokens strided over the blocks.
 template <typename T>
 __global__ __launch_bounds__(256) void embed_finish_ragged_kernel(const T *__restrict__ tok, const float *__restrict__ cls,
                                                                   const float *__restrict__ pos, T *__restrict__ X, const int32_t *__restrict__ n_tok,
@@ -203,39 +150,25 @@ __global__ __launch_bounds__(256) void embed_finish_ragged_kernel(const T *__res
     const int64_t r0 = tok_off[b], total = (int64_t)nb * dv;
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int t = (int)(i / dv), c0 = (int)(i - (int64_t)t * dv) * VN;
-        const int64_t row = r0 + t;
-        Vec16<T> o;
-        if (t == 0) {
-#pragma unroll
-            for (int k = 0; k < VN; ++k) o.set(k, cls[c0 + k] + pos[c0 + k]);
-        } else {
-            const Vec16<T> v = ld16(tok + (r0 - b - 1 + t) * (int64_t)d + c0);
-#pragma unroll
-            for (int k = 0; k < VN; ++k) o.set(k, v.get(k) + pos[(int64_t)t * d + c0 + k]);
-        }
-        if (thresh) {
-            float mk[VN];
-            dropout_maskN<VN, sizeof(T) == 2>(seed, (uint32_t)row * (uint32_t)d + (uint32_t)c0, thresh, inv_keep, mk);
-#pragma unroll
-            for (int k = 0; k < VN; ++k) o.set(k, o.get(k) * mk[k]);
-        }
-        st16(X + row * d + c0, o);
+        embed_finish_vec(tok, cls, pos, X, r0 - b - 1 + t, t, r0 + t, c0, d, seed, thresh, inv_keep);
     }
 }
 
-// its backward, laid out as embed_bwd_kernel: one block per (token t < N, group of 8 column chunks), 32 batch lanes walking their residue
-// classes over the records that hold token t, then the fixed-order LDS tree: dpos[t] = sum over those records, gathered per position in a
-// fixed order (no atomics, bit-reproducible); dcls = dpos[0]; dtok of every patch token.
-template <typename T>
-__global__ __launch_bounds__(256) void embed_bwd_ragged_kernel(const T *__restrict__ dX, T *__restrict__ dtok, float *__restrict__ dcls,
-                                                               float *__restrict__ dpos, const int32_t *__restrict__ n_tok,
-                                                               const int32_t *__restrict__ tok_off, int B, int d, uint64_t seed, uint32_t thresh,
-                                                               float inv_keep) {
+// dtok copy + dpos/dcls reductions over the batch.  One block per (token t, group of 8 16-B column chunks): 8 chunk columns x 32 batch
+// lanes; every thread walks its batch residue class (b = lane, lane + 32, ...), then a fixed-order LDS tree over the 32 lanes --
+// deterministic, and N * d/(8 VN) blocks of 256 threads instead of one sequential 512-deep loop per thread.
+// One body, forms by template: record b's tokens are the rows r0 .. of dX and its patch tokens the rows r0 - b .. of dtok.  The uniform form
+// has r0 = b * N, N = n + 1 tokens in every record; TABLES (a ragged batch) reads r0 = tok_off[b] and skips the records with t >= n_tok[b], so
+// dpos[t] = the sum over the records that hold token t, gathered per position in a fixed order (no atomics, bit-reproducible); dcls = dpos[0].
+template <typename T, bool TABLES>
+__device__ __forceinline__ void embed_bwd_body(const T *__restrict__ dX, T *__restrict__ dtok, float *__restrict__ dcls, float *__restrict__ dpos,
+                                               const int32_t *__restrict__ n_tok, const int32_t *__restrict__ tok_off, int B, int N, int d,
+                                               uint64_t seed, uint32_t thresh, float inv_keep) {
     constexpr int VN = Vec16<T>::N;
     __shared__ float red[32][8 * VN + 1];
     const int dv = d / VN, groups = (dv + 7) / 8;
     const int t = blockIdx.x / groups, cg = blockIdx.x - t * groups;
-    const int cc = threadIdx.x & 7, bl = threadIdx.x >> 3;
+    const int cc = threadIdx.x & 7, bl = threadIdx.x >> 3;       // chunk column within the group, batch lane
     const int chunk = cg * 8 + cc;
     const bool live = chunk < dv;
     const int c0 = chunk * VN;
@@ -244,8 +177,8 @@ __global__ __launch_bounds__(256) void embed_bwd_ragged_kernel(const T *__restri
     for (int k = 0; k < VN; ++k) acc[k] = 0.f;
     if (live) {
         for (int b = bl; b < B; b += 32) {
-            if (t >= n_tok[b]) continue;
-            const int64_t r0 = tok_off[b], row = r0 + t;
+            if (TABLES && t >= n_tok[b]) continue;
+            const int64_t r0 = TABLES ? tok_off[b] : (int64_t)b * N, row = r0 + t;
             Vec16<T> v = ld16(dX + row * d + c0);
             if (thresh) {
                 float mk[VN];
@@ -255,7 +188,7 @@ __global__ __launch_bounds__(256) void embed_bwd_ragged_kernel(const T *__restri
             }
 #pragma unroll
             for (int k = 0; k < VN; ++k) acc[k] += v.get(k);
-            if (t > 0) st16(dtok + (r0 - b - 1 + t) * d + c0, v);
+            if (t > 0) st16(dtok + (TABLES ? r0 - b - 1 + t : (int64_t)b * (N - 1) + (t - 1)) * d + c0, v);
         }
     }
 #pragma unroll
@@ -274,6 +207,21 @@ __global__ __launch_bounds__(256) void embed_bwd_ragged_kernel(const T *__restri
             if (t == 0) dcls[col] = tot;
         }
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void embed_bwd_kernel(const T *__restrict__ dX, T *__restrict__ dtok, float *__restrict__ dcls,
+                                                        float *__restrict__ dpos, int B, int n, int d, uint64_t seed,
+                                                        uint32_t thresh, float inv_keep) {
+    embed_bwd_body<T, false>(dX, dtok, dcls, dpos, nullptr, nullptr, B, n + 1, d, seed, thresh, inv_keep);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void embed_bwd_ragged_kernel(const T *__restrict__ dX, T *__restrict__ dtok, float *__restrict__ dcls,
+                                                               float *__restrict__ dpos, const int32_t *__restrict__ n_tok,
+                                                               const int32_t *__restrict__ tok_off, int B, int d, uint64_t seed, uint32_t thresh,
+                                                               float inv_keep) {
+    embed_bwd_body<T, true>(dX, dtok, dcls, dpos, n_tok, tok_off, B, 0, d, seed, thresh, inv_keep);
 }
 
 // =====================================================================================================
@@ -785,23 +733,31 @@ static bool ln_fit(int d) { const int e = d / 64; return d % 256 == 0 && (e == 4
 // ---------------------------------------------------------------------------------------------------
 extern "C" {
 
+// the gather's LDS tile: C * (PB * P + 1) floats, PB patches per block halved until the tile fits 48 KiB; false: one patch alone passes 64 KiB
+static bool patch_tile(int C, int P, int &PB, size_t &lds) {
+    PB = std::max(1, 256 / P);
+    while (PB > 1 && (size_t)C * (PB * P + 1) * 4 > 48 * 1024) PB >>= 1;
+    lds = (size_t)C * (PB * P + 1) * 4;
+    return lds <= 64 * 1024;
+}
+
 static int patch_gather_launch(const float *x, void *patches, int B, int C, int L, int P, int64_t ld, int dtype, void *stream, bool xf,
                                int L_raw, const float *mean, const float *inv_std, const int *t0, const int *tlen) {
     if (B <= 0 || C <= 0 || P <= 0 || L <= 0 || L % P != 0 || ld < (int64_t)C * P) return ECGVIT_EINVAL;
     if (xf && (!mean || !inv_std || L_raw <= 0 || L_raw > L || ((t0 == nullptr) != (tlen == nullptr)))) return ECGVIT_EINVAL;
     const int n = L / P;
-    int PB = std::max(1, 256 / P);
-    while (PB > 1 && (size_t)C * (PB * P + 1) * 4 > 48 * 1024) PB >>= 1;
-    const size_t lds = (size_t)C * (PB * P + 1) * 4;
-    if (lds > 64 * 1024) return ECGVIT_EINVAL;
+    int PB;
+    size_t lds;
+    if (!patch_tile(C, P, PB, lds)) return ECGVIT_EINVAL;
     dim3 grid((n + PB - 1) / PB, B);
-    if (dtype != ECGVIT_F32 && dtype != ECGVIT_BF16) return ECGVIT_EINVAL;
-#define PG(T, X) hipLaunchKernelGGL((patch_gather_kernel<T, X>), grid, dim3(256), lds, as_stream(stream), x, (T *)patches, C, L, P, n, PB, ld, L_raw, mean, inv_std, t0, tlen)
-    if (dtype == ECGVIT_F32) { if (xf) PG(float, true); else PG(float, false); }
-    else { if (xf) PG(bf16_t, true); else PG(bf16_t, false); }
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+#define PG(X) hipLaunchKernelGGL((patch_gather_kernel<T, X>), grid, dim3(256), lds, as_stream(stream), x, (T *)patches, C, L, P, n, PB, ld, L_raw, mean, inv_std, t0, tlen)
+        if (xf) PG(true); else PG(false);
 #undef PG
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
 }
 
 int ecgvit_patch_gather(const float *x, void *patches, int B, int C, int L, int P, int64_t ld, int dtype, void *stream) {
@@ -822,92 +778,85 @@ int ecgvit_patch_gather_transform_varlen(const float *x, void *patches, const in
     if (!x || !patches || !src_off || !raw_len || !n_patch || !row_off || !mean || !inv_std) return ECGVIT_EINVAL;
     if ((timeout_start == nullptr) != (timeout_len == nullptr)) return ECGVIT_EINVAL;
     if (n_rows_per_record > 0 && n_rows_per_record < n_max) return ECGVIT_EINVAL;
-    if (dtype != ECGVIT_F32 && dtype != ECGVIT_BF16) return ECGVIT_EINVAL;
     if (B > 65535 || (int64_t)n_max * ld > INT32_MAX) return ECGVIT_EINVAL;   // (grid.y; 32-bit offsets inside a record)
-    int PB = std::max(1, 256 / P);
-    while (PB > 1 && (size_t)C * (PB * P + 1) * 4 > 48 * 1024) PB >>= 1;
-    const size_t lds = (size_t)C * (PB * P + 1) * 4;
-    if (lds > 64 * 1024) return ECGVIT_EINVAL;
+    int PB;
+    size_t lds;
+    if (!patch_tile(C, P, PB, lds)) return ECGVIT_EINVAL;
     const int rows = n_rows_per_record > 0 ? n_rows_per_record : n_max;
     dim3 grid((rows + PB - 1) / PB, B);
-#define PGV(T) hipLaunchKernelGGL((patch_gather_transform_varlen_kernel<T>), grid, dim3(256), lds, as_stream(stream), x, (T *)patches, src_off, \
-                                  lead_stride, raw_len, n_patch, row_off, n_rows_per_record, n_max, C, P, PB, ld, mean, inv_std, timeout_start, timeout_len)
-    if (dtype == ECGVIT_F32) PGV(float); else PGV(bf16_t);
-#undef PGV
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        hipLaunchKernelGGL(patch_gather_transform_varlen_kernel<T>, grid, dim3(256), lds, as_stream(stream), x, (T *)patches, src_off, lead_stride,
+                           raw_len, n_patch, row_off, n_rows_per_record, n_max, C, P, PB, ld, mean, inv_std, timeout_start, timeout_len);
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
 }
 
+// the embedding launchers: d a multiple of 8 (a whole 16-B vector of either type); a dropout rate the element type cannot apply is refused
+// (bf16: p applied as round(256 p) / 256; below 1/512: rejected)
 int ecgvit_embed_finish(const void *tok, const float *cls, const float *pos, void *X, int B, int n, int d, float dropout_p,
                         uint64_t seed, int dtype, void *stream) {
     if (B <= 0 || n <= 0 || d <= 0 || d % 8 != 0) return ECGVIT_EINVAL;
-    uint32_t th;
-    float ik;
-    if (!dropout_site_params(dropout_p, dtype == ECGVIT_BF16, th, ik)) return ECGVIT_EINVAL;   // (bf16: p applied as round(256 p) / 256; below 1/512: rejected)
-    const int64_t total = (int64_t)B * (n + 1) * d / (dtype == ECGVIT_F32 ? 4 : 8);
-    const int grid = (int)std::min<int64_t>((total + 255) / 256, 4096);
-    if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(embed_finish_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), (const float *)tok, cls, pos, (float *)X, B, n, d, seed, th, ik);
-    else if (dtype == ECGVIT_BF16)
-        hipLaunchKernelGGL(embed_finish_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), (const bf16_t *)tok, cls, pos, (bf16_t *)X, B, n, d, seed, th, ik);
-    else return ECGVIT_EINVAL;
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        uint32_t th;
+        float ik;
+        if (!dropout_site_params(dropout_p, sizeof(T) == 2, th, ik)) return ECGVIT_EINVAL;
+        const int64_t total = (int64_t)B * (n + 1) * d / Vec16<T>::N;
+        const int grid = (int)std::min<int64_t>((total + 255) / 256, 4096);
+        hipLaunchKernelGGL(embed_finish_kernel<T>, dim3(grid), dim3(256), 0, as_stream(stream), (const T *)tok, cls, pos, (T *)X, B, n, d, seed, th, ik);
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
 }
 
 int ecgvit_embed_bwd(const void *dX, void *dtok, float *dcls, float *dpos, int B, int n, int d, float dropout_p, uint64_t seed,
                      int dtype, void *stream) {
     if (B <= 0 || n <= 0 || d <= 0 || d % 8 != 0) return ECGVIT_EINVAL;
-    uint32_t th;
-    float ik;
-    if (!dropout_site_params(dropout_p, dtype == ECGVIT_BF16, th, ik)) return ECGVIT_EINVAL;   // (bf16: p applied as round(256 p) / 256; below 1/512: rejected)
-    const int dv = d / (dtype == ECGVIT_F32 ? 4 : 8);
-    const int grid = (n + 1) * ((dv + 7) / 8);   // one block per (token, group of 8 column chunks)
-    if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(embed_bwd_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), (const float *)dX, (float *)dtok, dcls, dpos, B, n, d, seed, th, ik);
-    else if (dtype == ECGVIT_BF16)
-        hipLaunchKernelGGL(embed_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), (const bf16_t *)dX, (bf16_t *)dtok, dcls, dpos, B, n, d, seed, th, ik);
-    else return ECGVIT_EINVAL;
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        uint32_t th;
+        float ik;
+        if (!dropout_site_params(dropout_p, sizeof(T) == 2, th, ik)) return ECGVIT_EINVAL;
+        const int grid = (n + 1) * ((d / Vec16<T>::N + 7) / 8);   // one block per (token, group of 8 column chunks)
+        hipLaunchKernelGGL(embed_bwd_kernel<T>, dim3(grid), dim3(256), 0, as_stream(stream), (const T *)dX, (T *)dtok, dcls, dpos, B, n, d, seed, th, ik);
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
 }
 
 int ecgvit_embed_finish_ragged(const void *tok, const float *cls, const float *pos, void *X, const int32_t *n_tok, const int32_t *tok_off, int B,
                                int N, int d, float dropout_p, uint64_t seed, int dtype, void *stream) {
     if (B <= 0 || B > 65535 || N <= 0 || d <= 0 || d % 8 != 0 || !n_tok || !tok_off) return ECGVIT_EINVAL;
-    uint32_t th;
-    float ik;
-    if (!dropout_site_params(dropout_p, dtype == ECGVIT_BF16, th, ik)) return ECGVIT_EINVAL;
-    const int64_t per = (int64_t)N * d / (dtype == ECGVIT_F32 ? 4 : 8);
-    const dim3 grid((unsigned)std::min<int64_t>((per + 255) / 256, 1024), (unsigned)B);
-    if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(embed_finish_ragged_kernel<float>, grid, dim3(256), 0, as_stream(stream), (const float *)tok, cls, pos, (float *)X, n_tok,
-                           tok_off, N, d, seed, th, ik);
-    else if (dtype == ECGVIT_BF16)
-        hipLaunchKernelGGL(embed_finish_ragged_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), (const bf16_t *)tok, cls, pos, (bf16_t *)X, n_tok,
-                           tok_off, N, d, seed, th, ik);
-    else return ECGVIT_EINVAL;
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        uint32_t th;
+        float ik;
+        if (!dropout_site_params(dropout_p, sizeof(T) == 2, th, ik)) return ECGVIT_EINVAL;
+        const int64_t per = (int64_t)N * d / Vec16<T>::N;
+        const dim3 grid((unsigned)std::min<int64_t>((per + 255) / 256, 1024), (unsigned)B);
+        hipLaunchKernelGGL(embed_finish_ragged_kernel<T>, grid, dim3(256), 0, as_stream(stream), (const T *)tok, cls, pos, (T *)X, n_tok, tok_off, N, d,
+                           seed, th, ik);
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
 }
 
 int ecgvit_embed_bwd_ragged(const void *dX, void *dtok, float *dcls, float *dpos, const int32_t *n_tok, const int32_t *tok_off, int B, int N, int d,
                             float dropout_p, uint64_t seed, int dtype, void *stream) {
     if (B <= 0 || N <= 0 || d <= 0 || d % 8 != 0 || !n_tok || !tok_off) return ECGVIT_EINVAL;
-    uint32_t th;
-    float ik;
-    if (!dropout_site_params(dropout_p, dtype == ECGVIT_BF16, th, ik)) return ECGVIT_EINVAL;
-    const int dv = d / (dtype == ECGVIT_F32 ? 4 : 8);
-    const int grid = N * ((dv + 7) / 8);   // one block per (token, group of 8 column chunks)
-    if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(embed_bwd_ragged_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), (const float *)dX, (float *)dtok, dcls, dpos,
-                           n_tok, tok_off, B, d, seed, th, ik);
-    else if (dtype == ECGVIT_BF16)
-        hipLaunchKernelGGL(embed_bwd_ragged_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), (const bf16_t *)dX, (bf16_t *)dtok, dcls, dpos,
-                           n_tok, tok_off, B, d, seed, th, ik);
-    else return ECGVIT_EINVAL;
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        uint32_t th;
+        float ik;
+        if (!dropout_site_params(dropout_p, sizeof(T) == 2, th, ik)) return ECGVIT_EINVAL;
+        const int grid = N * ((d / Vec16<T>::N + 7) / 8);   // one block per (token, group of 8 column chunks)
+        hipLaunchKernelGGL(embed_bwd_ragged_kernel<T>, dim3(grid), dim3(256), 0, as_stream(stream), (const T *)dX, (T *)dtok, dcls, dpos, n_tok, tok_off,
+                           B, d, seed, th, ik);
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
 }
 
 int ecgvit_layernorm_fwd(const void *x, const float *gamma, const float *beta, void *y, float *mean, float *rstd, int64_t rows,
@@ -922,13 +871,17 @@ int ecgvit_layernorm_fwd(const void *x, const float *gamma, const float *beta, v
         ECGVIT_CHECK_LAUNCH();
         return ECGVIT_OK;
     }
-    const int nv = (d + (dtype == ECGVIT_F32 ? 256 : 512) - 1) / (dtype == ECGVIT_F32 ? 256 : 512);
-#define LN_FWD(T, MV) hipLaunchKernelGGL((layernorm_fwd_kernel<T, MV>), dim3(grid), dim3(256), 0, as_stream(stream), (const T *)x, gamma, beta, (T *)y, mean, rstd, rows, d, eps)
-    if (dtype == ECGVIT_F32) { if (nv <= 1) LN_FWD(float, 1); else if (nv <= 2) LN_FWD(float, 2); else if (nv <= 4) LN_FWD(float, 4); else LN_FWD(float, 8); }
-    else { if (nv <= 1) LN_FWD(bf16_t, 1); else if (nv <= 2) LN_FWD(bf16_t, 2); else LN_FWD(bf16_t, 4); }
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        constexpr int WV = 64 * Vec16<T>::N;   // the elements of a row one vector per lane covers
+        const int nv = (d + WV - 1) / WV;
+#define LN_FWD(MV) hipLaunchKernelGGL((layernorm_fwd_kernel<T, MV>), dim3(grid), dim3(256), 0, as_stream(stream), (const T *)x, gamma, beta, (T *)y, mean, rstd, rows, d, eps)
+        if (nv <= 1) LN_FWD(1); else if (nv <= 2) LN_FWD(2); else if (nv <= 4) LN_FWD(4);
+        else if constexpr (WV == 256) LN_FWD(8);   // (d <= 2048: four bf16 vectors per lane always suffice)
 #undef LN_FWD
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
 }
 
 // bf16 LayerNorm forward that also writes the e4m3 copy of its output (d = 64 * {4, 8, 12, 16, 24, 32} only)
@@ -978,16 +931,22 @@ static int ln_bwd_launch(const void *dy, const void *x, const float *gamma, cons
         ECGVIT_CHECK_LAUNCH();
         return ECGVIT_OK;
     }
-    const int nv = (d + (dtype == ECGVIT_F32 ? 256 : 512) - 1) / (dtype == ECGVIT_F32 ? 256 : 512);
-#define LN_BWD(T, MV)                                                                                                             \
+    const int rc = dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        constexpr int WV = 64 * Vec16<T>::N;   // the elements of a row one vector per lane covers
+        const int nv = (d + WV - 1) / WV;
+#define LN_BWD(MV)                                                                                                                \
     do {                                                                                                                          \
         if (extra) hipLaunchKernelGGL((layernorm_bwd_kernel<T, MV, true>), dim3(grid), dim3(256), lds, as_stream(stream), (const T *)dy, (const T *)x, gamma, mean, rstd, (const T *)dres, (T *)dx, (float *)partial, rows, d, (T *)dxm, seed, th, ik, mrp); \
         else hipLaunchKernelGGL((layernorm_bwd_kernel<T, MV, false>), dim3(grid), dim3(256), lds, as_stream(stream), (const T *)dy, (const T *)x, gamma, mean, rstd, (const T *)dres, (T *)dx, (float *)partial, rows, d, (T *)nullptr, seed, 0u, 1.f, 1u); \
     } while (0)
-    if (dtype == ECGVIT_F32) { if (nv <= 1) LN_BWD(float, 1); else if (nv <= 2) LN_BWD(float, 2); else if (nv <= 4) LN_BWD(float, 4); else LN_BWD(float, 8); }
-    else { if (nv <= 1) LN_BWD(bf16_t, 1); else if (nv <= 2) LN_BWD(bf16_t, 2); else LN_BWD(bf16_t, 4); }
+        if (nv <= 1) LN_BWD(1); else if (nv <= 2) LN_BWD(2); else if (nv <= 4) LN_BWD(4);
+        else if constexpr (WV == 256) LN_BWD(8);   // (d <= 2048: four bf16 vectors per lane always suffice)
 #undef LN_BWD
-    ECGVIT_CHECK_LAUNCH();
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
+    if (rc != ECGVIT_OK) return rc;
     hipLaunchKernelGGL(reduce_partials_kernel, dim3((np * d + 63) / 64), dim3(1024), 0, as_stream(stream), (const float *)partial, grid, np * d, dgamma, dbeta, d, extra ? dcolsum : nullptr);
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
@@ -1027,14 +986,14 @@ int ecgvit_colsum(const void *in, int64_t ld, float *out, void *partial, int64_t
     if (M <= 0 || N <= 0 || N % 8 != 0 || ld % 8 != 0 || !partial) return ECGVIT_EINVAL;
     const int rb = colsum_row_blocks(M);
     const int rpb = (int)((M + rb - 1) / rb);
-    const int vn = dtype == ECGVIT_F32 ? 4 : 8;
-    dim3 grid((N + 64 * vn - 1) / (64 * vn), rb);
-    if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, as_stream(stream), (const float *)in, ld, (float *)partial, M, N, rpb);
-    else if (dtype == ECGVIT_BF16)
-        hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), (const bf16_t *)in, ld, (float *)partial, M, N, rpb);
-    else return ECGVIT_EINVAL;
-    ECGVIT_CHECK_LAUNCH();
+    const int rc = dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        constexpr int WV = 64 * Vec16<T>::N;
+        hipLaunchKernelGGL(colsum_kernel<T>, dim3((N + WV - 1) / WV, rb), dim3(256), 0, as_stream(stream), (const T *)in, ld, (float *)partial, M, N, rpb);
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
+    if (rc != ECGVIT_OK) return rc;
     hipLaunchKernelGGL(reduce_partials_kernel, dim3((N + 63) / 64), dim3(1024), 0, as_stream(stream), (const float *)partial, rb, N, out, out, N);
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
@@ -1044,17 +1003,16 @@ static int dropout_apply_launch(const void *in, void *out, int64_t count, float 
                                 int64_t mrp) {
     if (count <= 0 || count % 8 != 0 || cols < 8 || cols % 8 != 0 || count % cols != 0 || mrp < 1 || (mrp > 1 && count * mrp >= (1ll << 32)))
         return ECGVIT_EINVAL;
-    uint32_t th;
-    float ik;
-    if (!dropout_site_params(dropout_p, dtype == ECGVIT_BF16, th, ik)) return ECGVIT_EINVAL;   // (bf16: p applied as round(256 p) / 256; below 1/512: rejected)
     const int grid = (int)std::min<int64_t>((count / 4 + 255) / 256, 4096);
-    if (dtype == ECGVIT_F32)
-        hipLaunchKernelGGL(dropout_apply_kernel<float>, dim3(grid), dim3(256), 0, as_stream(stream), (const float *)in, (float *)out, count, seed, th, ik, (uint32_t)cols, (uint32_t)mrp);
-    else if (dtype == ECGVIT_BF16)
-        hipLaunchKernelGGL(dropout_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, as_stream(stream), (const bf16_t *)in, (bf16_t *)out, count, seed, th, ik, (uint32_t)cols, (uint32_t)mrp);
-    else return ECGVIT_EINVAL;
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        uint32_t th;
+        float ik;
+        if (!dropout_site_params(dropout_p, sizeof(T) == 2, th, ik)) return ECGVIT_EINVAL;   // (bf16: p applied as round(256 p) / 256; below 1/512: rejected)
+        hipLaunchKernelGGL(dropout_apply_kernel<T>, dim3(grid), dim3(256), 0, as_stream(stream), (const T *)in, (T *)out, count, seed, th, ik, (uint32_t)cols, (uint32_t)mrp);
+        ECGVIT_CHECK_LAUNCH();
+        return ECGVIT_OK;
+    });
 }
 
 int ecgvit_dropout_apply(const void *in, void *out, int64_t count, float dropout_p, uint64_t seed, int dtype, void *stream) {

@@ -1,5 +1,5 @@
 """
-The embedding and masked-objective kernels (csrc/rowops.hip: ecgvit_embed_finish / _bwd; csrc/masked.hip: ecgvit_mask_embed_finish / _bwd,
+The embedding and masked-objective kernels (csrc/rowops.hip: ecgvit_embed_finish / _bwd and their ragged pair; csrc/masked.hip: ecgvit_mask_embed_finish / _bwd,
 ecgvit_gather_rows, ecgvit_scatter_rows, ecgvit_l1_loss_fwd_bwd) through the C ABI, element by element, against tests/embed_ref.py, whose case
 lists and bounds tests/test_embed_ref.py calibrates on the CPU.  Every output is a slice of a larger buffer whose 64-element sentinel bands must
 come back bit-identical, and is pre-filled with NaN; no element the contract owns may still be NaN; every call runs twice into fresh buffers and
@@ -11,6 +11,7 @@ Worst RATIO per kernel, measured on the MI355X over every case of this file (a r
 
     kernel, figure                    f32                               bf16
     ecgvit_embed_bwd       dpos       0.031   (33, 5, 72), p = 0        0.0039  (65, 3, 264), p = 0.5
+    ecgvit_embed_bwd_ragged dpos      0.059   65 records of 2..6 tokens 0.0012  the same
     ecgvit_mask_embed_bwd  dpos       0.082   (33, 5, 72), any m        0.0014  (65, 3, 264), any m
     (varlen at full length dpos       0.082   (33, 5, 72), m = 2        0)
     ecgvit_l1_loss_fwd_bwd loss       0.092   (3, 5, 7), h = 21         0.026   (1, 2049, 2056), h = 25
@@ -153,6 +154,75 @@ def test_embed_dropout_is_dropout_apply(dtype, shape, p):
     same_bits('X(p)', e.fwd(p, seed), want)
     dXd = dropout_apply(e.dX.view(B, n + 1, d), p, seed)
     e.hold_bwd(e.bwd(p, seed), dXd, f'-p{p}')
+
+
+# ------------------------------------------------------------------------------------------------------------------ embed_finish_ragged / _bwd_ragged
+def embed_ragged(e, tok, dX, n_tok, p=0.0, seed=0):
+    """ecgvit_embed_finish_ragged / ecgvit_embed_bwd_ragged on packed rows (record b: n_tok[b] tokens from row tok_off[b] = the exclusive prefix
+    sum), cls / pos / dtype of the Embed `e` -> X [M, d], dtok [M - B, d], dcls [d], dpos [N + 4, d] (N = the widest record)"""
+    B, d = e.B, e.d
+    n_tok = torch.as_tensor(n_tok, dtype=torch.int32)
+    M, N = int(n_tok.sum()), int(n_tok.max())
+    ntd, offd = n_tok.cuda(), (torch.cumsum(n_tok, 0, dtype=torch.int32) - n_tok).cuda()
+
+    def run():
+        o = dict(X=Guarded(M * d, e.dtype), dtok=Guarded((M - B) * d, e.dtype), dcls=Guarded(d, F32), dpos=Guarded((N + 4) * d, F32))
+        check(lib().ecgvit_embed_finish_ragged(ptr(tok), ptr(e.cls), ptr(e.pos), ptr(o['X'].t), ptr(ntd), ptr(offd), B, N, d, float(p), int(seed),
+                                               hip.code(e.dtype), stream()), 'embed_finish_ragged')
+        check(lib().ecgvit_embed_bwd_ragged(ptr(dX), ptr(o['dtok'].t), ptr(o['dcls'].t), ptr(o['dpos'].t), ptr(ntd), ptr(offd), B, N, d, float(p),
+                                            int(seed), hip.code(e.dtype), stream()), 'embed_bwd_ragged')
+        return o
+    o = twice(run)
+    X, dtok, dcls, dpos = o['X'].t.view(M, d), o['dtok'].t.view(M - B, d), o['dcls'].t, o['dpos'].t.view(N + 4, d)
+    written('X', X), written('dtok', dtok), written('dcls', dcls), written('dpos', dpos[:N])
+    assert bool(torch.isnan(dpos[N:]).all()), 'a dpos row past the widest record was written'
+    return X, dtok, dcls, dpos
+
+
+@pytest.mark.parametrize('dtype,shape,p', [pytest.param(dt, s, p, id=f'{R.dtype_id(dt)}-{R.shape_id(s)}-p{p}')
+                                           for dt in R.DTYPES for s in R.DROPOUT_SHAPES for p in (0.0, 0.1)])
+def test_embed_ragged_equals_uniform_at_equal_lengths(dtype, shape, p):
+    """n_tok[b] = n + 1, tok_off[b] = b (n + 1): the ragged pair returns the bits of the uniform pair -- the same element index for the dropout
+    counter, the same lane walk, the same fold.  (33, 5, 72): lane 0 takes a second trip, the last column group is partly live; (65, 3, 264): a
+    third trip"""
+    B, n, d = shape
+    e = Embed(B, n, d, dtype)
+    seed = R.DROPOUT_SEED
+    X, dtok, dcls, dpos = embed_ragged(e, e.tok, e.dX, [n + 1] * B, p, seed)
+    same_bits('X', X.view(B, n + 1, d), e.fwd(p, seed))
+    utok, ucls, upos = e.bwd(p, seed)
+    same_bits('dtok', dtok.view(B, n, d), utok)
+    same_bits('dpos', dpos[:n + 1], upos)
+    same_bits('dcls', dcls, ucls)
+
+
+@pytest.mark.parametrize('dtype', R.DTYPES, ids=R.dtype_id)
+def test_embed_ragged_mixed_lengths_by_element(dtype):
+    """B = 65 records of 2 + (7 b mod 5) tokens (N = 6; token 1 has 65 contributors, token 5 has 13: the lanes' trip counts differ across
+    positions): X is each record's own restatement rounded once, bit for bit; dtok the copied rows; dpos[t] within the bound of the f64 sum over
+    the records that hold t; dcls is row 0 of dpos"""
+    B, d = 65, 72
+    n_tok = [2 + 7 * b % 5 for b in range(B)]
+    N, M = max(n_tok), sum(n_tok)
+    e = Embed(B, N - 1, d, dtype)
+    tok, dX = e.tok[:M - B], e.dX[:M]
+    X, dtok, dcls, dpos = embed_ragged(e, tok, dX, n_tok)
+    r0 = 0
+    for b, nb in enumerate(n_tok):
+        same_bits(f'X of record {b}', X[r0:r0 + nb], R.embed_rounded(tok[r0 - b:r0 - b + nb - 1], e.cls, e.pos[:nb], 1, nb - 1, d, dtype)[0])
+        same_bits(f'dtok of record {b}', dtok[r0 - b:r0 - b + nb - 1], dX[r0 + 1:r0 + nb])
+        r0 += nb
+    same_bits('dcls == dpos[0]', dcls, dpos[0])
+    off = torch.cumsum(torch.tensor([0] + n_tok[:-1]), 0)
+    ref, bound = [], []
+    for t in range(N):
+        terms = dX[[int(off[b]) + t for b in range(B) if n_tok[b] > t]].to(R.F64)[:, None]     # [the records that hold t, 1, d]
+        assert terms.shape[0] == {0: 65, 1: 65, 5: 13}.get(t, terms.shape[0])
+        ref.append(terms.sum(0))
+        bound.append(R.dpos_bound(terms, ref[-1]))
+    cid = f'{R.dtype_id(dtype)}-ragged-{B}x{d}'
+    bad = hold(cid, 'embed_bwd_ragged.dpos', dpos[:N], torch.cat(ref), torch.cat(bound))
+    assert not bad, (cid, bad)
 
 
 # ------------------------------------------------------------------------------------------------------------------ mask_embed_finish / _bwd
