@@ -3,76 +3,11 @@
 //
 // Work is laid out per lead: workgroup (b, c) takes positions [b * span, (b + 1) * span) of lead c's segments, a position finds its record by
 // a binary search in seg_cum.  The padding is applied in the segment load; no padded copy of the store exists.
-#include "common.h"
+#include "tok_common.h"
 
-#define TOK_THREADS 256
 #define TOK_NS 4                                        // groups of 32 segments per wave: four independent accumulators
 #define TOK_SPAN (TOK_THREADS / WAVE * TOK_NS * 32)     // segments per workgroup of the assign kernel (512)
 #define TOK_CHUNK 8192                                  // centre floats per LDS chunk: 32 KiB, + the norms; the table is streamed chunk by chunk
-
-typedef unsigned long long u64;
-
-struct TokStore {
-    const float *x;
-    const int64_t *src_off;
-    int64_t lead_stride;
-    const int32_t *raw_len;
-    const int64_t *seg_cum;
-    const int64_t *dst_off;
-    int64_t dst_stride;
-    int R, pad;
-};
-
-// the record of position p: the last r with seg_cum[r] <= p (seg_cum[0] = 0 <= p < seg_cum[R])
-__device__ __forceinline__ int tok_record(const int64_t *__restrict__ seg_cum, int R, int64_t p) {
-    int lo = 0, hi = R;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (seg_cum[mid] <= p) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-struct TokSeg { int r, len; int64_t s, dst; };
-
-__device__ __forceinline__ TokSeg tok_locate(const TokStore &st, int c, int64_t p) {
-    TokSeg g;
-    g.r = tok_record(st.seg_cum, st.R, p);
-    g.s = p - st.seg_cum[g.r];
-    g.len = st.raw_len[g.r];
-    g.dst = st.dst_off[g.r] + (int64_t)c * st.dst_stride + g.s;
-    return g;
-}
-
-// the K samples of a segment minus their mean -> v, returns the mean.  Every index read lies in [0, len): position i >= len is 0 ('zero')
-// or sample i - n_pad ('shift'), clamped into the run.
-template <int K> __device__ __forceinline__ float tok_load(const TokStore &st, int c, const TokSeg &g, float (&v)[K]) {
-    const float *__restrict__ base = st.x + st.src_off[g.r] + (int64_t)c * st.lead_stride;
-    const int64_t len = g.len, i0 = g.s * K;
-    const int64_t n_pad = K - (len % K);
-#pragma unroll
-    for (int e = 0; e < K; ++e) {
-        const int64_t i = i0 + e;
-        float t = 0.f;
-        if (len > 0) {
-            if (i < len) {
-                t = base[i];
-            } else if (st.pad == 1) {
-                int64_t j = i - n_pad;
-                j = j < 0 ? 0 : (j >= len ? len - 1 : j);
-                t = base[j];
-            }
-        }
-        v[e] = t;
-    }
-    float sum = v[0];
-#pragma unroll
-    for (int e = 1; e < K; ++e) sum = sum + v[e];
-    const float mean = sum * (1.0f / K);
-#pragma unroll
-    for (int e = 0; e < K; ++e) v[e] = v[e] - mean;
-    return mean;
-}
 
 // =====================================================================================================
 // assign.  D = A . B + C on v_mfma_f32_32x32x2_f32 with A = 32 centres (row i on lane i & 31, sample 2 kk + (lane >> 5)), B = 32 segments
@@ -268,19 +203,6 @@ __global__ __launch_bounds__(TOK_THREADS) void tok_finish_kernel(const u64 *__re
 #define SEED_WS_CAND_G 16                                // workspace: the maximum's bits at 0, the candidates' g (int64 [16]),
 #define SEED_WS_CAND_C (SEED_WS_CAND_G + SEED_TMAX * 8)  //   the candidates' segments (f32 [16][32]),
 #define SEED_WS_SUMS (SEED_WS_CAND_C + SEED_TMAX * 32 * 4)   // block_sums (u64 [T][C * blocks]), then closest (f32 [C * n_seg])
-
-// sum_e (s_e - c_e)^2: f32, UNFUSED (every difference, product and addition rounds on its own), in sample order
-template <int K> __device__ __forceinline__ float tok_d2(const float (&v)[K], const float *c) {
-#pragma clang fp contract(off)
-    float acc = 0.f;
-#pragma unroll
-    for (int e = 0; e < K; ++e) {
-        const float d = v[e] - c[e];
-        const float sq = d * d;
-        acc = e ? acc + sq : sq;
-    }
-    return acc;
-}
 
 // rint(d 2^F) in f64, where the product is exact; a non-finite distance (a segment with a non-finite sample, the untouched +inf) weighs nothing
 __device__ __forceinline__ u64 tok_quant(float d, int F) {
@@ -506,29 +428,7 @@ __global__ __launch_bounds__(TOK_THREADS) void tok_decode_kernel(TokStore st, fl
 // =====================================================================================================
 // entry points
 // =====================================================================================================
-static inline bool tok_al(const void *p, unsigned a) { return p && (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
-
-static bool tok_store_ok(const float *x, const int64_t *src_off, const int32_t *raw_len, const int64_t *seg_cum, const int64_t *dst_off, int R, int C,
-                         int64_t n_seg, int k, int pad) {
-    return tok_al(x, 4) && tok_al(src_off, 8) && tok_al(raw_len, 4) && tok_al(seg_cum, 8) && tok_al(dst_off, 8) && R >= 1 && C >= 1 && C <= 65535 &&
-           n_seg >= (int64_t)R && (k == 8 || k == 16 || k == 32) && (pad == 0 || pad == 1);
-}
 static inline bool tok_table_ok(int V) { return V >= 1 && V <= 65536; }
-
-static inline TokStore tok_store(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
-                                 const int64_t *dst_off, int64_t dst_stride, int R, int pad) {
-    TokStore st;
-    st.x = x; st.src_off = src_off; st.lead_stride = lead_stride; st.raw_len = raw_len; st.seg_cum = seg_cum; st.dst_off = dst_off;
-    st.dst_stride = dst_stride; st.R = R; st.pad = pad;
-    return st;
-}
-
-#define TOK_BY_K(k, launch)                      \
-    do {                                         \
-        if ((k) == 8) { launch(8); }             \
-        else if ((k) == 16) { launch(16); }      \
-        else { launch(32); }                     \
-    } while (0)
 
 int ecgvit_tok_assign(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
                       const int64_t *dst_off, int64_t dst_stride, int R, int C, int64_t n_seg, int k, int pad, const float *centers, int V,

@@ -139,6 +139,13 @@ SIGNATURES = {
     'ecgvit_tok_seed_workspace': (c_int64, [_I, _L, _I, _I, _I]),
     'ecgvit_tok_seed': (c_int, [_P, _P, _L, _P, _P, _P, _L, _I, _I, _L, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P, _I, _P]),
     'ecgvit_tok_decode': (c_int, [_P, _P, _L, _P, _P, _P, _L, _I, _I, _L, _I, _P, _P, _P, _I, _P]),
+    'ecgvit_tok_segments': (c_int, [_P, _P, _L, _P, _P, _P, _L, _I, _I, _L, _I, _I, _P, _P, _P, _P]),
+    'ecgvit_tok_dbscan_tile': (c_int, []),
+    'ecgvit_tok_dbscan_rows': (c_int, [_I]),
+    'ecgvit_tok_dbscan_count': (c_int, [_P, _I, _I, _F, _I, _I, _P, _P]),
+    'ecgvit_tok_dbscan_link': (c_int, [_P, _I, _I, _F, _I, _I, _P, _P]),
+    'ecgvit_tok_dbscan_flatten': (c_int, [_P, _I, _P, _P]),
+    'ecgvit_tok_dbscan_border': (c_int, [_P, _I, _P, _P, _I, _I, _F, _I, _I, _P, _P]),
     'ecgvit_denoise_workspace': (c_int64, [_I, _I, _I]),
     'ecgvit_filtfilt': (c_int, [_P, _P, _P, _L, _P, _I, _I, _I, _I, POINTER(c_double), POINTER(c_double), POINTER(c_double), _I, _P, _P]),
     'ecgvit_nlm_sigma': (c_int, [_P, _P, _L, _P, _I, _I, _I, _P, _P, _P]),

@@ -7,7 +7,10 @@ vocabulary.  There is no CPU fallback: host tensors raise.
 
 k-means++ seeding (the reference's default `init`) is a kernel pair too: `EcgTokenizer.kmeans_plusplus`, and `init=KMeansPlusPlus()` in `fit`.
 
-Not built: `save` / pickling, the plots and the four non-k-means clusterings (DESIGN.md says why).
+DBSCAN (the reference's `dbscan` clustering) runs on the device as well (`csrc/dbscan.hip`): `EcgTokenizer.segments`, `EcgTokenizer.dbscan`, and
+`method=Dbscan()` in `fit`.  Two all-pairs sweeps and a union-find over the core segments; the contract is in include/ecgvit_hip.h.
+
+Not built: `save` / pickling, the plots and the three clusterings that are sequential by construction (DESIGN.md says why).
 """
 import numpy as np
 import torch
@@ -19,6 +22,9 @@ PADS = {'zero': 0, 'shift': 1}
 MAX_CLUSTERS = 65536
 MAX_LOCAL_TRIALS = 16
 SEED_SPAN = 1024            # consecutive positions of one lead per workgroup of the seeding's sweep (csrc/tokenize.hip)
+DBSCAN_TILE = 256           # segments per LDS tile of a DBSCAN sweep's column side (csrc/dbscan.hip)
+DBSCAN_ROWS = {8: 1024, 16: 1024, 32: 512}      # rows per workgroup of a DBSCAN sweep, by k: 256 threads, four or two rows each
+DBSCAN_PAIRS_PER_LAUNCH = 1 << 40               # no launch of a DBSCAN sweep covers more pairs (about a second of work): a sweep is enqueued as launches over row blocks
 D_CLS_TH = dict(hierarchical='distance_threshold', dbscan='eps', optics='max_eps', birch='threshold', kmeans='n_clusters')   # ecg_tokenizer.py:72-78
 
 
@@ -72,6 +78,37 @@ class KMeansPlusPlus:
         return min(T, MAX_LOCAL_TRIALS)
 
 
+def check_min_samples(min_samples):
+    if not (isinstance(min_samples, (int, np.integer)) and not isinstance(min_samples, bool) and min_samples >= 1):
+        raise ValueError(f'min_samples = {min_samples!r}: an int, at least 1')
+    return int(min_samples)
+
+
+def check_eps(eps):
+    """-> eps2 = fl32(fl32(eps) * fl32(eps)), what the kernels compare against"""
+    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)) or not np.isfinite(eps) or not eps > 0:
+        raise ValueError(f'eps = {eps!r}: a finite positive number')
+    e = np.float32(eps)
+    with np.errstate(over='ignore'):
+        eps2 = np.float32(e * e)
+    if not np.isfinite(eps2):
+        raise ValueError(f'eps = {eps!r}: its square is not a finite float32')
+    return float(eps2)
+
+
+class Dbscan:
+    """`fit(..., method=Dbscan(), cls_kwargs=dict(eps=...))`: sklearn's DBSCAN over the mean-removed segments, on the device
+    (`EcgTokenizer.dbscan`); min_samples as the reference's `cluster_args` has it, `cls_kwargs['min_samples']` overrides it.  An object, not
+    the string: the string `'dbscan'` promises sklearn's f64 comparison at eps as well, which the f32 kernels do not reproduce for a pair
+    within rounding of eps, and stays refused."""
+
+    def __init__(self, min_samples=5):
+        self.min_samples = check_min_samples(min_samples)
+
+    def __repr__(self):
+        return f'{self.__class__.__qualname__}(min_samples={self.min_samples})'
+
+
 def check_lengths(lengths, k, pad):
     """the one place run lengths are held to the padder's rule: 'shift' copies the n_pad = k - l % k samples before the end, so needs l >= n_pad"""
     lengths = np.asarray(lengths, np.int64)
@@ -100,6 +137,7 @@ class EcgTokenizer:
         self.centers = self.lens = None
         self.fit_method = self.n_sig = self.cls_th = None
         self.n_iter_ = self.inertia_ = self.changed_ = None     # of the last fit: assign passes run, sum of dist, ids changed per pass
+        self.n_noise = self.labels_ = None                      # of the last DBSCAN fit: segments left out as noise, every segment's label (-1: noise)
 
     # the vocabulary: assigning either array drops every table derived from the old one (device copies, th cuts)
     @property
@@ -247,6 +285,121 @@ class EcgTokenizer:
             centers, indices, _, _ = self._seed(st, V, T, first, u53)
             return centers.cpu().numpy(), indices.cpu().numpy()
 
+    # ---- DBSCAN -------------------------------------------------------------------------------------
+    def _segment_store(self, sigs, offsets, idxs):
+        """the store of a DBSCAN pass; the segment count is held to the sweeps' int32 indices before a device is asked for"""
+        if isinstance(sigs, torch.Tensor):
+            s = select_records(sigs, offsets, idxs)
+            n = s.C * int((s.raw_len // self.k + 1).sum())
+            if n >= 2 ** 31:
+                raise ValueError(f'{n} segments: the pair sweeps index fewer than 2^31')
+        return self._record_store(sigs, offsets, idxs)
+
+    def _segments(self, st, want_dst=False):
+        """-> (segs (n, k) f32, means (n,) f32, dst (n,) int64 or None): the dense table in the reference's flat order; dst: where segment q
+        has its id in a tensor of `st.out_shape`"""
+        from .hip import lib, check, ptr, stream
+        dev, n = st.x.device, st.C * st.n_seg
+        segs = torch.empty((n, self.k), dtype=torch.float32, device=dev)
+        means = torch.empty(n, dtype=torch.float32, device=dev)
+        dst = torch.empty(n, dtype=torch.int64, device=dev) if want_dst else None
+        check(lib().ecgvit_tok_segments(*st.args(), st.pad, ptr(segs), ptr(means), ptr(dst), stream()), 'ecgvit_tok_segments')
+        return segs, means, dst
+
+    def segments(self, sigs, offsets=None, idxs=None):
+        """-> (segs (n, k) f32, means (n,) f32), device tensors: the mean-removed segments of a store `fit` takes and their means, in the
+        reference's flat order `sigs.reshape(-1, k)`: segment s of lead c of the r-th selected record is row 12 * (segments of the records
+        before it) + c * n_r + s, whatever the store form.  The dense table every DBSCAN pass reads."""
+        st = self._segment_store(sigs, offsets, idxs)
+        with torch.cuda.device(sigs.device):
+            return self._segments(st)[:2]
+
+    def _row_blocks(self, rows, cols):
+        """[row0, row1) per launch of a sweep of `rows` rows against `cols` columns: whole workgroups, at most DBSCAN_PAIRS_PER_LAUNCH pairs
+        (one workgroup's rows where even that is more)"""
+        rpb = DBSCAN_ROWS[self.k]
+        step = max(1, DBSCAN_PAIRS_PER_LAUNCH // max(1, cols) // rpb) * rpb
+        return [(lo, min(lo + step, rows)) for lo in range(0, rows, step)]
+
+    def _dbscan(self, segs, eps2, min_samples):
+        """the passes over a dense (n, k) table -> (core (m,) int64 ascending, labels (n,) int32, roots (m,) int32 or None), device tensors.
+        torch compacts the core and the non-core rows and ranks the roots between the sweeps: plumbing; two host reads (the two counts)."""
+        from .hip import lib, check, ptr, stream
+        L, s, k, (n, dev) = lib(), stream(), self.k, (segs.shape[0], segs.device)
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        for lo, hi in self._row_blocks(n, n):
+            check(L.ecgvit_tok_dbscan_count(ptr(segs), n, k, eps2, lo, hi, ptr(count), s), 'ecgvit_tok_dbscan_count')
+        is_core = count >= min_samples
+        core = is_core.nonzero().view(-1)                 # ascending q
+        labels = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        m = int(core.numel())
+        if m == 0:
+            return core, labels, None
+        table = segs.index_select(0, core)
+        parent = torch.arange(m, dtype=torch.int32, device=dev)
+        for lo, hi in self._row_blocks(m, m):
+            if hi > 1:                                    # (row 0 has no column below it)
+                check(L.ecgvit_tok_dbscan_link(ptr(table), m, k, eps2, lo, hi, ptr(parent), s), 'ecgvit_tok_dbscan_link')
+        roots = torch.empty(m, dtype=torch.int32, device=dev)
+        check(L.ecgvit_tok_dbscan_flatten(ptr(parent), m, ptr(roots), s), 'ecgvit_tok_dbscan_flatten')
+        core_label = torch.unique(roots, sorted=True, return_inverse=True)[1].to(torch.int32)      # ascending root = ascending smallest q
+        labels[core] = core_label
+        rest = (~is_core).nonzero().view(-1)
+        nb = int(rest.numel())
+        if nb:
+            rows = segs.index_select(0, rest)
+            got = torch.empty(nb, dtype=torch.int32, device=dev)
+            for lo, hi in self._row_blocks(nb, m):
+                check(L.ecgvit_tok_dbscan_border(ptr(rows), nb, ptr(table), ptr(core_label), m, k, eps2, lo, hi, ptr(got), s), 'ecgvit_tok_dbscan_border')
+            labels[rest] = got
+        return core, labels, roots
+
+    def dbscan(self, sigs, eps, min_samples=5, offsets=None, idxs=None):
+        """`sklearn.cluster.dbscan` over the mean-removed segments of a store `fit` takes -> (core_sample_indices, labels), numpy int64 arrays
+        in the flat order of `segments`; -1 is noise.  sklearn's algorithm and its labels (clusters numbered by their first core segment, a
+        border segment with the first cluster that reaches it) with the f32 neighbour rule of include/ecgvit_hip.h: d2 <= fl32(eps)^2 on the
+        unfused f32 chain, which differs from sklearn's f64 comparison only for a pair within (k + 2) 2^-24 of eps.  A segment with a
+        non-finite sample is noise (sklearn raises)."""
+        eps2, min_samples = check_eps(eps), check_min_samples(min_samples)
+        st = self._segment_store(sigs, offsets, idxs)
+        with torch.cuda.device(sigs.device):
+            core, labels, _ = self._dbscan(self._segments(st)[0], eps2, min_samples)
+            return core.cpu().numpy(), labels.cpu().numpy().astype(np.int64)
+
+    def _fit_dbscan(self, sigs, method, cls_kwargs, offsets, idxs):
+        """the reference's post-processing of a clustering with outliers (:413-422, :489-490): noise is dropped, `lens` are the cluster sizes
+        (border members included) and `centers` the member means, through the Lloyd update's kernels (an id of -1 is left out there)"""
+        kw = dict(min_samples=method.min_samples)
+        kw.update(cls_kwargs or {})
+        unknown = set(kw) - {'eps', 'min_samples'}
+        if unknown:
+            raise ValueError(f'cls_kwargs {sorted(unknown)} are not supported: eps, min_samples')
+        if 'eps' not in kw:
+            raise ValueError("cls_kwargs needs 'eps'")
+        eps2, min_samples = check_eps(kw['eps']), check_min_samples(kw['min_samples'])
+        st = self._segment_store(sigs, offsets, idxs)
+        with torch.cuda.device(sigs.device):
+            from .hip import lib
+            segs, _, dst = self._segments(st, want_dst=True)
+            core, labels, roots = self._dbscan(segs, eps2, min_samples)
+            n_noise = int((labels < 0).sum())
+            V = 0 if roots is None else int(labels.max()) + 1
+            if V == 0:
+                raise ValueError(f"eps = {kw['eps']!r}, min_samples = {min_samples}: no cluster at all, every one of the {n_noise} segments is noise")
+            if V > MAX_CLUSTERS:
+                raise ValueError(f'{V} clusters: a vocabulary holds at most {MAX_CLUSTERS} (dbscan() still returns such labels)')
+            ids = st.new(torch.int32)
+            ids.view(-1)[dst] = labels
+            table = torch.zeros((V, self.k), dtype=torch.float32, device=sigs.device)      # every cluster holds a core segment: every row is written
+            lens = torch.zeros(V, dtype=torch.int64, device=sigs.device)
+            ws = torch.empty(lib().ecgvit_tok_workspace(V, self.k) // 8, dtype=torch.int64, device=sigs.device)
+            self._update(st, ids, table, lens, ws)
+        self.fit_method, self.n_sig, self.cls_th = 'dbscan', st.R, kw['eps']
+        self.n_iter_ = self.inertia_ = self.changed_ = None
+        self.n_noise, self.labels_ = n_noise, ids
+        self.centers, self.lens = table.cpu().numpy(), lens.cpu().numpy()
+        return self
+
     # ---- encode / decode ----------------------------------------------------------------------------
     def __call__(self, sig, th=None, offsets=None):
         """-> (ids, means): for (…, C, L) input both of shape (…, C, L // k + 1); for a ragged (12, S_total) store with `offsets` both (12, T_total)
@@ -349,7 +502,12 @@ class EcgTokenizer:
         seeded host generator), a `KMeansPlusPlus()` object (every restart seeded on the device, `kmeans_plusplus`; with n_init=8 the
         reference's default configuration) or a (n_clusters, k) array (Lloyd from a given start is deterministic).  Lloyd iterations are assign then update;
         they stop when an iteration changes no id, or at max_iter; n_init > 1 keeps the run of lowest inertia.  A centre that loses every
-        segment keeps its value with size 0.  Label order is the clustering's own, as in the reference; nothing is reordered."""
+        segment keeps its value with size 0.  Label order is the clustering's own, as in the reference; nothing is reordered.
+        method=Dbscan(min_samples=5) with cls_kwargs=dict(eps=..., min_samples=...): DBSCAN instead (`dbscan`), with the reference's
+        post-processing: noise is dropped (`n_noise`), `lens` are the cluster sizes, `centers` the member means, `labels_` every segment's label
+        (int32, device, -1: noise) in the layout of the ids `tok(sig)` returns; no cluster at all, or more than MAX_CLUSTERS, is a ValueError."""
+        if isinstance(method, Dbscan):
+            return self._fit_dbscan(sigs, method, cls_kwargs, offsets, idxs)
         if method != 'kmeans':
             if method in D_CLS_TH:
                 raise NotImplementedError(f"method = {method!r}: only 'kmeans' runs on the device (the hierarchical and density methods are not data-parallel in this form)")
@@ -399,5 +557,6 @@ class EcgTokenizer:
         table, lens, inertia, history = best
         self.fit_method, self.n_sig, self.cls_th = method, st.R, kw[D_CLS_TH[method]]
         self.n_iter_, self.inertia_, self.changed_ = len(history), inertia, history
+        self.n_noise = self.labels_ = None
         self.centers, self.lens = table.cpu().numpy(), lens.cpu().numpy()
         return self

@@ -579,6 +579,49 @@ int ecgvit_tok_seed(const float *x, const int64_t *src_off, int64_t lead_stride,
 int ecgvit_tok_decode(float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
                       const int64_t *dst_off, int64_t dst_stride, int R, int C, int64_t n_seg, int k, const int32_t *ids, const float *means,
                       const float *centers, int V, void *stream);
+/* DBSCAN (sklearn.cluster.DBSCAN, the reference's `dbscan` clustering) over the same mean-removed segments (dbscan.hip).  Additive entry
+ * points: the ABI version stays 6.  It is sklearn's algorithm, not its arithmetic: sklearn compares distances in f64.
+ *   order           the reference's flat order sigs.reshape(-1, k): record first (in the selection's order), then lead, then segment.  Segment s
+ *                   of lead c of record r is q = C * seg_cum[r] + c * n_r + s with n_r = seg_cum[r + 1] - seg_cum[r] -- the same rule for a
+ *                   rectangle, a ragged store and an idxs subset, so a record set gives the same labels in every store form.  n = C * n_seg
+ *                   < 2^31.
+ *   neighbours      i and j are neighbours iff d2(x_i, x_j) <= eps2, d2 the unfused f32 chain of the seeding (sum_e (a_e - b_e)^2 in sample
+ *                   order; every difference, product and addition rounds on its own) and eps2 = fl32(fl32(eps) * fl32(eps)), formed by the
+ *                   caller.  The chain is bit-symmetric in its arguments, so the graph is undirected, and a segment is its own neighbour.  A
+ *                   segment with a non-finite sample fails every comparison, its own too: it is nobody's neighbour and ends as noise.  The
+ *                   relative rounding error of the chain is at most (k + 2) 2^-24: the result differs from an f64 evaluation only where a pair
+ *                   lies that close to eps.
+ *   core            a segment whose neighbour count, itself included, is at least min_samples (the caller's comparison on `count`).
+ *   clusters        the connected components of the core segments under the neighbour relation, numbered 0, 1, ... by the smallest q among
+ *                   their core members.
+ *   border, noise   a non-core segment with a core neighbour takes the smallest label among its core neighbours, one with none is -1.  This is
+ *                   sklearn's result: it grows clusters one at a time in index order of their first core point and never relabels a point.
+ * ecgvit_tok_segments writes the dense table every later pass reads: segs (f32 [n][k], 16-byte aligned) = the mean-removed segments, bit for bit
+ * what every tokenizer kernel loads, and means (f32 [n]), both in q order; dst (NULL, or int64 [n]) = where segment q has its id in the (n, C, T)
+ * / (C, T_total) outputs of ecgvit_tok_assign (dst_off[r] + c * dst_stride + s).
+ * The pair sweeps take rows [row0, row1) of a table per call (0 <= row0 < row1 <= rows), so that the caller bounds the pairs of one launch; a
+ * workgroup holds ecgvit_tok_dbscan_rows(k) rows in registers and streams the other table through LDS in tiles of ecgvit_tok_dbscan_tile()
+ * segments.  No floating-point atomics, and no atomics at all outside `link`.
+ *   count   count[i] (int32 [n]) = the number of j in [0, n) with d2(segs_i, segs_j) <= eps2, for i in [row0, row1); one plain store per row.
+ *   link    core: the core segments in ascending q (f32 [m][k]); parent: int32 [m], parent[x] = x before the first call.  Rows i in [row0,
+ *           row1) meet the columns j < i; every edge joins the trees of i and j in a lock-free union-find: parent[x] <= x always, a find walks
+ *           down with relaxed loads, a union hooks the larger root under the smaller with an integer atomic min and, where that shows the
+ *           larger had been hooked meanwhile, goes on from the value it got back.  Every loop strictly descends indices and none waits for
+ *           another workgroup.  After all rows the root of a tree is its component's smallest index: the result has no run-to-run variation.
+ *   flatten root[i] (int32 [m]) = the root of core row i.  Ascending roots are ascending smallest q: their ranks are the labels.
+ *   border  rows: the non-core segments (f32 [nrows][k]); label[i] (int32 [nrows]) = the smallest core_label[j] (int32 [m], >= 0) over the core
+ *           rows j with d2 <= eps2, or -1, for i in [row0, row1).
+ * k in {8, 16, 32}, 0 <= eps2 < inf; anything else is ECGVIT_EINVAL and launches nothing. */
+int ecgvit_tok_segments(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
+                        const int64_t *dst_off, int64_t dst_stride, int R, int C, int64_t n_seg, int k, int pad, float *segs, float *means,
+                        int64_t *dst, void *stream);
+int ecgvit_tok_dbscan_tile(void);        /* segments per LDS tile of a sweep's column side */
+int ecgvit_tok_dbscan_rows(int k);       /* rows per workgroup of a sweep; 0 for an unsupported k */
+int ecgvit_tok_dbscan_count(const float *segs, int n, int k, float eps2, int row0, int row1, int32_t *count, void *stream);
+int ecgvit_tok_dbscan_link(const float *core, int m, int k, float eps2, int row0, int row1, int32_t *parent, void *stream);
+int ecgvit_tok_dbscan_flatten(const int32_t *parent, int m, int32_t *root, void *stream);
+int ecgvit_tok_dbscan_border(const float *rows, int nrows, const float *core, const int32_t *core_label, int m, int k, float eps2, int row0, int row1,
+                             int32_t *label, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * the Zheng et al. denoiser (denoise.py; the reference's preprocess/data_preprocessor.py:22-148 and its MATLAB twin): zero-phase low-pass, robust
