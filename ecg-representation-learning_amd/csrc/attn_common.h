@@ -8,9 +8,6 @@
 #pragma once
 #include "common.h"
 
-// longest record (tokens) the fused bf16 attention covers: the forward, backward and CLS-row entry points return ECGVIT_EINVAL above it
-#define ECGVIT_ATTN_MAX_N 2048
-
 // The fused attention of attention_varlen.hip for a uniform (n_tok == nullptr, dh = 128 only), padded (tok_off == nullptr) or packed batch; the
 // dh = 128 branches of ecgvit_attention_fwd / _bwd (attention.hip) call them.  Library-internal: hidden, not part of the C-ABI.
 __attribute__((visibility("hidden"))) int attn_fwd_run(const void *qkv, void *out, float *lse, const int32_t *n_tok, const int32_t *tok_off, int B,

@@ -17,7 +17,7 @@
 // strictly descends indices: each ends, and none waits for another workgroup.  The root of a tree is its smallest index, whatever the order.
 #include "tok_common.h"
 
-#define DBSCAN_TILE 256                                  // segments per LDS tile of the column side
+#define DBSCAN_TILE ECGVIT_TOK_DBSCAN_TILE               // segments per LDS tile of the column side
 #define DBSCAN_ROWS(K) ((K) == 32 ? 2 : 4)               // rows per thread: 32 / 64 / 64 registers at k = 8 / 16 / 32
 
 enum { DB_COUNT = 0, DB_LINK = 1, DB_BORDER = 2 };

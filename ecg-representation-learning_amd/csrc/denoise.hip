@@ -1,19 +1,17 @@
 // The Zheng et al. denoiser (denoise.py; the reference's preprocess/data_preprocessor.py): zero-phase low-pass, the noise estimate and non-local
 // means, per (record, lead), over a record store addressed as fit_stats.hip addresses it.  Contracts and the order of every sum: include/ecgvit_hip.h.
 //
-// One workgroup per (record, lead) in every kernel but the two tiled along time for records past DN_MAX_LEN (nlm_tiled_kernel, rloess_tiled_kernel:
+// One workgroup per (record, lead) in every kernel but the two tiled along time for records past ECGVIT_DENOISE_MAX_LEN (nlm_tiled_kernel, rloess_tiled_kernel:
 // grid (record, lead, tile), each described where it stands).  The robust LOESS baseline (rloess_kernel) is described at the end of the file.
 // Of the other three:  The low-pass and the noise estimate are sequential recurrences in f64: lane 0 walks
 // them chunk by chunk through LDS while the whole workgroup moves the chunks (coalesced), and their f64 intermediates live in a caller's
 // workspace.  Non-local means is the hot path: the lead sits in LDS as f32, a lane owns runs of NLM_RUN consecutive output samples.
 #include "common.h"
 
-#define DN_MAX_LEN 32768            // samples per record: 128 KiB of f32 in LDS for the non-local means
-#define DN_MAX_LEN_TILED (1 << 25)  // samples per record of the _long / _tiled entry points (24 hours at 360 Hz): nothing keeps a whole lead in LDS
 #define DN_WS_PAD 64                // workspace doubles per lead beyond max_len (the low-pass's two extensions: 2 * 3 * 9 = 54)
-#define DN_MAX_TAPS 9
+#define DN_MAX_TAPS ECGVIT_DENOISE_MAX_TAPS
 
-static bool dn_store_ok(const float *x, const int64_t *src_off, const int32_t *raw_len, int R, int C, int max_len, int cap = DN_MAX_LEN) {
+static bool dn_store_ok(const float *x, const int64_t *src_off, const int32_t *raw_len, int R, int C, int max_len, int cap = ECGVIT_DENOISE_MAX_LEN) {
     return x && src_off && raw_len && R > 0 && C > 0 && C <= 65535 && max_len > 0 && max_len <= cap && (reinterpret_cast<uintptr_t>(x) & 3u) == 0 &&
            (reinterpret_cast<uintptr_t>(src_off) & 7u) == 0 && (reinterpret_cast<uintptr_t>(raw_len) & 3u) == 0;
 }
@@ -22,8 +20,8 @@ static int64_t dn_workspace(int R, int C, int max_len, int cap) {
     if (R <= 0 || C <= 0 || max_len <= 0 || max_len > cap) return 0;
     return (int64_t)R * C * (max_len + DN_WS_PAD) * 8;
 }
-int64_t ecgvit_denoise_workspace(int R, int C, int max_len) { return dn_workspace(R, C, max_len, DN_MAX_LEN); }
-int64_t ecgvit_denoise_workspace_long(int R, int C, int max_len) { return dn_workspace(R, C, max_len, DN_MAX_LEN_TILED); }
+int64_t ecgvit_denoise_workspace(int R, int C, int max_len) { return dn_workspace(R, C, max_len, ECGVIT_DENOISE_MAX_LEN); }
+int64_t ecgvit_denoise_workspace_long(int R, int C, int max_len) { return dn_workspace(R, C, max_len, ECGVIT_DENOISE_MAX_LEN_TILED); }
 
 // =====================================================================================================
 // zero-phase IIR filter (scipy.signal.filtfilt with its defaults)
@@ -131,11 +129,11 @@ static int ff_launch(int cap, const float *x, float *out, const int64_t *src_off
 
 int ecgvit_filtfilt(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
                     int max_len, const double *b, const double *a, const double *zi, int ntaps, void *workspace, void *stream) {
-    return ff_launch(DN_MAX_LEN, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, b, a, zi, ntaps, workspace, stream);
+    return ff_launch(ECGVIT_DENOISE_MAX_LEN, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, b, a, zi, ntaps, workspace, stream);
 }
 int ecgvit_filtfilt_long(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
                          int max_len, const double *b, const double *a, const double *zi, int ntaps, void *workspace, void *stream) {
-    return ff_launch(DN_MAX_LEN_TILED, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, b, a, zi, ntaps, workspace, stream);
+    return ff_launch(ECGVIT_DENOISE_MAX_LEN_TILED, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, b, a, zi, ntaps, workspace, stream);
 }
 
 // =====================================================================================================
@@ -238,11 +236,11 @@ static int sg_launch(int cap, const float *x, const int64_t *src_off, int64_t le
 
 int ecgvit_nlm_sigma(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len, double *sigma,
                      void *workspace, void *stream) {
-    return sg_launch(DN_MAX_LEN, x, src_off, lead_stride, raw_len, R, C, max_len, sigma, workspace, stream);
+    return sg_launch(ECGVIT_DENOISE_MAX_LEN, x, src_off, lead_stride, raw_len, R, C, max_len, sigma, workspace, stream);
 }
 int ecgvit_nlm_sigma_long(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len, double *sigma,
                           void *workspace, void *stream) {
-    return sg_launch(DN_MAX_LEN_TILED, x, src_off, lead_stride, raw_len, R, C, max_len, sigma, workspace, stream);
+    return sg_launch(ECGVIT_DENOISE_MAX_LEN_TILED, x, src_off, lead_stride, raw_len, R, C, max_len, sigma, workspace, stream);
 }
 
 // =====================================================================================================
@@ -255,11 +253,11 @@ int ecgvit_nlm_sigma_long(const float *x, const int64_t *src_off, int64_t lead_s
 // The last run of a record is moved back to end on the last output sample (it recomputes a few samples of its neighbour and stores only its own),
 // so that every lane of a record longer than one run takes the fast body for the same t0.
 // =====================================================================================================
-#define NLM_RUN 15
+#define NLM_RUN ECGVIT_DENOISE_NLM_RUN
 #define NLM_P 10
 #define NLM_U 1                     // t0 per neighbour-window load of the fast body: 1 keeps the kernel at 158 VGPRs, three waves per SIMD (4: 256)
 #define NLM_WN (NLM_RUN + 2 * NLM_P)
-#define NLM_MAX_THREADS 512
+#define NLM_MAX_THREADS ECGVIT_DENOISE_NLM_MAX_THREADS
 
 struct NlmArgs {
     const float *x;
@@ -404,7 +402,7 @@ static bool nlm_args(NlmArgs &g, int cap, const float *x, float *out, const int6
 int ecgvit_nlm_denoise(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len,
                        const double *sigma, double scale, int patch_wd, int sch_wd, void *stream) {
     NlmArgs g;
-    if (!nlm_args(g, DN_MAX_LEN, x, out, src_off, lead_stride, raw_len, R, C, max_len, sigma, scale, patch_wd, sch_wd)) return ECGVIT_EINVAL;
+    if (!nlm_args(g, ECGVIT_DENOISE_MAX_LEN, x, out, src_off, lead_stride, raw_len, R, C, max_len, sigma, scale, patch_wd, sch_wd)) return ECGVIT_EINVAL;
     // one lane per run of the longest record, whole waves, at most NLM_MAX_THREADS (a lane then takes several runs)
     const int M = max_len - 2 * patch_wd - 1;
     int runs = M > 0 ? (M + NLM_RUN - 1) / NLM_RUN : 1;
@@ -412,7 +410,7 @@ int ecgvit_nlm_denoise(const float *x, float *out, const int64_t *src_off, int64
     if (threads > NLM_MAX_THREADS) threads = NLM_MAX_THREADS;
     if (max_len <= 4096) hipLaunchKernelGGL(nlm_kernel<4096>, dim3(R, C), dim3(threads), 0, as_stream(stream), g);
     else if (max_len <= 8192) hipLaunchKernelGGL(nlm_kernel<8192>, dim3(R, C), dim3(threads), 0, as_stream(stream), g);
-    else hipLaunchKernelGGL(nlm_kernel<DN_MAX_LEN>, dim3(R, C), dim3(threads), 0, as_stream(stream), g);
+    else hipLaunchKernelGGL(nlm_kernel<ECGVIT_DENOISE_MAX_LEN>, dim3(R, C), dim3(threads), 0, as_stream(stream), g);
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
 }
@@ -429,7 +427,6 @@ int ecgvit_nlm_denoise(const float *x, float *out, const int64_t *src_off, int64
 // -----------------------------------------------------------------------------------------------------
 #define NLT_CHUNK 256
 #define NLT_SPAN (NLT_CHUNK + NLM_RUN - 1 + 2 * NLM_P)
-#define NLT_MAX_TILES 65535
 
 __global__ __launch_bounds__(NLM_MAX_THREADS) void nlm_tiled_kernel(NlmArgs g) {
     __shared__ float sb[2][NLT_SPAN];
@@ -505,14 +502,14 @@ __global__ __launch_bounds__(NLM_MAX_THREADS) void nlm_tiled_kernel(NlmArgs g) {
 int ecgvit_nlm_denoise_tiled(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len,
                              const double *sigma, double scale, int patch_wd, int sch_wd, int tile_runs, void *stream) {
     NlmArgs g;
-    if (tile_runs < 0 || !nlm_args(g, DN_MAX_LEN_TILED, x, out, src_off, lead_stride, raw_len, R, C, max_len, sigma, scale, patch_wd, sch_wd))
+    if (tile_runs < 0 || !nlm_args(g, ECGVIT_DENOISE_MAX_LEN_TILED, x, out, src_off, lead_stride, raw_len, R, C, max_len, sigma, scale, patch_wd, sch_wd))
         return ECGVIT_EINVAL;
     if (out == x) return ECGVIT_EINVAL;        // a workgroup reads samples that another one writes
     const int64_t M = (int64_t)max_len - 2 * (int64_t)patch_wd - 1;
     const int runs = M > 0 ? (int)((M + NLM_RUN - 1) / NLM_RUN) : 1;
     g.tile_runs = min(tile_runs == 0 ? NLM_MAX_THREADS : tile_runs, runs);
     const int tiles = (runs + g.tile_runs - 1) / g.tile_runs;
-    if (tiles > NLT_MAX_TILES) return ECGVIT_EINVAL;
+    if (tiles > ECGVIT_DENOISE_MAX_TILES) return ECGVIT_EINVAL;
     int threads = (g.tile_runs + WAVE - 1) / WAVE * WAVE;
     if (threads > NLM_MAX_THREADS) threads = NLM_MAX_THREADS;
     hipLaunchKernelGGL(nlm_tiled_kernel, dim3(R, C, tiles), dim3(threads), 0, as_stream(stream), g);
@@ -539,8 +536,6 @@ int ecgvit_nlm_denoise_tiled(const float *x, float *out, const int64_t *src_off,
 // =====================================================================================================
 #pragma clang fp contract(off)
 #define RL_THREADS 512
-#define RL_MAX_POINTS 1024
-#define RL_MAX_ITERS 10
 #define RL_CUT 0.34
 #define RL_MIN_MAD 2.2250738585072014e-308
 
@@ -734,12 +729,10 @@ template <int NV, int CAP> __global__ __launch_bounds__(RL_THREADS) void rloess_
 // tiled along time: grid (record, lead, tile), a workgroup owns tile_samples consecutive output samples and keeps them with one window of halo on
 // either side in LDS: x[max(0, j0 - m) .. min(n, j0 + tile_samples + m)).  A sample's arithmetic reads only its window and is rl_sample's, so the
 // output and the iteration counts are rloess_kernel's bit for bit.  Other workgroups write out while this one reads x: the launcher refuses out == x.
-#define RLT_LDS 4096                // samples: a tile and two windows
-#define RLT_TILE (RLT_LDS - 2 * RL_MAX_POINTS)
-#define RLT_MAX_TILES 65535
+#define RLT_TILE (ECGVIT_DENOISE_LOESS_LDS - 2 * ECGVIT_DENOISE_MAX_POINTS)
 
 template <int NV> __global__ __launch_bounds__(RL_THREADS) void rloess_tiled_kernel(RloessArgs g) {
-    __shared__ float s[RLT_LDS];
+    __shared__ float s[ECGVIT_DENOISE_LOESS_LDS];
     const int rec = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
     const int n = g.raw_len[rec];
     if (n <= 0 || n > g.max_len) return;
@@ -750,7 +743,7 @@ template <int NV> __global__ __launch_bounds__(RL_THREADS) void rloess_tiled_ker
     if (j0 >= n) return;               // a tile past this record's end: before the barrier
     const int j1 = min(n, j0 + g.tile_samples);
     const int s0 = max(0, j0 - m), s1 = min(n, j0 + g.tile_samples + m);
-    if (s1 - s0 > RLT_LDS) return;     // (the launcher refused a tile that does not fit with the widest window)
+    if (s1 - s0 > ECGVIT_DENOISE_LOESS_LDS) return;     // (the launcher refused a tile that does not fit with the widest window)
     const int64_t base = g.src_off[rec] + (int64_t)c * g.lead_stride;
     const float *x = g.x + base;
     float *out = g.out + base;
@@ -781,14 +774,14 @@ template <class F> static void rl_dispatch(int nv, F launch) {
 static int rl_args(RloessArgs &g, int cap, const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C,
                    int min_len, int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters) {
     if (!dn_store_ok(x, src_off, raw_len, R, C, max_len, cap) || !out || (reinterpret_cast<uintptr_t>(out) & 3u) || lead_stride <= 0) return 0;
-    if (degree < 1 || degree > 2 || robust_iters < 0 || robust_iters > RL_MAX_ITERS || (subtract != 0 && subtract != 1)) return 0;
+    if (degree < 1 || degree > 2 || robust_iters < 0 || robust_iters > ECGVIT_DENOISE_MAX_ROBUST_ITERS || (subtract != 0 && subtract != 1)) return 0;
     if (!(frac >= 0.0 && frac <= 1.0) || min_len < degree + 2 || min_len > max_len) return 0;
     int widest = npoints;
     if (frac > 0.0) {          // the window of the shortest and of the longest record: a fraction's width grows with the length
         widest = rl_frac_points(max_len, frac);
         if (rl_frac_points(min_len, frac) < degree + 2) return 0;
     }
-    if (widest < degree + 2 || widest > RL_MAX_POINTS) return 0;
+    if (widest < degree + 2 || widest > ECGVIT_DENOISE_MAX_POINTS) return 0;
     g.x = x; g.out = out; g.src_off = src_off; g.lead_stride = lead_stride; g.raw_len = raw_len; g.iters = iters; g.frac = frac;
     g.C = C; g.max_len = max_len; g.npoints = npoints; g.degree = degree; g.robust_iters = robust_iters; g.subtract = subtract; g.tile_samples = 0;
     return min(widest, max_len);
@@ -797,14 +790,14 @@ static int rl_args(RloessArgs &g, int cap, const float *x, float *out, const int
 int ecgvit_rloess(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
                   int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters, void *stream) {
     RloessArgs g;
-    const int widest = rl_args(g, DN_MAX_LEN, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, npoints, frac, degree, robust_iters, subtract,
+    const int widest = rl_args(g, ECGVIT_DENOISE_MAX_LEN, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, npoints, frac, degree, robust_iters, subtract,
                                iters);
     if (widest <= 0) return ECGVIT_EINVAL;
     const int nv = (widest + 63) / 64;
     const dim3 grid(R, C), block(RL_THREADS);
     hipStream_t st = as_stream(stream);
     if (max_len <= 8192) rl_dispatch(nv, [&](auto v) { hipLaunchKernelGGL((rloess_kernel<decltype(v)::value, 8192>), grid, block, 0, st, g); });
-    else rl_dispatch(nv, [&](auto v) { hipLaunchKernelGGL((rloess_kernel<decltype(v)::value, DN_MAX_LEN>), grid, block, 0, st, g); });
+    else rl_dispatch(nv, [&](auto v) { hipLaunchKernelGGL((rloess_kernel<decltype(v)::value, ECGVIT_DENOISE_MAX_LEN>), grid, block, 0, st, g); });
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
 }
@@ -813,14 +806,14 @@ int ecgvit_rloess_tiled(const float *x, float *out, const int64_t *src_off, int6
                         int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters, int tile_samples,
                         void *stream) {
     RloessArgs g;
-    const int widest = rl_args(g, DN_MAX_LEN_TILED, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, npoints, frac, degree, robust_iters,
+    const int widest = rl_args(g, ECGVIT_DENOISE_MAX_LEN_TILED, x, out, src_off, lead_stride, raw_len, R, C, min_len, max_len, npoints, frac, degree, robust_iters,
                                subtract, iters);
     if (widest <= 0 || tile_samples < 0) return ECGVIT_EINVAL;
     if (out == x) return ECGVIT_EINVAL;        // a workgroup reads samples that another one writes
     g.tile_samples = tile_samples == 0 ? RLT_TILE : tile_samples;
-    if (g.tile_samples > RLT_LDS || g.tile_samples + 2 * widest > RLT_LDS) return ECGVIT_EINVAL;
+    if (g.tile_samples > ECGVIT_DENOISE_LOESS_LDS || g.tile_samples + 2 * widest > ECGVIT_DENOISE_LOESS_LDS) return ECGVIT_EINVAL;
     const int tiles = (max_len + g.tile_samples - 1) / g.tile_samples;
-    if (tiles > RLT_MAX_TILES) return ECGVIT_EINVAL;
+    if (tiles > ECGVIT_DENOISE_MAX_TILES) return ECGVIT_EINVAL;
     const dim3 grid(R, C, tiles), block(RL_THREADS);
     hipStream_t st = as_stream(stream);
     rl_dispatch((widest + 63) / 64, [&](auto v) { hipLaunchKernelGGL(rloess_tiled_kernel<decltype(v)::value>, grid, block, 0, st, g); });

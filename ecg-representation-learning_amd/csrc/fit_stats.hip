@@ -10,8 +10,8 @@
 
 #define FIT_THREADS 256
 #define FIT_GROUPS 512     // record groups per lead (fewer when there are fewer records)
-#define FIT_TARGETS 16     // order statistics per lead and select
-#define FIT_BINS 256       // 8-bit digits: four passes over the 32-bit key
+#define FIT_TARGETS ECGVIT_FIT_TARGETS   // order statistics per lead and select
+#define FIT_BINS ECGVIT_FIT_BINS         // 8-bit digits: four passes over the 32-bit key
 #define FIT_REPS 32        // copies of every bin in the top-digit pass (see fit_hist_top_kernel)
 
 typedef unsigned long long u64;

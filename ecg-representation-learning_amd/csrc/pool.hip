@@ -22,7 +22,7 @@ __global__ __launch_bounds__(POOL_THREADS) void pool_records_kernel(const T *__r
     const int b = blockIdx.x / nchunk, c0 = (blockIdx.x % nchunk) * CW;
     const int sub = threadIdx.x & 7, slot = threadIdx.x >> 3;
     const int col = c0 + sub * VN;
-    const int n = mode == 0 ? 1 : (n_tok ? n_tok[b] : N);
+    const int n = mode == ECGVIT_POOL_CLS ? 1 : (n_tok ? n_tok[b] : N);
     const int64_t row0 = tok_off ? (int64_t)tok_off[b] : (int64_t)b * N;
     float acc[VN];
 #pragma unroll
@@ -86,8 +86,8 @@ __global__ __launch_bounds__(256) void pool_layernorm_kernel(float *__restrict__
 
 int ecgvit_pool_records(const void *x, float *out, const int32_t *n_tok, const int32_t *tok_off, int B, int N, int d, int mode,
                         const float *gamma, const float *beta, float eps, int dtype, void *stream) {
-    if (!x || !out || B <= 0 || N <= 0 || d <= 0 || d % 8 != 0 || d > 2048) return ECGVIT_EINVAL;
-    if (mode != 0 && mode != 1) return ECGVIT_EINVAL;
+    if (!x || !out || B <= 0 || N <= 0 || d <= 0 || d % 8 != 0 || d > ECGVIT_ROW_MAX_D) return ECGVIT_EINVAL;
+    if (mode != ECGVIT_POOL_CLS && mode != ECGVIT_POOL_MEAN) return ECGVIT_EINVAL;
     if ((gamma == nullptr) != (beta == nullptr)) return ECGVIT_EINVAL;
     const int rc = dispatch_dtype(dtype, [&](auto e) -> int {
         using T = decltype(e);

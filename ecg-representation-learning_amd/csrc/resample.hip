@@ -5,12 +5,8 @@
 // every root of unity is read from the two tables the caller passes.
 #include "common.h"
 
-#define RS_MAX_LEN (1 << 25)        // samples per record: the cap of the denoiser's _long / _tiled entry points
-#define RS_MAX_CHIRP (1 << 24)      // samples of a length on the chirp route: M <= 2^25, the cap of the passes
-#define RS_MAX_GENERIC 65536        // the widest generic-radix pass that is launched (a thread walks all r inputs of its output)
 #define RS_MAX_PASSES 32
 #define RS_THREADS 256
-#define RS_MAX_GRID_Y 65535
 
 typedef double2 cd;
 
@@ -22,7 +18,7 @@ __device__ __forceinline__ cd rs_sub(cd a, cd b) { return cd{a.x - b.x, a.y - b.
 static const int RS_BUILT[] = {25, 16, 8, 5, 4, 3, 2};
 
 static int rs_plan(int n, int *radices, int cap) {
-    if (n < 1 || n > RS_MAX_LEN || cap < 0 || (cap > 0 && !radices)) return -1;
+    if (n < 1 || n > ECGVIT_RESAMPLE_MAX_LEN || cap < 0 || (cap > 0 && !radices)) return -1;
     int cnt = 0;
     for (int r : RS_BUILT)
         while (n % r == 0) {
@@ -49,17 +45,17 @@ static bool rs_is_built(int r) {
     return false;
 }
 
-// the plan of a length the launcher runs: every generic radix within RS_MAX_GENERIC
+// the plan of a length the launcher runs: every generic radix within ECGVIT_RESAMPLE_MAX_GENERIC
 static int rs_plan_checked(int n, int *radices) {
     const int cnt = rs_plan(n, radices, RS_MAX_PASSES);
     for (int i = 0; i < cnt; ++i)
-        if (!rs_is_built(radices[i]) && radices[i] > RS_MAX_GENERIC) return -1;
+        if (!rs_is_built(radices[i]) && radices[i] > ECGVIT_RESAMPLE_MAX_GENERIC) return -1;
     return cnt;
 }
 
 static int64_t rs_workspace(int R, int C, int n_in, int n_out) {
     int rad[RS_MAX_PASSES];
-    if (R <= 0 || C <= 0 || (C & 1) || C > 65534 || (int64_t)R * (C / 2) > RS_MAX_GRID_Y) return 0;
+    if (R <= 0 || C <= 0 || (C & 1) || C > 65534 || (int64_t)R * (C / 2) > ECGVIT_RESAMPLE_MAX_GRID_Y) return 0;
     if (rs_plan_checked(n_in, rad) < 0 || rs_plan_checked(n_out, rad) < 0) return 0;
     return 2 * 16 * (int64_t)R * (C / 2) * (int64_t)(n_in > n_out ? n_in : n_out);
 }
@@ -68,9 +64,9 @@ int64_t ecgvit_resample_workspace(int R, int C, int n_in, int n_out) { return rs
 
 // ---- the chirp route (Bluestein): a whole transform of length n as a circular convolution of length M, the smallest 2^a 3^b 5^c >= 2 n - 1 ------
 static int rs_chirp_length(int n) {
-    if (n < 1 || n > RS_MAX_CHIRP) return -1;
+    if (n < 1 || n > ECGVIT_RESAMPLE_MAX_CHIRP) return -1;
     const int64_t need = 2 * (int64_t)n - 1;
-    int64_t best = (int64_t)RS_MAX_LEN;         // 2^25 >= 2 n - 1 for every admitted n
+    int64_t best = (int64_t)ECGVIT_RESAMPLE_MAX_LEN;         // 2^25 >= 2 n - 1 for every admitted n
     for (int64_t p5 = 1; p5 <= best; p5 *= 5)
         for (int64_t p3 = p5; p3 <= best; p3 *= 3) {
             int64_t m = p3;
@@ -99,7 +95,7 @@ static bool rs_side_plan(int n, bool chirp, rs_side *s) {
 
 static int64_t rs_chirp_workspace(int R, int C, int n_in, int n_out, int chirp_in, int chirp_out) {
     rs_side a, b;
-    if (R <= 0 || C <= 0 || (C & 1) || C > 65534 || (int64_t)R * (C / 2) > RS_MAX_GRID_Y) return 0;
+    if (R <= 0 || C <= 0 || (C & 1) || C > 65534 || (int64_t)R * (C / 2) > ECGVIT_RESAMPLE_MAX_GRID_Y) return 0;
     if (!rs_side_plan(n_in, chirp_in != 0, &a) || !rs_side_plan(n_out, chirp_out != 0, &b)) return 0;
     return 2 * 16 * (int64_t)R * (C / 2) * (int64_t)(a.len > b.len ? a.len : b.len);
 }
@@ -453,8 +449,8 @@ int ecgvit_resample_chirp(const float *x, float *out, const int64_t *src_off, in
 // tools/ecgvit_hip_tools.h: ONE pass of radix r (after passes of product Ns) over T transforms of length n, in -> out, as ecgvit_resample
 // launches it: what tools/resample_rate.py times per pass kind
 extern "C" int ecgvit_tools_resample_pass(const void *in, void *out, const double *tw, int n, int T, int Ns, int r, void *stream) {
-    if (!in || !out || in == out || !tw || n < 1 || n > RS_MAX_LEN || T < 1 || T > RS_MAX_GRID_Y || r < 2 || Ns < 1 || n % r || (n / r) % Ns) return ECGVIT_EINVAL;
-    if (!rs_is_built(r) && r > RS_MAX_GENERIC) return ECGVIT_EINVAL;
+    if (!in || !out || in == out || !tw || n < 1 || n > ECGVIT_RESAMPLE_MAX_LEN || T < 1 || T > ECGVIT_RESAMPLE_MAX_GRID_Y || r < 2 || Ns < 1 || n % r || (n / r) % Ns) return ECGVIT_EINVAL;
+    if (!rs_is_built(r) && r > ECGVIT_RESAMPLE_MAX_GENERIC) return ECGVIT_EINVAL;
     rs_run_passes(reinterpret_cast<cd *>(const_cast<void *>(in)), reinterpret_cast<cd *>(out), reinterpret_cast<const cd *>(tw), n, T, &r, 1, as_stream(stream));
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
@@ -476,7 +472,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_tools_chirp_post_kernel(const c
 // post multiply; the pre multiply as a kernel of its own)
 extern "C" int ecgvit_tools_resample_chirp(const void *in, void *out, const double *chirp, const double *filter, const double *tw_M, int n, int M, int T,
                                            void *workspace, void *stream) {
-    if (!in || !out || !chirp || !filter || !tw_M || !workspace || T < 1 || T > RS_MAX_GRID_Y) return ECGVIT_EINVAL;
+    if (!in || !out || !chirp || !filter || !tw_M || !workspace || T < 1 || T > ECGVIT_RESAMPLE_MAX_GRID_Y) return ECGVIT_EINVAL;
     rs_side s;
     if (!rs_side_plan(n, true, &s) || s.len != M) return ECGVIT_EINVAL;
     cd *a = reinterpret_cast<cd *>(workspace), *b = a + (int64_t)T * M;

@@ -861,7 +861,7 @@ int ecgvit_embed_bwd_ragged(const void *dX, void *dtok, float *dcls, float *dpos
 
 int ecgvit_layernorm_fwd(const void *x, const float *gamma, const float *beta, void *y, float *mean, float *rstd, int64_t rows,
                          int d, float eps, int dtype, void *stream) {
-    if (rows <= 0 || d <= 0 || d % 8 != 0 || d > 2048) return ECGVIT_EINVAL;
+    if (rows <= 0 || d <= 0 || d % 8 != 0 || d > ECGVIT_ROW_MAX_D) return ECGVIT_EINVAL;
     const int grid = grid_for_rows(rows);
     if (dtype != ECGVIT_F32 && dtype != ECGVIT_BF16) return ECGVIT_EINVAL;
     if (dtype == ECGVIT_BF16 && ln_fit(d)) {
@@ -907,7 +907,7 @@ static int ln_bwd_launch(const void *dy, const void *x, const float *gamma, cons
     if (mask_row_pitch < 1 || (mask_row_pitch > 1 && (g8 || rows * mask_row_pitch * d >= (1ll << 32)))) return ECGVIT_EINVAL;
     const uint32_t mrp = (uint32_t)mask_row_pitch;
     if (g8 && (!extra || !q8_scale || !q8_amax || dtype != ECGVIT_BF16 || !ln_fit(d) || (int64_t)rows * d >= (1ll << 31))) return ECGVIT_EINVAL;
-    if (rows <= 0 || d <= 0 || d % 8 != 0 || d > 2048 || !partial) return ECGVIT_EINVAL;
+    if (rows <= 0 || d <= 0 || d % 8 != 0 || d > ECGVIT_ROW_MAX_D || !partial) return ECGVIT_EINVAL;
     if (extra && (!dcolsum || (dropout_p > 0.f && !dxm && !g8) || ((int64_t)rows * d) % 2)) return ECGVIT_EINVAL;
     const int grid = ln_bwd_grid(rows);
     const int np = extra ? 3 : 2;

@@ -196,9 +196,9 @@ __global__ __launch_bounds__(TOK_THREADS) void tok_finish_kernel(const u64 *__re
 // Step 0 is the same pipeline with one candidate, the given first segment, from closest = +inf (which is never quantised, nor stored: the
 // array is first written by sweep 1 and first read by pick 1).
 // =====================================================================================================
-#define SEED_SPAN 1024                                   // segments per workgroup of the sweep: four per thread
+#define SEED_SPAN ECGVIT_TOK_SEED_SPAN                    // segments per workgroup of the sweep: four per thread
 #define SEED_PER (SEED_SPAN / TOK_THREADS)
-#define SEED_TMAX 16                                     // candidates per step
+#define SEED_TMAX ECGVIT_TOK_MAX_LOCAL_TRIALS             // candidates per step
 #define SEED_PICK_THREADS SEED_SPAN                      // the pick scans a sweep span with one segment per thread
 #define SEED_WS_CAND_G 16                                // workspace: the maximum's bits at 0, the candidates' g (int64 [16]),
 #define SEED_WS_CAND_C (SEED_WS_CAND_G + SEED_TMAX * 8)  //   the candidates' segments (f32 [16][32]),
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(TOK_THREADS) void tok_decode_kernel(TokStore st, fl
 // =====================================================================================================
 // entry points
 // =====================================================================================================
-static inline bool tok_table_ok(int V) { return V >= 1 && V <= 65536; }
+static inline bool tok_table_ok(int V) { return V >= 1 && V <= ECGVIT_TOK_MAX_CLUSTERS; }
 
 int ecgvit_tok_assign(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, const int64_t *seg_cum,
                       const int64_t *dst_off, int64_t dst_stride, int R, int C, int64_t n_seg, int k, int pad, const float *centers, int V,

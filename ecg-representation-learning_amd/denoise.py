@@ -32,18 +32,20 @@ import math
 import numpy as np
 import torch
 
+from . import hip
+from .hip import lib, run, ptr, stream
 from .records import DeviceTables, RecordSelection, check_device_store, host_chunks, select_records
 
-MAX_LEN = 32768            # samples per record: the resident non-local means and LOESS keep a lead in LDS
-MAX_LEN_TILED = 1 << 25    # samples per record with tiled=True (24 hours at 360 Hz)
-NLM_RUN = 15               # output samples per run of the non-local means: `tile` is a multiple of it there
-NLM_TILE = 512 * NLM_RUN   # the default tile of the non-local means: one run per lane of a 512-lane workgroup
-LOESS_LDS = 4096           # samples the tiled LOESS keeps in LDS: a tile and two windows
-LOESS_TILE = LOESS_LDS - 2 * 1024      # its default tile
-_MAX_TILES = 65535         # tiles per lead (the grid's third dimension)
-MAX_TAPS = 9
-MAX_POINTS = 1024          # samples per LOESS window: covers every sampling rate of the reference's config (250, 257, 500, 1000)
-MAX_ROBUST_ITERS = 10
+MAX_LEN = hip.DENOISE_MAX_LEN                # samples per record: the resident non-local means and LOESS keep a lead in LDS
+MAX_LEN_TILED = hip.DENOISE_MAX_LEN_TILED    # samples per record with tiled=True (24 hours at 360 Hz)
+MAX_TAPS = hip.DENOISE_MAX_TAPS
+MAX_POINTS = hip.DENOISE_MAX_POINTS          # samples per LOESS window: covers every sampling rate of the reference's config (250, 257, 500, 1000)
+MAX_ROBUST_ITERS = hip.DENOISE_MAX_ROBUST_ITERS
+NLM_RUN = hip.DENOISE_NLM_RUN                # output samples per run of the non-local means: `tile` is a multiple of it there
+NLM_TILE = hip.DENOISE_NLM_MAX_THREADS * NLM_RUN   # the default tile of the non-local means: one run per lane of the widest workgroup
+LOESS_LDS = hip.DENOISE_LOESS_LDS            # samples the tiled LOESS keeps in LDS: a tile and two windows
+LOESS_TILE = LOESS_LDS - 2 * MAX_POINTS      # its default tile
+_MAX_TILES = hip.DENOISE_MAX_TILES           # tiles per lead (the grid's third dimension)
 C = 12                     # leads per record: what `select_records` admits
 _WS_BYTES = 256 * 2 ** 20  # f64 intermediates of the low-pass / noise estimate per launch: more records go in several launches
 
@@ -113,14 +115,13 @@ def _dp(arr):
 
 
 # ---- stores ---------------------------------------------------------------------------------------------------------------------------
-_ENTRY = {   # by `tiled`: the entry points that differ only in their cap, under the names `check` reports
+_ENTRY = {   # by `tiled`: the entry points that differ only in their cap
     False: dict(workspace='ecgvit_denoise_workspace', filtfilt='ecgvit_filtfilt', sigma='ecgvit_nlm_sigma'),
     True: dict(workspace='ecgvit_denoise_workspace_long', filtfilt='ecgvit_filtfilt_long', sigma='ecgvit_nlm_sigma_long')}
 
 
 def launches(tab, entry):
     """(first record, records) per launch over the `DeviceTables` tab, so that the f64 workspace of a launch stays within _WS_BYTES"""
-    from .hip import lib
     step = max(1, _WS_BYTES // getattr(lib(), entry['workspace'])(1, C, tab.max_len))
     return [(lo, min(step, tab.R - lo)) for lo in range(0, tab.R, step)]
 
@@ -242,7 +243,6 @@ def _sweep(records, s, out, chunk_records, stage):
 
 # ---- the stages -----------------------------------------------------------------------------------------------------------------------
 def _workspace(tab, device, entry):
-    from .hip import lib
     R = max(cnt for _, cnt in launches(tab, entry))
     return torch.empty(getattr(lib(), entry['workspace'])(R, C, tab.max_len) // 8, dtype=torch.float64, device=device)
 
@@ -252,7 +252,6 @@ def lowpass_taps(records, b, a, zi=None, offsets=None, idxs=None, out=None, chun
     3 * max(len(a), len(b)) samples, which every record must exceed).  zi: `lfilter_zi(b, a)` when None.
     tiled: run `ecgvit_filtfilt_long` (the same kernel, records up to `MAX_LEN_TILED` samples, the same bits); `tile` is checked and ignored --
     the recurrence is walked by one lane per lead whatever the length, and runs in place without a scratch."""
-    from .hip import lib, check, ptr, stream
     b, a, zi, nt = _taps(b, a, zi)
     _check_tile(tiled, tile)
     entry = _ENTRY[tiled]
@@ -260,8 +259,8 @@ def lowpass_taps(records, b, a, zi=None, offsets=None, idxs=None, out=None, chun
     def stage(x, o, tab, first):
         ws = _workspace(tab, x.device, entry)
         for lo, cnt in launches(tab, entry):
-            check(getattr(lib(), entry['filtfilt'])(ptr(x), ptr(o), ptr(tab.src_off[lo:]), tab.stride, ptr(tab.raw_len[lo:]), cnt, C, tab.min_len,
-                                                    tab.max_len, _dp(b), _dp(a), _dp(zi), nt, ptr(ws), stream()), entry['filtfilt'])
+            getattr(run, entry['filtfilt'])(ptr(x), ptr(o), ptr(tab.src_off[lo:]), tab.stride, ptr(tab.raw_len[lo:]), cnt, C, tab.min_len,
+                                            tab.max_len, _dp(b), _dp(a), _dp(zi), nt, ptr(ws), stream())
     return _sweep(*_resolve(records, offsets, idxs, 3 * nt + 1, tiled), out, chunk_records, stage)
 
 
@@ -275,13 +274,12 @@ def lowpass(records, fqs=500, passband=50, stopband=60, passband_ripple=1, stopb
 
 def _sigma_of(x, tab, tiled=False):
     """the noise estimate over exactly the records of `tab` (a device store)"""
-    from .hip import lib, check, ptr, stream
     entry = _ENTRY[tiled]
     sig = torch.zeros((tab.R, C), dtype=torch.float64, device=x.device)
     ws = _workspace(tab, x.device, entry)
     for lo, cnt in launches(tab, entry):
-        check(getattr(lib(), entry['sigma'])(ptr(x), ptr(tab.src_off[lo:]), tab.stride, ptr(tab.raw_len[lo:]), cnt, C, tab.max_len, ptr(sig[lo:]),
-                                             ptr(ws), stream()), entry['sigma'])
+        getattr(run, entry['sigma'])(ptr(x), ptr(tab.src_off[lo:]), tab.stride, ptr(tab.raw_len[lo:]), cnt, C, tab.max_len, ptr(sig[lo:]),
+                                     ptr(ws), stream())
     return sig
 
 
@@ -313,7 +311,6 @@ def nlm(records, scale=1.5, search_width=None, patch_width=10, sigma=None, offse
     tiled: run `ecgvit_nlm_denoise_tiled` (records up to `MAX_LEN_TILED` samples; the bits of the resident kernel for every record it takes and
     every tile).  tile: the output samples a workgroup owns, a multiple of 15 (None: 7680); a record may need at most 65535 tiles.  In place the
     tiled kernel runs through a scratch (the module's docstring says what it costs)."""
-    from .hip import lib, check, ptr, stream
     _check_nlm(scale, search_width, patch_width)
     tile_runs = _check_tile(tiled, tile, NLM_RUN) // NLM_RUN
     tail = (float(scale), int(patch_width), 0 if search_width is None else int(search_width))
@@ -326,15 +323,15 @@ def nlm(records, scale=1.5, search_width=None, patch_width=10, sigma=None, offse
     def stage(x, o, tab, first):
         sig = _sigma_of(x, tab, tiled) if sigma is None else sigma[first:first + tab.R].to(x.device).contiguous()
         if not tiled:
-            return check(lib().ecgvit_nlm_denoise(ptr(x), ptr(o), ptr(tab.src_off), tab.stride, ptr(tab.raw_len), tab.R, C, tab.max_len, ptr(sig), *tail,
-                                                  stream()), 'ecgvit_nlm_denoise')
+            return run.ecgvit_nlm_denoise(ptr(x), ptr(o), ptr(tab.src_off), tab.stride, ptr(tab.raw_len), tab.R, C, tab.max_len, ptr(sig), *tail,
+                                          stream())
         runs = max(1, -(-(tab.max_len - 2 * int(patch_width) - 1) // NLM_RUN))
         if -(-runs // min(tile_runs or NLM_TILE // NLM_RUN, runs)) > _MAX_TILES:
             raise ValueError(f'tile = {tile}: a record of {tab.max_len} samples would need more than {_MAX_TILES} tiles')
 
         def launch(xs, os_, off, stride, lo, cnt):
-            check(lib().ecgvit_nlm_denoise_tiled(ptr(xs), ptr(os_), ptr(off), stride, ptr(tab.raw_len[lo:]), cnt, C, tab.max_len, ptr(sig[lo:]), *tail,
-                                                 tile_runs, stream()), 'ecgvit_nlm_denoise_tiled')
+            run.ecgvit_nlm_denoise_tiled(ptr(xs), ptr(os_), ptr(off), stride, ptr(tab.raw_len[lo:]), cnt, C, tab.max_len, ptr(sig[lo:]), *tail,
+                                         tile_runs, stream())
         _tiled_groups(x, o, tab, launch)
     records, s = _resolve(records, offsets, idxs, 1, tiled)
     if sigma is not None and sigma.shape[0] != s.R:
@@ -393,7 +390,6 @@ def rloess(records, npoints=500, degree=2, robust_iters=10, subtract=False, offs
     record it takes and every tile).  tile: the output samples a workgroup owns (None: 2048); the tile and two windows must fit 4096 samples of
     LDS.  In place the tiled kernel runs through a scratch (the module's docstring says what it costs).  The iteration table is one byte per
     sample and lead of the selection (5.6 MB per record of 462 600 samples); a host store moves it to the host chunk by chunk."""
-    from .hip import lib, check, ptr, stream
     npoints, frac = _check_rloess_args(npoints, degree, robust_iters)
     records, s = _resolve(records, offsets, idxs, degree + 2, tiled, unique=(True, True))
     tile = _check_rloess_windows(s, npoints, frac, degree, tiled, tile)
@@ -405,12 +401,12 @@ def rloess(records, npoints=500, degree=2, robust_iters=10, subtract=False, offs
         it = torch.zeros((tab.R, C, tab.max_len), dtype=torch.int8, device=x.device) if return_iters else None
         if tiled:
             def launch(xs, os_, off, stride, lo, cnt):
-                check(lib().ecgvit_rloess_tiled(ptr(xs), ptr(os_), ptr(off), stride, ptr(tab.raw_len[lo:]), cnt, C, tab.min_len, tab.max_len, *tail,
-                                                ptr(it[lo:]) if it is not None else None, tile, stream()), 'ecgvit_rloess_tiled')
+                run.ecgvit_rloess_tiled(ptr(xs), ptr(os_), ptr(off), stride, ptr(tab.raw_len[lo:]), cnt, C, tab.min_len, tab.max_len, *tail,
+                                        ptr(it[lo:]) if it is not None else None, tile, stream())
             _tiled_groups(x, o, tab, launch)
         else:
-            check(lib().ecgvit_rloess(ptr(x), ptr(o), ptr(tab.src_off), tab.stride, ptr(tab.raw_len), tab.R, C, tab.min_len, tab.max_len, *tail,
-                                      ptr(it), stream()), 'ecgvit_rloess')
+            run.ecgvit_rloess(ptr(x), ptr(o), ptr(tab.src_off), tab.stride, ptr(tab.raw_len), tab.R, C, tab.min_len, tab.max_len, *tail,
+                              ptr(it), stream())
         if it is not None:
             it = it if tab.max_len == s.max_len else torch.nn.functional.pad(it, (0, s.max_len - tab.max_len))
             tables.append(it if on_device or not tiled else it.cpu())

@@ -460,8 +460,8 @@ class EcgVit(nn.Module):
         (the fused optimiser writes it itself and bumps nothing)."""
         ver = sum(p._version for p in self._param_list) + self._pflat._version
         if force or ver != self._wlow_version:
-            hip.check(hip.lib().ecgvit_cast_f32_to_bf16(self._pflat.data_ptr(), self._wlow.data_ptr(), self._layout.total,
-                                                        hip.stream()), 'cast_f32_to_bf16')
+            hip.run.ecgvit_cast_f32_to_bf16(self._pflat.data_ptr(), self._wlow.data_ptr(), self._layout.total,
+                                            hip.stream())
             self.refresh_transposed_weights()
             self._wlow_version = ver
 
@@ -477,8 +477,8 @@ class EcgVit(nn.Module):
                     self._tr_sub = (key,) + self._eng.transposed_weight_table(self._pflat.device, only=key)
                 table, nmat, tiles = self._tr_sub[1:]
             if nmat:
-                hip.check(hip.lib().ecgvit_transpose_bf16_batched(self._wlow.data_ptr(), self._wlow_t.data_ptr(), table.data_ptr(),
-                                                                  nmat, tiles, hip.stream()), 'transpose_bf16_batched')
+                hip.run.ecgvit_transpose_bf16_batched(self._wlow.data_ptr(), self._wlow_t.data_ptr(), table.data_ptr(),
+                                                      nmat, tiles, hip.stream())
         if self._eng is not None and getattr(self._eng, 'fp8', False):
             self._eng.refresh_fp8_weights(only)
 
@@ -502,8 +502,8 @@ class EcgVit(nn.Module):
         eng._set_width(x.shape[2])
         eng._alloc(B)
         a = eng.act
-        hip.check(hip.lib().ecgvit_patch_gather(x.data_ptr(), a['patches'].data_ptr(), B, eng.C, eng.L, eng.P, eng.CP,
-                                                hip.code(eng.dtype), hip.stream()), 'patch_gather')
+        hip.run.ecgvit_patch_gather(x.data_ptr(), a['patches'].data_ptr(), B, eng.C, eng.L, eng.P, eng.CP,
+                                    hip.code(eng.dtype), hip.stream())
         hip.gemm(hip.GEMM_NT, a['patches'], eng.W['vit.to_patch_embedding.1.weight'], a['tok'], B * eng.n, eng.d, eng.CP,
                  eng.CP, eng.CP, eng.d, epilogue=hip.EPI_BIAS, bias=eng.P32['vit.to_patch_embedding.1.bias'])
         return a['tok'].float().view(B, eng.n, eng.d).clone()

@@ -15,7 +15,7 @@ import os
 import torch
 
 from . import hip
-from .hip import lib, check, ptr, stream, GEMM_NT, GEMM_NN, GEMM_TN
+from .hip import lib, run, ptr, stream, GEMM_NT, GEMM_NN, GEMM_TN
 from .hip import EPI_BIAS, EPI_GELU, EPI_GELU_BWD, EPI_RESIDUAL, EPI_DROPOUT, EPI_COLSUM, EPI_GELU_GRAD_AUX, EPI_MUL_AUX
 
 LN_EPS = 1e-5  # nn.LayerNorm default, used by vit_pytorch PreNorm / mlp_head
@@ -474,15 +474,15 @@ class VitEngine:
         if d % 8 or f % 8 or self.CP % 8 or self.dh % 8:
             raise ValueError(f'HIP path needs hidden_size, intermediate_size, head dim and C*P to be multiples of 8 '
                              f'(got d={d}, f={f}, dh={self.dh}, C*P={self.CP})')
-        if d > 2048:
-            raise ValueError('HIP LayerNorm kernels cover hidden_size <= 2048')
+        if d > hip.ROW_MAX_D:
+            raise ValueError(f'HIP LayerNorm kernels cover hidden_size <= {hip.ROW_MAX_D}')
         if h == 1:
             raise NotImplementedError('heads == 1 (vit_pytorch drops to_out) is not covered by the HIP path')
         if dtype == torch.bfloat16:
             if self.dh not in (64, 128):
                 raise ValueError(f'bf16 fused attention needs head dim 64 or 128 (got {self.dh}); use dtype=torch.float32')
-            if self.N > 2048:
-                raise ValueError(f'bf16 fused attention covers <= 2048 tokens (got {self.N}); use dtype=torch.float32')
+            if self.N > hip.ATTN_MAX_N:
+                raise ValueError(f'bf16 fused attention covers <= {hip.ATTN_MAX_N} tokens (got {self.N}); use dtype=torch.float32')
             for nm, pv in (('hidden_dropout_prob', self.p_hidden), ('attention_probs_dropout_prob (the embedding dropout: reference ecg_vit.py:113)', self.p_emb)):
                 if 0.0 < pv < 1.0 / 512:
                     # every dropout site of the bf16 path draws 8 random bits per element: p is applied as round(256 p) / 256 (0.1 -> 0.1016)
@@ -585,7 +585,7 @@ class VitEngine:
         """e4m3 shadows of the block Linears' weights and of their transposes, one scale per matrix from its current amax: three
         launches over the flat bf16 shadows (call after the optimiser rewrote them).  only: the names that changed (None = all): the
         launches then cover each run of consecutive rows of the matrix table that holds only changed matrices"""
-        l, st = lib(), stream()
+        st = stream()
         nm = len(self.w8_index)
         runs = [(0, nm)]
         if only is not None:
@@ -598,11 +598,10 @@ class VitEngine:
                     r0 = None
         for r0, r1 in runs:
             tab, sc, am = self.w8_table[r0:r1], self.w8_scale[r0:r1], self.w8_amax[r0:r1]
-            check(l.ecgvit_fp8_amax(ptr(self._wlow), ptr(tab), r1 - r0, self.w8_count, ptr(am), st), 'fp8_amax')
-            check(l.ecgvit_fp8_scale_update(ptr(sc), ptr(am), r1 - r0, None, hip.FP8_E4M3, st), 'fp8_scale_update')
+            run.ecgvit_fp8_amax(ptr(self._wlow), ptr(tab), r1 - r0, self.w8_count, ptr(am), st)
+            run.ecgvit_fp8_scale_update(ptr(sc), ptr(am), r1 - r0, None, hip.FP8_E4M3, st)
             for src, dst in ((self._wlow, self.w8), (self._wlow_t, self.w8t)):
-                check(l.ecgvit_fp8_quantize(ptr(src), ptr(dst), ptr(tab), r1 - r0, self.w8_count, hip.FP8_E4M3, ptr(sc), None, st),
-                      'fp8_quantize')
+                run.ecgvit_fp8_quantize(ptr(src), ptr(dst), ptr(tab), r1 - r0, self.w8_count, hip.FP8_E4M3, ptr(sc), None, st)
 
     def fp8_begin_step(self, training=True):
         """delayed scaling: the scales of this pass come from the amax the previous pass's quantise kernels accumulated.
@@ -617,8 +616,7 @@ class VitEngine:
                 self.f8_scale.copy_(torch.where(self._f8_scale_train > 0, self._f8_scale_train, self.f8_scale))
                 self.f8_amax.zero_()
             else:
-                check(lib().ecgvit_fp8_scale_update(ptr(self.f8_scale), ptr(self.f8_amax), self.f8_scale.numel(), ptr(self.f8_fmt), 0, stream()),
-                      'fp8_scale_update')
+                run.ecgvit_fp8_scale_update(ptr(self.f8_scale), ptr(self.f8_amax), self.f8_scale.numel(), ptr(self.f8_fmt), 0, stream())
                 if not training and self._f8_last_training:
                     self._f8_scale_train = self.f8_scale.clone()   # train -> eval: what the last training pass's amax gave (8 floats per layer)
         self._f8_last_training = bool(training)
@@ -626,15 +624,15 @@ class VitEngine:
     def _quant(self, site, x, count, out=None):
         """x (bf16, `count` elements) -> `out` (a layer's persistent e4m3 copy: the weight-gradient product reads it again in the
         backward pass) or the shared 8-bit scratch, in the site's format; returns (8-bit view, scale pointer tensor)"""
-        l, st = lib(), stream()
+        st = stream()
         sc, am = self.f8_scale[site:site + 1], self.f8_amax[site:site + 1]
         fmt = hip.FP8_E4M3 if site % 8 < 4 else hip.BF8_E5M2
         if site not in self._f8_seen:   # first use: no history yet -> scale from this tensor's own amax (one extra read)
-            check(l.ecgvit_fp8_amax(ptr(x), None, 1, count, ptr(am), st), 'fp8_amax')
-            check(l.ecgvit_fp8_scale_update(ptr(sc), ptr(am), 1, None, fmt, st), 'fp8_scale_update')
+            run.ecgvit_fp8_amax(ptr(x), None, 1, count, ptr(am), st)
+            run.ecgvit_fp8_scale_update(ptr(sc), ptr(am), 1, None, fmt, st)
             self._f8_seen.add(site)
         q = out if out is not None else self.act['q8'][:count]
-        check(l.ecgvit_fp8_quantize(ptr(x), ptr(q), None, 1, count, fmt, ptr(sc), ptr(am), st), 'fp8_quantize')
+        run.ecgvit_fp8_quantize(ptr(x), ptr(q), None, 1, count, fmt, ptr(sc), ptr(am), st)
         return q, sc
 
     def _emit8(self, kw, site, ld, out=None, only8=False):
@@ -850,18 +848,17 @@ class VitEngine:
         if (self.fp8 and q8_site is not None and q8_site in self._f8_seen and rows >= 2048 and d % 256 == 0
                 and d // 64 in (4, 8, 12, 16, 24, 32)):
             # (y has 8-bit readers only when it has a persistent 8-bit copy for the weight gradient: see fp8_drop_dead_bf16)
-            check(lib().ecgvit_layernorm_fwd_q8(ptr(x), ptr(g), ptr(b), None if (y8 is not None and self._only8(rows)) else ptr(y), ptr(mean), ptr(rstd), rows, d, LN_EPS,
-                                                ptr(y8 if y8 is not None else self.act['q8']),
-                                                ptr(self.f8_scale[q8_site:q8_site + 1]), ptr(self.f8_amax[q8_site:q8_site + 1]), stream()),
-                  'layernorm_fwd_q8')
+            run.ecgvit_layernorm_fwd_q8(ptr(x), ptr(g), ptr(b), None if (y8 is not None and self._only8(rows)) else ptr(y), ptr(mean), ptr(rstd), rows, d, LN_EPS,
+                                        ptr(y8 if y8 is not None else self.act['q8']),
+                                        ptr(self.f8_scale[q8_site:q8_site + 1]), ptr(self.f8_amax[q8_site:q8_site + 1]), stream())
             return True
-        check(lib().ecgvit_layernorm_fwd(ptr(x), ptr(g), ptr(b), ptr(y), ptr(mean), ptr(rstd), rows, d, LN_EPS,
-                                         hip.code(self.dtype), stream()), 'layernorm_fwd')
+        run.ecgvit_layernorm_fwd(ptr(x), ptr(g), ptr(b), ptr(y), ptr(mean), ptr(rstd), rows, d, LN_EPS,
+                                 hip.code(self.dtype), stream())
         return False
 
     def _ln_bwd(self, dy, x, g, mean, rstd, dres, dx, dg, db, rows):
-        check(lib().ecgvit_layernorm_bwd(ptr(dy), ptr(x), ptr(g), ptr(mean), ptr(rstd), ptr(dres), ptr(dx), ptr(dg), ptr(db),
-                                         ptr(self.act['ws']), rows, self.d, hip.code(self.dtype), stream()), 'layernorm_bwd')
+        run.ecgvit_layernorm_bwd(ptr(dy), ptr(x), ptr(g), ptr(mean), ptr(rstd), ptr(dres), ptr(dx), ptr(dg), ptr(db),
+                                 ptr(self.act['ws']), rows, self.d, hip.code(self.dtype), stream())
 
     def _ln_bwd_fused(self, dy, x, g, mean, rstd, dres, dx, dg, db, rows, dxm, dcolsum, p, seed, q8_site=None):
         """LayerNorm backward that also emits, for the NEXT stage, the dropout-masked copy of dx and its column sums; q8_site
@@ -870,21 +867,20 @@ class VitEngine:
         d = self.d
         if (self.fp8 and q8_site is not None and q8_site in self._f8_seen and rows >= 2048 and d // 64 in (4, 8, 12, 16, 24, 32) and d % 64 == 0
                 and rows * d < 2 ** 31):
-            check(lib().ecgvit_layernorm_bwd_fused_q8(ptr(dy), ptr(x), ptr(g), ptr(mean), ptr(rstd), ptr(dres), ptr(dx), ptr(dg), ptr(db),
-                                                      ptr(self.act['ws']), rows, d, None if self._only8(rows) else ptr(dxm), ptr(dcolsum), p, seed, ptr(self.act['q8']),
-                                                      ptr(self.f8_scale[q8_site:q8_site + 1]), ptr(self.f8_amax[q8_site:q8_site + 1]), stream()),
-                  'layernorm_bwd_fused_q8')
+            run.ecgvit_layernorm_bwd_fused_q8(ptr(dy), ptr(x), ptr(g), ptr(mean), ptr(rstd), ptr(dres), ptr(dx), ptr(dg), ptr(db),
+                                              ptr(self.act['ws']), rows, d, None if self._only8(rows) else ptr(dxm), ptr(dcolsum), p, seed, ptr(self.act['q8']),
+                                              ptr(self.f8_scale[q8_site:q8_site + 1]), ptr(self.f8_amax[q8_site:q8_site + 1]), stream())
             return True
-        check(lib().ecgvit_layernorm_bwd_fused(ptr(dy), ptr(x), ptr(g), ptr(mean), ptr(rstd), ptr(dres), ptr(dx), ptr(dg), ptr(db),
-                                               ptr(self.act['ws']), rows, self.d, ptr(dxm), ptr(dcolsum), p, seed,
-                                               hip.code(self.dtype), stream()), 'layernorm_bwd_fused')
+        run.ecgvit_layernorm_bwd_fused(ptr(dy), ptr(x), ptr(g), ptr(mean), ptr(rstd), ptr(dres), ptr(dx), ptr(dg), ptr(db),
+                                       ptr(self.act['ws']), rows, self.d, ptr(dxm), ptr(dcolsum), p, seed,
+                                       hip.code(self.dtype), stream())
         return False
 
     def _colsum(self, x, ld, out, M, N):
-        check(lib().ecgvit_colsum(ptr(x), ld, ptr(out), ptr(self.act['ws']), M, N, hip.code(self.dtype), stream()), 'colsum')
+        run.ecgvit_colsum(ptr(x), ld, ptr(out), ptr(self.act['ws']), M, N, hip.code(self.dtype), stream())
 
     def _drop_apply(self, src, dst, count, p, seed):
-        check(lib().ecgvit_dropout_apply(ptr(src), ptr(dst), count, p, seed, hip.code(self.dtype), stream()), 'dropout_apply')
+        run.ecgvit_dropout_apply(ptr(src), ptr(dst), count, p, seed, hip.code(self.dtype), stream())
 
     def _wgrad(self, dY, X, name, Mout, Nin, rows, pre=None, x8=None, xsite=None):
         """dW[Mout, Nin] = dY[rows, Mout]^T . X[rows, Nin]  -> f32 gradient view (overwritten).  fp8_linear: pre = (e5m2 copy of dY,
@@ -916,17 +912,16 @@ class VitEngine:
             if xf.timeout and sv['training']:
                 t0, tl = xf.draw_timeout(B, self.L, x.device)
             self._xf_keep = (mean, inv_std, t0, tl)   # keep the int32 spans alive until the kernel has run
-            check(lib().ecgvit_patch_gather_transform(ptr(x), ptr(a['patches']), B, self.C, x.shape[2], self.L, self.P, self.CP, ptr(mean),
-                                                      ptr(inv_std), ptr(t0), ptr(tl), T, stream()), 'patch_gather_transform')
+            run.ecgvit_patch_gather_transform(ptr(x), ptr(a['patches']), B, self.C, x.shape[2], self.L, self.P, self.CP, ptr(mean),
+                                              ptr(inv_std), ptr(t0), ptr(tl), T, stream())
         elif rg is not None:   # packed rows: the uniform gather over the concatenation (patch row off_b / P + j is patch j of record b)
-            check(lib().ecgvit_patch_gather(ptr(x), ptr(a['patches']), 1, self.C, rg.S, self.P, self.CP, T, stream()), 'patch_gather')
+            run.ecgvit_patch_gather(ptr(x), ptr(a['patches']), 1, self.C, rg.S, self.P, self.CP, T, stream())
         elif ntok is not None:   # zero patches past each record's length.  The kernel's count includes a CLS token: the masked padded
             # form, whose ntok = n_b counts patches only, passes n_cls = n_b + 1
             cnt = ntok if geo is None else geo.n_cls
-            check(lib().ecgvit_patch_gather_varlen(ptr(x), ptr(a['patches']), ptr(cnt), B, self.C, self.L, self.P, self.CP, T, stream()),
-                  'patch_gather_varlen')
+            run.ecgvit_patch_gather_varlen(ptr(x), ptr(a['patches']), ptr(cnt), B, self.C, self.L, self.P, self.CP, T, stream())
         else:
-            check(lib().ecgvit_patch_gather(ptr(x), ptr(a['patches']), B, self.C, self.L, self.P, self.CP, T, stream()), 'patch_gather')
+            run.ecgvit_patch_gather(ptr(x), ptr(a['patches']), B, self.C, self.L, self.P, self.CP, T, stream())
         rows = self._pass_rows(B) - (0 if sv['masked'] else B)   # (no CLS rows among the patch rows)
         self._gemm(GEMM_NT, a['patches'], self.W['vit.to_patch_embedding.1.weight'], a['tok'], rows, self.d, self.CP, self.CP, self.CP, self.d,
                    epilogue=EPI_BIAS, bias=self.P32['vit.to_patch_embedding.1.bias'])
@@ -943,10 +938,9 @@ class VitEngine:
             span = _stage(xf.draw_timeout_records(rs.padded), x.device)
             t0, tl = span[0], span[1]
         self._xf_keep = (mean, inv_std, t0, tl, rs)   # keep the tables alive until the kernel has run
-        check(lib().ecgvit_patch_gather_transform_varlen(ptr(x), ptr(self.act['patches']), ptr(rs.src_off), rs.lead_stride, ptr(rs.raw_len),
-                                                         ptr(rs.n_patch), ptr(rs.row_off), rs.nrows, rs.n_max, rs.B, self.C, self.P, self.CP,
-                                                         ptr(mean), ptr(inv_std), ptr(t0), ptr(tl), hip.code(self.dtype), stream()),
-              'patch_gather_transform_varlen')
+        run.ecgvit_patch_gather_transform_varlen(ptr(x), ptr(self.act['patches']), ptr(rs.src_off), rs.lead_stride, ptr(rs.raw_len),
+                                                 ptr(rs.n_patch), ptr(rs.row_off), rs.nrows, rs.n_max, rs.B, self.C, self.P, self.CP,
+                                                 ptr(mean), ptr(inv_std), ptr(t0), ptr(tl), hip.code(self.dtype), stream())
 
     def check_raw_input(self, x, lengths):
         """validate a padded (B, C, W) batch of RAW records for this engine's per-record input transform before anything launches ->
@@ -1008,74 +1002,72 @@ class VitEngine:
     def _attention_fwd(self, L, i, B, ph, seed):
         """a7: softmax(q k^T * scale) v of block i, qkv -> attn, on the kernel the current pass calls for.  Returns True when the kernel also
         wrote the e4m3 copy of its output (fp8_linear, once site 8 i + 1 has a scale)"""
-        sv, l, st = self.saved, lib(), stream()
+        sv, st = self.saved, stream()
         h, dh, N = self.h, self.dh, self.T
         rg, ntok = sv.get('ragged'), sv.get('ntok')
         site = 8 * i + 1
         if rg is not None:
-            check(l.ecgvit_attention_ragged_fwd(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), ptr(rg.n_tok), ptr(rg.tok_off), B, N, h, dh, self.scale,
-                                                ph, seed, st), 'attention_ragged_fwd')
+            run.ecgvit_attention_ragged_fwd(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), ptr(rg.n_tok), ptr(rg.tok_off), B, N, h, dh, self.scale,
+                                            ph, seed, st)
         elif self.dtype == torch.bfloat16 and ntok is not None:
-            check(l.ecgvit_attention_varlen_fwd(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), ptr(ntok), B, N, h, dh, self.scale, ph, seed, st),
-                  'attention_varlen_fwd')
+            run.ecgvit_attention_varlen_fwd(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), ptr(ntok), B, N, h, dh, self.scale, ph, seed, st)
         elif self.dtype == torch.bfloat16:
             if self.fp8 and self._pass_rows(B) >= 2048 and site in self._f8_seen and dh == 64:   # (dh = 128: no 8-bit emission, _linear quantises attn)
-                check(l.ecgvit_attention_fwd_q8(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), B, N, h, dh, self.scale, ph, seed, ptr(L['attn_8']),
-                                                ptr(self.f8_scale[site:site + 1]), ptr(self.f8_amax[site:site + 1]), st), 'attention_fwd_q8')
+                run.ecgvit_attention_fwd_q8(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), B, N, h, dh, self.scale, ph, seed, ptr(L['attn_8']),
+                                            ptr(self.f8_scale[site:site + 1]), ptr(self.f8_amax[site:site + 1]), st)
                 return True
-            check(l.ecgvit_attention_fwd(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), B, N, h, dh, self.scale, ph, seed, hip.BF16, st), 'attention_fwd')
+            run.ecgvit_attention_fwd(ptr(L['qkv']), ptr(L['attn']), ptr(L['lse']), B, N, h, dh, self.scale, ph, seed, hip.BF16, st)
         else:
             self._attn_fwd_f32(L, B, ph, seed)
         return False
 
     def _attention_bwd(self, L, i, B, ph, seed):
         """backward of `_attention_fwd`: dattn -> dqkv.  Returns True when the kernel also wrote the e5m2 copy of dqkv (operand scratch)"""
-        a, sv, l, st = self.act, self.saved, lib(), stream()
+        a, sv, st = self.act, self.saved, stream()
         d, h, dh, N = self.d, self.h, self.dh, self.T
         rg, ntok = sv.get('ragged'), sv.get('ntok')
         site = 8 * i + 7
         if rg is not None:
-            check(l.ecgvit_attention_ragged_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), ptr(rg.n_tok),
-                                                ptr(rg.tok_off), B, N, h, dh, self.scale, ph, seed, st), 'attention_ragged_bwd')
+            run.ecgvit_attention_ragged_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), ptr(rg.n_tok),
+                                            ptr(rg.tok_off), B, N, h, dh, self.scale, ph, seed, st)
         elif self.dtype == torch.bfloat16 and ntok is not None:
-            check(l.ecgvit_attention_varlen_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), ptr(ntok), B, N, h,
-                                                dh, self.scale, ph, seed, st), 'attention_varlen_bwd')
+            run.ecgvit_attention_varlen_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), ptr(ntok), B, N, h,
+                                            dh, self.scale, ph, seed, st)
         elif self.dtype == torch.bfloat16:
             if (self.fp8 and self._pass_rows(B) >= 2048 and site in self._f8_seen and dh == 64 and 128 < N <= 512
                     and N * 3 * d * 2 < 2 ** 31):   # (dh = 128: _grad8 quantises dqkv)
-                check(l.ecgvit_attention_bwd_q8(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), B, N, h, dh, self.scale,
-                                                ph, seed, ptr(a['q8']), ptr(self.f8_scale[site:site + 1]), ptr(self.f8_amax[site:site + 1]), st),
-                      'attention_bwd_q8')
+                run.ecgvit_attention_bwd_q8(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), B, N, h, dh, self.scale,
+                                            ph, seed, ptr(a['q8']), ptr(self.f8_scale[site:site + 1]), ptr(self.f8_amax[site:site + 1]), st)
                 return True
-            check(l.ecgvit_attention_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), B, N, h, dh, self.scale, ph,
-                                         seed, hip.BF16, st), 'attention_bwd')
+            run.ecgvit_attention_bwd(ptr(L['qkv']), ptr(L['attn']), ptr(a['dattn']), ptr(L['lse']), ptr(a['dqkv']), B, N, h, dh, self.scale, ph,
+                                     seed, hip.BF16, st)
         else:
             self._attn_bwd_f32(L, B, ph, seed)
         return False
 
     def _attention_cls_fwd(self, L, B, ph, seed):
         """the CLS query of every record against all its keys (the pruned last block): qkv -> act['cls_attn'], act['cls_lse']"""
-        a, l, st = self.act, lib(), stream()
+        a, st = self.act, stream()
         h, dh, N = self.h, self.dh, self.T
         ntok = self.saved.get('ntok')
         if ntok is not None:
-            check(l.ecgvit_attention_varlen_cls_fwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_lse']), ptr(ntok), B, N, h, dh, self.scale, ph, seed,
-                                                    st), 'attention_varlen_cls_fwd')
+            run.ecgvit_attention_varlen_cls_fwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_lse']), ptr(ntok), B, N, h, dh, self.scale, ph, seed,
+                                                st)
         else:
-            check(l.ecgvit_attention_cls_fwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_lse']), B, N, h, dh, self.scale, ph, seed,
-                                             hip.code(self.dtype), st), 'attention_cls_fwd')
+            run.ecgvit_attention_cls_fwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_lse']), B, N, h, dh, self.scale, ph, seed,
+                                         hip.code(self.dtype), st)
 
     def _attention_cls_bwd(self, L, B, ph, seed):
         """backward of `_attention_cls_fwd`: act['cls_dattn'] -> dK / dV of every row in act['dqkv'], the compact dQ in act['cls_dq']"""
-        a, l, st = self.act, lib(), stream()
+        a, st = self.act, stream()
         h, dh, N = self.h, self.dh, self.T
         ntok = self.saved.get('ntok')
         if ntok is not None:
-            check(l.ecgvit_attention_varlen_cls_bwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_dattn']), ptr(a['cls_lse']), ptr(a['dqkv']),
-                                                    ptr(a['cls_dq']), ptr(ntok), B, N, h, dh, self.scale, ph, seed, st), 'attention_varlen_cls_bwd')
+            run.ecgvit_attention_varlen_cls_bwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_dattn']), ptr(a['cls_lse']), ptr(a['dqkv']),
+                                                ptr(a['cls_dq']), ptr(ntok), B, N, h, dh, self.scale, ph, seed, st)
         else:
-            check(l.ecgvit_attention_cls_bwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_dattn']), ptr(a['cls_lse']), ptr(a['dqkv']), ptr(a['cls_dq']),
-                                             B, N, h, dh, self.scale, ph, seed, hip.code(self.dtype), st), 'attention_cls_bwd')
+            run.ecgvit_attention_cls_bwd(ptr(L['qkv']), ptr(a['cls_attn']), ptr(a['cls_dattn']), ptr(a['cls_lse']), ptr(a['dqkv']), ptr(a['cls_dq']),
+                                         B, N, h, dh, self.scale, ph, seed, hip.code(self.dtype), st)
 
     def _cls_block_fwd(self, L, X, B, ph, s0, lp):
         """the last block when only its CLS rows are consumed (the classifier reads x[:, 0]): LayerNorm 1 and the K / V columns of to_qkv
@@ -1115,20 +1107,20 @@ class VitEngine:
         record at pitch saved['head_pitch']: N in the padded layout; 1 when X holds the CLS rows only (cls_only_last) or after gathering
         the CLS rows tok_off[b] of a ragged batch compact.  Returns (logits, loss_elem | None, loss_mean | None)"""
         a, sv, T = self.act, self.saved, hip.code(self.dtype)
-        l, st = lib(), stream()
+        st = stream()
         B, d, rg, labels = sv['B'], self.d, sv['ragged'], sv['labels']
         pre = 'vit.'
         sv['head_pitch'] = 1 if (sv['cls_only_last'] or rg is not None) else self.N
         if rg is not None:
-            check(l.ecgvit_gather_rows(ptr(X), ptr(rg.tok_off), ptr(a['cls_x2']), 1, rg.M, B, d, d, d, T, st), 'gather_rows')
+            run.ecgvit_gather_rows(ptr(X), ptr(rg.tok_off), ptr(a['cls_x2']), 1, rg.M, B, d, d, d, T, st)
             X = a['cls_x2']
-        check(l.ecgvit_head_fwd(ptr(X), sv['head_pitch'], ptr(self.P32[pre + 'mlp_head.0.weight']), ptr(self.P32[pre + 'mlp_head.0.bias']),
-                                ptr(self.P32[pre + 'mlp_head.1.weight']), ptr(self.P32[pre + 'mlp_head.1.bias']),
-                                ptr(a['logits']), ptr(a['xhat']), ptr(a['hrstd']), B, d, self.K, LN_EPS, T, st), 'head_fwd')
+        run.ecgvit_head_fwd(ptr(X), sv['head_pitch'], ptr(self.P32[pre + 'mlp_head.0.weight']), ptr(self.P32[pre + 'mlp_head.0.bias']),
+                            ptr(self.P32[pre + 'mlp_head.1.weight']), ptr(self.P32[pre + 'mlp_head.1.bias']),
+                            ptr(a['logits']), ptr(a['xhat']), ptr(a['hrstd']), B, d, self.K, LN_EPS, T, st)
         if labels is None:
             return a['logits'], None, None
-        check(l.ecgvit_bce_fwd(ptr(a['logits']), ptr(labels), ptr(sv['weight']), ptr(a['loss_elem']),
-                               ptr(a['loss_mean']) if want_mean else None, B * self.K, st), 'bce_fwd')
+        run.ecgvit_bce_fwd(ptr(a['logits']), ptr(labels), ptr(sv['weight']), ptr(a['loss_elem']),
+                           ptr(a['loss_mean']) if want_mean else None, B * self.K, st)
         return a['logits'], a['loss_elem'], (a['loss_mean'] if want_mean else None)
 
     def _trunk_pass(self, x, labels, weight, training, seed, cls_only_last, lengths):
@@ -1179,7 +1171,7 @@ class VitEngine:
         RaggedBatch of packed rows; ntok: per-record token counts of padded rows; raw: the `RawSide` of raw records"""
         self._alloc(B, rows=None if ragged is None else ragged.M)
         a, T = self.act, hip.code(self.dtype)
-        l, st = lib(), stream()
+        st = stream()
         ph = self.p_hidden if training else 0.0
         pe = self.p_emb if training else 0.0
         self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, labels=labels, weight=weight, masked=False, training=training, cls_only_last=cls_only_last,
@@ -1194,10 +1186,10 @@ class VitEngine:
         # a5: cat CLS, += pos_embedding[:, :n+1], emb dropout
         cls, pos = self.P32['vit.cls_token'], self.P32['vit.pos_embedding']
         if ragged is not None:
-            check(l.ecgvit_embed_finish_ragged(ptr(a['tok']), ptr(cls), ptr(pos), ptr(a['x0']), ptr(ragged.n_tok), ptr(ragged.tok_off), B, self.N,
-                                               self.d, pe, seed + 1, T, st), 'embed_finish_ragged')
+            run.ecgvit_embed_finish_ragged(ptr(a['tok']), ptr(cls), ptr(pos), ptr(a['x0']), ptr(ragged.n_tok), ptr(ragged.tok_off), B, self.N,
+                                           self.d, pe, seed + 1, T, st)
         else:
-            check(l.ecgvit_embed_finish(ptr(a['tok']), ptr(cls), ptr(pos), ptr(a['x0']), B, self.n, self.d, pe, seed + 1, T, st), 'embed_finish')
+            run.ecgvit_embed_finish(ptr(a['tok']), ptr(cls), ptr(pos), ptr(a['x0']), B, self.n, self.d, pe, seed + 1, T, st)
         X = self._trunk_fwd(B, ph, seed, cls_only_last)
         self.saved['xL'] = X
         return X
@@ -1265,8 +1257,8 @@ class VitEngine:
         B, pre = sv['B'], 'vit.'
         out = torch.empty((B, self.d), dtype=torch.float32, device=sv['xL'].device)
         g, b = (self.P32[pre + 'mlp_head.0.weight'], self.P32[pre + 'mlp_head.0.bias']) if norm else (None, None)
-        check(lib().ecgvit_pool_records(ptr(sv['xL']), ptr(out), ptr(n_tok), ptr(tok_off), B, N, self.d, self.POOL_MODES[pool], ptr(g), ptr(b),
-                                        LN_EPS, hip.code(self.dtype), stream()), 'pool_records')
+        run.ecgvit_pool_records(ptr(sv['xL']), ptr(out), ptr(n_tok), ptr(tok_off), B, N, self.d, self.POOL_MODES[pool], ptr(g), ptr(b),
+                                LN_EPS, hip.code(self.dtype), stream())
         return out
 
     @staticmethod
@@ -1295,8 +1287,8 @@ class VitEngine:
         if self.fp8:
             self.fp8_begin_step(training)
         self._patch_rows(x)
-        check(lib().ecgvit_mask_embed_finish(ptr(a['tok']), ptr(self.P32['pretrain.mask_token']), ptr(self.P32['vit.pos_embedding']),
-                                             ptr(idx), ptr(a['x0']), ptr(a['flag']), B, n, m, d, hip.code(self.dtype), stream()), 'mask_embed_finish')
+        run.ecgvit_mask_embed_finish(ptr(a['tok']), ptr(self.P32['pretrain.mask_token']), ptr(self.P32['vit.pos_embedding']),
+                                     ptr(idx), ptr(a['x0']), ptr(a['flag']), B, n, m, d, hip.code(self.dtype), stream())
         return self._masked_trunk_and_loss()
 
     def _masked_trunk_and_loss(self):
@@ -1304,20 +1296,19 @@ class VitEngine:
         raw patches.  saved['mrows'] = (batches, rows per batch, indices per batch) is how saved['idx'] addresses the masked rows: (B, n, m)
         for (B, m) record-local indices, (1, M, sum m_b) for row numbers of the whole pass.  Returns (pred, loss (1,))"""
         a, sv, T = self.act, self.saved, hip.code(self.dtype)
-        l, st = lib(), stream()
+        st = stream()
         B, pe, seed, idx, d, CP = sv['B'], sv['pe'], sv['seed'], sv['idx'], self.d, self.CP
         nb, nrow, m = sv['mrows']
         if pe > 0:
             self._drop_apply(a['x0'], a['x0'], self._pass_rows(B) * d, pe, seed + 1)
         X = self._trunk_fwd(B, sv['ph'], seed)
         sv['xL'] = X
-        check(l.ecgvit_gather_rows(ptr(X), ptr(idx), ptr(a['rows']), nb, nrow, m, d, d, d, T, st), 'gather_rows')
+        run.ecgvit_gather_rows(ptr(X), ptr(idx), ptr(a['rows']), nb, nrow, m, d, d, d, T, st)
         self._gemm(GEMM_NT, a['rows'], self.W['pretrain.to_pixels.weight'], a['pred'], nb * m, CP, d, d, d, CP, epilogue=EPI_BIAS,
                    bias=self.P32['pretrain.to_pixels.bias'])
-        check(l.ecgvit_gather_rows(ptr(a['patches']), ptr(idx), ptr(a['target']), nb, nrow, m, CP, CP, CP, T, st), 'gather_rows')
+        run.ecgvit_gather_rows(ptr(a['patches']), ptr(idx), ptr(a['target']), nb, nrow, m, CP, CP, CP, T, st)
         # L1 loss and d(loss)/d(pred) in one pass (upstream gradient 1; backward_masked re-runs it for any other upstream)
-        check(l.ecgvit_l1_loss_fwd_bwd(ptr(a['pred']), ptr(a['target']), ptr(a['mloss']), ptr(a['dpred']), None, ptr(a['l1part']), nb * m, CP, CP, T, st),
-              'l1_loss')
+        run.ecgvit_l1_loss_fwd_bwd(ptr(a['pred']), ptr(a['target']), ptr(a['mloss']), ptr(a['dpred']), None, ptr(a['l1part']), nb * m, CP, CP, T, st)
         return a['pred'], a['mloss']
 
     def check_masked_varlen_input(self, x, mask_idx, lengths, mask_counts):
@@ -1340,9 +1331,9 @@ class VitEngine:
         self.saved = dict(B=B, ph=ph, pe=pe, seed=seed, masked=True, idx=geo.rows, m=mt, mrows=(1, M, mt), training=training, geo=geo, lengths=True,
                           ntok=None if packed else geo.n_tok, ragged=geo if packed else None, raw=geo.rawside)
         self._patch_rows(x)
-        check(lib().ecgvit_mask_embed_varlen_fwd(ptr(a['tok']), ptr(self.P32['pretrain.mask_token']), ptr(self.P32['vit.pos_embedding']), ptr(geo.rows),
-                                                 ptr(a['x0']), ptr(a['flag']), ptr(geo.n_tok), ptr(geo.tok_off), B, geo.N, geo.n_pad, M, mt, self.d,
-                                                 hip.code(self.dtype), stream()), 'mask_embed_varlen_fwd')
+        run.ecgvit_mask_embed_varlen_fwd(ptr(a['tok']), ptr(self.P32['pretrain.mask_token']), ptr(self.P32['vit.pos_embedding']), ptr(geo.rows),
+                                         ptr(a['x0']), ptr(a['flag']), ptr(geo.n_tok), ptr(geo.tok_off), B, geo.N, geo.n_pad, M, mt, self.d,
+                                         hip.code(self.dtype), stream())
         return self._masked_trunk_and_loss()
 
     def backward_masked(self, gscalar=None, tiles_per_workgroup=0, trainable=None):
@@ -1359,7 +1350,7 @@ class VitEngine:
 
     def _backward_masked(self, gscalar):
         a, W, T = self.act, self.W, hip.code(self.dtype)
-        l, st = lib(), stream()
+        st = stream()
         sv = self.saved
         B, idx, pe, seed = sv['B'], sv['idx'], sv['pe'], sv['seed']
         d, n = self.d, self.n
@@ -1368,8 +1359,8 @@ class VitEngine:
         nb, nrow, m = sv['mrows']   # how idx addresses the masked rows (`_masked_trunk_and_loss`)
         Rm = nb * m
         if gscalar is not None:
-            check(l.ecgvit_l1_loss_fwd_bwd(ptr(a['pred']), ptr(a['target']), ptr(a['mloss']), ptr(a['dpred']), ptr(gscalar), ptr(a['l1part']), Rm,
-                                           self.CP, self.CP, T, st), 'l1_loss')
+            run.ecgvit_l1_loss_fwd_bwd(ptr(a['pred']), ptr(a['target']), ptr(a['mloss']), ptr(a['dpred']), ptr(gscalar), ptr(a['l1part']), Rm,
+                                       self.CP, self.CP, T, st)
         # the classification head does not take part: its gradients are zero for this objective -- known at once, so its bucket is
         # released FIRST and its exchange overlaps the whole backward pass (buckets complete in the order head, layers L-1..0, embed,
         # pretrain, as in the supervised pass)
@@ -1383,7 +1374,7 @@ class VitEngine:
         self._gemm(GEMM_NN, a['dpred'], W['pretrain.to_pixels.weight'], a['drows'], Rm, d, self.CP, self.CP, d, d)
         dX = a['dxa']
         dX.zero_()
-        check(l.ecgvit_scatter_rows(ptr(a['drows']), ptr(idx), ptr(dX), nb, nrow, m, d, d, d, T, st), 'scatter_rows')
+        run.ecgvit_scatter_rows(ptr(a['drows']), ptr(idx), ptr(dX), nb, nrow, m, d, d, d, T, st)
         dX = self._trunk_bwd(dX, a['dxb'])
         if dX is None or not self._reach(self._stage(-1, 0)):
             return
@@ -1391,13 +1382,13 @@ class VitEngine:
             self._drop_apply(dX, dX, M * d, pe, seed + 1)
         geo = sv.get('geo')   # records of unequal length
         if geo is not None:
-            check(l.ecgvit_mask_embed_varlen_bwd(ptr(dX), ptr(a['flag']), ptr(a['dtok']), ptr(a['dmasked']), ptr(G['vit.pos_embedding']),
-                                                 ptr(geo.n_tok), ptr(geo.tok_off), ptr(geo.order), B, geo.N, geo.n_pad, d, T, st), 'mask_embed_varlen_bwd')
+            run.ecgvit_mask_embed_varlen_bwd(ptr(dX), ptr(a['flag']), ptr(a['dtok']), ptr(a['dmasked']), ptr(G['vit.pos_embedding']),
+                                             ptr(geo.n_tok), ptr(geo.tok_off), ptr(geo.order), B, geo.N, geo.n_pad, d, T, st)
             if n < self.n_max:   # the kernel wrote position rows 0 .. n (n = the pass's patches per record); the rest take no part
                 G['vit.pos_embedding'].view(-1, d)[1 + n:].zero_()
         else:
-            check(l.ecgvit_mask_embed_bwd(ptr(dX), ptr(a['flag']), ptr(a['dtok']), ptr(a['dmasked']), ptr(G['vit.pos_embedding']), B, n, d,
-                                          T, st), 'mask_embed_bwd')
+            run.ecgvit_mask_embed_bwd(ptr(dX), ptr(a['flag']), ptr(a['dtok']), ptr(a['dmasked']), ptr(G['vit.pos_embedding']), B, n, d,
+                                      T, st)
         self._colsum(a['dmasked'], d, G['pretrain.mask_token'], M, d)
         self._colsum(a['dtok'], d, G['vit.to_patch_embedding.1.bias'], M, d)
         self._wgrad(a['dtok'], a['patches'], 'vit.to_patch_embedding.1.weight', d, self.CP, M)
@@ -1413,9 +1404,9 @@ class VitEngine:
                  strideC=(h * N * N, N * N), b_off=d)
         ntok = self.saved.get('ntok')
         if ntok is not None:   # keys past each record's length get probability 0, its padded query rows all zeros
-            check(lib().ecgvit_softmax_rows_varlen(ptr(S), ptr(ntok), B, h, N, N, stream()), 'softmax_rows_varlen')
+            run.ecgvit_softmax_rows_varlen(ptr(S), ptr(ntok), B, h, N, N, stream())
         else:
-            check(lib().ecgvit_softmax_rows(ptr(S), B * h * N, N, N, stream()), 'softmax_rows')
+            run.ecgvit_softmax_rows(ptr(S), B * h * N, N, N, stream())
         Pd = S
         if ph > 0:
             Pd = self.act['pd']
@@ -1428,7 +1419,7 @@ class VitEngine:
         # NOT the fused bf16 kernels' mask (one 8-bit hash per four keys, p rounded to 1/256, pitch ceil(N/4)): the two paths drop
         # different units, each consistently between its own forward and backward
         cnt8 = count // 8 * 8
-        check(lib().ecgvit_dropout_apply(ptr(src), ptr(dst), cnt8, p, seed, hip.F32, stream()), 'dropout_apply')
+        run.ecgvit_dropout_apply(ptr(src), ptr(dst), cnt8, p, seed, hip.F32, stream())
         if cnt8 != count:
             raise ValueError('f32 attention dropout needs B*h*N*N to be a multiple of 8')
 
@@ -1490,7 +1481,7 @@ class VitEngine:
 
     def _backward(self, gscalar, gelem, gscale, glogits):
         a, T = self.act, hip.code(self.dtype)
-        l, st = lib(), stream()
+        st = stream()
         sv = self.saved
         B, pe, seed = sv['B'], sv['pe'], sv['seed']
         d, N, n = self.d, self.N, self.n
@@ -1500,8 +1491,8 @@ class VitEngine:
         pre = 'vit.'
         G = self.G32
         if sv['labels'] is not None and (gscalar is not None or gelem is not None):
-            check(l.ecgvit_bce_bwd(ptr(a['logits']), ptr(sv['labels']), ptr(sv['weight']), ptr(gscalar), ptr(gelem), gscale,
-                                   ptr(a['dlogits']), B * self.K, st), 'bce_bwd')
+            run.ecgvit_bce_bwd(ptr(a['logits']), ptr(sv['labels']), ptr(sv['weight']), ptr(gscalar), ptr(gelem), gscale,
+                               ptr(a['dlogits']), B * self.K, st)
             dlog = a['dlogits']
             if glogits is not None:
                 raise NotImplementedError('simultaneous loss and logits upstream gradients')
@@ -1516,14 +1507,14 @@ class VitEngine:
         if not self._reach(0):   # frozen parameters: nothing trainable takes part in this objective's backward
             self._zero_pretrain_grads()
             return
-        check(l.ecgvit_head_bwd(ptr(dlog), ptr(a['xhat']), ptr(a['hrstd']), ptr(self.P32[pre + 'mlp_head.0.weight']),
-                                ptr(self.P32[pre + 'mlp_head.0.bias']), ptr(self.P32[pre + 'mlp_head.1.weight']),
-                                ptr(G[pre + 'mlp_head.1.weight']), ptr(G[pre + 'mlp_head.1.bias']),
-                                ptr(G[pre + 'mlp_head.0.weight']), ptr(G[pre + 'mlp_head.0.bias']),
-                                ptr(a['cls_dx'] if pitch == 1 else dX), pitch, B, d, self.K, T, st), 'head_bwd')
+        run.ecgvit_head_bwd(ptr(dlog), ptr(a['xhat']), ptr(a['hrstd']), ptr(self.P32[pre + 'mlp_head.0.weight']),
+                            ptr(self.P32[pre + 'mlp_head.0.bias']), ptr(self.P32[pre + 'mlp_head.1.weight']),
+                            ptr(G[pre + 'mlp_head.1.weight']), ptr(G[pre + 'mlp_head.1.bias']),
+                            ptr(G[pre + 'mlp_head.0.weight']), ptr(G[pre + 'mlp_head.0.bias']),
+                            ptr(a['cls_dx'] if pitch == 1 else dX), pitch, B, d, self.K, T, st)
         if rg is not None:   # the CLS rows' gradient, compact -> rows tok_off[b]; every other row 0
             dX[:M].zero_()
-            check(l.ecgvit_scatter_rows(ptr(a['cls_dx']), ptr(rg.tok_off), ptr(dX), 1, M, B, d, d, d, T, st), 'scatter_rows')
+            run.ecgvit_scatter_rows(ptr(a['cls_dx']), ptr(rg.tok_off), ptr(dX), 1, M, B, d, d, d, T, st)
         self._ready('head')
         dX = self._trunk_bwd(dX, a['dxb'], cls_only_last=cls)
         self._zero_pretrain_grads()
@@ -1531,11 +1522,11 @@ class VitEngine:
             return
         # ---- embedding backward
         if rg is not None:
-            check(l.ecgvit_embed_bwd_ragged(ptr(dX), ptr(a['dtok']), ptr(G[pre + 'cls_token']), ptr(G[pre + 'pos_embedding']), ptr(rg.n_tok),
-                                            ptr(rg.tok_off), B, N, d, pe, seed + 1, T, st), 'embed_bwd_ragged')
+            run.ecgvit_embed_bwd_ragged(ptr(dX), ptr(a['dtok']), ptr(G[pre + 'cls_token']), ptr(G[pre + 'pos_embedding']), ptr(rg.n_tok),
+                                        ptr(rg.tok_off), B, N, d, pe, seed + 1, T, st)
         else:
-            check(l.ecgvit_embed_bwd(ptr(dX), ptr(a['dtok']), ptr(G[pre + 'cls_token']), ptr(G[pre + 'pos_embedding']), B, n, d, pe,
-                                     seed + 1, T, st), 'embed_bwd')
+            run.ecgvit_embed_bwd(ptr(dX), ptr(a['dtok']), ptr(G[pre + 'cls_token']), ptr(G[pre + 'pos_embedding']), B, n, d, pe,
+                                 seed + 1, T, st)
         if N < self.N_max:   # a narrower pass: embed_bwd wrote position rows < N only, the rest take no part
             G[pre + 'pos_embedding'].view(-1, d)[N:].zero_()
         self._colsum(a['dtok'], d, G[pre + 'to_patch_embedding.1.bias'], Mp, d)
@@ -1655,7 +1646,7 @@ class VitEngine:
         the CLS rows only (scattered into the zeroed `dres`).  Fills the layer's gradients and releases its bucket; returns (d(x_in) = out,
         the free full slab = dres), or (None, None) when a backward plan (frozen parameters) stopped the pass inside the block"""
         a, W, P, G = self.act, self.W, self.P32, self.G32
-        l, st = lib(), stream()
+        st = stream()
         d, f, N = self.d, self.f, self.T
         M, T, ws = B * N, hip.code(self.dtype), a['ws']
         i = self.Ly - 1
@@ -1666,7 +1657,7 @@ class VitEngine:
         # ---- FeedForward: x2 = drop(hact W2^T + b2) + x1, the CLS rows
         dY = dXc
         if ph > 0:
-            check(l.ecgvit_dropout_apply_rows(ptr(dXc), ptr(a['cls_dy']), B, d, N, ph, s0 + 4, T, st), 'dropout_apply_rows')
+            run.ecgvit_dropout_apply_rows(ptr(dXc), ptr(a['cls_dy']), B, d, N, ph, s0 + 4, T, st)
             dY = a['cls_dy']
         self._colsum(dY, d, G[lp + '1.fn.net.3.bias'], B, d)
         if self._wants(lp + '1.fn.net.3.weight'):
@@ -1683,10 +1674,10 @@ class VitEngine:
         self._gemm(GEMM_NN, a['cls_dh'], W[lp + '1.fn.net.0.weight'], a['cls_dxn'], B, d, f, f, d, d)
         if not self._reach(b + 2):
             return None, None
-        check(l.ecgvit_layernorm_bwd_fused_rowpitch(ptr(a['cls_dxn']), ptr(a['cls_x1']), ptr(P[lp + '1.norm.weight']), ptr(a['cls_mean2']),
-                                                    ptr(a['cls_rstd2']), ptr(dXc), ptr(a['cls_dx1']), ptr(G[lp + '1.norm.weight']),
-                                                    ptr(G[lp + '1.norm.bias']), ptr(ws), B, d, ptr(a['cls_dxm']), ptr(G[lp + '0.fn.to_out.0.bias']),
-                                                    ph, s0 + 2, N, T, st), 'layernorm_bwd_fused_rowpitch')
+        run.ecgvit_layernorm_bwd_fused_rowpitch(ptr(a['cls_dxn']), ptr(a['cls_x1']), ptr(P[lp + '1.norm.weight']), ptr(a['cls_mean2']),
+                                                ptr(a['cls_rstd2']), ptr(dXc), ptr(a['cls_dx1']), ptr(G[lp + '1.norm.weight']),
+                                                ptr(G[lp + '1.norm.bias']), ptr(ws), B, d, ptr(a['cls_dxm']), ptr(G[lp + '0.fn.to_out.0.bias']),
+                                                ph, s0 + 2, N, T, st)
         # ---- Attention: x1 = drop(attn Wo^T + bo) + x, the CLS rows
         dY = a['cls_dxm'] if ph > 0 else a['cls_dx1']
         if self._wants(lp + '0.fn.to_out.0.weight'):
@@ -1713,7 +1704,7 @@ class VitEngine:
         if not self._reach(b + 6):
             return None, None
         dres.zero_()
-        check(l.ecgvit_scatter_rows(ptr(a['cls_dx1']), ptr(self._cls_rows(B)), ptr(dres), B, N, 1, d, d, d, T, st), 'scatter_rows')
+        run.ecgvit_scatter_rows(ptr(a['cls_dx1']), ptr(self._cls_rows(B)), ptr(dres), B, N, 1, d, d, d, T, st)
         if i > 0:
             lq = f'vit.transformer.layers.{i - 1}.'
             self._ln_bwd_fused(a['dxn'], Xin, P[lp + '0.norm.weight'], L['mean1'], L['rstd1'], dres, out, G[lp + '0.norm.weight'],
@@ -1746,7 +1737,7 @@ class VitEngine:
         if ph > 0:
             self._drop_apply_f32(dP, dP, B * h * N * N, ph, seed)
         # dS = P * (dP - rowsum(P dP)) * scale
-        check(lib().ecgvit_softmax_bwd_rows(ptr(P), ptr(dP), B * h * N, N, N, self.scale, stream()), 'softmax_bwd_rows')
+        run.ecgvit_softmax_bwd_rows(ptr(P), ptr(dP), B * h * N, N, N, self.scale, stream())
         # dQ = dS K ; dK = dS^T Q
         self._gemm(GEMM_NN, dP, qkv, dqkv, N, dh, N, N, 3 * d, 3 * d, batch=(B, h), strideA=sp, strideB=sq, strideC=sq, b_off=d)
         self._gemm(GEMM_TN, dP, qkv, dqkv, N, dh, N, N, 3 * d, 3 * d, batch=(B, h), strideA=sp, strideB=sq, strideC=sq, c_off=d)
@@ -1782,14 +1773,13 @@ class VitEngine:
         def src(L):   # (qkv, lse, probs) of a layer as the entry points take them
             return (ptr(L['qkv']), ptr(L['lse']), None) if bf16 else (None, None, ptr(L['probs']))
         for i in range(Ly):
-            check(l.ecgvit_rollout_cls(*src(layers[i]), ptr(c), ptr(n_tok), ptr(tok_off), B, N, h, dh, self.scale, T, st), 'rollout_cls')
+            run.ecgvit_rollout_cls(*src(layers[i]), ptr(c), ptr(n_tok), ptr(tok_off), B, N, h, dh, self.scale, T, st)
             row = c
             if i > 0:
-                check(l.ecgvit_rollout_colsum(*src(layers[i - 1]), ptr(c), ptr(r), ptr(ws), ptr(n_tok), ptr(tok_off), B, N, h, dh, self.scale, T, st),
-                      'rollout_colsum')
+                run.ecgvit_rollout_colsum(*src(layers[i - 1]), ptr(c), ptr(r), ptr(ws), ptr(n_tok), ptr(tok_off), B, N, h, dh, self.scale, T, st)
                 row = r
             maps[:, i].copy_(row[:, 1:])   # (a strided device copy: layer i of every record is row[1:])
-        check(l.ecgvit_rollout_finish(ptr(maps), ptr(n_tok), B, Ly, N, st), 'rollout_finish')
+        run.ecgvit_rollout_finish(ptr(maps), ptr(n_tok), B, Ly, N, st)
         P = self.P
         if rg is not None:
             counts = rg.lengths // P
@@ -1815,6 +1805,5 @@ class VitEngine:
         if self.dtype == torch.float32:
             return L['probs'].view(B, self.h, self.T, self.T)
         out = torch.empty(B, self.h, self.T, self.T, dtype=torch.float32, device=L['qkv'].device)
-        check(lib().ecgvit_attention_probs(ptr(L['qkv']), ptr(L['lse']), ptr(out), B, self.T, self.h, self.dh, self.scale, hip.BF16, stream()),
-              'attention_probs')
+        run.ecgvit_attention_probs(ptr(L['qkv']), ptr(L['lse']), ptr(out), B, self.T, self.h, self.dh, self.scale, hip.BF16, stream())
         return out

@@ -23,12 +23,19 @@ EPI_GELU_GRAD_AUX, EPI_MUL_AUX, EPI_QUANT_OUT, EPI_NO_OUT, EPI_AUX8 = 128, 256, 
 ACC_INIT, ACC_ADD, ACC_FOLD = 0, 1, 2   # ecgvit_grad_accumulate modes
 KERNEL_NONE, KERNEL_GEMM_F32, KERNEL_GEMM_BF16, KERNEL_GEMM_NT, KERNEL_GEMM_WGRAD = 0, 1, 2, 3, 4
 POOL_CLS, POOL_MEAN = 0, 1   # ecgvit_pool_records modes
+# limits and tile constants of include/ecgvit_hip.h (`ECGVIT_X` there is `X` here; tests/test_abi.py holds the two together, name by name)
+ATTN_MAX_N, ROW_MAX_D = 2048, 2048   # tokens per record of the fused bf16 attention; hidden size of the LayerNorm and pooling kernels
 FIT_TARGETS, FIT_BINS = 16, 256   # ecgvit_fit_histogram / ecgvit_fit_select: targets per lead, bins per pass
-DENOISE_MAX_LEN, DENOISE_MAX_TAPS = 32768, 9   # ecgvit_filtfilt / ecgvit_nlm_*: samples per record, filter taps
-DENOISE_MAX_LEN_TILED = 1 << 25   # ecgvit_*_long / ecgvit_*_tiled: samples per record
-DENOISE_MAX_POINTS = 1024   # ecgvit_rloess: samples per regression window
-RESAMPLE_MAX_LEN, RESAMPLE_MAX_GENERIC = 1 << 25, 65536   # ecgvit_resample: samples per record, the widest generic-radix pass
-RESAMPLE_MAX_CHIRP = 1 << 24   # ecgvit_resample_chirp: samples of a length on the chirp route (its M stays within RESAMPLE_MAX_LEN)
+DENOISE_MAX_LEN, DENOISE_MAX_LEN_TILED = 32768, 33554432   # samples per record: the resident entry points, the _long / _tiled ones (1 << 25)
+DENOISE_MAX_TAPS = 9   # ecgvit_filtfilt: filter taps
+DENOISE_MAX_POINTS, DENOISE_MAX_ROBUST_ITERS = 1024, 10   # ecgvit_rloess: samples per regression window, robust iterations
+DENOISE_NLM_RUN, DENOISE_NLM_MAX_THREADS = 15, 512   # ecgvit_nlm_denoise*: output samples per run, runs of the default tile
+DENOISE_LOESS_LDS = 4096   # ecgvit_rloess_tiled: samples in LDS, a tile and two windows
+DENOISE_MAX_TILES = 65535   # ecgvit_*_tiled: tiles per lead
+RESAMPLE_MAX_LEN, RESAMPLE_MAX_CHIRP = 33554432, 16777216   # ecgvit_resample*: samples per record (1 << 25), of a length on the chirp route (1 << 24)
+RESAMPLE_MAX_GENERIC, RESAMPLE_MAX_GRID_Y = 65536, 65535   # the widest generic-radix pass; records x lead pairs per launch
+TOK_MAX_CLUSTERS, TOK_MAX_LOCAL_TRIALS = 65536, 16   # ecgvit_tok_*: rows of a centre table, candidates per seeding step
+TOK_SEED_SPAN, TOK_DBSCAN_TILE = 1024, 256   # positions per workgroup of the seeding's sweep, segments per LDS tile of a DBSCAN sweep
 
 _ERR = {1: 'ECGVIT_EINVAL (unsupported shape / argument)', 2: 'ECGVIT_ELAUNCH (HIP launch failure)'}
 
@@ -200,6 +207,34 @@ def check(rc, what):
         raise RuntimeError(f'{what}: {_ERR.get(rc, rc)}')
 
 
+# entry points that return a value, not a status (beside every one whose return type is not int): `run` refuses them
+_QUERIES = frozenset(('ecgvit_abi_version', 'ecgvit_gemm_kernel', 'ecgvit_resample_plan', 'ecgvit_resample_chirp_length', 'ecgvit_tok_dbscan_tile',
+                      'ecgvit_tok_dbscan_rows'))
+
+
+class _Run:
+    """`run.ecgvit_x(*args)`: call `lib().ecgvit_x(*args)` and raise what `check` raises, under the entry point's own name, for a non-zero
+    status.  The function is taken from the library object at every call (tools/launch_trace.py swaps that object's attributes: they live in
+    its `__dict__`, where `lib()` has put every name of SIGNATURES); the checked callable of a name is made once and then found as a plain
+    attribute, so a call costs what `check(l.ecgvit_x(...), 'x')` cost."""
+
+    def __getattr__(self, name):
+        if name not in SIGNATURES or name in _QUERIES or SIGNATURES[name][0] is not c_int:
+            raise AttributeError(f'{name}: not an entry point that returns a status (queries go through lib())')
+        fns = vars(lib())
+
+        def call(*args):
+            rc = fns[name](*args)
+            if rc:
+                raise RuntimeError(f'{name}: {_ERR.get(rc, rc)}')
+        call.__name__ = name
+        setattr(self, name, call)
+        return call
+
+
+run = _Run()
+
+
 def ptr(t):
     return None if t is None else t.data_ptr()
 
@@ -260,9 +295,9 @@ def gemm(layout, A, B, C, M, N, K, lda, ldb, ldc, mask_row_pitch=1, **kw):
     of row m * mask_row_pitch (ecgvit_gemm_rowpitch: a product over one row per record)."""
     d = gemm_desc(layout, A, B, C, M, N, K, lda, ldb, ldc, **kw)
     if mask_row_pitch != 1:
-        check(lib().ecgvit_gemm_rowpitch(byref(d), mask_row_pitch, stream()), 'ecgvit_gemm_rowpitch')
+        run.ecgvit_gemm_rowpitch(byref(d), mask_row_pitch, stream())
     else:
-        check(lib().ecgvit_gemm(byref(d), stream()), 'ecgvit_gemm')
+        run.ecgvit_gemm(byref(d), stream())
 
 
 def gemm_kernel(layout, A, B, C, M, N, K, lda, ldb, ldc, mask_row_pitch=1, **kw):

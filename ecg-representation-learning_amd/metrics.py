@@ -17,7 +17,7 @@ import torch
 
 from . import hip
 from .engine import ragged_slice, RawPaddedBatch
-from .hip import lib, check, ptr, stream
+from .hip import run, ptr, stream
 
 
 class DeviceCounts:
@@ -55,8 +55,8 @@ def eval_counts(scores, labels, from_logits=False, return_auc=True, id2code=None
     assert scores.stride(1) == 1 and labels.stride(1) == 1
     B, K = scores.shape
     counts = torch.empty(4 + 2 * K, dtype=torch.int64, device=scores.device)
-    check(lib().ecgvit_eval_counts(ptr(scores), scores.stride(0), ptr(labels), labels.stride(0), B, K, int(from_logits), int(return_auc),
-                                   ptr(counts), stream()), 'eval_counts')
+    run.ecgvit_eval_counts(ptr(scores), scores.stride(0), ptr(labels), labels.stride(0), B, K, int(from_logits), int(return_auc),
+                           ptr(counts), stream())
     h = DeviceCounts(counts, B, K, return_auc, id2code)
     h._keep = (scores, labels)
     return h

@@ -38,11 +38,13 @@ import ctypes
 import numpy as np
 import torch
 
+from . import hip
+from .hip import lib, run, ptr, stream
 from .records import RecordSelection, check_device_store, host_chunks, select_records
 
-MAX_LEN = 1 << 25            # samples per record, before and after: the denoiser's Holter cap
-MAX_GENERIC = 65536          # the widest prime factor a length may have (one generic-radix pass; above it the pass would run for minutes)
-MAX_CHIRP = 1 << 24          # samples of a length on the chirp route: its M stays within MAX_LEN
+MAX_LEN = hip.RESAMPLE_MAX_LEN            # samples per record, before and after: the denoiser's Holter cap
+MAX_GENERIC = hip.RESAMPLE_MAX_GENERIC    # the widest prime factor a length may have (one generic-radix pass; above it the pass would run for minutes)
+MAX_CHIRP = hip.RESAMPLE_MAX_CHIRP        # samples of a length on the chirp route: its M stays within MAX_LEN
 # r0 of `chirp=True`, read off profiles/r24_resample_chirp.txt (tools/resample_rate.py --chirp): the smallest tabled prime from which the chirp
 # route beats the generic pass at both measured shapes (512 records near 5 000 samples: 3.67 against 2.16 ms; one record near 460 000: 1.75
 # against 0.63 ms); at 31 it still loses at the short shape (2.42 against 3.48 ms) and about draws at the long one (0.99 against 0.93 ms)
@@ -50,7 +52,7 @@ CHIRP_DEFAULT = 61
 BUILT_RADICES = (25, 16, 8, 5, 4, 3, 2)
 C = 12                       # leads per record: what `select_records` admits (the kernels pair them: lead 2p with lead 2p + 1)
 _WS_BYTES = 2 ** 30          # the default of `workspace_bytes`: the two ping-pong buffers of a record group
-_MAX_GROUP = 65535 // (C // 2)   # records per launch: the grid's second dimension holds record x lead pair
+_MAX_GROUP = hip.RESAMPLE_MAX_GRID_Y // (C // 2)   # records per launch: the grid's second dimension holds record x lead pair
 
 
 def resampled_length(n, fqs, fqs_target):
@@ -69,7 +71,6 @@ def resampled_length(n, fqs, fqs_target):
 def plan(n):
     """the radices of the passes of a transform of length n (`ecgvit_resample_plan`: host only): the built radices 25, 16, 8, 5, 4, 3, 2
     largest first, then every other prime factor, one generic pass each; [] for n == 1"""
-    from .hip import lib
     rad = (ctypes.c_int * 32)()
     cnt = lib().ecgvit_resample_plan(int(n), rad, 32)
     if cnt < 0:
@@ -80,7 +81,6 @@ def plan(n):
 def chirp_length(n):
     """M of the chirp route for a length n (`ecgvit_resample_chirp_length`: host only): the smallest 2^a 3^b 5^c >= 2 n - 1; -1 for n < 1 or
     n > 1 << 24"""
-    from .hip import lib
     return int(lib().ecgvit_resample_chirp_length(int(n)))
 
 
@@ -135,7 +135,6 @@ def _side_tables(n, sign, chirp, tables, device):
     """the device tables one side of `ecgvit_resample_chirp` takes -> (twiddles, chirp table, filter); plain: the table of (n, sign) and two
     None.  tables: the per-call cache, {(length, sign): twiddles, ('chirp', n, sign): w, ('filter', n, sign): DFT_M(b) / M}; the table of M is
     the forward table of that length, (M, -1), whatever the sign."""
-    from .hip import lib, check, ptr, stream
     key = (chirp_length(n), -1) if chirp else (n, sign)
     if key not in tables:
         tables[key] = torch.from_numpy(twiddles(*key)).to(device)
@@ -146,7 +145,7 @@ def _side_tables(n, sign, chirp, tables, device):
         w = tables[('chirp', n, sign)] = torch.from_numpy(chirp_table(n, sign)).to(device)
         filt = torch.empty((M, 2), dtype=torch.float64, device=device)
         ws = torch.empty((2 * M, 2), dtype=torch.float64, device=device)
-        check(lib().ecgvit_resample_chirp_filter(ptr(w), n, M, ptr(tables[key]), ptr(filt), ptr(ws), stream()), 'ecgvit_resample_chirp_filter')
+        run.ecgvit_resample_chirp_filter(ptr(w), n, M, ptr(tables[key]), ptr(filt), ptr(ws), stream())
         tables[('filter', n, sign)] = filt
     return tables[key], tables[('chirp', n, sign)], tables[('filter', n, sign)]
 
@@ -168,7 +167,6 @@ def _copy_records(x, out, src, s_stride, dst, d_stride, n):
 def _run(x, src_off, lens, s_stride, out, dst_off, out_lens, d_stride, ws_bytes, tables, chirp=None):
     """resample the records (src_off, lens) of the device store x into (dst_off, out_lens) of the device store out: grouped by length, then by
     workspace.  tables: {(n, sign): device table} and the chirp route's entries (`_side_tables`), kept over the chunks of one call."""
-    from .hip import lib, check, ptr, stream
     pairs = np.stack([lens, out_lens], axis=1)
     for n_in, n_out in np.unique(pairs, axis=0).tolist():
         g = np.nonzero((lens == n_in) & (out_lens == n_out))[0]
@@ -191,12 +189,11 @@ def _run(x, src_off, lens, s_stride, out, dst_off, out_lens, d_stride, ws_bytes,
         for lo in range(0, len(g), step):
             cnt = min(step, len(g) - lo)
             if c_in or c_out:
-                check(lib().ecgvit_resample_chirp(ptr(x), ptr(out), ptr(src_d[lo:]), s_stride, ptr(dst_d[lo:]), d_stride, cnt, C, n_in, n_out,
-                                                  ptr(tw_in), ptr(tw_out), ptr(w_in), ptr(f_in), ptr(w_out), ptr(f_out), ptr(ws), stream()),
-                      'ecgvit_resample_chirp')
+                run.ecgvit_resample_chirp(ptr(x), ptr(out), ptr(src_d[lo:]), s_stride, ptr(dst_d[lo:]), d_stride, cnt, C, n_in, n_out,
+                                          ptr(tw_in), ptr(tw_out), ptr(w_in), ptr(f_in), ptr(w_out), ptr(f_out), ptr(ws), stream())
             else:
-                check(lib().ecgvit_resample(ptr(x), ptr(out), ptr(src_d[lo:]), s_stride, ptr(dst_d[lo:]), d_stride, cnt, C, n_in, n_out,
-                                            ptr(tw_in), ptr(tw_out), ptr(ws), stream()), 'ecgvit_resample')
+                run.ecgvit_resample(ptr(x), ptr(out), ptr(src_d[lo:]), s_stride, ptr(dst_d[lo:]), d_stride, cnt, C, n_in, n_out,
+                                    ptr(tw_in), ptr(tw_out), ptr(ws), stream())
 
 
 def resample(records, fqs, fqs_target=250, num=None, offsets=None, idxs=None, chunk_records=None, workspace_bytes=None, chirp=None):

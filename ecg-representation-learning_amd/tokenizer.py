@@ -15,14 +15,16 @@ Not built: `save` / pickling, the plots and the three clusterings that are seque
 import numpy as np
 import torch
 
+from . import hip
+from .hip import lib, run, ptr, stream
 from .records import DeviceTables, check_device_store, select_records
 
 SEGMENT_SIZES = (8, 16, 32)
 PADS = {'zero': 0, 'shift': 1}
-MAX_CLUSTERS = 65536
-MAX_LOCAL_TRIALS = 16
-SEED_SPAN = 1024            # consecutive positions of one lead per workgroup of the seeding's sweep (csrc/tokenize.hip)
-DBSCAN_TILE = 256           # segments per LDS tile of a DBSCAN sweep's column side (csrc/dbscan.hip)
+MAX_CLUSTERS = hip.TOK_MAX_CLUSTERS
+MAX_LOCAL_TRIALS = hip.TOK_MAX_LOCAL_TRIALS
+SEED_SPAN = hip.TOK_SEED_SPAN        # consecutive positions of one lead per workgroup of the seeding's sweep (csrc/tokenize.hip)
+DBSCAN_TILE = hip.TOK_DBSCAN_TILE    # segments per LDS tile of a DBSCAN sweep's column side (csrc/dbscan.hip)
 DBSCAN_ROWS = {8: 1024, 16: 1024, 32: 512}      # rows per workgroup of a DBSCAN sweep, by k: 256 threads, four or two rows each
 DBSCAN_PAIRS_PER_LAUNCH = 1 << 40               # no launch of a DBSCAN sweep covers more pairs (about a second of work): a sweep is enqueued as launches over row blocks
 D_CLS_TH = dict(hierarchical='distance_threshold', dbscan='eps', optics='max_eps', birch='threshold', kmeans='n_clusters')   # ecg_tokenizer.py:72-78
@@ -47,7 +49,6 @@ class _Store(DeviceTables):
         self.dst_off = torch.from_numpy(np.ascontiguousarray(dst_off, np.int64)).to(x.device)
 
     def args(self, x=None):
-        from .hip import ptr
         return (ptr(self.x if x is None else x), ptr(self.src_off), self.stride, ptr(self.raw_len), ptr(self.seg_cum_d), ptr(self.dst_off),
                 self.dst_stride, self.R, self.C, self.n_seg, self.k)
 
@@ -229,21 +230,17 @@ class EcgTokenizer:
 
     # ---- kernels ------------------------------------------------------------------------------------
     def _assign(self, st, table, ids, means, dist=None, prev_ids=None, changed=None):
-        from .hip import lib, check, ptr, stream
-        check(lib().ecgvit_tok_assign(*st.args(), st.pad, ptr(table), table.shape[0], ptr(prev_ids), ptr(ids), ptr(means), ptr(dist), ptr(changed),
-                                      stream()), 'ecgvit_tok_assign')
+        run.ecgvit_tok_assign(*st.args(), st.pad, ptr(table), table.shape[0], ptr(prev_ids), ptr(ids), ptr(means), ptr(dist), ptr(changed),
+                              stream())
 
     def _update(self, st, ids, table, lens, ws, keep_amax=False):
         """keep_amax: `ws` was last used by an update over this very store, whose absolute maximum it still holds: that sweep is skipped"""
-        from .hip import lib, check, ptr, stream
-        check(lib().ecgvit_tok_update(*st.args(), st.pad, ptr(ids), ptr(table), table.shape[0], ptr(lens), ptr(ws), int(keep_amax), stream()),
-              'ecgvit_tok_update')
+        run.ecgvit_tok_update(*st.args(), st.pad, ptr(ids), ptr(table), table.shape[0], ptr(lens), ptr(ws), int(keep_amax), stream())
 
     def _seed(self, st, V, T, first, u53, trace=False, ws=None, keep_amax=False):
         """one k-means++ seeding, enqueued whole: -> (centres (V, k) f32, indices (V,) int64 [g = c * n_seg + p], trace (V - 1, T, 2) int64 or
         None, the workspace), device tensors.  u53: (V - 1, T) uint64 host array, floor(u 2^53).  keep_amax: `ws` comes from a seeding over this
         very store, whose absolute maximum it still holds"""
-        from .hip import lib, check, ptr, stream
         dev = st.x.device
         nbytes = lib().ecgvit_tok_seed_workspace(st.C, st.n_seg, V, st.k, T)
         if nbytes == 0:
@@ -258,8 +255,8 @@ class EcgTokenizer:
         centers = torch.empty((V, st.k), dtype=torch.float32, device=dev)
         indices = torch.empty(V, dtype=torch.int64, device=dev)
         tr = torch.zeros((V - 1, T, 2), dtype=torch.int64, device=dev) if trace else None
-        check(lib().ecgvit_tok_seed(*st.args(), st.pad, V, T, int(first), ptr(u_d), ptr(centers), ptr(indices), ptr(tr), ptr(ws), int(keep_amax),
-                                    stream()), 'ecgvit_tok_seed')
+        run.ecgvit_tok_seed(*st.args(), st.pad, V, T, int(first), ptr(u_d), ptr(centers), ptr(indices), ptr(tr), ptr(ws), int(keep_amax),
+                            stream())
         return centers, indices, tr, ws
 
     @staticmethod
@@ -298,12 +295,11 @@ class EcgTokenizer:
     def _segments(self, st, want_dst=False):
         """-> (segs (n, k) f32, means (n,) f32, dst (n,) int64 or None): the dense table in the reference's flat order; dst: where segment q
         has its id in a tensor of `st.out_shape`"""
-        from .hip import lib, check, ptr, stream
         dev, n = st.x.device, st.C * st.n_seg
         segs = torch.empty((n, self.k), dtype=torch.float32, device=dev)
         means = torch.empty(n, dtype=torch.float32, device=dev)
         dst = torch.empty(n, dtype=torch.int64, device=dev) if want_dst else None
-        check(lib().ecgvit_tok_segments(*st.args(), st.pad, ptr(segs), ptr(means), ptr(dst), stream()), 'ecgvit_tok_segments')
+        run.ecgvit_tok_segments(*st.args(), st.pad, ptr(segs), ptr(means), ptr(dst), stream())
         return segs, means, dst
 
     def segments(self, sigs, offsets=None, idxs=None):
@@ -324,11 +320,10 @@ class EcgTokenizer:
     def _dbscan(self, segs, eps2, min_samples):
         """the passes over a dense (n, k) table -> (core (m,) int64 ascending, labels (n,) int32, roots (m,) int32 or None), device tensors.
         torch compacts the core and the non-core rows and ranks the roots between the sweeps: plumbing; two host reads (the two counts)."""
-        from .hip import lib, check, ptr, stream
-        L, s, k, (n, dev) = lib(), stream(), self.k, (segs.shape[0], segs.device)
+        s, k, (n, dev) = stream(), self.k, (segs.shape[0], segs.device)
         count = torch.empty(n, dtype=torch.int32, device=dev)
         for lo, hi in self._row_blocks(n, n):
-            check(L.ecgvit_tok_dbscan_count(ptr(segs), n, k, eps2, lo, hi, ptr(count), s), 'ecgvit_tok_dbscan_count')
+            run.ecgvit_tok_dbscan_count(ptr(segs), n, k, eps2, lo, hi, ptr(count), s)
         is_core = count >= min_samples
         core = is_core.nonzero().view(-1)                 # ascending q
         labels = torch.full((n,), -1, dtype=torch.int32, device=dev)
@@ -339,9 +334,9 @@ class EcgTokenizer:
         parent = torch.arange(m, dtype=torch.int32, device=dev)
         for lo, hi in self._row_blocks(m, m):
             if hi > 1:                                    # (row 0 has no column below it)
-                check(L.ecgvit_tok_dbscan_link(ptr(table), m, k, eps2, lo, hi, ptr(parent), s), 'ecgvit_tok_dbscan_link')
+                run.ecgvit_tok_dbscan_link(ptr(table), m, k, eps2, lo, hi, ptr(parent), s)
         roots = torch.empty(m, dtype=torch.int32, device=dev)
-        check(L.ecgvit_tok_dbscan_flatten(ptr(parent), m, ptr(roots), s), 'ecgvit_tok_dbscan_flatten')
+        run.ecgvit_tok_dbscan_flatten(ptr(parent), m, ptr(roots), s)
         core_label = torch.unique(roots, sorted=True, return_inverse=True)[1].to(torch.int32)      # ascending root = ascending smallest q
         labels[core] = core_label
         rest = (~is_core).nonzero().view(-1)
@@ -350,7 +345,7 @@ class EcgTokenizer:
             rows = segs.index_select(0, rest)
             got = torch.empty(nb, dtype=torch.int32, device=dev)
             for lo, hi in self._row_blocks(nb, m):
-                check(L.ecgvit_tok_dbscan_border(ptr(rows), nb, ptr(table), ptr(core_label), m, k, eps2, lo, hi, ptr(got), s), 'ecgvit_tok_dbscan_border')
+                run.ecgvit_tok_dbscan_border(ptr(rows), nb, ptr(table), ptr(core_label), m, k, eps2, lo, hi, ptr(got), s)
             labels[rest] = got
         return core, labels, roots
 
@@ -379,7 +374,6 @@ class EcgTokenizer:
         eps2, min_samples = check_eps(kw['eps']), check_min_samples(kw['min_samples'])
         st = self._segment_store(sigs, offsets, idxs)
         with torch.cuda.device(sigs.device):
-            from .hip import lib
             segs, _, dst = self._segments(st, want_dst=True)
             core, labels, roots = self._dbscan(segs, eps2, min_samples)
             n_noise = int((labels < 0).sum())
@@ -450,10 +444,9 @@ class EcgTokenizer:
                 raise ValueError('ids must be (12, T_total) with T_total the segments of the given lengths')
             out = torch.empty((ids.shape[0], int(off[-1])), dtype=torch.float32, device=dev)
             st = self._record_store(out, off, None)
-        from .hip import lib, check, ptr, stream
         with torch.cuda.device(dev):
             table = self._table(dev, th)
-            check(lib().ecgvit_tok_decode(*st.args(), ptr(ids), ptr(means), ptr(table), table.shape[0], stream()), 'ecgvit_tok_decode')
+            run.ecgvit_tok_decode(*st.args(), ptr(ids), ptr(means), ptr(table), table.shape[0], stream())
         return out
 
     # ---- fit ----------------------------------------------------------------------------------------
@@ -539,7 +532,6 @@ class EcgTokenizer:
         rng = np.random.default_rng(kw['random_state'])
         best = seed_ws = None
         with torch.cuda.device(sigs.device):
-            from .hip import lib
             ws = torch.empty(lib().ecgvit_tok_workspace(V, self.k) // 8, dtype=torch.int64, device=sigs.device)
             ws_state = dict(amax=False)
             for _ in range(1 if fixed is not None else n_init):

@@ -283,7 +283,6 @@ class HipTrainStep:
             gflat, pflat, wlow = gflat[lo:hi], pflat[lo:hi], None if wlow is None else wlow[lo:hi]
         if self.collectives:
             self._xchg.finish()
-        l = hip.lib()
         st = hip.stream()
         spans = self._spans   # frozen parameters: the norm of the trainable gradients only
         _sumsq(gflat, spans, self.sumsq, self.ws)
@@ -298,16 +297,16 @@ class HipTrainStep:
         lr = self.lr0 * self.mult(self.step_count - 1)  # lr in effect for this optimiser step
         wlow = hip.ptr(wlow)
         if spans is None:
-            hip.check(l.ecgvit_adamw_step(
+            hip.run.ecgvit_adamw_step(
                 pflat.data_ptr(), gflat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), wlow, gflat.numel(), self.sumsq.data_ptr(),
                 1.0 / self.world, self.max_grad_norm, lr, 0.9, 0.999, 1e-8, self.wd, self.step_count, 1 if self.decoupled else 0,
-                self.norm_out.data_ptr(), st), 'adamw_step')
+                self.norm_out.data_ptr(), st)
         else:
             # frozen parameters: no update, no decay, no moment update; each span at its own step (the lr follows the global one)
-            hip.check(l.ecgvit_adamw_step_spans(
+            hip.run.ecgvit_adamw_step_spans(
                 pflat.data_ptr(), gflat.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), wlow, spans[0].data_ptr(), spans[1], spans[2],
                 self.sumsq.data_ptr(), 1.0 / self.world, self.max_grad_norm, lr, 0.9, 0.999, 1e-8, self.wd, self.step_count,
-                1 if self.decoupled else 0, self.norm_out.data_ptr(), st), 'adamw_step_spans')
+                1 if self.decoupled else 0, self.norm_out.data_ptr(), st)
             for i, f in enumerate(self._flags):
                 if not f:
                     self._lag[i] -= 1   # a frozen parameter's own step count stands still
@@ -421,8 +420,8 @@ class HipTrainStep:
         return self._acc_tables[3], self._acc_tables[4]
 
     def _accumulate(self, model, mode, table):
-        hip.check(hip.lib().ecgvit_grad_accumulate(self.gacc.data_ptr(), model._gflat.data_ptr(), table[0].data_ptr(), table[1], table[2], mode,
-                                                   1.0, hip.stream()), 'grad_accumulate')
+        hip.run.ecgvit_grad_accumulate(self.gacc.data_ptr(), model._gflat.data_ptr(), table[0].data_ptr(), table[1], table[2], mode,
+                                       1.0, hip.stream())
 
     def _fold_then_send(self, model):
         """the last pass's `on_grads_ready` under an overlapped exchange: g += acc over a bucket, then its all-reduce"""
@@ -515,16 +514,16 @@ class HipProbeStep(HipTrainStep):
         a = self._buf
         logits = torch.empty((B, K), device=x.device, dtype=torch.float32)
         loss = torch.empty(1, device=x.device, dtype=torch.float32)
-        l, st, ptr = hip.lib(), hip.stream(), hip.ptr
+        st, ptr = hip.stream(), hip.ptr
         P, G, pre = eng.P32, eng.G32, 'vit.mlp_head.'
-        hip.check(l.ecgvit_head_fwd(ptr(x), 1, ptr(P[pre + '0.weight']), ptr(P[pre + '0.bias']), ptr(P[pre + '1.weight']), ptr(P[pre + '1.bias']),
-                                    ptr(logits), ptr(a['xhat']), ptr(a['hrstd']), B, d, K, LN_EPS, hip.F32, st), 'head_fwd')
-        hip.check(l.ecgvit_bce_fwd(ptr(logits), ptr(y), ptr(w), ptr(a['loss_elem']), ptr(loss), B * K, st), 'bce_fwd')
+        hip.run.ecgvit_head_fwd(ptr(x), 1, ptr(P[pre + '0.weight']), ptr(P[pre + '0.bias']), ptr(P[pre + '1.weight']), ptr(P[pre + '1.bias']),
+                                ptr(logits), ptr(a['xhat']), ptr(a['hrstd']), B, d, K, LN_EPS, hip.F32, st)
+        hip.run.ecgvit_bce_fwd(ptr(logits), ptr(y), ptr(w), ptr(a['loss_elem']), ptr(loss), B * K, st)
         one = self._const(x.device, 'one', [1.0])
-        hip.check(l.ecgvit_bce_bwd(ptr(logits), ptr(y), ptr(w), ptr(one), None, 1.0 / (B * K), ptr(a['dlogits']), B * K, st), 'bce_bwd')
-        hip.check(l.ecgvit_head_bwd(ptr(a['dlogits']), ptr(a['xhat']), ptr(a['hrstd']), ptr(P[pre + '0.weight']), ptr(P[pre + '0.bias']),
-                                    ptr(P[pre + '1.weight']), ptr(G[pre + '1.weight']), ptr(G[pre + '1.bias']), ptr(G[pre + '0.weight']),
-                                    ptr(G[pre + '0.bias']), ptr(a['dx']), 1, B, d, K, hip.F32, st), 'head_bwd')
+        hip.run.ecgvit_bce_bwd(ptr(logits), ptr(y), ptr(w), ptr(one), None, 1.0 / (B * K), ptr(a['dlogits']), B * K, st)
+        hip.run.ecgvit_head_bwd(ptr(a['dlogits']), ptr(a['xhat']), ptr(a['hrstd']), ptr(P[pre + '0.weight']), ptr(P[pre + '0.bias']),
+                                ptr(P[pre + '1.weight']), ptr(G[pre + '1.weight']), ptr(G[pre + '1.bias']), ptr(G[pre + '0.weight']),
+                                ptr(G[pre + '0.bias']), ptr(a['dx']), 1, B, d, K, hip.F32, st)
         self._keep = (x, y, w)   # alive until the kernels that read them have run
         # (the alignment padding inside the head's range holds zeros and stays zero)
         self._update(model, lo, hi)
@@ -541,11 +540,11 @@ def _elem_weights(model, y):
 
 def _sumsq(g, spans, out, ws):
     """out = the sum of squares of the flat gradient buffer g (or a range of it), or of its spans (device table, rows, elements) only"""
-    l, st = hip.lib(), hip.stream()
+    st = hip.stream()
     if spans is None:
-        hip.check(l.ecgvit_sumsq(g.data_ptr(), g.numel(), out.data_ptr(), ws.data_ptr(), st), 'sumsq')
+        hip.run.ecgvit_sumsq(g.data_ptr(), g.numel(), out.data_ptr(), ws.data_ptr(), st)
     else:
-        hip.check(l.ecgvit_sumsq_spans(g.data_ptr(), spans[0].data_ptr(), spans[1], spans[2], out.data_ptr(), ws.data_ptr(), st), 'sumsq_spans')
+        hip.run.ecgvit_sumsq_spans(g.data_ptr(), spans[0].data_ptr(), spans[1], spans[2], out.data_ptr(), ws.data_ptr(), st)
 
 
 def _cuts(B, mb):
@@ -596,8 +595,8 @@ class _Supervised:
         if getattr(st, '_bce_elem', None) is None or st._bce_elem.shape != (B, K) or st._bce_elem.device != y.device:
             st._bce_elem = torch.empty((B, K), device=y.device, dtype=torch.float32)
         loss = torch.empty(1, device=y.device, dtype=torch.float32)
-        hip.check(hip.lib().ecgvit_bce_fwd(self.logits.data_ptr(), y.data_ptr(), hip.ptr(self.w), st._bce_elem.data_ptr(), loss.data_ptr(), B * K,
-                                           hip.stream()), 'bce_fwd')
+        hip.run.ecgvit_bce_fwd(self.logits.data_ptr(), y.data_ptr(), hip.ptr(self.w), st._bce_elem.data_ptr(), loss.data_ptr(), B * K,
+                               hip.stream())
         return loss, self.logits
 
 
@@ -646,8 +645,8 @@ class _Masked:
             self.pred = torch.empty((total,) + tuple(pred.shape[1:]), device=x.device, dtype=pred.dtype)
         self.pred[self.k0:self.k0 + rows].copy_(pred)
         self.k0 += rows
-        hip.check(hip.lib().ecgvit_grad_accumulate(self.loss.data_ptr(), mloss.data_ptr(), self.one_span.data_ptr(), 1, 1,
-                                                   hip.ACC_INIT if j == 0 else hip.ACC_ADD, wj, hip.stream()), 'grad_accumulate')
+        hip.run.ecgvit_grad_accumulate(self.loss.data_ptr(), mloss.data_ptr(), self.one_span.data_ptr(), 1, 1,
+                                       hip.ACC_INIT if j == 0 else hip.ACC_ADD, wj, hip.stream())
         return lambda tpw: eng.backward_masked(gscalar=gs, tiles_per_workgroup=tpw, trainable=st._trainable)
 
     def result(self):
@@ -708,8 +707,7 @@ def clip_grad_norm_(model, max_norm=1.0, error_if_nonfinite=True):
         rows = span_table(model._layout, model._param_names, has, [0] * len(has))
         spans = (torch.tensor(rows, dtype=torch.int64, device=g.device), len(rows), sum(r[1] for r in rows))
     _sumsq(g, spans, sumsq, ws)
-    hip.check(l.ecgvit_clip_scale(g.data_ptr(), g.numel(), sumsq.data_ptr(), float(max_norm), out.data_ptr(), hip.stream()),
-              'clip_scale')
+    hip.run.ecgvit_clip_scale(g.data_ptr(), g.numel(), sumsq.data_ptr(), float(max_norm), out.data_ptr(), hip.stream())
     norm, finite = out.tolist()
     if error_if_nonfinite and finite == 0.0:
         raise RuntimeError('The total norm for gradients is non-finite, so it cannot be clipped.')

@@ -20,6 +20,8 @@ import math
 import numpy as np
 import torch
 
+from . import hip
+from .hip import run, ptr, stream
 from .records import DeviceTables, check_device_store, chunk_step, host_chunks, select_records
 
 
@@ -72,7 +74,7 @@ class FusedInputTransform:
 # Fitting the statistics: the reference's DynamicNormalize (preprocess/transform.py:38-137), on the device
 # ------------------------------------------------------------------------------------------------------------------------------------
 SCHEMES = ('global', 'std', 'norm', 'none')
-MAX_TARGETS = 16   # order statistics per lead of one fit (hip.FIT_TARGETS)
+MAX_TARGETS = hip.FIT_TARGETS   # order statistics per lead of one fit
 
 
 def parse_normalize(normalize):
@@ -221,7 +223,6 @@ class _DeviceSweep:
     """the launches of one pass over the selected records: in place on a device store, or chunk by chunk through a staging buffer for a host one"""
 
     def __init__(self, records, s, chunk_records, device):
-        from . import hip
         if isinstance(records, torch.Tensor) and records.is_cuda:
             check_device_store(records, 'a device store')
             tab, R = DeviceTables.of(records, s), s.R
@@ -244,8 +245,6 @@ def device_raw_stats(records, specs, want_std, offsets=None, idxs=None, chunk_re
     """One sweep of the per-lead raw statistics on the device -> RawStats.  specs: `plan_order_stats` rank-specs; want_std: the second moments
     pass.  Passes: counts + sum together with the top-digit histogram; the squared deviations together with the second digit; the last two
     digits -- a host store is uploaded four times (twice without order statistics), a device store is read in place."""
-    from . import hip
-    from .hip import lib, check, ptr, stream
     s = select_records(records, offsets, idxs)
     C = s.C
     if len(specs) and 2 * len(specs) > MAX_TARGETS + (2 if 'min' in specs else 0):
@@ -264,10 +263,10 @@ def device_raw_stats(records, specs, want_std, offsets=None, idxs=None, chunk_re
         ws = sweep.ws
 
         def moments(mean):
-            return lambda t: check(lib().ecgvit_fit_moments(ptr(t.x), ptr(t.src_off), t.stride, ptr(t.raw_len), t.R, C, ptr(mean), ptr(ws), ptr(state), stream()), 'fit_moments')
+            return lambda t: run.ecgvit_fit_moments(ptr(t.x), ptr(t.src_off), t.stride, ptr(t.raw_len), t.R, C, ptr(mean), ptr(ws), ptr(state), stream())
 
         def histogram(p, T):
-            return lambda t: check(lib().ecgvit_fit_histogram(ptr(t.x), ptr(t.src_off), t.stride, ptr(t.raw_len), t.R, C, ptr(selt), T, p, ptr(hist[p]), stream()), 'fit_histogram')
+            return lambda t: run.ecgvit_fit_histogram(ptr(t.x), ptr(t.src_off), t.stride, ptr(t.raw_len), t.R, C, ptr(selt), T, p, ptr(hist[p]), stream())
 
         sweep.run(moments(None), *([histogram(0, 0)] if specs else []))
         st = state.cpu().numpy()
@@ -294,10 +293,10 @@ def device_raw_stats(records, specs, want_std, offsets=None, idxs=None, chunk_re
             host_sel = np.zeros((C, hip.FIT_TARGETS, 4), np.int64)
             host_sel[:, :T, 0] = np.stack(ranks, 1)
             selt.copy_(torch.from_numpy(host_sel))
-            check(lib().ecgvit_fit_select(ptr(hist[0]), ptr(selt), C, T, 0, stream()), 'fit_select')
+            run.ecgvit_fit_select(ptr(hist[0]), ptr(selt), C, T, 0, stream())
             for p in (1, 2, 3):
                 sweep.run(histogram(p, T), *([moments(mean_dev)] if (want_std and p == 1) else []))
-                check(lib().ecgvit_fit_select(ptr(hist[p]), ptr(selt), C, T, p, stream()), 'fit_select')
+                run.ecgvit_fit_select(ptr(hist[p]), ptr(selt), C, T, p, stream())
             out = selt.cpu().numpy()
             if (out[:, :T, 3] == 0).any():
                 raise RuntimeError('radix select: a rank lies past the count of its lead')

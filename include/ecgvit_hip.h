@@ -197,6 +197,7 @@ int ecgvit_embed_bwd_ragged(const void *dX, void *dtok, float *dcls, float *dpos
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm (eps 1e-5, biased variance, affine).  replaces: vit_pytorch PreNorm.norm / mlp_head[0].
  * ------------------------------------------------------------------------------------------------ */
+#define ECGVIT_ROW_MAX_D 2048 /* d of the LayerNorm entry points and of ecgvit_pool_records (a multiple of 8): a row is held in one wave's registers */
 int ecgvit_layernorm_fwd(const void *x, const float *gamma, const float *beta, void *y, float *mean, float *rstd,
                          int64_t rows, int d, float eps, int dtype, void *stream);
 /* fp8 operand path: the same forward (bf16, d in 64 * {4, 8, 12, 16, 24, 32}) that also writes y8 = saturate(y / *q8_scale) in e4m3 and
@@ -247,7 +248,7 @@ int ecgvit_colsum(const void *in, int64_t ld, float *out, void *partial, int64_t
  * Multi-head self-attention core, fused (bf16 path).  replaces vit_pytorch Attention.forward between
  * to_qkv and to_out: split heads, dots = q k^T * dh^-0.5, softmax, (dropout), attn v, merge heads.
  * qkv: [B*N, 3*h*dh] (columns [q | k | v], head-major inside each) ; out: [B*N, h*dh] ; lse: [B,h,N] f32.
- * bf16 path requires dh == 64 or dh == 128 and N <= 2048; every other dh returns ECGVIT_EINVAL.  dh == 64: online softmax over 32-key tiles;
+ * bf16 path requires dh == 64 or dh == 128 and N <= ECGVIT_ATTN_MAX_N; every other dh returns ECGVIT_EINVAL.  dh == 64: online softmax over 32-key tiles;
  * the backward takes N > 256 as one launch per 256-key window, each window after the first adding its dQ to the bf16 dQ already in dqkv.
  * dh == 128: online softmax over 64-key windows; the backward is two launches (dK / dV per 128-key block, then dQ with P recomputed), no
  * accumulation across launches.  Same layouts, LSE convention and dropout bits for both head dims.  Dropout hash index (bh N + q) ceil(N/4) + key/4 is uint32 and
@@ -256,6 +257,8 @@ int ecgvit_colsum(const void *in, int64_t ld, float *out, void *partial, int64_t
  * round(256 p) / 256 (p = 0.1 -> 26/256 = 0.1016), kept values rescaled by the exact 256 / (256 - round(256 p)); 0 < p < 1/512 cannot be
  * represented and is rejected (ECGVIT_EINVAL) rather than silently rounded to no dropout.
  * ------------------------------------------------------------------------------------------------ */
+#define ECGVIT_ATTN_MAX_N 2048 /* tokens per record of the fused bf16 attention: every fused entry point (forward, backward, CLS-row, varlen, ragged,
+                                  rollout) returns ECGVIT_EINVAL above it */
 int ecgvit_attention_fwd(const void *qkv, void *out, float *lse, int B, int N, int h, int dh, float scale,
                          float dropout_p, uint64_t seed, int dtype, void *stream);
 /* fp8 operand path (dh == 64 only: ECGVIT_EINVAL for dh == 128, the caller quantises `out` itself): the same forward that also writes out8 = saturate(out as stored / *q8_scale) in e4m3 (same [B*N, h*dh] layout, one byte
@@ -439,12 +442,14 @@ int ecgvit_eval_counts(const float *scores, int64_t ld_scores, const float *labe
  * record pooling (EcgVit.encode): one f32 vector per record from its token rows.  Additive entry point: the ABI version stays 6.
  * x: token rows [*, d] (dtype bf16 / f32); record b holds n_tok[b] rows (N when n_tok is NULL; 1 <= n_tok[b] <= N) starting at row
  * tok_off[b] (b * N when tok_off is NULL) -- int32 device arrays, the convention of ecgvit_attention_ragged_* / ecgvit_embed_finish_ragged.
- * mode 0: the record's row 0 (the CLS row);  mode 1: the mean over its n_tok[b] rows, CLS row included (vit_pytorch pool='mean').
+ * mode ECGVIT_POOL_CLS: the record's row 0 (the CLS row);  mode ECGVIT_POOL_MEAN: the mean over its n_tok[b] rows, CLS row included (vit_pytorch pool='mean').
  * Rows at or past n_tok[b] are never read.  gamma / beta non-NULL (both or neither): LayerNorm over d (biased variance, eps) of the pooled
  * f32 vector before the store (vit.mlp_head.0: what the classifier's Linear reads).  out: [B, d] f32, compact.
- * d a multiple of 8, at most 2048.  f32 accumulation in an order fixed by the record's own row count: no atomics, bit-reproducible, and
+ * d a multiple of 8, at most ECGVIT_ROW_MAX_D.  f32 accumulation in an order fixed by the record's own row count: no atomics, bit-reproducible, and
  * independent of B, of the other records and of the row base (packed and padded rows pool to the same bits).
  * ------------------------------------------------------------------------------------------------ */
+#define ECGVIT_POOL_CLS 0  /* mode: the record's row 0 */
+#define ECGVIT_POOL_MEAN 1 /* mode: the mean over the record's n_tok[b] rows */
 int ecgvit_pool_records(const void *x, float *out, const int32_t *n_tok, const int32_t *tok_off, int B, int N, int d, int mode,
                         const float *gamma, const float *beta, float eps, int dtype, void *stream);
 
@@ -487,6 +492,8 @@ int ecgvit_rollout_finish(float *maps, const int32_t *n_tok, int B, int layers, 
  * 4-byte address.  NaN samples are counted and otherwise left out, as the nan-functions leave them out; +-0, denormals and +-inf are ordinary
  * values.  Every entry point ADDS to state the caller owns and zeroes: a store larger than one launch is a sequence of launches per pass.
  * ------------------------------------------------------------------------------------------------ */
+#define ECGVIT_FIT_TARGETS 16 /* order statistics per lead of one select: the second extent of sel and hist */
+#define ECGVIT_FIT_BINS 256   /* bins per radix pass (8-bit digits): the third extent of hist */
 /* bytes of `workspace` ecgvit_fit_moments needs for R records (the per-workgroup partials its second stage adds in a fixed order) */
 int64_t ecgvit_fit_workspace(int R, int C);
 /* state: per lead 32 bytes { uint64 count of non-NaN samples, uint64 count of NaN samples, double sum, double sum of squared deviations }.
@@ -495,9 +502,9 @@ int64_t ecgvit_fit_workspace(int R, int C);
 int ecgvit_fit_moments(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, const double *mean,
                        void *workspace, void *state, void *stream);
 /* Exact order statistics by radix select on the monotone uint32 key of the f32 bit pattern (k = bits ^ (bits < 0 ? ~0 : 0x80000000): -0.0 sorts
- * directly below +0.0), 8 bits per pass, passes 0..3.  sel: uint64 [C][16][4] per (lead, target) { rank, key prefix, slot, count of the chosen
- * bin }; the caller writes the rank of each of its ntarget <= 16 targets (0-based among the lead's non-NaN samples) and zeroes the rest.
- * hist: uint64 [C][16][256], zeroed by the caller before each pass.  Pass p:
+ * directly below +0.0), 8 bits per pass, passes 0..3.  sel: uint64 [C][ECGVIT_FIT_TARGETS][4] per (lead, target) { rank, key prefix, slot, count of the chosen
+ * bin }; the caller writes the rank of each of its ntarget <= ECGVIT_FIT_TARGETS targets (0-based among the lead's non-NaN samples) and zeroes the rest.
+ * hist: uint64 [C][ECGVIT_FIT_TARGETS][ECGVIT_FIT_BINS], zeroed by the caller before each pass.  Pass p:
  *   ecgvit_fit_histogram (once per launch of the store) counts digit p of every non-NaN sample whose key starts with a target's decided prefix
  *     (pass 0: every sample, slot 0); targets that share a prefix share a slot.  Integer atomics only: exact, independent of order;
  *   ecgvit_fit_select then finds, per target, the bin holding its rank, appends it to the prefix and leaves the rank within the bin -- on the
@@ -522,7 +529,11 @@ int ecgvit_fit_select(const uint64_t *hist, uint64_t *sel, int C, int ntarget, i
  * Per segment: mean = (((x0 + x1) + x2) + ... ) * (1 / k) in f32, in that order whatever the layout or the batch; the segment minus its mean
  * is what is clustered.
  * ------------------------------------------------------------------------------------------------ */
-/* ids[.] = argmin_j |s - c_j|^2 over the V rows of centers (f32 [V][k], 1 <= V <= 65536), means[.] = the segment's mean, dist[.] (may be NULL)
+#define ECGVIT_TOK_MAX_CLUSTERS 65536  /* rows of a centre table (V) */
+#define ECGVIT_TOK_MAX_LOCAL_TRIALS 16 /* candidates per step of the k-means++ seeding (n_trials) */
+#define ECGVIT_TOK_SEED_SPAN 1024      /* consecutive positions of one lead per workgroup of the seeding's sweep: sizes ecgvit_tok_seed_workspace */
+#define ECGVIT_TOK_DBSCAN_TILE 256     /* segments per LDS tile of a DBSCAN sweep's column side: what ecgvit_tok_dbscan_tile() returns */
+/* ids[.] = argmin_j |s - c_j|^2 over the V rows of centers (f32 [V][k], 1 <= V <= ECGVIT_TOK_MAX_CLUSTERS), means[.] = the segment's mean, dist[.] (may be NULL)
  * = sum_e (s_e - c_e)^2 for the chosen centre, recomputed directly.  The argmin is taken on score_j = |c_j|^2 - 2 s . c_j, an f32 fma chain
  * in sample order on the matrix pipe (v_mfma_f32_32x32x2_f32, exact f32) that starts from |c_j|^2; equal scores go to the smaller index.
  * prev_ids != NULL (may be ids itself): *changed (uint64, device; zeroed by this call) receives the number of segments whose id differs from
@@ -557,7 +568,7 @@ int ecgvit_tok_update(const float *x, const int64_t *src_off, int64_t lead_strid
  *                   check exists.  C * n_seg >= 2^32 is refused.  The unit 2^-F is 2^-(61 - H) of k (2 A)^2: at 2^28 segments and k = 8,
  *                   2^-30 of 32 A^2.  A segment whose distance is not finite (it holds a non-finite sample) weighs 0.
  *   step 0          centre 0 is segment `first` (0 <= first < C * n_seg).
- *   step c >= 1     with pot = the potential under centres 0 .. c - 1, trial t (0 <= t < n_trials, 1 .. 16) draws target =
+ *   step c >= 1     with pot = the potential under centres 0 .. c - 1, trial t (0 <= t < n_trials, 1 .. ECGVIT_TOK_MAX_LOCAL_TRIALS) draws target =
  *                   (u53[(c - 1) * n_trials + t] * pot) >> 53 from the 117-bit product (u53: device uint64, each below 2^53 -- floor(u 2^53) of
  *                   a uniform u in [0, 1)); its candidate is the smallest g whose inclusive running sum of q exceeds the target (a segment of
  *                   weight 0 is never drawn), and g = 0 when pot == 0 (every segment coincides with a chosen centre: what sklearn's searchsorted
@@ -567,7 +578,7 @@ int ecgvit_tok_update(const float *x, const int64_t *src_off, int64_t lead_strid
  * keep_amax == 1: the sweep for A is skipped and the maximum a previous seeding left at the start of this workspace is used again (the first
  * 16 bytes of the workspace hold what the last 16 bytes of ecgvit_tok_update's hold: the bits of A, then zeros).
  * 2 V launches after that sweep, all on `stream`: no host read, allocation or synchronisation.  Per centre a sweep reads the store once, updates
- * closest (4 bytes read and written per segment) and leaves one uint64 per (trial, workgroup of 1024 consecutive positions of one lead); a
+ * closest (4 bytes read and written per segment) and leaves one uint64 per (trial, workgroup of ECGVIT_TOK_SEED_SPAN consecutive positions of one lead); a
  * one-workgroup pick sums them, takes the argmin and finds the next candidates by a scan of the winner's sums and of one span.  No atomics:
  * integer addition has no order, so the same arguments give the same bits, and a record gives the same weights in every store form. */
 int64_t ecgvit_tok_seed_workspace(int C, int64_t n_seg, int V, int k, int n_trials);   /* bytes; 0 when unsupported */
@@ -601,7 +612,7 @@ int ecgvit_tok_decode(float *out, const int64_t *src_off, int64_t lead_stride, c
  * / (C, T_total) outputs of ecgvit_tok_assign (dst_off[r] + c * dst_stride + s).
  * The pair sweeps take rows [row0, row1) of a table per call (0 <= row0 < row1 <= rows), so that the caller bounds the pairs of one launch; a
  * workgroup holds ecgvit_tok_dbscan_rows(k) rows in registers and streams the other table through LDS in tiles of ecgvit_tok_dbscan_tile()
- * segments.  No floating-point atomics, and no atomics at all outside `link`.
+ * == ECGVIT_TOK_DBSCAN_TILE segments.  No floating-point atomics, and no atomics at all outside `link`.
  *   count   count[i] (int32 [n]) = the number of j in [0, n) with d2(segs_i, segs_j) <= eps2, for i in [row0, row1); one plain store per row.
  *   link    core: the core segments in ascending q (f32 [m][k]); parent: int32 [m], parent[x] = x before the first call.  Rows i in [row0,
  *           row1) meet the columns j < i; every edge joins the trees of i and j in a lock-free union-find: parent[x] <= x always, a find walks
@@ -627,17 +638,26 @@ int ecgvit_tok_dbscan_border(const float *rows, int nrows, const float *core, co
  * the Zheng et al. denoiser (denoise.py; the reference's preprocess/data_preprocessor.py:22-148 and its MATLAB twin): zero-phase low-pass, robust
  * LOESS baseline, noise estimate, non-local means.  Additive entry points: the ABI version stays 6.
  * The store is addressed as ecgvit_fit_moments addresses it (x, src_off, lead_stride, raw_len; raw_len[r] <= 0 skips a record; a record starts
- * at any 4-byte address).  max_len: the caller's upper bound of raw_len, at most 32768 (the non-local means and the robust LOESS keep a lead in
- * LDS; the _long / _tiled entry points at the end of this section take up to 1 << 25); a record longer than max_len is left untouched.  out: the store's own layout (lead c of record r at out + src_off[r] + c * lead_stride); out == x runs in
+ * at any 4-byte address).  max_len: the caller's upper bound of raw_len, at most ECGVIT_DENOISE_MAX_LEN (the non-local means and the robust LOESS keep a lead in
+ * LDS; the _long / _tiled entry points at the end of this section take up to ECGVIT_DENOISE_MAX_LEN_TILED); a record longer than max_len is left untouched.  out: the store's own layout (lead c of record r at out + src_off[r] + c * lead_stride); out == x runs in
  * place, any other overlap is the caller's error.  Only the selected records' raw_len samples are written.  One workgroup per (record, lead);
  * every sum runs in an order that is a function of the record's own length and of the parameters alone, without floating-point atomics: a
  * record's output has the same bits in a rectangle, a ragged store or a subset, alone or in a batch.  NaN input is not supported.
  * ------------------------------------------------------------------------------------------------ */
+#define ECGVIT_DENOISE_MAX_LEN 32768          /* max_len of the resident entry points: the non-local means keeps a lead in LDS */
+#define ECGVIT_DENOISE_MAX_LEN_TILED 33554432 /* max_len of the _long / _tiled entry points: 1 << 25 samples, 24 hours at 360 Hz */
+#define ECGVIT_DENOISE_MAX_TAPS 9             /* ntaps of ecgvit_filtfilt */
+#define ECGVIT_DENOISE_MAX_POINTS 1024        /* samples per regression window of ecgvit_rloess (npoints, or the widest fraction's width) */
+#define ECGVIT_DENOISE_MAX_ROBUST_ITERS 10    /* robust_iters of ecgvit_rloess */
+#define ECGVIT_DENOISE_NLM_RUN 15             /* consecutive output samples a lane of the non-local means owns: the unit of tile_runs */
+#define ECGVIT_DENOISE_NLM_MAX_THREADS 512    /* lanes of a non-local means workgroup: tile_runs == 0 means one run per lane */
+#define ECGVIT_DENOISE_LOESS_LDS 4096         /* f32 samples ecgvit_rloess_tiled keeps in LDS: a tile and two windows */
+#define ECGVIT_DENOISE_MAX_TILES 65535        /* tiles per lead of the _tiled entry points (the grid's third dimension) */
 /* bytes of `workspace` ecgvit_filtfilt and ecgvit_nlm_sigma need (f64 intermediates, [R][C][max_len + 64]); 0 for unsupported arguments */
 int64_t ecgvit_denoise_workspace(int R, int C, int max_len);
 /* scipy.signal.filtfilt(b, a, x) with its defaults, per lead: odd extension by padlen = 3 * ntaps samples at each end, a direct-form-II-transposed
  * pass started from zi * x_ext[0], the same pass over the reversed result started from zi * y[-1], reversed again and stripped.  b, a (ntaps each,
- * the shorter padded with zeros; 1 <= ntaps <= 9; a[0] == 1) and zi (ntaps - 1; scipy.signal.lfilter_zi) are HOST arrays of finite doubles.
+ * the shorter padded with zeros; 1 <= ntaps <= ECGVIT_DENOISE_MAX_TAPS; a[0] == 1) and zi (ntaps - 1; scipy.signal.lfilter_zi) are HOST arrays of finite doubles.
  * f64 arithmetic, f32 loads and stores.  min_len: the caller's lower bound of the positive raw_len; min_len <= padlen is refused, where scipy
  * raises (a shorter record that reaches the kernel all the same is left untouched). */
 int ecgvit_filtfilt(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
@@ -654,7 +674,7 @@ int ecgvit_nlm_sigma(const float *x, const int64_t *src_off, int64_t lead_stride
  * 0 < ii + idx < n (sample 0 is never a neighbour), w = exp(-d / h), d = sum_{j = -p .. p} (x[ii + j] - x[ii + j + idx])^2 where a pair whose
  * second index lies outside [0, n) contributes 0.  The first p + 1 and the last p samples are copied; a record with n <= 2p + 1 is copied
  * through, and so is a lead with sigma == 0 (or with 1 / h past f32) -- the reference divides 0 by 0 there and returns NaN.
- * f32 arithmetic (1 / h once per lead from the f64 sigma, v_exp_f32).  A lane owns runs of 15 consecutive output samples (the last run of a
+ * f32 arithmetic (1 / h once per lead from the f64 sigma, v_exp_f32).  A lane owns runs of ECGVIT_DENOISE_NLM_RUN consecutive output samples (the last run of a
  * record ends on sample n - p - 1) and adds the shifts in ascending order; d is summed from its 2p + 1 terms at the start of each run and shift
  * and slides within the run (d += new^2 - old^2). */
 int ecgvit_nlm_denoise(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len,
@@ -676,8 +696,8 @@ int ecgvit_nlm_denoise(const float *x, float *out, const int64_t *src_off, int64
  * (2) mad == 0 (an all-zero lead; below the smallest normal f64 counts as 0) ends the robust loop and the fit it has stands (the reference
  * divides by zero), as the sigma == 0 lead of ecgvit_nlm_denoise is copied through.
  * frac > 0 replaces npoints per record by the reference's force_odd(int(n * frac) - 1) = 2 floor((int(n frac) - 1) / 2) + 1, computed in f64 as
- * Python computes it.  degree: 1 or 2; robust_iters: 0 (the plain LOESS) .. 10; npoints (frac == 0), or the fraction's width of a record of
- * max_len samples: at most 1024; npoints, and the fraction's width of a record of min_len samples: at least degree + 2.  min_len: the caller's
+ * Python computes it.  degree: 1 or 2; robust_iters: 0 (the plain LOESS) .. ECGVIT_DENOISE_MAX_ROBUST_ITERS; npoints (frac == 0), or the fraction's width of a record of
+ * max_len samples: at most ECGVIT_DENOISE_MAX_POINTS; npoints, and the fraction's width of a record of min_len samples: at least degree + 2.  min_len: the caller's
  * lower bound of the positive raw_len, at least degree + 2 (a record whose window is narrower or wider all the same is left untouched).
  * subtract == 0 writes the baseline, 1 writes x - baseline (the difference in f64, rounded once); out == x works in both.
  * iters (nullable): bytes [R][C][max_len], the robust iterations run at sample j of lead c of the launch's r-th record at
@@ -688,9 +708,9 @@ int ecgvit_nlm_denoise(const float *x, float *out, const int64_t *src_off, int64
 int ecgvit_rloess(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
                   int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters, void *stream);
 
-/* ---- records longer than 32768 samples (Holter length): the same stages with max_len up to 1 << 25 = 33554432 samples (24 hours at 360 Hz).
+/* ---- records longer than ECGVIT_DENOISE_MAX_LEN samples (Holter length): the same stages with max_len up to ECGVIT_DENOISE_MAX_LEN_TILED.
  * Additive entry points: the ABI version stays 6.  The store is addressed as above; every per-record index that multiplies by max_len is 64-bit.
- * The entry points above keep their cap of 32768 and their behaviour; these are opt-in and run short records too.
+ * The entry points above keep their cap and their behaviour; these are opt-in and run short records too.
  * ecgvit_denoise_workspace_long, ecgvit_filtfilt_long, ecgvit_nlm_sigma_long: the formula, the arguments and THE KERNELS of
  * ecgvit_denoise_workspace, ecgvit_filtfilt and ecgvit_nlm_sigma (one launcher each, two caps): a record's bits are the same from either entry
  * point.  Both kernels stage the lead through LDS in chunks and keep their f64 intermediates in `workspace`; the recurrence is walked by one
@@ -700,23 +720,23 @@ int ecgvit_filtfilt_long(const float *x, float *out, const int64_t *src_off, int
                          int max_len, const double *b, const double *a, const double *zi, int ntaps, void *workspace, void *stream);
 int ecgvit_nlm_sigma_long(const float *x, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len, double *sigma,
                           void *workspace, void *stream);
-/* ecgvit_nlm_denoise tiled along time: grid (R, C, tiles), a workgroup owns tile_runs consecutive runs of 15 output samples of one lead
- * (tile_runs == 0: 512, one run per lane of a 512-lane workgroup; more runs than the longest record holds are clamped to that).  The run
- * decomposition is ecgvit_nlm_denoise's: run k starts at p + 1 + 15 k, the last run is moved back to end on n - p - 1, a lane owns whole runs and
+/* ecgvit_nlm_denoise tiled along time: grid (R, C, tiles), a workgroup owns tile_runs consecutive runs of ECGVIT_DENOISE_NLM_RUN output samples of one lead
+ * (tile_runs == 0: ECGVIT_DENOISE_NLM_MAX_THREADS, one run per lane of a workgroup that wide; more runs than the longest record holds are clamped to that).  The run
+ * decomposition is ecgvit_nlm_denoise's: run k starts at p + 1 + ECGVIT_DENOISE_NLM_RUN k, the last run is moved back to end on n - p - 1, a lane owns whole runs and
  * adds the shifts in ascending order, d is summed afresh at the start of each (run, shift) and slides within the run.  A lane's own window is
  * loaded from global memory; the neighbour side is streamed through LDS in ascending chunks of 256 shifts, double-buffered.
  * CONTRACT: the order of every sum is a function of n, p and W alone, so the output is bit-identical to ecgvit_nlm_denoise for every
- * n <= 32768 and every tile_runs.
+ * n <= ECGVIT_DENOISE_MAX_LEN and every tile_runs.
  * out == x is REFUSED (ECGVIT_EINVAL): a workgroup reads samples that another workgroup writes, where ecgvit_nlm_denoise loads the lead before
- * its first store.  Also refused: tile_runs < 0, patch_wd > 1 << 25, and a tile_runs so small that max_len needs more than 65535 tiles. */
+ * its first store.  Also refused: tile_runs < 0, patch_wd > ECGVIT_DENOISE_MAX_LEN_TILED, and a tile_runs so small that max_len needs more than ECGVIT_DENOISE_MAX_TILES tiles. */
 int ecgvit_nlm_denoise_tiled(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int max_len,
                              const double *sigma, double scale, int patch_wd, int sch_wd, int tile_runs, void *stream);
 /* ecgvit_rloess tiled along time: grid (R, C, tiles), a workgroup owns tile_samples consecutive output samples [j0, j0 + tile_samples) and
- * loads x[max(0, j0 - m) .. min(n, j0 + tile_samples + m)) into an LDS array of 4096 f32 (tile_samples == 0: 2048, which fits with two windows
- * of the widest width, 1024).  The per-sample wave code is ecgvit_rloess's, unchanged (window placement, even-tie rule, moment sums,
+ * loads x[max(0, j0 - m) .. min(n, j0 + tile_samples + m)) into an LDS array of ECGVIT_DENOISE_LOESS_LDS f32 (tile_samples == 0: ECGVIT_DENOISE_LOESS_LDS - 2 * ECGVIT_DENOISE_MAX_POINTS, which fits with two
+ * windows of the widest width).  The per-sample wave code is ecgvit_rloess's, unchanged (window placement, even-tie rule, moment sums,
  * elimination, bit-by-bit median, `iters` bytes), and a sample's arithmetic reads only its window.
- * CONTRACT: the output and `iters` are bit-identical to ecgvit_rloess for every n <= 32768 and every tile_samples.
- * Refused: tile_samples < 0; tile_samples + 2 * (the launch's widest window, at most max_len) > 4096; more than 65535 tiles for max_len;
+ * CONTRACT: the output and `iters` are bit-identical to ecgvit_rloess for every n <= ECGVIT_DENOISE_MAX_LEN and every tile_samples.
+ * Refused: tile_samples < 0; tile_samples + 2 * (the launch's widest window, at most max_len) > ECGVIT_DENOISE_LOESS_LDS; more than ECGVIT_DENOISE_MAX_TILES tiles for max_len;
  * out == x (as above). */
 int ecgvit_rloess_tiled(const float *x, float *out, const int64_t *src_off, int64_t lead_stride, const int32_t *raw_len, int R, int C, int min_len,
                         int max_len, int npoints, double frac, int degree, int robust_iters, int subtract, int8_t *iters, int tile_samples,
@@ -730,7 +750,7 @@ int ecgvit_rloess_tiled(const float *x, float *out, const int64_t *src_off, int6
  * The one stage whose output has another shape than its input: the source is addressed as ecgvit_fit_moments addresses it (lead c of record r =
  * n_in f32 samples at x + src_off[r] + c * src_stride), the destination by a table of its own (n_out f32 samples at out + dst_off[r] +
  * c * dst_stride; src_off, dst_off int64 [R], device arrays); every record of a call has the same n_in and the same n_out: the caller groups a
- * ragged store by length.  A record starts at any 4-byte address; out must not overlap x.  1 <= n_in, n_out <= 1 << 25; all per-record indexing
+ * ragged store by length.  A record starts at any 4-byte address; out must not overlap x.  1 <= n_in, n_out <= ECGVIT_RESAMPLE_MAX_LEN; all per-record indexing
  * is 64-bit.  NaN input is not supported (wfdb interpolates NaN before it resamples).
  * ALGORITHM, per record:
  *   pairing   C is even; leads 2p and 2p + 1 are the real and the imaginary part of one complex f64 sequence z of n_in samples.  The resample is
@@ -752,7 +772,7 @@ int ecgvit_rloess_tiled(const float *x, float *out, const int64_t *src_off, int6
  *             order, with multiplicity.  The built radices run in registers (16 and 8 as 4 x 4 and 4 x 2, 25 as 5 x 5); any other radix r runs
  *             one generic pass: a thread per output, a loop over its r inputs.  With r = n that pass is the dense DFT, so a prime length works,
  *             at n^2 complex multiply-adds per lead pair and direction instead of n log n (n = 32 771, prime: 1.1e9; the chirp route below is
- *             the n log n form, through ecgvit_resample_chirp).  A generic radix above 65 536 is refused: its pass would hold the device for
+ *             the n log n form, through ecgvit_resample_chirp).  A generic radix above ECGVIT_RESAMPLE_MAX_GENERIC is refused: its pass would hold the device for
  *             minutes.
  *             Pass with radix r after passes of product Ns, butterfly j < n / r, k = j mod Ns: v[q] = in[j + q n / r] tw[q k n / (Ns r)],
  *             u = DFT_r(v), out[(j - k) r + k + p Ns] = u[p].
@@ -760,11 +780,15 @@ int ecgvit_rloess_tiled(const float *x, float *out, const int64_t *src_off, int6
  * No atomics; every sum runs in an order fixed by (n_in, n_out): a record's output has the same bits in a rectangle, a ragged store, a subset or
  * a chunk, alone or in a batch.
  * ------------------------------------------------------------------------------------------------ */
-/* radices[0 .. count) = the plan of a length n, 1 <= n <= 1 << 25 -> count (their product is n; n == 1 has the empty plan, count 0; a prime
+#define ECGVIT_RESAMPLE_MAX_LEN 33554432     /* n_in, n_out and the M of a chirp side: 1 << 25 samples, ECGVIT_DENOISE_MAX_LEN_TILED */
+#define ECGVIT_RESAMPLE_MAX_CHIRP 16777216   /* a length on the chirp route: 1 << 24 samples, so that its M stays within ECGVIT_RESAMPLE_MAX_LEN */
+#define ECGVIT_RESAMPLE_MAX_GENERIC 65536    /* the widest generic radix (prime factor) that is launched */
+#define ECGVIT_RESAMPLE_MAX_GRID_Y 65535     /* R * (C / 2) of one call: the grid's second dimension holds record x lead pair */
+/* radices[0 .. count) = the plan of a length n, 1 <= n <= ECGVIT_RESAMPLE_MAX_LEN -> count (their product is n; n == 1 has the empty plan, count 0; a prime
  * has the plan { n }); -1 for n out of range or more radices than `cap`.  Host only: nothing is launched. */
 int ecgvit_resample_plan(int n, int *radices, int cap);
 /* bytes of `workspace` ecgvit_resample needs: two buffers of R * (C / 2) * max(n_in, n_out) complex f64; 0 for unsupported arguments (C odd,
- * R * C / 2 > 65535, a length out of range or with a generic radix above 65 536) */
+ * R * C / 2 > ECGVIT_RESAMPLE_MAX_GRID_Y, a length out of range or with a generic radix above ECGVIT_RESAMPLE_MAX_GENERIC) */
 int64_t ecgvit_resample_workspace(int R, int C, int n_in, int n_out);
 /* launches: pack, the passes of n_in, the spectrum map, the passes of n_out, unpack.  n_in == n_out runs the round trip (resample.py copies
  * instead, as wfdb does).  Unsupported arguments (as above, a null or misaligned pointer) return ECGVIT_EINVAL and launch nothing. */
@@ -772,7 +796,7 @@ int ecgvit_resample(const float *x, float *out, const int64_t *src_off, int64_t 
                     int n_in, int n_out, const double *tw_in, const double *tw_out, void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
- * The chirp route (Bluestein's algorithm, the chirp-z transform): the exact DFT of ANY length n <= 1 << 24 at O(n log n), as one circular
+ * The chirp route (Bluestein's algorithm, the chirp-z transform): the exact DFT of ANY length n <= ECGVIT_RESAMPLE_MAX_CHIRP at O(n log n), as one circular
  * convolution of a smooth length M run by the passes above.  Additive and opt-in (resample.py: `chirp=`): ecgvit_resample, its plan and its
  * workspace query are unchanged, and the ABI version stays 6.  A side of a resample (the forward transform of n_in, the inverse transform of
  * n_out) either runs its plan as above ("plain") or is transformed AS A WHOLE by the chirp route; the two sides choose independently.
@@ -781,7 +805,7 @@ int ecgvit_resample(const float *x, float *out, const int64_t *src_off, int64_t 
  *             cos / sin(pi ((j j) mod 2 n) / n) with the square and the reduction in 64-bit integers (resample.py: numpy on the host).  No
  *             device trigonometry, as above.  j k = (j^2 + k^2 - (k - j)^2) / 2 gives X[k] = w[k] sum_j (z[j] w[j]) conj(w[k - j]).
  *   length    M = the smallest integer >= 2 n - 1 of the form 2^a 3^b 5^c (ecgvit_resample_chirp_length), so the plan of M holds built radices
- *             only; n <= 1 << 24 keeps M <= 1 << 25, the cap of the passes.
+ *             only; n <= ECGVIT_RESAMPLE_MAX_CHIRP keeps M <= ECGVIT_RESAMPLE_MAX_LEN, the cap of the passes.
  *   operand   a[j] = z[j] w[j], j < n; a[j] = 0, n <= j < M.
  *   filter    b[j] = conj(w[j]), j < n; b[M - j] = conj(w[j]), 1 <= j < n; b = 0 elsewhere.  filter = DFT_M(b) / M, computed on the device
  *             once per (n, s) by the same passes (ecgvit_resample_chirp_filter) and passed to every launch of that length.
@@ -799,10 +823,10 @@ int ecgvit_resample(const float *x, float *out, const int64_t *src_off, int64_t 
  * Launches of a chirp side: 2 passes(M) + 1 beside pack / map / unpack.  Every sum's order is fixed by (n_in, n_out, route of each side): a
  * record keeps the same bits in every store form.  The two routes of one length agree within rounding, not bit for bit.
  * ------------------------------------------------------------------------------------------------ */
-/* M of a length n: the smallest 2^a 3^b 5^c >= 2 n - 1; -1 for n < 1 or n > 1 << 24.  Host only. */
+/* M of a length n: the smallest 2^a 3^b 5^c >= 2 n - 1; -1 for n < 1 or n > ECGVIT_RESAMPLE_MAX_CHIRP.  Host only. */
 int ecgvit_resample_chirp_length(int n);
 /* bytes of `workspace` ecgvit_resample_chirp needs: two buffers of R * (C / 2) * max(side lengths) complex f64, where a chirp side (flag != 0)
- * counts its M and a plain side its n; 0 for anything refused (as ecgvit_resample_workspace for a plain side; n > 1 << 24 on a chirp side) */
+ * counts its M and a plain side its n; 0 for anything refused (as ecgvit_resample_workspace for a plain side; n > ECGVIT_RESAMPLE_MAX_CHIRP on a chirp side) */
 int64_t ecgvit_resample_chirp_workspace(int R, int C, int n_in, int n_out, int chirp_in, int chirp_out);
 /* filter[0 .. M) = DFT_M(b) / M for the chirp table `chirp` of n entries (either sign), M == ecgvit_resample_chirp_length(n), tw_M the table of
  * M above; `workspace`: 2 M complex f64 (32 M bytes), every element written before it is read.  All pointers device memory, 16-byte aligned.
@@ -813,7 +837,7 @@ int ecgvit_resample_chirp_filter(const double *chirp, int n, int M, const double
  * of M_in, exp(-2 pi i k / M_in).  chirp_out / filter_out likewise with (n_out, +1): plain takes tw_out = exp(+2 pi i k / n_out), chirp takes
  * tw_out = exp(-2 pi i k / M_out).  Both sides plain runs ecgvit_resample's launches and gives its bits.  `workspace`:
  * ecgvit_resample_chirp_workspace bytes.  Everything is checked on the host; a null or misaligned pointer, half of a chirp / filter pair, a
- * chirp side above 1 << 24 samples, a plain side ecgvit_resample refuses: ECGVIT_EINVAL, and nothing is launched. */
+ * chirp side above ECGVIT_RESAMPLE_MAX_CHIRP samples, a plain side ecgvit_resample refuses: ECGVIT_EINVAL, and nothing is launched. */
 int ecgvit_resample_chirp(const float *x, float *out, const int64_t *src_off, int64_t src_stride, const int64_t *dst_off, int64_t dst_stride, int R,
                           int C, int n_in, int n_out, const double *tw_in, const double *tw_out, const double *chirp_in, const double *filter_in,
                           const double *chirp_out, const double *filter_out, void *workspace, void *stream);

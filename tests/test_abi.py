@@ -1,18 +1,60 @@
-"""CPU: the C-ABI library loads and exports every symbol include/ecgvit_hip.h declares; the ctypes table covers them."""
+"""CPU: the C-ABI library loads and exports every symbol include/ecgvit_hip.h declares; the ctypes tables are the headers, type by type; the
+binding's constants are the header's defines."""
 import ctypes
 import os
 import re
+import sys
 
 import pytest
 
 from conftest import ROOT
+import abi_header
 import ecg_representation_learning_amd as E
 
 
 def declared_symbols():
-    src = open(os.path.join(ROOT, 'include', 'ecgvit_hip.h')).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    return sorted(set(re.findall(r'\b(ecgvit_[a-z0-9_]+)\s*\(', src)))
+    return sorted(abi_header.declarations())
+
+
+def test_signatures_are_the_headers_argument_by_argument():
+    """hip.SIGNATURES against every declaration of include/ecgvit_hip.h: the names in both directions, the return type and every argument
+    type (an `_I` where the header says int64_t, an `_F` where it says double puts the wrong thing in a register)"""
+    decls = abi_header.declarations()
+    assert len(decls) == 108 == len(E.hip.SIGNATURES)
+    assert abi_header.mismatches(E.hip.SIGNATURES, decls, E.hip.GemmDesc) == []
+    assert E.hip.SIGNATURES['ecgvit_gemm'][1][0] is ctypes.POINTER(E.hip.GemmDesc) and E.hip.SIGNATURES['ecgvit_version'][0] is ctypes.c_char_p
+
+
+def test_mismatches_reports_each_kind_of_difference():
+    """the comparison itself: one int64_t bound as int, one double bound as float and one argument dropped give exactly three entries (a parser
+    that matches nothing, or a comparison that accepts anything, would pass the test above)"""
+    hip, decls = E.hip, abi_header.declarations()
+    table = {n: (r, list(a)) for n, (r, a) in hip.SIGNATURES.items()}
+    i = table['ecgvit_fp8_amax'][1].index(hip._L)
+    table['ecgvit_fp8_amax'][1][i] = hip._I
+    j = table['ecgvit_nlm_denoise'][1].index(hip._D)
+    table['ecgvit_nlm_denoise'][1][j] = hip._F
+    del table['ecgvit_fit_select'][1][-2]
+    assert sorted(abi_header.mismatches(table, decls, hip.GemmDesc)) == [
+        'ecgvit_fit_select: 6 parameters, the table has 5',
+        f'ecgvit_fp8_amax: parameter {i} is int64_t, the table says c_int',
+        f'ecgvit_nlm_denoise: parameter {j} is double, the table says c_float']
+    del table['ecgvit_softmax_rows']                         # and both directions of the names, and the return type
+    table['ecgvit_nonesuch'] = (hip._I, [])
+    table['ecgvit_sumsq_workspace'] = (hip._I, [hip._L])
+    assert sorted(abi_header.mismatches(table, decls, hip.GemmDesc))[3:] == [
+        'ecgvit_nonesuch: in the table, not declared', 'ecgvit_softmax_rows: declared, not in the table',
+        'ecgvit_sumsq_workspace: returns int64_t, the table says c_int']
+
+
+def test_tools_signatures_are_the_tools_header():
+    """the tools binding's own table against tools/ecgvit_hip_tools.h (ecgvit_tools_gemm is bound by tools/gemm_ab.py alone, on the library it loads)"""
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    import toolslib
+    decls = abi_header.declarations(abi_header.TOOLS_HEADER)
+    assert set(decls) - set(toolslib.SIGNATURES) == {'ecgvit_tools_gemm'} and len(toolslib.SIGNATURES) == 5
+    assert abi_header.mismatches(toolslib.SIGNATURES, {n: decls[n] for n in toolslib.SIGNATURES}, E.hip.GemmDesc) == []
+    assert abi_header.accepts(ctypes.POINTER(E.hip.GemmDesc), decls['ecgvit_tools_gemm'][1][0], E.hip.GemmDesc)
 
 
 def test_library_exports_every_declared_symbol():
@@ -30,9 +72,7 @@ def test_library_exports_every_declared_symbol():
 def test_tools_header_symbols_live_in_the_tools_library_only():
     """tools/ecgvit_hip_tools.h (probes, the one-item attention backward, A/B switches) lives in build/libecgvit_hip_tools.so only: the
     product library exports none of it, the product binding names none of it"""
-    src = open(os.path.join(ROOT, 'tools', 'ecgvit_hip_tools.h')).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    tsyms = sorted(set(re.findall(r'\b(ecgvit_[a-z0-9_]+)\s*\(', src)))
+    tsyms = sorted(abi_header.declarations(abi_header.TOOLS_HEADER))
     assert 'ecgvit_probe_mfma_layout' in tsyms and 'ecgvit_attention_bwd_oneitem' in tsyms and 'ecgvit_tools_attn_fwd_variant' in tsyms
     tools_path = os.path.join(os.path.dirname(E.hip.LIB_PATH), 'csrc', 'build', 'libecgvit_hip_tools.so')
     if not os.path.exists(tools_path):
@@ -55,18 +95,12 @@ def test_version_and_abi():
 
 
 def test_gemm_desc_matches_header_field_order():
-    src = open(os.path.join(ROOT, 'include', 'ecgvit_hip.h')).read()
-    body = src[src.index('typedef struct ecgvit_gemm_desc {'):src.index('} ecgvit_gemm_desc;')]
-    body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
-    names = []
-    for stmt in body.split('{', 1)[1].split(';'):
-        stmt = stmt.strip()
-        if not stmt:
-            continue
-        decl = stmt.split(',')
-        for i, d in enumerate(decl):
-            names.append(re.findall(r'([A-Za-z_0-9]+)\s*$', d.strip())[0])
-    assert names == [f[0] for f in E.hip.GemmDesc._fields_]
+    """names, order AND types of the descriptor's fields"""
+    fields = abi_header.desc_fields()
+    assert len(fields) == 40 and [name for _, name in fields] == [f[0] for f in E.hip.GemmDesc._fields_]
+    assert abi_header.field_mismatches(E.hip.GemmDesc._fields_, fields) == []
+    wrong = [(n, ctypes.c_int64 if n == 'K' else ctypes.c_int32 if n == 'ldq8' else t) for n, t in E.hip.GemmDesc._fields_]
+    assert abi_header.field_mismatches(wrong, fields) == ['field 6: int32_t K, _fields_ has c_long K', 'field 34: int64_t ldq8, _fields_ has c_int ldq8']
 
 
 def test_gemm_kernel_route_query_is_host_only():
@@ -123,20 +157,30 @@ def test_gemm_route_and_workspace_table():
 
 
 def test_binding_constants_are_the_headers():
-    """every numeric #define of include/ecgvit_hip.h that the Python binding restates (dtype / layout / epilogue / kernel-family codes, error codes)
-    has the same value there: `ECGVIT_X` <-> `hip.X`"""
+    """two-sided: every numeric #define of include/ecgvit_hip.h (dtype / layout / epilogue / kernel-family / mode codes, limits and tile constants)
+    is an attribute of the binding with that value, `ECGVIT_X` <-> `hip.X` (the three status codes are held through `hip._ERR`), and every
+    all-capitals integer of the binding is such a define (ABI_VERSION is what ecgvit_abi_version() returns: test_version_and_abi)"""
     hip = E.hip
     text = open(os.path.join(ROOT, 'include', 'ecgvit_hip.h')).read()
     defs = {m.group(1): int(m.group(2)) for m in re.finditer(r'^#define ECGVIT_([A-Z0-9_]+)\s+(-?\d+)\b', text, re.M)}
-    assert len(defs) >= 25, defs
+    assert len(defs) >= 53, defs
+    status = {'OK', 'EINVAL', 'ELAUNCH'}
     checked = 0
     for name, val in defs.items():
-        if hasattr(hip, name):
-            assert getattr(hip, name) == val, (name, val, getattr(hip, name))
+        if name not in status:
+            assert type(getattr(hip, name, None)) is int and getattr(hip, name) == val, (name, val, getattr(hip, name, None))
             checked += 1
+    mirrored = {n for n, v in vars(hip).items() if n.isupper() and type(v) is int} - {'ABI_VERSION'}
+    assert mirrored == set(defs) - status, mirrored ^ (set(defs) - status)
     for need in ('F32', 'BF16', 'FP8_E4M3', 'BF8_E5M2', 'GEMM_NT', 'GEMM_NN', 'GEMM_TN', 'EPI_BIAS', 'EPI_GELU', 'EPI_GELU_BWD', 'EPI_RESIDUAL', 'EPI_ACCUM',
                  'EPI_DROPOUT', 'EPI_COLSUM', 'EPI_GELU_GRAD_AUX', 'EPI_MUL_AUX', 'EPI_QUANT_OUT', 'EPI_NO_OUT', 'KERNEL_NONE', 'KERNEL_GEMM_F32',
-                 'KERNEL_GEMM_BF16', 'KERNEL_GEMM_NT', 'KERNEL_GEMM_WGRAD'):
+                 'KERNEL_GEMM_BF16', 'KERNEL_GEMM_NT', 'KERNEL_GEMM_WGRAD', 'EPI_AUX8', 'ACC_INIT', 'ACC_ADD', 'ACC_FOLD', 'POOL_CLS', 'POOL_MEAN', 'ATTN_MAX_N', 'ROW_MAX_D',
+                 'FIT_TARGETS', 'FIT_BINS', 'DENOISE_MAX_LEN', 'DENOISE_MAX_LEN_TILED', 'DENOISE_MAX_TAPS', 'DENOISE_MAX_POINTS',
+                 'DENOISE_MAX_ROBUST_ITERS', 'DENOISE_NLM_RUN', 'DENOISE_NLM_MAX_THREADS', 'DENOISE_LOESS_LDS', 'DENOISE_MAX_TILES', 'RESAMPLE_MAX_LEN',
+                 'RESAMPLE_MAX_CHIRP', 'RESAMPLE_MAX_GENERIC', 'RESAMPLE_MAX_GRID_Y', 'TOK_MAX_CLUSTERS', 'TOK_MAX_LOCAL_TRIALS', 'TOK_SEED_SPAN',
+                 'TOK_DBSCAN_TILE'):
         assert need in defs and hasattr(hip, need), need
-    assert checked >= 23
+    assert checked >= 50
+    assert hip.DENOISE_MAX_LEN_TILED == hip.RESAMPLE_MAX_LEN == 1 << 25 and hip.RESAMPLE_MAX_CHIRP == 1 << 24
+    assert E.hip.lib().ecgvit_tok_dbscan_tile() == hip.TOK_DBSCAN_TILE
     assert {1: 'EINVAL', 2: 'ELAUNCH'} == {defs['EINVAL']: 'EINVAL', defs['ELAUNCH']: 'ELAUNCH'} and set(hip._ERR) == {1, 2}

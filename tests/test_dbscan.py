@@ -5,19 +5,16 @@ call launches nothing) and the constants the GPU tests build their edge cases fr
 Exact-integer stores: samples are integers in -2 .. 2, so a mean-removed sample is a multiple of 1 / k of magnitude at most 4, a squared
 distance a multiple of 1 / k^2 below k * 8^2 (in units of 1 / k^2: 32 * 64 * 32^2 = 2^21 < 2^24), and eps a half-integer whose square is
 exact: every decision is the same in f32 and f64, and a pair at exactly eps is a neighbour in both."""
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+import abi_header
 import ecg_representation_learning_amd as E
 from ecg_representation_learning_amd import hip, tokenizer
 import dbscan_ref as D
 
-HEADER = os.path.join(ROOT, 'include', 'ecgvit_hip.h')
 
 
 def test_restatement_equals_sklearn_on_exact_integer_stores():
@@ -123,12 +120,9 @@ ARITY = {'ecgvit_tok_segments': 16, 'ecgvit_tok_dbscan_count': 8, 'ecgvit_tok_db
 
 
 def test_symbols_constants_and_abi():
-    src = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
     lib = hip.lib()
-    for name, nargs in ARITY.items():
-        m = re.search(name + r'\s*\(([^)]*)\)', src)
-        assert m, name
-        assert len(m.group(1).split(',')) == nargs == len(hip.SIGNATURES[name][1]), name
+    abi_header.held(ARITY, hip.SIGNATURES)                  # declared, with this many arguments, bound with the declaration's types
+    for name in ARITY:
         assert hasattr(lib, name)
     assert lib.ecgvit_abi_version() == 6
     assert lib.ecgvit_tok_dbscan_tile() == tokenizer.DBSCAN_TILE

@@ -3,7 +3,6 @@ launchers (no GPU is touched: a refused call launches nothing), the workspace fo
 resources of the new kernels, and the host contract of `tiled=` / `tile=` in `denoise`."""
 import ctypes
 import os
-import re
 import sys
 
 import numpy as np
@@ -11,11 +10,12 @@ import pytest
 import torch
 
 from conftest import ROOT
+import abi_header
 import ecg_representation_learning_amd as E
 from ecg_representation_learning_amd import hip, denoise
 from ecg_representation_learning_amd.records import DeviceTables
 
-HEADER = os.path.join(ROOT, 'include', 'ecgvit_hip.h')
+HEADER = abi_header.HEADER
 CAP = 1 << 25
 INCART = 462600
 ARITY = {'ecgvit_denoise_workspace_long': 3, 'ecgvit_filtfilt_long': 15, 'ecgvit_nlm_sigma_long': 10, 'ecgvit_nlm_denoise_tiled': 14,
@@ -24,12 +24,9 @@ PRESENT = {'ecgvit_denoise_workspace_long': 'ecgvit_denoise_workspace', 'ecgvit_
 
 
 def test_symbols_exist_with_the_declared_arity():
-    src = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
     lib = hip.lib()
-    for name, nargs in ARITY.items():
-        m = re.search(name + r'\s*\(([^)]*)\)', src)
-        assert m, name
-        assert len(m.group(1).split(',')) == nargs == len(hip.SIGNATURES[name][1]), name
+    abi_header.held(ARITY, hip.SIGNATURES)                  # declared, with this many arguments, bound with the declaration's types
+    for name in ARITY:
         assert hasattr(lib, name)
     for name, present in PRESENT.items():                   # the _long forms take the arguments of the present entry points
         assert hip.SIGNATURES[name] == hip.SIGNATURES[present], name
@@ -41,8 +38,9 @@ def test_symbols_exist_with_the_declared_arity():
 
 def test_the_header_states_the_contracts():
     src = ' '.join(open(HEADER).read().split())
-    assert 'bit-identical to ecgvit_nlm_denoise for every * n <= 32768 and every tile_runs' in src
-    assert 'bit-identical to ecgvit_rloess for every n <= 32768 and every tile_samples' in src
+    assert 'bit-identical to ecgvit_nlm_denoise for every * n <= ECGVIT_DENOISE_MAX_LEN and every tile_runs' in src
+    assert 'bit-identical to ecgvit_rloess for every n <= ECGVIT_DENOISE_MAX_LEN and every tile_samples' in src
+    assert '#define ECGVIT_DENOISE_MAX_LEN 32768 ' in src
     assert 'out == x is REFUSED' in src
 
 

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import ROOT
+import abi_header
 
 import ecg_representation_learning_amd as E
 from ecg_representation_learning_amd import hip
@@ -26,11 +27,8 @@ def _engine(dtype=torch.bfloat16, N=251, **kw):
 
 
 def test_entry_point_declared_exported_and_bound_at_abi_6():
-    src = open(os.path.join(ROOT, 'include', 'ecgvit_hip.h')).read()
-    code = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    m = re.search(r'int\s+ecgvit_pool_records\s*\(([^;]*)\)\s*;', code)
-    assert m, 'ecgvit_pool_records is not declared in include/ecgvit_hip.h'
-    assert len(m.group(1).split(',')) == 13 == len(hip.SIGNATURES['ecgvit_pool_records'][1])
+    src = open(abi_header.HEADER).read()
+    assert abi_header.held({'ecgvit_pool_records': 13}, hip.SIGNATURES)['ecgvit_pool_records'][0] == 'int'
     assert hasattr(ctypes.CDLL(hip.LIB_PATH), 'ecgvit_pool_records')
     assert hip.ABI_VERSION == 6 and hip.lib().ecgvit_abi_version() == 6
     assert re.search(r'^#define ECGVIT_ABI\s+6\b', src, re.M) or 'abi6' in hip.lib().ecgvit_version().decode()

@@ -8,20 +8,17 @@ and so its median, are the rounding of the solver, 0 in one restatement and 1e-1
 is exactly 0 in either, which is what equal iteration counts need there (the decisions themselves are far from the cut: the three interpolated
 samples keep bw >= 0.79, the fourth has bw = 0)."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+import abi_header
 import ecg_representation_learning_amd as E
 from ecg_representation_learning_amd import hip, denoise
 import loess_ref as R
 from loess_gpu_cases import CASES, case_input
 
-HEADER = os.path.join(ROOT, 'include', 'ecgvit_hip.h')
 SHAPES = [(4, 31), (5, 4), (40, 31), (300, 31), (300, 32), (300, 65), (600, 501)]
 SEED = {(4, 31): 1, (5, 4): 3}
 
@@ -83,9 +80,7 @@ def test_fraction_width():
 
 # ---- ABI ----------------------------------------------------------------------------------------------
 def test_symbol_exists_with_the_declared_arity():
-    src = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    m = re.search(r'ecgvit_rloess\s*\(([^)]*)\)', src)
-    assert m and len(m.group(1).split(',')) == 16 == len(hip.SIGNATURES['ecgvit_rloess'][1])
+    abi_header.held({'ecgvit_rloess': 16}, hip.SIGNATURES)
     assert hasattr(hip.lib(), 'ecgvit_rloess') and hip.lib().ecgvit_abi_version() == 6
     assert hip.DENOISE_MAX_POINTS == denoise.MAX_POINTS == 1024
 

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import ROOT
+import abi_header
 import ecg_representation_learning_amd as E
 
 CONF = dict(max_signal_length=400, patch_size=20, hidden_size=64, num_hidden_layers=2, num_attention_heads=2, intermediate_size=128)
@@ -54,9 +55,9 @@ def test_train_args_carry_micro_batch_size():
 
 
 def test_accumulate_entry_point_is_bound():
-    assert 'ecgvit_grad_accumulate' in E.hip.SIGNATURES
+    abi_header.held({'ecgvit_grad_accumulate': 8}, E.hip.SIGNATURES)
     assert (E.hip.ACC_INIT, E.hip.ACC_ADD, E.hip.ACC_FOLD) == (0, 1, 2)
-    src = open(os.path.join(ROOT, 'include', 'ecgvit_hip.h')).read()
+    src = open(abi_header.HEADER).read()
     for k, v in (('INIT', 0), ('ADD', 1), ('FOLD', 2)):
         assert f'#define ECGVIT_ACC_{k} {v}' in src
 

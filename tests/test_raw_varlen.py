@@ -3,7 +3,6 @@ padded, ragged and masked layouts from hand-written raw lengths, slicing by reco
 token rows), the refusals that come before any launch, the per-record TimeOut draw against the reference's calls written out here, the new
 C-ABI entry point and its kernels' resources (code-object metadata), and the ragged feeder on device='cpu'.  No GPU."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -11,6 +10,7 @@ import pytest
 import torch
 
 from conftest import ROOT
+import abi_header
 
 import ecg_representation_learning_amd as E
 from ecg_representation_learning_amd import hip
@@ -19,7 +19,6 @@ from ecg_representation_learning_amd.engine import (VitEngine, RaggedBatch, RawP
 
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 LIB = os.path.join(ROOT, 'ecg-representation-learning_amd', 'libecgvit_hip.so')
-HEADER = os.path.join(ROOT, 'include', 'ecgvit_hip.h')
 P, C = 4, 12
 RAW = torch.tensor([1, 3, 8, 7, 30])     # l = 1, l < P, l = 2 P (the quirk: 3 patches), l = 2 P - 1, l = 7 P + 2
 PADDED = [4, 4, 12, 8, 32]
@@ -212,8 +211,7 @@ def test_per_record_timeout_draw_is_the_references_calls_on_each_padded_length(s
 # ------------------------------------------------------------------------------------------------ ABI / code object
 def test_entry_point_declared_bound_and_exported():
     name = 'ecgvit_patch_gather_transform_varlen'
-    assert re.search(r'\bint ' + name + r'\(', open(HEADER).read())
-    assert name in hip.SIGNATURES and len(hip.SIGNATURES[name][1]) == 19
+    assert abi_header.held({name: 19}, hip.SIGNATURES)[name][0] == 'int'
     import ctypes
     assert hasattr(ctypes.CDLL(LIB), name)
     assert ctypes.CDLL(LIB).ecgvit_abi_version() == 6

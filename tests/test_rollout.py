@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import ROOT, load_micro
+import abi_header
 
 import ecg_representation_learning_amd as E
 from ecg_representation_learning_amd import hip
@@ -66,14 +67,10 @@ def test_closed_form_from_qkv_rebuilds_the_probabilities():
 
 
 def test_entry_points_declared_exported_and_bound_at_abi_6():
-    src = open(os.path.join(ROOT, 'include', 'ecgvit_hip.h')).read()
-    code = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
     so = ctypes.CDLL(hip.LIB_PATH)
-    for name, nargs in NEW.items():
-        m = re.search(r'int(?:64_t)?\s+' + name + r'\s*\(([^;]*)\)\s*;', code)
-        assert m, f'{name} is not declared in include/ecgvit_hip.h'
-        assert len(m.group(1).split(',')) == nargs == len(hip.SIGNATURES[name][1]), name
-        assert hasattr(so, name)
+    decls = abi_header.held(NEW, hip.SIGNATURES)
+    for name in NEW:
+        assert decls[name][0] in ('int', 'int64_t') and hasattr(so, name)
     assert hip.ABI_VERSION == 6 and hip.lib().ecgvit_abi_version() == 6
     assert hip.lib().ecgvit_rollout_workspace(512, 251, 12) == 4 * 512 * 251 * 12
     assert hip.lib().ecgvit_rollout_workspace(0, 251, 12) == 0
