@@ -9,7 +9,7 @@ from .check_args import ca, CheckArg
 from .ecg_vit import EcgVitConfig, EcgVit, ModelOutput, RolloutOutput, HipViT, MaskedEcgVit, load_trained
 from .train import get_train_args, lr_multiplier, HipTrainStep, HipProbeStep, clip_grad_norm_
 from .transform import FusedInputTransform, fit_dynamic_normalize, DynamicNormalizeFit
-from .tokenizer import EcgTokenizer, KMeansPlusPlus, Dbscan
+from .tokenizer import EcgTokenizer, KMeansPlusPlus, ScalableKMeansPlusPlus, Dbscan
 from .denoise import EcgDenoiser, design_lowpass, rloess, lowpass, estimate_noise_std, nlm
 from . import denoise
 from .resample import resample, resampled_length, plan as resample_plan, chirp_length as resample_chirp_length, route as resample_route
@@ -20,4 +20,4 @@ from . import ddp
 from . import workload
 
 __all__ = ['ca', 'CheckArg', 'EcgVitConfig', 'EcgVit', 'ModelOutput', 'RolloutOutput', 'HipViT', 'MaskedEcgVit', 'load_trained', 'get_train_args', 'lr_multiplier',
-           'HipTrainStep', 'HipProbeStep', 'clip_grad_norm_', 'FusedInputTransform', 'fit_dynamic_normalize', 'DynamicNormalizeFit', 'EcgTokenizer', 'KMeansPlusPlus', 'Dbscan', 'EcgDenoiser', 'design_lowpass', 'rloess', 'lowpass', 'estimate_noise_std', 'nlm', 'denoise', 'resample', 'resampled_length', 'resample_plan', 'resample_chirp_length', 'resample_route', 'get_accuracy', 'eval_counts', 'HipEvaluator', 'HipEncoder', 'HipRollout', 'DeviceFeeder', 'RaggedDeviceFeeder', 'ptbxl_splits', 'lbs2multi_hot', 'open_records', 'hip', 'ddp', 'workload']
+           'HipTrainStep', 'HipProbeStep', 'clip_grad_norm_', 'FusedInputTransform', 'fit_dynamic_normalize', 'DynamicNormalizeFit', 'EcgTokenizer', 'KMeansPlusPlus', 'ScalableKMeansPlusPlus', 'Dbscan', 'EcgDenoiser', 'design_lowpass', 'rloess', 'lowpass', 'estimate_noise_std', 'nlm', 'denoise', 'resample', 'resampled_length', 'resample_plan', 'resample_chirp_length', 'resample_route', 'get_accuracy', 'eval_counts', 'HipEvaluator', 'HipEncoder', 'HipRollout', 'DeviceFeeder', 'RaggedDeviceFeeder', 'ptbxl_splits', 'lbs2multi_hot', 'open_records', 'hip', 'ddp', 'workload']

@@ -82,7 +82,57 @@ template <int K> __device__ __forceinline__ float tok_d2(const float (&v)[K], co
     return acc;
 }
 
+// ---- the seedings' integer weights (tokenize.hip, tok_scalable.hip) -------------------------------------
+// 2^(31 - E) with 2^(E - 1) <= A < 2^E for the maximum's bit pattern (A = 0: any scale does)
+__device__ __forceinline__ int tok_shift(uint32_t amax_bits) {
+    const int ex = (int)(amax_bits >> 23);                 // biased exponent; 0 for a denormal maximum, 255 for inf / NaN
+    return 31 - ((ex ? ex : 1) - 127 + 1);
+}
+
+// rint(d 2^F) in f64, where the product is exact; a non-finite distance (a segment with a non-finite sample, the untouched +inf) weighs nothing
+__device__ __forceinline__ u64 tok_quant(float d, int F) {
+    return (__float_as_uint(d) & 0x7F800000u) == 0x7F800000u ? 0ull : __double2ull_rn(ldexp((double)d, F));
+}
+
+// F = 63 - H - (2 E + 2 + log2 k) from fbase = 63 - H - 2 - log2 k and the maximum's bits
+__device__ __forceinline__ int tok_seed_f(int fbase, uint32_t amax_bits) { return fbase - 2 * (31 - tok_shift(amax_bits)); }
+
+// (U pot) >> 53 of the 117-bit product, U < 2^53
+__device__ __forceinline__ u64 tok_target(u64 U, u64 pot) { return (__umul64hi(U, pot) << 11) | ((U * pot) >> 53); }
+
+__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// inclusive scan over the workgroup's threads in thread order; sh: one u64 per wave
+__device__ __forceinline__ u64 block_scan_u64(u64 v, u64 *sh) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const u64 up = __shfl_up(v, o, 64);
+        if (lane >= o) v += up;
+    }
+    if (lane == 63) sh[wave] = v;
+    __syncthreads();
+    u64 before = 0;
+    for (int w = 0; w < nw; ++w) before += w < wave ? sh[w] : 0ull;
+    __syncthreads();
+    return v + before;
+}
+
 // ---- the launchers' side -------------------------------------------------------------------------------
+// the sweep for the absolute maximum of the mean-removed samples (tokenize.hip): *amax, zeroed by the caller, receives its bits
+int tok_launch_amax(const struct TokStore &st, int C, int64_t n_seg, int k, uint32_t *amax, hipStream_t stream);
+// fbase = 63 - H - 2 - log2 k with H = bit_length(C * n_seg): what tok_seed_f takes
+static inline int tok_seed_fbase(int C, int64_t n_seg, int k) {
+    int H = 0, log2k = 0;
+    while (((int64_t)C * n_seg) >> H) ++H;
+    while ((1 << log2k) < k) ++log2k;
+    return 63 - H - 2 - log2k;
+}
+
 static inline bool tok_al(const void *p, unsigned a) { return p && (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
 
 static bool tok_store_ok(const float *x, const int64_t *src_off, const int32_t *raw_len, const int64_t *seg_cum, const int64_t *dst_off, int R, int C,

@@ -149,10 +149,14 @@ __global__ __launch_bounds__(TOK_THREADS) void tok_amax_kernel(TokStore st, int6
     if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(amax, __float_as_uint(m));
 }
 
-// 2^(31 - E) with 2^(E - 1) <= A < 2^E for the maximum's bit pattern (A = 0: any scale does)
-__device__ __forceinline__ int tok_shift(uint32_t amax_bits) {
-    const int ex = (int)(amax_bits >> 23);                 // biased exponent; 0 for a denormal maximum, 255 for inf / NaN
-    return 31 - ((ex ? ex : 1) - 127 + 1);
+int tok_launch_amax(const TokStore &st, int C, int64_t n_seg, int k, uint32_t *amax, hipStream_t stream) {
+    const int64_t blocks = (n_seg + TOK_THREADS - 1) / TOK_THREADS;
+    if (blocks > 0x7FFFFFFFll) return ECGVIT_EINVAL;
+#define TOK_LAUNCH(KK) hipLaunchKernelGGL(tok_amax_kernel<KK>, dim3((unsigned)blocks, C), dim3(TOK_THREADS), 0, stream, st, n_seg, amax)
+    TOK_BY_K(k, TOK_LAUNCH);
+#undef TOK_LAUNCH
+    ECGVIT_CHECK_LAUNCH();
+    return ECGVIT_OK;
 }
 
 template <int K>
@@ -203,36 +207,6 @@ __global__ __launch_bounds__(TOK_THREADS) void tok_finish_kernel(const u64 *__re
 #define SEED_WS_CAND_G 16                                // workspace: the maximum's bits at 0, the candidates' g (int64 [16]),
 #define SEED_WS_CAND_C (SEED_WS_CAND_G + SEED_TMAX * 8)  //   the candidates' segments (f32 [16][32]),
 #define SEED_WS_SUMS (SEED_WS_CAND_C + SEED_TMAX * 32 * 4)   // block_sums (u64 [T][C * blocks]), then closest (f32 [C * n_seg])
-
-// rint(d 2^F) in f64, where the product is exact; a non-finite distance (a segment with a non-finite sample, the untouched +inf) weighs nothing
-__device__ __forceinline__ u64 tok_quant(float d, int F) {
-    return (__float_as_uint(d) & 0x7F800000u) == 0x7F800000u ? 0ull : __double2ull_rn(ldexp((double)d, F));
-}
-
-// F = 63 - H - (2 E + 2 + log2 k) from fbase = 63 - H - 2 - log2 k and the maximum's bits
-__device__ __forceinline__ int tok_seed_f(int fbase, uint32_t amax_bits) { return fbase - 2 * (31 - tok_shift(amax_bits)); }
-
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// inclusive scan over the workgroup's threads in thread order; sh: one u64 per wave
-__device__ __forceinline__ u64 block_scan_u64(u64 v, u64 *sh) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 up = __shfl_up(v, o, 64);
-        if (lane >= o) v += up;
-    }
-    if (lane == 63) sh[wave] = v;
-    __syncthreads();
-    u64 before = 0;
-    for (int w = 0; w < nw; ++w) before += w < wave ? sh[w] : 0ull;
-    __syncthreads();
-    return v + before;
-}
 
 template <int K>
 __global__ __launch_bounds__(TOK_THREADS) void tok_seed_sweep_kernel(TokStore st, int64_t n_seg, int step, int T, int64_t first,

@@ -194,12 +194,21 @@ def lib():
             raise HipLibraryMissing(
                 f'{LIB_PATH} not found: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                 f'(or `make -C {os.path.join(_PKG_DIR, "csrc")}`). There is no CPU / eager fallback.')
-        l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(l, name)  # AttributeError here = header/library mismatch: fail loudly
-            fn.restype, fn.argtypes = res, args
-        _lib = l
+        _lib = _typed(ctypes.CDLL(LIB_PATH), SIGNATURES)
     return _lib
+
+
+def _typed(l, table):
+    for name, (res, args) in table.items():
+        fn = getattr(l, name)  # AttributeError here = header/library mismatch: fail loudly
+        fn.restype, fn.argtypes = res, args
+    return l
+
+
+def bind(table):
+    """the loaded library with the entry points of a further table typed as well: a header of its own beside include/ecgvit_hip.h (the table's
+    module says which) -> the library object"""
+    return _typed(lib(), table)
 
 
 def check(rc, what):
@@ -216,12 +225,17 @@ class _Run:
     """`run.ecgvit_x(*args)`: call `lib().ecgvit_x(*args)` and raise what `check` raises, under the entry point's own name, for a non-zero
     status.  The function is taken from the library object at every call (tools/launch_trace.py swaps that object's attributes: they live in
     its `__dict__`, where `lib()` has put every name of SIGNATURES); the checked callable of a name is made once and then found as a plain
-    attribute, so a call costs what `check(l.ecgvit_x(...), 'x')` cost."""
+    attribute, so a call costs what `check(l.ecgvit_x(...), 'x')` cost.
+    `_Run(table, queries)`: the same for the entry points of another typed table (`bind`), which is typed on the library at first use."""
+
+    def __init__(self, table=None, queries=frozenset()):
+        self._table, self._queries = (SIGNATURES, _QUERIES) if table is None else (table, frozenset(queries))
 
     def __getattr__(self, name):
-        if name not in SIGNATURES or name in _QUERIES or SIGNATURES[name][0] is not c_int:
+        table = self._table
+        if name not in table or name in self._queries or table[name][0] is not c_int:
             raise AttributeError(f'{name}: not an entry point that returns a status (queries go through lib())')
-        fns = vars(lib())
+        fns = vars(lib() if table is SIGNATURES else bind(table))
 
         def call(*args):
             rc = fns[name](*args)

@@ -7,15 +7,24 @@ vocabulary.  There is no CPU fallback: host tensors raise.
 
 k-means++ seeding (the reference's default `init`) is a kernel pair too: `EcgTokenizer.kmeans_plusplus`, and `init=KMeansPlusPlus()` in `fit`.
 
+Scalable k-means++ (k-means||, Bahmani et al. 2012; what the reference's GPU backend asks cuML for as `init='scalable-k-means++'`) is
+`EcgTokenizer.kmeans_parallel` and `init=ScalableKMeansPlusPlus()` in `fit` (`csrc/tok_scalable.hip`, include/ecgvit_hip_tok_scalable.h): a
+few oversampling rounds over the store whatever the number of centres, then weighted k-means++ over the candidates.  It is the paper's
+algorithm under this project's integer rules, not cuML's random stream or its exact variant: parity with cuML is UNPINNED (cuML is not
+available to the tests), and the string stays refused.
+
 DBSCAN (the reference's `dbscan` clustering) runs on the device as well (`csrc/dbscan.hip`): `EcgTokenizer.segments`, `EcgTokenizer.dbscan`, and
 `method=Dbscan()` in `fit`.  Two all-pairs sweeps and a union-find over the core segments; the contract is in include/ecgvit_hip.h.
 
 Not built: `save` / pickling, the plots and the three clusterings that are sequential by construction (DESIGN.md says why).
 """
+import math
+from ctypes import POINTER, c_uint64
+
 import numpy as np
 import torch
 
-from . import hip
+from . import hip, tok_scalable_abi
 from .hip import lib, run, ptr, stream
 from .records import DeviceTables, check_device_store, select_records
 
@@ -23,6 +32,7 @@ SEGMENT_SIZES = (8, 16, 32)
 PADS = {'zero': 0, 'shift': 1}
 MAX_CLUSTERS = hip.TOK_MAX_CLUSTERS
 MAX_LOCAL_TRIALS = hip.TOK_MAX_LOCAL_TRIALS
+MAX_ROUNDS = tok_scalable_abi.MAX_ROUNDS     # oversampling rounds of the scalable seeding (csrc/tok_scalable.hip)
 SEED_SPAN = hip.TOK_SEED_SPAN        # consecutive positions of one lead per workgroup of the seeding's sweep (csrc/tokenize.hip)
 DBSCAN_TILE = hip.TOK_DBSCAN_TILE    # segments per LDS tile of a DBSCAN sweep's column side (csrc/dbscan.hip)
 DBSCAN_ROWS = {8: 1024, 16: 1024, 32: 512}      # rows per workgroup of a DBSCAN sweep, by k: 256 threads, four or two rows each
@@ -77,6 +87,50 @@ class KMeansPlusPlus:
         """the trials per centre for a table of V rows: sklearn's default rule, held to what the kernels take"""
         T = 2 + int(np.log(V)) if self.n_local_trials is None else int(self.n_local_trials)
         return min(T, MAX_LOCAL_TRIALS)
+
+
+def check_oversampling(oversampling_factor, n_rounds):
+    f = oversampling_factor
+    if isinstance(f, bool) or not isinstance(f, (int, float, np.integer, np.floating)) or not np.isfinite(f) or not f > 0:
+        raise ValueError(f'oversampling_factor = {f!r}: a finite positive number')
+    if isinstance(n_rounds, bool) or not isinstance(n_rounds, (int, np.integer)) or not 1 <= n_rounds <= MAX_ROUNDS:
+        raise ValueError(f'n_rounds = {n_rounds!r}: an int from 1 to {MAX_ROUNDS}')
+    return float(f), int(n_rounds)
+
+
+def scalable_cap(ell):
+    """the most rows one round appends: ell + 8 ceil(sqrt(ell)), eight standard deviations past the expected ell"""
+    return ell + 8 * (math.isqrt(ell - 1) + 1)
+
+
+class ScalableKMeansPlusPlus:
+    """`fit(..., cls_kwargs=dict(init=ScalableKMeansPlusPlus(), ...))`: every restart is seeded on the device by `EcgTokenizer.kmeans_parallel`'s
+    kernels: scalable k-means++ (k-means||, Bahmani et al. 2012) -- n_rounds sweeps that each take a segment with probability
+    min(1, ell q / pot), ell = ceil(oversampling_factor * n_clusters), then weighted greedy k-means++ over the candidates (n_local_trials as in
+    `KMeansPlusPlus`).  The defaults are cuML's oversampling_factor and the paper's five rounds.  An object, not the string: it is the paper's
+    algorithm under this project's integer rules, not cuML's random stream or its exact variant (parity with cuML is unpinned), and the
+    string `'scalable-k-means++'` stays refused."""
+
+    def __init__(self, oversampling_factor=2.0, n_rounds=5, n_local_trials=None):
+        self.n_local_trials = check_local_trials(n_local_trials)
+        self.oversampling_factor, self.n_rounds = check_oversampling(oversampling_factor, n_rounds)
+        self._cap = None      # the tests' override of `scalable_cap`
+
+    def __repr__(self):
+        return (f'{self.__class__.__qualname__}(oversampling_factor={self.oversampling_factor}, n_rounds={self.n_rounds}, '
+                f'n_local_trials={self.n_local_trials})')
+
+    trials = KMeansPlusPlus.trials
+
+    def plan(self, V):
+        """-> (T, R, ell, cap) for a table of V rows; the candidate table of 1 + R cap rows is held to the largest table here, on the host"""
+        ell = max(1, math.ceil(self.oversampling_factor * V))
+        cap = scalable_cap(ell) if self._cap is None else int(self._cap)
+        if cap < 1 or ell > MAX_CLUSTERS or 1 + self.n_rounds * cap > MAX_CLUSTERS:
+            raise ValueError(f'n_clusters = {V}, oversampling_factor = {self.oversampling_factor}, n_rounds = {self.n_rounds}: ell = {ell} segments '
+                             f'expected and at most {cap} appended per round make a candidate table of up to {1 + self.n_rounds * cap} rows; '
+                             f'a table holds at most {MAX_CLUSTERS}')
+        return self.trials(V), self.n_rounds, ell, cap
 
 
 def check_min_samples(min_samples):
@@ -264,6 +318,85 @@ class EcgTokenizer:
         """what one seeding takes from the generator, in this order: the first centre, then a (V - 1, T) block of uniforms"""
         first = int(rng.integers(total))
         return first, np.floor(rng.random((V - 1, T)) * 2.0 ** 53).astype(np.uint64)
+
+    def _seed_scalable(self, st, V, T, R, ell, cap, first, keys, u0, u53, ws=None, keep_amax=False):
+        """one scalable seeding, enqueued whole: -> (centres (V, k) f32, indices (V,) int64, cand_g and weights (1 + R cap,) int64, info, the
+        workspace), device tensors; only the first info[0] = n_c candidates count, and centres / indices are written only when n_c >= V (the
+        caller reads `info`).  keys: (R,) uint64 and u0 < 2^53 on the host; u53: (V - 1, T) uint64 host array"""
+        dev = st.x.device
+        nbytes = tok_scalable_abi.lib().ecgvit_tok_scalable_workspace(st.C, st.n_seg, V, st.k, T, R, cap)
+        if nbytes == 0:
+            raise ValueError(f'a scalable seeding of {V} centres with {T} trials, {R} rounds of at most {cap} rows over {st.C} x {st.n_seg} segments '
+                             f'is not supported (1 to {MAX_LOCAL_TRIALS} trials, 1 to {MAX_ROUNDS} rounds, at most {MAX_CLUSTERS} candidate rows, '
+                             f'n_clusters at most the segment count, fewer than 2^32 segments)')
+        if ws is None:
+            ws, keep_amax = torch.empty(nbytes // 8, dtype=torch.int64, device=dev), False
+        u53 = np.ascontiguousarray(u53, np.uint64).reshape(V - 1, T)
+        keys = np.ascontiguousarray(keys, np.uint64).reshape(R)
+        if (u53.size and int(u53.max()) >= 2 ** 53) or not 0 <= int(u0) < 2 ** 53:
+            raise ValueError('u0 and u53 hold floor(u 2^53) of uniform draws u in [0, 1)')
+        u_d = torch.from_numpy(u53.view(np.int64).reshape(-1).copy()).to(dev) if u53.size else None
+        rows = 1 + R * cap
+        centers = torch.zeros((V, st.k), dtype=torch.float32, device=dev)
+        indices = torch.zeros(V, dtype=torch.int64, device=dev)
+        cand_g = torch.zeros(rows, dtype=torch.int64, device=dev)
+        weights = torch.empty(rows, dtype=torch.int64, device=dev)
+        info = torch.empty(tok_scalable_abi.info_words(R), dtype=torch.int64, device=dev)
+        tok_scalable_abi.run.ecgvit_tok_scalable_seed(*st.args(), st.pad, V, T, R, ell, cap, int(first), keys.ctypes.data_as(POINTER(c_uint64)),
+                                                      int(u0), ptr(u_d), ptr(centers), ptr(indices), ptr(cand_g), ptr(weights), ptr(info), ptr(ws),
+                                                      int(keep_amax), stream())
+        return centers, indices, cand_g, weights, info, ws
+
+    @staticmethod
+    def _scalable_draws(rng, total, V, T, R):
+        """what one scalable seeding takes from the generator, in this order: the first candidate, the R round keys, u0, then a (V - 1, T) block
+        of uniforms"""
+        first = int(rng.integers(total))
+        keys = rng.integers(0, 2 ** 64, size=R, dtype=np.uint64)
+        u0 = int(np.floor(rng.random() * 2.0 ** 53))
+        return first, keys, u0, np.floor(rng.random((V - 1, T)) * 2.0 ** 53).astype(np.uint64)
+
+    @staticmethod
+    def _scalable_info(info, init, V):
+        """the one small read of a scalable seeding -> (n_c, selected (R,), truncated (R,), pots (R + 1,) uint64); too few candidates raise"""
+        h = info.cpu().numpy().view(np.uint64)
+        R, H = init.n_rounds, tok_scalable_abi.INFO_HEAD
+        n_c = int(h[0])
+        if n_c < V:
+            raise ValueError(f'the scalable seeding ended with n_c = {n_c} candidates, fewer than n_clusters = {V}: raise n_rounds = {R} or '
+                             f'oversampling_factor = {init.oversampling_factor} (a store with fewer than {V} distinct segments has no such seeding)')
+        return n_c, h[H:H + R].astype(np.int64), h[H + R:H + 2 * R].astype(np.int64), h[H + 2 * R:H + 3 * R + 1].copy()
+
+    def kmeans_parallel(self, sigs, n_clusters, random_state=None, oversampling_factor=2.0, n_rounds=5, n_local_trials=None, offsets=None,
+                        idxs=None, return_info=False, _cap=None):
+        """Scalable k-means++ (k-means||, Bahmani et al. 2012) over the mean-removed segments of a store `fit` takes -> (centers (V, k) f32,
+        indices (V,) int64), numpy arrays, as `kmeans_plusplus` returns them.  n_rounds sweeps whatever V is: each round takes segment g with
+        probability min(1, ell q(g) / pot), ell = ceil(oversampling_factor * V), from a counter-based generator keyed per round; the candidates
+        are weighted by the segments nearest to them and reclustered by weighted greedy k-means++ (n_local_trials as in `kmeans_plusplus`).
+        The contract, every integer rule included: include/ecgvit_hip_tok_scalable.h.  It is the paper's algorithm, not cuML's random stream
+        or its exact variant: parity with the reference's cuML backend is unpinned.
+        `random_state` seeds `np.random.default_rng` (a Generator is used as it is), which gives, in this order: the first candidate, the
+        n_rounds keys (uint64), u0 for the first centre, then (V - 1, n_local_trials) uniforms.
+        return_info: also a dict -- cand_g (n_c,) the candidates' segments in table order, weights (n_c,), selected / truncated (n_rounds,) the
+        segments each round's rule took and how many of them the per-round cap dropped, pots (n_rounds,) uint64 the potential each round drew
+        under, potential: the one after the last fold.  Fewer candidates than n_clusters is a ValueError."""
+        V = int(n_clusters)
+        if not 1 <= V <= MAX_CLUSTERS:
+            raise ValueError(f'n_clusters = {V}: 1 to {MAX_CLUSTERS} are supported')
+        init = ScalableKMeansPlusPlus(oversampling_factor, n_rounds, n_local_trials)
+        init._cap = _cap
+        T, R, ell, cap = init.plan(V)
+        st = self._record_store(sigs, offsets, idxs, n_clusters=V)
+        rng = np.random.default_rng(random_state)
+        with torch.cuda.device(sigs.device):
+            first, keys, u0, u53 = self._scalable_draws(rng, st.C * st.n_seg, V, T, R)
+            centers, indices, cand_g, weights, info, _ = self._seed_scalable(st, V, T, R, ell, cap, first, keys, u0, u53)
+            n_c, selected, truncated, pots = self._scalable_info(info, init, V)
+            out = centers.cpu().numpy(), indices.cpu().numpy()
+            if return_info:
+                out += (dict(cand_g=cand_g[:n_c].cpu().numpy(), weights=weights[:n_c].cpu().numpy(), selected=selected, truncated=truncated,
+                             pots=pots[:R], potential=int(pots[R])),)
+            return out
 
     def kmeans_plusplus(self, sigs, n_clusters, random_state=None, n_local_trials=None, offsets=None, idxs=None):
         """`sklearn.cluster.kmeans_plusplus` over the mean-removed segments of a store `fit` takes -> (centers (V, k) f32, indices (V,) int64),
@@ -493,7 +626,8 @@ class EcgTokenizer:
         `idxs` selects records without a copy (the record-store convention of `records.py`).
         cls_kwargs: n_clusters (required), max_iter=256, n_init=1, random_state=None, init='random' (n_clusters distinct segments drawn by a
         seeded host generator), a `KMeansPlusPlus()` object (every restart seeded on the device, `kmeans_plusplus`; with n_init=8 the
-        reference's default configuration) or a (n_clusters, k) array (Lloyd from a given start is deterministic).  Lloyd iterations are assign then update;
+        reference's default configuration), a `ScalableKMeansPlusPlus()` object (every restart seeded on the device by `kmeans_parallel`: a few
+        sweeps whatever n_clusters is; the algorithm the reference's cuML backend names, parity with cuML unpinned) or a (n_clusters, k) array (Lloyd from a given start is deterministic).  Lloyd iterations are assign then update;
         they stop when an iteration changes no id, or at max_iter; n_init > 1 keeps the run of lowest inertia.  A centre that loses every
         segment keeps its value with size 0.  Label order is the clustering's own, as in the reference; nothing is reordered.
         method=Dbscan(min_samples=5) with cls_kwargs=dict(eps=..., min_samples=...): DBSCAN instead (`dbscan`), with the reference's
@@ -517,18 +651,20 @@ class EcgTokenizer:
             raise ValueError(f'n_clusters = {V}: 1 to {MAX_CLUSTERS} are supported')
         if max_iter < 1 or n_init < 1:
             raise ValueError('max_iter and n_init must be at least 1')
-        fixed = plus = None
+        fixed = plus = scalable = None
         if isinstance(init, str):
             if init != 'random':
                 raise NotImplementedError(f"init = {init!r}: 'random', a KMeansPlusPlus() object (k-means++ seeding on the device: sklearn's algorithm, "
                                           f"not the random stream the string promises) or a (n_clusters, k) array are supported")
+        elif isinstance(init, ScalableKMeansPlusPlus):
+            scalable = init.plan(V)
         elif isinstance(init, KMeansPlusPlus):
             plus = init.trials(V)
         else:
             fixed = np.ascontiguousarray(init.detach().cpu().numpy() if isinstance(init, torch.Tensor) else init, dtype=np.float32)
             if fixed.shape != (V, self.k):
                 raise ValueError(f'init must be ({V}, {self.k}), got {fixed.shape}')
-        st = self._record_store(sigs, offsets, idxs, n_clusters=V if plus else None)
+        st = self._record_store(sigs, offsets, idxs, n_clusters=V if plus or scalable else None)
         rng = np.random.default_rng(kw['random_state'])
         best = seed_ws = None
         with torch.cuda.device(sigs.device):
@@ -538,10 +674,16 @@ class EcgTokenizer:
                 if plus:                # the table stays on the device; the seeding's sweep for the absolute maximum serves every update too
                     first, u53 = self._seed_draws(rng, st.C * st.n_seg, V, plus)
                     table, _, _, seed_ws = self._seed(st, V, plus, first, u53, ws=seed_ws, keep_amax=seed_ws is not None)
-                    if not ws_state['amax']:
-                        ws[-2:].copy_(seed_ws[:2])
-                        ws_state['amax'] = True
-                else:
+                elif scalable:          # the same sharing: both seedings keep the maximum in the first 16 bytes of their workspace
+                    T, R, ell, cap = scalable
+                    first, keys, u0, u53 = self._scalable_draws(rng, st.C * st.n_seg, V, T, R)
+                    table, _, _, _, info, seed_ws = self._seed_scalable(st, V, T, R, ell, cap, first, keys, u0, u53, ws=seed_ws,
+                                                                        keep_amax=seed_ws is not None)
+                    self._scalable_info(info, init, V)
+                if (plus or scalable) and not ws_state['amax']:
+                    ws[-2:].copy_(seed_ws[:2])
+                    ws_state['amax'] = True
+                if not (plus or scalable):
                     table = torch.from_numpy(fixed.copy()).to(sigs.device) if fixed is not None else self._random_init(st, V, rng)
                 run = self._lloyd(st, table, max_iter, ws, ws_state)
                 if best is None or run[2] < best[2]:

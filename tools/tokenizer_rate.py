@@ -16,7 +16,15 @@ Writes profiles/r19_tokenizer.txt (--out).
   (f) `sklearn.cluster.kmeans_plusplus` on the host at a size the host finishes (2 M segments, V = 256, f64) against the device on the same
       segments (skipped when sklearn is absent).
 Writes profiles/r25_tokenizer_seed.txt (--out).
-usage: python tools/tokenizer_rate.py [--reps 3] [--records 21837] [--seed]"""
+--scalable: the scalable k-means++ seeding (ecgvit_tok_scalable_seed, csrc/tok_scalable.hip) on the same store at the same two shapes, with the
+  defaults of `ScalableKMeansPlusPlus` (oversampling factor 2, five rounds, sklearn's T):
+  (g) a whole seeding (event-timed, the sweep for the maximum included), and the time of its folds, selections (count, scan, scatter), weights
+      pass and recluster from the kernel durations torch.profiler records for that run;
+  (h) the `KMeansPlusPlus` seeding re-measured in the same run, on the same store with the same T;
+  (i) the full-store potential of each seeding (the sum of the f32 distances `ecgvit_tok_assign` reports under its centres) and the inertia
+      after ten Lloyd iterations from each.
+Writes profiles/r27_tokenizer_scalable.txt (--out).
+usage: python tools/tokenizer_rate.py [--reps 3] [--records 21837] [--seed | --scalable]"""
 import argparse
 import os
 import sys
@@ -66,6 +74,81 @@ def kernel_split(fn):
     except Exception as e:          # a profiler that cannot attach is no reason to lose the table
         print(f'torch.profiler: {e!r}', flush=True)
         return {}
+
+
+def kernel_totals(fn, groups):
+    """{group: (launches, ms in all)} over one call of fn for {group: kernel-name stems}, from torch.profiler's device events; {} where it
+    records none"""
+    from torch.profiler import profile, ProfilerActivity
+    try:
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        out = {}
+        for ev in prof.key_averages():
+            total = getattr(ev, 'device_time_total', 0) or getattr(ev, 'cuda_time_total', 0)
+            for group, stems in groups.items():
+                if any(stem in ev.key for stem in stems) and ev.count and total:
+                    n, t = out.get(group, (0, 0.0))
+                    out[group] = (n + ev.count, t + total / 1e3)
+        return out
+    except Exception as e:          # a profiler that cannot attach is no reason to lose the table
+        print(f'torch.profiler: {e!r}', flush=True)
+        return {}
+
+
+def scalable_table(a, x, lines):
+    groups = dict(fold=('kmpar_fold_kernel', 'kmpar_pot_kernel'), select=('kmpar_select_',), weights=('kmpar_weights_kernel',),
+                  recluster=('kmpar_recluster_kernel',), maximum=('tok_amax_kernel', 'kmpar_init_kernel'))
+    for k, V in ((8, 4096), (16, 1024)):
+        tok = E.EcgTokenizer(k=k, pad='shift')
+        st = tok._record_store(x, None, None)
+        nseg = st.C * st.n_seg
+        init = E.ScalableKMeansPlusPlus()
+        T, R, ell, cap = init.plan(V)
+        ids, means, dist = st.new(torch.int32), st.new(torch.float32), st.new(torch.float32)
+        ws = torch.empty(lib().ecgvit_tok_workspace(V, k) // 8, dtype=torch.int64, device='cuda')
+        got = {}
+
+        def scalable():
+            first, keys, u0, u53 = tok._scalable_draws(np.random.default_rng(27), nseg, V, T, R)
+            got['s'] = tok._seed_scalable(st, V, T, R, ell, cap, first, keys, u0, u53)
+
+        def plus():
+            first, u53 = tok._seed_draws(np.random.default_rng(27), nseg, V, T)
+            got['p'] = tok._seed(st, V, T, first, u53)
+
+        def quality(table):
+            """-> (the seeding's full-store potential, the inertia after ten Lloyd iterations from it)"""
+            tok._assign(st, table, ids, means, dist=dist)
+            pot = float(dist.sum(dtype=torch.float64))
+            table, _, _, _ = tok._lloyd(st, table.clone(), 10, ws, dict(amax=False))
+            tok._assign(st, table, ids, means, dist=dist)
+            return pot, float(dist.sum(dtype=torch.float64))
+        small = tok._record_store(x[:64], None, None)                 # warm-up: every kernel of both seedings once, at a small size
+        f_, k_, u0_, u_ = tok._scalable_draws(np.random.default_rng(1), small.C * small.n_seg, 64, 6, R)
+        tok._seed_scalable(small, 64, 6, R, 128, 224, f_, k_, u0_, u_)
+        tok._seed(small, 64, 6, *tok._seed_draws(np.random.default_rng(1), small.C * small.n_seg, 64, 6))
+        t_runs = [timed(scalable, 1, warmup=0) for _ in range(2)]      # twice: the spread of a run beside the difference the table reports
+        t_s = min(t_runs)
+        n_c, selected, truncated, _ = tok._scalable_info(got['s'][4], init, V)
+        split = kernel_totals(scalable, groups)
+        t_p = timed(plus, 1, warmup=0)
+        pot_s, inertia_s = quality(got['s'][0])
+        pot_p, inertia_p = quality(got['p'][0])
+        lines.append(f'(g) k = {k}, V = {V}, T = {T}, ell = {ell}, {R} rounds, cap {cap}: {nseg} segments')
+        lines.append(f'    scalable seeding, whole  {t_s / 1e3:10.3f} s   (the faster of two runs: {", ".join(f"{t / 1e3:.3f}" for t in t_runs)} s; selected per round {selected.tolist()}, dropped at the cap {truncated.tolist()}, '
+                     f'{n_c} candidates)')
+        if split:
+            lines.append('    its kernels (torch.profiler, a second run): ' + ', '.join(
+                f'{g} {split[g][1] / 1e3:.3f} s in {split[g][0]} launches' for g in groups if g in split))
+        else:
+            lines.append('    its kernels              not taken: torch.profiler recorded no kernel of the seeding')
+        lines.append(f'(h) KMeansPlusPlus seeding   {t_p / 1e3:10.3f} s   = {t_p / V:8.3f} ms per centre (one run, the same store and T); scalable = x {t_s / t_p:.3f} of it')
+        lines.append(f'(i) full-store potential     scalable {pot_s:.6e}, k-means++ {pot_p:.6e} (ratio {pot_s / pot_p:.4f}); inertia after ten Lloyd iterations '
+                     f'scalable {inertia_s:.6e}, k-means++ {inertia_p:.6e} (ratio {inertia_s / inertia_p:.4f})')
+        print('\n'.join(lines[-5:]), flush=True)
+        del ids, means, dist, got
 
 
 def seed_table(a, x, lines):
@@ -127,9 +210,12 @@ def main():
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--records', type=int, default=21837)
     ap.add_argument('--seed', action='store_true', help='time the k-means++ seeding instead (profiles/r25_tokenizer_seed.txt)')
+    ap.add_argument('--scalable', action='store_true', help='time the scalable k-means++ seeding instead (profiles/r27_tokenizer_scalable.txt)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, 'profiles', 'r25_tokenizer_seed.txt' if a.seed else 'r19_tokenizer.txt')
+    if a.seed and a.scalable:
+        ap.error('--seed and --scalable are tables of their own: one at a time')
+    a.out = a.out or os.path.join(ROOT, 'profiles', 'r27_tokenizer_scalable.txt' if a.scalable else 'r25_tokenizer_seed.txt' if a.seed else 'r19_tokenizer.txt')
     import bench
     n = a.records
     g = torch.Generator(device='cuda').manual_seed(19)
@@ -138,7 +224,10 @@ def main():
              f'store: {n} x {C} x {L} f32 = {x.numel() * 4 / 1e9:.2f} GB, N(0.3, 0.7^2); {a.reps} launches after one warm-up']
     if a.seed:
         seed_table(a, x, lines)
-    for k, V in (() if a.seed else ((8, 4096), (16, 1024))):
+    if a.scalable:
+        lines[-1] = lines[-1].replace(f'{a.reps} launches after one warm-up', 'every seeding timed once, after a warm-up of its kernels on 64 records')
+        scalable_table(a, x, lines)
+    for k, V in (() if a.seed or a.scalable else ((8, 4096), (16, 1024))):
         tok = E.EcgTokenizer(k=k, pad='shift')
         st = tok._record_store(x, None, None)
         nseg = st.C * st.n_seg
