@@ -171,6 +171,61 @@ class HipEncoder:
         return out
 
 
+class HipKnnProbe:
+    """The weighted k-NN probe: a training-free score of an encoder.  The bank records' pooled representations (`HipEncoder`) are the bank;
+    every evaluation record votes with the labels of its k nearest bank records under the cosine metric, weighted by
+    exp((s_j - s_0) / temperature) (weights='softmax') or equally ('uniform').  The (Q, K) result, the weighted share of the neighbours that
+    carry each label (the multi-label form), goes to `eval_counts(..., from_logits=False)` as probabilities.  k = 20 and temperature = 0.07
+    are those of the usual weighted k-NN protocol (Wu et al., "Unsupervised Feature Learning via Non-Parametric Instance Discrimination",
+    CVPR 2018).  No optimiser runs: the price is one `encode` pass over both sets, a search (`knn.KnnIndex`) and a vote."""
+
+    def __init__(self, model, k=20, temperature=0.07, weights='softmax', batch_size=64, pool='cls', norm=True, id2code=None):
+        from . import knn
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= knn.knn_abi.MAX_K:
+            raise ValueError(f'k must be an integer in [1, {knn.knn_abi.MAX_K}], got {k!r}')
+        if weights not in knn.WEIGHTS:
+            raise ValueError(f'weights must be one of {knn.WEIGHTS}, got {weights!r}')
+        if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not 0 < temperature < float('inf'):
+            raise ValueError(f'temperature must be a positive finite number, got {temperature!r}')
+        self.model, self.k, self.temperature, self.weights, self.id2code = model, k, float(temperature), weights, id2code
+        self.encoder = HipEncoder(model, batch_size=batch_size, pool=pool, norm=norm)
+
+    def _encode(self, *sets):
+        # (`EcgVit.encode` is an eval pass under no_grad whatever `model.training` says, and leaves the flag as it was)
+        return [self.encoder.encode(x, lengths=ls) for x, ls in sets]
+
+    def _score(self, index, feats, labels_bank, labels_query, exclude_self, return_predictions):
+        from . import knn
+        for t, name in ((labels_bank, 'bank_y'), (labels_query, 'query_y')):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+                raise ValueError(f'{name} must be a 2-d float32 tensor')
+        if labels_bank.shape[0] != index.N:
+            raise ValueError(f'bank_y has {labels_bank.shape[0]} rows, the bank has {index.N} records')
+        if labels_query.shape != (feats.shape[0], labels_bank.shape[1]):
+            raise ValueError(f'query_y must be {(feats.shape[0], labels_bank.shape[1])}, got {tuple(labels_query.shape)}')
+        scores, indices = index.search(feats, self.k, exclude_self=exclude_self)
+        probs = index.vote(scores, indices, labels_bank, weights=self.weights, temperature=self.temperature)
+        m = eval_counts(probs, labels_query.contiguous(), from_logits=False, return_auc=True, id2code=self.id2code).result()
+        d = {f'knn/{key}': v for key, v in m.items()}
+        if return_predictions:
+            return dict(metrics=d, predictions=dict(labels=labels_query, probabilities=probs, scores=scores, indices=indices))
+        return d
+
+    def evaluate(self, bank_x, bank_y, query_x, query_y, bank_lengths=None, query_lengths=None, return_predictions=False):
+        """bank_x / query_x with their lengths: as `HipEncoder.encode` takes them (a rectangle, a rectangle with lengths, a ragged (C, S)
+        batch, raw records under a per-record input transform); bank_y (N, K), query_y (Q, K) f32 multi-hot labels on the device.
+        Returns the keys of `get_accuracy` under the `knn/` prefix (return_predictions: dict(metrics=..., predictions=...))."""
+        from . import knn
+        fb, fq = self._encode((bank_x, bank_lengths), (query_x, query_lengths))
+        return self._score(knn.KnnIndex(fb, metric='cosine'), fq, bank_y, query_y, False, return_predictions)
+
+    def leave_one_out(self, x, y, lengths=None, return_predictions=False):
+        """`evaluate` with the set as its own bank: record r never receives itself (by index: a duplicate of it is still a neighbour)"""
+        from . import knn
+        f, = self._encode((x, lengths))
+        return self._score(knn.KnnIndex(f, metric='cosine'), f, y, y, True, return_predictions)
+
+
 class HipRollout:
     """Attention maps of a resident data set (`EcgVit.attention_rollout_batch`), `batch_size` records per pass: what the reference derives one
     record at a time for the low / median / high-loss records of an evaluation (models/evaluate.py:31-55), for as many records as are asked."""
