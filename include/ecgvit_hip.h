@@ -202,7 +202,9 @@ int ecgvit_layernorm_fwd(const void *x, const float *gamma, const float *beta, v
                          int64_t rows, int d, float eps, int dtype, void *stream);
 /* fp8 operand path: the same forward (bf16, d in 64 * {4, 8, 12, 16, 24, 32}) that also writes y8 = saturate(y / *q8_scale) in e4m3 and
  * accumulates *q8_amax = max(*q8_amax, max |y|): the 8-bit operand of the next Linear's product, without a quantise pass over y.
- * y may be NULL (ABI 5): only y8 / mean / rstd are written -- for a step in which every consumer of y reads the 8-bit copy */
+ * y may be NULL (ABI 5): only y8 / mean / rstd are written -- for a step in which every consumer of y reads the 8-bit copy.
+ * mean, rstd and y meet the accuracy of ecgvit_layernorm_fwd but need not have its bits: the emitting kernel is an instantiation of its own whose
+ * multiply-adds the compiler fuses differently, so rstd, and with it a few y per million, may differ in the last place (tests/test_gpu_layernorm.py) */
 int ecgvit_layernorm_fwd_q8(const void *x, const float *gamma, const float *beta, void *y, float *mean, float *rstd,
                             int64_t rows, int d, float eps, void *y8, const float *q8_scale, float *q8_amax, void *stream);
 /* dx = (dres ? dres : 0) + LN'(dy) ; dgamma/dbeta are OVERWRITTEN with the full reduction over rows.
