@@ -76,8 +76,11 @@ class HipEvaluator:
     def __init__(self, model, eval_batch_size=64, id2code=None, gather=False, process_group=None):
         self.model, self.bsz, self.id2code, self.gather, self.pg = model, int(eval_batch_size), id2code, gather, process_group
 
-    def evaluate(self, sample_values, labels, return_predictions=False, lengths=None):
-        """sample_values: (n, C, L) f32 device tensor (this rank's shard), labels: (n, K) f32; lengths: optional (n,) per-record sample
+    def evaluate(self, sample_values, labels, return_predictions=False, lengths=None, bootstrap=None):
+        """bootstrap: None, or an int (replicates) or a dict of `rank_metrics.bootstrap_auc`'s keywords (n_boot, seed, indices, workspace_bytes):
+        adds `eval/macro_auc_ci` and `eval/per_class_auc_ci`, the 95 % percentile intervals over the resampled whole set (every rank of a
+        gathered evaluation holds the whole set and draws the same replicates from the same seed), and `bootstrap` under `predictions`.
+        sample_values: (n, C, L) f32 device tensor (this rank's shard), labels: (n, K) f32; lengths: optional (n,) per-record sample
         counts (EcgVit.forward), sliced with the batches.  A ragged (C, S) batch with its (n,) lengths is cut by record range: eval_batch_size
         records per call, each a ragged batch of its own.  Under a per-record input transform sample_values holds RAW records and lengths their
         raw sample counts (the ragged form is then cut at the raw offsets); evaluation draws no TimeOut."""
@@ -128,9 +131,21 @@ class HipEvaluator:
             loss = wsum / cnt[0]
         m = eval_counts(logits, lb.contiguous(), from_logits=True, return_auc=True, id2code=self.id2code).result()
         d = {'eval/loss': float(loss), **{f'eval/{k}': v for k, v in m.items()}}
+        pred = dict(labels=lb, logits=logits)
+        _add_bootstrap(d, pred, 'eval', bootstrap, logits, lb.contiguous(), True, self.id2code)
         if training:
             model.train()
-        return dict(metrics=d, predictions=dict(labels=lb, logits=logits)) if return_predictions else d
+        return dict(metrics=d, predictions=pred) if return_predictions else d
+
+
+def _add_bootstrap(d, predictions, prefix, bootstrap, scores, labels, from_logits, id2code):
+    """the interval keys of an evaluation that asked for them; with bootstrap=None nothing is added and nothing is launched"""
+    if bootstrap is None:
+        return
+    from . import rank_metrics
+    res = rank_metrics.evaluator_bootstrap(bootstrap, scores, labels, from_logits, id2code)
+    d[f'{prefix}/macro_auc_ci'], d[f'{prefix}/per_class_auc_ci'] = rank_metrics.intervals(res)
+    predictions['bootstrap'] = res
 
 
 class HipEncoder:
@@ -194,7 +209,7 @@ class HipKnnProbe:
         # (`EcgVit.encode` is an eval pass under no_grad whatever `model.training` says, and leaves the flag as it was)
         return [self.encoder.encode(x, lengths=ls) for x, ls in sets]
 
-    def _score(self, index, feats, labels_bank, labels_query, exclude_self, return_predictions):
+    def _score(self, index, feats, labels_bank, labels_query, exclude_self, return_predictions, bootstrap=None):
         from . import knn
         for t, name in ((labels_bank, 'bank_y'), (labels_query, 'query_y')):
             if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
@@ -207,23 +222,24 @@ class HipKnnProbe:
         probs = index.vote(scores, indices, labels_bank, weights=self.weights, temperature=self.temperature)
         m = eval_counts(probs, labels_query.contiguous(), from_logits=False, return_auc=True, id2code=self.id2code).result()
         d = {f'knn/{key}': v for key, v in m.items()}
-        if return_predictions:
-            return dict(metrics=d, predictions=dict(labels=labels_query, probabilities=probs, scores=scores, indices=indices))
-        return d
+        pred = dict(labels=labels_query, probabilities=probs, scores=scores, indices=indices)
+        _add_bootstrap(d, pred, 'knn', bootstrap, probs, labels_query.contiguous(), False, self.id2code)
+        return dict(metrics=d, predictions=pred) if return_predictions else d
 
-    def evaluate(self, bank_x, bank_y, query_x, query_y, bank_lengths=None, query_lengths=None, return_predictions=False):
+    def evaluate(self, bank_x, bank_y, query_x, query_y, bank_lengths=None, query_lengths=None, return_predictions=False, bootstrap=None):
         """bank_x / query_x with their lengths: as `HipEncoder.encode` takes them (a rectangle, a rectangle with lengths, a ragged (C, S)
         batch, raw records under a per-record input transform); bank_y (N, K), query_y (Q, K) f32 multi-hot labels on the device.
-        Returns the keys of `get_accuracy` under the `knn/` prefix (return_predictions: dict(metrics=..., predictions=...))."""
+        Returns the keys of `get_accuracy` under the `knn/` prefix (return_predictions: dict(metrics=..., predictions=...)).
+        bootstrap: as `HipEvaluator.evaluate` takes it, over the query records: adds `knn/macro_auc_ci` and `knn/per_class_auc_ci`."""
         from . import knn
         fb, fq = self._encode((bank_x, bank_lengths), (query_x, query_lengths))
-        return self._score(knn.KnnIndex(fb, metric='cosine'), fq, bank_y, query_y, False, return_predictions)
+        return self._score(knn.KnnIndex(fb, metric='cosine'), fq, bank_y, query_y, False, return_predictions, bootstrap)
 
-    def leave_one_out(self, x, y, lengths=None, return_predictions=False):
+    def leave_one_out(self, x, y, lengths=None, return_predictions=False, bootstrap=None):
         """`evaluate` with the set as its own bank: record r never receives itself (by index: a duplicate of it is still a neighbour)"""
         from . import knn
         f, = self._encode((x, lengths))
-        return self._score(knn.KnnIndex(f, metric='cosine'), f, y, y, True, return_predictions)
+        return self._score(knn.KnnIndex(f, metric='cosine'), f, y, y, True, return_predictions, bootstrap)
 
 
 class HipRollout:

@@ -1,0 +1,243 @@
+"""
+Rank-based AUROC and bootstrap confidence intervals on the device (`include/ecgvit_hip_rank.h` states the contract, `csrc/rank_metrics.hip`
+holds the kernels).
+
+`metrics.eval_counts` gets a class's AUROC from all (positive, negative) pairs, O(n^2 K).  Here every class column is sorted once (a stable
+radix sort of (key, record index)); a weighted prefix sum over the sorted order then gives the very integer the all-pairs kernel leaves in its
+pair slot, and, with a replicate's multiplicities as the weights, the integer behind `roc_auc_score(sample_weight=multiplicities)` -- which is
+the reference's `get_accuracy(preds[idx], labels[idx])` on the resample `idx`.  The device returns (R, K) triples (num2, wp, wn) of exact
+integers; the divisions and the percentiles are host f64, as in `DeviceCounts.result`.
+
+A replicate holding only one label value of a class is invalid for that class (the reference's own `msk_2_class` rule, util/train.py:29, applied
+to the resample): NaN in `per_class_auc`, left out of the replicate's macro average.  No class is redrawn and nothing is stratified.
+"""
+import warnings
+
+import numpy as np
+import torch
+
+from . import rank_abi
+from .hip import ptr, stream
+from .metrics import DeviceCounts
+from . import hip
+
+__all__ = ['RankedScores', 'BootstrapResult', 'rank_scores', 'auroc_counts', 'bootstrap_auc', 'draws', 'multiplicities']
+
+_M64 = (1 << 64) - 1
+_GAMMA = 0x9E3779B97F4A7C15
+DEFAULT_WORKSPACE_BYTES = 256 << 20   # multiplicities of one chunk of replicates
+
+
+def _check_pair(scores, labels):
+    """every refusal of a (scores, labels) pair, the device asked for last -> (n, K)"""
+    for t, name in ((scores, 'scores'), (labels, 'labels')):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f'{name} must be a torch tensor, got {type(t).__name__}')
+        if t.dtype != torch.float32:
+            raise ValueError(f'{name} must be float32, got {t.dtype}')
+        if t.dim() != 2:
+            raise ValueError(f'{name} must be (n, K), got {tuple(t.shape)}')
+    if scores.shape != labels.shape:
+        raise ValueError(f'labels must be {tuple(scores.shape)} as scores, got {tuple(labels.shape)}')
+    n, K = scores.shape
+    if n < 1 or K < 1:
+        raise ValueError(f'scores must hold at least one record and one class, got {tuple(scores.shape)}')
+    for t, name in ((scores, 'scores'), (labels, 'labels')):
+        if t.stride(1) != 1 and K > 1 or (n > 1 and t.stride(0) < K):
+            raise ValueError(f'{name} must have contiguous rows')
+    if n > rank_abi.MAX_ROWS:
+        raise ValueError(f'scores: n = {n} exceeds {rank_abi.MAX_ROWS}')
+    if K > rank_abi.MAX_CLASSES:
+        raise ValueError(f'scores: K = {K} exceeds {rank_abi.MAX_CLASSES}')
+    for t, name in ((scores, 'scores'), (labels, 'labels')):
+        if not t.is_cuda:
+            raise ValueError(f'{name} must be a device tensor (rank metrics run on the device: no CPU fallback exists)')
+    return n, K
+
+
+def _pitch(t):
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+class RankedScores:
+    """The sorted order of every class column: `packed` (K, n) int32 words (record index | label bit << 30 | last-of-tie-group bit << 31) and
+    `first_nan` (K,) int32, on the device."""
+
+    def __init__(self, packed, first_nan, scores, labels, from_logits):
+        self.packed, self.first_nan, self.from_logits = packed, first_nan, bool(from_logits)
+        self.K, self.n = packed.shape
+        self.scores, self.labels = scores, labels
+
+    def order(self, c):
+        """record indices of class c under (key ascending, record index ascending): (n,) int64 on the device"""
+        return (self.packed[c] & 0x3FFFFFFF).long()
+
+    def _walk(self, mult, R, out, pairs=None):
+        rank_abi.run.ecgvit_rank_walk(ptr(self.packed), ptr(self.first_nan), self.n, self.K, ptr(mult), R, ptr(out), ptr(pairs), stream())
+
+
+def rank_scores(scores, labels, from_logits=False) -> RankedScores:
+    """Sort every class column once (asynchronous).  scores / labels: (n, K) f32 device tensors with contiguous rows."""
+    n, K = _check_pair(scores, labels)
+    nbytes = rank_abi.lib().ecgvit_rank_workspace(n, K, 0)
+    if nbytes <= 0:
+        raise ValueError(f'scores: unsupported shape {(n, K)}')
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=scores.device)
+    packed = torch.empty(K, n, dtype=torch.int32, device=scores.device)
+    first_nan = torch.empty(K, dtype=torch.int32, device=scores.device)
+    rank_abi.run.ecgvit_rank_sort(ptr(scores), _pitch(scores), ptr(labels), _pitch(labels), n, K, int(bool(from_logits)), ptr(packed), ptr(first_nan),
+                                  ptr(ws), stream())
+    return RankedScores(packed, first_nan, scores, labels, from_logits)
+
+
+def _counts(ranked, id2code):
+    """the 4 + 2K layout of `eval_counts`: the confusion slots from `ecgvit_eval_counts` without its all-pairs kernel, the pair slots from the walk"""
+    s, y, n, K = ranked.scores, ranked.labels, ranked.n, ranked.K
+    counts = torch.empty(4 + 2 * K, dtype=torch.int64, device=s.device)
+    hip.run.ecgvit_eval_counts(ptr(s), _pitch(s), ptr(y), _pitch(y), n, K, int(ranked.from_logits), 0, ptr(counts), stream())
+    triples = torch.empty(1, K, 3, dtype=torch.int64, device=s.device)
+    ranked._walk(None, 1, triples, counts[4 + K:])
+    h = DeviceCounts(counts, n, K, True, id2code)
+    h._keep = (s, y, ranked, triples)
+    return h
+
+
+def auroc_counts(scores, labels, from_logits=False, id2code=None) -> DeviceCounts:
+    """`eval_counts(..., return_auc=True)` by the rank route: the same 4 + 2K integers, so `.result()` is the same dict."""
+    return _counts(rank_scores(scores, labels, from_logits), id2code)
+
+
+# ---- the generator, restated on the host (include/ecgvit_hip_rank.h) ---------------------------------------------------------------------
+def _mix(z):
+    z = np.asarray(z, dtype=np.uint64)
+    z = z ^ (z >> np.uint64(30))
+    z = z * np.uint64(0xBF58476D1CE4E5B9)
+    z = z ^ (z >> np.uint64(27))
+    z = z * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def draws(seed, replicate, n):
+    """the n draws of replicate `replicate` under `seed`, as the device makes them: (n,) int64 in [0, n)"""
+    with np.errstate(over='ignore'):
+        key = _mix(np.uint64((int(seed) + _GAMMA * (int(replicate) + 1)) & _M64))
+        u = _mix(key + np.uint64(_GAMMA) * np.arange(1, n + 1, dtype=np.uint64))
+        hi, lo = u >> np.uint64(32), u & np.uint64(0xFFFFFFFF)
+        return ((hi * np.uint64(n) + ((lo * np.uint64(n)) >> np.uint64(32))) >> np.uint64(32)).astype(np.int64)   # (u n) >> 64 for n < 2^32
+
+
+def multiplicities(seed, replicate, n):
+    return np.bincount(draws(seed, replicate, n), minlength=n).astype(np.int64)
+
+
+# ---- replicates ---------------------------------------------------------------------------------------------------------------------------
+class BootstrapResult:
+    """`point`: the `get_accuracy` dict of the whole set.  `triples`: (R, K, 3) int64 (num2, wp, wn) as the device left them.
+    `per_class_auc` (R, K) f64, NaN where the replicate holds one label value only; `macro_auc` (R,) the mean over the replicate's valid classes
+    (NaN: none); `n_valid` (K,) replicates in which the class is valid."""
+
+    def __init__(self, point, triples, id2code=None):
+        self.point, self.triples, self.id2code = point, triples, id2code
+        num2, wp, wn = (triples[..., i].astype(np.float64) for i in range(3))
+        valid = (triples[..., 1] > 0) & (triples[..., 2] > 0)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            self.per_class_auc = np.where(valid, num2 / (2.0 * wp * wn), np.nan)
+        cnt = valid.sum(axis=1)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            self.macro_auc = np.where(cnt > 0, np.where(valid, self.per_class_auc, 0.0).sum(axis=1) / cnt, np.nan)
+        self.n_valid = valid.sum(axis=0)
+
+    @staticmethod
+    def _alpha(alpha):
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0 < alpha < 1:
+            raise ValueError(f'alpha must be in (0, 1), got {alpha!r}')
+        return [100.0 * alpha / 2, 100.0 * (1 - alpha / 2)]
+
+    def ci(self, alpha=0.05):
+        """(lo, hi) of the macro AUROC: the alpha / 2 and 1 - alpha / 2 percentiles of the replicates that have a valid class"""
+        q = self._alpha(alpha)
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore', RuntimeWarning)
+            lo, hi = np.nanpercentile(self.macro_auc, q)
+        return float(lo), float(hi)
+
+    def class_ci(self, alpha=0.05):
+        """(K, 2) per-class (lo, hi) over the replicates in which the class is valid; NaN for a class that never is"""
+        q = self._alpha(alpha)
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore', RuntimeWarning)
+            return np.nanpercentile(self.per_class_auc, q, axis=0).T.copy()
+
+
+def _check_indices(indices, n):
+    """(R, n) integer draws, a torch tensor (host or device) or a numpy array -> the tensor; out-of-range draws are met here for a host array"""
+    if isinstance(indices, np.ndarray):
+        indices = torch.from_numpy(np.ascontiguousarray(indices))
+    if not isinstance(indices, torch.Tensor) or indices.dtype not in (torch.int64, torch.int32):
+        raise ValueError('indices must be an (R, n) int64 or int32 tensor or array')
+    if indices.dim() != 2 or indices.shape[1] != n or indices.shape[0] < 1:
+        raise ValueError(f'indices must be (R, {n}) with R >= 1, got {tuple(indices.shape)}')
+    if not indices.is_cuda and indices.device.type == 'cpu' and (int(indices.min()) < 0 or int(indices.max()) >= n):
+        raise ValueError(f'indices must lie in [0, {n}), got {int(indices.min())} .. {int(indices.max())}')
+    return indices
+
+
+def bootstrap_auc(scores, labels, n_boot=1000, seed=0, indices=None, from_logits=False, id2code=None, workspace_bytes=None) -> BootstrapResult:
+    """The point estimate and `n_boot` bootstrap replicates of the per-class and macro AUROC.
+    seed: the replicates' draws come from the device's counter-based generator (`draws` restates it); the same seed resamples two score sets
+    identically, whatever the chunking.  indices: (R, n) draws with replacement instead (host or device; R replaces n_boot): replicate b is then
+    `get_accuracy(preds[indices[b]], labels[indices[b]])`.  A seed other than 0 beside indices is refused.
+    workspace_bytes: bound on the multiplicity rows held at once (default 256 MiB); the replicates run in chunks of that many rows."""
+    if isinstance(n_boot, bool) or not isinstance(n_boot, int) or n_boot < 1:
+        raise ValueError(f'n_boot must be an integer >= 1, got {n_boot!r}')
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed <= _M64:
+        raise ValueError(f'seed must be an integer in [0, 2^64), got {seed!r}')
+    if indices is not None and seed != 0:
+        raise ValueError('seed and indices are both given: the draws come from one or the other')
+    if workspace_bytes is not None and (isinstance(workspace_bytes, bool) or not isinstance(workspace_bytes, int) or workspace_bytes < 1):
+        raise ValueError(f'workspace_bytes must be a positive integer, got {workspace_bytes!r}')
+    if isinstance(scores, torch.Tensor) and scores.dim() == 2 and indices is not None:
+        indices = _check_indices(indices, scores.shape[0])
+    R = n_boot if indices is None or not isinstance(indices, torch.Tensor) else indices.shape[0]
+    if R > rank_abi.MAX_REPLICATES:
+        raise ValueError(f'n_boot = {R} exceeds {rank_abi.MAX_REPLICATES}')
+    n, K = _check_pair(scores, labels)
+    quad = rank_abi.lib().ecgvit_rank_workspace(n, K, 4)   # the multiplicities are held four replicates wide
+    chunk = max(1, min(R, (DEFAULT_WORKSPACE_BYTES if workspace_bytes is None else workspace_bytes) // quad * 4))
+    ranked = rank_scores(scores, labels, from_logits)
+    point = _counts(ranked, id2code)
+    mult = torch.empty(n, (chunk + 3) // 4 * 4, dtype=torch.int32, device=scores.device)   # record-major; a shorter last chunk uses its head
+    triples = torch.empty(R, K, 3, dtype=torch.int64, device=scores.device)
+    for r0 in range(0, R, chunk):
+        rows = min(chunk, R - r0)
+        if indices is None:
+            rank_abi.run.ecgvit_rank_multiplicities_seeded(seed, r0, rows, n, ptr(mult), stream())
+        else:
+            idx = indices[r0:r0 + rows].to(device=scores.device, dtype=torch.int64).contiguous()
+            rank_abi.run.ecgvit_rank_multiplicities(ptr(idx), n, rows, n, ptr(mult), stream())
+        ranked._walk(mult, rows, triples[r0:r0 + rows])
+    res = BootstrapResult(point.result(), triples.cpu().numpy(), id2code)
+    res.chunk = chunk
+    return res
+
+
+def intervals(res, alpha=0.05):
+    """(macro (lo, hi), {class key of the point estimate: (lo, hi)} or None) for the evaluators' dicts"""
+    per = res.point['per_class_auc']
+    if per is None:
+        return res.ci(alpha), None
+    cc = res.class_ci(alpha)
+    keys = list(per)
+    cols = [k for k in range(cc.shape[0]) if (res.id2code[k] if res.id2code is not None else k) in per]
+    return res.ci(alpha), {key: (float(cc[k, 0]), float(cc[k, 1])) for key, k in zip(keys, cols)}
+
+
+def evaluator_bootstrap(bootstrap, scores, labels, from_logits, id2code):
+    """`bootstrap` of `HipEvaluator.evaluate` / `HipKnnProbe`: an int (n_boot) or a dict of `bootstrap_auc`'s keywords -> BootstrapResult"""
+    if isinstance(bootstrap, bool) or not isinstance(bootstrap, (int, dict)):
+        raise ValueError(f'bootstrap must be None, an integer or a dict of bootstrap_auc keywords, got {bootstrap!r}')
+    kw = dict(bootstrap) if isinstance(bootstrap, dict) else dict(n_boot=bootstrap)
+    bad = set(kw) - {'n_boot', 'seed', 'indices', 'workspace_bytes'}
+    if bad:
+        raise ValueError(f'bootstrap: unknown keywords {sorted(bad)}')
+    return bootstrap_auc(scores, labels, from_logits=from_logits, id2code=id2code, **kw)
