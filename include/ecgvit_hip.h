@@ -140,7 +140,9 @@ int64_t ecgvit_gemm_workspace(const ecgvit_gemm_desc *d);
 /* amax[s] = max(amax[s], max |x|) over bf16 x */
 int ecgvit_fp8_amax(const void *x, const int64_t *table, int nseg, int64_t count, float *amax, void *stream);
 /* y = saturate(x / scale[s]) in `format` (ECGVIT_FP8_E4M3 | ECGVIT_BF8_E5M2), one byte per element at the same element offsets;
- * amax_next (optional) accumulates max |x| per segment for the next step's scale (delayed scaling) */
+ * amax_next (optional) accumulates max |x| per segment for the next step's scale (delayed scaling).  Round to nearest even of x times the f32
+ * reciprocal of scale[s], +-inf and everything beyond +-max give +-max, a scale that is not positive gives zeros.  NaN input is outside the
+ * contract of every 8-bit emitter of this header: they clamp with a median and take the amax with fmaxf, neither of which propagates it */
 int ecgvit_fp8_quantize(const void *x, void *y, const int64_t *table, int nseg, int64_t count, int format, const float *scale,
                         float *amax_next, void *stream);
 /* scale[i] = amax[i] / FORMAT_MAX where amax[i] > 0 (else kept; 1.0 if never set); amax[i] = 0.  formats: per-entry, or NULL = format_all */
