@@ -18,10 +18,12 @@ from .knn import KnnIndex, knn_search, knn_merge
 from . import knn
 from .rank_metrics import rank_scores, auroc_counts, bootstrap_auc, RankedScores, BootstrapResult
 from . import rank_metrics
+from .pr_metrics import pr_walk, pr_counts, bootstrap_pr, paired_diff_ci, PrCounts, PrBootstrapResult
+from . import pr_metrics
 from .feed import DeviceFeeder, RaggedDeviceFeeder, ptbxl_splits, lbs2multi_hot, open_records
 from . import hip
 from . import ddp
 from . import workload
 
 __all__ = ['ca', 'CheckArg', 'EcgVitConfig', 'EcgVit', 'ModelOutput', 'RolloutOutput', 'HipViT', 'MaskedEcgVit', 'load_trained', 'get_train_args', 'lr_multiplier',
-           'HipTrainStep', 'HipProbeStep', 'clip_grad_norm_', 'FusedInputTransform', 'fit_dynamic_normalize', 'DynamicNormalizeFit', 'EcgTokenizer', 'KMeansPlusPlus', 'ScalableKMeansPlusPlus', 'Dbscan', 'EcgDenoiser', 'design_lowpass', 'rloess', 'lowpass', 'estimate_noise_std', 'nlm', 'denoise', 'resample', 'resampled_length', 'resample_plan', 'resample_chirp_length', 'resample_route', 'get_accuracy', 'eval_counts', 'HipEvaluator', 'HipEncoder', 'HipRollout', 'HipKnnProbe', 'KnnIndex', 'knn_search', 'knn_merge', 'knn', 'rank_scores', 'auroc_counts', 'bootstrap_auc', 'RankedScores', 'BootstrapResult', 'rank_metrics', 'DeviceFeeder', 'RaggedDeviceFeeder', 'ptbxl_splits', 'lbs2multi_hot', 'open_records', 'hip', 'ddp', 'workload']
+           'HipTrainStep', 'HipProbeStep', 'clip_grad_norm_', 'FusedInputTransform', 'fit_dynamic_normalize', 'DynamicNormalizeFit', 'EcgTokenizer', 'KMeansPlusPlus', 'ScalableKMeansPlusPlus', 'Dbscan', 'EcgDenoiser', 'design_lowpass', 'rloess', 'lowpass', 'estimate_noise_std', 'nlm', 'denoise', 'resample', 'resampled_length', 'resample_plan', 'resample_chirp_length', 'resample_route', 'get_accuracy', 'eval_counts', 'HipEvaluator', 'HipEncoder', 'HipRollout', 'HipKnnProbe', 'KnnIndex', 'knn_search', 'knn_merge', 'knn', 'rank_scores', 'auroc_counts', 'bootstrap_auc', 'RankedScores', 'BootstrapResult', 'rank_metrics', 'DeviceFeeder', 'RaggedDeviceFeeder', 'ptbxl_splits', 'lbs2multi_hot', 'open_records', 'hip', 'ddp', 'workload', 'pr_walk', 'pr_counts', 'bootstrap_pr', 'paired_diff_ci', 'PrCounts', 'PrBootstrapResult', 'pr_metrics']

@@ -76,10 +76,13 @@ class HipEvaluator:
     def __init__(self, model, eval_batch_size=64, id2code=None, gather=False, process_group=None):
         self.model, self.bsz, self.id2code, self.gather, self.pg = model, int(eval_batch_size), id2code, gather, process_group
 
-    def evaluate(self, sample_values, labels, return_predictions=False, lengths=None, bootstrap=None):
+    def evaluate(self, sample_values, labels, return_predictions=False, lengths=None, bootstrap=None, pr=False):
         """bootstrap: None, or an int (replicates) or a dict of `rank_metrics.bootstrap_auc`'s keywords (n_boot, seed, indices, workspace_bytes):
         adds `eval/macro_auc_ci` and `eval/per_class_auc_ci`, the 95 % percentile intervals over the resampled whole set (every rank of a
         gathered evaluation holds the whole set and draws the same replicates from the same seed), and `bootstrap` under `predictions`.
+        pr: True adds `eval/macro_ap`, `eval/per_class_ap`, `eval/macro_fmax`, `eval/per_class_fmax` and `eval/per_class_threshold`
+        (`pr_metrics.pr_counts`: average precision, the class-wise maximum of F1 over all thresholds, and the logit that attains it), and with
+        `bootstrap` their `_ci` keys over the same replicates (`bootstrap_pr` under `predictions`).  False: nothing is added or launched.
         sample_values: (n, C, L) f32 device tensor (this rank's shard), labels: (n, K) f32; lengths: optional (n,) per-record sample
         counts (EcgVit.forward), sliced with the batches.  A ragged (C, S) batch with its (n,) lengths is cut by record range: eval_batch_size
         records per call, each a ragged batch of its own.  Under a per-record input transform sample_values holds RAW records and lengths their
@@ -132,14 +135,20 @@ class HipEvaluator:
         m = eval_counts(logits, lb.contiguous(), from_logits=True, return_auc=True, id2code=self.id2code).result()
         d = {'eval/loss': float(loss), **{f'eval/{k}': v for k, v in m.items()}}
         pred = dict(labels=lb, logits=logits)
-        _add_bootstrap(d, pred, 'eval', bootstrap, logits, lb.contiguous(), True, self.id2code)
+        _add_bootstrap(d, pred, 'eval', bootstrap, logits, lb.contiguous(), True, self.id2code, pr)
         if training:
             model.train()
         return dict(metrics=d, predictions=pred) if return_predictions else d
 
 
-def _add_bootstrap(d, predictions, prefix, bootstrap, scores, labels, from_logits, id2code):
-    """the interval keys of an evaluation that asked for them; with bootstrap=None nothing is added and nothing is launched"""
+def _add_bootstrap(d, predictions, prefix, bootstrap, scores, labels, from_logits, id2code, pr=False):
+    """the interval keys of an evaluation that asked for them; with bootstrap=None nothing is added and nothing is launched.  pr: the keys of
+    average precision and F-max as well, and then the AUROC intervals come from the same sort and the same draws"""
+    if pr is not False:
+        if pr is not True:
+            raise ValueError(f'pr must be True or False, got {pr!r}')
+        from . import pr_metrics
+        return pr_metrics.add_keys(d, predictions, prefix, bootstrap, scores, labels, from_logits, id2code)
     if bootstrap is None:
         return
     from . import rank_metrics
@@ -209,7 +218,7 @@ class HipKnnProbe:
         # (`EcgVit.encode` is an eval pass under no_grad whatever `model.training` says, and leaves the flag as it was)
         return [self.encoder.encode(x, lengths=ls) for x, ls in sets]
 
-    def _score(self, index, feats, labels_bank, labels_query, exclude_self, return_predictions, bootstrap=None):
+    def _score(self, index, feats, labels_bank, labels_query, exclude_self, return_predictions, bootstrap=None, pr=False):
         from . import knn
         for t, name in ((labels_bank, 'bank_y'), (labels_query, 'query_y')):
             if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
@@ -223,23 +232,24 @@ class HipKnnProbe:
         m = eval_counts(probs, labels_query.contiguous(), from_logits=False, return_auc=True, id2code=self.id2code).result()
         d = {f'knn/{key}': v for key, v in m.items()}
         pred = dict(labels=labels_query, probabilities=probs, scores=scores, indices=indices)
-        _add_bootstrap(d, pred, 'knn', bootstrap, probs, labels_query.contiguous(), False, self.id2code)
+        _add_bootstrap(d, pred, 'knn', bootstrap, probs, labels_query.contiguous(), False, self.id2code, pr)
         return dict(metrics=d, predictions=pred) if return_predictions else d
 
-    def evaluate(self, bank_x, bank_y, query_x, query_y, bank_lengths=None, query_lengths=None, return_predictions=False, bootstrap=None):
+    def evaluate(self, bank_x, bank_y, query_x, query_y, bank_lengths=None, query_lengths=None, return_predictions=False, bootstrap=None, pr=False):
         """bank_x / query_x with their lengths: as `HipEncoder.encode` takes them (a rectangle, a rectangle with lengths, a ragged (C, S)
         batch, raw records under a per-record input transform); bank_y (N, K), query_y (Q, K) f32 multi-hot labels on the device.
         Returns the keys of `get_accuracy` under the `knn/` prefix (return_predictions: dict(metrics=..., predictions=...)).
-        bootstrap: as `HipEvaluator.evaluate` takes it, over the query records: adds `knn/macro_auc_ci` and `knn/per_class_auc_ci`."""
+        bootstrap: as `HipEvaluator.evaluate` takes it, over the query records: adds `knn/macro_auc_ci` and `knn/per_class_auc_ci`.
+        pr: as `HipEvaluator.evaluate` takes it: the average-precision and F-max keys under `knn/` (thresholds are vote shares)."""
         from . import knn
         fb, fq = self._encode((bank_x, bank_lengths), (query_x, query_lengths))
-        return self._score(knn.KnnIndex(fb, metric='cosine'), fq, bank_y, query_y, False, return_predictions, bootstrap)
+        return self._score(knn.KnnIndex(fb, metric='cosine'), fq, bank_y, query_y, False, return_predictions, bootstrap, pr)
 
-    def leave_one_out(self, x, y, lengths=None, return_predictions=False, bootstrap=None):
+    def leave_one_out(self, x, y, lengths=None, return_predictions=False, bootstrap=None, pr=False):
         """`evaluate` with the set as its own bank: record r never receives itself (by index: a duplicate of it is still a neighbour)"""
         from . import knn
         f, = self._encode((x, lengths))
-        return self._score(knn.KnnIndex(f, metric='cosine'), f, y, y, True, return_predictions, bootstrap)
+        return self._score(knn.KnnIndex(f, metric='cosine'), f, y, y, True, return_predictions, bootstrap, pr)
 
 
 class HipRollout:

@@ -138,6 +138,7 @@ class BootstrapResult:
 
     def __init__(self, point, triples, id2code=None):
         self.point, self.triples, self.id2code = point, triples, id2code
+        self.n = self.n_boot = self.seed = self.source = None   # the draws' record: `bootstrap_auc` fills it
         num2, wp, wn = (triples[..., i].astype(np.float64) for i in range(3))
         valid = (triples[..., 1] > 0) & (triples[..., 2] > 0)
         with np.errstate(divide='ignore', invalid='ignore'):
@@ -182,12 +183,8 @@ def _check_indices(indices, n):
     return indices
 
 
-def bootstrap_auc(scores, labels, n_boot=1000, seed=0, indices=None, from_logits=False, id2code=None, workspace_bytes=None) -> BootstrapResult:
-    """The point estimate and `n_boot` bootstrap replicates of the per-class and macro AUROC.
-    seed: the replicates' draws come from the device's counter-based generator (`draws` restates it); the same seed resamples two score sets
-    identically, whatever the chunking.  indices: (R, n) draws with replacement instead (host or device; R replaces n_boot): replicate b is then
-    `get_accuracy(preds[indices[b]], labels[indices[b]])`.  A seed other than 0 beside indices is refused.
-    workspace_bytes: bound on the multiplicity rows held at once (default 256 MiB); the replicates run in chunks of that many rows."""
+def _plan(scores, labels, n_boot, seed, indices, workspace_bytes):
+    """every refusal of a bootstrap call, the device asked for last -> (n, K, R, replicates per chunk, indices as a tensor or None)"""
     if isinstance(n_boot, bool) or not isinstance(n_boot, int) or n_boot < 1:
         raise ValueError(f'n_boot must be an integer >= 1, got {n_boot!r}')
     if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed <= _M64:
@@ -204,21 +201,51 @@ def bootstrap_auc(scores, labels, n_boot=1000, seed=0, indices=None, from_logits
     n, K = _check_pair(scores, labels)
     quad = rank_abi.lib().ecgvit_rank_workspace(n, K, 4)   # the multiplicities are held four replicates wide
     chunk = max(1, min(R, (DEFAULT_WORKSPACE_BYTES if workspace_bytes is None else workspace_bytes) // quad * 4))
-    ranked = rank_scores(scores, labels, from_logits)
-    point = _counts(ranked, id2code)
-    mult = torch.empty(n, (chunk + 3) // 4 * 4, dtype=torch.int32, device=scores.device)   # record-major; a shorter last chunk uses its head
-    triples = torch.empty(R, K, 3, dtype=torch.int64, device=scores.device)
+    return n, K, R, chunk, indices
+
+
+def _replicates(ranked, R, chunk, seed, indices, walks):
+    """the chunk loop of every bootstrap: one multiplicity fill per chunk of replicates, then each of `walks` as walk(mult, rows, r0)"""
+    n, dev = ranked.n, ranked.packed.device
+    mult = torch.empty(n, (chunk + 3) // 4 * 4, dtype=torch.int32, device=dev)   # record-major; a shorter last chunk uses its head
     for r0 in range(0, R, chunk):
         rows = min(chunk, R - r0)
         if indices is None:
             rank_abi.run.ecgvit_rank_multiplicities_seeded(seed, r0, rows, n, ptr(mult), stream())
         else:
-            idx = indices[r0:r0 + rows].to(device=scores.device, dtype=torch.int64).contiguous()
+            idx = indices[r0:r0 + rows].to(device=dev, dtype=torch.int64).contiguous()
             rank_abi.run.ecgvit_rank_multiplicities(ptr(idx), n, rows, n, ptr(mult), stream())
-        ranked._walk(mult, rows, triples[r0:r0 + rows])
-    res = BootstrapResult(point.result(), triples.cpu().numpy(), id2code)
-    res.chunk = chunk
+        for walk in walks:
+            walk(mult, rows, r0)
+
+
+def draw_source(seed, indices):
+    """what the replicates of a result were drawn from: ('seed', seed), or ('indices', R, a wrapping int64 checksum of the draws) -- two results
+    compare replicate by replicate only when these are equal"""
+    if indices is None:
+        return ('seed', int(seed))
+    flat = indices.to(torch.int64).reshape(-1)
+    return ('indices', int(indices.shape[0]), int((flat * torch.arange(1, flat.numel() + 1, dtype=torch.int64, device=flat.device)).sum()))
+
+
+def _stamp(res, n, R, chunk, seed, indices):
+    res.chunk, res.n, res.n_boot, res.seed, res.source = chunk, n, R, (seed if indices is None else None), draw_source(seed, indices)
     return res
+
+
+def bootstrap_auc(scores, labels, n_boot=1000, seed=0, indices=None, from_logits=False, id2code=None, workspace_bytes=None) -> BootstrapResult:
+    """The point estimate and `n_boot` bootstrap replicates of the per-class and macro AUROC.
+    seed: the replicates' draws come from the device's counter-based generator (`draws` restates it); the same seed resamples two score sets
+    identically, whatever the chunking.  indices: (R, n) draws with replacement instead (host or device; R replaces n_boot): replicate b is then
+    `get_accuracy(preds[indices[b]], labels[indices[b]])`.  A seed other than 0 beside indices is refused.
+    workspace_bytes: bound on the multiplicity rows held at once (default 256 MiB); the replicates run in chunks of that many rows.
+    The result records `n`, `n_boot`, `seed` (None under indices) and `source` (`draw_source`), which `pr_metrics.paired_diff_ci` compares."""
+    n, K, R, chunk, indices = _plan(scores, labels, n_boot, seed, indices, workspace_bytes)
+    ranked = rank_scores(scores, labels, from_logits)
+    point = _counts(ranked, id2code)
+    triples = torch.empty(R, K, 3, dtype=torch.int64, device=scores.device)
+    _replicates(ranked, R, chunk, seed, indices, [lambda mult, rows, r0: ranked._walk(mult, rows, triples[r0:r0 + rows])])
+    return _stamp(BootstrapResult(point.result(), triples.cpu().numpy(), id2code), n, R, chunk, seed, indices)
 
 
 def intervals(res, alpha=0.05):
@@ -232,12 +259,17 @@ def intervals(res, alpha=0.05):
     return res.ci(alpha), {key: (float(cc[k, 0]), float(cc[k, 1])) for key, k in zip(keys, cols)}
 
 
-def evaluator_bootstrap(bootstrap, scores, labels, from_logits, id2code):
-    """`bootstrap` of `HipEvaluator.evaluate` / `HipKnnProbe`: an int (n_boot) or a dict of `bootstrap_auc`'s keywords -> BootstrapResult"""
+def bootstrap_keywords(bootstrap):
+    """`bootstrap` of `HipEvaluator.evaluate` / `HipKnnProbe`: an int (n_boot) or a dict of `bootstrap_auc`'s keywords -> the dict"""
     if isinstance(bootstrap, bool) or not isinstance(bootstrap, (int, dict)):
         raise ValueError(f'bootstrap must be None, an integer or a dict of bootstrap_auc keywords, got {bootstrap!r}')
     kw = dict(bootstrap) if isinstance(bootstrap, dict) else dict(n_boot=bootstrap)
     bad = set(kw) - {'n_boot', 'seed', 'indices', 'workspace_bytes'}
     if bad:
         raise ValueError(f'bootstrap: unknown keywords {sorted(bad)}')
-    return bootstrap_auc(scores, labels, from_logits=from_logits, id2code=id2code, **kw)
+    return kw
+
+
+def evaluator_bootstrap(bootstrap, scores, labels, from_logits, id2code):
+    """the evaluators' `bootstrap` -> BootstrapResult"""
+    return bootstrap_auc(scores, labels, from_logits=from_logits, id2code=id2code, **bootstrap_keywords(bootstrap))
