@@ -27,8 +27,8 @@ namespace {
 // =====================================================================================================
 // forward: online softmax over 32-key tiles (running max / sum per query, O rescaled when the max moves)
 // =====================================================================================================
-// Q8 (fp8_linear): additionally out8 = saturate(out as stored / *q8_scale) in e4m3 -- the A operand of the out-projection's 8-bit
-// product, written here instead of by a quantise pass over `out` -- and *q8_amax = max(*q8_amax, max |out|) for the next step's scale
+// Q8 (fp8_linear): additionally out8 = the e4m3 copy of `out` at *q8_scale -- the A operand of the out-projection's 8-bit
+// product, written here instead of by a quantise pass over `out` -- and *q8_amax = max(*q8_amax, max |out|)
 // SPLIT (records of more than 256 tokens, e.g. patch 10 -> 501): one workgroup per (record, head, 256-query half); the keys pass through
 // the SAME 64 KiB of images in 256-key windows (the online softmax carries m, l and O across them), so two workgroups still share a CU --
 // with all 501 keys resident (128 KiB) a CU held one workgroup, two waves per SIMD, and this VALU-bound kernel ran at 2/3 of its rate.
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_bf16_kernel(const bf16_t *__r
         {
             const float inv = inv_keep / l;   // inv_keep = 1 without dropout
             [[maybe_unused]] float q8_inv = 0.f;
-            if constexpr (Q8) { const float sc = *q8_scale; q8_inv = sc > 0.f ? 1.0f / sc : 0.f; }
+            if constexpr (Q8) q8_inv = q8_inverse(*q8_scale);
             const int qr = q < N ? q : 0;
             bf16_t *orow = out + ((int64_t)b * N + qr) * d + hd * 64;
 #pragma unroll
@@ -198,17 +198,8 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_bf16_kernel(const bf16_t *__r
                         const u32x2 vv = __builtin_bit_cast(u32x2, v);
                         D[gg][0] = vv[0]; D[gg][1] = vv[1];
                         if constexpr (Q8) {
-                            float f[4];
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                f[k] = (float)v[k];                       // the value as stored
-                                qmax = fmaxf(qmax, q < N ? fabsf(f[k]) : 0.f);
-                                f[k] = __builtin_amdgcn_fmed3f(f[k] * q8_inv, -448.f, 448.f);
-                            }
-                            int w = 0;
-                            w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w, false);
-                            w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w, true);
-                            W8[gg] = (uint32_t)w;
+                            const float f[4] = {(float)v[0], (float)v[1], (float)v[2], (float)v[3]};   // the values as stored
+                            W8[gg] = q8_encode4<ECGVIT_FP8_E4M3>(f, q8_inv, qmax, q < N);
                         }
                     }
                     u32x4 st;
@@ -419,7 +410,7 @@ __global__ __launch_bounds__(MODE == 3 ? 512 : 1024, 4) void attn_fwd_stream_ker
         {
             const float inv = inv_keep / l;
             [[maybe_unused]] float q8_inv = 0.f;
-            if constexpr (Q8) { const float sc8 = *q8_scale; q8_inv = sc8 > 0.f ? 1.0f / sc8 : 0.f; }
+            if constexpr (Q8) q8_inv = q8_inverse(*q8_scale);
             const uint32_t bo = MODE == 4 ? (uint32_t)(((int64_t)(N - q0 - 1) * d + 64) * 2) : bytes_o;
             const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *)(out + ((int64_t)b * N + q0) * d + hd * 64), 0, bo, 0x00020000);
             const int ooff = (q * d + 16 * lh) * 2;
@@ -439,17 +430,8 @@ __global__ __launch_bounds__(MODE == 3 ? 512 : 1024, 4) void attn_fwd_stream_ker
                         const u32x2 vv = __builtin_bit_cast(u32x2, v);
                         D[gg][0] = vv[0]; D[gg][1] = vv[1];
                         if constexpr (Q8) {
-                            float f[4];
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                f[k] = (float)v[k];
-                                qmax = fmaxf(qmax, qg < N ? fabsf(f[k]) : 0.f);
-                                f[k] = __builtin_amdgcn_fmed3f(f[k] * q8_inv, -448.f, 448.f);
-                            }
-                            int wv = 0;
-                            wv = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], wv, false);
-                            wv = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], wv, true);
-                            W8[gg] = (uint32_t)wv;
+                            const float f[4] = {(float)v[0], (float)v[1], (float)v[2], (float)v[3]};   // the values as stored
+                            W8[gg] = q8_encode4<ECGVIT_FP8_E4M3>(f, q8_inv, qmax, qg < N);
                         }
                     }
                     u32x4 st;
@@ -701,7 +683,7 @@ __global__ __launch_bounds__(NKT * 64) void attn_bwd_bf16_kernel(const bf16_t *_
 
 // Records longer than 256 tokens (N <= 512, e.g. patch 10 -> 501) run as TWO launches, one per half of the keys: `k0` is the first key
 // of this launch's 256-key window, queries always run over all of N; the second launch adds its dQ to the first one's (ACCUM).
-// Q8 (fp8_linear; bit 0: dK / dV, bit 1: dQ): additionally dqkv8 = saturate(dqkv as stored / *q8_scale) in e5m2 (same [B*N, 3*h*dh] layout, one
+// Q8 (fp8_linear; bit 0: dK / dV, bit 1: dQ): additionally dqkv8 = the e5m2 copy of dqkv at *q8_scale (same [B*N, 3*h*dh] layout, one
 // byte per element) -- the A operand of the QKV projection's two backward products, written here instead of by a quantise pass over
 // dqkv -- and *q8_amax = max(*q8_amax, max |dqkv|).  With two key windows the first launch emits its dK / dV only (dQ is final in the second).
 // NQ = 2048 (512 < N <= 2048: one launch per 256-key window, up to eight; every launch after the first adds its dQ to the bf16 dQ in dqkv): the LSE row
@@ -717,7 +699,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
     constexpr int SQ = (Q8 & 2) ? 2 : 1;     // stores of one dQ tile (C phase)
     constexpr int SF = (Q8 & 1) ? 16 : 8;    // dK / dV stores of one item's flush
     [[maybe_unused]] float q8_inv = 0.f, qmax = 0.f;
-    if constexpr (Q8 != 0) { const float sc = *q8_scale; q8_inv = sc > 0.f ? 1.0f / sc : 0.f; }
+    if constexpr (Q8 != 0) q8_inv = q8_inverse(*q8_scale);
     constexpr int IMG = 32768, DSB = 16384, SLAB = 12288;
     constexpr int LBUF = NQ == 512 ? 2 : 1, LPL = NQ / 512;   // LSE row buffers; LSE values per lane (loads of the next item's row)
     static_assert(NQ == 512 || NQ == 2048, "NQ");
@@ -1088,16 +1070,8 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
             }
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), rdq, (q * d3 + dhc * 16 + 4 * dq_g) * 2, 0, 0);   // rows >= N: dropped
             if constexpr ((Q8 & 2) != 0) {
-                float f[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    f[r] = (float)v[r];                            // the value as stored
-                    qmax = fmaxf(qmax, q < N ? fabsf(f[r]) : 0.f);
-                    f[r] = __builtin_amdgcn_fmed3f(f[r] * q8_inv, -57344.f, 57344.f);
-                }
-                int w = 0;
-                w = __builtin_amdgcn_cvt_pk_bf8_f32(f[0], f[1], w, false);
-                w = __builtin_amdgcn_cvt_pk_bf8_f32(f[2], f[3], w, true);
+                const float f[4] = {(float)v[0], (float)v[1], (float)v[2], (float)v[3]};   // the values as stored
+                const uint32_t w = q8_encode4<ECGVIT_BF8_E5M2>(f, q8_inv, qmax, q < N);
                 const __amdgpu_buffer_rsrc_t rdq8 = __builtin_amdgcn_make_buffer_rsrc((void *)(dqkv8 + (int64_t)cur.b * N * d3 + cur.hd * 64), 0, bytes_q / 2, 0x00020000);
                 __builtin_amdgcn_raw_buffer_store_b32(w, rdq8, q * d3 + dhc * 16 + 4 * dq_g, 0, 0);
             }
@@ -1175,16 +1149,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t *__rest
 #pragma unroll
                         for (int k = 0; k < 4; ++k) { f[2 * k] = __builtin_bit_cast(float, val[k] << 16); f[2 * k + 1] = __builtin_bit_cast(float, val[k] & 0xFFFF0000u); }
                         const bool kin = key + k0 < N;
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) {
-                            qmax = fmaxf(qmax, kin ? fabsf(f[k]) : 0.f);
-                            f[k] = __builtin_amdgcn_fmed3f(f[k] * q8_inv, -57344.f, 57344.f);
-                        }
-                        int w0 = 0, w1 = 0;
-                        w0 = __builtin_amdgcn_cvt_pk_bf8_f32(f[0], f[1], w0, false); w0 = __builtin_amdgcn_cvt_pk_bf8_f32(f[2], f[3], w0, true);
-                        w1 = __builtin_amdgcn_cvt_pk_bf8_f32(f[4], f[5], w1, false); w1 = __builtin_amdgcn_cvt_pk_bf8_f32(f[6], f[7], w1, true);
-                        u32x2 q2;
-                        q2[0] = (uint32_t)w0; q2[1] = (uint32_t)w1;
+                        const u32x2 q2 = {q8_encode4<ECGVIT_BF8_E5M2>(f, q8_inv, qmax, kin), q8_encode4<ECGVIT_BF8_E5M2>(f + 4, q8_inv, qmax, kin)};
                         const __amdgpu_buffer_rsrc_t rkv8 = __builtin_amdgcn_make_buffer_rsrc((void *)(dqkv8 + ((int64_t)cur.b * N + k0) * d3 + (1 + which) * d + cur.hd * 64), 0, bytes_k / 2, 0x00020000);
                         __builtin_amdgcn_raw_buffer_store_b64(q2, rkv8, key * d3 + ch * 8, 0, 0);
                     }

@@ -88,6 +88,46 @@ __device__ __forceinline__ void wave_amax_publish(float *dst, float v, unsigned 
     if ((threadIdx.x & 63) == 0 && __float_as_uint(v) > seen) atomicMax(reinterpret_cast<unsigned int *>(dst), __float_as_uint(v));   // (v >= 0: never below a seen 0)
 }
 __device__ __forceinline__ void wave_amax_publish(float *dst, float v) { wave_amax_publish(dst, v, amax_peek(dst)); }
+
+// ---- the 8-bit encoder: the device statement of the rounding rule ecgvit_hip.h gives at ecgvit_fp8_quantize, which every 8-bit emitter of the
+// library follows -- the value AS STORED times the f32 reciprocal of the scale (0 for a scale that is not positive: zeros), clamped to +-max of
+// the format by a median, rounded to nearest even by the pack.  FMT = ECGVIT_FP8_E4M3 | ECGVIT_BF8_E5M2.
+constexpr float FP8_E4M3_MAX = 448.f, BF8_E5M2_MAX = 57344.f;
+template <int FMT> constexpr float q8_max() { return FMT == ECGVIT_BF8_E5M2 ? BF8_E5M2_MAX : FP8_E4M3_MAX; }
+__device__ __forceinline__ float q8_inverse(float scale) { return scale > 0.f ? 1.0f / scale : 0.f; }
+// four f32 -> one dword of four bytes, f[0] lowest; no scale, no clamp (the saved FFN tensor of ECGVIT_EPI_AUX8 is packed by this alone)
+template <int FMT> __device__ __forceinline__ uint32_t q8_pack4(const float *f) {
+    int w = 0;
+    if constexpr (FMT == ECGVIT_BF8_E5M2) {
+        w = __builtin_amdgcn_cvt_pk_bf8_f32(f[0], f[1], w, false);
+        w = __builtin_amdgcn_cvt_pk_bf8_f32(f[2], f[3], w, true);
+    } else {
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w, false);
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w, true);
+    }
+    return (uint32_t)w;
+}
+// the rule up to the pack: c = f * inv clamped to +-mx (mx as a value: gemm_nt.hip's format is a run-time field, it branches at the pack only)
+__device__ __forceinline__ void q8_clamp4(const float *f, float inv, float mx, float *c) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = __builtin_amdgcn_fmed3f(f[k] * inv, -mx, mx);
+}
+// f = four values as stored, inv = q8_inverse(scale); an 8-wide run is two calls
+template <int FMT> __device__ __forceinline__ uint32_t q8_encode4(const float *f, float inv) {
+    float c[4];
+    q8_clamp4(f, inv, q8_max<FMT>(), c);
+    return q8_pack4<FMT>(c);
+}
+// ... and amax = max(amax, |f|) where `counts` (rows past the tensor's end are encoded like any other -- their stores are dropped -- but stay
+// out of the next step's scale)
+__device__ __forceinline__ void q8_amax4(const float *f, float &amax, bool counts = true) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) amax = fmaxf(amax, counts ? fabsf(f[k]) : 0.f);
+}
+template <int FMT> __device__ __forceinline__ uint32_t q8_encode4(const float *f, float inv, float &amax, bool counts = true) {
+    q8_amax4(f, amax, counts);
+    return q8_encode4<FMT>(f, inv);
+}
 // sum over a block of NW waves; every thread gets the result. `red` = NW floats of LDS.
 template <int NW> __device__ __forceinline__ float block_sum(float v, float *red) {
     v = wave_sum(v);

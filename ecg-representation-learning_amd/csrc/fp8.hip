@@ -7,13 +7,7 @@
 
 namespace {
 
-constexpr float FP8_E4M3_MAX = 448.f, BF8_E5M2_MAX = 57344.f;
-
 __device__ __forceinline__ float fmt_max(int fmt) { return fmt == ECGVIT_BF8_E5M2 ? BF8_E5M2_MAX : FP8_E4M3_MAX; }
-
-__device__ __forceinline__ void wave_atomic_max(float *dst, float v) {
-    wave_amax_publish(dst, v);
-}
 
 // segments: table[2*s] = first element (multiple of 16), table[2*s+1] = element count (multiple of 8) of segment s = blockIdx.y; a null table = one
 // segment (off0, n0).  amax[s] = max(amax[s], max |x|).
@@ -27,38 +21,22 @@ __global__ __launch_bounds__(256) void fp8_amax_kernel(const bf16_t *__restrict_
 #pragma unroll
         for (int k = 0; k < 8; ++k) m = fmaxf(m, fabsf(v.get(k)));
     }
-    wave_atomic_max(amax + s, m);
+    wave_amax_publish(amax + s, m);
 }
 
-// y[i] = saturate(x[i] / scale[s]) in the 8-bit format; amax_next[s] (optional) accumulates max |x| for the next step's scale
+// y = the 8-bit copy of x at scale[s] (q8_encode4); amax_next[s] (optional) accumulates max |x| for the next step's scale
 template <int FMT>
 __global__ __launch_bounds__(256) void fp8_quantize_kernel(const bf16_t *__restrict__ x, uint8_t *__restrict__ y, const int64_t *__restrict__ table,
                                                            int64_t off0, int64_t n0, const float *__restrict__ scale, float *__restrict__ amax_next) {
     const int s = blockIdx.y;
     const int64_t off = table ? table[2 * s] : off0, n = table ? table[2 * s + 1] : n0;
-    const float sc = scale[s];
-    const float inv = sc > 0.f ? 1.0f / sc : 0.f;
-    constexpr float MX = FMT == ECGVIT_BF8_E5M2 ? BF8_E5M2_MAX : FP8_E4M3_MAX;
+    const float inv = q8_inverse(scale[s]);
     float m = 0.f;
     auto q8 = [&](const Vec16<bf16_t> &v) {   // 8 bf16 -> 8 bytes
         float f[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float r = v.get(k);
-            m = fmaxf(m, fabsf(r));
-            f[k] = __builtin_amdgcn_fmed3f(r * inv, -MX, MX);
-        }
-        int w0 = 0, w1 = 0;
-        if constexpr (FMT == ECGVIT_BF8_E5M2) {
-            w0 = __builtin_amdgcn_cvt_pk_bf8_f32(f[0], f[1], w0, false); w0 = __builtin_amdgcn_cvt_pk_bf8_f32(f[2], f[3], w0, true);
-            w1 = __builtin_amdgcn_cvt_pk_bf8_f32(f[4], f[5], w1, false); w1 = __builtin_amdgcn_cvt_pk_bf8_f32(f[6], f[7], w1, true);
-        } else {
-            w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w0, false); w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
-            w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], w1, false); w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
-        }
-        u32x2 o;
-        o[0] = (uint32_t)w0; o[1] = (uint32_t)w1;
-        return o;
+        for (int k = 0; k < 8; ++k) f[k] = v.get(k);
+        return u32x2{q8_encode4<FMT>(f, inv, m), q8_encode4<FMT>(f + 4, inv, m)};
     };
     // 16 elements per lane and step: two 16-B loads, one 16-B store (an 8-element tail, if any, goes as one 8-B store)
     for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16; i < n; i += (int64_t)gridDim.x * 256 * 16) {
@@ -72,7 +50,7 @@ __global__ __launch_bounds__(256) void fp8_quantize_kernel(const bf16_t *__restr
             *reinterpret_cast<u32x2 *>(y + off + i) = q8(ld16(x + off + i));
         }
     }
-    if (amax_next) wave_atomic_max(amax_next + s, m);
+    if (amax_next) wave_amax_publish(amax_next + s, m);
 }
 
 __global__ void fp8_scale_update_kernel(float *__restrict__ scale, float *__restrict__ amax, int n, const int32_t *__restrict__ fmt, int fmt_all) {

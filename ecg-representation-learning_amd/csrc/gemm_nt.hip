@@ -92,21 +92,13 @@ __device__ __forceinline__ void nt_epi8_tail(const u32x4 &out, bool ok, bool okm
         float f[8];
 #pragma unroll
         for (int k = 0; k < 4; ++k) { f[2 * k] = bf16_lo(out[k]); f[2 * k + 1] = bf16_hi(out[k]); }
-        if (ok) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) qmax = fmaxf(qmax, fabsf(f[k]));
-        }
-        const float mx = bf.q8_bf8 ? 57344.f : 448.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) f[k] = __builtin_amdgcn_fmed3f(f[k] * bf.q8_inv, -mx, mx);
-        int w0 = 0, w1 = 0;
-        if (bf.q8_bf8) {
-            w0 = __builtin_amdgcn_cvt_pk_bf8_f32(f[0], f[1], w0, false); w0 = __builtin_amdgcn_cvt_pk_bf8_f32(f[2], f[3], w0, true);
-            w1 = __builtin_amdgcn_cvt_pk_bf8_f32(f[4], f[5], w1, false); w1 = __builtin_amdgcn_cvt_pk_bf8_f32(f[6], f[7], w1, true);
-        } else {
-            w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w0, false); w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
-            w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], w1, false); w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
-        }
+        // q8_encode4 with the format as a run-time field of the descriptor: one clamp, the branch at the pack
+        if (ok) { q8_amax4(f, qmax); q8_amax4(f + 4, qmax); }
+        const float mx = bf.q8_bf8 ? BF8_E5M2_MAX : FP8_E4M3_MAX;
+        q8_clamp4(f, bf.q8_inv, mx, f); q8_clamp4(f + 4, bf.q8_inv, mx, f + 4);
+        int w0, w1;
+        if (bf.q8_bf8) { w0 = (int)q8_pack4<ECGVIT_BF8_E5M2>(f); w1 = (int)q8_pack4<ECGVIT_BF8_E5M2>(f + 4); }
+        else { w0 = (int)q8_pack4<ECGVIT_FP8_E4M3>(f); w1 = (int)q8_pack4<ECGVIT_FP8_E4M3>(f + 4); }
         u32x2 q;
         q[0] = (uint32_t)__builtin_amdgcn_ds_bpermute(bf.t_out, w0); q[1] = (uint32_t)__builtin_amdgcn_ds_bpermute(bf.t_out, w1);
         __builtin_amdgcn_raw_buffer_store_b64(q, bf.q8, okm ? mm * (uint32_t)bf.ldq + ncm : NT_OOB, 0, 0);
@@ -160,9 +152,8 @@ __device__ __forceinline__ void nt_epi8(float (&v)[8], const float *bias8, uint3
         }
         if constexpr ((FL & ECGVIT_EPI_AUX8) != 0) {
             // the saved tensor as e4m3 bytes (from the UNROUNDED f32 values): 8 B per run -- half the stream, two crossbar moves instead of four
-            int w0 = 0, w1 = 0;
-            w0 = __builtin_amdgcn_cvt_pk_fp8_f32(dy[0], dy[1], w0, false); w0 = __builtin_amdgcn_cvt_pk_fp8_f32(dy[2], dy[3], w0, true);
-            w1 = __builtin_amdgcn_cvt_pk_fp8_f32(dy[4], dy[5], w1, false); w1 = __builtin_amdgcn_cvt_pk_fp8_f32(dy[6], dy[7], w1, true);
+            // (the raw pack: no scale and no clamp)
+            int w0 = (int)q8_pack4<ECGVIT_FP8_E4M3>(dy), w1 = (int)q8_pack4<ECGVIT_FP8_E4M3>(dy + 4);
             if constexpr (kDrop) {   // byte masks from the pairs' halfword masks (sav already carries them: recover from the masked bf16 pairs' keep masks)
                 w0 &= (int)__builtin_amdgcn_perm(kmk[1], kmk[0], 0x06040200u);
                 w1 &= (int)__builtin_amdgcn_perm(kmk[3], kmk[2], 0x06040200u);
@@ -460,7 +451,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_kernel(ecgvit_gemm_desc d, Epi
     bf.t_out = ((lane >> 2) + 16 * (lane & 3)) << 2;   // memory-layout lane t takes its run from accumulator-layout lane (t>>2) + 16 (t&3)
     bf.t_in = (4 * (lane & 15) + (lane >> 4)) << 2;    // and back
     bf.q8_inv = 0.f;
-    if (NT_HAS(ECGVIT_EPI_QUANT_OUT)) { const float qs = *d.q8_scale; bf.q8_inv = qs > 0.f ? 1.0f / qs : 0.f; }
+    if (NT_HAS(ECGVIT_EPI_QUANT_OUT)) bf.q8_inv = q8_inverse(*d.q8_scale);
     // this wave's two DMA pieces of a half-tile: rows 16*wave + {0..7}, {8..15}; LDS chunk p of row r holds source chunk p ^ f(r)
     const int r0 = 16 * wave + (lane >> 3), r1 = r0 + 8, p = lane & 7;
     const int voA0 = r0 * lda2 + ((p ^ ((r0 >> 1) & 7)) << 4), voA1 = r1 * lda2 + ((p ^ ((r1 >> 1) & 7)) << 4);

@@ -432,10 +432,17 @@ template <int E> struct LaneRow {
             *reinterpret_cast<bf16x4 *>(row + 512 * N16 + 4 * lane) = t;
         }
     }
+    // the 8-bit copy of a row: v = the values as stored, inv = q8_inverse(scale); amax = max(amax, max |v|)
+    template <int FMT> static __device__ __forceinline__ void store8(uint8_t *row, int lane, const float (&v)[E], float inv, float &amax) {
+#pragma unroll
+        for (int i = 0; i < N16; ++i)
+            *reinterpret_cast<u32x2 *>(row + (i * 64 + lane) * 8) = u32x2{q8_encode4<FMT>(v + 8 * i, inv, amax), q8_encode4<FMT>(v + 8 * i + 4, inv, amax)};
+        if constexpr (N8 == 1) *reinterpret_cast<uint32_t *>(row + 512 * N16 + 4 * lane) = q8_encode4<FMT>(v + 8 * N16, inv, amax);
+    }
 };
 
-// Q8: additionally y8 = saturate(y as stored / *q8_scale) in e4m3 (the operand copy of the next Linear's fp8 product, written here
-// instead of by a quantise pass over y) and *q8_amax = max(*q8_amax, max |y|) for the next step's scale
+// Q8: additionally y8 = the e4m3 copy of y (the operand of the next Linear's fp8 product, written here instead of by a quantise pass
+// over y) at *q8_scale, and *q8_amax = max(*q8_amax, max |y|)
 template <int E, bool Q8 = false>
 __global__ __launch_bounds__(256) void layernorm_fwd_fit_kernel(const bf16_t *__restrict__ x, const float *__restrict__ gamma,
                                                                 const float *__restrict__ beta, bf16_t *__restrict__ y,
@@ -444,7 +451,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_fit_kernel(const bf16_t *__
                                                                 float *__restrict__ q8_amax = nullptr) {
     using L = LaneRow<E>;
     [[maybe_unused]] float q8_inv = 0.f, qmax = 0.f;
-    if constexpr (Q8) { const float sc = *q8_scale; q8_inv = sc > 0.f ? 1.0f / sc : 0.f; }
+    if constexpr (Q8) q8_inv = q8_inverse(*q8_scale);
     constexpr int d = 64 * E;
     const int lane = threadIdx.x & 63;
     const int64_t wave0 = blockIdx.x * 4ll + (threadIdx.x >> 6), nw = gridDim.x * 4ll;
@@ -466,28 +473,9 @@ __global__ __launch_bounds__(256) void layernorm_fwd_fit_kernel(const bf16_t *__
         for (int k = 0; k < E; ++k) v[k] = v[k] * rs * gm[k] + bt[k];
         if (!Q8 || y) L::store(y + r * d, lane, v);   // (Q8: y may be NULL -- every consumer reads the 8-bit copy)
         if constexpr (Q8) {
-            uint8_t *row8 = y8 + r * d;
 #pragma unroll
-            for (int k = 0; k < E; ++k) {
-                v[k] = (float)(bf16_t)v[k];                 // the value as stored
-                qmax = fmaxf(qmax, fabsf(v[k]));
-                v[k] = __builtin_amdgcn_fmed3f(v[k] * q8_inv, -448.f, 448.f);
-            }
-#pragma unroll
-            for (int i = 0; i < L::N16; ++i) {
-                int w0 = 0, w1 = 0;
-                w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[8 * i], v[8 * i + 1], w0, false); w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[8 * i + 2], v[8 * i + 3], w0, true);
-                w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[8 * i + 4], v[8 * i + 5], w1, false); w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[8 * i + 6], v[8 * i + 7], w1, true);
-                u32x2 o;
-                o[0] = (uint32_t)w0; o[1] = (uint32_t)w1;
-                *reinterpret_cast<u32x2 *>(row8 + (i * 64 + lane) * 8) = o;
-            }
-            if constexpr (L::N8 == 1) {
-                int w0 = 0;
-                w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[8 * L::N16], v[8 * L::N16 + 1], w0, false);
-                w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[8 * L::N16 + 2], v[8 * L::N16 + 3], w0, true);
-                *reinterpret_cast<uint32_t *>(row8 + 512 * L::N16 + 4 * lane) = (uint32_t)w0;
-            }
+            for (int k = 0; k < E; ++k) v[k] = (float)(bf16_t)v[k];   // the value as stored
+            L::template store8<ECGVIT_FP8_E4M3>(y8 + r * d, lane, v, q8_inv, qmax);
         }
         if (lane == 0) { mean[r] = mu; rstd[r] = rs; }
     }
@@ -496,9 +484,9 @@ __global__ __launch_bounds__(256) void layernorm_fwd_fit_kernel(const bf16_t *__
     }
 }
 
-// Q8 (with EXTRA): additionally g8 = saturate(v / *q8_scale) in e5m2 for v = the gradient the next backward stage consumes (dxm when a
-// mask is applied, else dx), as stored -- the 8-bit A operand of that stage's input-gradient product, written here instead of by a
-// quantise pass -- and *q8_amax = max(*q8_amax, max |v|) for the next step's scale
+// Q8 (with EXTRA): additionally g8 = the e5m2 copy of v = the gradient the next backward stage consumes (dxm when a mask is applied,
+// else dx) -- the 8-bit A operand of that stage's input-gradient product, written here instead of by a quantise pass -- at *q8_scale,
+// and *q8_amax = max(*q8_amax, max |v|)
 template <int E, bool EXTRA, bool Q8 = false>
 __global__ __launch_bounds__(256, E <= 12 ? 4 : 2) void layernorm_bwd_fit_kernel(const bf16_t *__restrict__ dy, const bf16_t *__restrict__ x,
                                                                 const float *__restrict__ gamma, const float *__restrict__ mean,
@@ -509,10 +497,11 @@ __global__ __launch_bounds__(256, E <= 12 ? 4 : 2) void layernorm_bwd_fit_kernel
                                                                 float *__restrict__ q8_amax = nullptr, uint32_t mrp = 1) {
     using L = LaneRow<E>;
     [[maybe_unused]] float q8_inv = 0.f, qmax = 0.f;
-    if constexpr (Q8) { const float sc = *q8_scale; q8_inv = sc > 0.f ? 1.0f / sc : 0.f; }
+    if constexpr (Q8) q8_inv = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, q8_inverse(*q8_scale))));
     constexpr int d = 64 * E, NP = EXTRA ? 3 : 2;
     extern __shared__ __attribute__((aligned(16))) float red[];  // [4][NP][d] partial sums, then gamma [d]
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    // (w and the Q8 reciprocal as SCALARS: the row index, its offsets and mean / rstd then live in SGPRs)
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t wave0 = blockIdx.x * 4ll + w, nw = gridDim.x * 4ll;
     float *gs = red + 4 * NP * d;   // gamma lives in LDS (3 reads per row) instead of E registers: the kernel fits 128 VGPRs = 4 waves/SIMD
     for (int c = threadIdx.x; c < d; c += 256) gs[c] = gamma[c];
@@ -521,12 +510,17 @@ __global__ __launch_bounds__(256, E <= 12 ? 4 : 2) void layernorm_bwd_fit_kernel
 #pragma unroll
     for (int k = 0; k < E; ++k) { ag[k] = 0.f; ab[k] = 0.f; if (EXTRA) ac[k] = 0.f; }
     for (int64_t r = wave0; r < rows; r += nw) {
+        // the lane index, taken anew per row: hipcc otherwise keeps one 64-bit per-lane pointer per tensor (dy, x, dres, dx, dxm, g8: 12 VGPRs) across
+        // the loop instead of one 32-bit offset beside the scalar row bases -- with them the E = 12 and E = 32 forms spilled (tests/test_code_objects.py)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        ln &= 63;
         const float mu = mean[r], rs = rstd[r];
         const uint32_t ro = (uint32_t)r * (uint32_t)d;   // 32-bit element offset (rows * d < 2^31 checked by the launcher): scalar base + one VGPR offset per access
         float g[E], xh[E], gm[E];
-        L::load(dy + ro, lane, g);
-        L::load(x + ro, lane, xh);
-        L::load_f32(gs, lane, gm);
+        L::load(dy + ro, ln, g);
+        L::load(x + ro, ln, xh);
+        L::load_f32(gs, ln, gm);
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int k = 0; k < E; ++k) {
@@ -539,57 +533,34 @@ __global__ __launch_bounds__(256, E <= 12 ? 4 : 2) void layernorm_bwd_fit_kernel
         }
         const float c1 = wave_sum(s1) * (1.0f / d), c2 = wave_sum(s2) * (1.0f / d);
         float o[E];
-        if (dres) L::load(dres + ro, lane, o);
+        if (dres) L::load(dres + ro, ln, o);
 #pragma unroll
         for (int k = 0; k < E; ++k) {
             const float v = rs * (g[k] - c1 - xh[k] * c2);
             o[k] = (float)(bf16_t)(dres ? o[k] + v : v);   // the value as stored (rounded): what dxm and the column sums see
         }
-        L::store(dx + ro, lane, o);
+        L::store(dx + ro, ln, o);
         if (EXTRA) {
             if (thresh) {
                 const uint32_t mo = ro * mrp;   // mask counter of row r * mrp (ecgvit_layernorm_bwd_fused_rowpitch)
 #pragma unroll
                 for (int i = 0; i < L::N16; ++i) {
                     float mk[8];
-                    dropout_maskN<8, true>(seed, mo + (uint32_t)((i * 64 + lane) * 8), thresh, inv_keep, mk);
+                    dropout_maskN<8, true>(seed, mo + (uint32_t)((i * 64 + ln) * 8), thresh, inv_keep, mk);
 #pragma unroll
                     for (int k = 0; k < 8; ++k) o[8 * i + k] = (float)(bf16_t)(o[8 * i + k] * mk[k]);
                 }
                 if constexpr (L::N8 == 1) {
                     float mk[4];
-                    dropout_maskN<4, true>(seed, mo + (uint32_t)(512 * L::N16 + 4 * lane), thresh, inv_keep, mk);
+                    dropout_maskN<4, true>(seed, mo + (uint32_t)(512 * L::N16 + 4 * ln), thresh, inv_keep, mk);
 #pragma unroll
                     for (int k = 0; k < 4; ++k) o[8 * L::N16 + k] = (float)(bf16_t)(o[8 * L::N16 + k] * mk[k]);
                 }
-                if (!Q8 || dxm) L::store(dxm + ro, lane, o);   // (Q8: dxm may be NULL -- the masked gradient leaves as g8 only)
+                if (!Q8 || dxm) L::store(dxm + ro, ln, o);   // (Q8: dxm may be NULL -- the masked gradient leaves as g8 only)
             }
 #pragma unroll
             for (int k = 0; k < E; ++k) ac[k] += o[k];
-            if constexpr (Q8) {   // o = the values as stored (bf16-rounded), masked if a mask applies
-                uint8_t *row8 = g8 + ro;
-                float q[E];
-#pragma unroll
-                for (int k = 0; k < E; ++k) {
-                    qmax = fmaxf(qmax, fabsf(o[k]));
-                    q[k] = __builtin_amdgcn_fmed3f(o[k] * q8_inv, -57344.f, 57344.f);
-                }
-#pragma unroll
-                for (int i = 0; i < L::N16; ++i) {
-                    int w0 = 0, w1 = 0;
-                    w0 = __builtin_amdgcn_cvt_pk_bf8_f32(q[8 * i], q[8 * i + 1], w0, false); w0 = __builtin_amdgcn_cvt_pk_bf8_f32(q[8 * i + 2], q[8 * i + 3], w0, true);
-                    w1 = __builtin_amdgcn_cvt_pk_bf8_f32(q[8 * i + 4], q[8 * i + 5], w1, false); w1 = __builtin_amdgcn_cvt_pk_bf8_f32(q[8 * i + 6], q[8 * i + 7], w1, true);
-                    u32x2 ov;
-                    ov[0] = (uint32_t)w0; ov[1] = (uint32_t)w1;
-                    *reinterpret_cast<u32x2 *>(row8 + (i * 64 + lane) * 8) = ov;
-                }
-                if constexpr (L::N8 == 1) {
-                    int w0 = 0;
-                    w0 = __builtin_amdgcn_cvt_pk_bf8_f32(q[8 * L::N16], q[8 * L::N16 + 1], w0, false);
-                    w0 = __builtin_amdgcn_cvt_pk_bf8_f32(q[8 * L::N16 + 2], q[8 * L::N16 + 3], w0, true);
-                    *reinterpret_cast<uint32_t *>(row8 + 512 * L::N16 + 4 * lane) = (uint32_t)w0;
-                }
-            }
+            if constexpr (Q8) L::template store8<ECGVIT_BF8_E5M2>(g8 + ro, ln, o, q8_inv, qmax);   // o = the values as stored (bf16-rounded), masked if a mask applies
         }
     }
     if constexpr (Q8) {
