@@ -582,8 +582,8 @@ __global__ __launch_bounds__(256, E <= 12 ? 4 : 2) void layernorm_bwd_fit_kernel
     }
 }
 
-// out[c] = sum_p partial[p][c]  for c < width ; optional split into two outputs (dgamma | dbeta).
-// Block = 64 columns x 4 row-slices (each slice sums every 4th partial row, 4 loads in flight), LDS combine.
+// out[c] = sum_p partial[p][c]  for c < width ; optional split into two or three outputs (dgamma | dbeta | dcolsum).
+// Block = 64 columns x 16 row slices (each slice sums every 16th partial row, 4 loads in flight), LDS combine.
 __global__ __launch_bounds__(1024) void reduce_partials_kernel(const float *__restrict__ partial, int nparts, int width,
                                                                float *__restrict__ out0, float *__restrict__ out1, int split,
                                                                float *__restrict__ out2 = nullptr) {
@@ -701,6 +701,27 @@ inline int grid_for_rows(int64_t rows) { return (int)std::min<int64_t>((rows + 3
 }  // namespace
 
 static bool ln_fit(int d) { const int e = d / 64; return d % 256 == 0 && (e == 4 || e == 8 || e == 12 || e == 16 || e == 24 || e == 32); }   // exact lane mapping available
+// the LayerNorm launchers' one routing: f(form), the form a type.  bf16 at an exact width takes LnExact<d / 64>, the exact-lane kernels, where
+// `exact_ok` (the caller's statement that their offsets suffice); everything else takes LnMasked<T, MAXV>, the generic kernels, MAXV = the 16-byte
+// vectors of a row per lane rounded up to a power of two
+template <int E_> struct LnExact { using T = bf16_t; static constexpr bool EXACT = true; static constexpr int E = E_; };
+template <typename T_, int MAXV_> struct LnMasked { using T = T_; static constexpr bool EXACT = false; static constexpr int MAXV = MAXV_; };
+template <typename F> static int ln_dispatch(int dtype, int d, bool exact_ok, F &&f) {
+    if (dtype == ECGVIT_BF16 && exact_ok && ln_fit(d)) switch (d / 64) {
+        case 4: return f(LnExact<4>{});    case 8: return f(LnExact<8>{});    case 12: return f(LnExact<12>{});
+        case 16: return f(LnExact<16>{});  case 24: return f(LnExact<24>{});  case 32: return f(LnExact<32>{});
+    }
+    return dispatch_dtype(dtype, [&](auto e) -> int {
+        using T = decltype(e);
+        constexpr int WV = 64 * Vec16<T>::N;   // the elements of a row one vector per lane covers
+        const int nv = (d + WV - 1) / WV;
+        if (nv <= 1) return f(LnMasked<T, 1>{});
+        if (nv <= 2) return f(LnMasked<T, 2>{});
+        if (nv <= 4) return f(LnMasked<T, 4>{});
+        if constexpr (WV == 256) return f(LnMasked<T, 8>{});   // (d <= 2048: four bf16 vectors per lane always suffice)
+        return ECGVIT_EINVAL;
+    });
+}
 // ---------------------------------------------------------------------------------------------------
 extern "C" {
 
@@ -830,44 +851,42 @@ int ecgvit_embed_bwd_ragged(const void *dX, void *dtok, float *dcls, float *dpos
     });
 }
 
-int ecgvit_layernorm_fwd(const void *x, const float *gamma, const float *beta, void *y, float *mean, float *rstd, int64_t rows,
-                         int d, float eps, int dtype, void *stream) {
-    if (rows <= 0 || d <= 0 || d % 8 != 0 || d > ECGVIT_ROW_MAX_D) return ECGVIT_EINVAL;
+// y8: the forward that also emits the 8-bit copy, an exact-lane kernel only (its callers have checked ln_fit(d)).  The forward's row bases are
+// 64-bit in either form, so the exact-lane kernels serve any row count
+static int ln_fwd_launch(const void *x, const float *gamma, const float *beta, void *y, float *mean, float *rstd, int64_t rows, int d, float eps,
+                         int dtype, void *stream, void *y8 = nullptr, const float *q8_scale = nullptr, float *q8_amax = nullptr) {
     const int grid = grid_for_rows(rows);
-    if (dtype != ECGVIT_F32 && dtype != ECGVIT_BF16) return ECGVIT_EINVAL;
-    if (dtype == ECGVIT_BF16 && ln_fit(d)) {
-#define LN_FIT(EE) case EE: hipLaunchKernelGGL((layernorm_fwd_fit_kernel<EE>), dim3(grid), dim3(256), 0, as_stream(stream), (const bf16_t *)x, gamma, beta, (bf16_t *)y, mean, rstd, rows, eps); break;
-        switch (d / 64) { LN_FIT(4) LN_FIT(8) LN_FIT(12) LN_FIT(16) LN_FIT(24) LN_FIT(32) default: return ECGVIT_EINVAL; }
-#undef LN_FIT
-        ECGVIT_CHECK_LAUNCH();
-        return ECGVIT_OK;
-    }
-    return dispatch_dtype(dtype, [&](auto e) -> int {
-        using T = decltype(e);
-        constexpr int WV = 64 * Vec16<T>::N;   // the elements of a row one vector per lane covers
-        const int nv = (d + WV - 1) / WV;
-#define LN_FWD(MV) hipLaunchKernelGGL((layernorm_fwd_kernel<T, MV>), dim3(grid), dim3(256), 0, as_stream(stream), (const T *)x, gamma, beta, (T *)y, mean, rstd, rows, d, eps)
-        if (nv <= 1) LN_FWD(1); else if (nv <= 2) LN_FWD(2); else if (nv <= 4) LN_FWD(4);
-        else if constexpr (WV == 256) LN_FWD(8);   // (d <= 2048: four bf16 vectors per lane always suffice)
-#undef LN_FWD
+    return ln_dispatch(dtype, d, true, [&](auto form) -> int {
+        using Form = decltype(form);
+        using T = typename Form::T;
+        if constexpr (Form::EXACT) {
+            auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, as_stream(stream), (const T *)x, gamma, beta, (T *)y, mean, rstd, rows, eps, (uint8_t *)y8, q8_scale, q8_amax);
+            };
+            if (y8) launch(layernorm_fwd_fit_kernel<Form::E, true>); else launch(layernorm_fwd_fit_kernel<Form::E, false>);
+        } else {
+            if (y8) return ECGVIT_EINVAL;
+            hipLaunchKernelGGL((layernorm_fwd_kernel<T, Form::MAXV>), dim3(grid), dim3(256), 0, as_stream(stream), (const T *)x, gamma, beta, (T *)y, mean, rstd, rows, d, eps);
+        }
         ECGVIT_CHECK_LAUNCH();
         return ECGVIT_OK;
     });
+}
+
+int ecgvit_layernorm_fwd(const void *x, const float *gamma, const float *beta, void *y, float *mean, float *rstd, int64_t rows,
+                         int d, float eps, int dtype, void *stream) {
+    if (rows <= 0 || d <= 0 || d % 8 != 0 || d > ECGVIT_ROW_MAX_D) return ECGVIT_EINVAL;
+    return ln_fwd_launch(x, gamma, beta, y, mean, rstd, rows, d, eps, dtype, stream);
 }
 
 // bf16 LayerNorm forward that also writes the e4m3 copy of its output (d = 64 * {4, 8, 12, 16, 24, 32} only)
 int ecgvit_layernorm_fwd_q8(const void *x, const float *gamma, const float *beta, void *y, float *mean, float *rstd, int64_t rows, int d,
                             float eps, void *y8, const float *q8_scale, float *q8_amax, void *stream) {
     if (rows <= 0 || !ln_fit(d) || !y8 || !q8_scale || !q8_amax) return ECGVIT_EINVAL;
-    const int grid = grid_for_rows(rows);
-#define LN_FIT8(EE) case EE: hipLaunchKernelGGL((layernorm_fwd_fit_kernel<EE, true>), dim3(grid), dim3(256), 0, as_stream(stream), (const bf16_t *)x, gamma, beta, (bf16_t *)y, mean, rstd, rows, eps, (uint8_t *)y8, q8_scale, q8_amax); break;
-    switch (d / 64) { LN_FIT8(4) LN_FIT8(8) LN_FIT8(12) LN_FIT8(16) LN_FIT8(24) LN_FIT8(32) default: return ECGVIT_EINVAL; }
-#undef LN_FIT8
-    ECGVIT_CHECK_LAUNCH();
-    return ECGVIT_OK;
+    return ln_fwd_launch(x, gamma, beta, y, mean, rstd, rows, d, eps, ECGVIT_BF16, stream, y8, q8_scale, q8_amax);
 }
 
-static int ln_bwd_grid(int64_t rows) { return (int)std::min<int64_t>((rows + 3) / 4, 1024); }  // up to 4 resident blocks per CU (fit kernels); the MAXV kernels hold 3
+static int ln_bwd_grid(int64_t rows) { return (int)std::min<int64_t>((rows + 3) / 4, 1024); }  // up to 4 resident blocks per CU (the exact-lane kernels at E <= 12; the others hold fewer)
 
 int64_t ecgvit_layernorm_bwd_workspace(int64_t rows, int d) { return (int64_t)ln_bwd_grid(rows) * 3 * d * 4; }
 
@@ -887,33 +906,25 @@ static int ln_bwd_launch(const void *dy, const void *x, const float *gamma, cons
     uint32_t th;
     float ik;
     if (!dropout_site_params(dropout_p, dtype == ECGVIT_BF16, th, ik)) return ECGVIT_EINVAL;   // (bf16: p applied as round(256 p) / 256; below 1/512: rejected)
-    if (dtype == ECGVIT_BF16 && ln_fit(d) && (int64_t)rows * d < (1ll << 31)) {
-        const size_t ldsf = lds + (size_t)d * 4;   // + gamma
-#define LN_FIT(EE)                                                                                                                \
-    case EE:                                                                                                                      \
-        if (g8) hipLaunchKernelGGL((layernorm_bwd_fit_kernel<EE, true, true>), dim3(grid), dim3(256), ldsf, as_stream(stream), (const bf16_t *)dy, (const bf16_t *)x, gamma, mean, rstd, (const bf16_t *)dres, (bf16_t *)dx, (float *)partial, rows, (bf16_t *)dxm, seed, th, ik, (uint8_t *)g8, q8_scale, q8_amax); \
-        else if (extra) hipLaunchKernelGGL((layernorm_bwd_fit_kernel<EE, true>), dim3(grid), dim3(256), ldsf, as_stream(stream), (const bf16_t *)dy, (const bf16_t *)x, gamma, mean, rstd, (const bf16_t *)dres, (bf16_t *)dx, (float *)partial, rows, (bf16_t *)dxm, seed, th, ik, nullptr, nullptr, nullptr, mrp); \
-        else hipLaunchKernelGGL((layernorm_bwd_fit_kernel<EE, false>), dim3(grid), dim3(256), ldsf, as_stream(stream), (const bf16_t *)dy, (const bf16_t *)x, gamma, mean, rstd, (const bf16_t *)dres, (bf16_t *)dx, (float *)partial, rows, (bf16_t *)nullptr, seed, 0u, 1.f); \
-        break;
-        switch (d / 64) { LN_FIT(4) LN_FIT(8) LN_FIT(12) LN_FIT(16) LN_FIT(24) LN_FIT(32) default: return ECGVIT_EINVAL; }
-#undef LN_FIT
-        ECGVIT_CHECK_LAUNCH();
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3((np * d + 63) / 64), dim3(1024), 0, as_stream(stream), (const float *)partial, grid, np * d, dgamma, dbeta, d, extra ? dcolsum : nullptr);
-        ECGVIT_CHECK_LAUNCH();
-        return ECGVIT_OK;
-    }
-    const int rc = dispatch_dtype(dtype, [&](auto e) -> int {
-        using T = decltype(e);
-        constexpr int WV = 64 * Vec16<T>::N;   // the elements of a row one vector per lane covers
-        const int nv = (d + WV - 1) / WV;
-#define LN_BWD(MV)                                                                                                                \
-    do {                                                                                                                          \
-        if (extra) hipLaunchKernelGGL((layernorm_bwd_kernel<T, MV, true>), dim3(grid), dim3(256), lds, as_stream(stream), (const T *)dy, (const T *)x, gamma, mean, rstd, (const T *)dres, (T *)dx, (float *)partial, rows, d, (T *)dxm, seed, th, ik, mrp); \
-        else hipLaunchKernelGGL((layernorm_bwd_kernel<T, MV, false>), dim3(grid), dim3(256), lds, as_stream(stream), (const T *)dy, (const T *)x, gamma, mean, rstd, (const T *)dres, (T *)dx, (float *)partial, rows, d, (T *)nullptr, seed, 0u, 1.f, 1u); \
-    } while (0)
-        if (nv <= 1) LN_BWD(1); else if (nv <= 2) LN_BWD(2); else if (nv <= 4) LN_BWD(4);
-        else if constexpr (WV == 256) LN_BWD(8);   // (d <= 2048: four bf16 vectors per lane always suffice)
-#undef LN_BWD
+    // the exact-lane kernels' 32-bit element offsets need rows * d < 2^31; past it the generic kernels take over
+    const int rc = ln_dispatch(dtype, d, (int64_t)rows * d < (1ll << 31), [&](auto form) -> int {
+        using Form = decltype(form);
+        using T = typename Form::T;
+        if constexpr (Form::EXACT) {
+            auto launch = [&](auto kernel) {   // (+ gamma in LDS)
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds + (size_t)d * 4, as_stream(stream), (const T *)dy, (const T *)x, gamma, mean, rstd, (const T *)dres, (T *)dx, (float *)partial, rows, (T *)dxm, seed, th, ik, (uint8_t *)g8, q8_scale, q8_amax, mrp);
+            };
+            if (g8) launch(layernorm_bwd_fit_kernel<Form::E, true, true>);
+            else if (extra) launch(layernorm_bwd_fit_kernel<Form::E, true, false>);
+            else launch(layernorm_bwd_fit_kernel<Form::E, false, false>);
+        } else {
+            auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, as_stream(stream), (const T *)dy, (const T *)x, gamma, mean, rstd, (const T *)dres, (T *)dx, (float *)partial, rows, d, (T *)dxm, seed, th, ik, mrp);
+            };
+            if (g8) return ECGVIT_EINVAL;   // (g8 has passed ln_fit(d) and rows * d < 2^31 above: never reached)
+            if (extra) launch(layernorm_bwd_kernel<T, Form::MAXV, true>);
+            else launch(layernorm_bwd_kernel<T, Form::MAXV, false>);
+        }
         ECGVIT_CHECK_LAUNCH();
         return ECGVIT_OK;
     });

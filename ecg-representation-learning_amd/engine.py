@@ -841,12 +841,16 @@ class VitEngine:
         return sp
 
     # ---------------------------------------------------------------- small launch helpers
+    @staticmethod
+    def _ln_exact(d):
+        """d has the exact lane mapping of csrc/rowops.hip (ln_fit): the widths whose bf16 LayerNorm can also emit the 8-bit copies"""
+        return d % 256 == 0 and d // 64 in (4, 8, 12, 16, 24, 32)
+
     def _ln_fwd(self, x, g, b, y, mean, rstd, rows, q8_site=None, y8=None):
         """LayerNorm forward; q8_site (fp8_linear): also write the e4m3 copy of y into the operand scratch for the Linear that consumes
-        it (returns True), once that site has a scale and when the exact-fit kernel covers d"""
+        it (returns True), once that site has a scale and when the exact lane mapping covers d"""
         d = self.d
-        if (self.fp8 and q8_site is not None and q8_site in self._f8_seen and rows >= 2048 and d % 256 == 0
-                and d // 64 in (4, 8, 12, 16, 24, 32)):
+        if self.fp8 and q8_site is not None and q8_site in self._f8_seen and rows >= 2048 and self._ln_exact(d):
             # (y has 8-bit readers only when it has a persistent 8-bit copy for the weight gradient: see fp8_drop_dead_bf16)
             run.ecgvit_layernorm_fwd_q8(ptr(x), ptr(g), ptr(b), None if (y8 is not None and self._only8(rows)) else ptr(y), ptr(mean), ptr(rstd), rows, d, LN_EPS,
                                         ptr(y8 if y8 is not None else self.act['q8']),
@@ -863,9 +867,9 @@ class VitEngine:
     def _ln_bwd_fused(self, dy, x, g, mean, rstd, dres, dx, dg, db, rows, dxm, dcolsum, p, seed, q8_site=None):
         """LayerNorm backward that also emits, for the NEXT stage, the dropout-masked copy of dx and its column sums; q8_site
         (fp8_linear): also the e5m2 copy of that gradient into the operand scratch for the input-gradient product that consumes it
-        (returns True), once the site has a scale and when the exact-fit kernel covers d"""
+        (returns True), once the site has a scale and when the exact lane mapping covers d"""
         d = self.d
-        if (self.fp8 and q8_site is not None and q8_site in self._f8_seen and rows >= 2048 and d // 64 in (4, 8, 12, 16, 24, 32) and d % 64 == 0
+        if (self.fp8 and q8_site is not None and q8_site in self._f8_seen and rows >= 2048 and self._ln_exact(d)
                 and rows * d < 2 ** 31):
             run.ecgvit_layernorm_bwd_fused_q8(ptr(dy), ptr(x), ptr(g), ptr(mean), ptr(rstd), ptr(dres), ptr(dx), ptr(dg), ptr(db),
                                               ptr(self.act['ws']), rows, d, None if self._only8(rows) else ptr(dxm), ptr(dcolsum), p, seed, ptr(self.act['q8']),
