@@ -10,10 +10,7 @@
 #define RANK_WAVE_ROWS (RANK_TILE / 4)          // a wave's quarter of a tile
 #define RANK_STEPS (RANK_WAVE_ROWS / WAVE)      // 64-row steps of a wave
 #define RANK_NAN_KEY 0xFFFFFFFFu
-#define RANK_INDEX_MASK 0x3FFFFFFFu
-#define RANK_LABEL_BIT 0x40000000u
-#define RANK_LAST_BIT 0x80000000u
-static_assert(RANK_TILE % (4 * WAVE) == 0 && ECGVIT_RANK_MAX_ROWS == (1 << 30), "tile of whole wave steps; index beside two flag bits");
+static_assert(RANK_TILE % (4 * WAVE) == 0, "tile of whole wave steps");
 
 // ---- keys ------------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t rank_key(float p) {
@@ -170,8 +167,6 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_pack_kernel(const uint32_t 
     if (p == n - 1 && key != RANK_NAN_KEY) first_nan[c] = (int32_t)n;
 }
 
-static __host__ __device__ inline int64_t rank_pad4(int64_t R) { return (R + 3) & ~(int64_t)3; }
-
 // ---- replicates: multiplicities --------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t rank_mix(uint64_t z) {
     z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull; z ^= z >> 31;
@@ -198,42 +193,24 @@ __global__ __launch_bounds__(256) void rank_multiplicity_kernel(const int64_t *_
 }
 
 // ---- the weighted rank sum ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t wave_scan_u32(uint32_t v, int l) {
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const uint32_t u = __shfl_up(v, o, WAVE);
-        if (l >= o) v += u;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-
-// wave (blockIdx.x * 4 + w) of class blockIdx.y carries replicates [wave * GROUP, wave * GROUP + GROUP).  State per replicate, wave-uniform: the
-// running sums of the positives' and the negatives' weights (P, A = Cn) and their values at the last closed tie group (Pc, Ac): the open
-// group's weights are P - Pc and A - Ac.  A position that closes a group adds (P - P') * (A' + A), with P', A' the sums at the closing
-// position before it: sum over the group's positives of w * (Cn before the group + Cn at its end).
+// The walk skeleton is metrics_common.h's.  State per replicate, wave-uniform: the running sums of the positives' and the negatives' weights
+// (P, A = Cn) and their values at the last closed tie group (Pc, Ac): the open group's weights are P - Pc and A - Ac.  A position that closes a
+// group adds (P - P') * (A' + A), with P', A' the sums at the closing position before it: sum over the group's positives of
+// w * (Cn before the group + Cn at its end).
 // A step is ECGVIT_RANK_WALK_ROWS positions, V = 4 consecutive ones per lane: a lane sums its own (first pass, relative to its first position,
 // remembering the sums at its last closing position), one exclusive wave scan per sum places the lane, the sums at the last closing position
-// before the lane come from the highest lower lane that holds one (a ballot and a shuffle) or from the carry, and a second pass over the
-// lane's positions adds the products.  A record's GROUP multiplicities are one 16-byte load from the record-major rows (a gather by record
-// index fetches a whole cache line whatever it uses of it: replicate-major rows moved sixteen times the bytes); the V loads of a step are in
-// flight together, and the four waves of a workgroup read neighbouring quarters of the same lines.
-__global__ __launch_bounds__(RANK_THREADS) void rank_walk_kernel(const uint32_t *__restrict__ packed, const int32_t *__restrict__ first_nan, int64_t n, int K,
+// before the lane come from the highest lower lane that holds one (a shuffle) or from the carry, and a second pass over the lane's positions adds
+// the products.  The V loads of a step are in flight together, and the four waves of a workgroup read neighbouring quarters of the same lines.
+// The placement is written out here and in prc_walk_kernel: as a shared function, in each of three forms, it cost a walk 1 to 10 % of its time
+// (profiles/r33_walk_skeleton.txt).
+__global__ __launch_bounds__(WALK_THREADS) void rank_walk_kernel(const uint32_t *__restrict__ packed, const int32_t *__restrict__ first_nan, int64_t n, int K,
                                                                  const uint32_t *__restrict__ mult, int64_t R, long long *__restrict__ out,
                                                                  long long *__restrict__ pairs) {
     constexpr int G = ECGVIT_RANK_GROUP, V = ECGVIT_RANK_WALK_ROWS / WAVE;
-    static_assert(G == 4, "a record's multiplicities of one wave are one u32x4");
-    const int64_t R4 = rank_pad4(R);
-    const int c = blockIdx.y, l = threadIdx.x & 63;
-    const int64_t r0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * G;
-    if (r0 >= R) return;   // wave-uniform; the kernel holds no barrier
-    const uint32_t *order = packed + (int64_t)c * n;
-    const int64_t nan0 = first_nan[c];
-    const uint64_t below = (1ull << l) - 1ull;
+    const WalkWave wv(packed, n, R);
+    if (wv.r0 >= R) return;   // wave-uniform; the kernel holds no barrier
+    const int l = wv.l;
+    const int64_t nan0 = first_nan[wv.c];
     uint32_t P[G], A[G], Pc[G], Ac[G], tp[G], tn[G];
     uint64_t acc[G];
 #pragma unroll
@@ -242,21 +219,13 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_walk_kernel(const uint32_t 
         const int64_t p0 = b + (int64_t)l * V;
         uint32_t word[V], w[V][G];
 #pragma unroll
-        for (int j = 0; j < V; ++j) word[j] = p0 + j < n ? order[p0 + j] : 0u;   // past the end: no label, no closing, weight 0
+        for (int j = 0; j < V; ++j) word[j] = p0 + j < n ? wv.order[p0 + j] : 0u;   // past the end: no label, no closing, weight 0
 #pragma unroll
-        for (int j = 0; j < V; ++j) {
-            const uint32_t i = word[j] & RANK_INDEX_MASK;
-            const bool in = p0 + j < n && i < n;
-            const u32x4 m = !in ? u32x4{0u, 0u, 0u, 0u} : mult ? *reinterpret_cast<const u32x4 *>(mult + (int64_t)i * R4 + r0) : u32x4{1u, 1u, 1u, 1u};
-#pragma unroll
-            for (int g = 0; g < G; ++g) w[j][g] = r0 + g < R ? m[g] : 0u;
-        }
+        for (int j = 0; j < V; ++j) walk_weights(wv, word[j], p0 + j < n, n, mult, R, w[j]);
         bool any = false;
 #pragma unroll
         for (int j = 0; j < V; ++j) any |= (word[j] & RANK_LAST_BIT) != 0;
-        const uint64_t closes = __ballot(any);
-        const uint64_t before = closes & below;
-        const int prev = before ? 63 - __clzll(before) : 0, top = closes ? 63 - __clzll(closes) : 0;
+        const WalkCloses k = walk_closes(any, wv.below);
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             uint32_t sp = 0, sa = 0, cp = 0, ca = 0;   // the lane's sums, and their values at its last closing position
@@ -270,10 +239,10 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_walk_kernel(const uint32_t 
                 sa += pos ? 0u : w[j][g];
                 if (word[j] & RANK_LAST_BIT) cp = sp, ca = sa;
             }
-            const uint32_t p_in = P[g] + wave_scan_u32(sp, l) - sp, a_in = A[g] + wave_scan_u32(sa, l) - sa;   // the sums before the lane
+            const uint32_t p_in = P[g] + walk_scan(sp, l) - sp, a_in = A[g] + walk_scan(sa, l) - sa;   // the sums before the lane
             const uint32_t p_cl = p_in + cp, a_cl = a_in + ca;
-            const uint32_t p_sh = __shfl(p_cl, prev, WAVE), a_sh = __shfl(a_cl, prev, WAVE);
-            uint32_t pc = before ? p_sh : Pc[g], ac = before ? a_sh : Ac[g], pr = p_in, ar = a_in;
+            const uint32_t p_sh = __shfl(p_cl, k.prev, WAVE), a_sh = __shfl(a_cl, k.prev, WAVE);
+            uint32_t pc = k.before ? p_sh : Pc[g], ac = k.before ? a_sh : Ac[g], pr = p_in, ar = a_in;
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 const bool pos = word[j] & RANK_LABEL_BIT;
@@ -284,25 +253,24 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_walk_kernel(const uint32_t 
                     pc = pr, ac = ar;
                 }
             }
-            const uint32_t p_top = __shfl(p_cl, top, WAVE), a_top = __shfl(a_cl, top, WAVE);
-            if (closes) Pc[g] = p_top, Ac[g] = a_top;
+            const uint32_t p_top = __shfl(p_cl, k.top, WAVE), a_top = __shfl(a_cl, k.top, WAVE);
+            if (k.closes) Pc[g] = p_top, Ac[g] = a_top;
             P[g] = __shfl(p_in + sp, 63, WAVE), A[g] = __shfl(a_in + sa, 63, WAVE);
         }
     }
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-        const uint64_t num2 = wave_sum_u64(acc[g]), wp = wave_sum_u64(tp[g]), wn = wave_sum_u64(tn[g]);
-        if (l == 0 && r0 + g < R) {
-            long long *o = out + ((r0 + g) * K + c) * 3;
+        const uint64_t num2 = walk_sum(acc[g]), wp = walk_sum<uint64_t>(tp[g]), wn = walk_sum<uint64_t>(tn[g]);
+        if (l == 0 && wv.r0 + g < R) {
+            long long *o = out + ((wv.r0 + g) * K + wv.c) * 3;
             o[0] = (long long)num2, o[1] = (long long)wp, o[2] = (long long)wn;
-            if (pairs) pairs[c] = (long long)num2;
+            if (pairs) pairs[wv.c] = (long long)num2;
         }
     }
 }
 
 // ---- entry points --------------------------------------------------------------------------------------------------------------------------------
 static inline int64_t rank_align(int64_t b) { return (b + 255) & ~(int64_t)255; }
-static inline bool rank_shape_ok(int64_t n, int K) { return n >= 1 && n <= ECGVIT_RANK_MAX_ROWS && K >= 1 && K <= ECGVIT_RANK_MAX_CLASSES; }
 static inline int64_t rank_tiles(int64_t n) { return (n + RANK_TILE - 1) / RANK_TILE; }
 
 extern "C" int64_t ecgvit_rank_workspace(int64_t n, int K, int64_t R) {
@@ -360,13 +328,9 @@ extern "C" int ecgvit_rank_multiplicities_seeded(uint64_t seed, int64_t first, i
 
 extern "C" int ecgvit_rank_walk(const uint32_t *packed, const int32_t *first_nan, int64_t n, int K, const uint32_t *mult, int64_t R, int64_t *out,
                                 int64_t *pairs, void *stream) {
-    if (!rank_shape_ok(n, K) || R < 1 || R > ECGVIT_RANK_MAX_REPLICATES || !packed || !first_nan || !out || (pairs && R != 1) ||
-        (reinterpret_cast<uintptr_t>(mult) & 15))
-        return ECGVIT_EINVAL;
-    const int64_t per = 4 * ECGVIT_RANK_GROUP;
-    rank_walk_kernel<<<dim3((unsigned)((R + per - 1) / per), K), RANK_THREADS, 0, as_stream(stream)>>>(packed, first_nan, n, K, mult, R,
-                                                                                                      reinterpret_cast<long long *>(out),
-                                                                                                      reinterpret_cast<long long *>(pairs));
+    if (!walk_args_ok(packed, first_nan, n, K, mult, R, out) || (pairs && R != 1)) return ECGVIT_EINVAL;
+    rank_walk_kernel<<<walk_grid(R, K), WALK_THREADS, 0, as_stream(stream)>>>(packed, first_nan, n, K, mult, R, reinterpret_cast<long long *>(out),
+                                                                              reinterpret_cast<long long *>(pairs));
     ECGVIT_CHECK_LAUNCH();
     return ECGVIT_OK;
 }

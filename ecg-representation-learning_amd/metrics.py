@@ -144,17 +144,26 @@ class HipEvaluator:
 def _add_bootstrap(d, predictions, prefix, bootstrap, scores, labels, from_logits, id2code, pr=False):
     """the interval keys of an evaluation that asked for them; with bootstrap=None nothing is added and nothing is launched.  pr: the keys of
     average precision and F-max as well, and then the AUROC intervals come from the same sort and the same draws"""
-    if pr is not False:
-        if pr is not True:
-            raise ValueError(f'pr must be True or False, got {pr!r}')
-        from . import pr_metrics
-        return pr_metrics.add_keys(d, predictions, prefix, bootstrap, scores, labels, from_logits, id2code)
-    if bootstrap is None:
+    if pr is not False and pr is not True:
+        raise ValueError(f'pr must be True or False, got {pr!r}')
+    if bootstrap is None and not pr:
         return
     from . import rank_metrics
-    res = rank_metrics.evaluator_bootstrap(bootstrap, scores, labels, from_logits, id2code)
-    d[f'{prefix}/macro_auc_ci'], d[f'{prefix}/per_class_auc_ci'] = rank_metrics.intervals(res)
-    predictions['bootstrap'] = res
+    routes = (rank_metrics.AUC,)
+    if pr:
+        from . import pr_metrics
+        routes += (pr_metrics.PR,)
+    if bootstrap is None:
+        point = pr_metrics.pr_counts(scores, labels, from_logits, id2code).result()
+    else:
+        results = rank_metrics._bootstrap(routes, scores, labels, from_logits=from_logits, id2code=id2code, **rank_metrics.bootstrap_keywords(bootstrap))
+        for route, res in zip(routes, results):
+            for metric in route.metrics:
+                d[f'{prefix}/macro_{metric}_ci'], d[f'{prefix}/per_class_{metric}_ci'] = rank_metrics.intervals(res, metric)
+            predictions[route.key] = res
+        point = results[-1].point   # the PR route's, under pr
+    if pr:
+        d.update({f'{prefix}/{k}': v for k, v in point.items()})
 
 
 class HipEncoder:

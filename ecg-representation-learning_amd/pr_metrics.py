@@ -15,14 +15,12 @@ A class is valid in a replicate when it holds a positive and a negative of non-z
 replicate's macro average.  The PTB-XL benchmark's sample-centric Fmax (per-record precision and recall over a threshold grid) is another quantity
 and is not built here.
 """
-import warnings
-
 import numpy as np
 import torch
 
 from . import pr_abi, rank_abi, rank_metrics
 from .hip import ptr, stream
-from .rank_metrics import RankedScores, BootstrapResult
+from .rank_metrics import RankedScores, BootstrapResult, ReplicateResult, Route
 
 __all__ = ['PrCounts', 'PrBootstrapResult', 'pr_walk', 'pr_counts', 'bootstrap_pr', 'paired_diff_ci']
 
@@ -45,7 +43,7 @@ def pr_walk(ranked, mult=None, replicates=1):
         if replicates != 1:
             raise ValueError(f'replicates must be 1 without mult (unit weights are one replicate), got {replicates}')
     else:
-        r4 = (replicates + 3) // 4 * 4
+        r4 = rank_metrics.pad4(replicates)
         if not isinstance(mult, torch.Tensor) or mult.dtype != torch.int32:
             raise ValueError('mult must be an int32 tensor of record-major multiplicities')
         if not mult.is_contiguous() or mult.numel() < ranked.n * r4:
@@ -66,17 +64,11 @@ def _walk(ranked, mult, R, out):
 def _values(sixes):
     """(..., K, 6) int64 -> valid (..., K) bool, AP and F-max (..., K) f64 with NaN where invalid"""
     ap_q, wp, wn, tp, fp = (sixes[..., i].astype(np.float64) for i in range(5))
-    valid = (sixes[..., 1] > 0) & (sixes[..., 2] > 0)
+    valid = rank_metrics.valid_classes(sixes)
     with np.errstate(divide='ignore', invalid='ignore'):
         ap = np.where(valid, ap_q / (_Q * wp), np.nan)
         fmax = np.where(valid, 2.0 * tp / (tp + fp + wp), np.nan)
     return valid, ap, fmax
-
-
-def _macro(valid, per):
-    cnt = valid.sum(axis=-1)
-    with np.errstate(divide='ignore', invalid='ignore'):
-        return np.where(cnt > 0, np.where(valid, per, 0.0).sum(axis=-1) / cnt, np.nan)
 
 
 class PrCounts:
@@ -92,7 +84,7 @@ class PrCounts:
         all score NaN has F-max 0 and threshold +inf (predict nothing)."""
         r, K = self.ranked, self.ranked.K
         pos = self.sixes[0, :, 5]
-        rec = (r.packed.gather(1, pos.clamp(min=0)[:, None])[:, 0] & 0x3FFFFFFF).long()
+        rec = r.records(r.packed.gather(1, pos.clamp(min=0)[:, None])[:, 0])
         thr = r.scores[rec, torch.arange(K, device=rec.device)].cpu().numpy()
         six = self.sixes.cpu().numpy()[0]
         valid, ap, fmax = _values(six)
@@ -116,17 +108,16 @@ def pr_counts(scores, labels, from_logits=False, id2code=None) -> PrCounts:
     return _counts(rank_metrics.rank_scores(scores, labels, from_logits), id2code)
 
 
-class PrBootstrapResult:
+class PrBootstrapResult(ReplicateResult):
     """`point`: the `pr_counts` dict of the whole set.  `sixes`: (R, K, 6) int64 as the device left them.  `per_class_ap`, `per_class_fmax` (R, K)
     f64, NaN where the replicate holds one label value only; `macro_ap`, `macro_fmax` (R,) the means over the replicate's valid classes (NaN:
     none); `n_valid` (K,) replicates in which the class is valid.  `n`, `n_boot`, `seed`, `source`: the draws' record, as on `BootstrapResult`."""
 
     def __init__(self, point, sixes, id2code=None):
-        self.point, self.sixes, self.id2code = point, sixes, id2code
-        valid, self.per_class_ap, self.per_class_fmax = _values(sixes)
-        self.macro_ap, self.macro_fmax = _macro(valid, self.per_class_ap), _macro(valid, self.per_class_fmax)
-        self.n_valid = valid.sum(axis=0)
-        self.n = self.n_boot = self.seed = self.source = None
+        super().__init__(point, sixes, id2code)
+        self.sixes = sixes
+        _, self.per_class_ap, self.per_class_fmax = _values(sixes)
+        self.macro_ap, self.macro_fmax = self._macro(self.per_class_ap), self._macro(self.per_class_fmax)
 
     @staticmethod
     def _metric(metric):
@@ -136,44 +127,20 @@ class PrBootstrapResult:
 
     def ci(self, metric='ap', alpha=0.05):
         """(lo, hi) of the macro value: the alpha / 2 and 1 - alpha / 2 percentiles of the replicates that have a valid class"""
-        m, q = getattr(self, 'macro_' + self._metric(metric)), BootstrapResult._alpha(alpha)
-        with warnings.catch_warnings():
-            warnings.simplefilter('ignore', RuntimeWarning)
-            lo, hi = np.nanpercentile(m, q)
-        return float(lo), float(hi)
+        return self._ci(self._metric(metric), alpha)
 
     def class_ci(self, metric='ap', alpha=0.05):
         """(K, 2) per-class (lo, hi) over the replicates in which the class is valid; NaN for a class that never is"""
-        m, q = getattr(self, 'per_class_' + self._metric(metric)), BootstrapResult._alpha(alpha)
-        with warnings.catch_warnings():
-            warnings.simplefilter('ignore', RuntimeWarning)
-            return np.nanpercentile(m, q, axis=0).T.copy()
+        return self._class_ci(self._metric(metric), alpha)
 
 
-def _bootstrap(scores, labels, n_boot, seed, indices, from_logits, id2code, workspace_bytes, auc):
-    """one sort and one multiplicity fill per chunk for the PR walk and, with `auc`, the AUROC walk beside it -> (BootstrapResult or None, PrBootstrapResult)"""
-    n, K, R, chunk, indices = rank_metrics._plan(scores, labels, n_boot, seed, indices, workspace_bytes)
-    if n >= pr_abi.MAX_WEIGHT:
-        raise ValueError(f'scores: n = {n}, the weights of a replicate must sum to less than {pr_abi.MAX_WEIGHT}')
-    ranked = rank_metrics.rank_scores(scores, labels, from_logits)
-    point = _counts(ranked, id2code)
-    sixes = torch.empty(R, K, pr_abi.SLOTS, dtype=torch.int64, device=scores.device)
-    walks = [lambda mult, rows, r0: _walk(ranked, mult, rows, sixes[r0:r0 + rows])]
-    if auc:
-        auc_point = rank_metrics._counts(ranked, id2code)
-        triples = torch.empty(R, K, 3, dtype=torch.int64, device=scores.device)
-        walks.append(lambda mult, rows, r0: ranked._walk(mult, rows, triples[r0:r0 + rows]))
-    rank_metrics._replicates(ranked, R, chunk, seed, indices, walks)
-    res = rank_metrics._stamp(PrBootstrapResult(point.result(), sixes.cpu().numpy(), id2code), n, R, chunk, seed, indices)
-    if not auc:
-        return None, res
-    return rank_metrics._stamp(BootstrapResult(auc_point.result(), triples.cpu().numpy(), id2code), n, R, chunk, seed, indices), res
+PR = Route(_counts, _walk, pr_abi.SLOTS, PrBootstrapResult, METRICS, 'bootstrap_pr', pr_abi.MAX_WEIGHT)
 
 
 def bootstrap_pr(scores, labels, n_boot=1000, seed=0, indices=None, from_logits=False, id2code=None, workspace_bytes=None) -> PrBootstrapResult:
     """The point estimate and `n_boot` bootstrap replicates of per-class and macro average precision and F-max.  Every argument is
     `bootstrap_auc`'s, and so are the draws: under one seed (or the same indices) replicate b here and replicate b there are the same resample."""
-    return _bootstrap(scores, labels, n_boot, seed, indices, from_logits, id2code, workspace_bytes, False)[1]
+    return rank_metrics._bootstrap((PR,), scores, labels, n_boot, seed, indices, from_logits, id2code, workspace_bytes)[0]
 
 
 def paired_diff_ci(a, b, metric, alpha=0.05):
@@ -191,36 +158,5 @@ def paired_diff_ci(a, b, metric, alpha=0.05):
     for field in ('n', 'n_boot', 'source'):
         if getattr(a, field) != getattr(b, field):
             raise ValueError(f'b was not resampled as a: {field} is {getattr(b, field)!r} against {getattr(a, field)!r}')
-    q = BootstrapResult._alpha(alpha)
-    diff = getattr(a, 'macro_' + metric) - getattr(b, 'macro_' + metric)
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore', RuntimeWarning)
-        lo, hi = np.nanpercentile(diff, q)
+    lo, hi = ReplicateResult.percentiles(getattr(a, 'macro_' + metric) - getattr(b, 'macro_' + metric), alpha)
     return float(lo), float(hi)
-
-
-# ---- the evaluators' keys ---------------------------------------------------------------------------------------------------------------------
-def _intervals(res, metric, alpha=0.05):
-    per = res.point[f'per_class_{metric}']
-    if per is None:
-        return res.ci(metric, alpha), None
-    cc = res.class_ci(metric, alpha)
-    cols = [k for k in range(cc.shape[0]) if (res.id2code[k] if res.id2code is not None else k) in per]
-    return res.ci(metric, alpha), {key: (float(cc[k, 0]), float(cc[k, 1])) for key, k in zip(per, cols)}
-
-
-def add_keys(d, predictions, prefix, bootstrap, scores, labels, from_logits, id2code):
-    """`pr=True` of `HipEvaluator.evaluate` / `HipKnnProbe`: the point keys, and with `bootstrap` the interval keys of AUROC, AP and F-max from one
-    sort and one set of draws; `bootstrap` and `bootstrap_pr` under `predictions`"""
-    if bootstrap is None:
-        point = pr_counts(scores, labels, from_logits, id2code).result()
-    else:
-        kw = rank_metrics.bootstrap_keywords(bootstrap)
-        auc, res = _bootstrap(scores, labels, kw.get('n_boot', 1000), kw.get('seed', 0), kw.get('indices'), from_logits, id2code,
-                              kw.get('workspace_bytes'), True)
-        d[f'{prefix}/macro_auc_ci'], d[f'{prefix}/per_class_auc_ci'] = rank_metrics.intervals(auc)
-        for metric in METRICS:
-            d[f'{prefix}/macro_{metric}_ci'], d[f'{prefix}/per_class_{metric}_ci'] = _intervals(res, metric)
-        predictions['bootstrap'], predictions['bootstrap_pr'] = auc, res
-        point = res.point
-    d.update({f'{prefix}/{k}': v for k, v in point.items()})

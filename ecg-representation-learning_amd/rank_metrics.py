@@ -11,6 +11,7 @@ integers; the divisions and the percentiles are host f64, as in `DeviceCounts.re
 A replicate holding only one label value of a class is invalid for that class (the reference's own `msk_2_class` rule, util/train.py:29, applied
 to the resample): NaN in `per_class_auc`, left out of the replicate's macro average.  No class is redrawn and nothing is stratified.
 """
+import collections
 import warnings
 
 import numpy as np
@@ -59,6 +60,11 @@ def _pitch(t):
     return t.stride(0) if t.shape[0] > 1 else t.shape[1]
 
 
+def pad4(replicates):
+    """the pitch of the record-major multiplicities: a wave of the walks takes four replicates of a record in one load"""
+    return (replicates + 3) // 4 * 4
+
+
 class RankedScores:
     """The sorted order of every class column: `packed` (K, n) int32 words (record index | label bit << 30 | last-of-tie-group bit << 31) and
     `first_nan` (K,) int32, on the device."""
@@ -70,7 +76,12 @@ class RankedScores:
 
     def order(self, c):
         """record indices of class c under (key ascending, record index ascending): (n,) int64 on the device"""
-        return (self.packed[c] & 0x3FFFFFFF).long()
+        return self.records(self.packed[c])
+
+    @staticmethod
+    def records(words):
+        """packed words -> the record indices they hold (int64)"""
+        return (words & 0x3FFFFFFF).long()
 
     def _walk(self, mult, R, out, pairs=None):
         rank_abi.run.ecgvit_rank_walk(ptr(self.packed), ptr(self.first_nan), self.n, self.K, ptr(mult), R, ptr(out), ptr(pairs), stream())
@@ -131,22 +142,32 @@ def multiplicities(seed, replicate, n):
 
 
 # ---- replicates ---------------------------------------------------------------------------------------------------------------------------
-class BootstrapResult:
-    """`point`: the `get_accuracy` dict of the whole set.  `triples`: (R, K, 3) int64 (num2, wp, wn) as the device left them.
-    `per_class_auc` (R, K) f64, NaN where the replicate holds one label value only; `macro_auc` (R,) the mean over the replicate's valid classes
-    (NaN: none); `n_valid` (K,) replicates in which the class is valid."""
+def valid_classes(counts):
+    """(..., K, slots) int64 of either walk, slots 1 and 2 holding wp and wn -> (..., K) bool: the class holds a positive and a negative of
+    non-zero weight"""
+    return (counts[..., 1] > 0) & (counts[..., 2] > 0)
 
-    def __init__(self, point, triples, id2code=None):
-        self.point, self.triples, self.id2code = point, triples, id2code
-        self.n = self.n_boot = self.seed = self.source = None   # the draws' record: `bootstrap_auc` fills it
-        num2, wp, wn = (triples[..., i].astype(np.float64) for i in range(3))
-        valid = (triples[..., 1] > 0) & (triples[..., 2] > 0)
+
+class ReplicateResult:
+    """What the results of every walk share.  `point`: the dict of the whole set.  `n_valid` (K,) replicates in which the class is valid.
+    `n`, `n_boot`, `seed` (None under indices), `source` (`draw_source`) and `chunk`: the draws' record, which the bootstrap driver fills.
+    A subclass sets `per_class_<metric>` (R, K) f64, NaN where invalid, and `macro_<metric>` (R,) = `_macro` of it, for each of its metrics."""
+
+    def __init__(self, point, counts, id2code=None):
+        self.point, self.id2code = point, id2code
+        self.n = self.n_boot = self.seed = self.source = self.chunk = None
+        self.valid = valid_classes(counts)
+        self.n_valid = self.valid.sum(axis=0)
+
+    def _macro(self, per):
+        """the mean over each replicate's valid classes (NaN: none)"""
+        cnt = self.valid.sum(axis=-1)
         with np.errstate(divide='ignore', invalid='ignore'):
-            self.per_class_auc = np.where(valid, num2 / (2.0 * wp * wn), np.nan)
-        cnt = valid.sum(axis=1)
-        with np.errstate(divide='ignore', invalid='ignore'):
-            self.macro_auc = np.where(cnt > 0, np.where(valid, self.per_class_auc, 0.0).sum(axis=1) / cnt, np.nan)
-        self.n_valid = valid.sum(axis=0)
+            return np.where(cnt > 0, np.where(self.valid, per, 0.0).sum(axis=-1) / cnt, np.nan)
+
+    def _drawn(self, n, R, chunk, seed, indices):
+        self.chunk, self.n, self.n_boot, self.seed, self.source = chunk, n, R, (seed if indices is None else None), draw_source(seed, indices)
+        return self
 
     @staticmethod
     def _alpha(alpha):
@@ -154,20 +175,52 @@ class BootstrapResult:
             raise ValueError(f'alpha must be in (0, 1), got {alpha!r}')
         return [100.0 * alpha / 2, 100.0 * (1 - alpha / 2)]
 
-    def ci(self, alpha=0.05):
-        """(lo, hi) of the macro AUROC: the alpha / 2 and 1 - alpha / 2 percentiles of the replicates that have a valid class"""
-        q = self._alpha(alpha)
+    @staticmethod
+    def percentiles(values, alpha, axis=None):
+        """the alpha / 2 and 1 - alpha / 2 percentiles of the values that are not NaN (NaN, without a warning, where none is)"""
+        q = ReplicateResult._alpha(alpha)
         with warnings.catch_warnings():
             warnings.simplefilter('ignore', RuntimeWarning)
-            lo, hi = np.nanpercentile(self.macro_auc, q)
+            return np.nanpercentile(values, q, axis=axis)
+
+    def _ci(self, metric, alpha):
+        lo, hi = self.percentiles(getattr(self, 'macro_' + metric), alpha)
         return float(lo), float(hi)
+
+    def _class_ci(self, metric, alpha):
+        return self.percentiles(getattr(self, 'per_class_' + metric), alpha, axis=0).T.copy()
+
+
+class BootstrapResult(ReplicateResult):
+    """`point`: the `get_accuracy` dict of the whole set.  `triples`: (R, K, 3) int64 (num2, wp, wn) as the device left them.
+    `per_class_auc` (R, K) f64, NaN where the replicate holds one label value only; `macro_auc` (R,) the mean over the replicate's valid classes
+    (NaN: none); `n_valid` (K,) replicates in which the class is valid."""
+
+    def __init__(self, point, triples, id2code=None):
+        super().__init__(point, triples, id2code)
+        self.triples = triples
+        num2, wp, wn = (triples[..., i].astype(np.float64) for i in range(3))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            self.per_class_auc = np.where(self.valid, num2 / (2.0 * wp * wn), np.nan)
+        self.macro_auc = self._macro(self.per_class_auc)
+
+    def ci(self, alpha=0.05):
+        """(lo, hi) of the macro AUROC: the alpha / 2 and 1 - alpha / 2 percentiles of the replicates that have a valid class"""
+        return self._ci('auc', alpha)
 
     def class_ci(self, alpha=0.05):
         """(K, 2) per-class (lo, hi) over the replicates in which the class is valid; NaN for a class that never is"""
-        q = self._alpha(alpha)
-        with warnings.catch_warnings():
-            warnings.simplefilter('ignore', RuntimeWarning)
-            return np.nanpercentile(self.per_class_auc, q, axis=0).T.copy()
+        return self._class_ci('auc', alpha)
+
+
+def intervals(res, metric='auc', alpha=0.05):
+    """(macro (lo, hi), {class key of the point estimate: (lo, hi)} or None) of one metric of a result, for the evaluators' dicts"""
+    per = res.point[f'per_class_{metric}']
+    if per is None:
+        return res._ci(metric, alpha), None
+    cc = res._class_ci(metric, alpha)
+    cols = [k for k in range(cc.shape[0]) if (res.id2code[k] if res.id2code is not None else k) in per]
+    return res._ci(metric, alpha), {key: (float(cc[k, 0]), float(cc[k, 1])) for key, k in zip(per, cols)}
 
 
 def _check_indices(indices, n):
@@ -204,21 +257,6 @@ def _plan(scores, labels, n_boot, seed, indices, workspace_bytes):
     return n, K, R, chunk, indices
 
 
-def _replicates(ranked, R, chunk, seed, indices, walks):
-    """the chunk loop of every bootstrap: one multiplicity fill per chunk of replicates, then each of `walks` as walk(mult, rows, r0)"""
-    n, dev = ranked.n, ranked.packed.device
-    mult = torch.empty(n, (chunk + 3) // 4 * 4, dtype=torch.int32, device=dev)   # record-major; a shorter last chunk uses its head
-    for r0 in range(0, R, chunk):
-        rows = min(chunk, R - r0)
-        if indices is None:
-            rank_abi.run.ecgvit_rank_multiplicities_seeded(seed, r0, rows, n, ptr(mult), stream())
-        else:
-            idx = indices[r0:r0 + rows].to(device=dev, dtype=torch.int64).contiguous()
-            rank_abi.run.ecgvit_rank_multiplicities(ptr(idx), n, rows, n, ptr(mult), stream())
-        for walk in walks:
-            walk(mult, rows, r0)
-
-
 def draw_source(seed, indices):
     """what the replicates of a result were drawn from: ('seed', seed), or ('indices', R, a wrapping int64 checksum of the draws) -- two results
     compare replicate by replicate only when these are equal"""
@@ -228,9 +266,34 @@ def draw_source(seed, indices):
     return ('indices', int(indices.shape[0]), int((flat * torch.arange(1, flat.numel() + 1, dtype=torch.int64, device=flat.device)).sum()))
 
 
-def _stamp(res, n, R, chunk, seed, indices):
-    res.chunk, res.n, res.n_boot, res.seed, res.source = chunk, n, R, (seed if indices is None else None), draw_source(seed, indices)
-    return res
+# A quantity on the sorted order, as the bootstrap driver and the evaluators' key assembly take it.  counts(ranked, id2code): the handle of the
+# point estimate; walk(ranked, mult, R, out): one launch over R replicates; slots: integers per (replicate, class); result: the ReplicateResult;
+# metrics: its `macro_` / `per_class_` names; key: the result's name under an evaluator's predictions; max_rows: n at which the route refuses.
+Route = collections.namedtuple('Route', 'counts walk slots result metrics key max_rows')
+AUC = Route(_counts, RankedScores._walk, 3, BootstrapResult, ('auc',), 'bootstrap', None)
+
+
+def _bootstrap(routes, scores, labels, n_boot=1000, seed=0, indices=None, from_logits=False, id2code=None, workspace_bytes=None):
+    """The bootstrap of every route of `routes` on one sort and one set of draws: a point estimate per route, then one multiplicity fill per chunk
+    of replicates and each route's walk over it -> [the route's result]"""
+    n, K, R, chunk, indices = _plan(scores, labels, n_boot, seed, indices, workspace_bytes)
+    for route in routes:
+        if route.max_rows is not None and n >= route.max_rows:
+            raise ValueError(f'scores: n = {n}, the weights of a replicate must sum to less than {route.max_rows}')
+    ranked, dev = rank_scores(scores, labels, from_logits), scores.device
+    points = [route.counts(ranked, id2code) for route in routes]
+    outs = [torch.empty(R, K, route.slots, dtype=torch.int64, device=dev) for route in routes]
+    mult = torch.empty(n, pad4(chunk), dtype=torch.int32, device=dev)   # record-major; a shorter last chunk uses its head
+    for r0 in range(0, R, chunk):
+        rows = min(chunk, R - r0)
+        if indices is None:
+            rank_abi.run.ecgvit_rank_multiplicities_seeded(seed, r0, rows, n, ptr(mult), stream())
+        else:
+            idx = indices[r0:r0 + rows].to(device=dev, dtype=torch.int64).contiguous()
+            rank_abi.run.ecgvit_rank_multiplicities(ptr(idx), n, rows, n, ptr(mult), stream())
+        for route, out in zip(routes, outs):
+            route.walk(ranked, mult, rows, out[r0:r0 + rows])
+    return [route.result(point.result(), out.cpu().numpy(), id2code)._drawn(n, R, chunk, seed, indices) for route, point, out in zip(routes, points, outs)]
 
 
 def bootstrap_auc(scores, labels, n_boot=1000, seed=0, indices=None, from_logits=False, id2code=None, workspace_bytes=None) -> BootstrapResult:
@@ -240,23 +303,7 @@ def bootstrap_auc(scores, labels, n_boot=1000, seed=0, indices=None, from_logits
     `get_accuracy(preds[indices[b]], labels[indices[b]])`.  A seed other than 0 beside indices is refused.
     workspace_bytes: bound on the multiplicity rows held at once (default 256 MiB); the replicates run in chunks of that many rows.
     The result records `n`, `n_boot`, `seed` (None under indices) and `source` (`draw_source`), which `pr_metrics.paired_diff_ci` compares."""
-    n, K, R, chunk, indices = _plan(scores, labels, n_boot, seed, indices, workspace_bytes)
-    ranked = rank_scores(scores, labels, from_logits)
-    point = _counts(ranked, id2code)
-    triples = torch.empty(R, K, 3, dtype=torch.int64, device=scores.device)
-    _replicates(ranked, R, chunk, seed, indices, [lambda mult, rows, r0: ranked._walk(mult, rows, triples[r0:r0 + rows])])
-    return _stamp(BootstrapResult(point.result(), triples.cpu().numpy(), id2code), n, R, chunk, seed, indices)
-
-
-def intervals(res, alpha=0.05):
-    """(macro (lo, hi), {class key of the point estimate: (lo, hi)} or None) for the evaluators' dicts"""
-    per = res.point['per_class_auc']
-    if per is None:
-        return res.ci(alpha), None
-    cc = res.class_ci(alpha)
-    keys = list(per)
-    cols = [k for k in range(cc.shape[0]) if (res.id2code[k] if res.id2code is not None else k) in per]
-    return res.ci(alpha), {key: (float(cc[k, 0]), float(cc[k, 1])) for key, k in zip(keys, cols)}
+    return _bootstrap((AUC,), scores, labels, n_boot, seed, indices, from_logits, id2code, workspace_bytes)[0]
 
 
 def bootstrap_keywords(bootstrap):
@@ -268,8 +315,3 @@ def bootstrap_keywords(bootstrap):
     if bad:
         raise ValueError(f'bootstrap: unknown keywords {sorted(bad)}')
     return kw
-
-
-def evaluator_bootstrap(bootstrap, scores, labels, from_logits, id2code):
-    """the evaluators' `bootstrap` -> BootstrapResult"""
-    return bootstrap_auc(scores, labels, from_logits=from_logits, id2code=id2code, **bootstrap_keywords(bootstrap))

@@ -104,7 +104,7 @@ def test_result_classes_and_paired_differences():
     assert np.array_equal(res.per_class_fmax, [[0.8, np.nan], [1.0, np.nan]], equal_nan=True)
     assert res.macro_ap.tolist() == [0.75, 1.0] and res.macro_fmax.tolist() == [0.8, 1.0] and res.n_valid.tolist() == [2, 0]
     assert res.ci('ap', 0.5) == (0.8125, 0.9375) and res.class_ci('fmax').shape == (2, 2) and np.isnan(res.class_ci('ap')[1]).all()
-    assert PM._intervals(res, 'ap', 0.5) == ((0.8125, 0.9375), {0: (0.8125, 0.9375)})
+    assert RM.intervals(res, 'ap', 0.5) == ((0.8125, 0.9375), {0: (0.8125, 0.9375)})
     with pytest.raises(ValueError, match='metric must be one of'):
         res.ci('auc')
     with pytest.raises(ValueError, match='alpha'):

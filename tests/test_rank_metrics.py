@@ -184,13 +184,14 @@ def test_refusals_name_their_argument():
             E.bootstrap_auc(s, y, workspace_bytes=ws)
     with pytest.raises(ValueError, match='scores must be a device tensor'):             # in-range host indices pass; the device is asked for last
         E.bootstrap_auc(s, y, indices=idx)
+    from ecg_representation_learning_amd.metrics import _add_bootstrap
     for bootstrap in (True, 1.5, 'yes'):
         with pytest.raises(ValueError, match='bootstrap must be'):
-            RM.evaluator_bootstrap(bootstrap, s, y, False, None)
+            _add_bootstrap({}, {}, 'eval', bootstrap, s, y, False, None)
     with pytest.raises(ValueError, match='unknown keywords'):
-        RM.evaluator_bootstrap(dict(n_boot=3, from_logits=True), s, y, False, None)
+        _add_bootstrap({}, {}, 'eval', dict(n_boot=3, from_logits=True), s, y, False, None)
     with pytest.raises(ValueError, match='n_boot'):
-        RM.evaluator_bootstrap(0, s, y, False, None)
+        _add_bootstrap({}, {}, 'eval', 0, s, y, False, None)
 
 
 def test_exports_and_signatures():
